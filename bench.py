@@ -2,9 +2,17 @@
 
     python bench.py [--gpus N --steps K --warmup W] [--orbitals 256] [--dtype f64|c128|mixed] [--config 2|3|4]
                     [--layout auto|replicated|rows|rows_rccl|sharded|inplace|rccl] [--gather] [--fresh-c auto|on|off]
-                    [--workload transform|spin_expand|antisymmetrize] [--no-cpu-baseline]
+                    [--workload transform|spin_expand|antisymmetrize] [--full [--no-cpu-baseline] [--no-probes]]
+                    [--dump-outputs DIR]
 
 Metric (BASELINE.json): "4-index u transform TFLOP/s (fp64) at L orbitals".
+
+A plain run sets up, warms up, times the K steps, writes the last step's result
+if `--dump-outputs DIR` is given, and prints the line.  `--full` adds what the
+headline figure does not need: the parity property at N = 1 (at N > 1 it picks
+the leg that makes `value`, so it always runs there), the dispatch record of one
+extra step and the roofline figures built on it, and at N = 1 the machine probes
+and the CPU baseline.
 A step is ONE full transform out = Ct Ct u C C of a synthetic RandomBasisSet-
 shaped tensor resident in HBM (BASELINE.json configs[2]: real fp64, l=256,
 u = 34.4 GB, C = real orthogonal).  The work figure is the algorithmic
@@ -50,7 +58,7 @@ the result, or a sharded layout with its all-to-all), and `config.layout` names 
 configs[4] (l=512 complex128, slabs generated per rank, rows layout, a new C(t) per step;
 below 8 GPUs the largest l whose two slabs fit).
 
-Prints ONE JSON line on rank 0; exits non-zero if the parity property fails.
+Prints ONE JSON line on rank 0; exits non-zero if the parity property is checked and fails.
 """
 
 import argparse
@@ -102,6 +110,12 @@ def parse(argv=None):
                     help="a new coefficient matrix every step, C_tilde derived inside the call (the per-step caller "
                          "system.py:222-225); auto = on for complex128 (time evolution), off for fp64 (one change_basis)")
     ap.add_argument("--staging-rows", type=int, default=1, help="rows per all-to-all of the in-place exchange")
+    ap.add_argument("--full", action="store_true",
+                    help="also check and measure what the headline figure does not need: the parity property (N = 1), "
+                         "the dispatch record and roofline of one extra step, the machine probes and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float64; a fixed, "
+                         "seeded sample of a tensor larger than the budget; one GPU only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-l", type=int, default=192, help="largest size of the CPU-baseline sample")
     ap.add_argument("--cpu-full", choices=["auto", "on", "off"], default="auto", nargs="?", const="on",
@@ -276,7 +290,7 @@ def compose_legs(args, n, legs, records, provisional=False, pending=()):
         if d:
             ent.update({"value": d["value"], "ms_per_step": d["ms_per_step"], "ms_per_step_median": d.get("ms_per_step_median"),
                         "layout": d["config"]["layout"], "parity": d["parity"], "collective": d.get("collective", {}).get("in_value"),
-                        "kernel": d["roofline"]["kernel"], "n_ranks_seen": d.get("n_ranks_seen")})
+                        "kernel": d.get("roofline", {}).get("kernel"), "n_ranks_seen": d.get("n_ranks_seen")})
             ok = rec["status"] == "ok" and d["parity"]["ok"]
             if "with_all_gather" in d:
                 ent["with_all_gather"] = d["with_all_gather"]
@@ -582,6 +596,29 @@ def timed_steps(torch, step, steps, warmup, barrier):
     return elapsed, evs[0].elapsed_time(evs[-1]) * 1e-3, per_step, res
 
 
+DUMP_BYTES = 32 << 20        # --dump-outputs: at most this much in all (float64 data)
+DUMP_SEED = 20241
+
+
+def dump_outputs(torch, outdir, arrays):
+    """`--dump-outputs DIR`: each tensor of `arrays` as DIR/<name>.npy in float64 (complex as a trailing (re, im) axis).
+    A tensor larger than its share of DUMP_BYTES is written as a fixed sample: its elements at sorted flat indices drawn
+    from a generator seeded by DUMP_SEED, so the same shape samples the same elements in every run."""
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    share = DUMP_BYTES // len(arrays)
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        per = 16 if t.is_complex() else 8
+        if flat.numel() * per > share:
+            idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), share // per, dtype=np.int64))
+            flat = flat.index_select(0, torch.from_numpy(idx).to(flat.device))
+        a = flat.cpu().numpy()
+        a = np.ascontiguousarray(a.view(np.float64).reshape(-1, 2) if np.iscomplexobj(a) else a, dtype=np.float64)
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 def median(xs):
     s = sorted(xs)
     n = len(s)
@@ -652,35 +689,42 @@ def bandwidth_workload(args, torch, dist, kernels, sharded, device, rank, world,
         torch.cuda.synchronize()
 
     elapsed, dev_elapsed, per_step, _ = timed_steps(torch, step, args.steps, args.warmup, barrier)
-    kernels.dispatch_log = []
-    step(0)
-    kernel, _, dispatch = dominant_kernel(kernels.dispatch_log)
-    kernels.dispatch_log = None
+    if args.dump_outputs:
+        # the caller receives the last rows of the streamed spin tensor in the reused buffer, or the whole result
+        last = buf[: 2 * (pc - (pc - 1) // rows * rows)] if args.workload == "spin_expand" else out
+        dump_outputs(torch, args.dump_outputs, {"out_last_rows" if args.workload == "spin_expand" else "out": last})
+    if args.full:
+        kernels.dispatch_log = []
+        step(0)
+        kernel, _, dispatch = dominant_kernel(kernels.dispatch_log)
+        kernels.dispatch_log = None
     if use_dist:
         t = torch.tensor([elapsed, dev_elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, dev_elapsed = t[0].item(), t[1].item()
-    # parity (value-exact): the first local p row against the definition written with torch ops
-    row = u[:1]
-    if args.workload == "spin_expand":
-        got = kernels.spin_expand_two_body(u, antisymmetrize=True, out_dtype=torch.complex128, p_lo=0, p_hi=1)
-        eye = torch.eye(2, dtype=torch.float64, device=device)
-        ref = torch.einsum("pqrs,ac,bd->paqbrcsd", row, eye, eye).reshape(2, 2 * l, 2 * l, 2 * l)
-        ref = (ref - ref.transpose(2, 3)).to(torch.complex128)
-    else:
-        got = kernels.antisymmetrize(row)
-        ref = row - row.transpose(2, 3)
-    ok = torch.tensor([1.0 if torch.equal(got, ref) else 0.0], dtype=torch.float64, device=device)
-    if use_dist:
-        dist.all_reduce(ok, op=dist.ReduceOp.MIN)
-    exact = bool(ok.item() == 1.0)
+    exact = True
+    if args.full:
+        # parity (value-exact): the first local p row against the definition written with torch ops
+        row = u[:1]
+        if args.workload == "spin_expand":
+            got = kernels.spin_expand_two_body(u, antisymmetrize=True, out_dtype=torch.complex128, p_lo=0, p_hi=1)
+            eye = torch.eye(2, dtype=torch.float64, device=device)
+            ref = torch.einsum("pqrs,ac,bd->paqbrcsd", row, eye, eye).reshape(2, 2 * l, 2 * l, 2 * l)
+            ref = (ref - ref.transpose(2, 3)).to(torch.complex128)
+        else:
+            got = kernels.antisymmetrize(row)
+            ref = row - row.transpose(2, 3)
+        ok = torch.tensor([1.0 if torch.equal(got, ref) else 0.0], dtype=torch.float64, device=device)
+        if use_dist:
+            dist.all_reduce(ok, op=dist.ReduceOp.MIN)
+        exact = bool(ok.item() == 1.0)
     if rank == 0:
         gbps = step_bytes * args.steps / elapsed / 1e9
         per_launch = dev_elapsed / (args.steps * launches)
         achieved = step_bytes / world / launches / per_launch / 1e9
         traffic = traffic_source = None
         prof = os.path.join(ROOT, "profiles", "traffic_latest.json")
-        if world == 1 and os.path.exists(prof):          # HBM bytes per (full-size) launch from this round's PMC passes
+        if args.full and world == 1 and os.path.exists(prof):   # HBM bytes per (full-size) launch from this round's PMC passes
             try:
                 with open(prof) as f:
                     for ent in json.load(f):
@@ -700,12 +744,13 @@ def bandwidth_workload(args, torch, dist, kernels, sharded, device, rank, world,
                                    f"through a reused slab buffer" if args.workload == "spin_expand"
                                    else f"anti-symmetrisation of real fp64 u l={l}, p-slab per GPU",
                        "l": l, "bytes_per_step": step_bytes},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_source,
-                         "kernel": kernel, "dispatch": dispatch,
-                         "bytes_per_launch": step_bytes / world / launches, "avg_launch_ms": per_launch * 1e3},
-            "parity": {"value_exact_vs_definition": exact},
         }
+        if args.full:
+            line["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                                "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_source,
+                                "kernel": kernel, "dispatch": dispatch,
+                                "bytes_per_launch": step_bytes / world / launches, "avg_launch_ms": per_launch * 1e3}
+            line["parity"] = {"value_exact_vs_definition": exact}
         print(json.dumps(line), flush=True)
     if use_dist:
         dist.barrier()
@@ -892,6 +937,10 @@ def run_rank(args):
 
     elapsed, dev_elapsed, per_step, res = timed_steps(torch, step, args.steps, args.warmup, barrier)
     last_i = args.warmup + args.steps - 1
+    if args.dump_outputs:
+        dump_outputs(torch, args.dump_outputs, {"out": res})
+    # at N > 1 the parity of every leg decides which one makes `value`: checked there whether or not --full
+    check = args.full or world > 1
 
     # second leg at N > 1: the same steps followed by the north star's all-gather of the result
     gather_leg = None
@@ -902,11 +951,14 @@ def run_rank(args):
         gather_leg = (e2, k2, ps2)
         full_buf[0] = None
 
-    # which kernels ran (one extra untimed step with the dispatch record on)
-    kernels.dispatch_log = []
-    res = local_step(last_i)
-    kernel, launches_per_step, dispatch = dominant_kernel(kernels.dispatch_log)
-    kernels.dispatch_log = None
+    if args.full:
+        # which kernels ran (one extra untimed step with the dispatch record on)
+        kernels.dispatch_log = []
+        res = local_step(last_i)
+        kernel, launches_per_step, dispatch = dominant_kernel(kernels.dispatch_log)
+        kernels.dispatch_log = None
+    elif check:
+        res = local_step(last_i)      # this rank's result of the last step (the timed one may be gathered, the gather leg reuses the buffers)
     torch.cuda.synchronize()
 
     if use_dist:
@@ -920,21 +972,24 @@ def run_rank(args):
         dist.all_reduce(ps, op=dist.ReduceOp.MAX)
         per_step = ps.tolist()
 
-    # parity property at full size: partial sums of both sides on this rank, summed over the ranks
-    C_last = Cs[last_i % n_c]
-    Ct_last = Cts[last_i % n_c]
-    rows = res[p_lo:p_hi] if layout_kind == "single" else res
-    if layout_kind in ("rows", "rows_rccl"):
-        lhs, rhs = identity_parts_rows(torch, u, rows, C_last, Ct_last, a_lo, p_lo)
-    else:
-        lhs, rhs = identity_parts(torch, u, rows, C_last, Ct_last, p_lo, b_lo=b_lo)
-    pair = torch.stack([lhs, rhs]).to(torch.complex128)
-    if use_dist:
-        pr = torch.view_as_real(pair).contiguous()
-        dist.all_reduce(pr)
-        pair = torch.view_as_complex(pr)
-    rel = (abs(pair[0] - pair[1]) / abs(pair[1])).item()
-    parity_ok = rel <= PARITY_BOUND
+    rel, parity_ok = None, True
+    if check:
+        # parity property at full size: partial sums of both sides on this rank, summed over the ranks
+        C_last = Cs[last_i % n_c]
+        Ct_last = Cts[last_i % n_c]
+        rows = res[p_lo:p_hi] if layout_kind == "single" else res
+        if layout_kind in ("rows", "rows_rccl"):
+            lhs, rhs = identity_parts_rows(torch, u, rows, C_last, Ct_last, a_lo, p_lo)
+        else:
+            lhs, rhs = identity_parts(torch, u, rows, C_last, Ct_last, p_lo, b_lo=b_lo)
+        pair = torch.stack([lhs, rhs]).to(torch.complex128)
+        if use_dist:
+            pr = torch.view_as_real(pair).contiguous()
+            dist.all_reduce(pr)
+            pair = torch.view_as_complex(pr)
+        rel = (abs(pair[0] - pair[1]) / abs(pair[1])).item()
+        parity_ok = rel <= PARITY_BOUND
+        del rows
 
     if rank != 0:
         if use_dist:
@@ -944,31 +999,33 @@ def run_rank(args):
 
     ms_per_step = elapsed / args.steps * 1e3
     value = flops * args.steps / elapsed / 1e12
-    # dominant kernel = the MFMA GEMM family: `launches_per_step` launches carry all the
-    # flops of a step; everything else on the stream is microseconds.
-    per_launch_s = dev_elapsed / (args.steps * launches_per_step)
-    achieved = (flops / world / launches_per_step) / per_launch_s / 1e12
-    roofline = {
-        "bound": "mfma", "achieved": achieved, "peak": MFMA_F64_PEAK_TFLOPS, "unit": "TFLOP/s",
-        "frac": achieved / MFMA_F64_PEAK_TFLOPS, "traffic": None,
-        "kernel": kernel, "dispatch": dispatch, "launches_per_step": launches_per_step,
-        "flops_per_launch": flops / world / launches_per_step,
-        "avg_launch_ms": per_launch_s * 1e3,
-    }
-    prof = os.path.join(ROOT, "profiles", "traffic_latest.json")
-    if world == 1 and os.path.exists(prof):
-        try:
-            with open(prof) as f:
-                tr = json.load(f)
-            for ent in (tr if isinstance(tr, list) else [tr]):       # one entry per (size, dtype, kernel) profiled
-                if ent.get("l") == l and ent.get("dtype") == args.dtype and ent.get("kernel", kernel) == kernel:
-                    roofline["traffic"] = ent["hbm_bytes_per_launch"]
-                    roofline["traffic_source"] = ent.get("source")
-        except Exception:
-            pass
+    roofline = None
+    if args.full:
+        # dominant kernel = the MFMA GEMM family: `launches_per_step` launches carry all the
+        # flops of a step; everything else on the stream is microseconds.
+        per_launch_s = dev_elapsed / (args.steps * launches_per_step)
+        achieved = (flops / world / launches_per_step) / per_launch_s / 1e12
+        roofline = {
+            "bound": "mfma", "achieved": achieved, "peak": MFMA_F64_PEAK_TFLOPS, "unit": "TFLOP/s",
+            "frac": achieved / MFMA_F64_PEAK_TFLOPS, "traffic": None,
+            "kernel": kernel, "dispatch": dispatch, "launches_per_step": launches_per_step,
+            "flops_per_launch": flops / world / launches_per_step,
+            "avg_launch_ms": per_launch_s * 1e3,
+        }
+        prof = os.path.join(ROOT, "profiles", "traffic_latest.json")
+        if world == 1 and os.path.exists(prof):
+            try:
+                with open(prof) as f:
+                    tr = json.load(f)
+                for ent in (tr if isinstance(tr, list) else [tr]):       # one entry per (size, dtype, kernel) profiled
+                    if ent.get("l") == l and ent.get("dtype") == args.dtype and ent.get("kernel", kernel) == kernel:
+                        roofline["traffic"] = ent["hbm_bytes_per_launch"]
+                        roofline["traffic_source"] = ent.get("source")
+            except Exception:
+                pass
 
     probes = {}
-    if not args.no_probes and world == 1:   # single-GPU ceilings; at N > 1 the other ranks would only wait
+    if args.full and not args.no_probes and world == 1:   # single-GPU ceilings; at N > 1 the other ranks would only wait
         st = torch.cuda.current_stream().cuda_stream
         blocks, iters = 256 * 8, 4000
         sink = torch.zeros(1 + 2 * blocks, dtype=torch.int64, device=device)
@@ -1012,10 +1069,11 @@ def run_rank(args):
             "l": l, "flops_per_step": flops, "layout": layout,
             "frac_of_mfma_peak": value / (MFMA_F64_PEAK_TFLOPS * world),
         },
-        "roofline": roofline,
-        "parity": {"randomised_identity_rel_diff": rel, "bound": PARITY_BOUND, "ok": parity_ok},
-        "probes": probes,
     }
+    if check:
+        line["parity"] = {"randomised_identity_rel_diff": rel, "bound": PARITY_BOUND, "ok": parity_ok}
+    if args.full:
+        line.update(roofline=roofline, probes=probes)
     if world > 1:
         line["collective"] = {"in_value": "all-gather of the result" if with_gather else (
             "none" if layout_kind == "replicated" else (
@@ -1026,8 +1084,8 @@ def run_rank(args):
             line["with_all_gather"] = {"value": flops * k2 / e2 / 1e12, "ms_per_step": e2 / k2 * 1e3, "steps": k2,
                                        "note": "same steps followed by the all-gather that replicates the "
                                                "p-sharded result on every GPU (north star's single collective)"}
-    if not args.no_cpu_baseline and world == 1:   # reported at N = 1 only (rank 0 would stall the others)
-        del res, rows
+    if args.full and not args.no_cpu_baseline and world == 1:   # reported at N = 1 only (rank 0 would stall the others)
+        del res
         full = args.cpu_full == "on" or (args.cpu_full == "auto" and args.dtype == "f64" and 4.2 * 8 * l**4 < 0.9 * host_mem_available()
                                          and host_mem_available() >= 110e9 and l >= 200)
         line["cpu_baseline"] = cpu_baseline(args.cpu_l, full_l=l if full else None)
@@ -1058,6 +1116,8 @@ def main():
     args = apply_config(parse())
     under_launcher = "WORLD_SIZE" in os.environ
     n = int(os.environ["WORLD_SIZE"]) if under_launcher else args.gpus
+    if args.dump_outputs and n > 1:
+        raise SystemExit("--dump-outputs: one GPU only (each rank holds a part of the result)")
     if (n > 1 and args.layout == "auto" and args.workload == "transform" and "QS_BENCH_LEG" not in os.environ
             and os.environ.get("QS_BENCH_SELF_LAUNCHED") != "1"):
         return run_legs(args, n, under_launcher)

@@ -47,10 +47,23 @@ qs = _import_reference()
 BasisSet = qs.BasisSet
 
 
+PART_BYTES = 768 << 10      # a committed file stays under 1 MiB: a larger field goes in slabs of its leading index
+
+
 def save(name, **arrays):
+    """name.npz, and <name>.<field>.<i>.npz for each slab of a field larger than PART_BYTES (tests/conftest.py joins them)."""
+    whole = {k: a for k, a in arrays.items() if np.asarray(a).nbytes <= PART_BYTES}
     path = os.path.join(HERE, name + ".npz")
-    np.savez_compressed(path, **arrays)
+    np.savez_compressed(path, **whole)
     print(f"{name}: {os.path.getsize(path) / 1e3:.1f} kB")
+    for k, a in arrays.items():
+        if k in whole:
+            continue
+        rows = max(1, PART_BYTES // (a.nbytes // a.shape[0]))
+        for i, r0 in enumerate(range(0, a.shape[0], rows)):
+            part = os.path.join(HERE, f"{name}.{k}.{i}.npz")
+            np.savez_compressed(part, **{k: a[r0:r0 + rows]})
+            print(f"{name}.{k}.{i}: {os.path.getsize(part) / 1e3:.1f} kB")
 
 
 def crand(rng, *shape):

@@ -65,3 +65,29 @@ def test_a_leg_without_parity_is_never_the_value():
            "rows": {"status": "ok", "wall_s": 1.0, "line": bad}}
     rc, line = compose(["replicated", "rows"], rec, False, [])
     assert rc == 0 and line["value"] == 180.0 and line["legs"]["rows"]["parity"]["ok"] is False
+
+
+def test_dump_outputs_is_float64_within_its_budget_and_samples_the_same_elements(tmp_path, monkeypatch):
+    # --dump-outputs (host logic, CPU tensors): a small tensor is written whole, a large one as the same seeded sample in
+    # every run; complex values as (re, im) pairs of float64
+    import numpy as np
+    import torch
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 1 << 12)
+    small = torch.arange(6, dtype=torch.float64).reshape(2, 3)
+    re = torch.arange(1000, dtype=torch.float64)
+    big = torch.complex(re, -re)
+    for run in ("a", "b"):
+        bench.dump_outputs(torch, str(tmp_path / run), {"small": small, "big": big})
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float64 and s.tolist() == [0.0, 1.0, 2.0, 3.0, 4.0, 5.0]
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float64 and a.ndim == 2 and a.shape[1] == 2 and 0 < a.nbytes <= (1 << 12) // 2
+    assert np.array_equal(a, b) and np.array_equal(a[:, 1], -a[:, 0])
+    assert np.all(np.diff(a[:, 0]) > 0)                  # sorted distinct elements of the tensor
+
+
+def test_plain_options_leave_the_extra_measurements_off():
+    args = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert args.full is False and args.dump_outputs is None and args.steps == 7 and args.warmup == 2
+    assert bench.parse(["--full", "--dump-outputs", "d"]).full is True

@@ -49,8 +49,10 @@ def run_demo(built, world, L, M, mode, chunk, coalesce, drop, stall_us, entry, d
     mock, exe = built
     # every stream of the process on a hardware queue of its own: with the runtime's default of four, streams share queues
     # and a delay kernel (or a stalled stream) holds back whatever was enqueued behind it on the same queue -- which would
-    # serialise exactly the races this transport exists to expose
-    env = dict(os.environ, QS_AMD_RCCL_LIB=mock, QS_MOCK_RCCL_DELAY_US=str(delay_us), GPU_MAX_HW_QUEUES="64")
+    # serialise exactly the races this transport exists to expose.  32 queues hold the world^2 transfer streams plus two
+    # streams per rank up to world = 4, the three-rank runs of the negative cases included; the five-rank positive case
+    # shares queues, which can only serialise, never break, a correct ordering
+    env = dict(os.environ, QS_AMD_RCCL_LIB=mock, QS_MOCK_RCCL_DELAY_US=str(delay_us), GPU_MAX_HW_QUEUES="32")
     cmd = [exe] + [str(x) for x in (world, L, M, mode, chunk, coalesce, drop, stall_us, entry)]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     return res.returncode, res.stdout + res.stderr

@@ -1,6 +1,7 @@
 """bench.py itself (the driver's measuring instrument), run as a child process at a small size:
 one JSON line on stdout with every field of the contract, for the transform and for the two
-bandwidth workloads."""
+bandwidth workloads (with --full: parity, roofline, probes and CPU baseline), and the plain run
+that only times the steps and writes what they computed (--dump-outputs)."""
 
 import json
 import os
@@ -17,12 +18,53 @@ CONTRACT = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 
 
 def run_bench(*args):
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", *args],
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", *args],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, res.stdout                        # exactly one JSON line
     return json.loads(lines[0])
+
+
+@pytest.mark.parametrize("dtype,l", [("f64", 24), ("c128", 40)])
+def test_plain_run_times_the_steps_and_dumps_what_the_last_one_computed(tmp_path, dtype, l):
+    # without --full: the timed steps and the line only; --dump-outputs holds the last step's result (whole at l = 24 fp64,
+    # the seeded sample at l = 40 complex128), which is the transform of the seeded inputs
+    import numpy as np
+    import torch
+
+    import bench
+    from oracle import qs_oracle as orc
+
+    out = tmp_path / "out"
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
+                          "--orbitals", str(l), "--dtype", dtype, "--dump-outputs", str(out)],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, res.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["unit"] == "TFLOP/s" and d["dtype"] == dtype and d["higher_is_better"]
+    flops = (8 if dtype == "f64" else 32) * l**5
+    assert abs(d["value"] - flops * 4 / (d["ms_per_step"] * 4e-3) / 1e12) < 1e-6 * d["value"]
+    assert not {"roofline", "parity", "probes", "cpu_baseline"} & set(d)
+    assert [p.name for p in out.iterdir()] == ["out.npy"]
+    got = np.load(out / "out.npy")
+    assert got.dtype == np.float64 and got.nbytes <= bench.DUMP_BYTES
+    dev = torch.device("cuda:0")
+    if dtype == "f64":
+        u, C, _ = bench.make_inputs(torch, l, torch.float64, dev)
+    else:        # a new C every step: the last one is that of step warmup + steps - 1
+        u = bench.make_inputs(torch, l, torch.complex128, dev)[0]
+        C = bench.make_unitary(torch, l, torch.complex128, dev, 99 + 4)
+    ref = orc.transform_two_body(u.cpu().numpy(), C.cpu().numpy()).reshape(-1)
+    if dtype == "f64":
+        assert got.shape == (l**4,)
+    else:
+        idx = np.unique(np.random.default_rng(bench.DUMP_SEED).integers(0, l**4, bench.DUMP_BYTES // 16, dtype=np.int64))
+        ref = np.stack([ref[idx].real, ref[idx].imag], axis=1)
+        assert got.shape == ref.shape and got.shape[0] < l**4
+    assert np.abs(got - ref).max() <= 1e-10 * np.abs(ref).max()
 
 
 def test_transform_line_has_the_contract_fields():
@@ -191,7 +233,7 @@ def test_rows_layouts_with_a_one_rank_group():
         env = dict(os.environ, QS_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=port,
                    RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-               "--orbitals", "64", "--layout", layout, "--no-cpu-baseline", "--no-probes", "--chunk-rows", "16"]
+               "--orbitals", "64", "--layout", layout, "--full", "--no-cpu-baseline", "--no-probes", "--chunk-rows", "16"]
         res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
         assert res.returncode == 0, res.stderr[-3000:]
         d = json.loads([ln for ln in res.stdout.splitlines() if ln.strip().startswith("{")][0])
@@ -222,7 +264,7 @@ def test_self_launch_bandwidth_workload_two_ranks():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--orbitals", "32", "--workload", "spin_expand"]
+           "--orbitals", "32", "--workload", "spin_expand", "--full"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
     d = json.loads([ln for ln in res.stdout.splitlines() if ln.strip()][0])
@@ -236,7 +278,7 @@ def test_rccl_layout_with_a_one_rank_group():
     env = dict(os.environ, QS_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29691",
                RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-           "--orbitals", "64", "--layout", "rccl", "--no-cpu-baseline", "--no-probes"]
+           "--orbitals", "64", "--layout", "rccl", "--full", "--no-cpu-baseline", "--no-probes"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
     d = json.loads([ln for ln in res.stdout.splitlines() if ln.strip().startswith("{")][0])
@@ -252,7 +294,7 @@ def test_failed_parity_exits_nonzero(monkeypatch):
     spec.loader.exec_module(bench)
     monkeypatch.setattr(bench, "PARITY_BOUND", 0.0)
     monkeypatch.setattr(sys, "argv", ["bench.py"])
-    args = bench.parse(["--orbitals", "32", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-probes"])
+    args = bench.parse(["--orbitals", "32", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--no-probes"])
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         monkeypatch.delenv(k, raising=False)
     assert bench.run_rank(args) == 3

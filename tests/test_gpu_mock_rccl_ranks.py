@@ -76,7 +76,7 @@ def test_bench_rccl_legs_with_two_ranks_over_the_stand_in(built):
         for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
             env.pop(k, None)
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-               "--orbitals", "48", "--layout", layout, "--no-cpu-baseline", "--no-probes", "--chunk-rows", "6"]
+               "--orbitals", "48", "--layout", layout, "--full", "--no-cpu-baseline", "--no-probes", "--chunk-rows", "6"]
         res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
         assert res.returncode == 0, res.stdout[-1000:] + res.stderr[-3000:]
         line = json.loads([ln for ln in res.stdout.splitlines() if ln.strip().startswith("{")][0])

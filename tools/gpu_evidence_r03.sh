@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 line() {   # name, rocprof?, bench args...
   local name=$1 prof=$2; shift 2
   echo "== $name: bench.py $@"
-  timeout -k 10 900 python bench.py "$@" > $OUT/$name.json 2> $OUT/$name.err || { tail -5 $OUT/$name.err; return 1; }
+  timeout -k 10 900 python bench.py --full "$@" > $OUT/$name.json 2> $OUT/$name.err || { tail -5 $OUT/$name.err; return 1; }
   cut -c1-300 $OUT/$name.json
   [ "$prof" = "1" ] || return 0
   (cd /tmp && timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$name -- \

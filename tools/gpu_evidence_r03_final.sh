@@ -11,7 +11,7 @@ export TMPDIR=/tmp
 line() {   # name, bench args...
   local name=$1; shift 1
   echo "== $name: bench.py $@"
-  timeout -k 10 600 python bench.py "$@" > $OUT/$name.json 2> $OUT/$name.err || { tail -5 $OUT/$name.err; return 1; }
+  timeout -k 10 600 python bench.py --full "$@" > $OUT/$name.json 2> $OUT/$name.err || { tail -5 $OUT/$name.err; return 1; }
   cut -c1-260 $OUT/$name.json
   (cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$name -- \
       python3 $ROOTDIR/bench.py "$@" --no-cpu-baseline --no-probes > $OUT/${name}_under_rocprof.json 2> $OUT/${name}_rocprof.err)

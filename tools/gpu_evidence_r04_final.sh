@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 ROOTDIR=$(pwd)
 bench_with_stats() {   # name, bench args...
   local name=$1; shift
-  timeout -k 10 400 python bench.py --no-cpu-baseline "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err || { echo "bench $name failed"; tail -3 $OUT/bench_$name.err; return 1; }
+  timeout -k 10 400 python bench.py --full --no-cpu-baseline "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err || { echo "bench $name failed"; tail -3 $OUT/bench_$name.err; return 1; }
   (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOTDIR/$OUT/prof_$name -- python3 $ROOTDIR/bench.py --no-cpu-baseline --no-probes "$@" > $ROOTDIR/$OUT/bench_${name}_under_rocprof.json 2> $ROOTDIR/$OUT/rocprof_$name.err)
   f=$(find $OUT/prof_$name -name "*kernel_stats*.csv" | head -1)
   [ -n "$f" ] && cp $f $OUT/kernel_stats_$name.csv
@@ -21,7 +21,7 @@ case $PART in
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { tail -20 $OUT/smoke.log; exit 1; }; tail -1 $OUT/smoke.log
   ;;
 2)
-  timeout -k 10 700 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err || { tail -5 $OUT/bench_default.err; exit 1; }
+  timeout -k 10 700 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err || { tail -5 $OUT/bench_default.err; exit 1; }
   python3 -c "import json; d=json.load(open('$OUT/bench_default.json')); print('default', d['value'], d['ms_per_step'], d['roofline']['frac'], d['cpu_baseline']['value'], d['cpu_baseline']['sample'][:120])"
   bench_with_stats l256_f64 --steps 10 --warmup 2
   bench_with_stats l256_c128 --dtype c128 --steps 4 --warmup 1

@@ -9,7 +9,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 timeout -k 10 600 python -m pytest tests/test_gpu_kernels.py tests/test_gpu_bench_script.py -x -q -m gpu > $OUT/pytest.log 2>&1 || { tail -20 $OUT/pytest.log; exit 1; }
 tail -2 $OUT/pytest.log
-timeout -k 10 300 python bench.py --orbitals 55 --steps 200 --warmup 20 > $OUT/bench_l55.json 2> $OUT/bench_l55.err || { tail $OUT/bench_l55.err; exit 1; }
+timeout -k 10 300 python bench.py --full --orbitals 55 --steps 200 --warmup 20 > $OUT/bench_l55.json 2> $OUT/bench_l55.err || { tail $OUT/bench_l55.err; exit 1; }
 cat $OUT/bench_l55.json | cut -c1-900
 cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 $ROOTDIR/bench.py --orbitals 55 --steps 200 --warmup 20 --no-cpu-baseline --no-probes > $OUT/bench_l55_under_rocprof.json 2> $OUT/rocprof.err
 cd $ROOTDIR
