@@ -11,7 +11,8 @@
 //   * global loads use the scalar-base form (SGPR buffer descriptor + one
 //     loop-invariant 32-bit lane offset); the bases advance on the scalar ALU;
 //   * LDS addresses are one VGPR + immediates (the loop is unrolled by two so
-//     the stage buffer is a compile-time constant);
+//     the stage buffer is a compile-time constant; the DMA form's A fragments
+//     take one VGPR per k-step and 16-row block, set before the loop);
 //   * no per-lane bounds checks.
 // Two forms (template parameter EDGE):
 //   * exact: every extent a whole multiple of the tile (l = 128, 256, 512, ...);
@@ -59,6 +60,13 @@
 #define QS_FAST_STORE(dst, v) (*(dst) = (v))
 #endif
 
+// Exact fp64 form (!CX && VEC && !EDGE): stages go HBM -> LDS directly (buffer_load_dwordx4 ... lds, no VGPR
+// destination, no ds_write) instead of through two staging register sets.  -DQS_FAST_DMA=0 builds the register-staged
+// form of round 4 (the A/B baseline).
+#ifndef QS_FAST_DMA
+#define QS_FAST_DMA 1
+#endif
+
 namespace qs {
 
 struct FastArgs {
@@ -102,7 +110,13 @@ void gemm_fast_kernel(const FastArgs g) {
 #else
     constexpr bool kSwizzleA = CX;
 #endif
-    constexpr int SA = kSwizzleA ? KT : KT + 2, SB = CX ? BN + 16 : BN;      // (B rows 8 mod 16 instead of 16 mod 32: measured, level)
+    // LDS-DMA staging (exact fp64 form): the destination of one wave-instruction is lane-linear (M0 + 16 x lane), so the
+    // A rows cannot be padded.  They are 16 doubles = 128 bytes, and the 16-byte slot s of row r holds k-pair
+    // s ^ ((r >> 1) & 7): the permutation is applied on the per-lane SOURCE address of the load and again on the fragment
+    // read.  A half wave of the fragment read (sixteen rows x one k-pair) then covers all 64 banks: the eight even rows
+    // fill bytes 0-127 of a bank row, the eight odd rows bytes 128-255.
+    constexpr bool kDma = QS_FAST_DMA && !CX && VEC && !EDGE;
+    constexpr int SA = (kSwizzleA || kDma) ? KT : KT + 2, SB = CX ? BN + 16 : BN;      // (B rows 8 mod 16 instead of 16 mod 32: measured, level)
     constexpr int EPI = (!CX && VEC) ? 2 : 1;           // tensor elements per global item
     constexpr int DPI = CX ? 1 : EPI;                   // doubles per item inside one LDS plane
     constexpr int IPR_A = KT / EPI;                     // items per A row of a stage
@@ -176,7 +190,10 @@ void gemm_fast_kernel(const FastArgs g) {
         for (int i = 0; i < NB; ++i) b_ptr[i] = uniform64(reinterpret_cast<uint64_t>(Bb + (size_t)(brow0 + i * RPS) * g.ldb * ESZ));
     };
     aim(f_v);
-    const unsigned voff_a = (unsigned)(tid / IPR_A) * (unsigned)g.lda * (unsigned)ESZ + (unsigned)(tid % IPR_A) * IB;
+    // (DMA form: the lane loads the k-pair whose swizzled slot is its lane-linear destination -- rows (tid / IPR_A) and
+    // (tid / IPR_A) + i RA agree in bits 1-3, so the permutation is loop-invariant)
+    const unsigned voff_a = (unsigned)(tid / IPR_A) * (unsigned)g.lda * (unsigned)ESZ +
+                            (unsigned)(kDma ? (tid % IPR_A) ^ (((tid / IPR_A) >> 1) & 7) : tid % IPR_A) * IB;
     const unsigned voff_b = (IPR_B < 64 ? (unsigned)(lane / IPR_B) * (unsigned)g.ldb * (unsigned)ESZ : 0u) +
                             (unsigned)(tid % IPR_B) * IB;
     const size_t a_step = KT * ESZ;
@@ -194,6 +211,26 @@ void gemm_fast_kernel(const FastArgs g) {
     // fp64: lane c of n-tile pair (2jp, 2jp+1) owns the ADJACENT columns 32jp + 2c, 32jp + 2c + 1,
     // so one 16-byte LDS read feeds two MFMA tiles and the epilogue stores 16 bytes per lane
     const double* rd_b = Bs + (lane >> 4) * SB + wn * 16 * TN + (CX ? 1 : 2) * (lane & 15);
+    // DMA form: k = 4 kk + (lane >> 4) sits in slot (2 kk + (lane >> 5)) ^ ((row >> 1) & 7) of its row, an XOR with kk --
+    // one offset per k-step of a stage (KS = 4) and, on top, per 16-row block i: the blocks are 2048 bytes apart, and
+    // reads of one base at those distances are fused into ds_read2st64_b64, which banks over 32 banks instead of 64
+    // (the even and odd rows of a half wave then collide: SQ_LDS_BANK_CONFLICT 1.1e9 per launch at l = 256).  An empty
+    // asm makes each offset opaque, so no two fragment reads share a base (16 VGPRs, set once).
+    unsigned rd_a_dma[KS][TM];
+    if constexpr (kDma) {
+#pragma unroll
+        for (int kk = 0; kk < KS; ++kk) {
+#pragma unroll
+            for (int i = 0; i < TM; ++i) {
+                rd_a_dma[kk][i] = (unsigned)((wm * 16 * TM + i * 16 + (lane & 15)) * SA +
+                                             2 * ((2 * kk + (lane >> 5)) ^ ((lane >> 1) & 7)) + ((lane >> 4) & 1));
+                asm volatile("" : "+v"(rd_a_dma[kk][i]));
+            }
+        }
+    }
+    // DMA destinations: the wave's first 16-byte item of each item step (lane-linear after it)
+    double* dst_a = As + wave * 64 * DPI;
+    double* dst_b = Bs + wave * SB;
 
     // two staging register sets: the data of global stage s waits in set s & 1, so a load has
     // two stages (not one) to arrive from HBM before it is written to LDS
@@ -211,6 +248,33 @@ void gemm_fast_kernel(const FastArgs g) {
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
             rb[set][i] = Item::load(b_ptr[i], EDGE ? bytes_left(g.b_end, b_ptr[i]) : 0xFFFFFFFFu, voff_b);
+            b_ptr[i] += b_step;
+        }
+        if (++f_k == nk) {
+            f_k = 0;
+            f_v += P;
+            f_valid = f_v < g.total;
+            if (f_valid) aim(f_v);
+        }
+    };
+
+    // DMA form: load the cursor's stage straight into LDS stage `buf` (one wave-instruction = 1 KB: eight A rows or one
+    // B row) and advance the cursor.  The LDS base goes to M0 on the scalar ALU.
+    static_assert(!kDma || (IPR_A == 8 && IPR_B == 64), "DMA staging: a wave-instruction is eight A rows or one B row");
+    constexpr int NDMA = NA + NB;                       // DMA wave-instructions per stage
+    auto fetch_dma = [&](auto buf_c) {
+        constexpr int buf = decltype(buf_c)::value;
+        typedef __attribute__((address_space(3))) void* lds_ptr;
+#pragma unroll
+        for (int i = 0; i < NA; ++i) {
+            const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(a_ptr[i]), (short)0, -1, 0x00020000);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr)(dst_a + buf * A_STAGE + i * RA * SA), 16, (int)voff_a, 0, 0, 0);
+            a_ptr[i] += a_step;
+        }
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+            const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(b_ptr[i]), (short)0, -1, 0x00020000);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr)(dst_b + buf * B_STAGE + i * RPS * SB), 16, (int)voff_b, 0, 0, 0);
             b_ptr[i] += b_step;
         }
         if (++f_k == nk) {
@@ -270,7 +334,10 @@ void gemm_fast_kernel(const FastArgs g) {
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
 #pragma unroll
-            for (int i = 0; i < TM; ++i) af[p][i] = as[p * BM * SA + i * 16 * SA + kk * 4];
+            for (int i = 0; i < TM; ++i) {
+                if constexpr (kDma) af[p][i] = As[rd_a_dma[kk][i] + buf * A_STAGE];
+                else af[p][i] = as[p * BM * SA + i * 16 * SA + kk * 4];
+            }
             if constexpr (CX) {
 #pragma unroll
                 for (int j = 0; j < TN; ++j) bf[p][j] = bs[p * KT * SB + kk * 4 * SB + j * 16];
@@ -385,16 +452,31 @@ void gemm_fast_kernel(const FastArgs g) {
     const unsigned my_tiles = (g.total - blockIdx.x + P - 1) / P;
     const int64_t stages = (int64_t)my_tiles * nk;
 
-    fetch(B0{});                       // global stage 0
-    stash(B0{});
-    __syncthreads();
     double a0[NP][TM], b0[NP][TN], a1[NP][TM], b1[NP][TN];
-    if (f_valid) fetch(B1{});          // stage 1
-    if (f_valid) fetch(B0{});          // stage 2
+    if constexpr (kDma) {
+        fetch_dma(B0{});               // global stage 0
+        if (f_valid) {
+            fetch_dma(B1{});           // stage 1
+            asm volatile("s_waitcnt vmcnt(%0)" ::"i"(NDMA) : "memory");
+        } else {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+    } else {
+        fetch(B0{});                   // global stage 0
+        stash(B0{});
+        __syncthreads();
+        if (f_valid) fetch(B1{});      // stage 1
+        if (f_valid) fetch(B0{});      // stage 2
+    }
     read_frags(B0{}, 0, a0, b0);
 
     unsigned c_v = blockIdx.x;   // virtual block being computed
     int c_k = 0;                 // its current k-stage
+    bool after_epi = false;      // DMA form: the previous stage ended with an epilogue
+    constexpr int EPI_ST = TM * 4 * (TN / 2);   // its stores per wave (VEC form)
+    static_assert(EPI_ST < 64, "the vmcnt field holds 0..63");
 
     // one global stage: k-steps 0 .. KS-2, [stash the next stage], barrier, [fetch the
     // stage after next], [first fragments of the next stage], k-step KS-1, and at a tile's
@@ -418,9 +500,23 @@ void gemm_fast_kernel(const FastArgs g) {
             else               { read_frags(cur_c, kk + 1, a0, b0); __builtin_amdgcn_sched_barrier(0); if (!EDGE || kk < ks_live) mfma_step(a1, b1, F_{}); }
             __builtin_amdgcn_sched_barrier(0);
         }
-        if (has_next) stash(NXT{});        // stage gs+1, loaded two stages ago
-        __syncthreads();
-        if (f_valid) fetch(NXT{});         // stage gs+3 into the set just written out
+        if constexpr (kDma) {
+            // Stage gs+1 has landed in LDS buffer NXT once its DMA, issued after the previous barrier, is done: the only
+            // vector-memory work issued since is the previous stage's epilogue (EPI_ST stores), which is not waited for.
+            // lgkmcnt(0): this wave's fragment reads of buffer `cur` are done before anyone's DMA overwrites it.  A raw
+            // s_barrier, because __syncthreads() would also wait for the DMA of the stage after.
+            if (after_epi) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"i"(EPI_ST) : "memory");
+            else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
+            after_epi = false;
+            if (f_valid) fetch_dma(cur_c);     // stage gs+2 into the buffer just read
+            __builtin_amdgcn_sched_barrier(0);
+        } else {
+            if (has_next) stash(NXT{});        // stage gs+1, loaded two stages ago
+            __syncthreads();
+            if (f_valid) fetch(NXT{});         // stage gs+3 into the set just written out
+        }
         if (has_next) read_frags(NXT{}, 0, a0, b0);
         __builtin_amdgcn_sched_barrier(0);
         if (!EDGE || KS - 1 < ks_live) mfma_step(a1, b1, F_{});
@@ -429,6 +525,7 @@ void gemm_fast_kernel(const FastArgs g) {
             epilogue(c_v);
             c_k = 0;
             c_v += P;
+            after_epi = true;
         }
     };
 
@@ -490,7 +587,8 @@ static int launch_fast(const double* A, const double* B, double* C, int64_t m, i
 #if defined(QS_FAST_CX_PAD)
     const size_t lds = sizeof(double) * 2 * NP * (BM * (KT + 2) + KT * (CX ? BN + 16 : BN));
 #else
-    const size_t lds = sizeof(double) * 2 * NP * (BM * (CX ? KT : KT + 2) + KT * (CX ? BN + 16 : BN));
+    constexpr bool DMA = QS_FAST_DMA && !CX && VEC && !EDGE;     // unpadded A rows (the kernel's kDma)
+    const size_t lds = sizeof(double) * 2 * NP * (BM * (CX || DMA ? KT : KT + 2) + KT * (CX ? BN + 16 : BN));
 #endif
     auto kern = gemm_fast_kernel<CX, TM, TN, VEC, EDGE>;
     static PerDeviceLds lds_opt_in;   // per instantiation and per device
