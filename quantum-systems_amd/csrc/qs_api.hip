@@ -151,6 +151,36 @@ static bool extents_ok(int64_t L, int64_t M) {
 
 static inline char* at(void* base, int64_t elems, size_t es) { return (char*)base + (size_t)elems * es; }
 
+// The two fused passes of a small-basis transform (qs_common.h: FusedPass), T2 (L, L, M, M) between them.
+// Slab pass, (d, c): item t = slab u[t] (L x L, contiguous), Out_t = C^T . u[t] . C = T2[t] (M x M); with `t2_transposed`
+// T2 is stored (r, s, a, b) instead (nitems = L^2 then).
+static FusedPass slab_pass(const void* u, void* T2, const void* C, int64_t nitems, int64_t L, int64_t M, bool t2_transposed) {
+    FusedPass p{};
+    p.in = (const double*)u; p.out = (double*)T2;
+    p.R = (const double*)C; p.r_sk = M; p.r_sj = 1;          // R = C (L x M)
+    p.Lm = (const double*)C; p.l_sp = 1; p.l_sa = M;         // Lm = C^T
+    p.in_item = L * L; p.in_row = L; p.in_col = 1;
+    if (t2_transposed) { p.out_item = 1; p.out_row = M * nitems; p.out_col = nitems; }
+    else { p.out_item = M * M; p.out_row = M; p.out_col = 1; }
+    p.L = (int)L; p.M = (int)M; p.nitems = (unsigned)nitems;     // (extents_ok: every count fits)
+    return p;
+}
+
+// Column pass, (b, a): item t = column (r, s) of T2, Out_t = Ct . T2[:, :, t] . Ct^T = out[:, :, t]; with `t2_transposed`
+// the items are T2's slabs.
+static FusedPass column_pass(const void* T2, void* out, const void* Ct, int64_t L, int64_t M, bool t2_transposed) {
+    const int64_t MM = M * M;
+    FusedPass p{};
+    p.in = (const double*)T2; p.out = (double*)out;
+    p.R = (const double*)Ct; p.r_sk = 1; p.r_sj = L;         // R = Ct^T (Ct: M x L)
+    p.Lm = (const double*)Ct; p.l_sp = L; p.l_sa = 1;        // Lm = Ct
+    if (t2_transposed) { p.in_item = L * L; p.in_row = L; p.in_col = 1; }
+    else { p.in_item = 1; p.in_row = L * MM; p.in_col = MM; }
+    p.out_item = 1; p.out_row = M * MM; p.out_col = MM;
+    p.L = (int)L; p.M = (int)M; p.nitems = (unsigned)MM;
+    return p;
+}
+
 // contractions d, c, b on `rows` leading-index rows.  `CT` is scratch for C^T: the c contraction of
 // the tiled path multiplies with it; the fused small-basis pass reads C itself and needs no transpose.
 static int contract_dcb(int in_dtype, int dtype, const void* u, const void* C, void* CT, const void* Ct,
@@ -160,7 +190,7 @@ static int contract_dcb(int in_dtype, int dtype, const void* u, const void* C, v
     //   T2[ab] = C^T . u[ab] . C   on the 4-wide matrix instruction, else on the 16-wide one
     int rc = 1;
     if (in_dtype == dtype && (g_tune.sandwich == 1 || g_tune.sandwich == 2 || g_tune.sandwich == 4 || g_tune.sandwich == 5))
-        rc = sandwich4_try(dtype, u, T2, C, M, 1, C, 1, M, rows * L, L, M, L * L, L, 1, M * M, M, 1, s);
+        rc = sandwich4_try(dtype, slab_pass(u, T2, C, rows * L, L, M, false), 0, s);
     if (rc == 1 && in_dtype == dtype) rc = slab_pair_try(dtype, u, C, T2, rows * L, L, M, s);
     if (rc == 1) {
         rc = transpose_small(dtype, C, CT, L, M, s);
@@ -221,7 +251,6 @@ int qs_tuning_set(const char* key, int64_t value) {
     if (!strcmp(key, "gemm_pick")) { g_tune.gemm_pick = (int)value; return QS_OK; }
     if (!strcmp(key, "small4")) { g_tune.small4 = (int)value; return QS_OK; }
     if (!strcmp(key, "quad4s")) { g_tune.quad4s = (int)value; return QS_OK; }
-    if (!strcmp(key, "pair4c_stream")) { g_tune.pair4c_stream = (int)value; return QS_OK; }
     if (!strcmp(key, "pair4c")) { g_tune.pair4c = (int)value; return QS_OK; }
     if (!strcmp(key, "sandwich")) { g_tune.sandwich = (int)value; return QS_OK; }
     if (!strcmp(key, "gemm_strip")) { g_tune.gemm_strip = (int)value; return QS_OK; }
@@ -285,6 +314,106 @@ static bool quad4s_wins(int64_t L, int64_t M) {
     return L >= 65 && M >= 65 && L <= 96 && M <= 96 && !(L == 96 && M == 96);
 }
 
+// The fused small-basis routes of the transform, tried in this order: small4, quad4s, pair4c, pair4m, sandwich.  T2
+// (L, L, M, M) goes to WA; CT and WB are scratch of the unfused first pass of the sandwich route.  QS_OK / error after
+// launching, 1 = no fused route applies (the four tiled products follow).
+static int transform_two_body_fused(int in_dtype, int dtype, const void* u, const void* C, const void* Ct, void* out,
+                                    void* CT, void* WA, void* WB, int64_t L, int64_t M, hipStream_t s) {
+    const FusedPass slab = slab_pass(u, WA, C, L * L, L, M, false), column = column_pass(WA, out, Ct, L, M, false);
+    // one family's two passes, pass_try(pass, tensor_is_b): 1 = it refused either pass, and the next candidate runs (after
+    // a first pass that ran, it writes T2 again from the start)
+    auto both = [&](auto pass_try) { const int rc = pass_try(slab, 0); return rc == QS_OK ? pass_try(column, 1) : rc; };
+    int rc = 1;
+
+    // up to 32 orbitals, both dtypes: two launches of the LDS-staged kernel (what is left below ~33 orbitals is launches, not
+    // work: the 16-wide kernels need three to five); T2 (L, L, M, M) in WA
+    // (same-box sweep with the launches of a transform captured in one graph, profiles/r03_small4.txt: 1.8-2.9x up to 15
+    // orbitals for both dtypes, 1.1-1.4x for complex128 up to 24.  Since the streamed kernels exist (below: the loads of the
+    // next items under the products of these) it is the automatic choice only up to 8 orbitals (fp64) / 4 (complex128) -- what the kernel waits for there is the one round trip of its loads and the
+    // drain of its stores, with one workgroup per CU and nothing to overlap them with.  g_tune.small4 == 2: wherever it exists)
+    const int64_t n4 = cdiv(L, 4);
+    if (in_dtype == dtype && g_tune.small4 && L <= 32 && M <= 32 && n4 == cdiv(M, 4) &&
+        (g_tune.small4 == 2 || n4 <= (dtype == QS_C128 ? 1 : 2)))
+        rc = both([&](const FusedPass& p, int b) { return small4_try(dtype, p, b, s); });
+
+    // fp64, 5 ... 96 orbitals: the two passes on the streamed kernel (qs_quad4s.h) where it measured faster than what
+    // follows (profiles/r03_quad4s.txt).  g_tune.quad4s == 2: wherever it exists.
+    if (rc == 1 && in_dtype == dtype && dtype == QS_F64 && g_tune.quad4s && L >= 5 && M >= 5 && L <= 96 && M <= 96 && n4 == cdiv(M, 4) &&
+        (g_tune.quad4s == 2 || (quad4s_wins(L, M) && g_tune.sandwich < 4)))       // (sandwich >= 4: tuning runs of those kernels)
+        rc = both([&](const FusedPass& p, int) { return quad4s_try(dtype, p, s); });
+
+    // complex128 up to 56 orbitals: the same two passes with two items per matrix instruction (qs_pair4c.hip).  Automatic
+    // where it measured faster than qs_small4.hip / the four 16-wide passes (same-box sweeps, profiles/r03_pair4c.txt): from 5
+    // orbitals, all of them in the STREAMED form (section 5: item pairs through a ring of row quads, fetched ahead): 1.07-1.56x
+    // (l = 20 17.2 -> 12.0 us, l = 55 409 -> 351 us = 45.9 TFLOP/s); 57 ... 64 orbitals exist but spill and lose.
+    // g_tune.pair4c == 2: wherever it exists.
+    if (rc == 1 && in_dtype == dtype && dtype == QS_C128 && g_tune.pair4c && L <= 64 && M <= 64 && n4 == cdiv(M, 4) &&
+        (g_tune.pair4c == 2 || (n4 >= 2 && n4 <= 14)))
+        rc = both([&](const FusedPass& p, int b) { return pair4c_try(dtype, p, b, s); });
+
+    // small bases: two passes over the tensor instead of four -- (d, c) per slab u[a, b], then (b, a) per
+    // column (r, s): out[:, :, rs] = Ct . T2[:, :, rs] . Ct^T (the same k-ordered sums, element for element)
+    // a REAL tensor against complex coefficients (qs_transform_two_body_mixed), 5 ... 56 orbitals: the streamed pair kernel with
+    // real items for the first pass (its first product is one MFMA per fragment instead of two), the complex one for the second
+    // (tools/mixed_small.py: the tiled route took 22.7 us at l = 20 where a complex tensor takes 13.3).
+    if (rc == 1 && in_dtype == QS_F64 && dtype == QS_C128 && g_tune.pair4c && L >= 5 && M >= 5 && L <= 56 && M <= 56 &&
+        n4 == cdiv(M, 4))
+        rc = both([&](const FusedPass& p, int b) { return b ? pair4c_try(dtype, p, b, s) : pair4m_try(p, s); });
+    if (rc != 1) return rc;
+
+    if (in_dtype == dtype && (g_tune.sandwich == 1 || g_tune.sandwich == 3 || g_tune.sandwich == 4 || g_tune.sandwich == 6)) {
+        // T2 (L, L, M, M) goes to WA; the eligibility of the second pass is known before the first runs
+        const int64_t MM = M * M;
+        // the policy (where two fused passes measured faster) ...
+        const bool wanted = dtype == QS_F64 && L <= 64 && M <= 64 && n4 == cdiv(M, 4) && MM >= 1024 &&
+                            (4 * n4) * L * MM * 2 * 8 < (int64_t(1) << 31) &&
+                            (g_tune.sandwich >= 4 ? n4 >= 6 : n4 >= 9) &&
+                            // (15: both passes on slabs through the balanced kernel's instantiation for 16, or not at all)
+                            (n4 != 15 || (g_tune.sandwich_v2 != 0 && g_tune.sandwich_t2 != 0 && g_tune.sandwich != 3 &&
+                                          g_tune.sandwich != 6));
+        // ... and the kernel's own eligibility rule, asked of the kernel (dry run of the very calls made below), so the
+        // two can never disagree after the first pass has run: T2 transposed only if both passes take that layout
+        const FusedPass slab_tr = slab_pass(u, WA, C, L * L, L, M, true), column_tr = column_pass(WA, out, Ct, L, M, true);
+        const bool second_nat = wanted && sandwich4_try(dtype, column, 1, s) == QS_OK;
+        const bool second_tr = wanted && g_tune.sandwich != 3 && g_tune.sandwich != 6 &&
+                               sandwich4_try(dtype, slab_tr, 1, s) == QS_OK && sandwich4_try(dtype, column_tr, 1, s) == QS_OK;
+        const bool second_ok = second_nat || second_tr;
+        if (second_ok) {
+            int rc2 = 1;
+            // T2 transposed, (r, s, a, b): the second pass then fetches slabs like the first (64-byte runs, the four
+            // waves of a workgroup on the same lines) instead of columns (32-byte runs), and the first one stores the
+            // way the second does.  Same-box sweep (profiles/r02_small_basis_sweep.txt): 4-10 % faster for
+            // ceil(l/4) in {10, 13, 14, 16}, faster than the second pass alone for 11, slower for 9 and l = 48 (45 ... 47:
+            // faster since round 3, gpurun_out r03y tail_ab*); 15 has
+            // slab passes only (the balanced kernel's instantiation for 16).
+            const bool want_t2 = second_tr && (!second_nat || (g_tune.sandwich_t2 >= 0 ? g_tune.sandwich_t2 != 0
+                                                                                         : (n4 == 10 || n4 == 11 || n4 >= 13 ||
+                                                                                            (n4 == 12 && L % 4 != 0) ||
+                                                                                            (n4 == 9 && L == 36 && M == 36 && g_tune.sandwich_tail))));
+            // (want_t2: the dry run of this very call passed, so it launches; otherwise second_nat holds)
+            if (g_tune.sandwich != 3 && g_tune.sandwich != 6) rc2 = sandwich4_try(dtype, want_t2 ? slab_tr : slab, 0, s);
+            if (rc2 == 1) {
+                // first pass on the 16-wide kernels (T1 in the spare buffer WB, T2 into WA, natural layout)
+                rc2 = slab_pair_try(dtype, u, C, WA, L * L, L, M, s);
+                if (rc2 == 1) {
+                    rc2 = transpose_small(dtype, C, CT, L, M, s);
+                    if (rc2) return rc2;
+                    rc2 = gemm(dtype, u, C, WB, L * L * L, M, L, L, M, M, 1, 0, 0, 0, s);
+                    if (rc2) return rc2;
+                    rc2 = gemm(dtype, CT, WB, WA, M, M, L, L, M, M, L * L, 0, L * M, MM, s);
+                }
+            }
+            if (rc2) return rc2;
+            rc2 = sandwich4_try(dtype, want_t2 ? column_tr : column, 0, s);
+            if (rc2 != 1) return rc2;
+            // not reached: the dry runs above ARE the kernel's eligibility rule for these very calls
+            snprintf(g_hip_err, sizeof(g_hip_err), "qs_transform_two_body: second fused pass refused after its dry run");
+            return QS_ERR_HIP;
+        }
+    }
+    return 1;
+}
+
 static int transform_two_body_impl(int in_dtype, int dtype, const void* u, const void* C, const void* Ct, void* out,
                                    void* work, int64_t work_bytes, int64_t L, int64_t M, void* stream) {
     dispatch_reset();
@@ -304,125 +433,9 @@ static int transform_two_body_impl(int in_dtype, int dtype, const void* u, const
     const int64_t wa = (L * L * L * M > L * M * M * M) ? L * L * L * M : L * M * M * M;
     void* WB = (M < L) ? at(WA, wa, es) : out;
 
-    // up to 32 orbitals, both dtypes: two launches of the LDS-staged kernel (what is left below ~33 orbitals is launches, not
-    // work: the 16-wide kernels need three to five); T2 (L, L, M, M) in WA
-    // (same-box sweep with the launches of a transform captured in one graph, profiles/r03_small4.txt: 1.8-2.9x up to 15
-    // orbitals for both dtypes, 1.1-1.4x for complex128 up to 24.  Since the streamed kernels exist (below: the loads of the
-    // next items under the products of these) it is the automatic choice only up to 8 orbitals (fp64) / 4 (complex128) -- what the kernel waits for there is the one round trip of its loads and the
-    // drain of its stores, with one workgroup per CU and nothing to overlap them with.  g_tune.small4 == 2: wherever it exists)
-    const int64_t n4s = cdiv(L, 4);
-    if (in_dtype == dtype && g_tune.small4 && L <= 32 && M <= 32 && n4s == cdiv(M, 4) &&
-        (g_tune.small4 == 2 || n4s <= (dtype == QS_C128 ? 1 : 2))) {
-        const int64_t MM = M * M;
-        int rc1 = small4_try(dtype, u, WA, C, M, 1, C, 1, M, L * L, L, M, L * L, L, 1, MM, M, 1, 0, s);
-        if (rc1 == QS_OK)
-            rc1 = small4_try(dtype, WA, out, Ct, 1, L, Ct, L, 1, MM, L, M, 1, L * MM, MM, 1, M * MM, MM, 1, s);
-        if (rc1 != 1) return rc1;
-    }
-
-    // fp64, 5 ... 96 orbitals: the two passes on the streamed kernel (qs_quad4s.h) where it measured faster than what
-    // follows (profiles/r03_quad4s.txt).  g_tune.quad4s == 2: wherever it exists.
-    if (in_dtype == dtype && dtype == QS_F64 && g_tune.quad4s && L >= 5 && M >= 5 && L <= 96 && M <= 96 && n4s == cdiv(M, 4) &&
-        (g_tune.quad4s == 2 || (quad4s_wins(L, M) && g_tune.sandwich < 4))) {       // (sandwich >= 4: tuning runs of those kernels)
-        const int64_t MM = M * M;
-        int rc1 = quad4s_try(dtype, u, WA, C, M, 1, C, 1, M, L * L, L, M, L * L, L, 1, MM, M, 1, s);
-        if (rc1 == QS_OK)
-            rc1 = quad4s_try(dtype, WA, out, Ct, 1, L, Ct, L, 1, MM, L, M, 1, L * MM, MM, 1, M * MM, MM, s);
-        if (rc1 != 1) return rc1;
-    }
-
-    // complex128 up to 56 orbitals: the same two passes with two items per matrix instruction (qs_pair4c.hip).  Automatic
-    // where it measured faster than qs_small4.hip / the four 16-wide passes (same-box sweeps, profiles/r03_pair4c.txt): from 5
-    // orbitals, all of them in the STREAMED form (section 5: item pairs through a ring of row quads, fetched ahead): 1.07-1.56x
-    // (l = 20 17.2 -> 12.0 us, l = 55 409 -> 351 us = 45.9 TFLOP/s); 57 ... 64 orbitals exist but spill and lose.
-    // g_tune.pair4c == 2: wherever it exists.
-    if (in_dtype == dtype && dtype == QS_C128 && g_tune.pair4c && L <= 64 && M <= 64 && n4s == cdiv(M, 4) &&
-        (g_tune.pair4c == 2 || (n4s >= 2 && n4s <= 14))) {
-        const int64_t MM = M * M;
-        int rc1 = pair4c_try(dtype, u, WA, C, M, 1, C, 1, M, L * L, L, M, L * L, L, 1, MM, M, 1, 0, s);
-        if (rc1 == QS_OK)
-            rc1 = pair4c_try(dtype, WA, out, Ct, 1, L, Ct, L, 1, MM, L, M, 1, L * MM, MM, 1, M * MM, MM, 1, s);
-        if (rc1 != 1) return rc1;
-    }
-
-    // small bases: two passes over the tensor instead of four -- (d, c) per slab u[a, b], then (b, a) per
-    // column (r, s): out[:, :, rs] = Ct . T2[:, :, rs] . Ct^T (the same k-ordered sums, element for element)
-    // a REAL tensor against complex coefficients (qs_transform_two_body_mixed), 5 ... 56 orbitals: the streamed pair kernel with
-    // real items for the first pass (its first product is one MFMA per fragment instead of two), the complex one for the second
-    // (tools/mixed_small.py: the tiled route took 22.7 us at l = 20 where a complex tensor takes 13.3).
-    if (in_dtype == QS_F64 && dtype == QS_C128 && g_tune.pair4c && L >= 5 && M >= 5 && L <= 56 && M <= 56 &&
-        n4s == cdiv(M, 4)) {
-        const int64_t MM = M * M;
-        int rc1 = pair4m_try(u, WA, C, M, 1, C, 1, M, L * L, L, M, L * L, L, 1, MM, M, 1, s);
-        if (rc1 == QS_OK)
-            rc1 = pair4c_try(dtype, WA, out, Ct, 1, L, Ct, L, 1, MM, L, M, 1, L * MM, MM, 1, M * MM, MM, 1, s);
-        if (rc1 != 1) return rc1;
-    }
-
-    if (in_dtype == dtype && (g_tune.sandwich == 1 || g_tune.sandwich == 3 || g_tune.sandwich == 4 || g_tune.sandwich == 6)) {
-        // T2 (L, L, M, M) goes to WA; the eligibility of the second pass is known before the first runs
-        const int64_t MM = M * M;
-        const int64_t n4 = cdiv(L, 4);
-        // the policy (where two fused passes measured faster) ...
-        const bool wanted = dtype == QS_F64 && L <= 64 && M <= 64 && n4 == cdiv(M, 4) && MM >= 1024 &&
-                            (4 * n4) * L * MM * 2 * 8 < (int64_t(1) << 31) &&
-                            (g_tune.sandwich >= 4 ? n4 >= 6 : n4 >= 9) &&
-                            // (15: both passes on slabs through the balanced kernel's instantiation for 16, or not at all)
-                            (n4 != 15 || (g_tune.sandwich_v2 != 0 && g_tune.sandwich_t2 != 0 && g_tune.sandwich != 3 &&
-                                          g_tune.sandwich != 6));
-        // ... and the kernel's own eligibility rule, asked of the kernel (dry run of the very calls made below), so the
-        // two can never disagree after the first pass has run: T2 transposed only if both passes take that layout
-        const bool second_nat = wanted && sandwich4_try(dtype, WA, out, Ct, 1, L, Ct, L, 1, MM, L, M, 1, L * MM, MM, 1,
-                                                        M * MM, MM, s, 1) == QS_OK;
-        const bool second_tr = wanted && g_tune.sandwich != 3 && g_tune.sandwich != 6 &&
-                               sandwich4_try(dtype, u, WA, C, M, 1, C, 1, M, L * L, L, M, L * L, L, 1, 1, M * L * L, L * L, s, 1) == QS_OK &&
-                               sandwich4_try(dtype, WA, out, Ct, 1, L, Ct, L, 1, MM, L, M, L * L, L, 1, 1, M * MM, MM, s, 1) == QS_OK;
-        const bool second_ok = second_nat || second_tr;
-        if (second_ok) {
-            void* T1s = (M < L) ? at(WA, wa, es) : out;     // scratch of the unfused fall-back of the first pass
-            int rc2 = 1;
-            // T2 transposed, (r, s, a, b): the second pass then fetches slabs like the first (64-byte runs, the four
-            // waves of a workgroup on the same lines) instead of columns (32-byte runs), and the first one stores the
-            // way the second does.  Same-box sweep (profiles/r02_small_basis_sweep.txt): 4-10 % faster for
-            // ceil(l/4) in {10, 13, 14, 16}, faster than the second pass alone for 11, slower for 9 and l = 48 (45 ... 47:
-            // faster since round 3, gpurun_out r03y tail_ab*); 15 has
-            // slab passes only (the balanced kernel's instantiation for 16).
-            const bool want_t2 = second_tr && (!second_nat || (g_tune.sandwich_t2 >= 0 ? g_tune.sandwich_t2 != 0
-                                                                                         : (n4 == 10 || n4 == 11 || n4 >= 13 ||
-                                                                                            (n4 == 12 && L % 4 != 0) ||
-                                                                                            (n4 == 9 && L == 36 && M == 36 && g_tune.sandwich_tail))));
-            bool t2_transposed = false;
-            if (g_tune.sandwich != 3 && g_tune.sandwich != 6) {
-                if (want_t2)
-                    rc2 = sandwich4_try(dtype, u, WA, C, M, 1, C, 1, M, L * L, L, M, L * L, L, 1, 1, M * L * L, L * L, s);
-                else if (second_nat)
-                    rc2 = sandwich4_try(dtype, u, WA, C, M, 1, C, 1, M, L * L, L, M, L * L, L, 1, MM, M, 1, s);
-                t2_transposed = want_t2 && rc2 != 1;
-            }
-            if (rc2 == 1 && second_nat) {
-                // first pass on the 16-wide kernels (T1 in the spare buffer, T2 into WA, natural layout)
-                rc2 = slab_pair_try(dtype, u, C, WA, L * L, L, M, s);
-                if (rc2 == 1) {
-                    rc2 = transpose_small(dtype, C, CT, L, M, s);
-                    if (rc2) return rc2;
-                    rc2 = gemm(dtype, u, C, T1s, L * L * L, M, L, L, M, M, 1, 0, 0, 0, s);
-                    if (rc2) return rc2;
-                    rc2 = gemm(dtype, CT, T1s, WA, M, M, L, L, M, M, L * L, 0, L * M, MM, s);
-                }
-            }
-            if (rc2) return rc2;
-            if (t2_transposed)
-                rc2 = sandwich4_try(dtype, WA, out, Ct, 1, L, Ct, L, 1, MM, L, M, L * L, L, 1, 1, M * MM, MM, s);
-            else
-                rc2 = sandwich4_try(dtype, WA, out, Ct, 1, L, Ct, L, 1, MM, L, M, 1, L * MM, MM, 1, M * MM, MM, s);
-            if (rc2 != 1) return rc2;
-            // not reached: the dry runs above ARE the kernel's eligibility rule for these very calls
-            snprintf(g_hip_err, sizeof(g_hip_err), "qs_transform_two_body: second fused pass refused after its dry run");
-            return QS_ERR_HIP;
-        }
-    }
-
-    int rc = contract_dcb(in_dtype, dtype, u, C, CT, Ct, /*T1*/ WA, /*T2*/ WB, /*T3*/ WA, L, L, M, s);
+    int rc = transform_two_body_fused(in_dtype, dtype, u, C, Ct, out, CT, WA, WB, L, M, s);
+    if (rc != 1) return rc;
+    rc = contract_dcb(in_dtype, dtype, u, C, CT, Ct, /*T1*/ WA, /*T2*/ WB, /*T3*/ WA, L, L, M, s);
     if (rc) return rc;
     return gemm(dtype, Ct, WA, out, M, M * M * M, L, L, M * M * M, M * M * M, 1, 0, 0, 0, s);
 }

@@ -107,33 +107,49 @@ int gemm_stream_try(int dtype, const double* A, const double* B, double* C, int6
 int slab_pair_try(int dtype, const void* X, const void* B, void* Z, int64_t nslabs, int64_t L, int64_t M,
                   hipStream_t stream);
 
-// Fused pair of contractions on the 4-wide matrix instruction (qs_sandwich4.hip): Out_t = Lm . In_t . R for a batch
-// of L x L matrices with arbitrary element strides; L, M <= 64, ceil(L/4) == ceil(M/4).  dry_run: launch nothing,
-// QS_OK = the call would launch.
-int sandwich4_try(int dtype, const void* in, void* out, const void* R, int64_t r_sk, int64_t r_sj, const void* Lm,
-                  int64_t l_sp, int64_t l_sa, int64_t nitems, int64_t L, int64_t M, int64_t in_item, int64_t in_row,
-                  int64_t in_col, int64_t out_item, int64_t out_row, int64_t out_col, hipStream_t stream,
-                  int dry_run = 0);
+// One fused pass of the small-basis kernels: Out_t = Lm . In_t . R for t < nitems, a batch of L x L matrices In_t with
+// arbitrary element strides, ceil(L/4) == ceil(M/4).  The common head of every family's kernel arguments
+// (S4Args, Small4Args, Quad4Args, Pair4Args derive from it and add their own fields): kernel symbols name those structs,
+// and their layout is the kernels' argument layout -- `ntuples` stays in here, so that the base has no tail padding.
+struct FusedPass {
+    const double* in;
+    double* out;
+    const double* R;      // R[k][j]  = R[k * r_sk + j * r_sj],   L x M
+    const double* Lm;     // Lm[p][a] = Lm[p * l_sp + a * l_sa],  M x L
+    int64_t r_sk, r_sj, l_sp, l_sa;
+    int64_t in_item, in_row, in_col;       // element strides of In_t[i][k]: in_col == 1 (a slab) or in_item == 1 (a column)
+    int64_t out_item, out_row, out_col;    // element strides of Out_t[p][j]
+    int L, M;
+    unsigned nitems;
+    unsigned ntuples;     // the item tuples one matrix instruction takes: quads, pairs in the pair kernels (set by the family)
+};
+static_assert(sizeof(FusedPass) == 128, "a family's own fields start at offset 128");
 
-// Fused pair of contractions for SMALL bases, L, M <= 32, ceil(L/4) == ceil(M/4), fp64 and complex128 (qs_small4.hip): the
-// same product on item quads staged in LDS.  tensor_is_b: complex only -- in the 16-wide kernels' call for the first
-// product the tensor is the B operand (the b contraction), which fixes the order of the two imaginary-part products.
-int small4_try(int dtype, const void* in, void* out, const void* R, int64_t r_sk, int64_t r_sj, const void* Lm,
-               int64_t l_sp, int64_t l_sa, int64_t nitems, int64_t L, int64_t M, int64_t in_item, int64_t in_row,
-               int64_t in_col, int64_t out_item, int64_t out_row, int64_t out_col, int tensor_is_b, hipStream_t stream);
+// A family's kernel arguments: `pass` and its item tuples of `per` items; the family's own fields zero.
+template <class Args>
+inline Args fused_args(const FusedPass& pass, int per) {
+    Args g{};
+    static_cast<FusedPass&>(g) = pass;
+    g.ntuples = (unsigned)cdiv(pass.nitems, per);
+    return g;
+}
 
+// The fused passes (qs_sandwich4.hip, qs_small4.hip, qs_quad4s.hip, qs_pair4c.hip): QS_OK / error after launching,
+// 1 = not eligible.
+// 4-wide matrix instruction, fp64, L, M <= 64.  dry_run: launch nothing, QS_OK = the call would launch.
+int sandwich4_try(int dtype, const FusedPass& pass, int dry_run, hipStream_t stream);
+
+// SMALL bases, L, M <= 32, fp64 and complex128: item quads staged in LDS.  tensor_is_b: complex only -- in the 16-wide
+// kernels' call for the first product the tensor is the B operand (the b contraction), which fixes the order of the two
+// imaginary-part products.
+int small4_try(int dtype, const FusedPass& pass, int tensor_is_b, hipStream_t stream);
+
+// fp64, 5 ... 96 orbitals, streamed: item quads through a ring of row quads, one wave per column group.
+int quad4s_try(int dtype, const FusedPass& pass, hipStream_t stream);
+// The same for complex128, 5 ... 64 orbitals (qs_pair4s.h): two items per matrix instruction, blocks = (item, re | im), streamed.
+int pair4c_try(int dtype, const FusedPass& pass, int tensor_is_b, hipStream_t stream);
 // ... and for REAL items against complex R and Lm (the first pass of a real tensor against complex coefficients), streamed form only
-int pair4m_try(const void* in, void* out, const void* R, int64_t r_sk, int64_t r_sj, const void* Lm, int64_t l_sp, int64_t l_sa,
-               int64_t nitems, int64_t L, int64_t M, int64_t in_item, int64_t in_row, int64_t in_col, int64_t out_item,
-               int64_t out_row, int64_t out_col, hipStream_t stream);
-// fp64, 17 ... 64 orbitals, streamed (qs_quad4s.hip): item quads through a ring of row quads, one wave per column group.
-int quad4s_try(int dtype, const void* in, void* out, const void* R, int64_t r_sk, int64_t r_sj, const void* Lm,
-               int64_t l_sp, int64_t l_sa, int64_t nitems, int64_t L, int64_t M, int64_t in_item, int64_t in_row,
-               int64_t in_col, int64_t out_item, int64_t out_row, int64_t out_col, hipStream_t stream);
-// The same for complex128, 5 ... 64 orbitals (qs_pair4s.h, qs_pair4c.hip): two items per matrix instruction, blocks = (item, re | im), streamed.
-int pair4c_try(int dtype, const void* in, void* out, const void* R, int64_t r_sk, int64_t r_sj, const void* Lm,
-               int64_t l_sp, int64_t l_sa, int64_t nitems, int64_t L, int64_t M, int64_t in_item, int64_t in_row,
-               int64_t in_col, int64_t out_item, int64_t out_row, int64_t out_col, int tensor_is_b, hipStream_t stream);
+int pair4m_try(const FusedPass& pass, hipStream_t stream);
 
 // Strip kernels (qs_gemm_strip.hip): same return convention; general_cost as for gemm_fast_try.
 int gemm_strip_try(int dtype, const double* A, const double* B, double* C, int64_t m, int64_t n, int64_t k, int64_t lda,
@@ -183,7 +199,6 @@ struct Tuning {
     int small4 = 1;              // both fused passes of a basis of <= 32 orbitals on the LDS-staged 4-wide kernel (qs_small4.hip), fp64 and
                                  // complex128: 1 automatic (fp64 up to 16, complex128 up to 24 orbitals), 2 wherever it exists (up to 32), 0 off
     int quad4s = 1;              // fp64 17 ... 64 orbitals on the streamed fused kernel (qs_quad4s.hip): 0 never, 1 where measured faster, 2 wherever it exists
-    int pair4c_stream = 1;       // (kept for old tuning scripts: the whole-pair form it switched to is gone)
     int pair4c = 1;              // complex128 up to 56 orbitals: both fused passes on the two-items-per-instruction kernel (qs_pair4c.hip):
                                  // 1 automatic, 2 wherever it exists, 0 off
     int gemm_strip = 1;          // strip kernels (qs_gemm_strip.hip: the small extent of a product, <= 256, covered by ONE tile to the next

@@ -51,16 +51,7 @@ __device__ __forceinline__ void unroll(F&& f) {
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 typedef int i32x2 __attribute__((ext_vector_type(2)));
 
-struct Pair4Args {
-    const double* in;
-    double* out;
-    const double* R;      // R[k][j]  = R[k * r_sk + j * r_sj],   L x M   (complex elements)
-    const double* Lm;     // Lm[p][a] = Lm[p * l_sp + a * l_sa],  M x L
-    int64_t r_sk, r_sj, l_sp, l_sa;
-    int64_t in_item, in_row, in_col;       // element strides of In_t[i][k]: in_col == 1 (a slab) or in_item == 1 (a column)
-    int64_t out_item, out_row, out_col;    // element strides of Out_t[p][j]
-    int L, M;
-    unsigned nitems, npairs;
+struct Pair4Args : FusedPass {      // R and Lm in complex elements; ntuples = item pairs
     int tensor_is_b;      // the 16-wide kernels' call for the FIRST product has the tensor as its B operand (the b contraction)
 };
 
@@ -127,8 +118,8 @@ __global__ __launch_bounds__(64 * stream_waves(N4)) void pair4s_kernel(const Pai
     const bool slab = g.in_col == 1;
 
     const unsigned n_xcd = 8, xcd = blockIdx.x % n_xcd, slot = blockIdx.x / n_xcd, slots = gridDim.x / n_xcd;
-    const unsigned per = (g.npairs + n_xcd - 1) / n_xcd;
-    const unsigned u_end = (xcd + 1) * per < g.npairs ? (xcd + 1) * per : g.npairs;
+    const unsigned per = (g.ntuples + n_xcd - 1) / n_xcd;
+    const unsigned u_end = (xcd + 1) * per < g.ntuples ? (xcd + 1) * per : g.ntuples;
     unsigned unit = xcd * per + slot;
     if (unit >= u_end) return;                              // (the whole workgroup, before any barrier)
 
@@ -430,7 +421,7 @@ int launch_pair4s(const Pair4Args& g, hipStream_t stream) {
     static PerDeviceLds lds_opt_in;
     if (int rc = opt_in_dynamic_lds((const void*)pair4s_kernel<N4, REAL_IN>, lds, lds_opt_in, "hipFuncSetAttribute(pair4s)")) return rc;
     const int n_cu = device_cu_count();
-    unsigned wgs = (g.npairs + 7u) / 8u * 8u;
+    unsigned wgs = (g.ntuples + 7u) / 8u * 8u;
     const unsigned cap = (unsigned)(n_cu - n_cu % 8 > 8 ? n_cu - n_cu % 8 : 8);      // one workgroup of N4 waves per CU
     if (wgs > cap) wgs = cap;
     // every byte offset inside an item pair stays below 2^31 (32-bit lane and scalar offsets of the fetch)

@@ -46,17 +46,7 @@ __device__ __forceinline__ void unroll_q(F&& f) {
 typedef double f64x2q __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4q __attribute__((ext_vector_type(4)));
 
-struct Quad4Args {
-    const double* in;
-    double* out;
-    const double* R;      // R[k][j]  = R[k * r_sk + j * r_sj],   L x M
-    const double* Lm;     // Lm[p][a] = Lm[p * l_sp + a * l_sa],  M x L
-    int64_t r_sk, r_sj, l_sp, l_sa;
-    int64_t in_item, in_row, in_col;       // element strides of In_t[i][k]: in_col == 1 (a slab) or in_item == 1 (a column)
-    int64_t out_item, out_row, out_col;    // element strides of Out_t[p][j]
-    int L, M;
-    unsigned nitems, nquads;
-};
+struct Quad4Args : FusedPass {};     // (its own name: the kernel symbols carry it)
 
 // development builds only: bit mask of parts to leave out (1 the fetches, 2 the stores, 8 the step barrier -- wrong results)
 #ifndef QS_QUAD4S_ABLATE
@@ -103,8 +93,8 @@ __global__ __launch_bounds__(64 * ((N4 + H - 1) / H)) void quad4s_kernel(const Q
     // (H = 2: workgroups 8 (2 q) + x and 8 (2 q + 1) + x of XCD x are the halves of the same quads)
     const unsigned n_xcd = 8, xcd = blockIdx.x % n_xcd, slot = (blockIdx.x / n_xcd) / H, slots = (gridDim.x / n_xcd) / H;
     const int half = (int)((blockIdx.x / n_xcd) % H);
-    const unsigned per = (g.nquads + n_xcd - 1) / n_xcd;
-    const unsigned u_end = (xcd + 1) * per < g.nquads ? (xcd + 1) * per : g.nquads;
+    const unsigned per = (g.ntuples + n_xcd - 1) / n_xcd;
+    const unsigned u_end = (xcd + 1) * per < g.ntuples ? (xcd + 1) * per : g.ntuples;
     unsigned unit = xcd * per + slot;
     if (unit >= u_end) return;                              // (the whole workgroup, before any barrier)
 
@@ -295,7 +285,7 @@ int launch_quad4s(const Quad4Args& g, hipStream_t stream) {
     static PerDeviceLds lds_opt_in;
     if (int rc = opt_in_dynamic_lds((const void*)quad4s_kernel<N4, H>, lds, lds_opt_in, "hipFuncSetAttribute(quad4s)")) return rc;
     const int n_cu = device_cu_count();
-    unsigned wgs = (g.nquads + 7u) / 8u * 8u * H;       // (a multiple of 8 H: whole quads per XCD slot pair)
+    unsigned wgs = (g.ntuples + 7u) / 8u * 8u * H;       // (a multiple of 8 H: whole quads per XCD slot pair)
     // workgroups resident per CU: by threads (2048 per CU) and LDS
 #ifndef QS_QUAD4S_TWO_PER_CU_TO
 #define QS_QUAD4S_TWO_PER_CU_TO 8

@@ -5,18 +5,11 @@
 
 #include <cstdint>
 
+#include "qs_common.h"
+
 namespace qs {
 
-struct S4Args {
-    const double* in;
-    double* out;
-    const double* R;      // R[k][j]  = R[k * r_sk + j * r_sj],   L x M
-    const double* Lm;     // Lm[p][a] = Lm[p * l_sp + a * l_sa],  M x L
-    int64_t r_sk, r_sj, l_sp, l_sa;
-    int64_t in_item, in_row, in_col;       // element strides of In_t[i][k]: in_col == 1 (a slab) or in_item == 1 (a column)
-    int64_t out_item, out_row, out_col;    // element strides of Out_t[p][j]
-    int L, M;
-    unsigned nitems, nquads;
+struct S4Args : FusedPass {
     unsigned tail_first, tail_parts;   // balanced form only (else 0, 0): item quads from tail_first on -- the partly filled last
                                        // round -- are split into tail_parts column-group parts, one workgroup each
     int mode;      // bit 0: the four waves take four ADJACENT item quads and the same chunk (else: one quad, four chunks);

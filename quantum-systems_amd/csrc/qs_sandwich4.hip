@@ -136,8 +136,8 @@ __global__ __launch_bounds__(256, 1) void sandwich4_kernel(const S4Args g) {
     //                     rotates with the round, so every workgroup sees all chunk sizes.
     const bool grouped = g.mode & 1, step_barrier = (g.mode & 3) == 3;
     const unsigned n_xcd = 8, xcd = blockIdx.x % n_xcd, slot = blockIdx.x / n_xcd, slots = gridDim.x / n_xcd;
-    const unsigned ngroups = (g.nquads + 3) / 4;
-    const unsigned nunits = grouped ? ngroups * NCH : g.nquads;
+    const unsigned ngroups = (g.ntuples + 3) / 4;
+    const unsigned nunits = grouped ? ngroups * NCH : g.ntuples;
     // (grouped: the chunk units of a group must fall into the same round of the same XCD, or the rotation would
     // hand one chunk out twice: an XCD's range and the workgroup stride are whole groups)
     unsigned per = (nunits + n_xcd - 1) / n_xcd;
@@ -433,8 +433,8 @@ __global__ __launch_bounds__(256, 1) void sandwich4_kernel(const S4Args g) {
     };
 
     unsigned v_in[4], v_nx[4], w_in[4], w_nx[4], v_out[4];
-    auto rs_in = rsrc(g.in - 1, iq < g.nquads ? iq : 0, g.in_item);
-    in_offsets(iq, !idle && iq < g.nquads, v_in, w_in);
+    auto rs_in = rsrc(g.in - 1, iq < g.ntuples ? iq : 0, g.in_item);
+    in_offsets(iq, !idle && iq < g.ntuples, v_in, w_in);
     {   // every thread issues all its loads before the first LDS write (a load-store-load chain would pay the
         // memory latency ceil(l/4)^2/16 times before the first MFMA).  Thread t takes element t & 15 of the 4 x 4
         // blocks t / 16, t / 16 + 16, ...: the block coordinates advance by additions (the first version spent
@@ -491,11 +491,11 @@ __global__ __launch_bounds__(256, 1) void sandwich4_kernel(const S4Args g) {
     unsigned phase = 0;       // fetch stage of row quad 0 of the current unit
     for (unsigned round = 0; unit < u_end; ++round) {
         const unsigned nu = unit + slots;
-        const unsigned nq = nu < u_end ? quad_of(nu) : g.nquads;
-        const bool more = nq < g.nquads;
+        const unsigned nq = nu < u_end ? quad_of(nu) : g.ntuples;
+        const bool more = nq < g.ntuples;
         auto rs_nx = rsrc(g.in - 1, more ? nq : 0, g.in_item);
         in_offsets(nq, more, v_nx, w_nx);
-        auto rs_out = rsrc(g.out, iq < g.nquads ? iq : 0, g.out_item);
+        auto rs_out = rsrc(g.out, iq < g.ntuples ? iq : 0, g.out_item);
         out_offsets(iq, v_out);
         const int c = chunk_of(unit, round);
         const int jg0 = chunk_first(c);
@@ -525,7 +525,7 @@ static int launch_sandwich4(const S4Args& g, hipStream_t stream, int dry_run) {
     const int n_cu = device_cu_count();
     int64_t wgs = n_cu - n_cu % 8;                       // one workgroup (four waves, one per SIMD) per CU
     if (wgs < 8) wgs = 8;
-    const int64_t units = (g.mode & 1) ? ((int64_t)g.nquads + 3) / 4 * ((N4 + 3) / 4) : (int64_t)g.nquads;
+    const int64_t units = (g.mode & 1) ? ((int64_t)g.ntuples + 3) / 4 * ((N4 + 3) / 4) : (int64_t)g.ntuples;
     const int64_t gran = (g.mode & 1) ? 8 * ((N4 + 3) / 4) : 8;       // grouped: workgroups per XCD in whole groups
     wgs -= wgs % gran;
     if (wgs < gran) wgs = gran;
@@ -543,9 +543,10 @@ static int launch_sandwich4(const S4Args& g, hipStream_t stream, int dry_run) {
 // Out_t = Lm . In_t . R for t < nitems (strides in elements); QS_OK / error after launching, 1 = not eligible.
 // With `dry_run` nothing is launched: QS_OK = this call would launch (the ONE eligibility rule, asked by
 // qs_transform_two_body before it commits the intermediate to the layout of the second fused pass).
-int sandwich4_try(int dtype, const void* in, void* out, const void* R, int64_t r_sk, int64_t r_sj, const void* Lm,
-                  int64_t l_sp, int64_t l_sa, int64_t nitems, int64_t L, int64_t M, int64_t in_item, int64_t in_row,
-                  int64_t in_col, int64_t out_item, int64_t out_row, int64_t out_col, hipStream_t stream, int dry_run) {
+int sandwich4_try(int dtype, const FusedPass& pass, int dry_run, hipStream_t stream) {
+    const int64_t L = pass.L, M = pass.M, nitems = pass.nitems;
+    const int64_t in_item = pass.in_item, in_row = pass.in_row, in_col = pass.in_col;
+    const int64_t out_item = pass.out_item, out_row = pass.out_row, out_col = pass.out_col;
     if (dtype != QS_F64) return 1;
     if (L < 1 || M < 1 || L > 64 || M > 64) return 1;
     const int n4 = (int)cdiv(L, 4);
@@ -589,16 +590,8 @@ int sandwich4_try(int dtype, const void* in, void* out, const void* R, int64_t r
     const int64_t in_span = (3 * in_item + (4 * n4) * (in_row > in_col ? in_row : in_col) * 2) * 8;
     const int64_t out_span = (3 * out_item + (4 * n4) * (out_row > out_col ? out_row : out_col) * 2) * 8;
     if (in_span >= (int64_t(1) << 31) || out_span >= (int64_t(1) << 31)) return 1;
-    S4Args g;
-    g.in = (const double*)in; g.out = (double*)out;
-    g.R = (const double*)R; g.Lm = (const double*)Lm;
-    g.r_sk = r_sk; g.r_sj = r_sj; g.l_sp = l_sp; g.l_sa = l_sa;
-    g.in_item = in_item; g.in_row = in_row; g.in_col = in_col;
-    g.out_item = out_item; g.out_row = out_row; g.out_col = out_col;
-    g.L = (int)L; g.M = (int)M;
-    g.nitems = (unsigned)nitems;
-    g.nquads = (unsigned)cdiv(nitems, 4);
-    g.tail_first = g.nquads; g.tail_parts = 0;
+    S4Args g = fused_args<S4Args>(pass, 4);
+    g.tail_first = g.ntuples;
     // items 8 bytes apart (the (b, a) pass): four adjacent quads per workgroup make whole lines; contiguous items
     // (the (d, c) pass): a workgroup per quad keeps its four fetch streams on the same lines
     g.mode = g_tune.sandwich_mode >= 0 ? g_tune.sandwich_mode : (in_item == 1 ? 3 : 0);

@@ -118,7 +118,7 @@ __global__ __launch_bounds__(256, 1) void sandwich4b_kernel(const S4Args g) {
     // ---- work units = item quads.  Every XCD takes a contiguous range and neighbouring workgroups of an XCD take
     // neighbouring quads.
     const unsigned n_xcd = 8, xcd = blockIdx.x % n_xcd, slot = blockIdx.x / n_xcd, slots = gridDim.x / n_xcd;
-    const unsigned nmain = g.tail_parts ? g.tail_first : g.nquads;      // (with a tail: a whole number of rounds of the grid)
+    const unsigned nmain = g.tail_parts ? g.tail_first : g.ntuples;      // (with a tail: a whole number of rounds of the grid)
     const unsigned per = (nmain + n_xcd - 1) / n_xcd;
     const unsigned u_end = (xcd + 1) * per < nmain ? (xcd + 1) * per : nmain;
     unsigned iq = xcd * per + slot;
@@ -500,7 +500,7 @@ __global__ __launch_bounds__(256, 1) void sandwich4b_kernel(const S4Args g) {
         constexpr int RS = N4 / 4;                                // sets that fit over the fragments of R (N4 N4 16 >= RS SET)
         const unsigned task = blockIdx.x;
         const unsigned tq = g.tail_first + task / g.tail_parts;   // (workgroup-uniform)
-        if (tq < g.nquads) {
+        if (tq < g.ntuples) {
             const int jg = 4 * (int)(task % g.tail_parts) + wave;
             const bool has_group = 4 * jg < M;                    // (wave-uniform; such a wave still fetches and takes the barriers)
             const int jgc = has_group ? jg : 0;
@@ -594,16 +594,16 @@ static int launch_sandwich4b(const S4Args& g, hipStream_t stream, int dry_run) {
     const int n_cu = device_cu_count();
     int64_t wgs = n_cu - n_cu % 8;                       // one workgroup (four waves, one per SIMD) per CU
     if (wgs < 8) wgs = 8;
-    const int64_t need = ((int64_t)g.nquads + 7) / 8 * 8;
+    const int64_t need = ((int64_t)g.ntuples + 7) / 8 * 8;
     if (wgs > need) wgs = need;                          // short item lists: no idle workgroups
     size_t lds = sizeof(double) * (2 * N4 * N4 * 16 + 8 * N4 * 64 + ((N4 % 4) ? 2 * N4 * 64 : 0));
     // A last round that is only partly filled: its quads split over all workgroups (the kernel's tail), when one task
     // per workgroup covers them.  (The whole-quad staging of the tail takes N4 - N4 / 4 sets behind the tables.)
     S4Args gt = g;
-    if (sandwich4b_tail_quads(g.nquads, g.M)) {
+    if (sandwich4b_tail_quads(g.ntuples, g.M)) {
         const size_t lds_tail = sizeof(double) * (2 * N4 * N4 * 16 + (N4 - N4 / 4) * N4 * 64);
         if (lds_tail <= 160 * 1024) {
-            gt.tail_first = g.nquads / (unsigned)wgs * (unsigned)wgs;
+            gt.tail_first = g.ntuples / (unsigned)wgs * (unsigned)wgs;
             gt.tail_parts = (unsigned)((cdiv(g.M, 4) + 3) / 4);
             if (lds_tail > lds) lds = lds_tail;
         }

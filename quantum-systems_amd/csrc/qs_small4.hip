@@ -49,16 +49,7 @@ __device__ __forceinline__ void unroll(F&& f) {
 
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 
-struct Small4Args {
-    const double* in;
-    double* out;
-    const double* R;      // R[k][j]  = R[k * r_sk + j * r_sj],   L x M
-    const double* Lm;     // Lm[p][a] = Lm[p * l_sp + a * l_sa],  M x L
-    int64_t r_sk, r_sj, l_sp, l_sa;
-    int64_t in_item, in_row, in_col;       // element strides of In_t[i][k]: in_col == 1 (a slab) or in_item == 1 (a column)
-    int64_t out_item, out_row, out_col;    // element strides of Out_t[p][j]
-    int L, M;
-    unsigned nitems, nquads;
+struct Small4Args : FusedPass {
     int tensor_is_b;      // complex only: in the 16-wide kernels' call for the FIRST product the tensor is the B operand
                           // (the b contraction, gemm(Ct, T2)): the two imaginary-part products then come in the other order
 };
@@ -167,8 +158,8 @@ __global__ __launch_bounds__(small4_threads(CX, N4)) void small4_kernel(const Sm
     // version -- every line was fetched by four L2s and written back as four partial lines (at l = 32: 12 of 29 us in the
     // loads, 16 in the stores; profiles/r03_small4.txt).
     const unsigned n_xcd = 8, xcd = blockIdx.x % n_xcd, slot = blockIdx.x / n_xcd, slots = gridDim.x / n_xcd;
-    const unsigned per = (g.nquads + n_xcd - 1) / n_xcd;
-    const unsigned u_end = (xcd + 1) * per < g.nquads ? (xcd + 1) * per : g.nquads;
+    const unsigned per = (g.ntuples + n_xcd - 1) / n_xcd;
+    const unsigned u_end = (xcd + 1) * per < g.ntuples ? (xcd + 1) * per : g.ntuples;
     unsigned unit = xcd * per + slot;
     if (unit >= u_end) return;                              // (the whole workgroup, before any barrier)
     {   // ---- tables: every element of R and Lm once per workgroup (they sit in L2 after the first workgroup); the loads of
@@ -336,7 +327,7 @@ static int launch_small4(const Small4Args& g, hipStream_t stream) {
     const int n_cu = device_cu_count();
     // an item quad per workgroup; above two quads per CU the workgroups walk the list (the tables are built once each).
     // Whole multiples of the eight XCDs: an XCD's workgroups share its range of quads.
-    unsigned wgs = (g.nquads + 7u) / 8u * 8u;
+    unsigned wgs = (g.ntuples + 7u) / 8u * 8u;
     const unsigned cap = 2u * (unsigned)(n_cu - n_cu % 8 > 8 ? n_cu - n_cu % 8 : 8);
     if (wgs > cap) wgs = cap;
     hipLaunchKernelGGL((small4_kernel<CX, N4>), dim3(wgs), dim3(64 * Split<CX, N4>::NW), lds, stream, g);
@@ -345,24 +336,16 @@ static int launch_small4(const Small4Args& g, hipStream_t stream) {
 }
 
 // Out_t = Lm . In_t . R for t < nitems (element strides); QS_OK / error after launching, 1 = not eligible.
-int small4_try(int dtype, const void* in, void* out, const void* R, int64_t r_sk, int64_t r_sj, const void* Lm,
-               int64_t l_sp, int64_t l_sa, int64_t nitems, int64_t L, int64_t M, int64_t in_item, int64_t in_row,
-               int64_t in_col, int64_t out_item, int64_t out_row, int64_t out_col, int tensor_is_b, hipStream_t stream) {
+int small4_try(int dtype, const FusedPass& pass, int tensor_is_b, hipStream_t stream) {
+    const int64_t L = pass.L, M = pass.M, nitems = pass.nitems;
     if (L < 1 || M < 1 || L > 32 || M > 32) return 1;
     const int n4 = (int)cdiv(L, 4);
     if (n4 != (int)cdiv(M, 4)) return 1;
     if (nitems < 1 || nitems >= (int64_t(1) << 31)) return 1;
-    if (in_col != 1 && in_item != 1) return 1;
-    if (dtype == QS_C128 && (!aligned(in, 16) || !aligned(out, 16) || !aligned(R, 16) || !aligned(Lm, 16))) return 1;
-    Small4Args g;
-    g.in = (const double*)in; g.out = (double*)out;
-    g.R = (const double*)R; g.Lm = (const double*)Lm;
-    g.r_sk = r_sk; g.r_sj = r_sj; g.l_sp = l_sp; g.l_sa = l_sa;
-    g.in_item = in_item; g.in_row = in_row; g.in_col = in_col;
-    g.out_item = out_item; g.out_row = out_row; g.out_col = out_col;
-    g.L = (int)L; g.M = (int)M;
-    g.nitems = (unsigned)nitems;
-    g.nquads = (unsigned)cdiv(nitems, 4);
+    if (pass.in_col != 1 && pass.in_item != 1) return 1;
+    if (dtype == QS_C128 && (!aligned(pass.in, 16) || !aligned(pass.out, 16) || !aligned(pass.R, 16) || !aligned(pass.Lm, 16)))
+        return 1;
+    Small4Args g = fused_args<Small4Args>(pass, 4);
     g.tensor_is_b = tensor_is_b;
     const bool cx = dtype == QS_C128;
     switch (n4) {
