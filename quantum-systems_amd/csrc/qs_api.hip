@@ -117,27 +117,15 @@ void note_dispatch(const char* fmt, ...) {
     g_dispatch_len += nl;
 }
 
-static int gemm(int dtype, const void* A, const void* B, void* C, int64_t m, int64_t n, int64_t k,
-                int64_t lda, int64_t ldb, int64_t ldc, int64_t batch, int64_t sa, int64_t sb,
-                int64_t sc, hipStream_t s, int accumulate = 0) {
-    if (dtype == QS_F64)
-        return gemm_f64((const double*)A, (const double*)B, (double*)C, m, n, k, lda, ldb, ldc, batch,
-                        sa, sb, sc, accumulate, s);
-    return gemm_c128((const double*)A, (const double*)B, (double*)C, m, n, k, lda, ldb, ldc, batch,
-                     sa, sb, sc, accumulate, s);
-}
-
-int matmul_real_by_complex(const void* A, const void* B, void* out, int64_t m, int64_t n, int64_t k, int64_t lda,
-                           int64_t ldb, int64_t ldc, hipStream_t stream) {
-    return gemm_f64((const double*)A, (const double*)B, (double*)out, m, 2 * n, k, lda, 2 * ldb, 2 * ldc, 1, 0, 0, 0, 0,
-                    stream);
+int matmul_real_by_complex(const void* A, const void* B, void* out, int64_t m, int64_t n, int64_t k, hipStream_t stream) {
+    return gemm(packed(QS_F64, A, B, out, m, 2 * n, k), stream);
 }
 
 // the d contraction: T1[(abc), s] = u[(abc), d] C[d, s]; `in_dtype` is the tensor's type, `dtype` that of C and T1
 static int gemm_d(int in_dtype, int dtype, const void* u, const void* C, void* T1, int64_t rows3, int64_t L, int64_t M,
                   hipStream_t s) {
-    if (in_dtype == dtype) return gemm(dtype, u, C, T1, rows3, M, L, L, M, M, 1, 0, 0, 0, s);
-    return matmul_real_by_complex(u, C, T1, rows3, M, L, L, M, M, s);
+    if (in_dtype == dtype) return gemm(packed(dtype, u, C, T1, rows3, M, L), s);
+    return matmul_real_by_complex(u, C, T1, rows3, M, L, s);
 }
 
 static inline int64_t even_up(int64_t x) { return (x + 1) & ~int64_t(1); }
@@ -197,10 +185,10 @@ static int contract_dcb(int in_dtype, int dtype, const void* u, const void* C, v
         if (rc) return rc;
         rc = gemm_d(in_dtype, dtype, u, C, T1, rows * L * L, L, M, s);
         if (rc) return rc;
-        rc = gemm(dtype, CT, T1, T2, M, M, L, L, M, M, rows * L, 0, L * M, M * M, s);
+        rc = gemm(packed(dtype, CT, T1, T2, M, M, L, rows * L), s);
     }
     if (rc) return rc;
-    return gemm(dtype, Ct, T2, T3, M, M * M, L, L, M * M, M * M, rows, 0, L * M * M, M * M * M, s);
+    return gemm(packed(dtype, Ct, T2, T3, M, M * M, L, rows), s);
 }
 
 }  // namespace qs
@@ -267,7 +255,8 @@ int qs_matmul(int dtype, const void* A, const void* B, void* out, int64_t m, int
               int64_t lda, int64_t ldb, int64_t ldc, int64_t batch, int64_t stride_a,
               int64_t stride_b, int64_t stride_c, int accumulate, void* stream) {
     dispatch_reset();
-    return matmul_checked(dtype, A, B, out, m, n, k, lda, ldb, ldc, batch, stride_a, stride_b, stride_c, accumulate,
+    return matmul_checked(Product{dtype, (const double*)A, (const double*)B, (double*)out, m, n, k, lda, ldb, ldc, batch,
+                                  stride_a, stride_b, stride_c, accumulate},
                           (hipStream_t)stream);
 }
 
@@ -275,15 +264,13 @@ int qs_matmul(int dtype, const void* A, const void* B, void* out, int64_t m, int
 
 namespace qs {
 // qs_matmul without the reset of the dispatch record (entry points that issue several products: qs_comm.hip)
-int matmul_checked(int dtype, const void* A, const void* B, void* out, int64_t m, int64_t n, int64_t k, int64_t lda,
-                   int64_t ldb, int64_t ldc, int64_t batch, int64_t stride_a, int64_t stride_b, int64_t stride_c,
-                   int accumulate, hipStream_t stream) {
-    if (!dtype_ok(dtype)) return QS_ERR_BAD_DTYPE;
-    if (!A || !B || !out) return QS_ERR_NULL_POINTER;
-    const size_t es = elem_size(dtype);
-    if (!aligned(A, es) || !aligned(B, es) || !aligned(out, es)) return QS_ERR_MISALIGNED;
-    if (stride_a < 0 || stride_b < 0 || stride_c < 0) return QS_ERR_BAD_EXTENT;
-    return gemm(dtype, A, B, out, m, n, k, lda, ldb, ldc, batch, stride_a, stride_b, stride_c, stream, accumulate);
+int matmul_checked(const Product& p, hipStream_t stream) {
+    if (!dtype_ok(p.dtype)) return QS_ERR_BAD_DTYPE;
+    if (!p.A || !p.B || !p.C) return QS_ERR_NULL_POINTER;
+    const size_t es = elem_size(p.dtype);
+    if (!aligned(p.A, es) || !aligned(p.B, es) || !aligned(p.C, es)) return QS_ERR_MISALIGNED;
+    if (p.sa < 0 || p.sb < 0 || p.sc < 0) return QS_ERR_BAD_EXTENT;
+    return gemm(p, stream);
 }
 }  // namespace qs
 
@@ -398,9 +385,9 @@ static int transform_two_body_fused(int in_dtype, int dtype, const void* u, cons
                 if (rc2 == 1) {
                     rc2 = transpose_small(dtype, C, CT, L, M, s);
                     if (rc2) return rc2;
-                    rc2 = gemm(dtype, u, C, WB, L * L * L, M, L, L, M, M, 1, 0, 0, 0, s);
+                    rc2 = gemm(packed(dtype, u, C, WB, L * L * L, M, L), s);
                     if (rc2) return rc2;
-                    rc2 = gemm(dtype, CT, WB, WA, M, M, L, L, M, M, L * L, 0, L * M, MM, s);
+                    rc2 = gemm(packed(dtype, CT, WB, WA, M, M, L, L * L), s);
                 }
             }
             if (rc2) return rc2;
@@ -437,7 +424,7 @@ static int transform_two_body_impl(int in_dtype, int dtype, const void* u, const
     if (rc != 1) return rc;
     rc = contract_dcb(in_dtype, dtype, u, C, CT, Ct, /*T1*/ WA, /*T2*/ WB, /*T3*/ WA, L, L, M, s);
     if (rc) return rc;
-    return gemm(dtype, Ct, WA, out, M, M * M * M, L, L, M * M * M, M * M * M, 1, 0, 0, 0, s);
+    return gemm(packed(dtype, Ct, WA, out, M, M * M * M, L), s);
 }
 }  // namespace qs
 
@@ -480,13 +467,13 @@ int qs_transform_two_body_inplace(int dtype, void* u, const void* C, const void*
     //   d: A (L^4) -> B (L^3 M)   c: B -> A (L^2 M^2)   b: A -> B (L M^3)   a: B -> A (M^4)
     int rc = transpose_small(dtype, C, CT, L, M, s);
     if (rc) return rc;
-    rc = gemm(dtype, u, C, B, L * L * L, M, L, L, M, M, 1, 0, 0, 0, s);
+    rc = gemm(packed(dtype, u, C, B, L * L * L, M, L), s);
     if (rc) return rc;
-    rc = gemm(dtype, CT, B, u, M, M, L, L, M, M, L * L, 0, L * M, M * M, s);
+    rc = gemm(packed(dtype, CT, B, u, M, M, L, L * L), s);
     if (rc) return rc;
-    rc = gemm(dtype, Ct, u, B, M, M * M, L, L, M * M, M * M, L, 0, L * M * M, M * M * M, s);
+    rc = gemm(packed(dtype, Ct, u, B, M, M * M, L, L), s);
     if (rc) return rc;
-    return gemm(dtype, Ct, B, u, M, M * M * M, L, L, M * M * M, M * M * M, 1, 0, 0, 0, s);
+    return gemm(packed(dtype, Ct, B, u, M, M * M * M, L), s);
 }
 
 int64_t qs_transform_two_body_partial_workspace(int dtype, int64_t L, int64_t M, int64_t rows) {
@@ -529,10 +516,10 @@ int qs_transform_one_body(int dtype, const void* h, const void* C, const void* C
     if (work_bytes < nmat * L * M * (int64_t)es) return QS_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     // T[(i,a), q] = sum_b h[i][a, b] C[b, q]
-    int rc = gemm(dtype, h, C, work, nmat * L, M, L, L, M, M, 1, 0, 0, 0, s);
+    int rc = gemm(packed(dtype, h, C, work, nmat * L, M, L), s);
     if (rc) return rc;
     // out[i][p, q] = sum_a Ct[p, a] T[i][a, q]
-    return gemm(dtype, Ct, work, out, M, M, L, L, M, M, nmat, 0, L * M, M * M, s);
+    return gemm(packed(dtype, Ct, work, out, M, M, L, nmat), s);
 }
 
 int qs_antisymmetrize(int dtype, const void* u, void* out, int64_t npq, int64_t l, void* stream) {

@@ -393,10 +393,10 @@ int qs_transform_two_body_sharded(void* comm, int dtype, const void* u_bslab, co
         rc = transpose_small(dtype, C, CT, L, M, s);
         if (rc) return rc;
         // d:  T1[(a,b,c), s] = u[(a,b,c), d] C[d, s]
-        rc = matmul_checked(dtype, u_bslab, C, T1, L * bl * L, M, L, L, M, M, 1, 0, 0, 0, 0, s);
+        rc = matmul_checked(packed(dtype, u_bslab, C, T1, L * bl * L, M, L), s);
         if (rc) return rc;
         // c:  T2[(a,b)][r, s] = CT[r, c] T1[(a,b)][c, s]
-        rc = matmul_checked(dtype, CT, T1, T2, M, M, L, L, M, M, L * bl, 0, L * M, MM, 0, s);
+        rc = matmul_checked(packed(dtype, CT, T1, T2, M, M, L, L * bl), s);
         if (rc) return rc;
     }
     // the exchange must not start before earlier work on the caller's stream that R / X might still be read by
@@ -411,16 +411,14 @@ int qs_transform_two_body_sharded(void* comm, int dtype, const void* u_bslab, co
         if (n <= 0) return QS_OK;
         hipError_t ee = dropped(8) ? hipSuccess : hipStreamWaitEvent(s, c->r_ready[k], 0);
         if (ee != hipSuccess) return hip_status(ee, "qs_transform_two_body_sharded: wait for rows");
-        return matmul_checked(dtype, Ct, at(R, lo * L * MM), at(out_pslab, lo * M * MM), M, MM, L, L, MM, MM, n, 0, L * MM,
-                         M * MM, 0, s);
+        return matmul_checked(packed(dtype, Ct, at(R, lo * L * MM), at(out_pslab, lo * M * MM), M, MM, L, n), s);
     };
     int op = 0;
     for (int k = 0; k < nchunks; ++k) {
         const int64_t slot0 = plan.chunk_slot0[k], rows_k = plan.chunk_slot0[k + 1] - slot0;
         // a:  X[slot, (b,r,s)] = CtX[slot, a] T2[a, (b,r,s)]   for the rows of chunk k
         if (bl > 0 && rows_k > 0) {
-            rc = matmul_checked(dtype, at(CtX, slot0 * L), T2, at(X, slot0 * row_x), rows_k, row_x, L, L, row_x, row_x, 1, 0, 0,
-                           0, 0, s);
+            rc = matmul_checked(packed(dtype, at(CtX, slot0 * L), T2, at(X, slot0 * row_x), rows_k, row_x, L), s);
             if (rc) return k ? fail_mid_exchange(c, rc) : rc;
         }
         e = hipEventRecord(c->x_ready[k], s);
@@ -727,14 +725,18 @@ int qs_transform_two_body_sharded_rows(void* comm, int in_dtype, int dtype, cons
         if (n > 0) {
             const void* src = (const char*)rows + (size_t)(i0 * L * L * L) * ies;
             // d:  t1[(i,j,c), s] = rows[(i,j,c), d] C[d, s]        (a real tensor against complex coefficients: the mixed product)
-            rc = in_dtype == dtype ? matmul_checked(dtype, src, C, T1, n * L * L, M, L, L, M, M, 1, 0, 0, 0, 0, s)
-                                   : matmul_real_by_complex(src, C, T1, n * L * L, M, L, L, M, M, s);
+            rc = in_dtype == dtype ? matmul_checked(packed(dtype, src, C, T1, n * L * L, M, L), s)
+                                   : matmul_real_by_complex(src, C, T1, n * L * L, M, L, s);
             if (rc) return fail(rc);
             // c:  t2[(i,j)][r, s] = CT[r, c] t1[(i,j)][c, s]
-            rc = matmul_checked(dtype, CT, T1, T2, M, M, L, L, M, M, n * L, 0, L * M, MM, 0, s);
+            rc = matmul_checked(packed(dtype, CT, T1, T2, M, M, L, n * L), s);
             if (rc) return fail(rc);
-            // J:  W[j', i, (r,s)] = Ct[j', j] t2[i][j, (r,s)]     one product per row i, rows of W n*MM apart
-            rc = matmul_checked(dtype, Ct, T2, W[w], M, MM, L, L, MM, n * MM, n, 0, L * MM, MM, 0, s);
+            // J:  W[j', i, (r,s)] = Ct[j', j] t2[i][j, (r,s)]     one product per row i, rows of W n*MM apart: the packed form
+            // of batch n but for W's row pitch and batch stride
+            Product J = packed(dtype, Ct, T2, W[w], M, MM, L, n);
+            J.ldc = n * MM;
+            J.sc = MM;
+            rc = matmul_checked(J, s);
             if (rc) return fail(rc);
         }
         e = hipEventRecord(c->x_ready[w], s);
@@ -780,8 +782,7 @@ int qs_transform_two_body_sharded_rows(void* comm, int in_dtype, int dtype, cons
     if (e != hipSuccess) return fail(hip_status(e, "qs_transform_two_body_sharded_rows: join"));
     // I:  out[p][i', (r,s)] = Ct[i', i] R[p][i, (r,s)], row by row, packed from the start of the buffer
     for (int64_t p = 0; p < q.jl; ++p) {
-        rc = matmul_checked(dtype, Ct, at(out_buffer, q.r0 + p * L * MM), at(out_buffer, p * M * MM), M, MM, L, L, MM, MM, 1,
-                            0, 0, 0, 0, s);
+        rc = matmul_checked(packed(dtype, Ct, at(out_buffer, q.r0 + p * L * MM), at(out_buffer, p * M * MM), M, MM, L), s);
         if (rc) return rc;
     }
     note_dispatch("rccl grouped send/recv (%lld steps of %lld rows%s)", (long long)nsteps, (long long)ni,

@@ -71,37 +71,51 @@ void note_dispatch(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
 // ceil division for positive operands
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-// Internal launchers (defined in qs_gemm_f64.hip / qs_gemm_c128.hip).
-int gemm_f64(const double* A, const double* B, double* C, int64_t m, int64_t n,
-             int64_t k, int64_t lda, int64_t ldb, int64_t ldc, int64_t batch,
-             int64_t sa, int64_t sb, int64_t sc, int accumulate, hipStream_t stream);
-int gemm_c128(const double* A, const double* B, double* C, int64_t m, int64_t n,
-              int64_t k, int64_t lda, int64_t ldb, int64_t ldc, int64_t batch,
-              int64_t sa, int64_t sb, int64_t sc, int accumulate, hipStream_t stream);
+// One batched product (qs_gemm.hip): C[t] (m x n) = A[t] (m x k) . B[t] (k x n) for t < batch, row-major, leading dimensions
+// and batch strides in elements of `dtype` (a complex128 element is two interleaved doubles); accumulate: C += A.B.
+struct Product {
+    int dtype;
+    const double* A;
+    const double* B;
+    double* C;
+    int64_t m, n, k, lda, ldb, ldc, batch, sa, sb, sc;
+    int accumulate;
+    // which operand is the stream that neighbouring tiles should share in L2: a shared (stride-0) A, or a short-and-wide
+    // product, streams B (the tiled kernels walk the tiles of one B panel first)
+    int group_along_m() const { return ((sa == 0 && batch > 1) || m < n) ? 1 : 0; }
+};
 
-// qs_matmul's body without the reset of the dispatch record (qs_api.hip)
-int matmul_checked(int dtype, const void* A, const void* B, void* out, int64_t m, int64_t n, int64_t k, int64_t lda,
-                   int64_t ldb, int64_t ldc, int64_t batch, int64_t stride_a, int64_t stride_b, int64_t stride_c,
-                   int accumulate, hipStream_t stream);
+// The one layout of the library's contractions: C[t] = A . B[t], A shared, B and C packed.
+inline Product packed(int dtype, const void* A, const void* B, void* C, int64_t m, int64_t n, int64_t k, int64_t batch = 1) {
+    return Product{dtype, (const double*)A, (const double*)B, (double*)C, m, n, k, k, n, n, batch, 0, k * n, m * n, 0};
+}
 
-// A real (m x k, fp64) times B complex (k x n) -> out complex (m x n), row-major, leading dimensions in elements of each
-// operand's own type.  Interleaved complex storage makes this EXACTLY the real product A . [B as k x 2n] -> [out as
-// m x 2n]: the real kernels run it with 2 MFMAs per fragment pair and 8 bytes read per element of A -- no complex copy
-// of A (the d contraction of a real u against complex coefficients, basis_set.py:341-342 with NumPy's promotion).
-int matmul_real_by_complex(const void* A, const void* B, void* out, int64_t m, int64_t n, int64_t k, int64_t lda,
-                           int64_t ldb, int64_t ldc, hipStream_t stream);
+// Validates the extents and strides, then launches the product on the first route that takes it (qs_gemm.hip).
+int gemm(const Product& p, hipStream_t stream);
 
-// VALU-free fast path, exact and edge forms (qs_gemm_fast.hip): QS_OK / error after launching, 1 = not eligible.
-// general_cost: the general kernel's estimated time for this product (its best shape, in this kernel's units): the edge
-// form runs when its own estimate is not worse.
-int gemm_fast_try(int dtype, const double* A, const double* B, double* C, int64_t m, int64_t n,
-                  int64_t k, int64_t lda, int64_t ldb, int64_t ldc, int64_t batch, int64_t sa,
-                  int64_t sb, int64_t sc, int accumulate, int group_along_m, double general_cost, hipStream_t stream);
+// qs_matmul's body without the reset of the dispatch record (qs_api.hip): also checks dtype, pointers and alignment
+int matmul_checked(const Product& p, hipStream_t stream);
 
-// Small-coefficient streaming product, m, k <= 64 (qs_gemm_stream.hip): same return convention.
-int gemm_stream_try(int dtype, const double* A, const double* B, double* C, int64_t m, int64_t n,
-                    int64_t k, int64_t lda, int64_t ldb, int64_t ldc, int64_t batch, int64_t sa,
-                    int64_t sb, int64_t sc, int accumulate, hipStream_t stream);
+// A real (m x k, fp64) times B complex (k x n) -> out complex (m x n), packed row-major.  Interleaved complex storage makes
+// this EXACTLY the real product A . [B as k x 2n] -> [out as m x 2n]: the real kernels run it with 2 MFMAs per fragment
+// pair and 8 bytes read per element of A -- no complex copy of A (the d contraction of a real u against complex
+// coefficients, basis_set.py:341-342 with NumPy's promotion).
+int matmul_real_by_complex(const void* A, const void* B, void* out, int64_t m, int64_t n, int64_t k, hipStream_t stream);
+
+// The product families that gemm() tries before its general tiled kernel: QS_OK / error after launching, 1 = not eligible.
+// They take the product as gemm() validated it.
+// VALU-free fast path, exact and edge forms (qs_gemm_fast.hip).  general_cost: the general kernel's estimated time for
+// this product (its best shape, in this kernel's units): the edge form runs when its own estimate is not worse.
+int gemm_fast_try(const Product& p, double general_cost, hipStream_t stream);
+
+// Small-coefficient streaming product, m, k <= 64 (qs_gemm_stream.hip).
+int gemm_stream_try(const Product& p, hipStream_t stream);
+
+// Strip kernels (qs_gemm_strip.hip); other_cost: the other tiled kernels' best estimate, as general_cost above.
+int gemm_strip_try(const Product& p, double other_cost, hipStream_t stream);
+
+// Short-and-wide streaming product (qs_gemm_skinny.hip).
+int gemm_skinny_try(const Product& p, hipStream_t stream);
 
 // Fused pair of contractions on contiguous L x L slabs, L, M <= 64 (qs_slab_pair.hip): Z[s] = B^T.X[s].B.
 int slab_pair_try(int dtype, const void* X, const void* B, void* Z, int64_t nslabs, int64_t L, int64_t M,
@@ -150,16 +164,6 @@ int quad4s_try(int dtype, const FusedPass& pass, hipStream_t stream);
 int pair4c_try(int dtype, const FusedPass& pass, int tensor_is_b, hipStream_t stream);
 // ... and for REAL items against complex R and Lm (the first pass of a real tensor against complex coefficients), streamed form only
 int pair4m_try(const FusedPass& pass, hipStream_t stream);
-
-// Strip kernels (qs_gemm_strip.hip): same return convention; general_cost as for gemm_fast_try.
-int gemm_strip_try(int dtype, const double* A, const double* B, double* C, int64_t m, int64_t n, int64_t k, int64_t lda,
-                   int64_t ldb, int64_t ldc, int64_t batch, int64_t sa, int64_t sb, int64_t sc, int accumulate,
-                   double general_cost, hipStream_t stream);
-
-// Short-and-wide streaming product (qs_gemm_skinny.hip): same return convention.
-int gemm_skinny_try(int dtype, const double* A, const double* B, double* C, int64_t m, int64_t n,
-                    int64_t k, int64_t lda, int64_t ldb, int64_t ldc, int64_t batch, int accumulate,
-                    hipStream_t stream);
 
 // out (cols, rows) = in (rows, cols)^T, element = 8 or 16 bytes (tiny helper
 // for the coefficient matrices).

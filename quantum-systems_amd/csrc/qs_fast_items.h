@@ -61,6 +61,6 @@ __device__ __forceinline__ unsigned bytes_left(uint64_t end, uint64_t p) {
 // Estimated time of qs_gemm_fast.hip's best form for a product (exact form when every extent is a whole number of tiles,
 // otherwise the best edge-form shape; `even`: 16-byte aligned bases, even strides and extents), in the units of its shape
 // weights: rounds of the tile list over two workgroups per CU x tile area / relative rate.  Host side only.
-double gemm_fast_estimate(int dtype, int64_t m, int64_t n, int64_t k, int64_t batch, bool even);
+double gemm_fast_estimate(const Product& p, bool even);
 
 }  // namespace qs

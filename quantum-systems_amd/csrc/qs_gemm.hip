@@ -33,9 +33,9 @@
 // fp64 MFMA issues one 16x16x4 (2048 flop) per 64 cycles per SIMD:
 // 256 CU x 4 SIMD x 32 flop/clk x 2.4 GHz = 78.6 TFLOP/s peak.
 
-#include <type_traits>
-
+#include <algorithm>
 #include <cmath>
+#include <type_traits>
 
 #include "qs_common.h"
 #include "qs_fast_items.h"
@@ -368,24 +368,6 @@ static int launch_one(GemmArgs g, int64_t batch, hipStream_t stream) {
     return launch_status("gemm launch");
 }
 
-static bool fill_args(GemmArgs& g, const double* A, const double* B, double* C, int64_t m,
-                      int64_t n, int64_t k, int64_t lda, int64_t ldb, int64_t ldc, int64_t batch,
-                      int64_t sa, int64_t sb, int64_t sc, int accumulate) {
-    if (m <= 0 || n <= 0 || k <= 0 || batch <= 0) return false;
-    if (m > INT32_MAX || n > INT32_MAX || k > INT32_MAX) return false;
-    if (lda < k || ldb < n || ldc < n) return false;
-    g.A = A; g.B = B; g.C = C;
-    g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    g.sa = sa; g.sb = sb; g.sc = sc;
-    g.m = (int)m; g.n = (int)n; g.k = (int)k;
-    g.tiles_m = g.tiles_n = 0;
-    g.accumulate = accumulate ? 1 : 0;
-    // Which operand is the stream that neighbouring tiles should share in L2:
-    // a shared (stride-0) A, or a short-and-wide product, streams B.
-    g.group_along_m = ((sa == 0 && batch > 1) || m < n) ? 1 : 0;
-    return true;
-}
-
 // ---------------------------------------------------------------------------
 // Tile-shape choice.  All shapes are 4-wave workgroups (two resident per CU)
 // except the two 8-wave ones kept for tuning.  The automatic choice minimises
@@ -464,34 +446,48 @@ static int dispatch_f64(int cfg, const GemmArgs& g, int64_t batch, hipStream_t s
 #endif
 }
 
-int gemm_f64(const double* A, const double* B, double* C, int64_t m, int64_t n, int64_t k,
-             int64_t lda, int64_t ldb, int64_t ldc, int64_t batch, int64_t sa, int64_t sb,
-             int64_t sc, int accumulate, hipStream_t stream) {
+int gemm(const Product& p, hipStream_t stream) {
+    if (!dtype_ok(p.dtype)) return QS_ERR_BAD_DTYPE;
+    if (p.m <= 0 || p.n <= 0 || p.k <= 0 || p.batch <= 0) return QS_ERR_BAD_EXTENT;
+    if (p.m > INT32_MAX || p.n > INT32_MAX || p.k > INT32_MAX) return QS_ERR_BAD_EXTENT;
+    if (p.lda < p.k || p.ldb < p.n || p.ldc < p.n) return QS_ERR_BAD_EXTENT;
+    const bool cx = p.dtype == QS_C128;
+    const int64_t m = p.m, n = p.n, batch = p.batch;
     GemmArgs g;
-    if (!fill_args(g, A, B, C, m, n, k, lda, ldb, ldc, batch, sa, sb, sc, accumulate))
-        return QS_ERR_BAD_EXTENT;
-    // 16-byte loads need even extents/strides and 16-byte aligned bases.
-    const bool vec = aligned(A, 16) && aligned(B, 16) && !(lda & 1) && !(ldb & 1) && !(k & 1) &&
-                     !(n & 1) && !(sa & 1) && !(sb & 1);
-    int cfg = g_tune.gemm_f64_cfg;
+    g.A = p.A; g.B = p.B; g.C = p.C;
+    g.lda = p.lda; g.ldb = p.ldb; g.ldc = p.ldc;
+    g.sa = p.sa; g.sb = p.sb; g.sc = p.sc;
+    g.m = (int)m; g.n = (int)n; g.k = (int)p.k;
+    g.tiles_m = g.tiles_n = 0;
+    g.group_along_m = p.group_along_m();
+    g.accumulate = p.accumulate ? 1 : 0;
+    // fp64: 16-byte loads need even extents/strides and 16-byte aligned bases (complex elements are 16 bytes by themselves)
+    const bool vec = !cx && aligned(p.A, 16) && aligned(p.B, 16) && !(p.lda & 1) && !(p.ldb & 1) && !(p.k & 1) &&
+                     !(n & 1) && !(p.sa & 1) && !(p.sb & 1);
+    int cfg = cx ? g_tune.gemm_c128_cfg : g_tune.gemm_f64_cfg;      // a forced shape skips every other route
     if (cfg == 0) {
-        int rc = gemm_skinny_try(QS_F64, A, B, C, m, n, k, lda, ldb, ldc, batch, accumulate, stream);
+        int rc = gemm_skinny_try(p, stream);
         if (rc != 1) return rc;
-        rc = gemm_stream_try(QS_F64, A, B, C, m, n, k, lda, ldb, ldc, batch, sa, sb, sc, accumulate, stream);
+        rc = gemm_stream_try(p, stream);
         if (rc != 1) return rc;
-        static const TileShape cand[] = {
+        static const TileShape f64_cand[] = {
             {1, 128, 128, 1.00}, {12, 96, 128, 0.98}, {13, 128, 96, 0.98}, {8, 96, 96, 0.96},
             {5, 64, 64, 0.95},   {9, 128, 64, 0.90},  {10, 64, 128, 0.90}, {11, 32, 32, 0.73},
         };
+        static const TileShape c128_cand[] = {
+            {1, 64, 128, 1.00}, {2, 128, 64, 1.00}, {6, 64, 64, 1.00}, {9, 96, 96, 0.97},
+            {7, 96, 64, 0.95},  {8, 64, 96, 0.95},  {4, 32, 32, 0.94},
+        };
         double cost = 0.0;
-        cfg = pick_shape(cand, sizeof(cand) / sizeof(cand[0]), m, n, batch, &cost);
-        // Fitted shapes (see dispatch_f64): a basis size between 65 and 256 as m or as n.  Measured (same-box sweep with the
-        // shapes forced, profiles/r03_mid_size_shapes.txt): on their plain schedule they reach ~0.7 of the VALU-free kernel's
-        // rate -- they pay where everything is on 8-byte staging anyway (odd basis sizes) and the tile they save is large:
-        // l = 65 +14 %, 97 +12 %, 105 +11 %, 129 +4 %; with 16-byte staging available the other kernels win.
+        cfg = cx ? pick_shape(c128_cand, sizeof(c128_cand) / sizeof(c128_cand[0]), m, n, batch, &cost)
+                 : pick_shape(f64_cand, sizeof(f64_cand) / sizeof(f64_cand[0]), m, n, batch, &cost);
+        // Fitted shapes, fp64 only (see dispatch_f64): a basis size between 65 and 256 as m or as n.  Measured (same-box sweep
+        // with the shapes forced, profiles/r03_mid_size_shapes.txt): on their plain schedule they reach ~0.7 of the VALU-free
+        // kernel's rate -- they pay where everything is on 8-byte staging anyway (odd basis sizes) and the tile they save is
+        // large: l = 65 +14 %, 97 +12 %, 105 +11 %, 129 +4 %; with 16-byte staging available the other kernels win.
         int fit_cfg = 0;
-        if (!vec) cost /= kScalarStagingRate;
-        if (g_tune.gemm_fit == 2 || (g_tune.gemm_fit == 1 && !vec)) {
+        if (!cx && !vec) cost /= kScalarStagingRate;
+        if (!cx && (g_tune.gemm_fit == 2 || (g_tune.gemm_fit == 1 && !vec))) {
             const int tm = (int)cdiv(m, 16), tn = (int)cdiv(n, 16);
             TileShape fit[2];
             int nfit = 0;
@@ -507,15 +503,14 @@ int gemm_f64(const double* A, const double* B, double* C, int64_t m, int64_t n, 
         }
         if (g_tune.gemm_strip == 2 || g_tune.gemm_fast == 1) {
             // strip kernels (qs_gemm_strip.hip): the small extent of the product covered by one tile to the next multiple of 16
-            // (not when a tuning key forces one of the other tiled kernels)
-            const bool even = vec && aligned(C, 16) && !(ldc & 1) && !(sc & 1);
-            const double fast = gemm_fast_estimate(QS_F64, m, n, k, batch, even);
-            const double gen = cost / kGeneralRelativeRate;
-            rc = gemm_strip_try(QS_F64, A, B, C, m, n, k, lda, ldb, ldc, batch, sa, sb, sc, accumulate, fast < gen ? fast : gen, stream);
+            // (not when a tuning key forces one of the other tiled kernels).  fp64 compares with the general kernel's cost in
+            // the fast kernel's units; complex128 takes its cost as it stands and a 16-byte layout for granted.
+            const bool even = cx || (vec && aligned(p.C, 16) && !(p.ldc & 1) && !(p.sc & 1));
+            const double other = cx ? cost : cost / kGeneralRelativeRate;
+            rc = gemm_strip_try(p, std::min(gemm_fast_estimate(p, even), other), stream);
             if (rc != 1) return rc;
         }
-        rc = gemm_fast_try(QS_F64, A, B, C, m, n, k, lda, ldb, ldc, batch, sa, sb, sc,
-                           accumulate, g.group_along_m, g_tune.gemm_fit == 2 && fit_cfg ? 0.0 : cost / kGeneralRelativeRate, stream);
+        rc = gemm_fast_try(p, cx || (g_tune.gemm_fit == 2 && fit_cfg) ? 0.0 : cost / kGeneralRelativeRate, stream);
         if (rc != 1) return rc;
         if (fit_cfg) {
             // 16-byte staging only for an even tile count; an odd one takes the 8-byte form whatever the alignment
@@ -524,38 +519,7 @@ int gemm_f64(const double* A, const double* B, double* C, int64_t m, int64_t n, 
                                  : dispatch_f64<MODE_F64_SCALAR>(fit_cfg, g, batch, stream);
         }
     }
-    return vec ? dispatch_f64<MODE_F64_VEC2>(cfg, g, batch, stream)
-               : dispatch_f64<MODE_F64_SCALAR>(cfg, g, batch, stream);
-}
-
-int gemm_c128(const double* A, const double* B, double* C, int64_t m, int64_t n, int64_t k,
-              int64_t lda, int64_t ldb, int64_t ldc, int64_t batch, int64_t sa, int64_t sb,
-              int64_t sc, int accumulate, hipStream_t stream) {
-    GemmArgs g;
-    if (!fill_args(g, A, B, C, m, n, k, lda, ldb, ldc, batch, sa, sb, sc, accumulate))
-        return QS_ERR_BAD_EXTENT;
-    int cfg = g_tune.gemm_c128_cfg;
-    if (cfg == 0) {
-        int rc = gemm_skinny_try(QS_C128, A, B, C, m, n, k, lda, ldb, ldc, batch, accumulate, stream);
-        if (rc != 1) return rc;
-        rc = gemm_stream_try(QS_C128, A, B, C, m, n, k, lda, ldb, ldc, batch, sa, sb, sc, accumulate, stream);
-        if (rc != 1) return rc;
-        static const TileShape cand[] = {
-            {1, 64, 128, 1.00}, {2, 128, 64, 1.00}, {6, 64, 64, 1.00}, {9, 96, 96, 0.97},
-            {7, 96, 64, 0.95},  {8, 64, 96, 0.95},  {4, 32, 32, 0.94},
-        };
-        double cost = 0.0;
-        cfg = pick_shape(cand, sizeof(cand) / sizeof(cand[0]), m, n, batch, &cost);
-        if (g_tune.gemm_strip == 2 || g_tune.gemm_fast == 1) {
-            // strip kernels (qs_gemm_strip.hip), complex form: a basis of up to 128 orbitals covered by one tile to the next multiple of 16
-            const double fast = gemm_fast_estimate(QS_C128, m, n, k, batch, true);
-            rc = gemm_strip_try(QS_C128, A, B, C, m, n, k, lda, ldb, ldc, batch, sa, sb, sc, accumulate, fast < cost ? fast : cost, stream);
-            if (rc != 1) return rc;
-        }
-        rc = gemm_fast_try(QS_C128, A, B, C, m, n, k, lda, ldb, ldc, batch, sa, sb, sc,
-                           accumulate, g.group_along_m, 0.0, stream);
-        if (rc != 1) return rc;
-    }
+    if (!cx) return vec ? dispatch_f64<MODE_F64_VEC2>(cfg, g, batch, stream) : dispatch_f64<MODE_F64_SCALAR>(cfg, g, batch, stream);
     switch (cfg) {
         case 1: return launch_one<2, 2, 2, 4, 8, MODE_C128>(g, batch, stream);   //  64 x 128
         case 2: return launch_one<2, 2, 4, 2, 8, MODE_C128>(g, batch, stream);   // 128 x  64

@@ -537,29 +537,27 @@ void gemm_fast_kernel(const FastArgs g) {
 
 
 template <bool CX, int TM, int TN, bool VEC, bool EDGE>
-static int launch_fast(const double* A, const double* B, double* C, int64_t m, int64_t n, int64_t k,
-                       int64_t lda, int64_t ldb, int64_t ldc, int64_t batch, int64_t sa, int64_t sb,
-                       int64_t sc, int accumulate, int group_along_m, hipStream_t stream) {
+static int launch_fast(const Product& p, hipStream_t stream) {
     constexpr int KT = CX ? 8 : 16;
     constexpr int NP = CX ? 2 : 1;
     constexpr int BM = 32 * TM, BN = 32 * TN;
     constexpr int64_t ESZ = CX ? 16 : 8;
     constexpr int IPR_B = BN / ((!CX && VEC) ? 2 : 1);
     // a wave-instruction of the B loads spans 64 / IPR_B rows through its 32-bit lane offset
-    if (IPR_B < 64 && (64 / IPR_B) * ldb * ESZ + 4096 >= (int64_t(1) << 32)) return 1;
+    if (IPR_B < 64 && (64 / IPR_B) * p.ldb * ESZ + 4096 >= (int64_t(1) << 32)) return 1;
     FastArgs g;
-    g.A = A; g.B = B; g.C = C;
-    g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    g.sa = sa; g.sb = sb; g.sc = sc;
-    g.a_end = reinterpret_cast<uint64_t>(A) + (uint64_t)(((batch - 1) * sa + (m - 1) * lda + k) * ESZ);
-    g.b_end = reinterpret_cast<uint64_t>(B) + (uint64_t)(((batch - 1) * sb + (k - 1) * ldb + n) * ESZ);
-    g.m = m; g.n = (int)n; g.k = (int)k;
-    g.nk = (int)cdiv(k, KT);
-    g.tiles_m = (int)cdiv(m, BM);
-    g.tiles_n = (int)cdiv(n, BN);
-    g.group_along_m = group_along_m;
-    g.accumulate = accumulate ? 1 : 0;
-    const int64_t total = (int64_t)g.tiles_m * g.tiles_n * batch;
+    g.A = p.A; g.B = p.B; g.C = p.C;
+    g.lda = p.lda; g.ldb = p.ldb; g.ldc = p.ldc;
+    g.sa = p.sa; g.sb = p.sb; g.sc = p.sc;
+    g.a_end = reinterpret_cast<uint64_t>(p.A) + (uint64_t)(((p.batch - 1) * p.sa + (p.m - 1) * p.lda + p.k) * ESZ);
+    g.b_end = reinterpret_cast<uint64_t>(p.B) + (uint64_t)(((p.batch - 1) * p.sb + (p.k - 1) * p.ldb + p.n) * ESZ);
+    g.m = p.m; g.n = (int)p.n; g.k = (int)p.k;
+    g.nk = (int)cdiv(p.k, KT);
+    g.tiles_m = (int)cdiv(p.m, BM);
+    g.tiles_n = (int)cdiv(p.n, BN);
+    g.group_along_m = p.group_along_m();
+    g.accumulate = p.accumulate ? 1 : 0;
+    const int64_t total = (int64_t)g.tiles_m * g.tiles_n * p.batch;
     if (total <= 0 || total >= (int64_t(1) << 31)) return QS_ERR_BAD_EXTENT;
     g.total = (unsigned)total;
     // two persistent workgroups per CU (the LDS and register budget admits exactly two)
@@ -630,9 +628,10 @@ int pick_fast_shape(const FastShape (&cand)[N], int64_t m, int64_t n, int64_t ba
 }
 }  // namespace
 
-double gemm_fast_estimate(int dtype, int64_t m, int64_t n, int64_t k, int64_t batch, bool even) {
+double gemm_fast_estimate(const Product& p, bool even) {
     if (!g_tune.gemm_fast) return 1e300;
-    const bool cx = dtype == QS_C128;
+    const bool cx = p.dtype == QS_C128;
+    const int64_t m = p.m, n = p.n, k = p.k, batch = p.batch;
     const double slots = 2.0 * device_cu_count();
     auto whole = [&](int bm, int bn, double w) {
         const double tiles = (double)(m / bm) * (double)(n / bn) * (double)batch;
@@ -656,38 +655,50 @@ double gemm_fast_estimate(int dtype, int64_t m, int64_t n, int64_t k, int64_t ba
     return cost;
 }
 
+// fp64 edge form, shape id of kF64Shapes
+template <bool VEC>
+static int launch_edge_f64(int shape, const Product& p, hipStream_t stream) {
+    switch (shape) {
+        case 1: return launch_fast<false, 4, 4, VEC, true>(p, stream);
+        case 2: return launch_fast<false, 2, 4, VEC, true>(p, stream);
+        case 3: return launch_fast<false, 4, 2, VEC, true>(p, stream);
+        case 5: return launch_fast<false, 3, 4, VEC, true>(p, stream);
+        case 6: return launch_fast<false, 5, 2, VEC, true>(p, stream);
+        case 7: return launch_fast<false, 6, 2, VEC, true>(p, stream);
+        case 8: return launch_fast<false, 7, 2, VEC, true>(p, stream);
+        case 9: return launch_fast<false, 3, 2, VEC, true>(p, stream);
+        default: return launch_fast<false, 2, 2, VEC, true>(p, stream);
+    }
+}
+
 // Returns QS_OK after launching, or 1 when the product does not qualify
 // (caller falls back to the general kernel).
-int gemm_fast_try(int dtype, const double* A, const double* B, double* C, int64_t m, int64_t n,
-                  int64_t k, int64_t lda, int64_t ldb, int64_t ldc, int64_t batch, int64_t sa,
-                  int64_t sb, int64_t sc, int accumulate, int group_along_m, double general_cost, hipStream_t stream) {
+int gemm_fast_try(const Product& p, double general_cost, hipStream_t stream) {
     if (!g_tune.gemm_fast) return 1;
-    const bool cx = dtype == QS_C128;
+    const bool cx = p.dtype == QS_C128;
     const int64_t esz = cx ? 16 : 8;
-    if (cx && (!aligned(A, 16) || !aligned(B, 16) || !aligned(C, 16))) return 1;
+    const int64_t m = p.m, n = p.n, k = p.k;
+    if (cx && (!aligned(p.A, 16) || !aligned(p.B, 16) || !aligned(p.C, 16))) return 1;
     // the lane offsets of the loads are 32-bit: one item step of rows must fit
-    if (32 * lda * esz + 256 >= (int64_t(1) << 32)) return 1;
+    if (32 * p.lda * esz + 256 >= (int64_t(1) << 32)) return 1;
     if (m >= (int64_t(1) << 31) - 256 || n >= (int64_t(1) << 31) - 256 || k >= (int64_t(1) << 31) - 256) return 1;
     // 16-byte accesses: aligned bases, even strides (complex elements are 16 bytes by themselves)
     // gfx950 carries out 16-byte buffer loads and global stores at ANY 8-byte-aligned address (tools/probe_unaligned.hip), so odd
     // strides and extents -- every odd basis size -- stage with 16-byte items too (g_tune.gemm_fast_unaligned = 0: 8-byte items
     // there, the rule of rounds 1-3); LDS accesses stay 16-byte aligned (the stage layout does not depend on the strides).
-    const bool even = aligned(A, 16) && aligned(B, 16) && aligned(C, 16) && !(lda & 1) && !(ldb & 1) &&
-                      !(ldc & 1) && !(sa & 1) && !(sb & 1) && !(sc & 1) && !(n & 1);
+    const bool even = aligned(p.A, 16) && aligned(p.B, 16) && aligned(p.C, 16) && !(p.lda & 1) && !(p.ldb & 1) &&
+                      !(p.ldc & 1) && !(p.sa & 1) && !(p.sb & 1) && !(p.sc & 1) && !(n & 1);
     const bool vec = cx || even || g_tune.gemm_fast_unaligned != 0;
-#define QS_FAST(CXF, TMF, TNF, VECF, EDGEF)                                                          \
-    return launch_fast<CXF, TMF, TNF, VECF, EDGEF>(A, B, C, m, n, k, lda, ldb, ldc, batch, sa, sb, sc, \
-                                                    accumulate, group_along_m, stream)
     // ---- exact form: every extent a whole number of tiles
     if (!cx && vec && k % 16 == 0) {
-        if (m % 128 == 0 && n % 128 == 0) QS_FAST(false, 4, 4, true, false);
-        if (m % 64 == 0 && n % 128 == 0) QS_FAST(false, 2, 4, true, false);
+        if (m % 128 == 0 && n % 128 == 0) return launch_fast<false, 4, 4, true, false>(p, stream);
+        if (m % 64 == 0 && n % 128 == 0) return launch_fast<false, 2, 4, true, false>(p, stream);
     }
     if (cx && k % 8 == 0) {
-        if (m >= n && m % 128 == 0 && n % 64 == 0) QS_FAST(true, 4, 2, true, false);
-        if (m % 64 == 0 && n % 128 == 0) QS_FAST(true, 2, 4, true, false);
-        if (m % 128 == 0 && n % 64 == 0) QS_FAST(true, 4, 2, true, false);
-        if (m % 64 == 0 && n % 64 == 0) QS_FAST(true, 2, 2, true, false);
+        if (m >= n && m % 128 == 0 && n % 64 == 0) return launch_fast<true, 4, 2, true, false>(p, stream);
+        if (m % 64 == 0 && n % 128 == 0) return launch_fast<true, 2, 4, true, false>(p, stream);
+        if (m % 128 == 0 && n % 64 == 0) return launch_fast<true, 4, 2, true, false>(p, stream);
+        if (m % 64 == 0 && n % 64 == 0) return launch_fast<true, 2, 2, true, false>(p, stream);
     }
     // ---- edge form.  Round 1 measured it against the general kernel with the four shapes of that time: +3...9 % for fp64
     // products whose m and n are both >= 100, slower below (short tile lists: the general kernel's small and 96-wide shapes
@@ -698,41 +709,17 @@ int gemm_fast_try(int dtype, const double* A, const double* B, double* C, int64_
     if (g_tune.gemm_fast != 1 && g_tune.gemm_fast != 3) return 1;
     if (cx) {
         if (g_tune.gemm_fast == 1) return 1;
-        switch (pick_fast_shape(kC128Shapes, m, n, batch, nullptr)) {
-            case 1: QS_FAST(true, 4, 2, true, true);
-            case 2: QS_FAST(true, 2, 4, true, true);
-            default: QS_FAST(true, 2, 2, true, true);
+        switch (pick_fast_shape(kC128Shapes, m, n, p.batch, nullptr)) {
+            case 1: return launch_fast<true, 4, 2, true, true>(p, stream);
+            case 2: return launch_fast<true, 2, 4, true, true>(p, stream);
+            default: return launch_fast<true, 2, 2, true, true>(p, stream);
         }
     }
     double cost = 0.0;
-    const int shape = pick_fast_shape(kF64Shapes, m, n, batch, &cost);
+    const int shape = pick_fast_shape(kF64Shapes, m, n, p.batch, &cost);
     if (!vec) cost /= 0.85;                 // 8-byte staging (l = 255 against 256: 52.9 / 67.3 TFLOP/s with the K tail and the padding taken out)
     if (g_tune.gemm_fast == 1 && !(cost <= general_cost)) return 1;
-    if (vec) {
-        switch (shape) {
-            case 1: QS_FAST(false, 4, 4, true, true);
-            case 2: QS_FAST(false, 2, 4, true, true);
-            case 3: QS_FAST(false, 4, 2, true, true);
-            case 5: QS_FAST(false, 3, 4, true, true);
-            case 6: QS_FAST(false, 5, 2, true, true);
-            case 7: QS_FAST(false, 6, 2, true, true);
-            case 8: QS_FAST(false, 7, 2, true, true);
-            case 9: QS_FAST(false, 3, 2, true, true);
-            default: QS_FAST(false, 2, 2, true, true);
-        }
-    }
-    switch (shape) {
-        case 1: QS_FAST(false, 4, 4, false, true);
-        case 2: QS_FAST(false, 2, 4, false, true);
-        case 3: QS_FAST(false, 4, 2, false, true);
-        case 5: QS_FAST(false, 3, 4, false, true);
-        case 6: QS_FAST(false, 5, 2, false, true);
-        case 7: QS_FAST(false, 6, 2, false, true);
-        case 8: QS_FAST(false, 7, 2, false, true);
-        case 9: QS_FAST(false, 3, 2, false, true);
-        default: QS_FAST(false, 2, 2, false, true);
-    }
-#undef QS_FAST
+    return vec ? launch_edge_f64<true>(shape, p, stream) : launch_edge_f64<false>(shape, p, stream);
 }
 
 }  // namespace qs

@@ -155,18 +155,17 @@ void gemm_skinny_kernel(const SkinnyArgs g) {
 }
 
 template <bool CX, int TMS>
-static int launch_skinny(const double* A, const double* B, double* C, int64_t n, int64_t k,
-                         int64_t lda, int64_t ldb, int64_t ldc, hipStream_t stream) {
+static int launch_skinny(const Product& p, hipStream_t stream) {
     constexpr int NP = CX ? 2 : 1;
     constexpr int M = 16 * TMS;
     constexpr int WGSTRIP = 4 * (CX ? 32 : 64);
     SkinnyArgs g;
-    g.A = A; g.B = B; g.C = C;
-    g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    g.k = (int)k; g.n = n;
-    const int64_t nwg = n / WGSTRIP;
+    g.A = p.A; g.B = p.B; g.C = p.C;
+    g.lda = p.lda; g.ldb = p.ldb; g.ldc = p.ldc;
+    g.k = (int)p.k; g.n = p.n;
+    const int64_t nwg = p.n / WGSTRIP;
     if (nwg <= 0 || nwg >= (int64_t(1) << 31)) return QS_ERR_BAD_EXTENT;
-    const size_t lds = sizeof(double) * NP * M * (k + 2);
+    const size_t lds = sizeof(double) * NP * M * (p.k + 2);
     auto kern = gemm_skinny_kernel<CX, TMS>;
     static PerDeviceLds lds_opt_in;
     if (int rc = opt_in_dynamic_lds((const void*)kern, lds, lds_opt_in, "hipFuncSetAttribute(gemm_skinny)")) return rc;
@@ -177,29 +176,24 @@ static int launch_skinny(const double* A, const double* B, double* C, int64_t n,
 
 
 // QS_OK / error after launching, 1 = not eligible (caller falls back).
-int gemm_skinny_try(int dtype, const double* A, const double* B, double* C, int64_t m, int64_t n,
-                    int64_t k, int64_t lda, int64_t ldb, int64_t ldc, int64_t batch, int accumulate,
-                    hipStream_t stream) {
-    if (!g_tune.gemm_skinny || batch != 1 || accumulate) return 1;
-    const bool cx = dtype == QS_C128;
+int gemm_skinny_try(const Product& p, hipStream_t stream) {
+    if (!g_tune.gemm_skinny || p.batch != 1 || p.accumulate) return 1;
+    const bool cx = p.dtype == QS_C128;
+    const int64_t m = p.m, n = p.n, k = p.k;
     // m = 64 is MFMA-bound (16 flop/B) and runs better on the tiled kernel (9.8 vs 15.3 ms at
     // l = 256); the streaming form is used where the product is HBM-bound: m <= 32 rows
-    if (m > 32 || (m & 15) || (k & 3) || k < 4) return 1;
+    if (m > 32 || (m & 15) || (k & 3)) return 1;
     if (n < (int64_t(1) << 16)) return 1;                       // only worth it for a long stream
     if (n % (cx ? 128 : 256)) return 1;
-    if (!aligned(B, 16) || !aligned(C, 16) || !aligned(A, cx ? 16 : 8)) return 1;
-    if (!cx && ((ldb & 1) || (ldc & 1))) return 1;
+    if (!aligned(p.B, 16) || !aligned(p.C, 16) || !aligned(p.A, cx ? 16 : 8)) return 1;
+    if (!cx && ((p.ldb & 1) || (p.ldc & 1))) return 1;
     const int64_t lds = (cx ? 16 : 8) * m * (k + 2);
     if (lds > 150 * 1024) return 1;
     switch (m / 16) {
-        case 1: return cx ? launch_skinny<true, 1>(A, B, C, n, k, lda, ldb, ldc, stream)
-                          : launch_skinny<false, 1>(A, B, C, n, k, lda, ldb, ldc, stream);
-        case 2: return cx ? launch_skinny<true, 2>(A, B, C, n, k, lda, ldb, ldc, stream)
-                          : launch_skinny<false, 2>(A, B, C, n, k, lda, ldb, ldc, stream);
-        case 3: return cx ? launch_skinny<true, 3>(A, B, C, n, k, lda, ldb, ldc, stream)
-                          : launch_skinny<false, 3>(A, B, C, n, k, lda, ldb, ldc, stream);
-        case 4: return cx ? launch_skinny<true, 4>(A, B, C, n, k, lda, ldb, ldc, stream)
-                          : launch_skinny<false, 4>(A, B, C, n, k, lda, ldb, ldc, stream);
+        case 1: return cx ? launch_skinny<true, 1>(p, stream) : launch_skinny<false, 1>(p, stream);
+        case 2: return cx ? launch_skinny<true, 2>(p, stream) : launch_skinny<false, 2>(p, stream);
+        case 3: return cx ? launch_skinny<true, 3>(p, stream) : launch_skinny<false, 3>(p, stream);
+        case 4: return cx ? launch_skinny<true, 4>(p, stream) : launch_skinny<false, 4>(p, stream);
         default: return 1;
     }
 }

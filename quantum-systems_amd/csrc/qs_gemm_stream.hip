@@ -371,17 +371,15 @@ static int launch_stream_cx(const StreamArgs& g0, int64_t batch, hipStream_t str
 }
 
 // QS_OK / error after launching, 1 = not eligible (caller falls back).
-int gemm_stream_try(int dtype, const double* A, const double* B, double* C, int64_t m, int64_t n,
-                    int64_t k, int64_t lda, int64_t ldb, int64_t ldc, int64_t batch, int64_t sa,
-                    int64_t sb, int64_t sc, int accumulate, hipStream_t stream) {
-    if (!g_tune.gemm_stream || accumulate) return 1;
-    if (dtype != QS_F64 && dtype != QS_C128) return 1;
-    const bool cx = dtype == QS_C128;
+int gemm_stream_try(const Product& p, hipStream_t stream) {
+    if (!g_tune.gemm_stream || p.accumulate) return 1;
+    const bool cx = p.dtype == QS_C128;
     const int64_t esz = cx ? 16 : 8;
-    if (m > 64 || k > 64 || m < 1 || k < 1) return 1;
-    if (batch > 1 && sa != 0) return 1;                  // A is the shared coefficient matrix
-    if (ldb < n || ldc < n) return 1;                    // the range checks assume rows do not overlap
-    // 32-bit offsets inside a batch slice, with the "column >= n" marker bit free
+    const int64_t m = p.m, n = p.n, k = p.k, ldb = p.ldb, ldc = p.ldc, batch = p.batch;
+    if (m > 64 || k > 64) return 1;
+    if (batch > 1 && p.sa != 0) return 1;                // A is the shared coefficient matrix
+    // 32-bit offsets inside a batch slice, with the "column >= n" marker bit free (the range checks also rely on
+    // ldb, ldc >= n: rows do not overlap)
     if (((k + 3) * ldb + n) * esz >= (int64_t(1) << 31) || ((m + 63) * ldc + n) * esz >= (int64_t(1) << 31)) return 1;
     if (batch >= (int64_t(1) << 30)) return 1;
     // a stream long enough to keep every wave busy for a few blocks.  Measured against the tiled kernels
@@ -392,15 +390,15 @@ int gemm_stream_try(int dtype, const double* A, const double* B, double* C, int6
     // whole-tile fp64 products (l = 64) run faster on the exact form of the tiled kernel (42.7 vs 41.3 TFLOP/s)
     if (!cx && m % 64 == 0 && n % 128 == 0 && k % 16 == 0) return 1;
     StreamArgs g;
-    g.A = A; g.B = B; g.C = C;
-    g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    g.sb = sb; g.sc = sc;
+    g.A = p.A; g.B = p.B; g.C = p.C;
+    g.lda = p.lda; g.ldb = ldb; g.ldc = ldc;
+    g.sb = p.sb; g.sc = p.sc;
     g.m = (int)m; g.k = (int)k; g.n = (int)n;
     g.blocks_per_batch = 0;
     g.total_blocks = 0;
     const int tm = (int)cdiv(m, 16), kq = (int)cdiv(k, 16);
     if (cx) {
-        if (!aligned(A, 16) || !aligned(B, 16) || !aligned(C, 16)) return 1;
+        if (!aligned(p.A, 16) || !aligned(p.B, 16) || !aligned(p.C, 16)) return 1;
 #define QS_STREAM_CX(TMWV, SPLITV)                                              \
         switch (kq) {                                                           \
             case 1: return launch_stream_cx<TMWV, SPLITV, 1>(g, batch, stream); \
@@ -413,8 +411,8 @@ int gemm_stream_try(int dtype, const double* A, const double* B, double* C, int6
         QS_STREAM_CX(2, 2)
 #undef QS_STREAM_CX
     }
-    const bool vec = aligned(B, 16) && aligned(C, 16) && !(ldb & 1) && !(ldc & 1) && !(sb & 1) &&
-                     !(sc & 1) && !(n & 1);
+    const bool vec = aligned(p.B, 16) && aligned(p.C, 16) && !(ldb & 1) && !(ldc & 1) && !(p.sb & 1) &&
+                     !(p.sc & 1) && !(n & 1);
     const bool split = tm > 2 && g_tune.gemm_stream != 2;
 #define QS_STREAM_KQ(TMWV, SPLITV)                                                                         \
     switch (kq) {                                                                                          \

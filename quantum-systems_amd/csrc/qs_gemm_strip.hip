@@ -579,26 +579,29 @@ int launch_strip_t(bool cx, int t, bool wide, const StripArgs& g, hipStream_t st
 // QS_OK after launching, 1 = not eligible / not the cheapest (the caller goes on to the other kernels).
 // other_cost: the best estimate of the other tiled kernels for this product, in the units of qs_gemm_fast.hip (tiles x tile
 // area / relative rate over two workgroups per CU).
-int gemm_strip_try(int dtype, const double* A, const double* B, double* C, int64_t m, int64_t n, int64_t k, int64_t lda,
-                   int64_t ldb, int64_t ldc, int64_t batch, int64_t sa, int64_t sb, int64_t sc, int accumulate,
-                   double other_cost, hipStream_t stream) {
-    if (!g_tune.gemm_strip || accumulate) return 1;
-    if (m <= 0 || n <= 0 || k <= 0 || batch <= 0 || k >= (int64_t(1) << 30)) return 1;
-    const bool cx = dtype == QS_C128;
+int gemm_strip_try(const Product& p, double other_cost, hipStream_t stream) {
+    if (!g_tune.gemm_strip || p.accumulate) return 1;
+    if (p.k >= (int64_t(1) << 30)) return 1;
+    const bool cx = p.dtype == QS_C128;
     const int64_t esz = cx ? 16 : 8;
-    static const int max_t_env = [] { const char* e = getenv("QS_STRIP_MAXT"); return e ? atoi(e) : 0; }();      // (tuning runs)
+    const int64_t m = p.m, n = p.n, k = p.k, lda = p.lda, ldb = p.ldb, ldc = p.ldc, batch = p.batch;
+#ifdef QS_STRIP_TUNING_ENV      // development: tuning runs set the tile height limit / the wide form (read once)
+    static const int max_t_env = [] { const char* e = getenv("QS_STRIP_MAXT"); return e ? atoi(e) : 0; }();
+#else
+    constexpr int max_t_env = 0;
+#endif
     const int max_t = (max_t_env > 0 && !cx) ? max_t_env : (cx ? kMaxTComplex : kMaxT);
     const int max_small = 16 * max_t * kMaxSmallTiles;
-    if (cx && (!aligned(A, 16) || !aligned(B, 16) || !aligned(C, 16))) return 1;
+    if (cx && (!aligned(p.A, 16) || !aligned(p.B, 16) || !aligned(p.C, 16))) return 1;
     // which extent is the small one: A shared by the batch and m small -> tall tiles over virtual columns; otherwise one
     // product with n small -> wide tiles over the rows
     int form;
-    if ((batch == 1 || sa == 0) && m <= max_small && (batch > 1 || n >= m)) form = 0;
+    if ((batch == 1 || p.sa == 0) && m <= max_small && (batch > 1 || n >= m)) form = 0;
     else if (batch == 1 && n <= max_small) form = 1;
     else return 1;
-    if (batch == 1) { sb = 0; sc = 0; }
+    const int64_t sb = batch == 1 ? 0 : p.sb, sc = batch == 1 ? 0 : p.sc;
     StripArgs g;
-    g.A = A; g.B = B; g.C = C;
+    g.A = p.A; g.B = p.B; g.C = p.C;
     g.lda = lda; g.ldb = ldb; g.ldc = ldc;
     g.sb = sb; g.sc = sc;
     g.k = (int)k; g.nk = (int)cdiv(k, cx ? 8 : 16);
@@ -607,7 +610,7 @@ int gemm_strip_try(int dtype, const double* A, const double* B, double* C, int64
         // Lane offsets are 32-bit and unsigned: a tile's columns reach at most 256 / n + 1 segments past its first one.  (Columns
         // past the last one of the last tile compute offsets of their own -- whatever they address is either inside the
         // operand or cut off by the range check of the buffer descriptor, and they are never stored.)
-        if (sb < 0 || sc < 0 || lda < k || ldb < n || ldc < n) return 1;
+        if (sb < 0 || sc < 0) return 1;
         if (((256 / n + 2) * sb + n) * esz >= (int64_t(1) << 32) - 65536 || 64 * lda * esz >= (int64_t(1) << 31)) return 1;
         if (((256 / n + 2) * sc + n + 4 * ldc) * esz >= (int64_t(1) << 31)) return 1;      // store offsets stay below the descriptor's range
         g.W = n; g.Wp = cx ? n : n + (n & 1);
@@ -615,7 +618,6 @@ int gemm_strip_try(int dtype, const double* A, const double* B, double* C, int64
         g.big = g.Wp * batch; g.small = (int)m;
         t = (int)cdiv(m, 16);
     } else {
-        if (lda < k || ldb < n || ldc < n) return 1;
         if (64 * lda * esz >= (int64_t(1) << 31) || 16 * ldb * esz + 4096 >= (int64_t(1) << 30) || 4 * ldc * esz + 8192 >= (int64_t(1) << 31)) return 1;
         g.big = m; g.W = g.Wp = 0; g.small = (int)n;
         t = (int)cdiv(n, 16);
@@ -627,14 +629,16 @@ int gemm_strip_try(int dtype, const double* A, const double* B, double* C, int64
     // (176 = 11 and 208 = 13 blocks would pad to 12 / 14: -5 % / -3.5 %; profiles/r04_strip_ablation.txt)
     if (!cx && max_t_env <= 0 && g.nsmall == 1 && t >= 12 && t % 2 == 0) g.nsmall = 2;
     t = (int)cdiv(t, g.nsmall);
-    g.a_end = reinterpret_cast<uint64_t>(A) + (uint64_t)(((m - 1) * lda + k) * esz);
-    g.b_end = reinterpret_cast<uint64_t>(B) + (uint64_t)(((batch - 1) * sb + (k - 1) * ldb + n) * esz);
-    g.c_end = reinterpret_cast<uint64_t>(C) + (uint64_t)(((batch - 1) * sc + (m - 1) * ldc + n) * esz);
+    g.a_end = reinterpret_cast<uint64_t>(p.A) + (uint64_t)(((m - 1) * lda + k) * esz);
+    g.b_end = reinterpret_cast<uint64_t>(p.B) + (uint64_t)(((batch - 1) * sb + (k - 1) * ldb + n) * esz);
+    g.c_end = reinterpret_cast<uint64_t>(p.C) + (uint64_t)(((batch - 1) * sc + (m - 1) * ldc + n) * esz);
     // wide tiles (256 of the big extent) where the accumulators fit and the list still fills the chip a few times over
     const double slots = device_cu_count();
-    static const int wide_env = [] { const char* e = getenv("QS_STRIP_WIDE"); return e ? atoi(e) : -1; }();      // (tuning runs)
     bool wide = !cx && t <= kWideMaxT && cdiv(g.big, 256) >= 4 * (int64_t)slots;
+#ifdef QS_STRIP_TUNING_ENV
+    static const int wide_env = [] { const char* e = getenv("QS_STRIP_WIDE"); return e ? atoi(e) : -1; }();
     if (wide_env >= 0) wide = !cx && wide_env != 0 && t <= kWideMaxT;
+#endif
     const int64_t tiles = cdiv(g.big, wide ? 256 : 128) * g.nsmall;
     if (g_tune.gemm_strip == 1 && t * g.nsmall < 3) return 1;      // (up to 32 rows / columns: the other kernels' ground, not measured here)
     if (g_tune.gemm_strip == 1) {

@@ -791,6 +791,76 @@ def test_edge_form_with_16_byte_items_at_odd_strides_is_bit_identical(K, m, n, k
         K.tuning_reset()
 
 
+# Strided and offset operands through every product route that takes them: bases one element past an allocation, odd
+# leading dimensions, ldc > n, odd batch strides; the padding of C (columns n ... ldc, the gaps between batch slices, the
+# element before the base) holds a sentinel that must survive.  Each case: (dtype, m, n, k, batch, shared A, lda - k,
+# ldb - n, ldc - n, element offsets of A / B / C, odd batch strides, tuning, route, route with accumulate).  A route that
+# refuses accumulate, or the layout, hands over to the one named instead.
+_STRIDED = {
+    "strip_f64": (torch.float64, 70, 45, 37, 3, True, 2, 2, 3, (1, 1, 1), True, dict(gemm_strip=2, gemm_fast=0),
+                  "qs::gemm_strip_kernel<false,", "qs::gemm_kernel<"),
+    "strip_c128": (torch.complex128, 40, 33, 21, 3, True, 2, 2, 3, (1, 1, 1), True, dict(gemm_strip=2, gemm_fast=0),
+                   "qs::gemm_strip_kernel<true,", "qs::gemm_kernel<"),
+    "fast_edge_f64": (torch.float64, 100, 75, 29, 2, False, 2, 2, 3, (1, 1, 1), True, dict(gemm_strip=0, gemm_fast=3),
+                      "qs::gemm_fast_kernel<false,", "qs::gemm_fast_kernel<false,"),
+    "fast_edge_c128": (torch.complex128, 70, 50, 13, 2, False, 2, 3, 2, (1, 1, 1), True, dict(gemm_strip=0, gemm_fast=3),
+                       "qs::gemm_fast_kernel<true,", "qs::gemm_fast_kernel<true,"),
+    # (the exact form: whole tiles, even leading dimensions beyond the extents)
+    "fast_exact_f64": (torch.float64, 128, 128, 32, 2, False, 2, 2, 4, (0, 0, 0), False, dict(gemm_strip=0),
+                       "qs::gemm_fast_kernel<false, 4, 4, true, false>", "qs::gemm_fast_kernel<false, 4, 4, true, false>"),
+    "stream_f64": (torch.float64, 20, 4001, 13, 9, True, 2, 2, 5, (1, 1, 1), True, dict(gemm_strip=0, gemm_fast=0),
+                   "qs::gemm_stream_left_kernel<", "qs::gemm_kernel<"),
+    "stream_c128": (torch.complex128, 24, 8193, 9, 8, True, 2, 2, 3, (1, 1, 1), True, dict(gemm_strip=0, gemm_fast=0),
+                    "qs::gemm_stream_left_cx_kernel<", "qs::gemm_kernel<"),
+    # (skinny takes an offset A, odd lda and ldc > n; B and C must be 16-byte aligned with even ldb / ldc, else stream runs)
+    "skinny_f64": (torch.float64, 32, 65536, 8, 1, True, 1, 2, 4, (1, 0, 0), False, dict(gemm_strip=0, gemm_fast=0),
+                   "qs::gemm_skinny_kernel<false, 2>", "qs::gemm_kernel<"),
+    "skinny_refused_f64": (torch.float64, 32, 65536, 8, 1, True, 1, 2, 4, (1, 1, 1), False, dict(gemm_strip=0, gemm_fast=0),
+                           "qs::gemm_stream_left_kernel<", "qs::gemm_kernel<"),
+    "general_f64": (torch.float64, 70, 45, 37, 3, False, 2, 2, 3, (1, 1, 1), True, dict(gemm_strip=0, gemm_fast=0),
+                    "qs::gemm_kernel<", "qs::gemm_kernel<"),
+    "general_c128": (torch.complex128, 40, 33, 21, 3, False, 2, 2, 3, (1, 1, 1), True, dict(gemm_strip=0, gemm_fast=0),
+                     "qs::gemm_kernel<", "qs::gemm_kernel<"),
+}
+
+
+@pytest.mark.parametrize("accumulate", [False, True])
+@pytest.mark.parametrize("case", sorted(_STRIDED))
+def test_products_on_strided_offset_operands(K, case, accumulate):
+    dt, m, n, k, batch, shared_a, pa, pb, pc, (a_off, b_off, c_off), odd, knobs, route, route_acc = _STRIDED[case]
+    lda, ldb, ldc = k + pa, n + pb, n + pc
+    step = (lambda x: x | 1) if odd else (lambda x: x + (x & 1))     # batch strides: odd, or even, and >= one slice
+    sa = 0 if shared_a else step(m * lda + 1)
+    sb, sc = step(k * ldb + 1), step(m * ldc + 1)
+    na = 1 if shared_a else batch
+    g = torch.Generator().manual_seed(sum(map(ord, case)))
+
+    def buffer(off, views, stride, rows, cols, ld, fill):
+        # storage of `views` matrices rows x cols (ld apart, `stride` between matrices, from element `off`), random inside,
+        # `fill` everywhere else, and 64 elements of slack
+        buf = torch.full((off + (views - 1) * stride + (rows - 1) * ld + cols + 64,), fill, dtype=dt)
+        view = buf.as_strided((views, rows, cols), (stride, ld, 1), off)
+        view.copy_(torch.randn(views, rows, cols, dtype=dt, generator=g))
+        return buf, view
+
+    A, Av = buffer(a_off, na, sa, m, k, lda, 750.0)
+    B, Bv = buffer(b_off, batch, sb, k, n, ldb, 750.0)
+    C, Cv = buffer(c_off, batch, sc, m, n, ldc, -3.25)
+    ref = Av @ Bv + (Cv if accumulate else 0)
+    dC = C.cuda()
+    with K.tuning(**knobs):
+        K.gemm_raw(dt, A.cuda(), B.cuda(), dC, m, n, k, lda, ldb, ldc, batch, sa, sb, sc, accumulate, a_off, b_off, c_off)
+        ran = K.last_dispatch()
+    assert ran.startswith(route_acc if accumulate else route), (case, ran)
+    got = dC.cpu()
+    err = (got.as_strided(Cv.shape, Cv.stride(), c_off) - ref).abs().max().item()
+    assert err <= 1e-13 * max(1.0, ref.abs().max().item()) * k ** 0.5, (case, ran, err)
+    # nothing outside the result moved
+    mask = torch.ones(C.numel(), dtype=torch.bool)
+    mask.as_strided(Cv.shape, Cv.stride(), c_off).fill_(False)
+    assert torch.equal(got[mask], C[mask]), (case, ran)
+
+
 def test_edge_form_keeps_non_finite_values_in_their_rows(K):
     # the K tail is removed with selects, not by multiplying with zero: a NaN/Inf in one row of A
     # (or one column of B) must not reach any other row (column) of the product
