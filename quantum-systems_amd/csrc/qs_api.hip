@@ -121,21 +121,12 @@ int matmul_real_by_complex(const void* A, const void* B, void* out, int64_t m, i
     return gemm(packed(QS_F64, A, B, out, m, 2 * n, k), stream);
 }
 
-// the d contraction: T1[(abc), s] = u[(abc), d] C[d, s]; `in_dtype` is the tensor's type, `dtype` that of C and T1
-static int gemm_d(int in_dtype, int dtype, const void* u, const void* C, void* T1, int64_t rows3, int64_t L, int64_t M,
-                  hipStream_t s) {
+int gemm_d(int in_dtype, int dtype, const void* u, const void* C, void* T1, int64_t rows3, int64_t L, int64_t M, hipStream_t s) {
     if (in_dtype == dtype) return gemm(packed(dtype, u, C, T1, rows3, M, L), s);
     return matmul_real_by_complex(u, C, T1, rows3, M, L, s);
 }
 
 static inline int64_t even_up(int64_t x) { return (x + 1) & ~int64_t(1); }
-
-// Extents for which every product keeps its n and grid inside 32 bits.
-static bool extents_ok(int64_t L, int64_t M) {
-    if (L <= 0 || M <= 0) return false;
-    if (L > 4096 || M > 1024) return false;   // M^3 < 2^31 needs M <= 1290
-    return true;
-}
 
 static inline char* at(void* base, int64_t elems, size_t es) { return (char*)base + (size_t)elems * es; }
 
@@ -255,26 +246,15 @@ int qs_matmul(int dtype, const void* A, const void* B, void* out, int64_t m, int
               int64_t lda, int64_t ldb, int64_t ldc, int64_t batch, int64_t stride_a,
               int64_t stride_b, int64_t stride_c, int accumulate, void* stream) {
     dispatch_reset();
-    return matmul_checked(Product{dtype, (const double*)A, (const double*)B, (double*)out, m, n, k, lda, ldb, ldc, batch,
-                                  stride_a, stride_b, stride_c, accumulate},
-                          (hipStream_t)stream);
+    if (!dtype_ok(dtype)) return QS_ERR_BAD_DTYPE;
+    if (!A || !B || !out) return QS_ERR_NULL_POINTER;
+    const size_t es = elem_size(dtype);
+    if (!aligned(A, es) || !aligned(B, es) || !aligned(out, es)) return QS_ERR_MISALIGNED;
+    if (stride_a < 0 || stride_b < 0 || stride_c < 0) return QS_ERR_BAD_EXTENT;
+    return gemm(Product{dtype, (const double*)A, (const double*)B, (double*)out, m, n, k, lda, ldb, ldc, batch,
+                        stride_a, stride_b, stride_c, accumulate},
+                (hipStream_t)stream);
 }
-
-}  // extern "C"
-
-namespace qs {
-// qs_matmul without the reset of the dispatch record (entry points that issue several products: qs_comm.hip)
-int matmul_checked(const Product& p, hipStream_t stream) {
-    if (!dtype_ok(p.dtype)) return QS_ERR_BAD_DTYPE;
-    if (!p.A || !p.B || !p.C) return QS_ERR_NULL_POINTER;
-    const size_t es = elem_size(p.dtype);
-    if (!aligned(p.A, es) || !aligned(p.B, es) || !aligned(p.C, es)) return QS_ERR_MISALIGNED;
-    if (p.sa < 0 || p.sb < 0 || p.sc < 0) return QS_ERR_BAD_EXTENT;
-    return gemm(p, stream);
-}
-}  // namespace qs
-
-extern "C" {
 
 int64_t qs_transform_two_body_workspace(int dtype, int64_t L, int64_t M) {
     if (!dtype_ok(dtype)) return QS_ERR_BAD_DTYPE;

@@ -68,6 +68,11 @@ int resident_workgroups(const void* kern, PerDeviceInt& cache, int fallback);
 void dispatch_reset();
 void note_dispatch(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
 
+// Extents of a transform (L orbitals to M) for which every product keeps its n and grid inside 32 bits.
+inline bool extents_ok(int64_t L, int64_t M) {
+    return L > 0 && M > 0 && L <= 4096 && M <= 1024;      // M^3 < 2^31 needs M <= 1290
+}
+
 // ceil division for positive operands
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
@@ -93,14 +98,15 @@ inline Product packed(int dtype, const void* A, const void* B, void* C, int64_t 
 // Validates the extents and strides, then launches the product on the first route that takes it (qs_gemm.hip).
 int gemm(const Product& p, hipStream_t stream);
 
-// qs_matmul's body without the reset of the dispatch record (qs_api.hip): also checks dtype, pointers and alignment
-int matmul_checked(const Product& p, hipStream_t stream);
-
 // A real (m x k, fp64) times B complex (k x n) -> out complex (m x n), packed row-major.  Interleaved complex storage makes
 // this EXACTLY the real product A . [B as k x 2n] -> [out as m x 2n]: the real kernels run it with 2 MFMAs per fragment
 // pair and 8 bytes read per element of A -- no complex copy of A (the d contraction of a real u against complex
 // coefficients, basis_set.py:341-342 with NumPy's promotion).
 int matmul_real_by_complex(const void* A, const void* B, void* out, int64_t m, int64_t n, int64_t k, hipStream_t stream);
+
+// The d contraction T1[(abc), s] = u[(abc), d] C[d, s]: `in_dtype` is the tensor's type, `dtype` that of C and T1; the plain
+// product, or the mixed one above for a real tensor against complex coefficients (qs_api.hip).
+int gemm_d(int in_dtype, int dtype, const void* u, const void* C, void* T1, int64_t rows3, int64_t L, int64_t M, hipStream_t s);
 
 // The product families that gemm() tries before its general tiled kernel: QS_OK / error after launching, 1 = not eligible.
 // They take the product as gemm() validated it.
