@@ -10,6 +10,7 @@ import torch
 
 from . import _lib
 from ._lib import QS_C128, QS_F64, check
+from .partition import SlabPartition
 
 _F64 = torch.float64
 _C128 = torch.complex128
@@ -673,12 +674,8 @@ class RcclComm:
             if (in_part.n, in_part.world) != (L, self.world):
                 raise ValueError("the input partition does not describe L rows over this communicator's ranks")
             starts = (ctypes.c_int64 * (self.world + 1))(*in_part.starts)
-            il = in_part.count(self.rank)
-        else:
-            base, extra = divmod(L, self.world)
-            il = base + (1 if self.rank < extra else 0)
-        base, extra = divmod(M, self.world)
-        jl = base + (1 if self.rank < extra else 0)
+        il = (in_part or SlabPartition(L, self.world)).count(self.rank)
+        jl = SlabPartition(M, self.world).count(self.rank)
         if tuple(rows.shape) != (il, L, L, L) or tuple(Ct.shape) != (M, L):
             raise ValueError(f"rank {self.rank}: expected rows of shape {(il, L, L, L)} and C_tilde {(M, L)}")
         p_starts = ctypes.cast(starts, ctypes.c_void_p) if starts is not None else None
@@ -715,10 +712,7 @@ class RcclComm:
         u_bslab, C, Ct = _dev(u_bslab, dt), _dev(C, dt), _dev(C_tilde, dt)
         L, M = C.shape
         code = dtype_code(dt)
-        base, extra = divmod(M, self.world)
-        pc = base + (1 if self.rank < extra else 0)
-        base, extra = divmod(L, self.world)
-        bl = base + (1 if self.rank < extra else 0)
+        pc, bl = SlabPartition(M, self.world).count(self.rank), SlabPartition(L, self.world).count(self.rank)
         if tuple(u_bslab.shape) != (L, bl, L, L) or tuple(Ct.shape) != (M, L):
             raise ValueError(f"rank {self.rank}: expected a slab of shape {(L, bl, L, L)} and C_tilde {(M, L)}")
         if out is None:

@@ -3,72 +3,62 @@
 over xGMI; ``gloo`` in the CPU tests).
 
 The reference has no parallelism at all; this layer exists so the
-same ``transform_two_body_elements`` call scales past one device.  Two layouts,
-both producing the result sharded over its LEADING index ``p``
-(``out[p_lo:p_hi, :, :, :]`` on each rank, contiguous):
+same ``transform_two_body_elements`` call scales past one device.  A tensor is
+split over ONE of its two leading indices (``SlabPartition``).  Five layouts of
+the transform; ``rows`` is the one the package itself uses, the others are
+bench modes and cross-checks:
 
+``transform_two_body_rows``
+    in: rows of one leading index (either one, any partition); out: rows of the
+    OTHER transformed leading index (balanced).  Streamed: one asynchronous
+    all-to-all per step of ``chunk_rows`` input rows, hidden under the next
+    step's products; everything but the input and result rows is O(l^3).
+    Used by ``ShardedDeviceModule`` (``sharded_basis.transform_two_body``);
+    ``kernels.RcclComm.transform_two_body_rows`` is the same algorithm as one
+    C-ABI call.
 ``transform_two_body_replicated``
-    ``u`` is resident on every rank (l=256 fp64: 34 GB of 288 GB).  Rank g
-    contracts ``a`` first with its rows of ``Ct`` and then d, c, b on its own
-    slab.  No collective on the data path; 8 l^5 / G flops per rank.
-    ``all_gather_slabs`` replicates the p-sharded result when a caller wants
-    the whole tensor everywhere (the single all-gather of the north star).
-
+    in: ``u`` whole on every rank (l=256 fp64: 34 GB of 288 GB); out: rows
+    ``out[p_lo:p_hi]``.  Rank g contracts ``a`` first with its rows of ``Ct``,
+    then d, c, b on its slab.  No collective; 8 l^5 / G flops per rank.
+    ``all_gather_slabs`` replicates the result when a caller wants it whole
+    (one all-gather, or one broadcast per rank for uneven slabs).  Bench mode.
 ``transform_two_body_sharded``
-    ``u`` is sharded over its SECOND index (``u[:, b_lo:b_hi]``), so it never
-    has to fit on one device (l=512 complex128 = 1.1 TB).  d, c and a are
-    contracted locally -- ``a`` is fully local in this layout -- then ONE
-    all-to-all re-shards ``[p, b_loc] -> [p_loc, b]`` (per-rank traffic
-    (G-1)/G^2 * l^4 elements, G times less than an all-gather of the
-    intermediate) and the contraction over b closes on the received slabs.
+    in: ``u[:, b_lo:b_hi]`` (second index), so ``u`` never has to fit one
+    device; out: ``out[p_lo:p_hi]`` (balanced).  d, c and a are contracted
+    locally, ONE all-to-all re-shards ``[p, b_loc] -> [p_loc, b]`` (per-rank
+    traffic (G-1)/G^2 * l^4 elements), the contraction over b closes on the
+    received slabs.  Bench mode, cross-check of the other layouts.
+``transform_two_body_sharded_a``
+    the mirror image: in ``u[a_lo:a_hi]`` (leading index), out
+    ``out[:, q_lo:q_hi]``; d, c, b on the slab, ONE all-to-all, a closes.
+    Cross-check of ``rows`` (tests/_rows_worker.py).
+``transform_two_body_sharded_inplace``
+    in / out as ``transform_two_body_sharded``, square and divisible sizes
+    only, everything inside the output buffer; ONE exchange step of equal
+    slots, issued as ``ceil(pc / staging_rows)`` all-to-alls through a staging
+    buffer.  Bench mode (superseded by ``rows``).
 
-The contraction order differs from the reference's d, c, b, a only in where the
-``a`` sum sits; every element is still the same four sums, and parity is
-checked to the same 1e-10 bound.
+The contraction orders differ from the reference's d, c, b, a only in where the
+sums over the two leading indices sit; every element is still the same four
+sums, and parity is checked to the same 1e-10 bound.
 
-All arithmetic goes through an *engine* with two methods (``matmul`` and
-``partial``).  The only engine in the package is the HIP one below; the CPU
-tests inject their own (oracle-backed) engine to exercise partitioning and the
-exchange under ``gloo`` with world_size 2.
+What the layouts share is written once: ``post_exchange`` / ``unpack_exchange``
+(the variable-split all-to-all, complex values travelling as float64 pairs) and
+``close_over_slabs`` (the contraction over the index that was sharded).  The
+first consumers of a sharded ``u`` -- Fock matrix and reference energy, for
+either sharded index -- follow at the end.
+
+All arithmetic goes through an *engine* (``matmul``, ``partial``,
+``gemm_strided`` and the slab-local operations of a sharded ``BasisSet``).  The
+only engine in the package is the HIP one below; the CPU tests inject their own
+(oracle-backed) engine to exercise partitioning and the exchange under ``gloo``.
 """
 
 import torch
 import torch.distributed as dist
 
 from . import kernels
-
-
-class SlabPartition:
-    """Contiguous split of ``n`` rows over ``world`` ranks: balanced by default, or the explicit
-    ``starts`` (world + 1 non-decreasing offsets from 0 to n) -- spin doubling turns the balanced split of
-    l spatial rows into twice those offsets, which is not the balanced split of 2l when l % world != 0."""
-
-    def __init__(self, n, world, starts=None):
-        if world < 1 or n < 1:
-            raise ValueError("need n >= 1 and world >= 1")
-        self.n, self.world = int(n), int(world)
-        if starts is None:
-            base, extra = divmod(self.n, self.world)
-            self.starts = [r * base + min(r, extra) for r in range(self.world + 1)]
-        else:
-            self.starts = [int(x) for x in starts]
-            if (len(self.starts) != self.world + 1 or self.starts[0] != 0 or self.starts[-1] != self.n
-                    or any(b < a for a, b in zip(self.starts, self.starts[1:]))):
-                raise ValueError(f"bad partition {self.starts} of {self.n} rows over {self.world} ranks")
-
-    def bounds(self, rank):
-        return self.starts[rank], self.starts[rank + 1]
-
-    def count(self, rank):
-        lo, hi = self.bounds(rank)
-        return hi - lo
-
-    def doubled(self):
-        """The partition of the 2n spin rows P = 2p + sigma that keeps every rank's rows together."""
-        return SlabPartition(2 * self.n, self.world, [2 * x for x in self.starts])
-
-    def is_balanced(self):
-        return self.starts == SlabPartition(self.n, self.world).starts
+from .partition import SlabPartition  # noqa: F401  (re-exported: ``sharded.SlabPartition``)
 
 
 class HipEngine:
@@ -133,12 +123,55 @@ def transform_two_body_replicated(u, C, C_tilde=None, rank=0, world=1, engine=Hi
     return engine.partial(w.reshape(hi - lo, L, L, L), C, Ct)  # (p_loc, q, r, s)
 
 
-def _as_real_flat(t):
+def real_words(dtype):
+    """float64 words per element: the collectives carry complex values as interleaved pairs."""
+    return 2 if dtype.is_complex else 1
+
+
+def as_real_flat(t):
     """1-D float64 view for the collectives (complex -> interleaved pairs)."""
     t = t.contiguous()
     if t.is_complex():
         t = torch.view_as_real(t)
     return t.reshape(-1)
+
+
+def post_exchange(send, send_counts, recv_counts, group=None, recv=None, async_op=False):
+    """The variable-split all-to-all of a typed buffer: ``send_counts[g]`` ELEMENTS of ``send`` (consecutive blocks)
+    go to rank g, ``recv_counts[g]`` arrive from it.  Returns the float64 receive buffer -- the front of ``recv``
+    when the caller supplies its staging, else allocated here -- and the handle of the collective (``async_op``;
+    ``send`` must then outlive it).  ``unpack_exchange`` gives the blocks their type back."""
+    width = real_words(send.dtype)
+    flat = as_real_flat(send)
+    n = sum(recv_counts) * width
+    recv = torch.empty(n, dtype=torch.float64, device=flat.device) if recv is None else recv[:n]
+    work = dist.all_to_all_single(recv, flat, [c * width for c in recv_counts], [c * width for c in send_counts],
+                                  group=group, async_op=async_op)
+    return recv, work
+
+
+def unpack_exchange(recv, recv_counts, dtype):
+    """The receive buffer of ``post_exchange`` as one flat block of ``dtype`` per source rank (views)."""
+    width = real_words(dtype)
+    blocks, off = [], 0
+    for c in recv_counts:
+        blk = recv[off: off + c * width]
+        off += c * width
+        blocks.append(torch.view_as_complex(blk.reshape(-1, 2)) if width == 2 else blk)
+    return blocks
+
+
+def close_over_slabs(engine, Ct, part, blocks, out):
+    """``out = sum_g Ct[:, slab(g)] blocks[g]``: the contraction over the index that was sharded by ``part``, one
+    accumulating product per source rank with a non-empty slab."""
+    first = True
+    for g in range(part.world):
+        lo, hi = part.bounds(g)
+        if hi == lo:
+            continue
+        engine.matmul(Ct[:, lo:hi].contiguous(), blocks[g], out=out, accumulate=not first)
+        first = False
+    return out
 
 
 def all_gather_slabs(out_slab, M, rank, world, group=None, full=None, part=None):
@@ -150,11 +183,11 @@ def all_gather_slabs(out_slab, M, rank, world, group=None, full=None, part=None)
     if world == 1:
         return out_slab
     per_row = M * M * M
-    width = 2 if out_slab.is_complex() else 1
+    width = real_words(out_slab.dtype)
     if full is None:
         full = torch.empty((M, M, M, M), dtype=out_slab.dtype, device=out_slab.device)
-    full_flat = _as_real_flat(full)  # view of `full`
-    flat = _as_real_flat(out_slab)
+    full_flat = as_real_flat(full)  # view of `full`
+    flat = as_real_flat(out_slab)
     if M % world == 0 and part.is_balanced():
         dist.all_gather_into_tensor(full_flat, flat, group=group)
         return full
@@ -188,7 +221,6 @@ def transform_two_body_sharded(u_bslab, C, C_tilde=None, rank=0, world=1, group=
         raise ValueError(f"rank {rank}: slab shape {tuple(u_bslab.shape)}, expected {(L, bl, L, L)}")
     dt = kernels.result_dtype(u_bslab, C, Ct)
     u_bslab, C, Ct = u_bslab.to(dt), C.to(dt), Ct.to(dt)
-    width = 2 if dt.is_complex else 1
     p_lo, p_hi = ppart.bounds(rank)
     pc = p_hi - p_lo
 
@@ -210,32 +242,16 @@ def transform_two_body_sharded(u_bslab, C, C_tilde=None, rank=0, world=1, group=
     else:
         # one all-to-all: rows p of X go to the owner of p; we receive, from every
         # source g, the block [p_loc, b in slab(g), (r,s)]
-        send = _as_real_flat(x)
-        in_splits = [ppart.count(g) * bl * M * M * width for g in range(world)]
-        out_splits = [pc * bpart.count(g) * M * M * width for g in range(world)]
-        recv = torch.empty(sum(out_splits), dtype=torch.float64, device=send.device)
-        dist.all_to_all_single(recv, send, out_splits, in_splits, group=group)
-        del x, send
-        recv_blocks, off = [], 0
-        for g in range(world):
-            blk = recv[off: off + out_splits[g]]
-            off += out_splits[g]
-            if width == 2:
-                blk = torch.view_as_complex(blk.reshape(-1, 2))
-            recv_blocks.append(blk.reshape(pc, bpart.count(g), M * M))
+        counts = [pc * bpart.count(g) * M * M for g in range(world)]
+        recv, _ = post_exchange(x, [ppart.count(g) * bl * M * M for g in range(world)], counts, group)
+        del x
+        recv_blocks = [blk.reshape(pc, bpart.count(g), M * M) for g, blk in enumerate(unpack_exchange(recv, counts, dt))]
 
     # b:  out[p][q, (r,s)] = sum_g Ct[q, b in slab(g)] R_g[p][b, (r,s)]
     out = torch.empty((pc, M, M * M), dtype=dt, device=u_bslab.device)
     if pc == 0:
         return out.reshape(0, M, M, M)
-    first = True
-    for g in range(world):
-        g_lo, g_hi = bpart.bounds(g)
-        if g_hi == g_lo:
-            continue
-        engine.matmul(Ct[:, g_lo:g_hi].contiguous(), recv_blocks[g], out=out, accumulate=not first)
-        first = False
-    return out.reshape(pc, M, M, M)
+    return close_over_slabs(engine, Ct, bpart, recv_blocks, out).reshape(pc, M, M, M)
 
 
 def transform_two_body_sharded_a(u_aslab, C, C_tilde=None, rank=0, world=1, group=None,
@@ -259,7 +275,6 @@ def transform_two_body_sharded_a(u_aslab, C, C_tilde=None, rank=0, world=1, grou
         raise ValueError(f"rank {rank}: slab shape {tuple(u_aslab.shape)}, expected {(al, L, L, L)}")
     dt = kernels.result_dtype(u_aslab, C, Ct)
     u_aslab, C, Ct = u_aslab.to(dt), C.to(dt), Ct.to(dt)
-    width = 2 if dt.is_complex else 1
     q_lo, q_hi = qpart.bounds(rank)
     ql = q_hi - q_lo
     MM = M * M
@@ -273,33 +288,16 @@ def transform_two_body_sharded_a(u_aslab, C, C_tilde=None, rank=0, world=1, grou
         # one all-to-all: columns q of v go to the owner of q.  Packed per destination g as
         # [a_loc][q in slab(g)][(r, s)]; from source g we receive [a in slab(g)][q_loc][(r, s)]
         send = torch.cat([v[:, qpart.bounds(g)[0]:qpart.bounds(g)[1]].reshape(-1) for g in range(world)])
-        send = _as_real_flat(send)
-        in_splits = [al * qpart.count(g) * MM * width for g in range(world)]
-        out_splits = [apart.count(g) * ql * MM * width for g in range(world)]
-        recv = torch.empty(sum(out_splits), dtype=torch.float64, device=send.device)
-        del v
-        dist.all_to_all_single(recv, send, out_splits, in_splits, group=group)
-        del send
-        recv_blocks, off = [], 0
-        for g in range(world):
-            blk = recv[off: off + out_splits[g]]
-            off += out_splits[g]
-            if width == 2:
-                blk = torch.view_as_complex(blk.reshape(-1, 2))
-            recv_blocks.append(blk.reshape(apart.count(g), ql * MM))
+        counts = [apart.count(g) * ql * MM for g in range(world)]
+        recv, _ = post_exchange(send, [al * qpart.count(g) * MM for g in range(world)], counts, group)
+        del v, send
+        recv_blocks = [blk.reshape(apart.count(g), ql * MM) for g, blk in enumerate(unpack_exchange(recv, counts, dt))]
 
     # a:  out[p, (q_loc, r, s)] = sum_g Ct[p, a in slab(g)] R_g[a, (q_loc, r, s)]
     out = torch.empty((M, ql * MM), dtype=dt, device=u_aslab.device)
     if ql == 0:
         return out.reshape(M, 0, M, M)
-    first = True
-    for g in range(world):
-        g_lo, g_hi = apart.bounds(g)
-        if g_hi == g_lo:
-            continue
-        engine.matmul(Ct[:, g_lo:g_hi].contiguous(), recv_blocks[g], out=out, accumulate=not first)
-        first = False
-    return out.reshape(M, ql, M, M)
+    return close_over_slabs(engine, Ct, apart, recv_blocks, out).reshape(M, ql, M, M)
 
 
 def transform_two_body_sharded_inplace(u_bslab, C, C_tilde=None, rank=0, world=1, group=None,
@@ -375,9 +373,8 @@ def transform_two_body_sharded_inplace(u_bslab, C, C_tilde=None, rank=0, world=1
     # ---- 2. exchange in place: slot (p', g) <-> what peer g holds for our row p'
     x = buf[1:]                                   # (pc, L, L, L) = [p'][g][b][(r, s)]
     if world > 1:
-        width = 2 if dt.is_complex else 1
-        blk = bl * L2 * width                     # float64 words per slot
-        slots = _as_real_flat(x).reshape(pc, world, blk)          # view
+        blk = bl * L2 * real_words(dt)            # float64 words per slot
+        slots = as_real_flat(x).reshape(pc, world, blk)          # view
         rows = max(1, min(int(staging_rows), pc))
         send = torch.empty((world, rows, blk), dtype=torch.float64, device=dev)
         recv = torch.empty_like(send)
@@ -466,8 +463,7 @@ def transform_two_body_rows(rows, C, C_tilde=None, rank=0, world=1, group=None, 
     CT = C.transpose(0, 1).contiguous()
     dev = rows.device
     MM = M * M
-    width = 2 if dt.is_complex else 1
-    es = 16 if dt.is_complex else 8
+    width = real_words(dt)
     nbuf = rows_buffer_elems(L, M, jl)
     if out is None:
         buf = torch.empty(nbuf, dtype=dt, device=dev)
@@ -478,7 +474,7 @@ def transform_two_body_rows(rows, C, C_tilde=None, rank=0, world=1, group=None, 
     r0 = jl * max(M - L, 0) * MM + L * MM                  # element offset of received row 0
     R = buf[r0: r0 + jl * L * MM].view(jl, L, MM)
     il_max = max(ipart.count(g) for g in range(world))
-    ni = stream_chunk_rows(L, M, il_max, es) if chunk_rows is None else max(1, min(int(chunk_rows), il_max))
+    ni = stream_chunk_rows(L, M, il_max, 8 * width) if chunk_rows is None else max(1, min(int(chunk_rows), il_max))
     nsteps = -(-il_max // ni)
     t1 = torch.empty(ni * L * L * M, dtype=dt, device=dev)
     t2 = torch.empty(ni * L * MM, dtype=dt, device=dev)
@@ -494,17 +490,12 @@ def transform_two_body_rows(rows, C, C_tilde=None, rank=0, world=1, group=None, 
 
     def settle(pending):
         """The received blocks of an earlier step into place: R[j'_loc][i_global][(r,s)]."""
-        work, recv, out_splits, counts, i0 = pending
+        work, recv, counts, i0 = pending
         work.wait()
-        off = 0
-        for g in range(world):
-            if out_splits[g]:
-                blk = recv[off: off + out_splits[g]]
-                if width == 2:
-                    blk = torch.view_as_complex(blk.reshape(-1, 2))
+        for g, blk in enumerate(unpack_exchange(recv, [jl * c * MM for c in counts], dt)):
+            if blk.numel():
                 g0 = ipart.starts[g] + i0
                 R[:, g0:g0 + counts[g]].copy_(blk.reshape(jl, counts[g], MM))
-            off += out_splits[g]
 
     pending = None
     for t in range(nsteps):
@@ -526,13 +517,11 @@ def transform_two_body_rows(rows, C, C_tilde=None, rank=0, world=1, group=None, 
             if n > 0:
                 R[:, i0:i0 + n].copy_(W[:M * n * MM].view(M, n, MM))
             continue
-        in_splits = [jpart.count(g) * n * MM * width for g in range(world)]
-        out_splits = [jl * counts[g] * MM * width for g in range(world)]
-        recv = stages[t % nbuf_x][:sum(out_splits)]
-        work = dist.all_to_all_single(recv, _as_real_flat(W[:M * n * MM]), out_splits, in_splits, group=group, async_op=True)
+        recv, work = post_exchange(W[:M * n * MM], [jpart.count(g) * n * MM for g in range(world)],
+                                   [jl * c * MM for c in counts], group, recv=stages[t % nbuf_x], async_op=True)
         if pending is not None:
             settle(pending)                                # step t - 1: done by now, or waited for here
-        pending = (work, recv, out_splits, counts, i0)
+        pending = (work, recv, counts, i0)
     if pending is not None:
         settle(pending)
     del t1, t2, Ws, stages
@@ -550,6 +539,27 @@ def transform_two_body_rows(rows, C, C_tilde=None, rank=0, world=1, group=None, 
 # ---------------------------------------------------------------------------
 
 
+def fock_two_body(u_slab, n_occ, lo=0, spin_orbitals=False, axis=0, onto=None):
+    """The two-body terms of the Fock matrix held by one slab of ``u``, added to ``onto`` (zeros by default):
+    2 u_piqi - u_piiq (spatial orbitals) or u_piqi (spin orbitals, anti-symmetrised u) over the occupied i.
+    ``axis = 0``: ``u_slab = u[lo:hi]`` holds every term of its rows p -- a (rows, l) block.  ``axis = 1``:
+    ``u_slab = u[:, lo:hi]`` holds the terms of its own occupied i for every p -- an (l, l) share, the shares of
+    all slabs add up."""
+    L = u_slab.shape[1 - axis]
+    f = torch.zeros((u_slab.shape[0], L), dtype=u_slab.dtype, device=u_slab.device) if onto is None else onto
+    if axis == 0:
+        loc = occ = slice(0, n_occ)
+    else:
+        i_lo, i_hi = min(lo, n_occ), min(lo + u_slab.shape[1], n_occ)
+        if i_hi <= i_lo:
+            return f
+        loc, occ = slice(i_lo - lo, i_hi - lo), slice(i_lo, i_hi)
+    direct = torch.einsum("piqi->pq", u_slab[:, loc, :, occ])
+    if spin_orbitals:
+        return f + direct
+    return f + 2 * direct - torch.einsum("piiq->pq", u_slab[:, loc, occ, :])
+
+
 def fock_rows(h, u_slab, n_occ, p_lo, spin_orbitals=False):
     """Rows ``p_lo : p_lo + u_slab.shape[0]`` of the Fock matrix.
 
@@ -559,13 +569,7 @@ def fock_rows(h, u_slab, n_occ, p_lo, spin_orbitals=False):
         f_pq = h_pq + u_piqi
     summed over the ``n_occ`` occupied orbitals i.  ``u_slab = u[p_lo:p_hi]``.
     """
-    pc = u_slab.shape[0]
-    f = h[p_lo:p_lo + pc].clone()
-    o = slice(0, n_occ)
-    direct = torch.einsum("piqi->pq", u_slab[:, o, :, o])
-    if spin_orbitals:
-        return f + direct
-    return f + 2 * direct - torch.einsum("piiq->pq", u_slab[:, o, o, :])
+    return fock_two_body(u_slab, n_occ, p_lo, spin_orbitals, onto=h[p_lo:p_lo + u_slab.shape[0]].clone())
 
 
 def construct_fock_matrix_sharded(h, u_slab, n_occ, rank=0, world=1, spin_orbitals=False, group=None,
@@ -580,15 +584,15 @@ def construct_fock_matrix_sharded(h, u_slab, n_occ, rank=0, world=1, spin_orbita
     rows = fock_rows(h, u_slab, n_occ, lo, spin_orbitals)
     if world == 1:
         return rows
-    width = 2 if rows.is_complex() else 1
+    width = real_words(rows.dtype)
     biggest = max(part.count(r) for r in range(world)) * l * width
     send = torch.zeros(biggest, dtype=torch.float64, device=rows.device)
-    flat = _as_real_flat(rows)
+    flat = as_real_flat(rows)
     send[: flat.numel()] = flat
     recv = torch.empty(world * biggest, dtype=torch.float64, device=rows.device)
     dist.all_gather_into_tensor(recv, send, group=group)
     f = torch.empty((l, l), dtype=rows.dtype, device=rows.device)
-    ff = _as_real_flat(f)
+    ff = as_real_flat(f)
     for r in range(world):
         r_lo, r_hi = part.bounds(r)
         n = (r_hi - r_lo) * l * width
@@ -596,77 +600,22 @@ def construct_fock_matrix_sharded(h, u_slab, n_occ, rank=0, world=1, spin_orbita
     return f
 
 
-def reference_energy_partial(h, u_slab, n_occ, p_lo, spin_orbitals=False):
-    """This slab's share of the reference-determinant energy (no nuclear term): the sum over the occupied
-    rows i in [p_lo, p_lo + rows) of  2 h_ii + 2 u_ijij - u_ijji  (spatial orbitals) or  h_ii + 1/2 u_ijij
-    (spin orbitals, anti-symmetrised u); the shares of all slabs add up to the energy."""
-    lo, hi = p_lo, p_lo + u_slab.shape[0]
-    i_lo, i_hi = min(lo, n_occ), min(hi, n_occ)          # occupied rows of this slab
-    o = slice(0, n_occ)
+def reference_energy_partial(h, u_slab, n_occ, p_lo, spin_orbitals=False, axis=0):
+    """This slab's share of the reference-determinant energy (no nuclear term): the terms  2 h_ii + 2 u_ijij - u_ijji
+    (spatial orbitals) or  h_ii + 1/2 u_ijij  (spin orbitals, anti-symmetrised u) whose occupied i -- ``axis = 0``,
+    ``u_slab = u[p_lo:p_hi]`` -- or whose occupied j -- ``axis = 1``, ``u_slab = u[:, p_lo:p_hi]`` -- lies in the
+    slab; the shares of all slabs add up to the energy."""
+    i_lo, i_hi = min(p_lo, n_occ), min(p_lo + u_slab.shape[axis], n_occ)      # occupied rows of this slab
     part = torch.zeros((), dtype=u_slab.dtype, device=u_slab.device)
     if i_hi > i_lo:
-        blk = u_slab[i_lo - lo:i_hi - lo, o, :, :][:, :, i_lo:i_hi, o]    # u[i, j, i', j'], i' in the same rows
-        coul = torch.einsum("ijij->", blk)
+        o, loc, mine = slice(0, n_occ), slice(i_lo - p_lo, i_hi - p_lo), slice(i_lo, i_hi)
+        coul = torch.einsum("ijij->", u_slab[loc, o, mine, o] if axis == 0 else u_slab[o, loc, o, mine])
         hd = torch.diagonal(h)[i_lo:i_hi].sum().to(u_slab.dtype)
         if spin_orbitals:
             part = hd + 0.5 * coul
         else:
-            part = 2 * hd + 2 * coul - torch.einsum("ijji->", u_slab[i_lo - lo:i_hi - lo, o, o, :][:, :, :, i_lo:i_hi])
-    return part
-
-
-def reference_energy_sharded(h, u_slab, n_occ, rank=0, world=1, spin_orbitals=False,
-                             nuclear_repulsion_energy=0.0, group=None):
-    """Reference-determinant energy from a p-sharded ``u``.
-
-    spatial (spatial_orbital_system.py:106-150): 2 h_ii + 2 u_ijij - u_ijji + E_nuc
-    spin orbitals (general_orbital_system.py:75-121): h_ii + 1/2 u_ijij + E_nuc
-    The leading index i of ``u`` is the sharded one: each rank sums its occupied
-    rows, one all-reduce of a single number closes the sum.
-    """
-    l = h.shape[0]
-    lo, hi = SlabPartition(l, world).bounds(rank)
-    if u_slab.shape[0] != hi - lo:
-        raise ValueError(f"rank {rank}: slab has {u_slab.shape[0]} rows, expected {hi - lo}")
-    part = reference_energy_partial(h, u_slab, n_occ, lo, spin_orbitals)
-    if world > 1:
-        buf = torch.view_as_real(part.to(torch.complex128).reshape(1)).reshape(-1).contiguous()
-        dist.all_reduce(buf, group=group)
-        total = torch.view_as_complex(buf.reshape(1, 2))[0]
-        part = total if u_slab.is_complex() else total.real
-    return part + nuclear_repulsion_energy
-
-
-def fock_partial_second_index(u_bslab, n_occ, b_lo, spin_orbitals=False):
-    """This rank's share of the two-body part of the Fock matrix when ``u`` is sharded over its SECOND
-    index (``u_bslab = u[:, b_lo:b_hi]``): the sums over the occupied i run over the second index,
-    so each rank adds the terms of its own occupied i and the shares add up (one all-reduce of l*l)."""
-    L = u_bslab.shape[0]
-    i_lo, i_hi = min(b_lo, n_occ), min(b_lo + u_bslab.shape[1], n_occ)
-    f = torch.zeros((L, L), dtype=u_bslab.dtype, device=u_bslab.device)
-    if i_hi > i_lo:
-        loc = slice(i_lo - b_lo, i_hi - b_lo)
-        direct = torch.einsum("piqi->pq", u_bslab[:, loc, :, i_lo:i_hi])
-        if spin_orbitals:
-            return f + direct
-        return f + 2 * direct - torch.einsum("piiq->pq", u_bslab[:, loc, i_lo:i_hi, :])
-    return f
-
-
-def reference_energy_partial_second_index(h, u_bslab, n_occ, b_lo, spin_orbitals=False):
-    """Share of the reference energy held by a second-index slab ``u[:, b_lo:b_hi]``: the terms
-    u_ijij / u_ijji whose j lies in the slab, plus the one-body terms h_jj of those j."""
-    j_lo, j_hi = min(b_lo, n_occ), min(b_lo + u_bslab.shape[1], n_occ)
-    o = slice(0, n_occ)
-    part = torch.zeros((), dtype=u_bslab.dtype, device=u_bslab.device)
-    if j_hi > j_lo:
-        loc = slice(j_lo - b_lo, j_hi - b_lo)
-        coul = torch.einsum("ijij->", u_bslab[o, loc, o, j_lo:j_hi])
-        hd = torch.diagonal(h)[j_lo:j_hi].sum().to(u_bslab.dtype)
-        if spin_orbitals:
-            part = hd + 0.5 * coul
-        else:
-            part = 2 * hd + 2 * coul - torch.einsum("ijji->", u_bslab[o, loc, j_lo:j_hi, o])
+            part = 2 * hd + 2 * coul - torch.einsum(
+                "ijji->", u_slab[loc, o, o, mine] if axis == 0 else u_slab[o, loc, mine, o])
     return part
 
 
@@ -674,10 +623,22 @@ def all_reduce_sum(t, world, group=None):
     """Sum of a (small) tensor over the ranks; complex values travel as interleaved pairs."""
     if world == 1:
         return t
-    if t.is_complex():
-        buf = torch.view_as_real(t.contiguous()).contiguous()
-        dist.all_reduce(buf, group=group)
-        return torch.view_as_complex(buf)
     buf = t.contiguous()
-    dist.all_reduce(buf, group=group)
+    dist.all_reduce(torch.view_as_real(buf) if buf.is_complex() else buf, group=group)
     return buf
+
+
+def reference_energy_sharded(h, u_slab, n_occ, rank=0, world=1, spin_orbitals=False,
+                             nuclear_repulsion_energy=0.0, group=None, part=None):
+    """Reference-determinant energy from a p-sharded ``u``.
+
+    spatial (spatial_orbital_system.py:106-150): 2 h_ii + 2 u_ijij - u_ijji + E_nuc
+    spin orbitals (general_orbital_system.py:75-121): h_ii + 1/2 u_ijij + E_nuc
+    The leading index i of ``u`` is the sharded one: each rank sums its occupied
+    rows, one all-reduce of a single number closes the sum.
+    """
+    lo, hi = (part or SlabPartition(h.shape[0], world)).bounds(rank)
+    if u_slab.shape[0] != hi - lo:
+        raise ValueError(f"rank {rank}: slab has {u_slab.shape[0]} rows, expected {hi - lo}")
+    share = reference_energy_partial(h, u_slab, n_occ, lo, spin_orbitals)
+    return all_reduce_sum(share.reshape(1), world, group)[0] + nuclear_repulsion_energy

@@ -199,7 +199,7 @@ def construct_fock_matrix(h, u, n_occ, spin_orbitals, f=None):
         out = sharded.construct_fock_matrix_sharded(hp, u.local, n_occ, u.rank, u.world, spin_orbitals, u.group,
                                                     part=u.part)
     else:
-        part = sharded.fock_partial_second_index(u.local, n_occ, u.lo, spin_orbitals)
+        part = sharded.fock_two_body(u.local, n_occ, u.lo, spin_orbitals, axis=1)
         out = hp.to(part.dtype) + sharded.all_reduce_sum(part, u.world, u.group)
     if f is not None:
         f.fill(0)
@@ -211,10 +211,6 @@ def construct_fock_matrix(h, u, n_occ, spin_orbitals, f=None):
 def compute_reference_energy(h, u, n_occ, spin_orbitals, nuclear_repulsion_energy):
     """Reference-determinant energy from a sharded ``u`` (spatial_orbital_system.py:106-150,
     general_orbital_system.py:75-121): one number per rank, one all-reduce."""
-    hp = _plain(h)
-    if u.axis == 0:
-        part = sharded.reference_energy_partial(hp, u.local, n_occ, u.lo, spin_orbitals)
-    else:
-        part = sharded.reference_energy_partial_second_index(hp, u.local, n_occ, u.lo, spin_orbitals)
+    part = sharded.reference_energy_partial(_plain(h), u.local, n_occ, u.lo, spin_orbitals, axis=u.axis)
     total = sharded.all_reduce_sum(part.reshape(1), u.world, u.group)[0]
     return wrap(total + nuclear_repulsion_energy)

@@ -152,22 +152,14 @@ class ShardedTensor4:
         if self.world == 1:
             return self._like(self.rows.transpose(0, 1).contiguous(), axis=axis)
         mine = self.hi - self.lo
-        width = 2 if self.rows.is_complex() else 1
-        blk = l * l
         # the block (my rows, rank g's rows of the other index) goes to rank g, other index leading
         pieces = [self.rows[:, part.bounds(g)[0]:part.bounds(g)[1]].transpose(0, 1).reshape(-1)
                   for g in range(self.world)]
-        send = sharded._as_real_flat(torch.cat(pieces))
-        splits = [mine * part.count(g) * blk * width for g in range(self.world)]
-        recv = torch.empty(sum(splits), dtype=torch.float64, device=send.device)
-        dist.all_to_all_single(recv, send, splits, splits, group=self.group)
-        out, off = [], 0
-        for g in range(self.world):
-            piece = recv[off: off + splits[g]]
-            off += splits[g]
-            if width == 2:
-                piece = torch.view_as_complex(piece.reshape(-1, 2))
-            out.append(piece.reshape(mine, part.count(g), l, l))    # [my new rows][sender's rows of the old index]
+        counts = [mine * part.count(g) * l * l for g in range(self.world)]
+        recv, _ = sharded.post_exchange(torch.cat(pieces), counts, counts, self.group)
+        # from rank g: [my new rows][g's rows of the old index]
+        out = [piece.reshape(mine, part.count(g), l, l)
+               for g, piece in enumerate(sharded.unpack_exchange(recv, counts, self.rows.dtype))]
         return self._like(torch.cat(out, dim=1).contiguous(), axis=axis)
 
     def __repr__(self):
