@@ -469,6 +469,37 @@ const char* qs_last_dispatch(void);
  */
 int qs_tuning_set(const char* key, int64_t value);
 int qs_tuning_reset(void);
+
+/*
+ * Mean-field (Fock) contraction of the two-body tensor with a one-body density,
+ * both sums from ONE read of `u`:
+ *   W[p,q] = cj * sum_{r,s} u[p,r,q,s] D[s,r]  +  ck * sum_{r,s} u[p,r,s,q] D[s,r]
+ *   u_slab : (P, R, L, L) contiguous -- rows p_lo ... p_lo+P of the leading index
+ *            and r_lo ... r_lo+R of the second (the whole tensor, u[lo:hi] and
+ *            u[:, lo:hi] made contiguous are all this one call); with R < L the
+ *            result is the partial sum over the slab's r;
+ *   D      : (L, L) row-major, D[s, r];   W : (P, L).
+ * dtype pairs (u, D): (F64, F64) -> W fp64; (C128, C128) -> W complex128;
+ * (F64, C128) -> W complex128 with no complex copy of `u`; (C128, F64) is
+ * QS_ERR_BAD_DTYPE.  1 <= L <= 1024, 1 <= P <= L, 1 <= R, r_lo >= 0, r_lo + R <= L.
+ * cj == 0 / ck == 0 skip that sum's arithmetic.  RHF: cj = 1, ck = -1/2 with the
+ * spin-summed density; anti-symmetrised spin orbitals: cj = 1, ck = 0.
+ * Replaces np.einsum("prqs,sr->pq") / ("prsq,sr->pq") on the whole tensor (the
+ * reference names the step: change_to_hf_basis, general_orbital_system.py:161-169).
+ * Deterministic (no floating-point atomics): the r range is cut into chunks of
+ *   Rc = min(ceil(R / min(ceil(4096 / L), R)), max(1, floor(2048 / (Le * dw))))
+ * consecutive r, Le = L rounded up to even, dw = 1 for an fp64 D and 2 for a
+ * complex one; each (p, chunk) sum goes to the workspace and a second launch adds
+ * the chunks in ascending order.  The split depends on (L, R, dtypes) only: row p
+ * of a slab call is bit-identical to row p of the full call.
+ * Workspace: P * L * ceil(R / Rc) elements of W's dtype (bytes per row times P);
+ * nothing else is allocated or written.  `W` must not overlap `u_slab`, `D` or
+ * the workspace.
+ */
+int64_t qs_mean_field_workspace(int u_dtype, int d_dtype, int64_t L, int64_t P, int64_t R);
+int qs_mean_field(int u_dtype, int d_dtype, const void* u_slab, const void* D, void* W,
+                  int64_t L, int64_t P, int64_t R, int64_t r_lo, double cj, double ck,
+                  void* workspace, int64_t workspace_bytes, void* stream);
 int qs_probe_mfma_f64(void* sink, int64_t blocks, int64_t iters, void* stream);
 int qs_probe_stream_copy(const void* src, void* dst, int64_t bytes, void* stream);
 

@@ -17,6 +17,7 @@ from .sharded_module import ShardedDeviceModule, ShardedTensor4
 from .basis_set import BasisSet, ChangeBasisPlan
 from .custom_system import construct_custom_system, setup_basis_set
 from .general_orbital_system import GeneralOrbitalSystem
+from .hartree_fock import HartreeFock
 from .one_dim_qd import ODQD
 from .random_basis import RandomBasisSet
 from .sinc_dvr import ODSincDVR
@@ -26,7 +27,7 @@ from .two_dim_ho import TwoDimensionalDoubleWell, TwoDimensionalHarmonicOscillat
 
 __all__ = [
     "BasisSet", "RandomBasisSet", "QuantumSystem", "SpatialOrbitalSystem",
-    "GeneralOrbitalSystem", "setup_basis_set", "construct_custom_system",
+    "GeneralOrbitalSystem", "HartreeFock", "setup_basis_set", "construct_custom_system",
     "TwoDimensionalHarmonicOscillator", "TwoDimensionalDoubleWell", "TwoDimHarmonicOscB", "ODQD", "ODSincDVR",
     "ChangeBasisPlan", "hip", "DeviceModule", "DeviceArray", "ShardedDeviceModule", "ShardedTensor4", "kernels", "sharded",
 ]

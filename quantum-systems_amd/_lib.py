@@ -73,6 +73,10 @@ SIGNATURES = {
     "qs_tuning_reset": (c_int, []),
     "qs_probe_mfma_f64": (c_int, [c_ptr, c_i64, c_i64, c_ptr]),
     "qs_probe_stream_copy": (c_int, [c_ptr, c_ptr, c_i64, c_ptr]),
+    "qs_mean_field_workspace": (c_i64, [c_int, c_int, c_i64, c_i64, c_i64]),
+    "qs_mean_field": (
+        c_int, [c_int, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, ctypes.c_double, ctypes.c_double,
+                c_ptr, c_i64, c_ptr]),
 }
 
 ABI_VERSION = 4

@@ -58,5 +58,9 @@ class GeneralOrbitalSystem(QuantumSystem):
         f += np.einsum("piqi -> pq", u[:, o, :, o])
         return f
 
+    def _mean_field_weights(self):
+        # anti-symmetrised u carries the exchange term already: f = h + J(rho); a plain u: f = h + J(rho) - K(rho)
+        return (1.0, 0.0) if self._basis_set._anti_symmetrized_u else (1.0, -1.0)
+
     def change_to_hf_basis(self, *args, **kwargs):
         raise NotImplementedError("There is currently no GHF implementation")

@@ -1,0 +1,130 @@
+"""Self-consistent field on top of ``kernels.mean_field``: restricted Hartree-Fock for a ``SpatialOrbitalSystem``,
+general Hartree-Fock for a ``GeneralOrbitalSystem``.
+
+The reference names this step and leaves it out (``change_to_hf_basis`` raises, the ``tdhf`` call is commented out in
+general_orbital_system.py:161-169).  Every iteration contracts the WHOLE two-body tensor with the current density --
+one ``qs_mean_field`` launch, one read of ``u`` -- and everything else is O(l^3) plumbing on l x l matrices
+(``torch.linalg.eigh``, a handful of products).
+
+    hf = HartreeFock(system)
+    C, epsilon, energies = hf.scf(tol=1e-10)
+    hf.change_system_basis()            # system.change_basis(C): the Fock matrix is diagonal now
+
+``system.change_to_hf_basis()`` keeps raising ``NotImplementedError`` as in the reference.
+"""
+
+import numpy
+import torch
+
+from . import kernels, sharded_basis
+from .basis_set import _deliver, _stage
+from .general_orbital_system import GeneralOrbitalSystem
+from .sharded_module import is_sharded
+from .spatial_orbital_system import SpatialOrbitalSystem
+
+
+def _dagger(A):
+    return A.conj().transpose(0, 1)
+
+
+class HartreeFock:
+    """SCF driver: core-Hamiltonian guess, Loewdin orthogonalisation with the basis set's overlap ``s``, DIIS on
+    ``F rho s - s rho F``.  ``system.n`` lowest orbitals are occupied (doubly for spatial orbitals)."""
+
+    def __init__(self, system):
+        if isinstance(system, SpatialOrbitalSystem):
+            self.occupation = 2.0
+        elif isinstance(system, GeneralOrbitalSystem):
+            self.occupation = 1.0
+        else:
+            raise TypeError("HartreeFock needs a SpatialOrbitalSystem (RHF) or a GeneralOrbitalSystem (GHF)")
+        self.system = system
+        self.C = self.epsilon = None
+        self.energies = []
+        self.converged = False
+        self.iterations = 0
+
+    # -- the one O(l^4) step of an iteration
+    def _mean_field(self, u, rho):
+        cj, ck = self.system._mean_field_weights()
+        if is_sharded(u):
+            return sharded_basis.mean_field(u, rho, cj, ck, self.system.np).as_subclass(torch.Tensor)
+        return kernels.mean_field(u, rho, cj=cj, ck=ck)
+
+    def _density(self, C):
+        Co = C[:, : self.system.n]
+        return (self.occupation * (Co @ _dagger(Co))).contiguous()
+
+    def scf(self, tol=1e-10, max_iter=100, diis_vectors=8):
+        """Iterate to ``max |X^H (F rho s - s rho F) X| < tol`` (X = s^-1/2).  Returns ``(C, epsilon, energies)``:
+        the coefficients (columns = canonical orbitals, ``C^H s C = 1``) and orbital energies of the final Fock matrix
+        in the system's array module, and the list of energies E[rho_k], one per iteration (the first is the
+        core-guess determinant's)."""
+        system = self.system
+        with torch._C.DisableTorchFunctionSubclass():
+            u = system.u if is_sharded(system.u) else _stage(system.u).as_subclass(torch.Tensor)
+            h = _stage(system.h).as_subclass(torch.Tensor)
+            s = _stage(system.s).as_subclass(torch.Tensor)
+            dt = torch.complex128 if torch.complex128 in (h.dtype, s.dtype, u.dtype) else torch.float64
+            h, s = h.to(dt), s.to(dt)
+            e_nuc = system.nuclear_repulsion_energy
+
+            sv, sU = torch.linalg.eigh(s)
+            X = (sU * sv.rsqrt().to(dt)) @ _dagger(sU)                   # s^-1/2
+            Xh = _dagger(X)
+
+            def diagonalise(F):
+                eps, Cp = torch.linalg.eigh(Xh @ F @ X)
+                return eps, X @ Cp
+
+            epsilon, C = diagonalise(h)                                   # core-Hamiltonian guess
+            rho = self._density(C)
+            self.energies, self.converged = [], False
+            focks, errors = [], []
+            for it in range(1, max_iter + 1):
+                self.iterations = it
+                W = self._mean_field(u, rho).to(dt)
+                F = h + W
+                rho_t = rho.transpose(0, 1)
+                energy = ((h + 0.5 * W) * rho_t).sum() + e_nuc
+                self.energies.append(float(energy.real.item()))
+                err = Xh @ (F @ rho @ s - s @ rho @ F) @ X
+                if float(err.abs().max().item()) < tol:
+                    self.converged = True
+                    break
+                if diis_vectors and diis_vectors > 1:
+                    focks.append(F)
+                    errors.append(err)
+                    del focks[:-diis_vectors], errors[:-diis_vectors]
+                    F = self._extrapolate(focks, errors)
+                epsilon, C = diagonalise(F)
+                rho = self._density(C)
+            # canonical orbitals of the last Fock matrix itself (not of an extrapolated one)
+            epsilon, C = diagonalise(F if self.converged else h + self._mean_field(u, rho).to(dt))
+            self.C, self.epsilon = _deliver(C.contiguous(), system.np), _deliver(epsilon, system.np)
+        return self.C, self.epsilon, self.energies
+
+    @staticmethod
+    def _extrapolate(focks, errors):
+        """Pulay's DIIS: the combination of the stored Fock matrices whose combined error is smallest."""
+        m = len(focks)
+        if m < 2:
+            return focks[-1]
+        B = numpy.zeros((m + 1, m + 1))
+        for i in range(m):
+            for j in range(i + 1):
+                B[i, j] = B[j, i] = float((errors[i].conj() * errors[j]).sum().real.item())
+        B[:m, m] = B[m, :m] = -1.0
+        rhs = numpy.zeros(m + 1)
+        rhs[m] = -1.0
+        scale = max(B[:m, :m].diagonal().max(), 1e-300)
+        B[:m, :m] /= scale
+        c = numpy.linalg.lstsq(B, rhs, rcond=None)[0][:m]
+        return sum(float(ci) * Fi for ci, Fi in zip(c, focks))
+
+    def change_system_basis(self):
+        """``system.change_basis(C)`` with the converged coefficients: the system's Fock matrix becomes diagonal."""
+        if self.C is None:
+            raise RuntimeError("run scf() first")
+        self.system.change_basis(self.C)
+        return self.system

@@ -602,6 +602,46 @@ def antisymmetrize_(u):
     return antisymmetrize(u, out=u)
 
 
+@_plain
+def mean_field(u, D, cj=1.0, ck=0.0, r_lo=0, out=None):
+    """Mean-field contraction of the two-body tensor with a one-body density, both sums from one read of ``u``
+    (``qs_mean_field``):
+
+        W[p,q] = cj * sum_rs u[p,r,q,s] D[s,r]  +  ck * sum_rs u[p,r,s,q] D[s,r]
+
+    ``u`` is (P, R, L, L): the whole tensor, a rows slab ``u[lo:hi]`` or a second-index slab ``u[:, lo:hi]`` whose
+    ``r`` starts at ``r_lo`` (then ``W`` is the partial sum over the slab's ``r``).  ``D`` is (L, L).  A real ``u``
+    with a complex ``D`` stays real (complex ``W``).  Returns ``W`` (P, L)."""
+    lib = _lib.load()
+    dt = result_dtype(u, D)
+    udt = _F64 if isinstance(u, torch.Tensor) and u.dtype == _F64 else dt
+    u = _dev(u, udt)
+    D = _dev(D, dt)
+    if u.dim() != 4 or D.dim() != 2:
+        raise ValueError("u must be (P, R, L, L) and D (L, L)")
+    P, R, L = u.shape[0], u.shape[1], u.shape[3]
+    if u.shape[2] != L or tuple(D.shape) != (L, L):
+        raise ValueError(f"u has shape {tuple(u.shape)}, D {tuple(D.shape)}: need u (P, R, L, L) and D (L, L)")
+    if not (1 <= P <= L and 1 <= R and 0 <= r_lo and r_lo + R <= L):
+        raise ValueError(f"slab of {P} rows and second indices [{r_lo}, {r_lo + R}) does not fit L = {L}")
+    ucode, dcode = dtype_code(udt), dtype_code(dt)
+    nbytes = check(lib.qs_mean_field_workspace(ucode, dcode, L, P, R), "workspace query")
+    if out is None:
+        out = torch.empty((P, L), dtype=dt, device=u.device)
+    else:
+        _check_out(out, (P, L), dt, "mean_field")
+    with _on_device_of(u, D, out):
+        work = workspace.get(nbytes, u.device)
+        _ran(
+            lib.qs_mean_field(
+                ucode, dcode, u.data_ptr(), D.data_ptr(), out.data_ptr(), L, P, R, int(r_lo), float(cj), float(ck),
+                work.data_ptr(), work.numel(), _stream(),
+            ),
+            "qs_mean_field",
+        )
+    return out
+
+
 class RcclComm:
     """The C ABI's communicator (``qs_comm_init``: RCCL over xGMI, one process per GPU) for hosts that drive the
     library from Python without ``torch.distributed``.  ``unique_id()`` on one rank, the 128 bytes to the others by

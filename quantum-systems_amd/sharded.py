@@ -103,6 +103,10 @@ class HipEngine:
     def spin_squared_two_body(S, antisymmetrize=False, p_lo=0, p_hi=None):
         return kernels.spin_squared_two_body(S, antisymmetrize=antisymmetrize, p_lo=p_lo, p_hi=p_hi)
 
+    @staticmethod
+    def mean_field(u_slab, D, cj=1.0, ck=0.0, r_lo=0):
+        return kernels.mean_field(u_slab, D, cj=cj, ck=ck, r_lo=r_lo)
+
 
 def _bra(C, C_tilde):
     return kernels.default_bra(C) if C_tilde is None else C_tilde
@@ -581,7 +585,13 @@ def construct_fock_matrix_sharded(h, u_slab, n_occ, rank=0, world=1, spin_orbita
     lo, hi = part.bounds(rank)
     if tuple(u_slab.shape[:1]) != (hi - lo,):
         raise ValueError(f"rank {rank}: slab has {u_slab.shape[0]} rows, expected {hi - lo}")
-    rows = fock_rows(h, u_slab, n_occ, lo, spin_orbitals)
+    return gather_rows(fock_rows(h, u_slab, n_occ, lo, spin_orbitals), l, rank, world, group, part)
+
+
+def gather_rows(rows, l, rank=0, world=1, group=None, part=None):
+    """The full (l, l) matrix on every rank from each rank's rows ``part.bounds(rank)`` of it: one all-gather of
+    l*l numbers (uneven slabs travel padded to the largest)."""
+    part = part or SlabPartition(l, world)
     if world == 1:
         return rows
     width = real_words(rows.dtype)
@@ -598,6 +608,24 @@ def construct_fock_matrix_sharded(h, u_slab, n_occ, rank=0, world=1, spin_orbita
         n = (r_hi - r_lo) * l * width
         ff[r_lo * l * width: r_lo * l * width + n] = recv[r * biggest: r * biggest + n]
     return f
+
+
+def mean_field_local(rows, D, cj, ck, lo=0, axis=0, engine=HipEngine):
+    """One rank's share of  W[p,q] = cj u[p,r,q,s] D[s,r] + ck u[p,r,s,q] D[s,r]  from its ``ShardedTensor4.rows``
+    (the sharded index leading), one pass over the slab (``qs_mean_field``).  ``axis = 0``: ``rows = u[lo:hi]``, the
+    (rows, l) block W[lo:hi].  ``axis = 1``: ``rows[i] = u[:, lo + i]``, the (l, l) partial sum over the slab's r -- one
+    call per held r on its (l, l, l) block as it is stored, no re-ordered copy of the slab; the shares of all slabs add
+    up."""
+    l = rows.shape[-1]
+    dt = kernels.result_dtype(rows, D)
+    if axis == 0:
+        if rows.shape[0] == 0:
+            return torch.empty((0, l), dtype=dt, device=rows.device)
+        return engine.mean_field(rows, D, cj, ck)
+    W = torch.zeros((l, l), dtype=dt, device=rows.device)
+    for i in range(rows.shape[0]):
+        W += engine.mean_field(rows[i].unsqueeze(1), D, cj, ck, r_lo=lo + i)
+    return W
 
 
 def reference_energy_partial(h, u_slab, n_occ, p_lo, spin_orbitals=False, axis=0):

@@ -208,6 +208,17 @@ def construct_fock_matrix(h, u, n_occ, spin_orbitals, f=None):
     return wrap(out)
 
 
+def mean_field(u, rho_qp, cj, ck, np):
+    """``W[p,q] = cj u[p,r,q,s] rho[s,r] + ck u[p,r,s,q] rho[s,r]`` on every rank from a sharded ``u``: each rank's
+    slab goes through the one-pass kernel as it is stored, then l*l numbers over the node (rows gathered when the
+    leading index is sharded, partial sums added when the second index is).  ``u`` stays sharded."""
+    D = _plain(np.asarray(rho_qp)).contiguous()
+    part = sharded.mean_field_local(u.rows, D, cj, ck, u.lo, u.axis, engine=np.engine)
+    if u.axis == 0:
+        return wrap(sharded.gather_rows(part, u.l, u.rank, u.world, u.group, u.part))
+    return wrap(sharded.all_reduce_sum(part, u.world, u.group))
+
+
 def compute_reference_energy(h, u, n_occ, spin_orbitals, nuclear_repulsion_energy):
     """Reference-determinant energy from a sharded ``u`` (spatial_orbital_system.py:106-150,
     general_orbital_system.py:75-121): one number per rank, one all-reduce."""

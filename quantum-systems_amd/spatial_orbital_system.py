@@ -81,5 +81,9 @@ class SpatialOrbitalSystem(QuantumSystem):
         f -= np.einsum("piiq -> pq", u[:, o, o, :])
         return f
 
+    def _mean_field_weights(self):
+        # closed shell, spin-summed density: f = h + J(rho) - K(rho) / 2
+        return 1.0, -0.5
+
     def change_to_hf_basis(self, *args, **kwargs):
         raise NotImplementedError("There is currently no RHF implementation")

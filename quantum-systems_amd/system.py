@@ -44,6 +44,46 @@ class QuantumSystem(metaclass=abc.ABCMeta):
     def compute_reference_energy(self, h=None, u=None):
         pass
 
+    # -- mean field of a general one-body density: ONE pass over u on the GPU (kernels.mean_field)
+    def _mean_field_weights(self):
+        """``(cj, ck)`` of  W[p,q] = cj u[p,r,q,s] rho[s,r] + ck u[p,r,s,q] rho[s,r]  for this kind of system."""
+        raise NotImplementedError
+
+    def construct_mean_field_from_density(self, rho_qp, u=None):
+        """The two-body part ``W`` of the Fock matrix for the one-body density ``rho_qp`` (the convention of
+        ``compute_particle_density``: the full, spin-summed density, trace(rho s) = n)."""
+        from . import kernels, sharded_basis
+        from .basis_set import _deliver, _stage
+        from .sharded_module import is_sharded
+
+        u = self.u if u is None else u
+        cj, ck = self._mean_field_weights()
+        if is_sharded(u):
+            return sharded_basis.mean_field(u, rho_qp, cj, ck, self.np)
+        return _deliver(kernels.mean_field(_stage(u), _stage(rho_qp), cj=cj, ck=ck), self.np)
+
+    def construct_fock_matrix_from_density(self, rho_qp, h=None, u=None, f=None):
+        """``f = h + W(rho)``: ``construct_fock_matrix`` for a general density instead of the reference determinant
+        (with rho = that determinant the two agree).  ``f`` may supply the buffer, which is filled and returned."""
+        h = self.h if h is None else h
+        W = self.construct_mean_field_from_density(rho_qp, u)
+        if f is None:
+            return h + W
+        f.fill(0)
+        f += h
+        f += W
+        return f
+
+    def compute_energy_from_density(self, rho_qp, h=None, u=None):
+        """E = h_pq rho_qp + 1/2 W_pq rho_qp + E_nuc: ``compute_reference_energy`` for a general density."""
+        np = self.np
+        h = self.h if h is None else h
+        W = self.construct_mean_field_from_density(rho_qp, u)
+        rho = np.asarray(rho_qp)
+        return (
+            np.einsum("pq,qp->", h, rho) + 0.5 * np.einsum("pq,qp->", W, rho) + self.nuclear_repulsion_energy
+        )
+
     # -- forwarding (system.py:57-71, :217-225)
     def change_module(self, np):
         self.np = np
