@@ -500,6 +500,22 @@ int64_t qs_mean_field_workspace(int u_dtype, int d_dtype, int64_t L, int64_t P, 
 int qs_mean_field(int u_dtype, int d_dtype, const void* u_slab, const void* D, void* W,
                   int64_t L, int64_t P, int64_t R, int64_t r_lo, double cj, double ck,
                   void* workspace, int64_t workspace_bytes, void* stream);
+/* The launch geometry qs_mean_field uses for (dtypes, L, P, R), as numbers (pure
+ * index arithmetic from the functions the entry itself calls: no GPU, no HIP
+ * call).  Test hook: the suite derives the geometry classes its cases must
+ * cover from it.  Writes 7 values to `out` (n_out >= 7):
+ *   {Rc, nchunk, ct_log, ncb, nrb, lds_bytes, grid}
+ * Rc consecutive r per work unit, nchunk = ceil(R / Rc) units per row; CT =
+ * 1 << ct_log column threads of one 16-byte item (cpi = 2 real columns, or 1
+ * complex element of u), RT = 256 / CT row threads of 8 rows: a tile is RB =
+ * 8 RT rows by CT * cpi columns, a slab ncb x nrb tiles, a tile row WPR =
+ * max(1, CT / 64) waves; lds_bytes = 8 * aw * (Rc * Le + nrb * RB + ncb * CT *
+ * cpi + RB * WPR + 256 * cpi) dynamic LDS, aw = 1 for an fp64 D and 2 for a
+ * complex one; grid = P * nchunk workgroups.  All but `grid` depend on (dtypes,
+ * L, R) only.  Returns 0 or what qs_mean_field_workspace refuses (dtype pair,
+ * extents; QS_ERR_BAD_EXTENT for n_out < 7, QS_ERR_NULL_POINTER for out == 0). */
+int qs_mean_field_plan(int u_dtype, int d_dtype, int64_t L, int64_t P, int64_t R,
+                       int64_t* out, int n_out);
 int qs_probe_mfma_f64(void* sink, int64_t blocks, int64_t iters, void* stream);
 int qs_probe_stream_copy(const void* src, void* dst, int64_t bytes, void* stream);
 

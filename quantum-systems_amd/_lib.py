@@ -77,6 +77,7 @@ SIGNATURES = {
     "qs_mean_field": (
         c_int, [c_int, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, ctypes.c_double, ctypes.c_double,
                 c_ptr, c_i64, c_ptr]),
+    "qs_mean_field_plan": (c_int, [c_int, c_int, c_i64, c_i64, c_i64, c_ptr, c_int]),
 }
 
 ABI_VERSION = 4

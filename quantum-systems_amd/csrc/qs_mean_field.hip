@@ -260,6 +260,23 @@ static inline bool mf_extents_ok(int64_t L, int64_t P, int64_t R) {
     return L > 0 && L <= 1024 && P > 0 && P <= L && R > 0 && R <= L;
 }
 
+// The launch geometry of one call: everything the kernel reads from MfArgs apart from the pointers, the weights and
+// r_lo, its dynamic LDS in bytes and its grid -- a function of (form, L, P, R); all but the grid of (form, L, R) only.
+// The entry, the workspace query and the plan hook all take it from here.
+static inline void mf_plan(int form, int64_t L, int64_t P, int64_t R, MfArgs* g, size_t* lds, unsigned* grid) {
+    const int aw = form == 0 ? 1 : 2, cpi = form == 1 ? 1 : 2, uw = form == 1 ? 2 : 1;
+    g->slab_words = L * L * uw;
+    g->L = (int)L; g->R = (int)R;
+    mf_chunks(L, R, aw, &g->Rc, &g->nchunk);
+    g->ct_log = mf_ct_log(L, cpi);
+    const int64_t ct = int64_t(1) << g->ct_log, rb = (256 >> g->ct_log) * kMfRows;
+    g->ncb = (int)cdiv(cdiv(L, cpi), ct);
+    g->nrb = (int)cdiv(L, rb);
+    const int64_t Ls = (L + 1) & ~int64_t(1), wpr = ct > 64 ? ct >> 6 : 1;
+    *lds = (size_t)(g->Rc * Ls + g->nrb * rb + g->ncb * ct * cpi + rb * wpr + 256 * cpi) * aw * 8;
+    *grid = (unsigned)(P * g->nchunk);
+}
+
 static inline bool overlaps(const void* a, int64_t na, const void* b, int64_t nb) {
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
     return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
@@ -275,9 +292,25 @@ int64_t qs_mean_field_workspace(int u_dtype, int d_dtype, int64_t L, int64_t P, 
     const int form = mf_form(u_dtype, d_dtype);
     if (form < 0) return form;
     if (!mf_extents_ok(L, P, R)) return QS_ERR_BAD_EXTENT;
-    int Rc, nchunk;
-    mf_chunks(L, R, form == 0 ? 1 : 2, &Rc, &nchunk);
-    return P * L * nchunk * (int64_t)elem_size(d_dtype);
+    MfArgs g{};
+    size_t lds;
+    unsigned grid;
+    mf_plan(form, L, P, R, &g, &lds, &grid);
+    return P * L * g.nchunk * (int64_t)elem_size(d_dtype);
+}
+
+int qs_mean_field_plan(int u_dtype, int d_dtype, int64_t L, int64_t P, int64_t R, int64_t* out, int n_out) {
+    const int form = mf_form(u_dtype, d_dtype);
+    if (form < 0) return form;
+    if (!mf_extents_ok(L, P, R) || n_out < 7) return QS_ERR_BAD_EXTENT;
+    if (!out) return QS_ERR_NULL_POINTER;
+    MfArgs g{};
+    size_t lds;
+    unsigned grid;
+    mf_plan(form, L, P, R, &g, &lds, &grid);
+    const int64_t plan[7] = {g.Rc, g.nchunk, g.ct_log, g.ncb, g.nrb, (int64_t)lds, (int64_t)grid};
+    for (int i = 0; i < 7; ++i) out[i] = plan[i];
+    return 0;
 }
 
 int qs_mean_field(int u_dtype, int d_dtype, const void* u_slab, const void* D, void* W, int64_t L, int64_t P,
@@ -297,22 +330,16 @@ int qs_mean_field(int u_dtype, int d_dtype, const void* u_slab, const void* D, v
         return QS_ERR_ALIAS;
     if (workspace_bytes < need) return QS_ERR_WORKSPACE;
 
-    const int aw = form == 0 ? 1 : 2, cpi = form == 1 ? 1 : 2;
     MfArgs g{};
+    size_t lds;
+    unsigned grid;
+    mf_plan(form, L, P, R, &g, &lds, &grid);
+    if (lds > 64 * 1024) return QS_ERR_BAD_EXTENT;      // (not reached for L <= 1024)
     g.u = (const double*)u_slab; g.D = (const double*)D; g.part = (double*)workspace;
     g.cj = cj; g.ck = ck;
-    g.slab_words = L * L * (ues / 8);
-    g.L = (int)L; g.R = (int)R; g.r_lo = (int)r_lo;
-    mf_chunks(L, R, aw, &g.Rc, &g.nchunk);
-    g.ct_log = mf_ct_log(L, cpi);
-    const int64_t ct = int64_t(1) << g.ct_log, rb = (256 >> g.ct_log) * kMfRows;
-    g.ncb = (int)cdiv(cdiv(L, cpi), ct);
-    g.nrb = (int)cdiv(L, rb);
-    const int64_t Ls = (L + 1) & ~int64_t(1), wpr = ct > 64 ? ct >> 6 : 1;
-    const size_t lds = (size_t)(g.Rc * Ls + g.nrb * rb + g.ncb * ct * cpi + rb * wpr + 256 * cpi) * aw * 8;
-    if (lds > 64 * 1024) return QS_ERR_BAD_EXTENT;      // (not reached for L <= 1024)
+    g.r_lo = (int)r_lo;
+    const int aw = form == 0 ? 1 : 2;
     hipStream_t s = (hipStream_t)stream;
-    const unsigned grid = (unsigned)(P * g.nchunk);
     if (form == 0) mf_launch<0>(g, grid, lds, s);
     else if (form == 1) mf_launch<1>(g, grid, lds, s);
     else mf_launch<2>(g, grid, lds, s);

@@ -5,7 +5,10 @@ methods against the reference-generated golden values, and the SCF driver.
 Parity bound (derived, not tuned): an element of W is a sum of n = 2 R L products; every summation order satisfies
 |W - W_exact| <= gamma_(n+2) * A with gamma_k = k eps / (1 - k eps), eps = 2^-53, A = the formula on |u|, |D|, |cj|,
 |ck| (complex results: a further factor 2 sqrt 2); W_exact is the numpy.longdouble evaluation.  The largest observed
-error / bound per dtype form is printed and, when QS_MEAN_FIELD_PARITY_OUT names a file, written there."""
+error / bound per dtype form is printed and, when QS_MEAN_FIELD_PARITY_OUT names a file, written there.
+
+The sizes here stop at L = 96; the launch geometries above that (more than one column block, CT = 8, two live waves per
+tile row, capped chunk lengths) are run by tests/test_gpu_mean_field_geometry.py."""
 
 import os
 
