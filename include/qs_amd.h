@@ -457,7 +457,10 @@ const char* qs_last_dispatch(void);
  *     address), "comm_drop_wait" (TEST HOOK of the sharded entry points: a bit
  *     mask of stream waits between the caller's stream and the communicator's
  *     to leave out -- the negative control of the asynchronous stand-in
- *     transport, tests/test_gpu_async_transport.py; never set it elsewhere).
+ *     transport, tests/test_gpu_async_transport.py; never set it elsewhere),
+ *     "lead_rows_max" (qs_transform_two_body_blocks: the most leading rows M0
+ *     whose step a takes the streaming kernel of qs_lead_contract, 0 ... 32;
+ *     a value outside that range is refused with QS_ERR_BAD_EXTENT).
  *   qs_probe_mfma_f64: register-resident fp64 MFMA loop, `blocks` workgroups
  *     of 4 waves, each wave issuing iters*8 v_mfma_f64_16x16x4_f64
  *     (flops = blocks*4*iters*8*2048); `sink` is a device scratch of
@@ -516,6 +519,51 @@ int qs_mean_field(int u_dtype, int d_dtype, const void* u_slab, const void* D, v
  * extents; QS_ERR_BAD_EXTENT for n_out < 7, QS_ERR_NULL_POINTER for out == 0). */
 int qs_mean_field_plan(int u_dtype, int d_dtype, int64_t L, int64_t P, int64_t R,
                        int64_t* out, int n_out);
+
+/*
+ * Leading-index contraction with a few rows (csrc/qs_lead_contract.hip):
+ *   T[i, x] = sum_a A[i, a] * B[a, x]      A (m, k) lda;  B (k, n) ldb;  T (m, n) ldt
+ * for 1 <= m <= 32, any k >= 1 and any n >= 1 (odd included), row-major, leading
+ * dimensions in elements (lda >= k, ldb >= n, ldt >= n).  dtype pairs (A, B):
+ * (F64, F64) -> T fp64; (C128, C128) -> T complex128; (C128, F64) -> T
+ * complex128 with B read as stored; a complex B with a real A is
+ * QS_ERR_BAD_DTYPE.  One read of B, no workspace.  Every T[i, x] is ONE fused
+ * multiply-add chain over ascending a: row i of an m-row call has the bits of
+ * the 1-row call on that row, and column x depends neither on n, ldb nor on the
+ * launch geometry.  Nothing outside B's (k - 1) * ldb + n elements is read.
+ * `T` must not overlap `A` or `B`.
+ */
+int qs_lead_contract(int a_dtype, int b_dtype, const void* A, const void* B, void* T,
+                     int64_t m, int64_t n, int64_t k, int64_t lda, int64_t ldb, int64_t ldt,
+                     void* stream);
+
+/*
+ * Four-index transform with ONE coefficient matrix PER INDEX, to a block:
+ *   out[p,q,r,s] = sum_abcd Ct0[p,a] Ct1[q,b] u[a,b,c,d] C2[c,r] C3[d,s]
+ *   u (L,L,L,L);  Ct0 (M0,L), Ct1 (M1,L): bra rows;  C2 (L,M2), C3 (L,M3): ket
+ *   columns;  out (M0,M1,M2,M3); all contiguous.
+ * Contraction order a, b, d, c -- the LEADING index first, so every step works
+ * on a tensor already shrunk by the blocks in front of it: put the small blocks
+ * (the occupied orbitals of <ij|ab>) first; for a Hermitian u, <ab|ij> is the
+ * conjugate of <ij|ab>.  Step a is qs_lead_contract (one read of u) when
+ * M0 <= the tuning key "lead_rows_max" (0 ... 32, default 8), otherwise one
+ * tiled product; b, d and c are batched products of the general dispatch.
+ * dtype pairs (u, C) as qs_mean_field: (F64, F64); (C128, C128); (F64, C128) ->
+ * complex128 out with u read as stored; (C128, F64) is QS_ERR_BAD_DTYPE.
+ * 1 <= L <= 4096, 1 <= Mi <= L.
+ * Workspace, in elements of the result dtype (Le = rounded up to even):
+ *   Le(L * (M0 + M2)) + M0 * L^3 + M0 * M1 * L^2
+ * = scratch for C2 transposed and the split rows of Ct0, the intermediate of
+ * step a, and that of step b; the intermediate of step d (M0 * M1 * L * M3
+ * elements) reuses the place of step a's, which it fits since M1 * M3 <= L^2.
+ * `out` must not overlap any operand or the workspace, nor the workspace `u`.
+ */
+int64_t qs_transform_two_body_blocks_workspace(int u_dtype, int c_dtype, int64_t L,
+                                               int64_t M0, int64_t M1, int64_t M2, int64_t M3);
+int qs_transform_two_body_blocks(int u_dtype, int c_dtype, const void* u, const void* Ct0,
+                                 const void* Ct1, const void* C2, const void* C3, void* out,
+                                 void* work, int64_t work_bytes, int64_t L, int64_t M0,
+                                 int64_t M1, int64_t M2, int64_t M3, void* stream);
 int qs_probe_mfma_f64(void* sink, int64_t blocks, int64_t iters, void* stream);
 int qs_probe_stream_copy(const void* src, void* dst, int64_t bytes, void* stream);
 

@@ -367,6 +367,20 @@ class BasisSet:
         Ct = None if C_tilde is None else _stage(C_tilde)
         return _deliver(kernels.transform_two_body(_stage(u), _stage(C), Ct), np)
 
+    def transform_two_body_blocks(self, bras, kets):
+        """``out[pqrs] = Ct0[pa] Ct1[qb] u[abcd] C2[cr] C3[ds]`` with ``bras = (Ct0, Ct1)`` (rows, (M, l)) and ``kets =
+        (C2, C3)`` (columns, (l, M)): a block of the transformed two-body tensor -- ``<ij|ab>`` from occupied bras and
+        virtual kets -- without the full transform (kernels.transform_two_body_blocks: leading index first, one read
+        of ``u`` for a small leading block).  Returns a new array in this basis set's array module; the basis set is
+        left as it is."""
+        if is_sharded(self.u):
+            raise NotImplementedError(
+                "transform_two_body_blocks does not take a sharded u: the block transform is not sharded (gather u, "
+                "or run the sharded transform_two_body_elements and slice)")
+        (Ct0, Ct1), (C2, C3) = bras, kets
+        return _deliver(
+            kernels.transform_two_body_blocks(_stage(self.u), _stage(Ct0), _stage(Ct1), _stage(C2), _stage(C3)), self.np)
+
     def get_transformed_h(self, C):
         return self.transform_one_body_elements(self.h, C, np=self.np)
 

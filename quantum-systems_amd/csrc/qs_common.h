@@ -217,6 +217,9 @@ struct Tuning {
     int gemm_fast_unaligned = 1; // 16-byte items of the VALU-free kernel's edge form also at odd strides / extents (0: 8-byte items there)
     int comm_drop_wait = 0;      // TEST HOOK (qs_comm.hip): bit mask of stream waits of the sharded entry points to leave out -- the negative
                                  // test of the asynchronous stand-in transport; never set outside tests/
+    int lead_rows_max = 8;       // qs_transform_two_body_blocks: most leading rows M0 that take qs_lead_contract.hip's streaming kernel for
+                                 // step a (0 = never, at most 32 = the kernel's own limit); above it step a is one tiled product.
+                                 // 8 = the 8-row instantiation, the largest measured one that beats the product (profiles/r08_blocks.txt)
     int sandwich = 1;            // 4-wide fused passes of a small-basis transform: 0 off, 1 both (d, c) and (b, a), 2 (d, c) only, 3 (b, a) only;
                                  // tuning runs, wherever the kernel exists (not only where it measured faster): 4 both, 5 (d, c) only, 6 (b, a) only
 };

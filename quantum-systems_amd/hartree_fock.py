@@ -8,6 +8,7 @@ one ``qs_mean_field`` launch, one read of ``u`` -- and everything else is O(l^3)
 
     hf = HartreeFock(system)
     C, epsilon, energies = hf.scf(tol=1e-10)
+    e2 = hf.mp2()                       # second-order correlation energy on the converged orbitals
     hf.change_system_basis()            # system.change_basis(C): the Fock matrix is diagonal now
 
 ``system.change_to_hf_basis()`` keeps raising ``NotImplementedError`` as in the reference.
@@ -43,6 +44,7 @@ class HartreeFock:
         self.energies = []
         self.converged = False
         self.iterations = 0
+        self._basis_changed = False
 
     # -- the one O(l^4) step of an iteration
     def _mean_field(self, u, rho):
@@ -127,4 +129,18 @@ class HartreeFock:
         if self.C is None:
             raise RuntimeError("run scf() first")
         self.system.change_basis(self.C)
+        self._basis_changed = True
         return self.system
+
+    def mp2(self):
+        """Second-order Moller-Plesset correlation energy on the converged orbitals:
+        ``moller_plesset.mp2_energy(system, C, epsilon)``."""
+        from .moller_plesset import mp2_energy
+
+        if self.C is None:
+            raise RuntimeError("run scf() first")
+        if self._basis_changed:
+            raise RuntimeError(
+                "the system is in its Hartree-Fock basis already (change_system_basis): C no longer refers to it -- "
+                "call moller_plesset.mp2_energy(system)")
+        return mp2_energy(self.system, self.C, self.epsilon)

@@ -642,6 +642,78 @@ def mean_field(u, D, cj=1.0, ck=0.0, r_lo=0, out=None):
     return out
 
 
+@_plain
+def lead_contract(A, B, out=None):
+    """``A @ B`` for a few rows: ``A`` (m, k) with ``1 <= m <= 32``, ``B`` (k, n) -- contiguous, or a column slice
+    ``W[:, :n]`` of a wider row-major buffer, read in place -- on the streaming kernel of ``qs_lead_contract``: one
+    read of ``B``, every element one fused multiply-add chain over ascending ``a``.  A real ``B`` with a complex ``A``
+    stays real (complex result).  Returns ``T`` (m, n)."""
+    lib = _lib.load()
+    dt = result_dtype(A, B)
+    bdt = _F64 if isinstance(B, torch.Tensor) and B.dtype == _F64 else dt
+    A = _dev(A, dt)
+    if not isinstance(B, torch.Tensor):
+        raise TypeError("expected a torch.Tensor")
+    if A.dim() != 2 or B.dim() != 2 or B.shape[0] != A.shape[1]:
+        raise ValueError("A must be (m, k) and B (k, n)")
+    if not (B.is_cuda and B.dtype == bdt and not B.is_conj() and B.stride(1) == 1 and
+            (B.shape[0] == 1 or B.stride(0) >= B.shape[1])):
+        B = _dev(B, bdt)
+    m, k = A.shape
+    n = B.shape[1]
+    ldb = B.stride(0) if k > 1 else max(n, B.stride(0))
+    if not 1 <= m <= 32:
+        raise ValueError(f"lead_contract takes 1 ... 32 rows, got {m}")
+    if out is None:
+        out = torch.empty((m, n), dtype=dt, device=B.device)
+    else:
+        _check_out(out, (m, n), dt, "lead_contract")
+    with _on_device_of(A, B, out):
+        _ran(
+            lib.qs_lead_contract(dtype_code(dt), dtype_code(bdt), A.data_ptr(), B.data_ptr(), out.data_ptr(), m, n, k,
+                                 k, ldb, n, _stream()),
+            "qs_lead_contract",
+        )
+    return out
+
+
+@_plain
+def transform_two_body_blocks(u, Ct0, Ct1, C2, C3, out=None):
+    """``out[pqrs] = Ct0[pa] Ct1[qb] u[abcd] C2[cr] C3[ds]``: one coefficient matrix per index
+    (``qs_transform_two_body_blocks``), contracted in the order a, b, d, c so that small blocks in front shrink the
+    tensor first -- ``<ij|ab>`` costs one read of ``u``.  ``Ct0`` (M0, L) and ``Ct1`` (M1, L) are bra ROWS, ``C2``
+    (L, M2) and ``C3`` (L, M3) ket COLUMNS.  A real ``u`` against complex coefficients stays real."""
+    lib = _lib.load()
+    dt = result_dtype(u, Ct0, Ct1, C2, C3)
+    udt = _F64 if isinstance(u, torch.Tensor) and u.dtype == _F64 else dt
+    u = _dev(u, udt)
+    Ct0, Ct1, C2, C3 = _dev(Ct0, dt), _dev(Ct1, dt), _dev(C2, dt), _dev(C3, dt)
+    if u.dim() != 4 or any(c.dim() != 2 for c in (Ct0, Ct1, C2, C3)):
+        raise ValueError("u must be (L, L, L, L) and the coefficient blocks 2-D")
+    L = u.shape[0]
+    M0, M1, M2, M3 = Ct0.shape[0], Ct1.shape[0], C2.shape[1], C3.shape[1]
+    if tuple(u.shape) != (L, L, L, L) or not (Ct0.shape[1] == Ct1.shape[1] == C2.shape[0] == C3.shape[0] == L):
+        raise ValueError(
+            f"u {tuple(u.shape)}, bras {tuple(Ct0.shape)} {tuple(Ct1.shape)}, kets {tuple(C2.shape)} {tuple(C3.shape)}: "
+            "need u (L,L,L,L), bras (M0,L) (M1,L) and kets (L,M2) (L,M3)")
+    ucode, code = dtype_code(udt), dtype_code(dt)
+    nbytes = check(lib.qs_transform_two_body_blocks_workspace(ucode, code, L, M0, M1, M2, M3), "workspace query")
+    if out is None:
+        out = torch.empty((M0, M1, M2, M3), dtype=dt, device=u.device)
+    else:
+        _check_out(out, (M0, M1, M2, M3), dt, "transform_two_body_blocks")
+    with _on_device_of(u, Ct0, Ct1, C2, C3, out):
+        work = workspace.get(nbytes, u.device)
+        _ran(
+            lib.qs_transform_two_body_blocks(
+                ucode, code, u.data_ptr(), Ct0.data_ptr(), Ct1.data_ptr(), C2.data_ptr(), C3.data_ptr(), out.data_ptr(),
+                work.data_ptr(), work.numel(), L, M0, M1, M2, M3, _stream(),
+            ),
+            "qs_transform_two_body_blocks",
+        )
+    return out
+
+
 class RcclComm:
     """The C ABI's communicator (``qs_comm_init``: RCCL over xGMI, one process per GPU) for hosts that drive the
     library from Python without ``torch.distributed``.  ``unique_id()`` on one rank, the 128 bytes to the others by

@@ -104,6 +104,9 @@ class QuantumSystem(metaclass=abc.ABCMeta):
     def transform_two_body_elements(self, u, C, C_tilde=None):
         return self._basis_set.transform_two_body_elements(u, C, np=self.np, C_tilde=C_tilde)
 
+    def transform_two_body_blocks(self, bras, kets):
+        return self._basis_set.transform_two_body_blocks(bras, kets)
+
     def compute_particle_density(self, rho_qp, C=None, C_tilde=None):
         return self._basis_set.compute_particle_density(rho_qp, C=C, C_tilde=C_tilde)
 
