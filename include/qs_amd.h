@@ -521,6 +521,52 @@ int qs_mean_field_plan(int u_dtype, int d_dtype, int64_t L, int64_t P, int64_t R
                        int64_t* out, int n_out);
 
 /*
+ * The same contraction for a BATCH of densities from one read of `u` per group
+ * of G of them (csrc/qs_mean_field_batch.hip):
+ *   W_k[p,q] = cj[k] * sum_{r,s} u[p,r,q,s] D_k[s,r] + ck[k] * sum_{r,s} u[p,r,s,q] D_k[s,r]
+ *   u_slab : (P, R, L, L) as for qs_mean_field;  D : (ND, L, L);  W : (ND, P, L);
+ *   cj, ck : HOST arrays of ND weights (read before the call returns).
+ * dtype pairs, extents and r_lo as qs_mean_field; 1 <= ND <= 65536.  A zero
+ * weight leaves its sum out of W_k.  ceil(ND / G) streaming launches and one
+ * closing launch.  G is a property of the dtype pair (fp64 8; complex128 4;
+ * real u with complex D 4), halved for the L at which the group's share of the
+ * 64 KB of LDS -- one column of every density plus the unit's sums -- no longer
+ * fits (qs_mean_field_batch_plan reports it).
+ * Deterministic, and independent of the batch: the r range is cut into chunks of
+ *   Rc = the largest rc <= ceil(R / min(ceil(4096 / L), R)) with
+ *        (rc * Le + nrb * RB + ncb * CT * cpi) * G * aw <= 8192   (rc >= 1)
+ * consecutive r (Le, aw, cpi, CT, RB, ncb, nrb: see qs_mean_field_batch_plan), a
+ * function of (L, R, dtypes) only -- not of ND, of k, or of whether a group is
+ * partial.  W_k has the same bits whether D_k is sent alone or anywhere in a
+ * batch of any size, and row p of a slab call has the bits of row p of the full
+ * call.  (Equality of bits with qs_mean_field is not promised.)
+ * Workspace: ND * P * L * ceil(R / Rc) elements of W's dtype; nothing else is
+ * allocated or written.  `W` must not overlap `u_slab`, `D` or the workspace.
+ * Errors as qs_mean_field, checked in the same order before any HIP call;
+ * ND < 1 is QS_ERR_BAD_EXTENT, a null weight array QS_ERR_NULL_POINTER.
+ */
+int64_t qs_mean_field_batch_workspace(int u_dtype, int d_dtype, int64_t L, int64_t P, int64_t R,
+                                      int64_t ND);
+int qs_mean_field_batch(int u_dtype, int d_dtype, const void* u_slab, const void* D, void* W,
+                        int64_t L, int64_t P, int64_t R, int64_t r_lo, int64_t ND,
+                        const double* cj, const double* ck, void* workspace,
+                        int64_t workspace_bytes, void* stream);
+/* The launch geometry qs_mean_field_batch uses, as numbers (host only, no HIP
+ * call; test hook).  Writes 9 values to `out` (n_out >= 9):
+ *   {G, passes, Rc, nchunk, ct_log, ncb, nrb, lds_bytes, grid}
+ * G densities per load of u, passes = ceil(ND / G) streaming launches; CT =
+ * 1 << ct_log column threads of one 16-byte item (cpi = 2 real columns or 1
+ * complex element of u), RT = 256 / CT row threads of 4 rows: a tile is RB =
+ * 4 RT rows by CT * cpi columns, a slab ncb x nrb tiles; lds_bytes = 8 * aw * G *
+ * (Rc * Le + nrb * RB + ncb * CT * cpi) dynamic LDS of a full group, Le = L
+ * rounded up to even, aw = 1 for an fp64 D and 2 for a complex one; grid =
+ * P * nchunk workgroups per launch.  All but `passes` and `grid` depend on
+ * (dtypes, L, R) only.  Returns 0 or what qs_mean_field_batch_workspace refuses
+ * (QS_ERR_BAD_EXTENT for n_out < 9, QS_ERR_NULL_POINTER for out == 0). */
+int qs_mean_field_batch_plan(int u_dtype, int d_dtype, int64_t L, int64_t P, int64_t R,
+                             int64_t ND, int64_t* out, int n_out);
+
+/*
  * Leading-index contraction with a few rows (csrc/qs_lead_contract.hip):
  *   T[i, x] = sum_a A[i, a] * B[a, x]      A (m, k) lda;  B (k, n) ldb;  T (m, n) ldt
  * for 1 <= m <= 32, any k >= 1 and any n >= 1 (odd included), row-major, leading

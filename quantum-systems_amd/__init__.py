@@ -11,10 +11,11 @@ The directory is named ``quantum-systems_amd`` after the upstream project;
 import it as ``quantum_systems_amd`` (the sibling shim package aliases it).
 """
 
-from . import _lib, kernels, moller_plesset, sharded  # noqa: F401
+from . import _lib, configuration_interaction, kernels, moller_plesset, sharded  # noqa: F401
 from .array_module import DeviceArray, DeviceModule, hip
 from .sharded_module import ShardedDeviceModule, ShardedTensor4
 from .basis_set import BasisSet, ChangeBasisPlan
+from .configuration_interaction import CIS
 from .custom_system import construct_custom_system, setup_basis_set
 from .general_orbital_system import GeneralOrbitalSystem
 from .hartree_fock import HartreeFock
@@ -28,7 +29,7 @@ from .two_dim_ho import TwoDimensionalDoubleWell, TwoDimensionalHarmonicOscillat
 
 __all__ = [
     "BasisSet", "RandomBasisSet", "QuantumSystem", "SpatialOrbitalSystem",
-    "GeneralOrbitalSystem", "HartreeFock", "mp2_energy", "setup_basis_set", "construct_custom_system",
+    "GeneralOrbitalSystem", "HartreeFock", "mp2_energy", "CIS", "configuration_interaction", "setup_basis_set", "construct_custom_system",
     "TwoDimensionalHarmonicOscillator", "TwoDimensionalDoubleWell", "TwoDimHarmonicOscB", "ODQD", "ODSincDVR",
     "ChangeBasisPlan", "hip", "DeviceModule", "DeviceArray", "ShardedDeviceModule", "ShardedTensor4", "kernels", "sharded",
 ]

@@ -78,6 +78,10 @@ SIGNATURES = {
         c_int, [c_int, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, ctypes.c_double, ctypes.c_double,
                 c_ptr, c_i64, c_ptr]),
     "qs_mean_field_plan": (c_int, [c_int, c_int, c_i64, c_i64, c_i64, c_ptr, c_int]),
+    "qs_mean_field_batch_workspace": (c_i64, [c_int, c_int, c_i64, c_i64, c_i64, c_i64]),
+    "qs_mean_field_batch": (
+        c_int, [c_int, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
+    "qs_mean_field_batch_plan": (c_int, [c_int, c_int, c_i64, c_i64, c_i64, c_i64, c_ptr, c_int]),
     "qs_lead_contract": (c_int, [c_int, c_int, c_ptr, c_ptr, c_ptr] + [c_i64] * 6 + [c_ptr]),
     "qs_transform_two_body_blocks_workspace": (c_i64, [c_int, c_int] + [c_i64] * 5),
     "qs_transform_two_body_blocks": (

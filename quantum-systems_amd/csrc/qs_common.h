@@ -220,6 +220,8 @@ struct Tuning {
     int lead_rows_max = 8;       // qs_transform_two_body_blocks: most leading rows M0 that take qs_lead_contract.hip's streaming kernel for
                                  // step a (0 = never, at most 32 = the kernel's own limit); above it step a is one tiled product.
                                  // 8 = the 8-row instantiation, the largest measured one that beats the product (profiles/r08_blocks.txt)
+    int mean_field_batch_g = 0;  // qs_mean_field_batch: densities per load of u, 0 = the shipped group size of the form; 1, 2, 4, 8 = tuning runs
+                                 // (the chunk length follows the group size: results of different settings agree to rounding, not bit for bit)
     int sandwich = 1;            // 4-wide fused passes of a small-basis transform: 0 off, 1 both (d, c) and (b, a), 2 (d, c) only, 3 (b, a) only;
                                  // tuning runs, wherever the kernel exists (not only where it measured faster): 4 both, 5 (d, c) only, 6 (b, a) only
 };

@@ -9,6 +9,7 @@ one ``qs_mean_field`` launch, one read of ``u`` -- and everything else is O(l^3)
     hf = HartreeFock(system)
     C, epsilon, energies = hf.scf(tol=1e-10)
     e2 = hf.mp2()                       # second-order correlation energy on the converged orbitals
+    omega, X = hf.cis().solve(4)        # lowest excited states (configuration interaction singles)
     hf.change_system_basis()            # system.change_basis(C): the Fock matrix is diagonal now
 
 ``system.change_to_hf_basis()`` keeps raising ``NotImplementedError`` as in the reference.
@@ -144,3 +145,16 @@ class HartreeFock:
                 "the system is in its Hartree-Fock basis already (change_system_basis): C no longer refers to it -- "
                 "call moller_plesset.mp2_energy(system)")
         return mp2_energy(self.system, self.C, self.epsilon)
+
+    def cis(self, **kw):
+        """Configuration interaction singles on the converged orbitals:
+        ``configuration_interaction.CIS(system, C, epsilon, **kw)``."""
+        from .configuration_interaction import CIS
+
+        if self.C is None:
+            raise RuntimeError("run scf() first")
+        if self._basis_changed:
+            raise RuntimeError(
+                "the system is in its Hartree-Fock basis already (change_system_basis): C no longer refers to it -- "
+                "call configuration_interaction.CIS(system)")
+        return CIS(self.system, self.C, self.epsilon, **kw)

@@ -6,6 +6,8 @@ and the current HIP stream.  Every function hands raw device pointers to
 CPU path: a tensor that is not on a ``cuda`` device is an error.
 """
 
+import ctypes
+
 import torch
 
 from . import _lib
@@ -638,6 +640,60 @@ def mean_field(u, D, cj=1.0, ck=0.0, r_lo=0, out=None):
                 work.data_ptr(), work.numel(), _stream(),
             ),
             "qs_mean_field",
+        )
+    return out
+
+
+def _weights(x, nd, name):
+    """A scalar or a length-ND sequence of weights as a host array of ND doubles."""
+    if isinstance(x, torch.Tensor):
+        x = x.tolist()
+    scalar = getattr(x, "ndim", None) == 0 or not hasattr(x, "__len__")       # a 0-d array has __len__ and no length
+    vals = [float(x)] * nd if scalar else [float(v) for v in x]
+    if len(vals) != nd:
+        raise ValueError(f"{name} has {len(vals)} weights for {nd} densities")
+    return (ctypes.c_double * nd)(*vals)
+
+
+@_plain
+def mean_field_batch(u, D, cj=1.0, ck=0.0, r_lo=0, out=None):
+    """The mean-field contraction of ``mean_field`` for a batch of densities from ONE read of ``u`` per group of G of
+    them (``qs_mean_field_batch``):
+
+        W[k,p,q] = cj[k] * sum_rs u[p,r,q,s] D[k,s,r]  +  ck[k] * sum_rs u[p,r,s,q] D[k,s,r]
+
+    ``u`` is (P, R, L, L) as for ``mean_field``, ``D`` is (ND, L, L), ``cj`` / ``ck`` are scalars or length-ND
+    sequences.  ``W[k]`` has the same bits whether ``D[k]`` is sent alone or anywhere in a batch of any size.
+    Returns ``W`` (ND, P, L)."""
+    lib = _lib.load()
+    dt = result_dtype(u, D)
+    udt = _F64 if isinstance(u, torch.Tensor) and u.dtype == _F64 else dt
+    u = _dev(u, udt)
+    D = _dev(D, dt)
+    if u.dim() != 4 or D.dim() != 3:
+        raise ValueError("u must be (P, R, L, L) and D (ND, L, L)")
+    P, R, L = u.shape[0], u.shape[1], u.shape[3]
+    ND = D.shape[0]
+    if u.shape[2] != L or tuple(D.shape[1:]) != (L, L) or ND < 1:
+        raise ValueError(f"u has shape {tuple(u.shape)}, D {tuple(D.shape)}: need u (P, R, L, L) and D (ND, L, L), ND >= 1")
+    if not (1 <= P <= L and 1 <= R and 0 <= r_lo and r_lo + R <= L):
+        raise ValueError(f"slab of {P} rows and second indices [{r_lo}, {r_lo + R}) does not fit L = {L}")
+    wj, wk = _weights(cj, ND, "cj"), _weights(ck, ND, "ck")
+    ucode, dcode = dtype_code(udt), dtype_code(dt)
+    nbytes = check(lib.qs_mean_field_batch_workspace(ucode, dcode, L, P, R, ND), "workspace query")
+    if out is None:
+        out = torch.empty((ND, P, L), dtype=dt, device=u.device)
+    else:
+        _check_out(out, (ND, P, L), dt, "mean_field_batch")
+    with _on_device_of(u, D, out):
+        work = workspace.get(nbytes, u.device)
+        _ran(
+            lib.qs_mean_field_batch(
+                ucode, dcode, u.data_ptr(), D.data_ptr(), out.data_ptr(), L, P, R, int(r_lo), ND,
+                ctypes.cast(wj, ctypes.c_void_p), ctypes.cast(wk, ctypes.c_void_p),
+                work.data_ptr(), work.numel(), _stream(),
+            ),
+            "qs_mean_field_batch",
         )
     return out
 

@@ -62,6 +62,21 @@ class QuantumSystem(metaclass=abc.ABCMeta):
             return sharded_basis.mean_field(u, rho_qp, cj, ck, self.np)
         return _deliver(kernels.mean_field(_stage(u), _stage(rho_qp), cj=cj, ck=ck), self.np)
 
+    def construct_mean_fields_from_densities(self, rhos, u=None):
+        """``construct_mean_field_from_density`` for a stack of densities ``rhos`` (ND, l, l) from ONE read of ``u`` per
+        group of them (``kernels.mean_field_batch``).  Returns (ND, l, l); every ``W[k]`` has the same bits whatever
+        else is in the stack."""
+        from . import kernels
+        from .basis_set import _deliver, _stage
+        from .sharded_module import is_sharded
+
+        u = self.u if u is None else u
+        if is_sharded(u):
+            raise NotImplementedError("construct_mean_fields_from_densities does not take a sharded u: "
+                                      "the batched mean-field contraction is not sharded")
+        cj, ck = self._mean_field_weights()
+        return _deliver(kernels.mean_field_batch(_stage(u), _stage(rhos), cj=cj, ck=ck), self.np)
+
     def construct_fock_matrix_from_density(self, rho_qp, h=None, u=None, f=None):
         """``f = h + W(rho)``: ``construct_fock_matrix`` for a general density instead of the reference determinant
         (with rho = that determinant the two agree).  ``f`` may supply the buffer, which is filled and returned."""
