@@ -460,7 +460,9 @@ const char* qs_last_dispatch(void);
  *     transport, tests/test_gpu_async_transport.py; never set it elsewhere),
  *     "lead_rows_max" (qs_transform_two_body_blocks: the most leading rows M0
  *     whose step a takes the streaming kernel of qs_lead_contract, 0 ... 32;
- *     a value outside that range is refused with QS_ERR_BAD_EXTENT).
+ *     a value outside that range is refused with QS_ERR_BAD_EXTENT),
+ *     "pair_contract_g" (qs_pair_contract: vectors per load of U, 0 = the
+ *     shipped group size of the dtype pair, 1, 2, 4 or 8 for tuning runs).
  *   qs_probe_mfma_f64: register-resident fp64 MFMA loop, `blocks` workgroups
  *     of 4 waves, each wave issuing iters*8 v_mfma_f64_16x16x4_f64
  *     (flops = blocks*4*iters*8*2048); `sink` is a device scratch of
@@ -610,6 +612,47 @@ int qs_transform_two_body_blocks(int u_dtype, int c_dtype, const void* u, const 
                                  const void* Ct1, const void* C2, const void* C3, void* out,
                                  void* work, int64_t work_bytes, int64_t L, int64_t M0,
                                  int64_t M1, int64_t M2, int64_t M3, void* stream);
+/*
+ * Contraction with a few vectors over the TRAILING index, one read of the matrix
+ * per group of G vectors (csrc/qs_pair_contract.hip):
+ *   S[k, x] = sum_y U[x * ldu + y] * T[k * Y + y]      (no conjugation)
+ *   U : X rows of Y elements, row-major, ldu >= Y (elements);  T : (K, Y);  S : (K, X).
+ * With U = u viewed as (l^2, l^2) this is S[k,p,q] = sum_rs u[p,q,r,s] T[k,r,s]:
+ * the u-dependent part of the sigma vector of a two-particle full CI, and the
+ * particle-particle ladder of coupled-cluster doubles on the untransformed tensor.
+ * Replaces np.einsum("pqrs,krs->kpq") / np.tensordot(u, T, ((2, 3), (0, 1))).
+ * dtype pairs (U, T): (F64, F64) -> S fp64; (C128, C128) -> S complex128;
+ * (F64, C128) -> S complex128 with U read as stored (two real accumulations per
+ * element, no complex copy of U); (C128, F64) is QS_ERR_BAD_DTYPE.
+ * 1 <= X <= 2^32, 1 <= Y <= ldu <= 2^24 (odd Y and odd ldu included), 1 <= K <= 65536.
+ * ceil(K / G) streaming launches and nothing else: a wave of 64 lanes walks along
+ * four rows in steps of 64 16-byte items and closes each row sum once, so y is
+ * never split and the workspace is 0 bytes (`work` may be NULL; the query stays in
+ * the ABI for a geometry that would split y).  G is a property of the dtype pair
+ * (fp64 8; complex128 8; real U with complex T 4), the tuning key
+ * "pair_contract_g" (0 = shipped, 1, 2, 4, 8; anything else QS_ERR_BAD_EXTENT)
+ * overrides it for the calling thread.  A partial last group runs on the smallest
+ * instantiation that holds it.
+ * Promises (tests/test_gpu_pair_contract.py):
+ *   1. S[k] has the same bits alone and at any position in a batch of any K (and
+ *      under any "pair_contract_g");
+ *   2. row x has the same bits whatever X, whatever ldu and wherever the slab
+ *      starts (8- or 16-byte-aligned base, rows cut out of a larger tensor): the
+ *      lanes' shares of a row and the order of every sum depend on Y and the
+ *      dtype pair only;
+ *   3. repeating a call gives the same bits (no floating-point atomics);
+ *   4. a non-finite value in row x of U reaches S[:, x] only, one in T[k] reaches
+ *      S[k] only, and nothing outside U[0 : (X - 1) * ldu + Y) is read: the bytes
+ *      between rows (ldu > Y) are fetched with the rows' items only where an item
+ *      straddles a row's end, and then dropped by a select.
+ * Errors, checked in this order before any HIP call: dtype pair, extents
+ * (ldu < Y included), null U / T / S, misaligned pointer (element size), S
+ * overlapping U or T (QS_ERR_ALIAS), work_elems below the query (negative).
+ */
+int64_t qs_pair_contract_workspace(int u_dtype, int t_dtype, int64_t X, int64_t Y, int64_t K);
+int qs_pair_contract(int u_dtype, int t_dtype, const void* U, const void* T, void* S,
+                     int64_t X, int64_t Y, int64_t K, int64_t ldu,
+                     void* work, int64_t work_elems, void* stream);
 int qs_probe_mfma_f64(void* sink, int64_t blocks, int64_t iters, void* stream);
 int qs_probe_stream_copy(const void* src, void* dst, int64_t bytes, void* stream);
 

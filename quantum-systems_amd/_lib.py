@@ -86,6 +86,8 @@ SIGNATURES = {
     "qs_transform_two_body_blocks_workspace": (c_i64, [c_int, c_int] + [c_i64] * 5),
     "qs_transform_two_body_blocks": (
         c_int, [c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr] + [c_i64] * 6 + [c_ptr]),
+    "qs_pair_contract_workspace": (c_i64, [c_int, c_int, c_i64, c_i64, c_i64]),
+    "qs_pair_contract": (c_int, [c_int, c_int, c_ptr, c_ptr, c_ptr] + [c_i64] * 4 + [c_ptr, c_i64, c_ptr]),
 }
 
 ABI_VERSION = 4

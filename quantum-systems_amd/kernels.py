@@ -734,6 +734,55 @@ def lead_contract(A, B, out=None):
 
 
 @_plain
+def pair_contract(u, T, out=None):
+    """``S[k,p,q] = sum_rs u[p,q,r,s] T[k,r,s]`` (no conjugation) on the streaming kernel of ``qs_pair_contract``: one
+    read of ``u`` per group of G amplitudes, ``u`` never reshaped or copied.  ``u`` is (P, Q, R, S'), contiguous, a
+    leading slice ``w[lo:hi]`` of a contiguous tensor, or rows of R S' contiguous elements at one uniform distance
+    (``w[:, :, :R * S'].unflatten(2, (R, S'))`` of a wider buffer), all read in place; ``T`` is (K, R, S') or (R, S').  A real ``u`` with a complex
+    ``T`` stays real (complex result).  ``S[k]`` has the same bits alone and anywhere in a batch of any size, and a row
+    ``(p, q)`` the same bits whatever slice of ``u`` it is sent in.  Returns (K, P, Q), or (P, Q) for a 2-D ``T``."""
+    lib = _lib.load()
+    dt = result_dtype(u, T)
+    udt = _F64 if isinstance(u, torch.Tensor) and u.dtype == _F64 else dt
+    if not isinstance(u, torch.Tensor):
+        raise TypeError("expected a torch.Tensor")
+    if u.dim() != 4 or not isinstance(T, torch.Tensor) or T.dim() not in (2, 3):
+        raise ValueError("u must be (P, Q, R, S) and T (K, R, S) or (R, S)")
+    # rows (p, q) of R * S contiguous elements at one uniform distance ldu >= R * S are read in place
+    ldu = u.stride(1) if u.shape[0] * u.shape[1] > 1 else u.shape[2] * u.shape[3]
+    if not (u.is_cuda and u.dtype == udt and not u.is_conj() and min(u.shape) >= 1 and u.stride(3) == 1 and
+            u.stride(2) == u.shape[3] and ldu >= u.shape[2] * u.shape[3] and
+            (u.shape[0] == 1 or u.shape[1] == 1 or u.stride(0) == u.shape[1] * ldu)):
+        u = _dev(u, udt)
+        ldu = u.shape[2] * u.shape[3]
+    elif u.shape[1] == 1 and u.shape[0] > 1:
+        ldu = u.stride(0)
+    T = _dev(T, dt)
+    single = T.dim() == 2
+    if single:
+        T = T[None]
+    P, Q, R, S_ = u.shape
+    K = T.shape[0]
+    if tuple(T.shape[1:]) != (R, S_) or K < 1 or min(P, Q, R, S_) < 1:
+        raise ValueError(f"u has shape {tuple(u.shape)}, T {tuple(T.shape)}: need u (P, Q, R, S) and T (K, R, S), K >= 1")
+    X, Y = P * Q, R * S_
+    ucode, tcode = dtype_code(udt), dtype_code(dt)
+    nbytes = check(lib.qs_pair_contract_workspace(ucode, tcode, X, Y, K), "workspace query")
+    if out is None:
+        out = torch.empty((P, Q) if single else (K, P, Q), dtype=dt, device=u.device)
+    else:
+        _check_out(out, (P, Q) if single else (K, P, Q), dt, "pair_contract")
+    with _on_device_of(u, T, out):
+        work = workspace.get(nbytes, u.device) if nbytes else None
+        _ran(
+            lib.qs_pair_contract(ucode, tcode, u.data_ptr(), T.data_ptr(), out.data_ptr(), X, Y, K, ldu,
+                                 work.data_ptr() if nbytes else None, work.numel() if nbytes else 0, _stream()),
+            "qs_pair_contract",
+        )
+    return out
+
+
+@_plain
 def transform_two_body_blocks(u, Ct0, Ct1, C2, C3, out=None):
     """``out[pqrs] = Ct0[pa] Ct1[qb] u[abcd] C2[cr] C3[ds]``: one coefficient matrix per index
     (``qs_transform_two_body_blocks``), contracted in the order a, b, d, c so that small blocks in front shrink the
