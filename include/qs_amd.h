@@ -462,7 +462,9 @@ const char* qs_last_dispatch(void);
  *     whose step a takes the streaming kernel of qs_lead_contract, 0 ... 32;
  *     a value outside that range is refused with QS_ERR_BAD_EXTENT),
  *     "pair_contract_g" (qs_pair_contract: vectors per load of U, 0 = the
- *     shipped group size of the dtype pair, 1, 2, 4 or 8 for tuning runs).
+ *     shipped group size of the dtype pair, 1, 2, 4 or 8 for tuning runs),
+ *     "det_ci_g" (qs_det_ci_sigma: vectors per walk of a determinant's
+ *     excitations, 0 = shipped, 1, 2, 4 or 8 for tuning runs).
  *   qs_probe_mfma_f64: register-resident fp64 MFMA loop, `blocks` workgroups
  *     of 4 waves, each wave issuing iters*8 v_mfma_f64_16x16x4_f64
  *     (flops = blocks*4*iters*8*2048); `sink` is a device scratch of
@@ -653,6 +655,54 @@ int64_t qs_pair_contract_workspace(int u_dtype, int t_dtype, int64_t X, int64_t 
 int qs_pair_contract(int u_dtype, int t_dtype, const void* U, const void* T, void* S,
                      int64_t X, int64_t Y, int64_t K, int64_t ldu,
                      void* work, int64_t work_elems, void* stream);
+/*
+ * Direct configuration interaction on Slater determinants (csrc/qs_det_ci.hip):
+ *   H = sum_pq ht[p,q] a+_p a_q + 1/4 sum_pqrs ut[p,q,r,s] a+_p a+_q a_s a_r
+ *   ht : (m, m) Hermitian;  ut : (m, m, m, m), ut[p,q,r,s] = <pq|rs> - <pq|sr>.
+ * A determinant is a 64-bit occupation mask over 1 <= m <= 63 orthonormal spin
+ * orbitals (bit p = orbital p occupied); the space is data: `dets` holds dim
+ * ascending, duplicate-free masks of exactly N bits, none at or above m (the
+ * full space, a spin sector, an excitation-truncated space, any subset).  A
+ * connection whose target is not in `dets` contributes nothing: the matrix of a
+ * subset is the projection of the full one.  The caller vouches for the list (a
+ * bit at or above m is masked off before it indexes anything; an unsorted list
+ * gives wrong numbers, never an access outside the arguments).
+ *   qs_det_ci_diagonal : D[I] = <I|H|I>, dim doubles (real in both forms).
+ *   qs_det_ci_sigma    : sigma[k * dim + I] = sum_J <I|H|J> c[J * ldc + k],
+ *       k < K.  c is stored with the K values of one determinant adjacent
+ *       (ldc >= K elements between determinants), sigma as K rows of dim.  D is
+ *       the output of qs_det_ci_diagonal for the same ht, ut and dets.
+ *       ceil(K / G) launches and nothing else: the thread that owns I walks its
+ *       single and double excitations once per group of G vectors, looks each
+ *       target up by binary search and feeds G running sums.  G is 8 in both
+ *       forms; the tuning key "det_ci_g" (0 = shipped, 1, 2, 4, 8; anything
+ *       else QS_ERR_BAD_EXTENT) overrides it for the calling thread.  A partial
+ *       last group runs on the smallest instantiation that holds it.  The
+ *       workspace is 0 bytes (`work` may be NULL).
+ *   qs_det_ci_density1 : rho[q * m + p] = sum_IJ conj(c[I]) <I|a+_p a_q|J> c[J]
+ *       for ONE vector c[dim]: one workgroup per (p, q), a fixed-order sum.
+ * dtype pairs (ht and ut, c): (F64, F64) and (C128, C128); any other pair is
+ * QS_ERR_BAD_DTYPE.  The diagonal takes the dtype of ht / ut, the density that
+ * of c (rho has it too).
+ * Promises (tests/test_gpu_det_ci.py):
+ *   1. sigma[k] has the same bits alone, at any position in a batch of any K and
+ *      under any "det_ci_g"; repeating a call gives the same bits (no atomics,
+ *      every product an explicit fma, a sum order fixed by I and dets);
+ *   2. nothing outside sigma[0 : K * dim), D[0 : dim), rho[0 : m * m) is written,
+ *      whatever dim is relative to the workgroup of 64 determinants.
+ * Errors, checked in this order before any HIP call: dtype pair, extents (m
+ * outside 1 ... 63, N outside 1 ... m, dim < 1 or > 2^31 - 1, K < 1, ldc < K),
+ * null pointer, misaligned pointer (element size; 8 for dets and D), an output
+ * overlapping an input (QS_ERR_ALIAS), work_elems below the query (negative).
+ */
+int64_t qs_det_ci_workspace(int h_dtype, int c_dtype, int64_t m, int64_t N, int64_t dim, int64_t K);
+int qs_det_ci_diagonal(int h_dtype, const void* ht, const void* ut, const int64_t* dets, double* D,
+                       int64_t m, int64_t N, int64_t dim, void* stream);
+int qs_det_ci_sigma(int h_dtype, int c_dtype, const void* ht, const void* ut, const int64_t* dets,
+                    const double* D, const void* c, void* sigma, int64_t m, int64_t N, int64_t dim,
+                    int64_t K, int64_t ldc, void* work, int64_t work_elems, void* stream);
+int qs_det_ci_density1(int c_dtype, const int64_t* dets, const void* c, void* rho,
+                       int64_t m, int64_t N, int64_t dim, void* stream);
 int qs_probe_mfma_f64(void* sink, int64_t blocks, int64_t iters, void* stream);
 int qs_probe_stream_copy(const void* src, void* dst, int64_t bytes, void* stream);
 

@@ -249,6 +249,11 @@ int qs_tuning_set(const char* key, int64_t value) {
         g_tune.pair_contract_g = (int)value;
         return QS_OK;
     }
+    if (!strcmp(key, "det_ci_g")) {
+        if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8) return QS_ERR_BAD_EXTENT;
+        g_tune.det_ci_g = (int)value;
+        return QS_OK;
+    }
     if (!strcmp(key, "lead_rows_max")) {
         if (value < 0 || value > 32) return QS_ERR_BAD_EXTENT;
         g_tune.lead_rows_max = (int)value;

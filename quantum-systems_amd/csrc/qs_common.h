@@ -224,6 +224,8 @@ struct Tuning {
                                  // (the chunk length follows the group size: results of different settings agree to rounding, not bit for bit)
     int pair_contract_g = 0;     // qs_pair_contract: vectors per load of U, 0 = the shipped group size of the form; 1, 2, 4, 8 = tuning runs
                                  // (every setting gives the same bits: the fma chains and the closing butterfly do not know G)
+    int det_ci_g = 0;            // qs_det_ci_sigma: vectors per walk of a determinant's excitations, 0 = the shipped group size of the form;
+                                 // 1, 2, 4, 8 = tuning runs (every setting gives the same bits: a vector's fma chain does not know G)
     int sandwich = 1;            // 4-wide fused passes of a small-basis transform: 0 off, 1 both (d, c) and (b, a), 2 (d, c) only, 3 (b, a) only;
                                  // tuning runs, wherever the kernel exists (not only where it measured faster): 4 both, 5 (d, c) only, 6 (b, a) only
 };

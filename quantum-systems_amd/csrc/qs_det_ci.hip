@@ -1,0 +1,367 @@
+// H c on Slater determinants (direct configuration interaction), its diagonal and the one-body density of a vector.
+//   H = sum_pq ht[p,q] a+_p a_q + 1/4 sum_pqrs ut[p,q,r,s] a+_p a+_q a_s a_r,   ut[p,q,r,s] = <pq|rs> - <pq|sr>
+// A determinant is a 64-bit occupation mask over m <= 63 orthonormal spin orbitals (bit p = orbital p occupied); the
+// space is an ascending, duplicate-free list dets[dim] of masks with N bits each -- the full space, a spin sector, an
+// excitation-truncated space or any other subset.  A connection whose target is not in the list contributes nothing:
+// the Hamiltonian of a subset is the projection of the full one.
+//
+//   D[I]        = <I|H|I> = sum_{i in I} ht[i,i] + sum_{i<j in I} ut[i,j,i,j]                        (real)
+//   sigma[k, I] = D[I] c[k,I] + sum_{p in I, q not in I} s (ht[p,q] + sum_{j in I, j != p} ut[p,j,q,j]) c[k, I-p+q]
+//                             + sum_{p1<p2 in I, q1<q2 not in I} s ut[p1,p2,q1,q2] c[k, I-p1-p2+q1+q2]
+//   rho[q, p]   = sum_I conj(c[I]) s c[I-p+q]                                                        (p in I, q not in I or q = p)
+// s = (-1)^(occupied orbitals strictly between the moved ones): one popcount of the mask between p and q for a single
+// excitation; for a double, that of p1 -> q1 on I times that of p2 -> q2 on the intermediate I-p1+q1.
+//
+// sigma is the GATHER form: the thread that owns I walks I's excitations with bit arithmetic (lowest set bit of the
+// occupied / of the empty mask, no occupation lists, so nothing is indexed in registers), finds the target by binary
+// search in dets, forms the matrix element from ht (a copy in LDS) and ut, and feeds the running sums of the G vectors
+// of the launch.  c is stored with the vectors of one determinant adjacent (c[J * ldc + k]): the G values one
+// connection needs come from one or two cache lines.  ut, dets and c are gathers meant to stay in L2 / MALL.
+// One thread per determinant, 64 threads per workgroup: all lanes run the same trip counts (N and m - N are uniform),
+// a space below one wave or off a multiple of 64 only leaves lanes idle, and nothing depends on K.
+//
+// Reproducible: no atomics, every product an explicit fma, the order of a determinant's sum is the order of the walk
+// above (fixed by I and dets), and the chain of vector k never sees another vector: sigma[k] has the same bits alone, at
+// any position in any batch and on any instantiation (a partial last group takes the smallest one that holds it).
+// The density maps one workgroup to each (p, q), strides over dets and closes with one butterfly and a fixed sum over
+// the four waves.
+
+#include "qs_common.h"
+
+namespace qs {
+
+constexpr int kDcBlock = 64;           // determinants (threads) per workgroup of sigma and of the diagonal
+constexpr int kDcRhoBlock = 256;       // threads of the density's workgroup
+// Shipped group size per form {fp64, complex128}: the largest G whose code object has no scratch and no spills; the
+// sweep of tools/det_ci_bench.py is monotone in G in both forms (profiles/r10_det_ci.txt).
+constexpr int kDcGroup[2] = {8, 8};
+
+struct DcArgs {
+    const double* ht;         // (m, m)
+    const double* ut;         // (m, m, m, m), anti-symmetrised
+    const int64_t* dets;      // [dim], ascending
+    const double* D;          // [dim]
+    const double* c;          // first vector of the group: element (J, g) at c[J * ldc + g]
+    double* sigma;            // first vector of the group: element (g, I) at sigma[g * dim + I]
+    int64_t dim, ldc;
+    int m, ng;                // ng = vectors of this launch, 1 ... G of the instantiation
+};
+
+__device__ __forceinline__ uint64_t dc_bit(int p) { return uint64_t(1) << p; }
+
+// orbitals strictly between a and b
+__device__ __forceinline__ uint64_t dc_between(int a, int b) {
+    const int lo = a < b ? a : b, hi = a < b ? b : a;
+    return (dc_bit(hi) - 1) & ~((dc_bit(lo) << 1) - 1);
+}
+
+__device__ __forceinline__ int dc_lowest(uint64_t x) { return __ffsll((unsigned long long)x) - 1; }
+
+// position of mask J in dets, or -1
+__device__ __forceinline__ int64_t dc_find(const int64_t* __restrict__ dets, int64_t dim, uint64_t J) {
+    int64_t lo = 0, hi = dim;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if ((uint64_t)dets[mid] < J) lo = mid + 1;
+        else hi = mid;
+    }
+    return (lo < dim && (uint64_t)dets[lo] == J) ? lo : -1;
+}
+
+// acc[g] += e * c[J, g] for the launch's vectors; CW = doubles per element
+template <int CW, int G>
+__device__ __forceinline__ void dc_feed(double (&acc)[G * CW], const double (&e)[CW], const double* __restrict__ cj, int ng) {
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        if (g < ng) {
+            if constexpr (CW == 1) {
+                acc[g] = fma(e[0], cj[g], acc[g]);
+            } else {
+                const double cr = cj[2 * g], ci = cj[2 * g + 1];
+                acc[2 * g] = fma(-e[CW - 1], ci, fma(e[0], cr, acc[2 * g]));
+                acc[2 * g + 1] = fma(e[CW - 1], cr, fma(e[0], ci, acc[2 * g + 1]));
+            }
+        }
+    }
+}
+
+template <int CW, int G>
+__global__ __launch_bounds__(kDcBlock) void det_ci_sigma_kernel(const DcArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double dc_ht[];
+    const int m = a.m;
+    for (int idx = threadIdx.x; idx < m * m * CW; idx += kDcBlock) dc_ht[idx] = a.ht[idx];
+    __syncthreads();
+    const int64_t row = (int64_t)blockIdx.x * kDcBlock + threadIdx.x;
+    if (row >= a.dim) return;
+
+    const int64_t* __restrict__ dets = a.dets;
+    const double* __restrict__ ut = a.ut;
+    const uint64_t I = (uint64_t)dets[row] & (dc_bit(m) - 1);          // a bit at or above m would index past ut
+    const uint64_t empty = ~I & (dc_bit(m) - 1);
+
+    double acc[G * CW];
+#pragma unroll
+    for (int j = 0; j < G * CW; ++j) acc[j] = 0.0;
+    {
+        double d[CW];
+        d[0] = a.D[row];
+        if constexpr (CW == 2) d[1] = 0.0;
+        dc_feed<CW, G>(acc, d, a.c + row * a.ldc * CW, a.ng);
+    }
+
+    // single excitations p -> q
+    for (uint64_t po = I; po; po &= po - 1) {
+        const int p = dc_lowest(po);
+        const uint64_t rest = I ^ dc_bit(p);
+        for (uint64_t vq = empty; vq; vq &= vq - 1) {
+            const int q = dc_lowest(vq);
+            const int64_t pos = dc_find(dets, a.dim, rest | dc_bit(q));
+            if (pos < 0) continue;
+            double e[CW];
+#pragma unroll
+            for (int w = 0; w < CW; ++w) e[w] = dc_ht[(p * m + q) * CW + w];
+            for (uint64_t oj = rest; oj; oj &= oj - 1) {
+                const int j = dc_lowest(oj);
+                const double* x = ut + (size_t)(((p * m + j) * m + q) * m + j) * CW;
+#pragma unroll
+                for (int w = 0; w < CW; ++w) e[w] += x[w];
+            }
+            if (__popcll((unsigned long long)(I & dc_between(p, q))) & 1) {
+#pragma unroll
+                for (int w = 0; w < CW; ++w) e[w] = -e[w];
+            }
+            dc_feed<CW, G>(acc, e, a.c + pos * a.ldc * CW, a.ng);
+        }
+    }
+
+    // double excitations p1 < p2 -> q1 < q2
+    for (uint64_t po1 = I; po1; po1 &= po1 - 1) {
+        const int p1 = dc_lowest(po1);
+        for (uint64_t po2 = po1 & (po1 - 1); po2; po2 &= po2 - 1) {
+            const int p2 = dc_lowest(po2);
+            const uint64_t rest = I ^ dc_bit(p1) ^ dc_bit(p2);
+            for (uint64_t vq1 = empty; vq1; vq1 &= vq1 - 1) {
+                const int q1 = dc_lowest(vq1);
+                const uint64_t mid = I ^ dc_bit(p1) ^ dc_bit(q1);
+                const int s1 = __popcll((unsigned long long)(I & dc_between(p1, q1)));
+                for (uint64_t vq2 = vq1 & (vq1 - 1); vq2; vq2 &= vq2 - 1) {
+                    const int q2 = dc_lowest(vq2);
+                    const int64_t pos = dc_find(dets, a.dim, rest | dc_bit(q1) | dc_bit(q2));
+                    if (pos < 0) continue;
+                    const double* x = ut + (size_t)(((p1 * m + p2) * m + q1) * m + q2) * CW;
+                    const bool minus = ((s1 + __popcll((unsigned long long)(mid & dc_between(p2, q2)))) & 1) != 0;
+                    double e[CW];
+#pragma unroll
+                    for (int w = 0; w < CW; ++w) e[w] = minus ? -x[w] : x[w];
+                    dc_feed<CW, G>(acc, e, a.c + pos * a.ldc * CW, a.ng);
+                }
+            }
+        }
+    }
+
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        if (g < a.ng) {
+#pragma unroll
+            for (int w = 0; w < CW; ++w) a.sigma[((int64_t)g * a.dim + row) * CW + w] = acc[g * CW + w];
+        }
+    }
+}
+
+template <int CW>
+__global__ __launch_bounds__(kDcBlock) void det_ci_diagonal_kernel(const double* __restrict__ ht, const double* __restrict__ ut,
+                                                                   const int64_t* __restrict__ dets, double* __restrict__ D,
+                                                                   int m, int64_t dim) {
+    const int64_t row = (int64_t)blockIdx.x * kDcBlock + threadIdx.x;
+    if (row >= dim) return;
+    const uint64_t I = (uint64_t)dets[row] & (dc_bit(m) - 1);
+    double d = 0.0;
+    for (uint64_t po = I; po; po &= po - 1) {
+        const int p = dc_lowest(po);
+        d += ht[(size_t)(p * m + p) * CW];
+    }
+    for (uint64_t po = I; po; po &= po - 1) {
+        const int p = dc_lowest(po);
+        for (uint64_t oq = po & (po - 1); oq; oq &= oq - 1) {
+            const int q = dc_lowest(oq);
+            d += ut[(size_t)(((p * m + q) * m + p) * m + q) * CW];
+        }
+    }
+    D[row] = d;
+}
+
+// One workgroup per (p, q) = (blockIdx / m, blockIdx % m): thread t takes determinants t, t + 256, ...
+template <int CW>
+__global__ __launch_bounds__(kDcRhoBlock) void det_ci_density1_kernel(const int64_t* __restrict__ dets, const double* __restrict__ c,
+                                                                      double* __restrict__ rho, int m, int64_t dim) {
+    __shared__ double part[kDcRhoBlock / 64][CW];
+    const int p = blockIdx.x / m, q = blockIdx.x % m;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint64_t between = dc_between(p, q);
+    double acc[CW];
+#pragma unroll
+    for (int w = 0; w < CW; ++w) acc[w] = 0.0;
+    for (int64_t i = tid; i < dim; i += kDcRhoBlock) {
+        const uint64_t I = (uint64_t)dets[i];
+        if (!(I & dc_bit(p))) continue;
+        int64_t pos = i;
+        if (p != q) {
+            if (I & dc_bit(q)) continue;
+            pos = dc_find(dets, dim, I ^ dc_bit(p) ^ dc_bit(q));
+            if (pos < 0) continue;
+        }
+        const bool minus = (__popcll((unsigned long long)(I & between)) & 1) != 0;
+        if constexpr (CW == 1) {
+            const double b = minus ? -c[pos] : c[pos];
+            acc[0] = fma(c[i], b, acc[0]);
+        } else {
+            const double ar = c[2 * i], ai = c[2 * i + 1];
+            const double br = minus ? -c[2 * pos] : c[2 * pos], bi = minus ? -c[2 * pos + 1] : c[2 * pos + 1];
+            acc[0] = fma(ai, bi, fma(ar, br, acc[0]));                  // conj(a) b
+            acc[CW - 1] = fma(-ai, br, fma(ar, bi, acc[CW - 1]));
+        }
+    }
+#pragma unroll
+    for (int w = 0; w < CW; ++w) {
+#pragma unroll
+        for (int mask = 32; mask >= 1; mask >>= 1) acc[w] += __shfl_xor(acc[w], mask);
+        if (lane == 0) part[wave][w] = acc[w];
+    }
+    __syncthreads();
+    if (tid < CW) {
+        double s = part[0][tid];
+#pragma unroll
+        for (int v = 1; v < kDcRhoBlock / 64; ++v) s += part[v][tid];
+        rho[(size_t)(q * m + p) * CW + tid] = s;
+    }
+}
+
+template <int CW, int G>
+static void dc_launch_one(const DcArgs& a, hipStream_t s) {
+    const unsigned grid = (unsigned)cdiv(a.dim, kDcBlock);
+    hipLaunchKernelGGL((det_ci_sigma_kernel<CW, G>), dim3(grid), dim3(kDcBlock), (size_t)a.m * a.m * CW * sizeof(double), s, a);
+    note_dispatch("qs::det_ci_sigma_kernel<%d, %d>", CW, G);
+}
+
+// One group of a.ng vectors on the smallest instantiation that holds it.
+template <int CW>
+static void dc_launch(const DcArgs& a, hipStream_t s) {
+    if (a.ng <= 1) dc_launch_one<CW, 1>(a, s);
+    else if (a.ng <= 2) dc_launch_one<CW, 2>(a, s);
+    else if (a.ng <= 4) dc_launch_one<CW, 4>(a, s);
+    else dc_launch_one<CW, 8>(a, s);
+}
+
+// 0 = fp64, 1 = complex128, negative = the pair is refused
+static inline int dc_form(int h_dtype, int c_dtype) {
+    if (!dtype_ok(h_dtype) || !dtype_ok(c_dtype) || h_dtype != c_dtype) return QS_ERR_BAD_DTYPE;
+    return h_dtype == QS_C128 ? 1 : 0;
+}
+
+static inline bool dc_extents_ok(int64_t m, int64_t N, int64_t dim, int64_t K) {
+    return m >= 1 && m <= 63 && N >= 1 && N <= m && dim >= 1 && dim <= 0x7fffffffLL && K >= 1;
+}
+
+// The form's group size: the shipped one, or the tuning run's (det_ci_g = 1, 2, 4, 8).
+static inline int dc_group(int form) {
+    const int t = g_tune.det_ci_g;
+    return (t == 1 || t == 2 || t == 4 || t == 8) ? t : kDcGroup[form];
+}
+
+static inline bool dc_overlaps(const void* a, int64_t na, const void* b, int64_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
+}
+
+}  // namespace qs
+
+using namespace qs;
+
+extern "C" {
+
+int64_t qs_det_ci_workspace(int h_dtype, int c_dtype, int64_t m, int64_t N, int64_t dim, int64_t K) {
+    const int form = dc_form(h_dtype, c_dtype);
+    if (form < 0) return form;
+    if (!dc_extents_ok(m, N, dim, K)) return QS_ERR_BAD_EXTENT;
+    return 0;          // every sum is closed inside its thread
+}
+
+int qs_det_ci_diagonal(int h_dtype, const void* ht, const void* ut, const int64_t* dets, double* D, int64_t m, int64_t N,
+                       int64_t dim, void* stream) {
+    dispatch_reset();
+    if (!dtype_ok(h_dtype)) return QS_ERR_BAD_DTYPE;
+    if (!dc_extents_ok(m, N, dim, 1)) return QS_ERR_BAD_EXTENT;
+    if (!ht || !ut || !dets || !D) return QS_ERR_NULL_POINTER;
+    const int64_t es = (int64_t)elem_size(h_dtype);
+    if (!aligned(ht, (size_t)es) || !aligned(ut, (size_t)es) || !aligned(dets, 8) || !aligned(D, 8)) return QS_ERR_MISALIGNED;
+    const int64_t d_bytes = dim * 8;
+    if (dc_overlaps(D, d_bytes, ht, m * m * es) || dc_overlaps(D, d_bytes, ut, m * m * m * m * es) ||
+        dc_overlaps(D, d_bytes, dets, dim * 8))
+        return QS_ERR_ALIAS;
+    const unsigned grid = (unsigned)cdiv(dim, kDcBlock);
+    hipStream_t s = (hipStream_t)stream;
+    if (h_dtype == QS_F64)
+        hipLaunchKernelGGL((det_ci_diagonal_kernel<1>), dim3(grid), dim3(kDcBlock), 0, s, (const double*)ht, (const double*)ut, dets, D, (int)m, dim);
+    else
+        hipLaunchKernelGGL((det_ci_diagonal_kernel<2>), dim3(grid), dim3(kDcBlock), 0, s, (const double*)ht, (const double*)ut, dets, D, (int)m, dim);
+    note_dispatch("qs::det_ci_diagonal_kernel<%d>", h_dtype == QS_F64 ? 1 : 2);
+    return launch_status("determinant CI diagonal launch");
+}
+
+int qs_det_ci_sigma(int h_dtype, int c_dtype, const void* ht, const void* ut, const int64_t* dets, const double* D,
+                    const void* c, void* sigma, int64_t m, int64_t N, int64_t dim, int64_t K, int64_t ldc, void* work,
+                    int64_t work_elems, void* stream) {
+    dispatch_reset();
+    (void)work;
+    const int form = dc_form(h_dtype, c_dtype);
+    if (form < 0) return form;
+    if (!dc_extents_ok(m, N, dim, K) || ldc < K) return QS_ERR_BAD_EXTENT;
+    if (!ht || !ut || !dets || !D || !c || !sigma) return QS_ERR_NULL_POINTER;
+    const int64_t es = (int64_t)elem_size(c_dtype);
+    if (!aligned(ht, (size_t)es) || !aligned(ut, (size_t)es) || !aligned(dets, 8) || !aligned(D, 8) || !aligned(c, (size_t)es) ||
+        !aligned(sigma, (size_t)es))
+        return QS_ERR_MISALIGNED;
+    const int64_t s_bytes = K * dim * es;
+    if (dc_overlaps(sigma, s_bytes, ht, m * m * es) || dc_overlaps(sigma, s_bytes, ut, m * m * m * m * es) ||
+        dc_overlaps(sigma, s_bytes, dets, dim * 8) || dc_overlaps(sigma, s_bytes, D, dim * 8) ||
+        dc_overlaps(sigma, s_bytes, c, ((dim - 1) * ldc + K) * es))
+        return QS_ERR_ALIAS;
+    if (work_elems < qs_det_ci_workspace(h_dtype, c_dtype, m, N, dim, K)) return QS_ERR_WORKSPACE;
+
+    const int G = dc_group(form), cw = form == 0 ? 1 : 2;
+    DcArgs a{};
+    a.ht = (const double*)ht; a.ut = (const double*)ut; a.dets = dets; a.D = D;
+    a.dim = dim; a.ldc = ldc; a.m = (int)m;
+    hipStream_t s = (hipStream_t)stream;
+    for (int64_t k0 = 0; k0 < K; k0 += G) {
+        a.ng = (int)(K - k0 < G ? K - k0 : G);
+        a.c = (const double*)c + k0 * cw;
+        a.sigma = (double*)sigma + k0 * dim * cw;
+        if (form == 0) dc_launch<1>(a, s);
+        else dc_launch<2>(a, s);
+        const int rc = launch_status("determinant CI sigma launch");
+        if (rc) return rc;
+    }
+    return QS_OK;
+}
+
+int qs_det_ci_density1(int c_dtype, const int64_t* dets, const void* c, void* rho, int64_t m, int64_t N, int64_t dim,
+                       void* stream) {
+    dispatch_reset();
+    if (!dtype_ok(c_dtype)) return QS_ERR_BAD_DTYPE;
+    if (!dc_extents_ok(m, N, dim, 1)) return QS_ERR_BAD_EXTENT;
+    if (!dets || !c || !rho) return QS_ERR_NULL_POINTER;
+    const int64_t es = (int64_t)elem_size(c_dtype);
+    if (!aligned(dets, 8) || !aligned(c, (size_t)es) || !aligned(rho, (size_t)es)) return QS_ERR_MISALIGNED;
+    if (dc_overlaps(rho, m * m * es, dets, dim * 8) || dc_overlaps(rho, m * m * es, c, dim * es)) return QS_ERR_ALIAS;
+    const unsigned grid = (unsigned)(m * m);
+    hipStream_t s = (hipStream_t)stream;
+    if (c_dtype == QS_F64)
+        hipLaunchKernelGGL((det_ci_density1_kernel<1>), dim3(grid), dim3(kDcRhoBlock), 0, s, dets, (const double*)c, (double*)rho, (int)m, dim);
+    else
+        hipLaunchKernelGGL((det_ci_density1_kernel<2>), dim3(grid), dim3(kDcRhoBlock), 0, s, dets, (const double*)c, (double*)rho, (int)m, dim);
+    note_dispatch("qs::det_ci_density1_kernel<%d>", c_dtype == QS_F64 ? 1 : 2);
+    return launch_status("determinant CI density launch");
+}
+
+}  // extern "C"

@@ -782,6 +782,106 @@ def pair_contract(u, T, out=None):
     return out
 
 
+def _det_ci_operands(ht, ut, dets, *more):
+    """Device operands of the determinant kernels: ``ht`` (m, m), ``ut`` (m, m, m, m) in one dtype, ``dets`` int64."""
+    if not isinstance(dets, torch.Tensor) or dets.dtype != torch.int64 or dets.dim() != 1:
+        raise ValueError("dets must be a 1-D int64 tensor of occupation masks")
+    dt = result_dtype(ht, ut, *more)
+    ht, ut = _dev(ht, dt), _dev(ut, dt)
+    dets = _dev(dets)
+    m = ht.shape[-1]
+    if tuple(ht.shape) != (m, m) or tuple(ut.shape) != (m, m, m, m) or dets.numel() < 1:
+        raise ValueError(f"need ht (m, m), ut (m, m, m, m) and at least one determinant, got {tuple(ht.shape)}, "
+                         f"{tuple(ut.shape)}, {tuple(dets.shape)}")
+    return dt, ht, ut, dets, m
+
+
+@_plain
+def det_ci_diagonal(ht, ut, dets, N, out=None):
+    """``D[I] = <I|H|I>`` (real, fp64) of the determinants ``dets`` (ascending int64 occupation masks of ``N`` bits over
+    the m orbitals of ``ht`` (m, m) and the anti-symmetrised ``ut`` (m, m, m, m)) on ``qs_det_ci_diagonal``: the
+    preconditioner of a Davidson iteration and the diagonal term ``det_ci_sigma`` takes."""
+    lib = _lib.load()
+    dt, ht, ut, dets, m = _det_ci_operands(ht, ut, dets)
+    dim = dets.numel()
+    if out is None:
+        out = torch.empty(dim, dtype=_F64, device=dets.device)
+    else:
+        _check_out(out, (dim,), _F64, "det_ci_diagonal")
+    with _on_device_of(ht, ut, dets, out):
+        _ran(
+            lib.qs_det_ci_diagonal(dtype_code(dt), ht.data_ptr(), ut.data_ptr(), dets.data_ptr(), out.data_ptr(),
+                                   m, int(N), dim, _stream()),
+            "qs_det_ci_diagonal",
+        )
+    return out
+
+
+@_plain
+def det_ci_sigma(ht, ut, dets, N, diag, c, out=None):
+    """``sigma[k, I] = sum_J <I|H|J> c[k, J]`` on the determinants ``dets`` for ``c`` (K, dim) or (dim,), on
+    ``qs_det_ci_sigma``: one walk over every determinant's single and double excitations per group of G vectors,
+    ceil(K / G) launches.  ``diag`` is ``det_ci_diagonal(ht, ut, dets, N)``.  The kernel reads ``c`` with the K values
+    of a determinant adjacent: a ``c`` that is the transposed view of a contiguous (dim, K) tensor is read in place,
+    any other is copied into that layout first.  ``sigma[k]`` has the same bits alone and anywhere in a batch."""
+    lib = _lib.load()
+    if not isinstance(c, torch.Tensor) or c.dim() not in (1, 2):
+        raise ValueError("c must be (K, dim) or (dim,)")
+    dt, ht, ut, dets, m = _det_ci_operands(ht, ut, dets, c)
+    dim = dets.numel()
+    single = c.dim() == 1
+    if single:
+        c = c[None]
+    K = c.shape[0]
+    if c.shape[1] != dim or K < 1:
+        raise ValueError(f"c has shape {tuple(c.shape)}: need (K, {dim}) with K >= 1")
+    ct = _dev(c.transpose(0, 1), dt)                                               # (dim, K), K adjacent
+    diag = _dev(diag, _F64)
+    if tuple(diag.shape) != (dim,):
+        raise ValueError(f"diag has shape {tuple(diag.shape)}: need ({dim},)")
+    code = dtype_code(dt)
+    nbytes = check(lib.qs_det_ci_workspace(code, code, m, int(N), dim, K), "workspace query")
+    if out is None:
+        out = torch.empty((dim,) if single else (K, dim), dtype=dt, device=dets.device)
+    else:
+        _check_out(out, (dim,) if single else (K, dim), dt, "det_ci_sigma")
+    with _on_device_of(ht, ut, dets, diag, ct, out):
+        work = workspace.get(nbytes, dets.device) if nbytes else None
+        _ran(
+            lib.qs_det_ci_sigma(code, code, ht.data_ptr(), ut.data_ptr(), dets.data_ptr(), diag.data_ptr(),
+                                ct.data_ptr(), out.data_ptr(), m, int(N), dim, K, K,
+                                work.data_ptr() if nbytes else None, work.numel() if nbytes else 0, _stream()),
+            "qs_det_ci_sigma",
+        )
+    return out
+
+
+@_plain
+def det_ci_density1(dets, c, m, N, out=None):
+    """``rho[q, p] = sum_IJ conj(c[I]) <I|a+_p a_q|J> c[J]`` of ONE vector ``c`` (dim,) on the determinants ``dets``
+    over ``m`` orbitals (``qs_det_ci_density1``), in the index order ``compute_particle_density(rho_qp)`` takes."""
+    lib = _lib.load()
+    if not isinstance(dets, torch.Tensor) or dets.dtype != torch.int64 or dets.dim() != 1:
+        raise ValueError("dets must be a 1-D int64 tensor of occupation masks")
+    dt = result_dtype(c)
+    c, dets = _dev(c, dt), _dev(dets)
+    dim = dets.numel()
+    if tuple(c.shape) != (dim,) or dim < 1:
+        raise ValueError(f"c has shape {tuple(c.shape)}: need ({dim},), one vector")
+    m = int(m)
+    if out is None:
+        out = torch.empty((m, m) if 1 <= m <= 63 else (0, 0), dtype=dt, device=dets.device)
+    else:
+        _check_out(out, (m, m), dt, "det_ci_density1")
+    with _on_device_of(dets, c, out):
+        _ran(
+            lib.qs_det_ci_density1(dtype_code(dt), dets.data_ptr(), c.data_ptr(), out.data_ptr(), m, int(N), dim,
+                                   _stream()),
+            "qs_det_ci_density1",
+        )
+    return out
+
+
 @_plain
 def transform_two_body_blocks(u, Ct0, Ct1, C2, C3, out=None):
     """``out[pqrs] = Ct0[pa] Ct1[qb] u[abcd] C2[cr] C3[ds]``: one coefficient matrix per index

@@ -1,0 +1,92 @@
+"""The dense oracle of the determinant kernels (tests/_det_ci_ref.py: Jordan-Wigner matrices, no Slater-Condon rule)
+pins itself on the CPU, and the space helpers of ``determinant_ci`` are checked against a brute-force filter."""
+
+import numpy as np
+import pytest
+
+import _det_ci_ref as ref
+import _two_particle_ref as tp
+
+
+@pytest.mark.parametrize("cplx", [False, True], ids=["real", "complex"])
+def test_one_particle_spectrum_is_that_of_ht(cplx):
+    ht, ut = ref.random_hamiltonian(7, 11, cplx)
+    H = ref.dense_hamiltonian(ht, ut, 1)
+    np.testing.assert_allclose(H, ht, atol=1e-14)                      # the masks 1 << p are ascending in p
+    np.testing.assert_allclose(np.linalg.eigvalsh(H), np.linalg.eigvalsh(ht), atol=1e-13)
+
+
+@pytest.mark.parametrize("cplx", [False, True], ids=["real", "complex"])
+def test_two_particle_spectrum_is_that_of_the_pair_oracle(cplx):
+    m = 6
+    ht, ut = ref.random_hamiltonian(m, 12, cplx)
+    got = np.linalg.eigvalsh(ref.dense_hamiltonian(ht, ut, 2))
+    want = tp.spectrum(ht, ut, np.eye(m), -1, 0.5)                     # an anti-symmetrised u counts every pair twice
+    assert got.shape == want.shape == (15,)
+    np.testing.assert_allclose(got, want, atol=1e-12)
+
+
+@pytest.mark.parametrize("cplx", [False, True], ids=["real", "complex"])
+def test_the_filled_shell_is_one_number(cplx):
+    m = 5
+    ht, ut = ref.random_hamiltonian(m, 13, cplx)
+    H = ref.dense_hamiltonian(ht, ut, m)
+    want = np.einsum("pp->", ht) + 0.5 * np.einsum("pqpq->", ut)
+    assert H.shape == (1, 1) and abs(H[0, 0] - want) <= 1e-12 * max(1.0, abs(want))
+
+
+@pytest.mark.parametrize("m,N", [(4, 2), (6, 3), (7, 3), (8, 4), (7, 6)])
+def test_hermitian_and_anti_symmetrised(m, N):
+    for cplx in (False, True):
+        ht, ut = ref.random_hamiltonian(m, 14 + m, cplx)
+        np.testing.assert_allclose(ut, -ut.transpose(1, 0, 2, 3), atol=0)
+        np.testing.assert_allclose(ut, -ut.transpose(0, 1, 3, 2), atol=0)
+        np.testing.assert_allclose(ut, ut.conj().transpose(2, 3, 0, 1), atol=1e-15)
+        H = ref.dense_hamiltonian(ht, ut, N)
+        np.testing.assert_allclose(H, H.conj().T, atol=1e-13)
+        Hx = ref.dense_hamiltonian(ht, ut, N, extended=True)
+        assert Hx.dtype in (np.longdouble, np.clongdouble)
+        np.testing.assert_allclose(H, Hx.astype(H.dtype), atol=1e-13)
+
+
+def test_density_of_the_oracle():
+    m, N = 6, 3
+    rng = np.random.default_rng(3)
+    c = rng.standard_normal(20) + 1j * rng.standard_normal(20)
+    c /= np.linalg.norm(c)
+    rho = ref.one_body_density(c, m, N)
+    assert abs(np.trace(rho) - N) <= 1e-14
+    np.testing.assert_allclose(rho, rho.conj().T, atol=1e-15)
+    ht, ut = ref.random_hamiltonian(m, 15, True)
+    zero = np.zeros_like(ut)
+    e1 = c.conj() @ ref.dense_hamiltonian(ht, zero, N) @ c             # <H_1> = sum_pq ht[p,q] rho[q,p]
+    assert abs(e1 - np.einsum("pq,qp->", ht, rho)) <= 1e-12
+
+
+def test_space_helpers_match_a_brute_force_filter():
+    from quantum_systems_amd import determinant_ci as dci
+
+    def pop(x):
+        return bin(x).count("1")
+
+    for m in range(1, 9):
+        every = range(1 << m)
+        for N in range(1, m + 1):
+            full = dci.full_space(m, N)
+            assert full.dtype == np.int64 and full.tolist() == [x for x in every if pop(x) == N]
+            for two_sz in range(-N, N + 1):
+                want = [x for x in every if pop(x) == N and pop(x & 0x55) - pop(x & 0xAA) == two_sz]
+                assert dci.sz_sector(m, N, two_sz).tolist() == want, (m, N, two_sz)
+    for m, reference in [(6, 0b000111), (7, 0b0101001), (8, 0b00001111), (5, 0b10000)]:
+        N = pop(reference)
+        for level in range(0, 4):
+            want = [x for x in range(1 << m) if pop(x) == N and pop(x & ~reference) <= level]
+            got = dci.truncated_space(m, reference, level)
+            assert got.dtype == np.int64 and got.tolist() == want, (m, reference, level)
+    assert dci.full_space(63, 1)[-1] == 1 << 62 and len(dci.full_space(40, 3)) == 9880
+    assert dci.popcounts(np.array([0, 1, 3, (1 << 62) | 5], dtype=np.int64)).tolist() == [0, 1, 2, 3]
+    for bad in [(64, 2), (0, 1), (4, 0), (4, 5)]:
+        with pytest.raises(ValueError):
+            dci.full_space(*bad)
+    with pytest.raises(ValueError):
+        dci.truncated_space(4, 0b10001, 1)
