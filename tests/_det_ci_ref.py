@@ -7,7 +7,12 @@ built from the Jordan-Wigner matrices of ``a_p`` on the 2^m Fock space (bit p of
 and restricted to the N-particle states in ascending order of their masks.  No Slater-Condon rule, no phase from a
 popcount and no excitation list appears here: a sign or index-order mistake in the kernels is not mirrored.  The pair
 operators ``a_s a_r`` are cut to the (N -> N - 2)-particle block before the O(m^4) sum, so m <= 8 takes well under a
-second.  Nothing here imports the package under test."""
+second.
+
+Past m = 8 a second oracle, ``string_hamiltonian`` / ``string_density``, applies the same operator strings term by term
+to a LIST of masks with the textbook sign of ``a_p`` (462 determinants of 11 orbitals in about a second, orbitals up
+to 62); tests/test_det_ci_ref_host.py pins it against the Jordan-Wigner matrices.  Nothing here imports the package
+under test."""
 
 from math import comb
 
@@ -122,6 +127,84 @@ def density_bound(c, m, N):
     """Each element is a sum of at most dim products c*_I c_J: gamma_(dim+2) sum_I |c_I| |c_J(I)| <= gamma_(dim+2) |c|^2."""
     dim = len(c)
     return gamma(dim + 2) * float(np.sum(np.abs(c) ** 2)) * (2.0 * np.sqrt(2.0) if np.iscomplexobj(c) else 1.0)
+
+
+# ---- a second oracle that scales past M_MAX: the operator strings applied to a LIST of masks, term by term ----------
+# a_p |I> = (-1)^popcount(I & (2^p - 1)) |I - p>, zero if p is empty; a+_p is its adjoint (the same sign on the state it
+# fills).  A state is (mask, sign, alive) per determinant of the list; an operator string is applied factor by factor,
+# right to left.  No case analysis, no count between two orbitals, no excitation list, no symmetry of ut.
+
+
+def _bits(x):
+    """Set bits of every non-negative int64 of an array."""
+    return np.unpackbits(np.ascontiguousarray(x, dtype=np.int64).view(np.uint8).reshape(-1, 8), axis=1).sum(axis=1)
+
+
+def _ladder(state, p, fill):
+    """a+_p (``fill``) or a_p on every (mask, sign, alive) of ``state``."""
+    mask, sign, alive = state
+    bit = np.int64(1) << np.int64(p)
+    occupied = (mask & bit) != 0
+    odd = (_bits(mask & (bit - np.int64(1))) & 1) != 0
+    return mask ^ bit, np.where(odd, -sign, sign), alive & (~occupied if fill else occupied)
+
+
+def _start(dets):
+    dets = np.ascontiguousarray(dets, dtype=np.int64)
+    assert dets.ndim == 1 and (dets >= 0).all() and (np.diff(dets) > 0).all(), "an ascending list of masks"
+    return dets, (dets, np.ones(len(dets), dtype=np.int64), np.ones(len(dets), dtype=bool))
+
+
+def _land(dets, state):
+    """(col, row, sign) of the states that are alive and in the list: string |dets[col]> = sign |dets[row]>."""
+    mask, sign, alive = state
+    pos = np.minimum(np.searchsorted(dets, mask), len(dets) - 1)
+    hit = alive & (dets[pos] == mask)
+    col = np.nonzero(hit)[0]
+    return col, pos[col], sign[col]
+
+
+def string_hamiltonian(ht, ut, dets, moduli=False):
+    """H on the ascending int64 masks ``dets`` (any list: a full sector or a subset), in ``numpy.longdouble``:
+    every non-zero ht[p,q] adds ht[p,q] a+_p a_q, every non-zero ut[p,q,r,s] adds 1/4 ut[p,q,r,s] a+_p a+_q a_s a_r; a
+    target outside the list contributes nothing.  One string maps a determinant to at most one target, so the (row,
+    column) pairs of one term are distinct.  With ``moduli`` the sum of the moduli of the terms of every element."""
+    dets, start = _start(dets)
+    dim = len(dets)
+    ht, ut = _wide(ht), _wide(ut)
+    H = np.zeros((dim, dim), dtype=np.longdouble if moduli else ht.dtype)
+
+    def add(state, value):
+        col, row, sign = _land(dets, state)
+        H[row, col] += abs(value) if moduli else value * sign
+
+    for q in np.nonzero((ht != 0).any(axis=0))[0]:
+        lowered = _ladder(start, q, False)
+        for p in np.nonzero(ht[:, q])[0]:
+            add(_ladder(lowered, p, True), ht[p, q])
+    quarter = np.longdouble(0.25)
+    for r, s in zip(*np.nonzero((ut != 0).any(axis=(0, 1)))):
+        lowered = _ladder(_ladder(start, r, False), s, False)                      # a_s a_r, once per (r, s)
+        if not lowered[2].any():
+            continue
+        for q in np.nonzero((ut[:, :, r, s] != 0).any(axis=0))[0]:
+            raised = _ladder(lowered, q, True)
+            for p in np.nonzero(ut[:, q, r, s])[0]:
+                add(_ladder(raised, p, True), quarter * ut[p, q, r, s])
+    return H
+
+
+def string_density(c, dets, m):
+    """rho[q, p] = <c| a+_p a_q |c> of one vector on the list ``dets``, in ``numpy.longdouble``, from the same a_p."""
+    dets, start = _start(dets)
+    cw = _wide(np.asarray(c))
+    rho = np.zeros((m, m), dtype=cw.dtype)
+    for q in range(m):
+        lowered = _ladder(start, q, False)
+        for p in range(m):
+            col, row, sign = _land(dets, _ladder(lowered, p, True))
+            rho[q, p] = np.sum(cw[row].conj() * sign * cw[col])
+    return rho
 
 
 def loewdin(s):

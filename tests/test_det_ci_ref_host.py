@@ -1,5 +1,6 @@
 """The dense oracle of the determinant kernels (tests/_det_ci_ref.py: Jordan-Wigner matrices, no Slater-Condon rule)
-pins itself on the CPU, and the space helpers of ``determinant_ci`` are checked against a brute-force filter."""
+pins itself on the CPU, the string oracle that scales past m = 8 is pinned against it, and the space helpers of
+``determinant_ci`` are checked against a brute-force filter."""
 
 import numpy as np
 import pytest
@@ -90,3 +91,77 @@ def test_space_helpers_match_a_brute_force_filter():
             dci.full_space(*bad)
     with pytest.raises(ValueError):
         dci.truncated_space(4, 0b10001, 1)
+
+
+# ---- the string oracle (``string_hamiltonian`` / ``string_density``: a_p applied to a list of masks) against the
+# Jordan-Wigner one.  Both sum in longdouble, in different orders: they agree to gamma_(n+2) times the moduli of an
+# element's terms, n = ``terms(m, N)`` -- in practice to the last bit.
+
+SHAPES = [(4, 2), (6, 3), (7, 3), (8, 4), (7, 1), (7, 6), (5, 5)]                 # those of tests/test_gpu_det_ci.py
+LD = np.finfo(np.longdouble).eps / np.finfo(np.float64).eps                       # longdouble roundings in units of 2^-53
+
+
+def half(dim, seed):
+    """A seeded random half of range(dim), ascending, with holes (everything when dim = 1)."""
+    return np.sort(np.random.default_rng(seed).permutation(dim)[:max(1, dim // 2)])
+
+
+def unit_vector(dim, cplx, seed):
+    rng = np.random.default_rng(seed)
+    c = rng.standard_normal(dim) + (1j * rng.standard_normal(dim) if cplx else 0.0)
+    return c / np.linalg.norm(c)
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: f"m{s[0]}_N{s[1]}")
+@pytest.mark.parametrize("cplx", [False, True], ids=["real", "complex"])
+def test_string_hamiltonian_is_the_jordan_wigner_one(cplx, shape):
+    m, N = shape
+    ht, ut = ref.random_hamiltonian(m, 100 * m + N, cplx)
+    dets = ref.sector(m, N)
+    want = ref.dense_hamiltonian(ht, ut, N, extended=True)
+    for keep in (np.arange(len(dets)), half(len(dets), 7 * m + N)):
+        got = ref.string_hamiltonian(ht, ut, dets[keep])
+        assert got.dtype == want.dtype and got.shape == (len(keep), len(keep))
+        bound = ref.gamma(ref.terms(m, N) + 2) * LD * ref.string_hamiltonian(ht, ut, dets[keep], moduli=True)
+        err = np.abs(got - want[np.ix_(keep, keep)])
+        print(f"m={m} N={N} {len(keep)} of {len(dets)}: largest |H_string - H_jw| = {float(err.max()):.2e}")
+        assert (err <= bound).all()
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: f"m{s[0]}_N{s[1]}")
+@pytest.mark.parametrize("cplx", [False, True], ids=["real", "complex"])
+def test_string_density_is_the_jordan_wigner_one(cplx, shape):
+    m, N = shape
+    dets = ref.sector(m, N)
+    c = unit_vector(len(dets), cplx, 50 + m)
+    got, want = ref.string_density(c, dets, m), ref.one_body_density(c, m, N)
+    err = float(np.abs(got - want).max())
+    print(f"m={m} N={N}: largest |rho_string - rho_jw| = {err:.2e}")
+    assert got.shape == (m, m) and err <= ref.density_bound(c, m, N) * LD
+    # on a subset: the density of the zero-padded vector on the full space
+    keep = half(len(dets), 9 * m + N)
+    padded = np.zeros_like(c)
+    padded[keep] = c[keep]
+    sub = ref.string_density(c[keep], dets[keep], m)
+    err = float(np.abs(sub - ref.one_body_density(padded, m, N)).max())
+    print(f"m={m} N={N} {len(keep)} of {len(dets)}: largest |rho_string(subset) - rho_jw(padded)| = {err:.2e}")
+    assert err <= ref.density_bound(padded, m, N) * LD
+
+
+def test_string_oracle_beyond_bit_31():
+    """Three particles on the orbitals {0, 31, 32, 62} of m = 63: an order-preserving placement keeps every sign, so H is
+    that of four adjacent orbitals."""
+    where = np.array([0, 31, 32, 62])
+    ht4, ut4 = ref.random_hamiltonian(4, 21, True)
+    ht, ut = np.zeros((63, 63), dtype=complex), np.zeros((63,) * 4, dtype=complex)
+    ht[np.ix_(where, where)] = ht4
+    ut[np.ix_(where, where, where, where)] = ut4
+    small = ref.sector(4, 3)
+    dets = np.array([sum(1 << int(where[i]) for i in range(4) if x >> i & 1) for x in small.tolist()], dtype=np.int64)
+    assert (np.diff(dets) > 0).all() and int(dets.max()) > 1 << 62
+    assert np.array_equal(ref.string_hamiltonian(ht, ut, dets), ref.string_hamiltonian(ht4, ut4, small))
+    c = unit_vector(4, True, 3)
+    rho = ref.string_density(c, dets, 63)
+    assert np.array_equal(rho[np.ix_(where, where)], ref.string_density(c, small, 4))
+    rho[np.ix_(where, where)] = 0
+    assert not rho.any()

@@ -11,6 +11,8 @@ Tolerances (derived, not tuned):
   * the solver: for a Hermitian matrix an eigenvalue lies within ||r|| of each Ritz value, so with the Davidson
     ``tol = 1e-9`` the energies are asserted to ``1e-8 * max(1, max |lambda|)``; the factor 10 covers the rounding of
     the sigma products (the reasoning of tests/test_gpu_two_particle.py).  ``||H_dense c - E c||`` has the same bound.
+    A solve that stops early still gives upper bounds: Ritz values of a subspace interlace the spectrum from above.
+Larger spaces, orbital indices up to 62 and padded rows of ``c`` are in tests/test_gpu_det_ci_scale.py.
 Every comparison prints its worst ratio to the bound before it asserts."""
 
 import functools
@@ -315,6 +317,95 @@ def test_solver_against_the_dense_spectrum(form):
             assert (solver.m, solver.N, solver.dim) == (8, n, comb(8, n))
             check_solver(solver, ref.dense_hamiltonian(ht, ut, n), 3, G)
             assert np.array_equal(H(system.u), u_before)
+
+
+@functools.lru_cache(maxsize=None)
+def spin_doubled_problem(cplx):
+    """The l = 4 spin-doubled problem of ``test_solver_against_the_dense_spectrum`` (u anti-symmetrised by the system):
+    (h, u, s, C2, ht, ut), host arrays, computed once and never modified."""
+    import _two_particle_ref as tp
+
+    h, u, s = mf.hermitian_problem(4, seed=404, scale=0.2, complex_=cplx)
+    h2, u2, C2, _ = tp.spin_double(h, u, tp.loewdin(s), True)
+    return (h, u, s, C2) + tuple(ref.orbital_hamiltonian(h2, u2, C2, True))
+
+
+@pytest.mark.parametrize("form", list(FORMS))
+def test_solver_collapses_to_the_ritz_vectors(form, monkeypatch):
+    """``max_space = 2 n_guess = 12``, the smallest the function allows, on 70 determinants: the space collapses every
+    other step.  The size of every projected problem is read from the ``torch.linalg.eigh`` calls of the loop: it never
+    exceeds ``max_space`` and it shrinks at least once; without a collapse it would grow past 12 at the fourth step."""
+    from quantum_systems_amd import DeterminantCI, hip
+
+    cplx = FORMS[form]
+    h, u, s, C2, ht, ut = spin_doubled_problem(cplx)
+    solver = DeterminantCI(n_particles(spin_doubled_system(h, u, s, True), 4), hip.asarray(C2))
+    assert solver.dim == 70
+    n_roots, max_space = 3, 12
+    sizes, eigh = [], torch.linalg.eigh
+
+    def spy(a, *args, **kw):
+        sizes.append(a.shape[-1])
+        return eigh(a, *args, **kw)
+
+    monkeypatch.setattr(torch.linalg, "eigh", spy)
+    solver.solve = functools.partial(solver.solve, max_space=max_space)             # check_solver as it is
+    check_solver(solver, ref.dense_hamiltonian(ht, ut, 4), n_roots, shipped_group(cplx))
+    print(f"{form}: projected sizes {sizes}")
+    assert len(sizes) == solver.iterations and sizes[0] == 2 * n_roots
+    assert max(sizes) <= max_space and any(b < a for a, b in zip(sizes, sizes[1:]))
+    assert sum(solver.sigma_history) > max_space                                    # more vectors than the space ever held
+
+
+@pytest.mark.parametrize("form", list(FORMS))
+def test_solver_on_sz_sectors(form):
+    """``sz_sector`` lists against ``eigvalsh`` of the oracle's H restricted to those masks (same bound as the full
+    space).  The spin-doubled H conserves S_z, so the lowest root over all sectors is the full-space ground energy
+    (two solves: twice the bound)."""
+    from quantum_systems_amd import DeterminantCI, hip, sz_sector
+
+    cplx = FORMS[form]
+    G = shipped_group(cplx)
+    h, u, s, C2, ht, ut = spin_doubled_problem(cplx)
+    base = spin_doubled_system(h, u, s, True)
+    for n, two_sz in ((4, 0), (3, 1)):
+        dets = sz_sector(8, n, two_sz)
+        full = ref.sector(8, n)
+        keep = np.searchsorted(full, dets)
+        assert (full[keep] == dets).all() and len(dets) == comb(4, (n + two_sz) // 2) * comb(4, (n - two_sz) // 2)
+        solver = DeterminantCI(n_particles(base, n), hip.asarray(C2), dets=dets)
+        assert (solver.m, solver.N, solver.dim) == (8, n, len(dets)) and np.array_equal(solver.dets, dets)
+        check_solver(solver, ref.dense_hamiltonian(ht, ut, n)[np.ix_(keep, keep)], 3, G)
+    lam = np.linalg.eigvalsh(ref.dense_hamiltonian(ht, ut, 4))
+    bound = 1e-8 * max(1.0, np.abs(lam).max())
+    lowest = []
+    for two_sz in (-4, -2, 0, 2, 4):
+        solver = DeterminantCI(n_particles(base, 4), hip.asarray(C2), dets=sz_sector(8, 4, two_sz))
+        lowest.append(float(H(solver.solve(1, tol=TOL)[0])[0]) - E_NUC)
+        assert solver.converged
+    print(f"{form}: lowest root per S_z sector {lowest}, full space {lam[0]}: |dE| = {abs(min(lowest) - lam[0]):.2e} "
+          f"(bound {2 * bound:.1e})")
+    assert abs(min(lowest) - lam[0]) <= 2 * bound and int(np.argmin(lowest)) == 2
+
+
+@pytest.mark.parametrize("form", list(FORMS))
+def test_solver_that_runs_out_of_iterations(form):
+    """``max_iter = 1`` on 70 determinants from 6 guesses: not converged, and the Ritz values of a subspace are upper
+    bounds of the eigenvalues (Cauchy interlacing), whatever the residuals."""
+    from quantum_systems_amd import DeterminantCI, hip
+
+    cplx = FORMS[form]
+    h, u, s, C2, ht, ut = spin_doubled_problem(cplx)
+    solver = DeterminantCI(n_particles(spin_doubled_system(h, u, s, True), 4), hip.asarray(C2))
+    lam = np.linalg.eigvalsh(ref.dense_hamiltonian(ht, ut, 4))
+    bound = 1e-8 * max(1.0, np.abs(lam).max())
+    E, c = solver.solve(3, tol=TOL, max_iter=1)
+    E = H(E) - E_NUC
+    print(f"{form}: after one iteration E - lambda = {E - lam[:3]}, residuals {solver.residuals}")
+    assert solver.converged is False and solver.iterations == 1 and solver.sigma_history == [6]
+    assert len(solver.residuals) == 3 and np.isfinite(solver.residuals).all() and min(solver.residuals) >= TOL
+    assert E.shape == (3,) and np.isfinite(E).all() and (E >= lam[:3] - bound).all()
+    assert np.abs(np.linalg.norm(H(c), axis=1) - 1.0).max() <= 1e-12
 
 
 def test_the_whole_space_ends_in_one_iteration_and_the_filled_shell_is_the_identity():
