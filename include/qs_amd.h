@@ -681,9 +681,27 @@ int qs_pair_contract(int u_dtype, int t_dtype, const void* U, const void* T, voi
  *       workspace is 0 bytes (`work` may be NULL).
  *   qs_det_ci_density1 : rho[q * m + p] = sum_IJ conj(c[I]) <I|a+_p a_q|J> c[J]
  *       for ONE vector c[dim]: one workgroup per (p, q), a fixed-order sum.
+ *   qs_det_ci_transition_density1 :
+ *       rho[q * m + p] = sum_IJ conj(bra[I]) <I|a+_p a_q|J> ket[J]
+ *       for two vectors bra[dim], ket[dim] of one dtype: the same kernel, and
+ *       with bra == ket (the same pointer is allowed) the bits of
+ *       qs_det_ci_density1.
+ *   qs_det_ci_density2 :
+ *       gamma2[((p*m + q)*m + r)*m + s]
+ *           = sum_IJ conj(bra[I]) <I|a+_p a+_q a_s a_r|J> ket[J],
+ *       m^4 elements, every one written by the call: the output is zeroed on
+ *       the stream (elements with p = q or r = s; everything at N = 1), then
+ *       one workgroup per unique (p < q, r < s), C(m,2)^2 of them, strides over
+ *       dets, closes its sum in a fixed order and writes the four copies
+ *       gamma2[pqrs] = -gamma2[qprs] = -gamma2[pqsr] = gamma2[qpsr] (exact
+ *       anti-symmetry, no atomics, repeatable bits).  With this index order
+ *       <bra|H|ket> = sum_pq ht[p,q] rho[q,p]
+ *                     + 1/4 sum_pqrs ut[p,q,r,s] gamma2[p,q,r,s].
+ *       A target outside `dets` contributes nothing: a subset gives the
+ *       densities of the projected problem.
  * dtype pairs (ht and ut, c): (F64, F64) and (C128, C128); any other pair is
- * QS_ERR_BAD_DTYPE.  The diagonal takes the dtype of ht / ut, the density that
- * of c (rho has it too).
+ * QS_ERR_BAD_DTYPE.  The diagonal takes the dtype of ht / ut, the densities that
+ * of c or of bra and ket (rho and gamma2 have it too).
  * Promises (tests/test_gpu_det_ci.py):
  *   1. sigma[k] has the same bits alone, at any position in a batch of any K and
  *      under any "det_ci_g"; repeating a call gives the same bits (no atomics,
@@ -693,7 +711,8 @@ int qs_pair_contract(int u_dtype, int t_dtype, const void* U, const void* T, voi
  * Errors, checked in this order before any HIP call: dtype pair, extents (m
  * outside 1 ... 63, N outside 1 ... m, dim < 1 or > 2^31 - 1, K < 1, ldc < K),
  * null pointer, misaligned pointer (element size; 8 for dets and D), an output
- * overlapping an input (QS_ERR_ALIAS), work_elems below the query (negative).
+ * overlapping an input (QS_ERR_ALIAS; rho and gamma2 against dets, bra and ket),
+ * work_elems below the query (negative).
  */
 int64_t qs_det_ci_workspace(int h_dtype, int c_dtype, int64_t m, int64_t N, int64_t dim, int64_t K);
 int qs_det_ci_diagonal(int h_dtype, const void* ht, const void* ut, const int64_t* dets, double* D,
@@ -703,6 +722,10 @@ int qs_det_ci_sigma(int h_dtype, int c_dtype, const void* ht, const void* ut, co
                     int64_t K, int64_t ldc, void* work, int64_t work_elems, void* stream);
 int qs_det_ci_density1(int c_dtype, const int64_t* dets, const void* c, void* rho,
                        int64_t m, int64_t N, int64_t dim, void* stream);
+int qs_det_ci_transition_density1(int c_dtype, const int64_t* dets, const void* bra, const void* ket,
+                                  void* rho, int64_t m, int64_t N, int64_t dim, void* stream);
+int qs_det_ci_density2(int c_dtype, const int64_t* dets, const void* bra, const void* ket,
+                       void* gamma2, int64_t m, int64_t N, int64_t dim, void* stream);
 int qs_probe_mfma_f64(void* sink, int64_t blocks, int64_t iters, void* stream);
 int qs_probe_stream_copy(const void* src, void* dst, int64_t bytes, void* stream);
 

@@ -92,6 +92,8 @@ SIGNATURES = {
     "qs_det_ci_diagonal": (c_int, [c_int, c_ptr, c_ptr, c_ptr, c_ptr] + [c_i64] * 3 + [c_ptr]),
     "qs_det_ci_sigma": (c_int, [c_int, c_int] + [c_ptr] * 6 + [c_i64] * 5 + [c_ptr, c_i64, c_ptr]),
     "qs_det_ci_density1": (c_int, [c_int, c_ptr, c_ptr, c_ptr] + [c_i64] * 3 + [c_ptr]),
+    "qs_det_ci_transition_density1": (c_int, [c_int, c_ptr, c_ptr, c_ptr, c_ptr] + [c_i64] * 3 + [c_ptr]),
+    "qs_det_ci_density2": (c_int, [c_int, c_ptr, c_ptr, c_ptr, c_ptr] + [c_i64] * 3 + [c_ptr]),
 }
 
 ABI_VERSION = 4

@@ -1,4 +1,5 @@
-// H c on Slater determinants (direct configuration interaction), its diagonal and the one-body density of a vector.
+// H c on Slater determinants (direct configuration interaction), its diagonal and the one- and two-body (transition)
+// densities of its vectors.
 //   H = sum_pq ht[p,q] a+_p a_q + 1/4 sum_pqrs ut[p,q,r,s] a+_p a+_q a_s a_r,   ut[p,q,r,s] = <pq|rs> - <pq|sr>
 // A determinant is a 64-bit occupation mask over m <= 63 orthonormal spin orbitals (bit p = orbital p occupied); the
 // space is an ascending, duplicate-free list dets[dim] of masks with N bits each -- the full space, a spin sector, an
@@ -23,8 +24,11 @@
 // Reproducible: no atomics, every product an explicit fma, the order of a determinant's sum is the order of the walk
 // above (fixed by I and dets), and the chain of vector k never sees another vector: sigma[k] has the same bits alone, at
 // any position in any batch and on any instantiation (a partial last group takes the smallest one that holds it).
-// The density maps one workgroup to each (p, q), strides over dets and closes with one butterfly and a fixed sum over
-// the four waves.
+// The densities map one workgroup to each output -- (p, q) of rho, the unique (p < q, r < s) of gamma2 --, stride over
+// dets and close with one butterfly and a fixed sum over the four waves.  They take a bra and a ket vector:
+//   rho[q, p]          = sum_IJ conj(bra[I]) <I| a+_p a_q |J> ket[J]
+//   gamma2[p, q, r, s] = sum_IJ conj(bra[I]) <I| a+_p a+_q a_s a_r |J> ket[J]
+// so that <bra|H|ket> = sum_pq ht[p,q] rho[q,p] + 1/4 sum_pqrs ut[p,q,r,s] gamma2[p,q,r,s]; bra = ket is a state's density.
 
 #include "qs_common.h"
 
@@ -190,13 +194,37 @@ __global__ __launch_bounds__(kDcBlock) void det_ci_diagonal_kernel(const double*
     D[row] = d;
 }
 
-// One workgroup per (p, q) = (blockIdx / m, blockIdx % m): thread t takes determinants t, t + 256, ...
+// Close a 256-thread workgroup's sums: the xor butterfly inside each wave, lane 0 to LDS, then (dc_total, threads
+// 0 ... CW - 1) the four waves in their fixed order.
 template <int CW>
-__global__ __launch_bounds__(kDcRhoBlock) void det_ci_density1_kernel(const int64_t* __restrict__ dets, const double* __restrict__ c,
-                                                                      double* __restrict__ rho, int m, int64_t dim) {
+__device__ __forceinline__ void dc_close(double (&acc)[CW], double (&part)[kDcRhoBlock / 64][CW]) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int w = 0; w < CW; ++w) {
+#pragma unroll
+        for (int mask = 32; mask >= 1; mask >>= 1) acc[w] += __shfl_xor(acc[w], mask);
+        if (lane == 0) part[wave][w] = acc[w];
+    }
+    __syncthreads();
+}
+
+template <int CW>
+__device__ __forceinline__ double dc_total(const double (&part)[kDcRhoBlock / 64][CW], int w) {
+    double s = part[0][w];
+#pragma unroll
+    for (int v = 1; v < kDcRhoBlock / 64; ++v) s += part[v][w];
+    return s;
+}
+
+// One workgroup per (p, q) = (blockIdx / m, blockIdx % m): thread t takes determinants t, t + 256, ... as the bra
+// determinant I (p in I, q not in I or q = p) and looks J = I - p + q up.  bra == ket is the density of one vector.
+template <int CW>
+__global__ __launch_bounds__(kDcRhoBlock) void det_ci_density1_kernel(const int64_t* __restrict__ dets, const double* bra,
+                                                                      const double* ket, double* __restrict__ rho, int m,
+                                                                      int64_t dim) {
     __shared__ double part[kDcRhoBlock / 64][CW];
     const int p = blockIdx.x / m, q = blockIdx.x % m;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const uint64_t between = dc_between(p, q);
     double acc[CW];
 #pragma unroll
@@ -212,27 +240,79 @@ __global__ __launch_bounds__(kDcRhoBlock) void det_ci_density1_kernel(const int6
         }
         const bool minus = (__popcll((unsigned long long)(I & between)) & 1) != 0;
         if constexpr (CW == 1) {
-            const double b = minus ? -c[pos] : c[pos];
-            acc[0] = fma(c[i], b, acc[0]);
+            const double b = minus ? -ket[pos] : ket[pos];
+            acc[0] = fma(bra[i], b, acc[0]);
         } else {
-            const double ar = c[2 * i], ai = c[2 * i + 1];
-            const double br = minus ? -c[2 * pos] : c[2 * pos], bi = minus ? -c[2 * pos + 1] : c[2 * pos + 1];
+            const double ar = bra[2 * i], ai = bra[2 * i + 1];
+            const double br = minus ? -ket[2 * pos] : ket[2 * pos], bi = minus ? -ket[2 * pos + 1] : ket[2 * pos + 1];
             acc[0] = fma(ai, bi, fma(ar, br, acc[0]));                  // conj(a) b
             acc[CW - 1] = fma(-ai, br, fma(ar, bi, acc[CW - 1]));
         }
     }
-#pragma unroll
-    for (int w = 0; w < CW; ++w) {
-#pragma unroll
-        for (int mask = 32; mask >= 1; mask >>= 1) acc[w] += __shfl_xor(acc[w], mask);
-        if (lane == 0) part[wave][w] = acc[w];
+    dc_close<CW>(acc, part);
+    if (tid < CW) rho[(size_t)(q * m + p) * CW + tid] = dc_total<CW>(part, tid);
+}
+
+// (a, b) with a < b of the idx-th pair of m orbitals, pairs counted (0,1), (0,2), ..., (0,m-1), (1,2), ...
+__device__ __forceinline__ void dc_pair(int idx, int m, int& a, int& b) {
+    a = 0;
+    while (idx >= m - 1 - a) {
+        idx -= m - 1 - a;
+        ++a;
     }
-    __syncthreads();
-    if (tid < CW) {
-        double s = part[0][tid];
+    b = a + 1 + idx;
+}
+
+// Two-body density.  One workgroup per unique quadruple (p < q, r < s) = pairs (blockIdx / npair, blockIdx % npair):
+// thread t takes determinants t, t + 256, ... as the ket determinant J (r, s in J), applies a_r, a_s, a+_q, a+_p with
+//   a_x |K> = (-1)^popcount(K & (2^x - 1)) |K - x>     (a+_x: the same sign on the state it fills)
+// on the running mask (p, q may coincide with r, s), looks I = J - r - s + p + q up and adds conj(bra[I]) sign ket[J].
+// The four copies gamma[pqrs] = -gamma[qprs] = -gamma[pqsr] = gamma[qpsr] come from one sum: the anti-symmetry is exact.
+// Elements with p = q or r = s are not touched here: the entry zeroes the whole output first, on the same stream.
+template <int CW>
+__global__ __launch_bounds__(kDcRhoBlock) void det_ci_density2_kernel(const int64_t* __restrict__ dets, const double* bra,
+                                                                      const double* ket, double* __restrict__ gamma2, int m,
+                                                                      int npair, int64_t dim) {
+    __shared__ double part[kDcRhoBlock / 64][CW];
+    int p, q, r, s;
+    dc_pair((int)(blockIdx.x / (unsigned)npair), m, p, q);
+    dc_pair((int)(blockIdx.x % (unsigned)npair), m, r, s);
+    const int tid = threadIdx.x;
+    const uint64_t out_bits = dc_bit(r) | dc_bit(s), in_bits = dc_bit(p) | dc_bit(q);
+    const uint64_t below_r = dc_bit(r) - 1, below_s = dc_bit(s) - 1, below_q = dc_bit(q) - 1, below_p = dc_bit(p) - 1;
+    double acc[CW];
 #pragma unroll
-        for (int v = 1; v < kDcRhoBlock / 64; ++v) s += part[v][tid];
-        rho[(size_t)(q * m + p) * CW + tid] = s;
+    for (int w = 0; w < CW; ++w) acc[w] = 0.0;
+    for (int64_t i = tid; i < dim; i += kDcRhoBlock) {
+        const uint64_t J = (uint64_t)dets[i];
+        if ((J & out_bits) != out_bits) continue;
+        const uint64_t J1 = J ^ dc_bit(r);                            // a_r |J>
+        const uint64_t J2 = J1 ^ dc_bit(s);                           // a_s a_r |J>
+        if (J2 & in_bits) continue;
+        const uint64_t J3 = J2 | dc_bit(q);                           // a+_q a_s a_r |J>
+        const int64_t pos = dc_find(dets, dim, J3 | dc_bit(p));
+        if (pos < 0) continue;
+        const int flips = __popcll((unsigned long long)(J & below_r)) + __popcll((unsigned long long)(J1 & below_s)) +
+                          __popcll((unsigned long long)(J2 & below_q)) + __popcll((unsigned long long)(J3 & below_p));
+        const bool minus = (flips & 1) != 0;
+        if constexpr (CW == 1) {
+            const double b = minus ? -ket[i] : ket[i];
+            acc[0] = fma(bra[pos], b, acc[0]);
+        } else {
+            const double ar = bra[2 * pos], ai = bra[2 * pos + 1];
+            const double br = minus ? -ket[2 * i] : ket[2 * i], bi = minus ? -ket[2 * i + 1] : ket[2 * i + 1];
+            acc[0] = fma(ai, bi, fma(ar, br, acc[0]));                  // conj(a) b
+            acc[CW - 1] = fma(-ai, br, fma(ar, bi, acc[CW - 1]));
+        }
+    }
+    dc_close<CW>(acc, part);
+    if (tid < CW) {
+        const double v = dc_total<CW>(part, tid);
+        const size_t mm = (size_t)m;
+        gamma2[(((p * mm + q) * mm + r) * mm + s) * CW + tid] = v;
+        gamma2[(((q * mm + p) * mm + r) * mm + s) * CW + tid] = -v;
+        gamma2[(((p * mm + q) * mm + s) * mm + r) * CW + tid] = -v;
+        gamma2[(((q * mm + p) * mm + s) * mm + r) * CW + tid] = v;
     }
 }
 
@@ -271,6 +351,36 @@ static inline int dc_group(int form) {
 static inline bool dc_overlaps(const void* a, int64_t na, const void* b, int64_t nb) {
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
     return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
+}
+
+// The checks the three density entries share, in the order of the other entries; out_elems elements of the form.
+static int dc_density_refusal(int c_dtype, const int64_t* dets, const void* bra, const void* ket, const void* out,
+                              int64_t out_elems, int64_t m, int64_t N, int64_t dim) {
+    if (!dtype_ok(c_dtype)) return QS_ERR_BAD_DTYPE;
+    if (!dc_extents_ok(m, N, dim, 1)) return QS_ERR_BAD_EXTENT;
+    if (!dets || !bra || !ket || !out) return QS_ERR_NULL_POINTER;
+    const int64_t es = (int64_t)elem_size(c_dtype);
+    if (!aligned(dets, 8) || !aligned(bra, (size_t)es) || !aligned(ket, (size_t)es) || !aligned(out, (size_t)es))
+        return QS_ERR_MISALIGNED;
+    if (dc_overlaps(out, out_elems * es, dets, dim * 8) || dc_overlaps(out, out_elems * es, bra, dim * es) ||
+        dc_overlaps(out, out_elems * es, ket, dim * es))
+        return QS_ERR_ALIAS;
+    return QS_OK;
+}
+
+static int dc_density1(int c_dtype, const int64_t* dets, const void* bra, const void* ket, void* rho, int64_t m, int64_t N,
+                       int64_t dim, void* stream) {
+    dispatch_reset();
+    const int rc = dc_density_refusal(c_dtype, dets, bra, ket, rho, m * m, m, N, dim);
+    if (rc) return rc;
+    const unsigned grid = (unsigned)(m * m);
+    hipStream_t s = (hipStream_t)stream;
+    if (c_dtype == QS_F64)
+        hipLaunchKernelGGL((det_ci_density1_kernel<1>), dim3(grid), dim3(kDcRhoBlock), 0, s, dets, (const double*)bra, (const double*)ket, (double*)rho, (int)m, dim);
+    else
+        hipLaunchKernelGGL((det_ci_density1_kernel<2>), dim3(grid), dim3(kDcRhoBlock), 0, s, dets, (const double*)bra, (const double*)ket, (double*)rho, (int)m, dim);
+    note_dispatch("qs::det_ci_density1_kernel<%d>", c_dtype == QS_F64 ? 1 : 2);
+    return launch_status("determinant CI density launch");
 }
 
 }  // namespace qs
@@ -347,21 +457,32 @@ int qs_det_ci_sigma(int h_dtype, int c_dtype, const void* ht, const void* ut, co
 
 int qs_det_ci_density1(int c_dtype, const int64_t* dets, const void* c, void* rho, int64_t m, int64_t N, int64_t dim,
                        void* stream) {
+    return dc_density1(c_dtype, dets, c, c, rho, m, N, dim, stream);
+}
+
+int qs_det_ci_transition_density1(int c_dtype, const int64_t* dets, const void* bra, const void* ket, void* rho, int64_t m,
+                                  int64_t N, int64_t dim, void* stream) {
+    return dc_density1(c_dtype, dets, bra, ket, rho, m, N, dim, stream);
+}
+
+int qs_det_ci_density2(int c_dtype, const int64_t* dets, const void* bra, const void* ket, void* gamma2, int64_t m, int64_t N,
+                       int64_t dim, void* stream) {
     dispatch_reset();
-    if (!dtype_ok(c_dtype)) return QS_ERR_BAD_DTYPE;
-    if (!dc_extents_ok(m, N, dim, 1)) return QS_ERR_BAD_EXTENT;
-    if (!dets || !c || !rho) return QS_ERR_NULL_POINTER;
-    const int64_t es = (int64_t)elem_size(c_dtype);
-    if (!aligned(dets, 8) || !aligned(c, (size_t)es) || !aligned(rho, (size_t)es)) return QS_ERR_MISALIGNED;
-    if (dc_overlaps(rho, m * m * es, dets, dim * 8) || dc_overlaps(rho, m * m * es, c, dim * es)) return QS_ERR_ALIAS;
-    const unsigned grid = (unsigned)(m * m);
+    const int64_t elems = m * m * m * m;
+    int rc = dc_density_refusal(c_dtype, dets, bra, ket, gamma2, elems, m, N, dim);
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
+    // the elements with p = q or r = s (all of them at N = 1 or m = 1) are exact zeros
+    rc = hip_status(hipMemsetAsync(gamma2, 0, (size_t)elems * elem_size(c_dtype), s), "determinant CI two-body density fill");
+    if (rc || N < 2) return rc;
+    const int64_t npair = m * (m - 1) / 2;                             // <= 1953: the grid is at most 3 814 209
+    const unsigned grid = (unsigned)(npair * npair);
     if (c_dtype == QS_F64)
-        hipLaunchKernelGGL((det_ci_density1_kernel<1>), dim3(grid), dim3(kDcRhoBlock), 0, s, dets, (const double*)c, (double*)rho, (int)m, dim);
+        hipLaunchKernelGGL((det_ci_density2_kernel<1>), dim3(grid), dim3(kDcRhoBlock), 0, s, dets, (const double*)bra, (const double*)ket, (double*)gamma2, (int)m, (int)npair, dim);
     else
-        hipLaunchKernelGGL((det_ci_density1_kernel<2>), dim3(grid), dim3(kDcRhoBlock), 0, s, dets, (const double*)c, (double*)rho, (int)m, dim);
-    note_dispatch("qs::det_ci_density1_kernel<%d>", c_dtype == QS_F64 ? 1 : 2);
-    return launch_status("determinant CI density launch");
+        hipLaunchKernelGGL((det_ci_density2_kernel<2>), dim3(grid), dim3(kDcRhoBlock), 0, s, dets, (const double*)bra, (const double*)ket, (double*)gamma2, (int)m, (int)npair, dim);
+    note_dispatch("qs::det_ci_density2_kernel<%d>", c_dtype == QS_F64 ? 1 : 2);
+    return launch_status("determinant CI two-body density launch");
 }
 
 }  // extern "C"

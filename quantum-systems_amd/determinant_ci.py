@@ -13,6 +13,16 @@ is the projection of the full one.  H is never stored: a Davidson step is ONE ``
     ci = DeterminantCI(system, C)                     # a GeneralOrbitalSystem, HF orbitals; dets=None: the full space
     E, c = ci.solve(n_roots=3)
     rho = ci.one_body_density(0)                      # for system.compute_particle_density(rho, C=C)
+
+What a solved state is good for beyond its energy comes from two reductions over the determinants,
+``kernels.det_ci_transition_density1`` and ``kernels.det_ci_density2``:
+
+    rho[q, p]       = <c_k| a+_p a_q |c_l>                   ci.transition_density(k, l)
+    G[p, q, r, s]   = <c_k| a+_p a+_q a_s a_r |c_l>          ci.two_body_density(k, l)
+    <c_k| H |c_l>   = sum_pq ht[p,q] rho[q,p] + 1/4 sum_pqrs ut[p,q,r,s] G[p,q,r,s]
+
+and everything after them is an m^2- or m^4-sized contraction: ``energy_from_densities``, ``expectation_one_body``,
+``transition_dipole``, ``spin_squared``, ``natural_orbitals``.
 """
 
 import numpy
@@ -241,3 +251,93 @@ class DeterminantCI:
         with torch._C.DisableTorchFunctionSubclass():
             rho = kernels.det_ci_density1(self._dets, self._c[k].contiguous(), self.m, self.N)
         return _deliver(rho, self.system.np)
+
+    # ---- densities of the solved states and what follows from them ----------------------------------------------------
+
+    def _states(self, k, l=None):
+        """Vectors k and l (default: k) of the last solve; the SAME tensor twice when they coincide."""
+        if self._c is None:
+            raise RuntimeError("call solve() first")
+        bra = self._c[k]
+        return bra, (bra if l is None or l == k else self._c[l])
+
+    def _rho(self, k, l=None):
+        bra, ket = self._states(k, l)
+        return kernels.det_ci_transition_density1(self._dets, bra, ket, self.m, self.N)
+
+    def _gamma2(self, k, l=None):
+        bra, ket = self._states(k, l)
+        return kernels.det_ci_density2(self._dets, bra, ket, self.m, self.N)
+
+    def _in_orbitals(self, A):
+        """``C^H A C`` of a matrix (l, l) or a stack (d, l, l) given in the system's basis."""
+        A = _plain(A)
+        if A.dim() not in (2, 3) or tuple(A.shape[-2:]) != (self._C.shape[0],) * 2:
+            raise ValueError(f"need an (l, l) matrix or a (d, l, l) stack with l = {self._C.shape[0]}, got {tuple(A.shape)}")
+        dt = torch.complex128 if (A.is_complex() or self._dt == torch.complex128) else torch.float64
+        C = self._C.to(dt)
+        return _dagger(C) @ A.to(dt) @ C
+
+    def transition_density(self, k, l):
+        """``rho[q, p] = <c_k| a+_p a_q |c_l>`` between two solved states; ``transition_density(k, k)`` has the bits of
+        ``one_body_density(k)``."""
+        with torch._C.DisableTorchFunctionSubclass():
+            rho = self._rho(k, l)
+        return _deliver(rho, self.system.np)
+
+    def two_body_density(self, k=0, l=None):
+        """``G[p, q, r, s] = <c_k| a+_p a+_q a_s a_r |c_l>`` (m, m, m, m) of solved state ``k``, or between ``k`` and
+        ``l``: anti-symmetric in (p, q) and in (r, s) exactly, one ``det_ci_density2`` call."""
+        with torch._C.DisableTorchFunctionSubclass():
+            G = self._gamma2(k, l)
+        return _deliver(G, self.system.np)
+
+    def energy_from_densities(self, k=0):
+        """``sum ht[p,q] rho[q,p] + 1/4 sum ut[p,q,r,s] G[p,q,r,s]`` plus the nuclear repulsion: the Rayleigh quotient of
+        the stored (unit) vector ``k`` -- not the Ritz value ``E[k]``, from which it differs by the square of the
+        residual -- without the sigma kernel."""
+        with torch._C.DisableTorchFunctionSubclass():
+            rho, G = self._rho(k), self._gamma2(k)
+            e = (self._ht * rho.transpose(0, 1)).sum() + 0.25 * (self._ut * G).sum()
+            return float(e.real.item()) + float(self.system.nuclear_repulsion_energy)
+
+    def expectation_one_body(self, A, k=0, l=None):
+        """``<c_k| A |c_l>`` (``l`` defaults to ``k``) of a one-body operator given in the system's basis as a matrix
+        (l, l) or a stack (d, l, l): ``sum_pq (C^H A C)[p,q] rho[q,p]``, one value or d of them."""
+        with torch._C.DisableTorchFunctionSubclass():
+            At = self._in_orbitals(A)
+            rho = self._rho(k, l)
+            value = (At * rho.transpose(0, 1).to(At.dtype)).sum(dim=(-2, -1))
+        return _deliver(value, self.system.np)
+
+    def transition_dipole(self, k, l):
+        """``<c_k| dipole_moment |c_l>``, one value per spatial dimension."""
+        return self.expectation_one_body(self.system.dipole_moment, k, l)
+
+    def spin_squared(self, k=0):
+        """``<c_k| S^2 |c_k>`` from the densities: the one-body part ``spin_2`` and the two-body part
+        ``sum_i S_i[p,r] S_i[q,s] a+_p a+_q a_s a_r`` (coefficient 1: the product is not anti-symmetrised), with the
+        spin matrices taken to the orbitals ``C``; ``spin_2_tb`` is never built."""
+        if self._c is None:
+            raise RuntimeError("call solve() first")
+        spins = [getattr(self.system, name, None) for name in ("spin_x", "spin_y", "spin_z", "spin_2")]
+        if any(a is None for a in spins):
+            raise ValueError("the system has no spin matrices: build it with construct_general_orbital_system()")
+        with torch._C.DisableTorchFunctionSubclass():
+            st = self._in_orbitals(torch.stack([_plain(a).to(torch.complex128) for a in spins[:3]]))
+            s2 = self._in_orbitals(_plain(spins[3]).to(torch.complex128))
+            rho, G = self._rho(k).to(st.dtype), self._gamma2(k).to(st.dtype)
+            one = (s2 * rho.transpose(0, 1)).sum()
+            half = torch.einsum("ipr,pqrs->iqs", st, G)
+            return float((one + (st * half).sum()).real.item())
+
+    def natural_orbitals(self, k=0):
+        """``(n, C_nat)`` of solved state ``k``: the occupations ``n`` (descending eigenvalues of the Hermitian part of
+        the matrix ``rho[q, p]``) and ``C_nat = C U`` with its eigenvectors as columns; in ``C_nat`` the one-body
+        density of the state is ``diag(n)``."""
+        with torch._C.DisableTorchFunctionSubclass():
+            rho = self._rho(k)
+            n, U = torch.linalg.eigh(0.5 * (rho + _dagger(rho)))
+            n, U = n.flip(0).contiguous(), U.flip(1)
+            C_nat = (self._C @ U.to(self._dt)).contiguous()
+        return _deliver(n, self.system.np), _deliver(C_nat, self.system.np)

@@ -882,6 +882,61 @@ def det_ci_density1(dets, c, m, N, out=None):
     return out
 
 
+def _det_ci_pair(dets, bra, ket, m, what):
+    """Device operands of the transition densities: ``dets`` int64 and two vectors (dim,) in one dtype."""
+    if not isinstance(dets, torch.Tensor) or dets.dtype != torch.int64 or dets.dim() != 1:
+        raise ValueError("dets must be a 1-D int64 tensor of occupation masks")
+    dt = result_dtype(bra, ket)
+    same = bra is ket
+    bra, dets = _dev(bra, dt), _dev(dets)
+    ket = bra if same else _dev(ket, dt)
+    dim = dets.numel()
+    if tuple(bra.shape) != (dim,) or tuple(ket.shape) != (dim,) or dim < 1:
+        raise ValueError(f"{what}: bra and ket have shapes {tuple(bra.shape)}, {tuple(ket.shape)}: need ({dim},) each")
+    return dt, dets, bra, ket, dim, int(m)
+
+
+@_plain
+def det_ci_transition_density1(dets, bra, ket, m, N, out=None):
+    """``rho[q, p] = sum_IJ conj(bra[I]) <I|a+_p a_q|J> ket[J]`` of two vectors (dim,) on the determinants ``dets`` over
+    ``m`` orbitals (``qs_det_ci_transition_density1``): the kernel of ``det_ci_density1`` with a second vector, and with
+    ``bra is ket`` its bits.  A real and a complex vector promote to complex128."""
+    lib = _lib.load()
+    dt, dets, bra, ket, dim, m = _det_ci_pair(dets, bra, ket, m, "det_ci_transition_density1")
+    if out is None:
+        out = torch.empty((m, m) if 1 <= m <= 63 else (0, 0), dtype=dt, device=dets.device)
+    else:
+        _check_out(out, (m, m), dt, "det_ci_transition_density1")
+    with _on_device_of(dets, bra, ket, out):
+        _ran(
+            lib.qs_det_ci_transition_density1(dtype_code(dt), dets.data_ptr(), bra.data_ptr(), ket.data_ptr(),
+                                              out.data_ptr(), m, int(N), dim, _stream()),
+            "qs_det_ci_transition_density1",
+        )
+    return out
+
+
+@_plain
+def det_ci_density2(dets, bra, ket, m, N, out=None):
+    """``gamma2[p, q, r, s] = sum_IJ conj(bra[I]) <I|a+_p a+_q a_s a_r|J> ket[J]`` (m, m, m, m) of two vectors (dim,) on the
+    determinants ``dets`` (``qs_det_ci_density2``): ``bra is ket`` gives the two-body density of a state.  With
+    ``det_ci_transition_density1`` ``<bra|H|ket> = sum ht[p,q] rho[q,p] + 1/4 sum ut[p,q,r,s] gamma2[p,q,r,s]``.  Every
+    element is written; the anti-symmetry in (p, q) and in (r, s) is exact and repeated calls give the same bits."""
+    lib = _lib.load()
+    dt, dets, bra, ket, dim, m = _det_ci_pair(dets, bra, ket, m, "det_ci_density2")
+    if out is None:
+        out = torch.empty((m, m, m, m) if 1 <= m <= 63 else (0, 0, 0, 0), dtype=dt, device=dets.device)
+    else:
+        _check_out(out, (m, m, m, m), dt, "det_ci_density2")
+    with _on_device_of(dets, bra, ket, out):
+        _ran(
+            lib.qs_det_ci_density2(dtype_code(dt), dets.data_ptr(), bra.data_ptr(), ket.data_ptr(), out.data_ptr(),
+                                   m, int(N), dim, _stream()),
+            "qs_det_ci_density2",
+        )
+    return out
+
+
 @_plain
 def transform_two_body_blocks(u, Ct0, Ct1, C2, C3, out=None):
     """``out[pqrs] = Ct0[pa] Ct1[qb] u[abcd] C2[cr] C3[ds]``: one coefficient matrix per index
