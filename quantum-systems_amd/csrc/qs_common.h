@@ -29,6 +29,12 @@ inline bool aligned(const void* p, size_t a) {
     return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0;
 }
 
+// Do the byte ranges [a, a + na) and [b, b + nb) share a byte?  (The alias test of every entry.)
+inline bool overlaps(const void* a, int64_t na, const void* b, int64_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
+}
+
 inline size_t elem_size(int dtype) { return dtype == QS_C128 ? 16 : 8; }
 
 inline bool dtype_ok(int dtype) { return dtype == QS_F64 || dtype == QS_C128; }

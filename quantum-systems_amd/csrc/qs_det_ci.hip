@@ -30,7 +30,7 @@
 //   gamma2[p, q, r, s] = sum_IJ conj(bra[I]) <I| a+_p a+_q a_s a_r |J> ket[J]
 // so that <bra|H|ket> = sum_pq ht[p,q] rho[q,p] + 1/4 sum_pqrs ut[p,q,r,s] gamma2[p,q,r,s]; bra = ket is a state's density.
 
-#include "qs_common.h"
+#include "qs_contract_common.h"
 
 namespace qs {
 
@@ -316,20 +316,20 @@ __global__ __launch_bounds__(kDcRhoBlock) void det_ci_density2_kernel(const int6
     }
 }
 
-template <int CW, int G>
-static void dc_launch_one(const DcArgs& a, hipStream_t s) {
-    const unsigned grid = (unsigned)cdiv(a.dim, kDcBlock);
-    hipLaunchKernelGGL((det_ci_sigma_kernel<CW, G>), dim3(grid), dim3(kDcBlock), (size_t)a.m * a.m * CW * sizeof(double), s, a);
-    note_dispatch("qs::det_ci_sigma_kernel<%d, %d>", CW, G);
+// CW (doubles per element) of a dtype as a constant: f(std::integral_constant<int, CW>)
+template <class F>
+static auto dc_with_width(int dtype, F&& f) {
+    return with_form(dtype == QS_F64 ? 0 : 1, [&](auto FORM) { return f(std::integral_constant<int, form_widths(FORM).aw>{}); });
 }
 
 // One group of a.ng vectors on the smallest instantiation that holds it.
 template <int CW>
 static void dc_launch(const DcArgs& a, hipStream_t s) {
-    if (a.ng <= 1) dc_launch_one<CW, 1>(a, s);
-    else if (a.ng <= 2) dc_launch_one<CW, 2>(a, s);
-    else if (a.ng <= 4) dc_launch_one<CW, 4>(a, s);
-    else dc_launch_one<CW, 8>(a, s);
+    const unsigned grid = (unsigned)cdiv(a.dim, kDcBlock);
+    with_group(a.ng, [&](auto G) {
+        hipLaunchKernelGGL((det_ci_sigma_kernel<CW, G>), dim3(grid), dim3(kDcBlock), (size_t)a.m * a.m * CW * sizeof(double), s, a);
+        note_dispatch("qs::det_ci_sigma_kernel<%d, %d>", CW, (int)G);
+    });
 }
 
 // 0 = fp64, 1 = complex128, negative = the pair is refused
@@ -343,15 +343,7 @@ static inline bool dc_extents_ok(int64_t m, int64_t N, int64_t dim, int64_t K) {
 }
 
 // The form's group size: the shipped one, or the tuning run's (det_ci_g = 1, 2, 4, 8).
-static inline int dc_group(int form) {
-    const int t = g_tune.det_ci_g;
-    return (t == 1 || t == 2 || t == 4 || t == 8) ? t : kDcGroup[form];
-}
-
-static inline bool dc_overlaps(const void* a, int64_t na, const void* b, int64_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
-}
+static inline int dc_group(int form) { return group_size(g_tune.det_ci_g, kDcGroup[form]); }
 
 // The checks the three density entries share, in the order of the other entries; out_elems elements of the form.
 static int dc_density_refusal(int c_dtype, const int64_t* dets, const void* bra, const void* ket, const void* out,
@@ -362,8 +354,8 @@ static int dc_density_refusal(int c_dtype, const int64_t* dets, const void* bra,
     const int64_t es = (int64_t)elem_size(c_dtype);
     if (!aligned(dets, 8) || !aligned(bra, (size_t)es) || !aligned(ket, (size_t)es) || !aligned(out, (size_t)es))
         return QS_ERR_MISALIGNED;
-    if (dc_overlaps(out, out_elems * es, dets, dim * 8) || dc_overlaps(out, out_elems * es, bra, dim * es) ||
-        dc_overlaps(out, out_elems * es, ket, dim * es))
+    if (overlaps(out, out_elems * es, dets, dim * 8) || overlaps(out, out_elems * es, bra, dim * es) ||
+        overlaps(out, out_elems * es, ket, dim * es))
         return QS_ERR_ALIAS;
     return QS_OK;
 }
@@ -375,11 +367,10 @@ static int dc_density1(int c_dtype, const int64_t* dets, const void* bra, const 
     if (rc) return rc;
     const unsigned grid = (unsigned)(m * m);
     hipStream_t s = (hipStream_t)stream;
-    if (c_dtype == QS_F64)
-        hipLaunchKernelGGL((det_ci_density1_kernel<1>), dim3(grid), dim3(kDcRhoBlock), 0, s, dets, (const double*)bra, (const double*)ket, (double*)rho, (int)m, dim);
-    else
-        hipLaunchKernelGGL((det_ci_density1_kernel<2>), dim3(grid), dim3(kDcRhoBlock), 0, s, dets, (const double*)bra, (const double*)ket, (double*)rho, (int)m, dim);
-    note_dispatch("qs::det_ci_density1_kernel<%d>", c_dtype == QS_F64 ? 1 : 2);
+    dc_with_width(c_dtype, [&](auto CW) {
+        hipLaunchKernelGGL((det_ci_density1_kernel<CW>), dim3(grid), dim3(kDcRhoBlock), 0, s, dets, (const double*)bra, (const double*)ket, (double*)rho, (int)m, dim);
+        note_dispatch("qs::det_ci_density1_kernel<%d>", (int)CW);
+    });
     return launch_status("determinant CI density launch");
 }
 
@@ -405,16 +396,15 @@ int qs_det_ci_diagonal(int h_dtype, const void* ht, const void* ut, const int64_
     const int64_t es = (int64_t)elem_size(h_dtype);
     if (!aligned(ht, (size_t)es) || !aligned(ut, (size_t)es) || !aligned(dets, 8) || !aligned(D, 8)) return QS_ERR_MISALIGNED;
     const int64_t d_bytes = dim * 8;
-    if (dc_overlaps(D, d_bytes, ht, m * m * es) || dc_overlaps(D, d_bytes, ut, m * m * m * m * es) ||
-        dc_overlaps(D, d_bytes, dets, dim * 8))
+    if (overlaps(D, d_bytes, ht, m * m * es) || overlaps(D, d_bytes, ut, m * m * m * m * es) ||
+        overlaps(D, d_bytes, dets, dim * 8))
         return QS_ERR_ALIAS;
     const unsigned grid = (unsigned)cdiv(dim, kDcBlock);
     hipStream_t s = (hipStream_t)stream;
-    if (h_dtype == QS_F64)
-        hipLaunchKernelGGL((det_ci_diagonal_kernel<1>), dim3(grid), dim3(kDcBlock), 0, s, (const double*)ht, (const double*)ut, dets, D, (int)m, dim);
-    else
-        hipLaunchKernelGGL((det_ci_diagonal_kernel<2>), dim3(grid), dim3(kDcBlock), 0, s, (const double*)ht, (const double*)ut, dets, D, (int)m, dim);
-    note_dispatch("qs::det_ci_diagonal_kernel<%d>", h_dtype == QS_F64 ? 1 : 2);
+    dc_with_width(h_dtype, [&](auto CW) {
+        hipLaunchKernelGGL((det_ci_diagonal_kernel<CW>), dim3(grid), dim3(kDcBlock), 0, s, (const double*)ht, (const double*)ut, dets, D, (int)m, dim);
+        note_dispatch("qs::det_ci_diagonal_kernel<%d>", (int)CW);
+    });
     return launch_status("determinant CI diagonal launch");
 }
 
@@ -432,27 +422,24 @@ int qs_det_ci_sigma(int h_dtype, int c_dtype, const void* ht, const void* ut, co
         !aligned(sigma, (size_t)es))
         return QS_ERR_MISALIGNED;
     const int64_t s_bytes = K * dim * es;
-    if (dc_overlaps(sigma, s_bytes, ht, m * m * es) || dc_overlaps(sigma, s_bytes, ut, m * m * m * m * es) ||
-        dc_overlaps(sigma, s_bytes, dets, dim * 8) || dc_overlaps(sigma, s_bytes, D, dim * 8) ||
-        dc_overlaps(sigma, s_bytes, c, ((dim - 1) * ldc + K) * es))
+    if (overlaps(sigma, s_bytes, ht, m * m * es) || overlaps(sigma, s_bytes, ut, m * m * m * m * es) ||
+        overlaps(sigma, s_bytes, dets, dim * 8) || overlaps(sigma, s_bytes, D, dim * 8) ||
+        overlaps(sigma, s_bytes, c, ((dim - 1) * ldc + K) * es))
         return QS_ERR_ALIAS;
     if (work_elems < qs_det_ci_workspace(h_dtype, c_dtype, m, N, dim, K)) return QS_ERR_WORKSPACE;
 
-    const int G = dc_group(form), cw = form == 0 ? 1 : 2;
+    const int cw = form_widths(form).aw;
     DcArgs a{};
     a.ht = (const double*)ht; a.ut = (const double*)ut; a.dets = dets; a.D = D;
     a.dim = dim; a.ldc = ldc; a.m = (int)m;
     hipStream_t s = (hipStream_t)stream;
-    for (int64_t k0 = 0; k0 < K; k0 += G) {
-        a.ng = (int)(K - k0 < G ? K - k0 : G);
+    return for_each_group(K, dc_group(form), [&](int64_t k0, int ng) {
+        a.ng = ng;
         a.c = (const double*)c + k0 * cw;
         a.sigma = (double*)sigma + k0 * dim * cw;
-        if (form == 0) dc_launch<1>(a, s);
-        else dc_launch<2>(a, s);
-        const int rc = launch_status("determinant CI sigma launch");
-        if (rc) return rc;
-    }
-    return QS_OK;
+        dc_with_width(c_dtype, [&](auto CW) { dc_launch<CW>(a, s); });
+        return launch_status("determinant CI sigma launch");
+    });
 }
 
 int qs_det_ci_density1(int c_dtype, const int64_t* dets, const void* c, void* rho, int64_t m, int64_t N, int64_t dim,
@@ -477,11 +464,10 @@ int qs_det_ci_density2(int c_dtype, const int64_t* dets, const void* bra, const 
     if (rc || N < 2) return rc;
     const int64_t npair = m * (m - 1) / 2;                             // <= 1953: the grid is at most 3 814 209
     const unsigned grid = (unsigned)(npair * npair);
-    if (c_dtype == QS_F64)
-        hipLaunchKernelGGL((det_ci_density2_kernel<1>), dim3(grid), dim3(kDcRhoBlock), 0, s, dets, (const double*)bra, (const double*)ket, (double*)gamma2, (int)m, (int)npair, dim);
-    else
-        hipLaunchKernelGGL((det_ci_density2_kernel<2>), dim3(grid), dim3(kDcRhoBlock), 0, s, dets, (const double*)bra, (const double*)ket, (double*)gamma2, (int)m, (int)npair, dim);
-    note_dispatch("qs::det_ci_density2_kernel<%d>", c_dtype == QS_F64 ? 1 : 2);
+    dc_with_width(c_dtype, [&](auto CW) {
+        hipLaunchKernelGGL((det_ci_density2_kernel<CW>), dim3(grid), dim3(kDcRhoBlock), 0, s, dets, (const double*)bra, (const double*)ket, (double*)gamma2, (int)m, (int)npair, dim);
+        note_dispatch("qs::det_ci_density2_kernel<%d>", (int)CW);
+    });
     return launch_status("determinant CI two-body density launch");
 }
 

@@ -17,7 +17,7 @@
 // fetch).  16-byte items at 8-byte-aligned addresses for odd n / ldb; the last item of an odd-n row straddles into the
 // next row (or into the surplus columns of a wider buffer): that half is dropped with a select, never multiplied.
 
-#include "qs_fast_items.h"
+#include "qs_contract_common.h"
 
 namespace qs {
 
@@ -36,9 +36,8 @@ struct LcArgs {
 // FORM 0: A, B, T real; 1: all complex128; 2: real B, complex A and T (two real accumulations per element of B).
 template <int FORM, int R>
 __global__ __launch_bounds__(256) void lead_contract_kernel(const LcArgs g) {
-    constexpr int BW = FORM == 1 ? 2 : 1;      // doubles per element of B
-    constexpr int AW = FORM == 0 ? 1 : 2;      // doubles per element of A and T
-    constexpr int CPI = FORM == 1 ? 1 : 2;     // columns per 16-byte item
+    constexpr auto W = form_widths(FORM);      // B is the tensor, A the coefficients
+    constexpr int BW = W.uw, AW = W.aw, CPI = W.cpi;
     constexpr int NACC = FORM == 2 ? 4 : 2;    // running sums (doubles) per row
     constexpr int D = kLcDepth;
     extern __shared__ __attribute__((aligned(16))) double lc_lds[];     // [kc][R][AW]
@@ -134,7 +133,7 @@ __global__ __launch_bounds__(256) void lead_contract_kernel(const LcArgs g) {
 
 template <int FORM, int R>
 static int lc_launch(LcArgs g, hipStream_t s) {
-    constexpr int AW = FORM == 0 ? 1 : 2, CPI = FORM == 1 ? 1 : 2;
+    constexpr int AW = form_widths(FORM).aw, CPI = form_widths(FORM).cpi;
     const int64_t kpad = cdiv(g.k, kLcDepth) * kLcDepth;
     const int64_t fit = kLcLdsBytes / (R * AW * 8) / kLcDepth * kLcDepth;
     g.kc = (int)(kpad < fit ? kpad : fit);
@@ -153,22 +152,11 @@ static int lc_rows(const LcArgs& g, hipStream_t s) {
     return lc_launch<FORM, 32>(g, s);
 }
 
-// 0 ... 2 = the kernel's form, negative = the pair is refused (the rule of qs_mean_field: tensor dtype, coefficient dtype)
-static inline int lc_form(int u_dtype, int c_dtype) {
-    if (!dtype_ok(u_dtype) || !dtype_ok(c_dtype) || (u_dtype == QS_C128 && c_dtype == QS_F64)) return QS_ERR_BAD_DTYPE;
-    return u_dtype == QS_C128 ? 1 : (c_dtype == QS_C128 ? 2 : 0);
-}
-
-static inline bool overlap(const void* a, int64_t na, const void* b, int64_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
-}
-
 // the arguments as the entry validated them
 static int lead_contract(int form, const void* A, const void* B, void* T, int64_t m, int64_t n, int64_t k, int64_t lda,
                          int64_t ldb, int64_t ldt, hipStream_t s) {
     LcArgs g{(const double*)A, (const double*)B, (double*)T, n, lda, ldb, ldt, (int)m, (int)k, 0};
-    return form == 0 ? lc_rows<0>(g, s) : form == 1 ? lc_rows<1>(g, s) : lc_rows<2>(g, s);
+    return with_form(form, [&](auto F) { return lc_rows<F>(g, s); });
 }
 
 // Complex A (m x k) against a REAL B through the tiled products (the rows beyond the lead kernel): the real product
@@ -207,20 +195,20 @@ extern "C" {
 int qs_lead_contract(int a_dtype, int b_dtype, const void* A, const void* B, void* T, int64_t m, int64_t n, int64_t k,
                      int64_t lda, int64_t ldb, int64_t ldt, void* stream) {
     dispatch_reset();
-    const int form = lc_form(b_dtype, a_dtype);
+    const int form = tensor_form(b_dtype, a_dtype);
     if (form < 0) return form;
     if (m < 1 || m > 32 || n < 1 || k < 1 || k > INT32_MAX || lda < k || ldb < n || ldt < n) return QS_ERR_BAD_EXTENT;
     if (!A || !B || !T) return QS_ERR_NULL_POINTER;
     const int64_t aes = (int64_t)elem_size(a_dtype), bes = (int64_t)elem_size(b_dtype);
     if (!aligned(A, (size_t)aes) || !aligned(B, (size_t)bes) || !aligned(T, (size_t)aes)) return QS_ERR_MISALIGNED;
     const int64_t tb = ((m - 1) * ldt + n) * aes;
-    if (overlap(T, tb, A, ((m - 1) * lda + k) * aes) || overlap(T, tb, B, ((k - 1) * ldb + n) * bes)) return QS_ERR_ALIAS;
+    if (overlaps(T, tb, A, ((m - 1) * lda + k) * aes) || overlaps(T, tb, B, ((k - 1) * ldb + n) * bes)) return QS_ERR_ALIAS;
     return lead_contract(form, A, B, T, m, n, k, lda, ldb, ldt, (hipStream_t)stream);
 }
 
 int64_t qs_transform_two_body_blocks_workspace(int u_dtype, int c_dtype, int64_t L, int64_t M0, int64_t M1, int64_t M2,
                                                int64_t M3) {
-    const int form = lc_form(u_dtype, c_dtype);
+    const int form = tensor_form(u_dtype, c_dtype);
     if (form < 0) return form;
     if (!blocks_extents_ok(L, M0, M1, M2, M3)) return QS_ERR_BAD_EXTENT;
     return (even_up(L * (M0 + M2)) + M0 * L * L * L + M0 * M1 * L * L) * (int64_t)elem_size(c_dtype);
@@ -230,7 +218,7 @@ int qs_transform_two_body_blocks(int u_dtype, int c_dtype, const void* u, const 
                                  const void* C2, const void* C3, void* out, void* work, int64_t work_bytes, int64_t L,
                                  int64_t M0, int64_t M1, int64_t M2, int64_t M3, void* stream) {
     dispatch_reset();
-    const int form = lc_form(u_dtype, c_dtype);
+    const int form = tensor_form(u_dtype, c_dtype);
     if (form < 0) return form;
     if (!blocks_extents_ok(L, M0, M1, M2, M3)) return QS_ERR_BAD_EXTENT;
     if (!u || !Ct0 || !Ct1 || !C2 || !C3 || !out || !work) return QS_ERR_NULL_POINTER;
@@ -240,10 +228,10 @@ int qs_transform_two_body_blocks(int u_dtype, int c_dtype, const void* u, const 
         return QS_ERR_MISALIGNED;
     const int64_t need = qs_transform_two_body_blocks_workspace(u_dtype, c_dtype, L, M0, M1, M2, M3);
     const int64_t ob = M0 * M1 * M2 * M3 * (int64_t)es, L3 = L * L * L;
-    if (overlap(out, ob, u, L3 * L * (int64_t)ues) || overlap(out, ob, work, need) ||
-        overlap(work, need, u, L3 * L * (int64_t)ues) || overlap(out, ob, Ct0, M0 * L * (int64_t)es) ||
-        overlap(out, ob, Ct1, M1 * L * (int64_t)es) || overlap(out, ob, C2, L * M2 * (int64_t)es) ||
-        overlap(out, ob, C3, L * M3 * (int64_t)es))
+    if (overlaps(out, ob, u, L3 * L * (int64_t)ues) || overlaps(out, ob, work, need) ||
+        overlaps(work, need, u, L3 * L * (int64_t)ues) || overlaps(out, ob, Ct0, M0 * L * (int64_t)es) ||
+        overlaps(out, ob, Ct1, M1 * L * (int64_t)es) || overlaps(out, ob, C2, L * M2 * (int64_t)es) ||
+        overlaps(out, ob, C3, L * M3 * (int64_t)es))
         return QS_ERR_ALIAS;
     if (work_bytes < need) return QS_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;

@@ -19,7 +19,7 @@
 // L x L slab of u).  Global items are raw buffer loads over one slab: the range check returns zero for padding lanes
 // and never fetches past the slab; 16-byte items at 8-byte-aligned addresses (odd L).
 
-#include "qs_fast_items.h"
+#include "qs_contract_common.h"
 
 namespace qs {
 
@@ -48,25 +48,11 @@ static inline void mf_chunks(int64_t L, int64_t R, int dw, int* Rc, int* nchunk)
     *nchunk = (int)cdiv(R, rc);
 }
 
-// Column threads: the power of two in 8 ... 128 with the least padded tile area (ties: the widest, whole rows per wave).
-static inline int mf_ct_log(int64_t L, int cpi) {
-    const int64_t items = cdiv(L, cpi);
-    int best = 3;
-    int64_t best_area = -1;
-    for (int lg = 3; lg <= 7; ++lg) {
-        const int64_t ct = int64_t(1) << lg, rb = (256 >> lg) * kMfRows;
-        const int64_t area = cdiv(items, ct) * ct * cdiv(L, rb) * rb;
-        if (best_area < 0 || area <= best_area) { best = lg; best_area = area; }
-    }
-    return best;
-}
-
 // FORM 0: u, D, W real; 1: all complex128; 2: real u, complex D and W (two real accumulations from one load).
 template <int FORM, bool DOJ, bool DOK>
 __global__ __launch_bounds__(256) void mean_field_kernel(const MfArgs g) {
-    constexpr int UW = FORM == 1 ? 2 : 1;    // doubles per element of u
-    constexpr int AW = FORM == 0 ? 1 : 2;    // doubles per element of D and W
-    constexpr int CPI = FORM == 1 ? 1 : 2;   // columns per 16-byte item = K sums per thread
+    constexpr auto W = form_widths(FORM);
+    constexpr int UW = W.uw, AW = W.aw, CPI = W.cpi;      // (CPI columns per item = K sums per thread)
     constexpr int TA = kMfRows;
     extern __shared__ __attribute__((aligned(16))) double mf_lds[];
 
@@ -233,53 +219,42 @@ __global__ __launch_bounds__(256) void mean_field_close_kernel(const double* __r
     W[idx] = x;
 }
 
+int mean_field_close(const double* part, double* W, int64_t total, int row_words, int nchunk, hipStream_t s) {
+    hipLaunchKernelGGL(mean_field_close_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, s, part, W, total,
+                       row_words, nchunk);
+    note_dispatch("qs::mean_field_close_kernel");
+    return launch_status("mean field close launch");
+}
+
 template <int FORM>
 static void mf_launch(const MfArgs& g, unsigned grid, size_t lds, hipStream_t s) {
     const bool j = g.cj != 0.0, k = g.ck != 0.0;
-    const char* form = FORM == 0 ? "0" : FORM == 1 ? "1" : "2";
     if (j && k) {
         hipLaunchKernelGGL((mean_field_kernel<FORM, true, true>), dim3(grid), dim3(256), lds, s, g);
-        note_dispatch("qs::mean_field_kernel<%s, true, true>", form);
+        note_dispatch("qs::mean_field_kernel<%d, true, true>", FORM);
     } else if (k) {
         hipLaunchKernelGGL((mean_field_kernel<FORM, false, true>), dim3(grid), dim3(256), lds, s, g);
-        note_dispatch("qs::mean_field_kernel<%s, false, true>", form);
+        note_dispatch("qs::mean_field_kernel<%d, false, true>", FORM);
     } else {
         // (cj == ck == 0: the J form, scaled by zero)
         hipLaunchKernelGGL((mean_field_kernel<FORM, true, false>), dim3(grid), dim3(256), lds, s, g);
-        note_dispatch("qs::mean_field_kernel<%s, true, false>", form);
+        note_dispatch("qs::mean_field_kernel<%d, true, false>", FORM);
     }
-}
-
-// 0 ... 2 = the kernel's form, negative = the pair is refused
-static inline int mf_form(int u_dtype, int d_dtype) {
-    if (!dtype_ok(u_dtype) || !dtype_ok(d_dtype) || (u_dtype == QS_C128 && d_dtype == QS_F64)) return QS_ERR_BAD_DTYPE;
-    return u_dtype == QS_C128 ? 1 : (d_dtype == QS_C128 ? 2 : 0);
-}
-
-static inline bool mf_extents_ok(int64_t L, int64_t P, int64_t R) {
-    return L > 0 && L <= 1024 && P > 0 && P <= L && R > 0 && R <= L;
 }
 
 // The launch geometry of one call: everything the kernel reads from MfArgs apart from the pointers, the weights and
 // r_lo, its dynamic LDS in bytes and its grid -- a function of (form, L, P, R); all but the grid of (form, L, R) only.
 // The entry, the workspace query and the plan hook all take it from here.
 static inline void mf_plan(int form, int64_t L, int64_t P, int64_t R, MfArgs* g, size_t* lds, unsigned* grid) {
-    const int aw = form == 0 ? 1 : 2, cpi = form == 1 ? 1 : 2, uw = form == 1 ? 2 : 1;
-    g->slab_words = L * L * uw;
+    const FormWidths w = form_widths(form);
+    const MfTiles t = mf_tiles(L, w.cpi, kMfRows);
+    g->slab_words = L * L * w.uw;
     g->L = (int)L; g->R = (int)R;
-    mf_chunks(L, R, aw, &g->Rc, &g->nchunk);
-    g->ct_log = mf_ct_log(L, cpi);
-    const int64_t ct = int64_t(1) << g->ct_log, rb = (256 >> g->ct_log) * kMfRows;
-    g->ncb = (int)cdiv(cdiv(L, cpi), ct);
-    g->nrb = (int)cdiv(L, rb);
-    const int64_t Ls = (L + 1) & ~int64_t(1), wpr = ct > 64 ? ct >> 6 : 1;
-    *lds = (size_t)(g->Rc * Ls + g->nrb * rb + g->ncb * ct * cpi + rb * wpr + 256 * cpi) * aw * 8;
+    mf_chunks(L, R, w.aw, &g->Rc, &g->nchunk);
+    g->ct_log = t.ct_log; g->ncb = t.ncb; g->nrb = t.nrb;
+    const int64_t wpr = t.ct > 64 ? t.ct >> 6 : 1;
+    *lds = (size_t)(g->Rc * t.Ls + t.nrb * t.rb + t.ncb * t.ct * w.cpi + t.rb * wpr + 256 * w.cpi) * w.aw * 8;
     *grid = (unsigned)(P * g->nchunk);
-}
-
-static inline bool overlaps(const void* a, int64_t na, const void* b, int64_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
 }
 
 }  // namespace qs
@@ -289,7 +264,7 @@ using namespace qs;
 extern "C" {
 
 int64_t qs_mean_field_workspace(int u_dtype, int d_dtype, int64_t L, int64_t P, int64_t R) {
-    const int form = mf_form(u_dtype, d_dtype);
+    const int form = tensor_form(u_dtype, d_dtype);
     if (form < 0) return form;
     if (!mf_extents_ok(L, P, R)) return QS_ERR_BAD_EXTENT;
     MfArgs g{};
@@ -300,7 +275,7 @@ int64_t qs_mean_field_workspace(int u_dtype, int d_dtype, int64_t L, int64_t P, 
 }
 
 int qs_mean_field_plan(int u_dtype, int d_dtype, int64_t L, int64_t P, int64_t R, int64_t* out, int n_out) {
-    const int form = mf_form(u_dtype, d_dtype);
+    const int form = tensor_form(u_dtype, d_dtype);
     if (form < 0) return form;
     if (!mf_extents_ok(L, P, R) || n_out < 7) return QS_ERR_BAD_EXTENT;
     if (!out) return QS_ERR_NULL_POINTER;
@@ -317,7 +292,7 @@ int qs_mean_field(int u_dtype, int d_dtype, const void* u_slab, const void* D, v
                   int64_t R, int64_t r_lo, double cj, double ck, void* workspace, int64_t workspace_bytes,
                   void* stream) {
     dispatch_reset();
-    const int form = mf_form(u_dtype, d_dtype);
+    const int form = tensor_form(u_dtype, d_dtype);
     if (form < 0) return form;
     if (!mf_extents_ok(L, P, R) || r_lo < 0 || r_lo + R > L) return QS_ERR_BAD_EXTENT;
     if (!u_slab || !D || !W || !workspace) return QS_ERR_NULL_POINTER;
@@ -338,18 +313,12 @@ int qs_mean_field(int u_dtype, int d_dtype, const void* u_slab, const void* D, v
     g.u = (const double*)u_slab; g.D = (const double*)D; g.part = (double*)workspace;
     g.cj = cj; g.ck = ck;
     g.r_lo = (int)r_lo;
-    const int aw = form == 0 ? 1 : 2;
     hipStream_t s = (hipStream_t)stream;
-    if (form == 0) mf_launch<0>(g, grid, lds, s);
-    else if (form == 1) mf_launch<1>(g, grid, lds, s);
-    else mf_launch<2>(g, grid, lds, s);
-    int rc = launch_status("mean field launch");
+    with_form(form, [&](auto F) { mf_launch<F>(g, grid, lds, s); });
+    const int rc = launch_status("mean field launch");
     if (rc) return rc;
-    const int64_t total = P * L * aw;
-    hipLaunchKernelGGL(mean_field_close_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, s,
-                       (const double*)workspace, (double*)W, total, (int)(L * aw), g.nchunk);
-    note_dispatch("qs::mean_field_close_kernel");
-    return launch_status("mean field close launch");
+    const int64_t row_words = L * form_widths(form).aw;
+    return mean_field_close((const double*)workspace, (double*)W, P * row_words, (int)row_words, g.nchunk, s);
 }
 
 }  // extern "C"

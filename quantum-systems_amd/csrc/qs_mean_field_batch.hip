@@ -20,7 +20,7 @@
 // anywhere in a batch of any size.  Both sums of every density are always accumulated (the arithmetic hides under the
 // load stream); a zero weight drops its sum where the unit stores, so a NaN in a sum that is not asked for stays out.
 
-#include "qs_fast_items.h"
+#include "qs_contract_common.h"
 
 namespace qs {
 
@@ -49,41 +49,25 @@ struct MfbPlan {
     int G, Rc, nchunk, ct_log, ncb, nrb;
 };
 
-// Column threads: the power of two in 8 ... 128 with the least padded tile area (ties: the widest).
-static inline int mfb_ct_log(int64_t L, int cpi) {
-    const int64_t items = cdiv(L, cpi);
-    int best = 3;
-    int64_t best_area = -1;
-    for (int lg = 3; lg <= 7; ++lg) {
-        const int64_t ct = int64_t(1) << lg, rb = (256 >> lg) * kMfbRows;
-        const int64_t area = cdiv(items, ct) * ct * cdiv(L, rb) * rb;
-        if (best_area < 0 || area <= best_area) { best = lg; best_area = area; }
-    }
-    return best;
-}
+static inline MfTiles mfb_tiles(int form, int64_t L) { return mf_tiles(L, form_widths(form).cpi, kMfbRows); }
 
 // LDS doubles of a unit that stages `rc` columns for `G` densities.
-static inline int64_t mfb_lds_words(const MfbPlan& pl, int64_t L, int form, int64_t rc, int G) {
-    const int aw = form == 0 ? 1 : 2, cpi = form == 1 ? 1 : 2;
-    const int64_t Ls = (L + 1) & ~int64_t(1), ct = int64_t(1) << pl.ct_log, rb = (256 >> pl.ct_log) * kMfbRows;
-    return (rc * Ls + pl.nrb * rb + pl.ncb * ct * cpi) * G * aw;
+static inline int64_t mfb_lds_words(const MfTiles& t, int form, int64_t rc, int G) {
+    const FormWidths w = form_widths(form);
+    return (rc * t.Ls + t.nrb * t.rb + t.ncb * t.ct * w.cpi) * G * w.aw;
 }
 
 // Everything the kernel's geometry rests on: a function of (form, L, R) and the form's group size only.  The group
 // size is lowered (halved) for the L at which one column of every density and the unit's sums no longer fit the LDS.
-static inline MfbPlan mfb_plan(int form, int64_t L, int64_t R, int group) {
-    const int cpi = form == 1 ? 1 : 2;
+static inline MfbPlan mfb_plan(const MfTiles& t, int form, int64_t L, int64_t R, int group) {
     MfbPlan pl{};
-    pl.ct_log = mfb_ct_log(L, cpi);
-    const int64_t ct = int64_t(1) << pl.ct_log, rb = (256 >> pl.ct_log) * kMfbRows;
-    pl.ncb = (int)cdiv(cdiv(L, cpi), ct);
-    pl.nrb = (int)cdiv(L, rb);
+    pl.ct_log = t.ct_log; pl.ncb = t.ncb; pl.nrb = t.nrb;
     int G = group;
-    while (G > 1 && mfb_lds_words(pl, L, form, 1, G) > kMfbLdsWords) G >>= 1;
+    while (G > 1 && mfb_lds_words(t, form, 1, G) > kMfbLdsWords) G >>= 1;
     pl.G = G;
     const int64_t want = cdiv(kMfbChunkTarget, L) < R ? cdiv(kMfbChunkTarget, L) : R;
     int64_t rc = cdiv(R, want);
-    while (rc > 1 && mfb_lds_words(pl, L, form, rc, G) > kMfbLdsWords) --rc;
+    while (rc > 1 && mfb_lds_words(t, form, rc, G) > kMfbLdsWords) --rc;
     pl.Rc = (int)rc;
     pl.nchunk = (int)cdiv(R, rc);
     return pl;
@@ -92,9 +76,8 @@ static inline MfbPlan mfb_plan(int form, int64_t L, int64_t R, int group) {
 // FORM 0: u, D, W real; 1: all complex128; 2: real u, complex D and W.  G: densities per load of u.
 template <int FORM, int G>
 __global__ __launch_bounds__(256) void mean_field_batch_kernel(const MfbArgs g) {
-    constexpr int UW = FORM == 1 ? 2 : 1;    // doubles per element of u
-    constexpr int AW = FORM == 0 ? 1 : 2;    // doubles per element of D and W
-    constexpr int CPI = FORM == 1 ? 1 : 2;   // columns per 16-byte item = K sums per thread and density
+    constexpr auto W = form_widths(FORM);
+    constexpr int UW = W.uw, AW = W.aw, CPI = W.cpi;      // (CPI columns per item = K sums per thread and density)
     constexpr int TA = kMfbRows;
     extern __shared__ __attribute__((aligned(16))) double mfb_lds[];
 
@@ -275,57 +258,19 @@ __global__ __launch_bounds__(256) void mean_field_batch_kernel(const MfbArgs g) 
     }
 }
 
-// W[k][p][j] = sum over the chunks, ascending: one thread per real word of the result ([k][p] = ND * P rows).
-__global__ __launch_bounds__(256) void mean_field_batch_close_kernel(const double* __restrict__ part,
-                                                                     double* __restrict__ W, int64_t total,
-                                                                     int row_words, int nchunk) {
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= total) return;
-    const int64_t p = idx / row_words, j = idx - p * row_words;
-    const double* src = part + p * nchunk * (int64_t)row_words + j;
-    double x = src[0];
-    for (int c = 1; c < nchunk; ++c) x += src[(int64_t)c * row_words];
-    W[idx] = x;
-}
-
-template <int FORM, int G>
-static void mfb_launch_one(const MfbArgs& g, unsigned grid, size_t lds, hipStream_t s) {
-    hipLaunchKernelGGL((mean_field_batch_kernel<FORM, G>), dim3(grid), dim3(256), lds, s, g);
-    note_dispatch("qs::mean_field_batch_kernel<%d, %d>", FORM, G);
-}
-
-// One group of g.ng densities on the smallest instantiation that holds it.
-template <int FORM>
-static void mfb_launch(const MfbArgs& g, const MfbPlan& pl, unsigned grid, hipStream_t s) {
-    int G = 1;
-    while (G < g.ng) G <<= 1;
-    const size_t lds = (size_t)mfb_lds_words(pl, g.L, FORM, pl.Rc, G) * 8;
-    if (G == 1) mfb_launch_one<FORM, 1>(g, grid, lds, s);
-    else if (G == 2) mfb_launch_one<FORM, 2>(g, grid, lds, s);
-    else if (G == 4) mfb_launch_one<FORM, 4>(g, grid, lds, s);
-    else mfb_launch_one<FORM, 8>(g, grid, lds, s);
-}
-
-// 0 ... 2 = the kernel's form, negative = the pair is refused
-static inline int mfb_form(int u_dtype, int d_dtype) {
-    if (!dtype_ok(u_dtype) || !dtype_ok(d_dtype) || (u_dtype == QS_C128 && d_dtype == QS_F64)) return QS_ERR_BAD_DTYPE;
-    return u_dtype == QS_C128 ? 1 : (d_dtype == QS_C128 ? 2 : 0);
-}
-
-static inline bool mfb_extents_ok(int64_t L, int64_t P, int64_t R, int64_t ND) {
-    return L > 0 && L <= 1024 && P > 0 && P <= L && R > 0 && R <= L && ND > 0 && ND <= 65536;
+// One group of g.ng densities on the smallest instantiation that holds it; the LDS size follows that instantiation.
+static void mfb_launch(int form, const MfbArgs& g, const MfTiles& t, int rc, unsigned grid, hipStream_t s) {
+    with_form(form, [&](auto F) {
+        with_group(g.ng, [&](auto G) {
+            const size_t lds = (size_t)mfb_lds_words(t, F, rc, G) * 8;
+            hipLaunchKernelGGL((mean_field_batch_kernel<F, G>), dim3(grid), dim3(256), lds, s, g);
+            note_dispatch("qs::mean_field_batch_kernel<%d, %d>", (int)F, (int)G);
+        });
+    });
 }
 
 // The form's group size: the shipped one, or the tuning run's (mean_field_batch_g = 1, 2, 4, 8).
-static inline int mfb_group(int form) {
-    const int t = g_tune.mean_field_batch_g;
-    return (t == 1 || t == 2 || t == 4 || t == 8) ? t : kMfbGroup[form];
-}
-
-static inline bool mfb_overlaps(const void* a, int64_t na, const void* b, int64_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
-}
+static inline int mfb_group(int form) { return group_size(g_tune.mean_field_batch_g, kMfbGroup[form]); }
 
 }  // namespace qs
 
@@ -334,22 +279,23 @@ using namespace qs;
 extern "C" {
 
 int64_t qs_mean_field_batch_workspace(int u_dtype, int d_dtype, int64_t L, int64_t P, int64_t R, int64_t ND) {
-    const int form = mfb_form(u_dtype, d_dtype);
+    const int form = tensor_form(u_dtype, d_dtype);
     if (form < 0) return form;
-    if (!mfb_extents_ok(L, P, R, ND)) return QS_ERR_BAD_EXTENT;
-    const MfbPlan pl = mfb_plan(form, L, R, mfb_group(form));
+    if (!mf_extents_ok(L, P, R, ND)) return QS_ERR_BAD_EXTENT;
+    const MfbPlan pl = mfb_plan(mfb_tiles(form, L), form, L, R, mfb_group(form));
     return ND * P * L * pl.nchunk * (int64_t)elem_size(d_dtype);
 }
 
 int qs_mean_field_batch_plan(int u_dtype, int d_dtype, int64_t L, int64_t P, int64_t R, int64_t ND, int64_t* out,
                              int n_out) {
-    const int form = mfb_form(u_dtype, d_dtype);
+    const int form = tensor_form(u_dtype, d_dtype);
     if (form < 0) return form;
-    if (!mfb_extents_ok(L, P, R, ND) || n_out < 9) return QS_ERR_BAD_EXTENT;
+    if (!mf_extents_ok(L, P, R, ND) || n_out < 9) return QS_ERR_BAD_EXTENT;
     if (!out) return QS_ERR_NULL_POINTER;
-    const MfbPlan pl = mfb_plan(form, L, R, mfb_group(form));
+    const MfTiles t = mfb_tiles(form, L);
+    const MfbPlan pl = mfb_plan(t, form, L, R, mfb_group(form));
     const int64_t plan[9] = {pl.G, cdiv(ND, pl.G), pl.Rc, pl.nchunk, pl.ct_log, pl.ncb, pl.nrb,
-                             mfb_lds_words(pl, L, form, pl.Rc, pl.G) * 8, P * pl.nchunk};
+                             mfb_lds_words(t, form, pl.Rc, pl.G) * 8, P * pl.nchunk};
     for (int i = 0; i < 9; ++i) out[i] = plan[i];
     return 0;
 }
@@ -358,51 +304,47 @@ int qs_mean_field_batch(int u_dtype, int d_dtype, const void* u_slab, const void
                         int64_t R, int64_t r_lo, int64_t ND, const double* cj, const double* ck, void* workspace,
                         int64_t workspace_bytes, void* stream) {
     dispatch_reset();
-    const int form = mfb_form(u_dtype, d_dtype);
+    const int form = tensor_form(u_dtype, d_dtype);
     if (form < 0) return form;
-    if (!mfb_extents_ok(L, P, R, ND) || r_lo < 0 || r_lo + R > L) return QS_ERR_BAD_EXTENT;
+    if (!mf_extents_ok(L, P, R, ND) || r_lo < 0 || r_lo + R > L) return QS_ERR_BAD_EXTENT;
     if (!u_slab || !D || !W || !workspace || !cj || !ck) return QS_ERR_NULL_POINTER;
     const int64_t es = (int64_t)elem_size(d_dtype), ues = (int64_t)elem_size(u_dtype);
     if (!aligned(u_slab, (size_t)ues) || !aligned(D, (size_t)es) || !aligned(W, (size_t)es) || !aligned(workspace, 16))
         return QS_ERR_MISALIGNED;
     const int64_t need = qs_mean_field_batch_workspace(u_dtype, d_dtype, L, P, R, ND);
     const int64_t w_bytes = ND * P * L * es;
-    if (mfb_overlaps(W, w_bytes, u_slab, P * R * L * L * ues) || mfb_overlaps(W, w_bytes, D, ND * L * L * es) ||
-        mfb_overlaps(W, w_bytes, workspace, need))
+    if (overlaps(W, w_bytes, u_slab, P * R * L * L * ues) || overlaps(W, w_bytes, D, ND * L * L * es) ||
+        overlaps(W, w_bytes, workspace, need))
         return QS_ERR_ALIAS;
     if (workspace_bytes < need) return QS_ERR_WORKSPACE;
 
-    const MfbPlan pl = mfb_plan(form, L, R, mfb_group(form));
-    if (mfb_lds_words(pl, L, form, pl.Rc, pl.G) > kMfbLdsWords) return QS_ERR_BAD_EXTENT;      // (not reached for L <= 1024)
-    const int aw = form == 0 ? 1 : 2;
+    const MfTiles t = mfb_tiles(form, L);
+    const MfbPlan pl = mfb_plan(t, form, L, R, mfb_group(form));
+    if (mfb_lds_words(t, form, pl.Rc, pl.G) > kMfbLdsWords) return QS_ERR_BAD_EXTENT;      // (not reached for L <= 1024)
+    const FormWidths w = form_widths(form);
     MfbArgs g{};
     g.u = (const double*)u_slab;
-    g.slab_words = L * L * (form == 1 ? 2 : 1);
-    g.d_words = L * L * aw;
-    g.part_words = P * pl.nchunk * L * aw;
+    g.slab_words = L * L * w.uw;
+    g.d_words = L * L * w.aw;
+    g.part_words = P * pl.nchunk * L * w.aw;
     g.L = (int)L; g.R = (int)R; g.r_lo = (int)r_lo;
     g.Rc = pl.Rc; g.nchunk = pl.nchunk; g.ct_log = pl.ct_log; g.ncb = pl.ncb; g.nrb = pl.nrb;
     const unsigned grid = (unsigned)(P * pl.nchunk);
     hipStream_t s = (hipStream_t)stream;
-    for (int64_t k0 = 0; k0 < ND; k0 += pl.G) {
-        g.ng = (int)(ND - k0 < pl.G ? ND - k0 : pl.G);
+    const int rc = for_each_group(ND, pl.G, [&](int64_t k0, int ng) {
+        g.ng = ng;
         g.D = (const double*)D + k0 * g.d_words;
         g.part = (double*)workspace + k0 * g.part_words;
         for (int q = 0; q < kMfbMaxG; ++q) {
-            g.cj[q] = q < g.ng ? cj[k0 + q] : 0.0;
-            g.ck[q] = q < g.ng ? ck[k0 + q] : 0.0;
+            g.cj[q] = q < ng ? cj[k0 + q] : 0.0;
+            g.ck[q] = q < ng ? ck[k0 + q] : 0.0;
         }
-        if (form == 0) mfb_launch<0>(g, pl, grid, s);
-        else if (form == 1) mfb_launch<1>(g, pl, grid, s);
-        else mfb_launch<2>(g, pl, grid, s);
-        const int rc = launch_status("mean field batch launch");
-        if (rc) return rc;
-    }
-    const int64_t total = ND * P * L * aw;
-    hipLaunchKernelGGL(mean_field_batch_close_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, s,
-                       (const double*)workspace, (double*)W, total, (int)(L * aw), pl.nchunk);
-    note_dispatch("qs::mean_field_batch_close_kernel");
-    return launch_status("mean field batch close launch");
+        mfb_launch(form, g, t, pl.Rc, grid, s);
+        return launch_status("mean field batch launch");
+    });
+    if (rc) return rc;
+    const int64_t row_words = L * w.aw;
+    return mean_field_close((const double*)workspace, (double*)W, ND * P * row_words, (int)row_words, pl.nchunk, s);
 }
 
 }  // extern "C"

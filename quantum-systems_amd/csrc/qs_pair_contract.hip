@@ -23,7 +23,7 @@
 // nothing at all -- so row x has the same bits whatever X, ldu, K, the position of k in the batch or the instantiation
 // its group runs on (a partial last group takes the smallest instantiation that holds it).
 
-#include "qs_fast_items.h"
+#include "qs_contract_common.h"
 
 namespace qs {
 
@@ -45,7 +45,7 @@ struct PcArgs {
 
 // 16-byte units of one item's record in LDS: CPI * G * AW doubles, padded to an odd number of units
 static constexpr int pc_record_units(int form, int G) {
-    const int words = (form == 1 ? 1 : 2) * G * (form == 0 ? 1 : 2);
+    const int words = form_widths(form).cpi * G * form_widths(form).aw;
     return (words / 2) | 1;
 }
 
@@ -91,9 +91,8 @@ __device__ __forceinline__ int pc_close(double (&v)[N], int lane) {
 // FORM 0: U, T, S real; 1: all complex128; 2: real U, complex T and S.  G: vectors per load of U.
 template <int FORM, int G>
 __global__ __launch_bounds__(256) void pair_contract_kernel(const PcArgs g) {
-    constexpr int UW = FORM == 1 ? 2 : 1;    // doubles per element of U
-    constexpr int AW = FORM == 0 ? 1 : 2;    // doubles per element of T and S
-    constexpr int CPI = FORM == 1 ? 1 : 2;   // elements of U per 16-byte item
+    constexpr auto W = form_widths(FORM);
+    constexpr int UW = W.uw, AW = W.aw, CPI = W.cpi;
     constexpr int TA = kPcRows;
     constexpr int RW = pc_record_units(FORM, G) * 2;       // doubles of one item's record
     constexpr int NS = pc_steps(FORM, G);                  // steps per staged chunk
@@ -202,25 +201,14 @@ __global__ __launch_bounds__(256) void pair_contract_kernel(const PcArgs g) {
     if (first && q < g.ng && row0 + i < X) g.S[((int64_t)q * X + row0 + i) * AW + w] = acc[0];
 }
 
-template <int FORM, int G>
-static void pc_launch_one(const PcArgs& g, unsigned grid, hipStream_t s) {
-    hipLaunchKernelGGL((pair_contract_kernel<FORM, G>), dim3(grid), dim3(256), pc_lds_bytes(FORM, G), s, g);
-    note_dispatch("qs::pair_contract_kernel<%d, %d>", FORM, G);
-}
-
 // One group of g.ng vectors on the smallest instantiation that holds it.
-template <int FORM>
-static void pc_launch(const PcArgs& g, unsigned grid, hipStream_t s) {
-    if (g.ng <= 1) pc_launch_one<FORM, 1>(g, grid, s);
-    else if (g.ng <= 2) pc_launch_one<FORM, 2>(g, grid, s);
-    else if (g.ng <= 4) pc_launch_one<FORM, 4>(g, grid, s);
-    else pc_launch_one<FORM, 8>(g, grid, s);
-}
-
-// 0 ... 2 = the kernel's form, negative = the pair is refused
-static inline int pc_form(int u_dtype, int t_dtype) {
-    if (!dtype_ok(u_dtype) || !dtype_ok(t_dtype) || (u_dtype == QS_C128 && t_dtype == QS_F64)) return QS_ERR_BAD_DTYPE;
-    return u_dtype == QS_C128 ? 1 : (t_dtype == QS_C128 ? 2 : 0);
+static void pc_launch(int form, const PcArgs& g, unsigned grid, hipStream_t s) {
+    with_form(form, [&](auto F) {
+        with_group(g.ng, [&](auto G) {
+            hipLaunchKernelGGL((pair_contract_kernel<F, G>), dim3(grid), dim3(256), pc_lds_bytes(F, G), s, g);
+            note_dispatch("qs::pair_contract_kernel<%d, %d>", (int)F, (int)G);
+        });
+    });
 }
 
 // ldu <= 2^24 elements keeps the lane offsets of a wave's rows below the 2 GB buffer range
@@ -229,15 +217,7 @@ static inline bool pc_extents_ok(int64_t X, int64_t Y, int64_t K) {
 }
 
 // The form's group size: the shipped one, or the tuning run's (pair_contract_g = 1, 2, 4, 8).
-static inline int pc_group(int form) {
-    const int t = g_tune.pair_contract_g;
-    return (t == 1 || t == 2 || t == 4 || t == 8) ? t : kPcGroup[form];
-}
-
-static inline bool pc_overlaps(const void* a, int64_t na, const void* b, int64_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
-}
+static inline int pc_group(int form) { return group_size(g_tune.pair_contract_g, kPcGroup[form]); }
 
 }  // namespace qs
 
@@ -246,7 +226,7 @@ using namespace qs;
 extern "C" {
 
 int64_t qs_pair_contract_workspace(int u_dtype, int t_dtype, int64_t X, int64_t Y, int64_t K) {
-    const int form = pc_form(u_dtype, t_dtype);
+    const int form = tensor_form(u_dtype, t_dtype);
     if (form < 0) return form;
     if (!pc_extents_ok(X, Y, K)) return QS_ERR_BAD_EXTENT;
     return 0;          // y is never split: every row sum is closed inside its wave
@@ -256,33 +236,29 @@ int qs_pair_contract(int u_dtype, int t_dtype, const void* U, const void* T, voi
                      int64_t ldu, void* work, int64_t work_elems, void* stream) {
     dispatch_reset();
     (void)work;
-    const int form = pc_form(u_dtype, t_dtype);
+    const int form = tensor_form(u_dtype, t_dtype);
     if (form < 0) return form;
     if (!pc_extents_ok(X, Y, K) || ldu < Y || ldu > (int64_t(1) << 24)) return QS_ERR_BAD_EXTENT;
     if (!U || !T || !S) return QS_ERR_NULL_POINTER;
     const int64_t es = (int64_t)elem_size(t_dtype), ues = (int64_t)elem_size(u_dtype);
     if (!aligned(U, (size_t)ues) || !aligned(T, (size_t)es) || !aligned(S, (size_t)es)) return QS_ERR_MISALIGNED;
     const int64_t s_bytes = K * X * es;
-    if (pc_overlaps(S, s_bytes, U, ((X - 1) * ldu + Y) * ues) || pc_overlaps(S, s_bytes, T, K * Y * es)) return QS_ERR_ALIAS;
+    if (overlaps(S, s_bytes, U, ((X - 1) * ldu + Y) * ues) || overlaps(S, s_bytes, T, K * Y * es)) return QS_ERR_ALIAS;
     if (work_elems < qs_pair_contract_workspace(u_dtype, t_dtype, X, Y, K)) return QS_ERR_WORKSPACE;
 
-    const int G = pc_group(form), aw = form == 0 ? 1 : 2;
+    const int aw = form_widths(form).aw;
     PcArgs g{};
     g.U = (const double*)U;
     g.X = X; g.Y = Y; g.ldu = ldu;
     const unsigned grid = (unsigned)cdiv(X, 4 * kPcRows);
     hipStream_t s = (hipStream_t)stream;
-    for (int64_t k0 = 0; k0 < K; k0 += G) {
-        g.ng = (int)(K - k0 < G ? K - k0 : G);
+    return for_each_group(K, pc_group(form), [&](int64_t k0, int ng) {
+        g.ng = ng;
         g.T = (const double*)T + k0 * Y * aw;
         g.S = (double*)S + k0 * X * aw;
-        if (form == 0) pc_launch<0>(g, grid, s);
-        else if (form == 1) pc_launch<1>(g, grid, s);
-        else pc_launch<2>(g, grid, s);
-        const int rc = launch_status("pair contract launch");
-        if (rc) return rc;
-    }
-    return QS_OK;
+        pc_launch(form, g, grid, s);
+        return launch_status("pair contract launch");
+    });
 }
 
 }  // extern "C"

@@ -173,6 +173,15 @@ class Workspace:
 
 workspace = Workspace()
 
+
+def _work(nbytes, device):
+    """``(pointer, size)`` of ``nbytes`` of the shared scratch of ``device``; ``(None, 0)`` for a call that needs none."""
+    if not nbytes:
+        return None, 0
+    work = workspace.get(nbytes, device)
+    return work.data_ptr(), work.numel()
+
+
 # A/B switch for measurements (bench.py --dtype mixed, tests): False restores the route of rounds 1-2 for a real u against
 # complex coefficients -- a complex copy of the whole tensor, then the complex transform.
 mixed_real_u = True
@@ -604,6 +613,25 @@ def antisymmetrize_(u):
     return antisymmetrize(u, out=u)
 
 
+def _mean_field_operands(u, D, d_dims, r_lo):
+    """Device operands of the mean-field kernels: ``u`` (P, R, L, L) and ``D`` (L, L) (``d_dims`` = 2) or (ND, L, L)
+    (3), and the slab's extents.  Returns ``(u, D, udt, dt, P, R, L)``."""
+    d_shape = "(L, L)" if d_dims == 2 else "(ND, L, L)"
+    dt = result_dtype(u, D)
+    udt = _F64 if isinstance(u, torch.Tensor) and u.dtype == _F64 else dt
+    u = _dev(u, udt)
+    D = _dev(D, dt)
+    if u.dim() != 4 or D.dim() != d_dims:
+        raise ValueError(f"u must be (P, R, L, L) and D {d_shape}")
+    P, R, L = u.shape[0], u.shape[1], u.shape[3]
+    if u.shape[2] != L or tuple(D.shape[-2:]) != (L, L) or (d_dims == 3 and D.shape[0] < 1):
+        raise ValueError(f"u has shape {tuple(u.shape)}, D {tuple(D.shape)}: need u (P, R, L, L) and D {d_shape}"
+                         + (", ND >= 1" if d_dims == 3 else ""))
+    if not (1 <= P <= L and 1 <= R and 0 <= r_lo and r_lo + R <= L):
+        raise ValueError(f"slab of {P} rows and second indices [{r_lo}, {r_lo + R}) does not fit L = {L}")
+    return u, D, udt, dt, P, R, L
+
+
 @_plain
 def mean_field(u, D, cj=1.0, ck=0.0, r_lo=0, out=None):
     """Mean-field contraction of the two-body tensor with a one-body density, both sums from one read of ``u``
@@ -615,17 +643,7 @@ def mean_field(u, D, cj=1.0, ck=0.0, r_lo=0, out=None):
     ``r`` starts at ``r_lo`` (then ``W`` is the partial sum over the slab's ``r``).  ``D`` is (L, L).  A real ``u``
     with a complex ``D`` stays real (complex ``W``).  Returns ``W`` (P, L)."""
     lib = _lib.load()
-    dt = result_dtype(u, D)
-    udt = _F64 if isinstance(u, torch.Tensor) and u.dtype == _F64 else dt
-    u = _dev(u, udt)
-    D = _dev(D, dt)
-    if u.dim() != 4 or D.dim() != 2:
-        raise ValueError("u must be (P, R, L, L) and D (L, L)")
-    P, R, L = u.shape[0], u.shape[1], u.shape[3]
-    if u.shape[2] != L or tuple(D.shape) != (L, L):
-        raise ValueError(f"u has shape {tuple(u.shape)}, D {tuple(D.shape)}: need u (P, R, L, L) and D (L, L)")
-    if not (1 <= P <= L and 1 <= R and 0 <= r_lo and r_lo + R <= L):
-        raise ValueError(f"slab of {P} rows and second indices [{r_lo}, {r_lo + R}) does not fit L = {L}")
+    u, D, udt, dt, P, R, L = _mean_field_operands(u, D, 2, r_lo)
     ucode, dcode = dtype_code(udt), dtype_code(dt)
     nbytes = check(lib.qs_mean_field_workspace(ucode, dcode, L, P, R), "workspace query")
     if out is None:
@@ -666,18 +684,8 @@ def mean_field_batch(u, D, cj=1.0, ck=0.0, r_lo=0, out=None):
     sequences.  ``W[k]`` has the same bits whether ``D[k]`` is sent alone or anywhere in a batch of any size.
     Returns ``W`` (ND, P, L)."""
     lib = _lib.load()
-    dt = result_dtype(u, D)
-    udt = _F64 if isinstance(u, torch.Tensor) and u.dtype == _F64 else dt
-    u = _dev(u, udt)
-    D = _dev(D, dt)
-    if u.dim() != 4 or D.dim() != 3:
-        raise ValueError("u must be (P, R, L, L) and D (ND, L, L)")
-    P, R, L = u.shape[0], u.shape[1], u.shape[3]
+    u, D, udt, dt, P, R, L = _mean_field_operands(u, D, 3, r_lo)
     ND = D.shape[0]
-    if u.shape[2] != L or tuple(D.shape[1:]) != (L, L) or ND < 1:
-        raise ValueError(f"u has shape {tuple(u.shape)}, D {tuple(D.shape)}: need u (P, R, L, L) and D (ND, L, L), ND >= 1")
-    if not (1 <= P <= L and 1 <= R and 0 <= r_lo and r_lo + R <= L):
-        raise ValueError(f"slab of {P} rows and second indices [{r_lo}, {r_lo + R}) does not fit L = {L}")
     wj, wk = _weights(cj, ND, "cj"), _weights(ck, ND, "ck")
     ucode, dcode = dtype_code(udt), dtype_code(dt)
     nbytes = check(lib.qs_mean_field_batch_workspace(ucode, dcode, L, P, R, ND), "workspace query")
@@ -773,19 +781,23 @@ def pair_contract(u, T, out=None):
     else:
         _check_out(out, (P, Q) if single else (K, P, Q), dt, "pair_contract")
     with _on_device_of(u, T, out):
-        work = workspace.get(nbytes, u.device) if nbytes else None
         _ran(
             lib.qs_pair_contract(ucode, tcode, u.data_ptr(), T.data_ptr(), out.data_ptr(), X, Y, K, ldu,
-                                 work.data_ptr() if nbytes else None, work.numel() if nbytes else 0, _stream()),
+                                 *_work(nbytes, u.device), _stream()),
             "qs_pair_contract",
         )
     return out
 
 
-def _det_ci_operands(ht, ut, dets, *more):
-    """Device operands of the determinant kernels: ``ht`` (m, m), ``ut`` (m, m, m, m) in one dtype, ``dets`` int64."""
+def _dets_checked(dets):
+    """The determinant list every determinant kernel takes: a 1-D int64 tensor."""
     if not isinstance(dets, torch.Tensor) or dets.dtype != torch.int64 or dets.dim() != 1:
         raise ValueError("dets must be a 1-D int64 tensor of occupation masks")
+
+
+def _det_ci_operands(ht, ut, dets, *more):
+    """Device operands of the determinant kernels: ``ht`` (m, m), ``ut`` (m, m, m, m) in one dtype, ``dets`` int64."""
+    _dets_checked(dets)
     dt = result_dtype(ht, ut, *more)
     ht, ut = _dev(ht, dt), _dev(ut, dt)
     dets = _dev(dets)
@@ -846,11 +858,10 @@ def det_ci_sigma(ht, ut, dets, N, diag, c, out=None):
     else:
         _check_out(out, (dim,) if single else (K, dim), dt, "det_ci_sigma")
     with _on_device_of(ht, ut, dets, diag, ct, out):
-        work = workspace.get(nbytes, dets.device) if nbytes else None
         _ran(
             lib.qs_det_ci_sigma(code, code, ht.data_ptr(), ut.data_ptr(), dets.data_ptr(), diag.data_ptr(),
-                                ct.data_ptr(), out.data_ptr(), m, int(N), dim, K, K,
-                                work.data_ptr() if nbytes else None, work.numel() if nbytes else 0, _stream()),
+                                ct.data_ptr(), out.data_ptr(), m, int(N), dim, K, K, *_work(nbytes, dets.device),
+                                _stream()),
             "qs_det_ci_sigma",
         )
     return out
@@ -861,8 +872,7 @@ def det_ci_density1(dets, c, m, N, out=None):
     """``rho[q, p] = sum_IJ conj(c[I]) <I|a+_p a_q|J> c[J]`` of ONE vector ``c`` (dim,) on the determinants ``dets``
     over ``m`` orbitals (``qs_det_ci_density1``), in the index order ``compute_particle_density(rho_qp)`` takes."""
     lib = _lib.load()
-    if not isinstance(dets, torch.Tensor) or dets.dtype != torch.int64 or dets.dim() != 1:
-        raise ValueError("dets must be a 1-D int64 tensor of occupation masks")
+    _dets_checked(dets)
     dt = result_dtype(c)
     c, dets = _dev(c, dt), _dev(dets)
     dim = dets.numel()
@@ -884,8 +894,7 @@ def det_ci_density1(dets, c, m, N, out=None):
 
 def _det_ci_pair(dets, bra, ket, m, what):
     """Device operands of the transition densities: ``dets`` int64 and two vectors (dim,) in one dtype."""
-    if not isinstance(dets, torch.Tensor) or dets.dtype != torch.int64 or dets.dim() != 1:
-        raise ValueError("dets must be a 1-D int64 tensor of occupation masks")
+    _dets_checked(dets)
     dt = result_dtype(bra, ket)
     same = bra is ket
     bra, dets = _dev(bra, dt), _dev(dets)

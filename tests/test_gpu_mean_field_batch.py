@@ -260,7 +260,7 @@ def test_one_pass_per_group(form):
         kernels.mean_field_batch(d_u, d_D[:nd], cj=1.0, ck=-0.5)
         log = kernels.last_dispatch()
         assert streaming_launches(log) == -(-nd // G), (nd, log)
-        assert log.count("qs::mean_field_batch_close_kernel") == 1 and "qs::mean_field_kernel" not in log, log
+        assert log.count("qs::mean_field_close_kernel") == 1 and "qs::mean_field_kernel" not in log, log
         assert f"qs::mean_field_batch_kernel<{FORM_INDEX[form]}, " in log
 
 
