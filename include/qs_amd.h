@@ -464,7 +464,10 @@ const char* qs_last_dispatch(void);
  *     "pair_contract_g" (qs_pair_contract: vectors per load of U, 0 = the
  *     shipped group size of the dtype pair, 1, 2, 4 or 8 for tuning runs),
  *     "det_ci_g" (qs_det_ci_sigma: vectors per walk of a determinant's
- *     excitations, 0 = shipped, 1, 2, 4 or 8 for tuning runs).
+ *     excitations, 0 = shipped, 1, 2, 4 or 8 for tuning runs),
+ *     "string_ci_bytes" (qs_string_ci_group: the byte budget of the D and G
+ *     panels of one qs_string_ci_sigma call, 0 = the caller's shipped value;
+ *     a negative value is refused with QS_ERR_BAD_EXTENT).
  *   qs_probe_mfma_f64: register-resident fp64 MFMA loop, `blocks` workgroups
  *     of 4 waves, each wave issuing iters*8 v_mfma_f64_16x16x4_f64
  *     (flops = blocks*4*iters*8*2048); `sink` is a device scratch of
@@ -726,6 +729,72 @@ int qs_det_ci_transition_density1(int c_dtype, const int64_t* dets, const void* 
                                   void* rho, int64_t m, int64_t N, int64_t dim, void* stream);
 int qs_det_ci_density2(int c_dtype, const int64_t* dets, const void* bra, const void* ket,
                        void* gamma2, int64_t m, int64_t N, int64_t dim, void* stream);
+/*
+ * Spin-free configuration interaction on alpha and beta occupation strings
+ * (Knowles-Handy; csrc/qs_string_ci.hip), for SPATIAL orbitals:
+ *   H = sum_pr k[p,r] E_pr + sum_(pr),(qs) W[(pr),(qs)] E_pr E_qs,
+ *   E_pq = sum_spin a+_p,spin a_q,spin,
+ *   k[p,r] = ht[p,r] - 1/2 sum_q ut[p,q,q,r],
+ *   W[(pr),(qs)] = 1/2 ut[p,q,r,s]       (m^2 x m^2, row p*m + r, column q*m + s)
+ * with ht (m, m) and ut (m, m, m, m) = <pq|rs>, NOT anti-symmetrised.  A state
+ * is c[Ia * nb + Ib] over a list of na alpha and a list of nb beta strings:
+ * ascending, duplicate-free 64-bit masks over 1 <= m <= 63 spatial orbitals with
+ * Na and Nb bits; the determinant is all alpha creators first, ascending within
+ * each spin.  The lists are data: a replacement whose target string is missing
+ * contributes nothing.
+ *   qs_string_ci_table : T[K * m*m + p*m + q] (int32) of one list of n strings:
+ *       +-(index of J + 1) where <K|E_pq|J> = +-1 -- J = K - p + q, p in K, q not
+ *       in K or q = p, sign (-1)^(bits of K strictly between p and q) --, 0 where
+ *       the replacement is empty or J is not in the list.  One table per spin;
+ *       equal lists may share one (ta == tb is allowed below).
+ *   qs_string_ci_diagonal : D[Ia * nb + Ib] = <I|H|I>, na * nb doubles, from ht
+ *       and ut (real parts), n_p = n_p,alpha + n_p,beta:
+ *       sum_p n_p ht[p,p] + 1/2 sum_pq n_p n_q ut[p,q,p,q]
+ *                         - 1/2 sum_pq (n_pa n_qa + n_pb n_qb) ut[p,q,q,p].
+ *   qs_string_ci_sigma : sigma[k, Ia, Ib] = (H c_k)[Ia, Ib] for the K vectors of
+ *       c, (K, na, nb) contiguous in and out, in three steps without atomics:
+ *         expand : D[(qs), k, :] = E_qs c_k              (m^2 x K na nb, work)
+ *         product: G = W . D                             (the dispatcher of qs_matmul)
+ *         fold   : sigma_k = sum_pr E_pr (G[(pr), k, :] + k[p,r] c_k)
+ *       The fold's sum has a fixed order (pr ascending, alpha before beta, explicit
+ *       fmas): repeating a call gives the same bits.  Bit-equality of sigma_k
+ *       between DIFFERENT K (alone, in a batch, in another group) is NOT promised:
+ *       the product dispatcher chooses its kernel by the extents.
+ *   qs_string_ci_workspace : bytes of `work` for K vectors,
+ *         2 * ceil16(m^2 * K * na * nb * sizeof(element of c)),
+ *       D then G.  qs_string_ci_density1 needs D only, for one vector: the query
+ *       with K = 1 is sufficient for it (half of it is what it checks).
+ *   qs_string_ci_group : the number of vectors, 1 ... K, to send per
+ *       qs_string_ci_sigma call so that its workspace stays within budget_bytes
+ *       (the calling thread's tuning key "string_ci_bytes" when that is set; 2 GiB
+ *       when both are 0) and its product within 2^31 - 1 columns; at least 1.
+ *       A positive tuning key takes precedence over budget_bytes: it is the
+ *       override of a tuning run, not a default.
+ *   qs_string_ci_density1 : rho[q * m + p] = <bra| E_pq |ket>
+ *       = sum_K conj(bra[K]) (E_pq ket)[K], spin-summed, one expand of ket and one
+ *       fixed-order sum per (p, q); bra == ket (the same pointer is allowed) is a
+ *       state's density.
+ * dtype pairs (ht, ut, k, W; c): (F64, F64), (C128, C128) and (F64, C128), which
+ * runs the product in fp64 on the re / im pairs of D as 2 K na nb columns (no
+ * complex copy of W); (C128, F64) is QS_ERR_BAD_DTYPE.
+ * Errors, checked in this order before any HIP call: dtype (pair), extents (m
+ * outside 1 ... 63, Na or Nb outside 0 ... m, a list of < 1 or >= 2^31 - 1
+ * strings, K < 1, more than 2^31 - 1 columns K na nb -- 2 K na nb for (F64,
+ * C128) -- in one call), null pointer, misaligned pointer (element size; 8 for
+ * strings and D, 4 for tables, 16 for work), work_bytes too small
+ * (QS_ERR_WORKSPACE), an output overlapping an input or the workspace, or the
+ * workspace overlapping an input (QS_ERR_ALIAS).  A table entry that points past its list is read as 0.
+ */
+int qs_string_ci_table(const int64_t* strings, int64_t n, int64_t m, int64_t N, int32_t* table, void* stream);
+int qs_string_ci_diagonal(int h_dtype, const void* ht, const void* ut, const int64_t* sa, int64_t na, int64_t Na,
+                          const int64_t* sb, int64_t nb, int64_t Nb, int64_t m, double* D, void* stream);
+int64_t qs_string_ci_workspace(int h_dtype, int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t K);
+int64_t qs_string_ci_group(int h_dtype, int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t K, int64_t budget_bytes);
+int qs_string_ci_sigma(int h_dtype, int c_dtype, const void* k, const void* W, const int32_t* ta, const int32_t* tb,
+                       int64_t m, int64_t na, int64_t nb, const void* c, int64_t K, void* sigma,
+                       void* work, int64_t work_bytes, void* stream);
+int qs_string_ci_density1(int c_dtype, const int32_t* ta, const int32_t* tb, int64_t m, int64_t na, int64_t nb,
+                          const void* bra, const void* ket, void* rho, void* work, int64_t work_bytes, void* stream);
 int qs_probe_mfma_f64(void* sink, int64_t blocks, int64_t iters, void* stream);
 int qs_probe_stream_copy(const void* src, void* dst, int64_t bytes, void* stream);
 

@@ -232,6 +232,7 @@ struct Tuning {
                                  // (every setting gives the same bits: the fma chains and the closing butterfly do not know G)
     int det_ci_g = 0;            // qs_det_ci_sigma: vectors per walk of a determinant's excitations, 0 = the shipped group size of the form;
                                  // 1, 2, 4, 8 = tuning runs (every setting gives the same bits: a vector's fma chain does not know G)
+    int64_t string_ci_bytes = 0; // qs_string_ci_group: byte budget of the D and G panels of one qs_string_ci_sigma call, 0 = the caller's shipped value
     int sandwich = 1;            // 4-wide fused passes of a small-basis transform: 0 off, 1 both (d, c) and (b, a), 2 (d, c) only, 3 (b, a) only;
                                  // tuning runs, wherever the kernel exists (not only where it measured faster): 4 both, 5 (d, c) only, 6 (b, a) only
 };

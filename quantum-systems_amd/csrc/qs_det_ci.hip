@@ -31,6 +31,7 @@
 // so that <bra|H|ket> = sum_pq ht[p,q] rho[q,p] + 1/4 sum_pqrs ut[p,q,r,s] gamma2[p,q,r,s]; bra = ket is a state's density.
 
 #include "qs_contract_common.h"
+#include "qs_strings.h"
 
 namespace qs {
 
@@ -50,27 +51,6 @@ struct DcArgs {
     int64_t dim, ldc;
     int m, ng;                // ng = vectors of this launch, 1 ... G of the instantiation
 };
-
-__device__ __forceinline__ uint64_t dc_bit(int p) { return uint64_t(1) << p; }
-
-// orbitals strictly between a and b
-__device__ __forceinline__ uint64_t dc_between(int a, int b) {
-    const int lo = a < b ? a : b, hi = a < b ? b : a;
-    return (dc_bit(hi) - 1) & ~((dc_bit(lo) << 1) - 1);
-}
-
-__device__ __forceinline__ int dc_lowest(uint64_t x) { return __ffsll((unsigned long long)x) - 1; }
-
-// position of mask J in dets, or -1
-__device__ __forceinline__ int64_t dc_find(const int64_t* __restrict__ dets, int64_t dim, uint64_t J) {
-    int64_t lo = 0, hi = dim;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if ((uint64_t)dets[mid] < J) lo = mid + 1;
-        else hi = mid;
-    }
-    return (lo < dim && (uint64_t)dets[lo] == J) ? lo : -1;
-}
 
 // acc[g] += e * c[J, g] for the launch's vectors; CW = doubles per element
 template <int CW, int G>

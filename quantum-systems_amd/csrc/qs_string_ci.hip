@@ -1,0 +1,441 @@
+// Spin-free configuration interaction on alpha and beta occupation strings (Knowles-Handy): H c with the two-body part
+// as ONE dense product on the library's product dispatcher.
+//   H = sum_pr k[p,r] E_pr + sum_(pr),(qs) W[(pr),(qs)] E_pr E_qs,      E_pq = sum_spin a+_p,spin a_q,spin
+//   k[p,r] = ht[p,r] - 1/2 sum_q ut[p,q,q,r],      W[(pr),(qs)] = 1/2 ut[p,q,r,s]   (ut = <pq|rs>, NOT anti-symmetrised)
+// A state is c[Ia, Ib] (Ib fastest) over a list of na alpha and a list of nb beta strings: ascending 64-bit masks over
+// m <= 63 SPATIAL orbitals; the determinant is all alpha creators first, ascending within each spin, so E_pq acts on one
+// string at a time with that string's own sign.  The lists are data: a replacement whose target is missing contributes
+// nothing.
+//
+// The replacement table of a list is T[K, p * m + q] (int32): +-(index of J + 1) where <K|E_pq|J> = +-1, i.e.
+// J = K - p + q with p in K and q not in K or q = p, sign (-1)^(bits of K strictly between p and q); 0 where the
+// replacement is empty or its target is not in the list.  It is the only place a string is searched for.
+//
+// One sigma per group of K vectors, three steps, no atomics:
+//   expand : D[(qs), k, Ka, Kb] = (E_qs c_k)[Ka, Kb] = sgn c_k[Ta[Ka,qs], Kb] + sgn c_k[Ka, Tb[Kb,qs]]     (m^2 x K dim)
+//   product: G = W . D                                                            gemm(Product{...}), qs_gemm.hip
+//   fold   : sigma_k[Ia, Ib] = sum_pr ( sgn X[(pr), k, Ta[Ia,pr], Ib] + sgn X[(pr), k, Ia, Tb[Ib,pr]] ),
+//            X[(pr), k, K] = G[(pr), k, K] + k[p,r] c_k[K]
+// expand and fold are streams of m^2 K dim elements.  A workgroup owns one alpha string Ia and a tile of up to 256
+// consecutive beta strings, thread t the string Ib = tile + t: the alpha part reads and writes whole contiguous rows,
+// and its table entry Ta[Ia, pq] has a wave-uniform address (Ia comes from the workgroup's index, pq from the loop
+// counter), so it is a scalar load.  The beta part gathers inside the one row c[Ia, :] of nb elements; its table
+// entries are staged through LDS in chunks of 16 columns, read from T row-wise (64 contiguous bytes per string) and
+// stored column-wise, so that a lane reads its own entry without a bank conflict.
+// The fold's sum has a fixed order -- pr ascending, alpha before beta, every product an explicit fma --, skips the
+// table's zeros, and never sees another vector: repeating a call gives the same bits.  (The PRODUCT is chosen by its
+// extents, so sigma_k alone and sigma_k in a batch agree to rounding, not bit for bit.)
+// A table entry that points at or past the end of its list is treated as 0: a wrong table gives wrong numbers, never
+// an access outside the arguments.
+
+#include "qs_contract_common.h"
+#include "qs_strings.h"
+
+namespace qs {
+
+constexpr int kScChunk = 16;          // table columns staged per step
+constexpr int kScBlock = 256;         // most beta strings (threads) of a workgroup; 64 or 128 for shorter lists
+constexpr int kScRhoBlock = 256;      // threads of the density's and of the diagonal's workgroup
+// Shipped byte budget of the D and G of one qs_string_ci_sigma call: qs_string_ci_group() splits a batch by it when
+// the caller passes 0 (kernels.STRING_CI_BYTES passes its own).  Not measured yet.
+constexpr int64_t kScBytes = int64_t(2) << 30;
+
+struct ScArgs {
+    const int32_t* ta;        // (na, m^2)
+    const int32_t* tb;        // (nb, m^2)
+    const double* c;          // (K, na, nb)
+    const double* kk;         // (m, m), fold only
+    const double* G;          // (m^2, K, na, nb), fold only
+    double* out;              // expand: D (m^2, K, na, nb); fold: sigma (K, na, nb)
+    int64_t na, nb;
+    unsigned ntile;           // tiles of blockDim.x beta strings
+    int m2, K;
+};
+
+// The workgroup's chunk of the beta table, columns pq0 ... pq0 + 15 of its strings: sc_tb[j][r] = Tb[ib0 + r, pq0 + j].
+__device__ __forceinline__ void sc_stage(int32_t* sc_tb, const int32_t* __restrict__ tb, int64_t ib0, int64_t nb, int pq0,
+                                         int m2) {
+    const int B = blockDim.x;
+    for (int idx = threadIdx.x; idx < B * kScChunk; idx += B) {
+        const int r = idx / kScChunk, j = idx % kScChunk;
+        const int64_t row = ib0 + r;
+        const int pq = pq0 + j;
+        sc_tb[j * (B + 1) + r] = (row < nb && pq < m2) ? tb[row * m2 + pq] : 0;
+    }
+}
+
+// index behind a table entry e != 0, or -1 when it points past the n strings of the list
+__device__ __forceinline__ int64_t sc_target(int32_t e, int64_t n) {
+    const int64_t j = (int64_t)(e < 0 ? -e : e) - 1;
+    return j < n ? j : -1;
+}
+
+template <int CW>
+__global__ __launch_bounds__(kScBlock) void string_ci_expand_kernel(const ScArgs a, const int32_t* __restrict__ ta,
+                                                                   double* __restrict__ D) {
+    // ta and D are kernel arguments of their own: only there does __restrict__ tell the compiler that the stores of D
+    // cannot change the table, which lets the uniform read below be a scalar load
+    extern __shared__ __attribute__((aligned(16))) int32_t sc_tb[];
+    const int B = blockDim.x, t = threadIdx.x, m2 = a.m2;
+    const int64_t ia = blockIdx.x / a.ntile;                              // uniform
+    const int64_t ib0 = (int64_t)(blockIdx.x % a.ntile) * B;
+    const int64_t ib = ib0 + t, nb = a.nb, dim = a.na * a.nb;
+    const bool live = ib < nb;
+    const int32_t* __restrict__ ta_row = ta + ia * m2;
+    const double* __restrict__ c = a.c;
+    for (int pq0 = 0; pq0 < m2; pq0 += kScChunk) {
+        __syncthreads();
+        sc_stage(sc_tb, a.tb, ib0, nb, pq0, m2);
+        __syncthreads();
+        if (!live) continue;
+        const int nj = m2 - pq0 < kScChunk ? m2 - pq0 : kScChunk;
+        for (int j = 0; j < nj; ++j) {
+            const int pq = pq0 + j;
+            const int32_t ea = ta_row[pq];                                // uniform address: a scalar load
+            const int32_t eb = sc_tb[j * (B + 1) + t];
+            const int64_t ja = ea ? sc_target(ea, a.na) : -1, jb = eb ? sc_target(eb, nb) : -1;
+            for (int k = 0; k < a.K; ++k) {
+                const double* __restrict__ ck = c + (int64_t)k * dim * CW;
+                double v[CW];
+#pragma unroll
+                for (int w = 0; w < CW; ++w) v[w] = 0.0;
+                if (ja >= 0) {
+                    const double* x = ck + (ja * nb + ib) * CW;
+#pragma unroll
+                    for (int w = 0; w < CW; ++w) v[w] = ea < 0 ? -x[w] : x[w];
+                }
+                if (jb >= 0) {
+                    const double* x = ck + (ia * nb + jb) * CW;
+#pragma unroll
+                    for (int w = 0; w < CW; ++w) v[w] += eb < 0 ? -x[w] : x[w];
+                }
+                double* d = D + (((int64_t)pq * a.K + k) * dim + ia * nb + ib) * CW;
+#pragma unroll
+                for (int w = 0; w < CW; ++w) d[w] = v[w];
+            }
+        }
+    }
+}
+
+// acc += s (g + kk c) at one element: HW doubles per element of kk, CW per element of g, c and acc
+template <int HW, int CW>
+__device__ __forceinline__ void sc_feed(double (&acc)[CW], const double (&kk)[HW], const double* __restrict__ g,
+                                        const double* __restrict__ c, bool minus) {
+    const double s = minus ? -1.0 : 1.0;
+    if constexpr (CW == 1) {
+        acc[0] = fma(s, fma(kk[0], c[0], g[0]), acc[0]);
+    } else {
+        double xr = fma(kk[0], c[0], g[0]), xi = fma(kk[0], c[1], g[1]);
+        if constexpr (HW == 2) {
+            xr = fma(-kk[HW - 1], c[1], xr);
+            xi = fma(kk[HW - 1], c[0], xi);
+        }
+        acc[0] = fma(s, xr, acc[0]);
+        acc[CW - 1] = fma(s, xi, acc[CW - 1]);
+    }
+}
+
+template <int FORM>
+__global__ __launch_bounds__(kScBlock) void string_ci_fold_kernel(const ScArgs a) {
+    constexpr int HW = form_widths(FORM).uw, CW = form_widths(FORM).aw;
+    extern __shared__ __attribute__((aligned(16))) int32_t sc_tb[];
+    const int B = blockDim.x, t = threadIdx.x, m2 = a.m2;
+    const unsigned row = blockIdx.x / a.ntile;                            // (k, ia), uniform
+    const int64_t k = row / (unsigned)a.na, ia = row % (unsigned)a.na;
+    const int64_t ib0 = (int64_t)(blockIdx.x % a.ntile) * B;
+    const int64_t ib = ib0 + t, nb = a.nb, dim = a.na * a.nb;
+    const bool live = ib < nb;
+    const int32_t* __restrict__ ta_row = a.ta + ia * m2;
+    const double* __restrict__ ck = a.c + k * dim * CW;
+    const double* __restrict__ kk = a.kk;
+    double acc[CW];
+#pragma unroll
+    for (int w = 0; w < CW; ++w) acc[w] = 0.0;
+    for (int pr0 = 0; pr0 < m2; pr0 += kScChunk) {
+        __syncthreads();
+        sc_stage(sc_tb, a.tb, ib0, nb, pr0, m2);
+        __syncthreads();
+        if (!live) continue;
+        const int nj = m2 - pr0 < kScChunk ? m2 - pr0 : kScChunk;
+        for (int j = 0; j < nj; ++j) {
+            const int pr = pr0 + j;
+            const int32_t ea = ta_row[pr];                                // uniform address: a scalar load
+            const int32_t eb = sc_tb[j * (B + 1) + t];
+            double kpr[HW];
+#pragma unroll
+            for (int w = 0; w < HW; ++w) kpr[w] = kk[pr * HW + w];
+            const double* __restrict__ g = a.G + ((int64_t)pr * a.K + k) * dim * CW;
+            if (ea) {
+                const int64_t ja = sc_target(ea, a.na);
+                if (ja >= 0) sc_feed<HW, CW>(acc, kpr, g + (ja * nb + ib) * CW, ck + (ja * nb + ib) * CW, ea < 0);
+            }
+            if (eb) {
+                const int64_t jb = sc_target(eb, nb);
+                if (jb >= 0) sc_feed<HW, CW>(acc, kpr, g + (ia * nb + jb) * CW, ck + (ia * nb + jb) * CW, eb < 0);
+            }
+        }
+    }
+    if (live) {
+#pragma unroll
+        for (int w = 0; w < CW; ++w) a.out[(k * dim + ia * nb + ib) * CW + w] = acc[w];
+    }
+}
+
+// T[K, p * m + q] of one string list: one thread per entry (grid-stride).
+__global__ __launch_bounds__(kScRhoBlock) void string_ci_table_kernel(const int64_t* __restrict__ strings, int64_t n, int m,
+                                                                      int32_t* __restrict__ table) {
+    const int64_t total = n * m * m, step = (int64_t)gridDim.x * kScRhoBlock;
+    for (int64_t idx = (int64_t)blockIdx.x * kScRhoBlock + threadIdx.x; idx < total; idx += step) {
+        const int64_t row = idx / (m * m);
+        const int pq = (int)(idx % (m * m)), p = pq / m, q = pq % m;
+        const uint64_t Kmask = (uint64_t)strings[row] & (dc_bit(m) - 1);
+        int32_t e = 0;
+        if ((Kmask & dc_bit(p)) && (p == q || !(Kmask & dc_bit(q)))) {
+            const int64_t pos = p == q ? row : dc_find(strings, n, Kmask ^ dc_bit(p) ^ dc_bit(q));
+            if (pos >= 0) {
+                const bool minus = (__popcll((unsigned long long)(Kmask & dc_between(p, q))) & 1) != 0;
+                e = minus ? -(int32_t)(pos + 1) : (int32_t)(pos + 1);
+            }
+        }
+        table[idx] = e;
+    }
+}
+
+// D[Ia, Ib] = sum_p n_p ht[p,p] + 1/2 sum_pq n_p n_q ut[p,q,p,q] - 1/2 sum_pq (n_pa n_qa + n_pb n_qb) ut[p,q,q,p]  (real
+// parts): one thread per determinant (grid-stride), p and q ascending over the occupied orbitals.
+template <int HW>
+__global__ __launch_bounds__(kScRhoBlock) void string_ci_diagonal_kernel(const double* __restrict__ ht, const double* __restrict__ ut,
+                                                                         const int64_t* __restrict__ sa, const int64_t* __restrict__ sb,
+                                                                         int64_t na, int64_t nb, int m, double* __restrict__ D) {
+    const int64_t total = na * nb, step = (int64_t)gridDim.x * kScRhoBlock;
+    const uint64_t all = dc_bit(m) - 1;
+    for (int64_t idx = (int64_t)blockIdx.x * kScRhoBlock + threadIdx.x; idx < total; idx += step) {
+        const uint64_t A = (uint64_t)sa[idx / nb] & all, Bm = (uint64_t)sb[idx % nb] & all;
+        double d = 0.0;
+        for (uint64_t po = A | Bm; po; po &= po - 1) {
+            const int p = dc_lowest(po);
+            const double pa = (double)((A >> p) & 1), pb = (double)((Bm >> p) & 1);
+            d = fma(pa + pb, ht[(size_t)(p * m + p) * HW], d);
+            for (uint64_t qo = A | Bm; qo; qo &= qo - 1) {
+                const int q = dc_lowest(qo);
+                const double qa = (double)((A >> q) & 1), qb = (double)((Bm >> q) & 1);
+                d = fma(0.5 * (pa + pb) * (qa + qb), ut[(size_t)(((p * m + q) * m + p) * m + q) * HW], d);
+                d = fma(-0.5 * (pa * qa + pb * qb), ut[(size_t)(((p * m + q) * m + q) * m + p) * HW], d);
+            }
+        }
+        D[idx] = d;
+    }
+}
+
+// rho[q * m + p] = sum_K conj(bra[K]) D[(pq), K]: one workgroup per pq = p * m + q strides over the dim determinants and
+// closes with the xor butterfly of each wave and a fixed sum over the four waves.
+template <int CW>
+__global__ __launch_bounds__(kScRhoBlock) void string_ci_dot_kernel(const double* __restrict__ bra, const double* __restrict__ D,
+                                                                    double* __restrict__ rho, int m, int64_t dim) {
+    __shared__ double part[kScRhoBlock / 64][CW];
+    const int p = blockIdx.x / m, q = blockIdx.x % m, tid = threadIdx.x;
+    const double* __restrict__ row = D + (int64_t)blockIdx.x * dim * CW;
+    double acc[CW];
+#pragma unroll
+    for (int w = 0; w < CW; ++w) acc[w] = 0.0;
+    for (int64_t i = tid; i < dim; i += kScRhoBlock) {
+        if constexpr (CW == 1) {
+            acc[0] = fma(bra[i], row[i], acc[0]);
+        } else {
+            const double ar = bra[2 * i], ai = bra[2 * i + 1], br = row[2 * i], bi = row[2 * i + 1];
+            acc[0] = fma(ai, bi, fma(ar, br, acc[0]));                    // conj(a) b
+            acc[CW - 1] = fma(-ai, br, fma(ar, bi, acc[CW - 1]));
+        }
+    }
+    const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int w = 0; w < CW; ++w) {
+#pragma unroll
+        for (int mask = 32; mask >= 1; mask >>= 1) acc[w] += __shfl_xor(acc[w], mask);
+        if (lane == 0) part[wave][w] = acc[w];
+    }
+    __syncthreads();
+    if (tid < CW) {
+        double s = part[0][tid];
+#pragma unroll
+        for (int v = 1; v < kScRhoBlock / 64; ++v) s += part[v][tid];
+        rho[(size_t)(q * m + p) * CW + tid] = s;
+    }
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------
+
+static inline bool sc_list_ok(int64_t n) { return n >= 1 && n < 0x7fffffffLL; }
+
+// Extents of one call on K vectors: the columns of its product (K na nb elements of c, twice that as real columns for a
+// real W against complex c) fit the product's 32-bit extents, which also keeps every grid below 2^31 workgroups.
+static inline bool sc_extents_ok(int form, int64_t m, int64_t na, int64_t nb, int64_t K) {
+    if (m < 1 || m > 63 || !sc_list_ok(na) || !sc_list_ok(nb) || K < 1) return false;
+    int64_t cols;
+    if (__builtin_mul_overflow(na * nb, K, &cols) || __builtin_mul_overflow(cols, (int64_t)(form == 2 ? 2 : 1), &cols)) return false;
+    return cols <= 0x7fffffffLL;
+}
+
+// bytes of D (and of G): m^2 K na nb elements of c, to the next multiple of 16
+static inline int64_t sc_panel_bytes(int form, int64_t m, int64_t na, int64_t nb, int64_t K) {
+    return (m * m * K * na * nb * 8 * form_widths(form).aw + 15) & ~int64_t(15);      // < 2^12 * 2^31 * 16; G stays 16-byte aligned
+}
+
+static inline int sc_threads(int64_t nb) { return nb <= 64 ? 64 : (nb <= 128 ? 128 : kScBlock); }
+static inline size_t sc_lds(int threads) { return sizeof(int32_t) * kScChunk * (threads + 1); }
+
+static ScArgs sc_args(const int32_t* ta, const int32_t* tb, const void* c, int64_t m, int64_t na, int64_t nb, int64_t K) {
+    ScArgs a{};
+    a.ta = ta; a.tb = tb; a.c = (const double*)c;
+    a.na = na; a.nb = nb; a.m2 = (int)(m * m); a.K = (int)K;
+    a.ntile = (unsigned)cdiv(nb, sc_threads(nb));
+    return a;
+}
+
+// D = expand(c) for the K vectors of c
+static int sc_expand(int cw, ScArgs a, void* D, hipStream_t s) {
+    a.out = (double*)D;
+    const int threads = sc_threads(a.nb);
+    const unsigned grid = (unsigned)(a.na * a.ntile);
+    if (cw == 1) hipLaunchKernelGGL((string_ci_expand_kernel<1>), dim3(grid), dim3(threads), sc_lds(threads), s, a, a.ta, a.out);
+    else hipLaunchKernelGGL((string_ci_expand_kernel<2>), dim3(grid), dim3(threads), sc_lds(threads), s, a, a.ta, a.out);
+    note_dispatch("qs::string_ci_expand_kernel<%d>", cw);
+    return launch_status("string CI expand launch");
+}
+
+static unsigned sc_stride_grid(int64_t total) {
+    const int64_t want = cdiv(total, kScRhoBlock);
+    return (unsigned)(want < 65536 ? want : 65536);
+}
+
+}  // namespace qs
+
+using namespace qs;
+
+extern "C" {
+
+int qs_string_ci_table(const int64_t* strings, int64_t n, int64_t m, int64_t N, int32_t* table, void* stream) {
+    dispatch_reset();
+    if (m < 1 || m > 63 || N < 0 || N > m || !sc_list_ok(n)) return QS_ERR_BAD_EXTENT;
+    if (!strings || !table) return QS_ERR_NULL_POINTER;
+    if (!aligned(strings, 8) || !aligned(table, 4)) return QS_ERR_MISALIGNED;
+    if (overlaps(table, n * m * m * 4, strings, n * 8)) return QS_ERR_ALIAS;
+    hipLaunchKernelGGL(string_ci_table_kernel, dim3(sc_stride_grid(n * m * m)), dim3(kScRhoBlock), 0, (hipStream_t)stream,
+                       strings, n, (int)m, table);
+    note_dispatch("qs::string_ci_table_kernel");
+    return launch_status("string CI table launch");
+}
+
+int qs_string_ci_diagonal(int h_dtype, const void* ht, const void* ut, const int64_t* sa, int64_t na, int64_t Na,
+                          const int64_t* sb, int64_t nb, int64_t Nb, int64_t m, double* D, void* stream) {
+    dispatch_reset();
+    if (!dtype_ok(h_dtype)) return QS_ERR_BAD_DTYPE;
+    if (m < 1 || m > 63 || Na < 0 || Na > m || Nb < 0 || Nb > m || !sc_list_ok(na) || !sc_list_ok(nb)) return QS_ERR_BAD_EXTENT;
+    if (!ht || !ut || !sa || !sb || !D) return QS_ERR_NULL_POINTER;
+    const int64_t es = (int64_t)elem_size(h_dtype);
+    if (!aligned(ht, (size_t)es) || !aligned(ut, (size_t)es) || !aligned(sa, 8) || !aligned(sb, 8) || !aligned(D, 8))
+        return QS_ERR_MISALIGNED;
+    const int64_t d_bytes = na * nb * 8;
+    if (overlaps(D, d_bytes, ht, m * m * es) || overlaps(D, d_bytes, ut, m * m * m * m * es) ||
+        overlaps(D, d_bytes, sa, na * 8) || overlaps(D, d_bytes, sb, nb * 8))
+        return QS_ERR_ALIAS;
+    const unsigned grid = sc_stride_grid(na * nb);
+    hipStream_t s = (hipStream_t)stream;
+    if (h_dtype == QS_F64)
+        hipLaunchKernelGGL((string_ci_diagonal_kernel<1>), dim3(grid), dim3(kScRhoBlock), 0, s, (const double*)ht, (const double*)ut, sa, sb, na, nb, (int)m, D);
+    else
+        hipLaunchKernelGGL((string_ci_diagonal_kernel<2>), dim3(grid), dim3(kScRhoBlock), 0, s, (const double*)ht, (const double*)ut, sa, sb, na, nb, (int)m, D);
+    note_dispatch("qs::string_ci_diagonal_kernel<%d>", h_dtype == QS_F64 ? 1 : 2);
+    return launch_status("string CI diagonal launch");
+}
+
+int64_t qs_string_ci_workspace(int h_dtype, int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t K) {
+    const int form = tensor_form(h_dtype, c_dtype);
+    if (form < 0) return form;
+    if (!sc_extents_ok(form, m, na, nb, K)) return QS_ERR_BAD_EXTENT;
+    return 2 * sc_panel_bytes(form, m, na, nb, K);
+}
+
+int64_t qs_string_ci_group(int h_dtype, int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t K, int64_t budget_bytes) {
+    const int form = tensor_form(h_dtype, c_dtype);
+    if (form < 0) return form;
+    if (!sc_extents_ok(form, m, na, nb, 1) || K < 1 || budget_bytes < 0) return QS_ERR_BAD_EXTENT;
+    const int64_t budget = g_tune.string_ci_bytes > 0 ? g_tune.string_ci_bytes : (budget_bytes > 0 ? budget_bytes : kScBytes);
+    int64_t g = budget / (2 * sc_panel_bytes(form, m, na, nb, 1));
+    const int64_t cols = 0x7fffffffLL / (na * nb * (form == 2 ? 2 : 1));      // the product's 32-bit extent
+    g = g < cols ? g : cols;
+    return g < 1 ? 1 : (g < K ? g : K);
+}
+
+int qs_string_ci_sigma(int h_dtype, int c_dtype, const void* k, const void* W, const int32_t* ta, const int32_t* tb,
+                       int64_t m, int64_t na, int64_t nb, const void* c, int64_t K, void* sigma, void* work,
+                       int64_t work_bytes, void* stream) {
+    dispatch_reset();
+    const int form = tensor_form(h_dtype, c_dtype);
+    if (form < 0) return form;
+    if (!sc_extents_ok(form, m, na, nb, K)) return QS_ERR_BAD_EXTENT;
+    if (!k || !W || !ta || !tb || !c || !sigma || !work) return QS_ERR_NULL_POINTER;
+    const int64_t hs = (int64_t)elem_size(h_dtype), cs = (int64_t)elem_size(c_dtype);
+    if (!aligned(k, (size_t)hs) || !aligned(W, (size_t)hs) || !aligned(ta, 4) || !aligned(tb, 4) || !aligned(c, (size_t)cs) ||
+        !aligned(sigma, (size_t)cs) || !aligned(work, 16))
+        return QS_ERR_MISALIGNED;
+    const int64_t panel = sc_panel_bytes(form, m, na, nb, K);
+    if (work_bytes < 2 * panel) return QS_ERR_WORKSPACE;
+    const int64_t m2 = m * m, s_bytes = K * na * nb * cs;
+    if (overlaps(sigma, s_bytes, c, s_bytes) || overlaps(sigma, s_bytes, W, m2 * m2 * hs) || overlaps(sigma, s_bytes, k, m2 * hs) ||
+        overlaps(sigma, s_bytes, ta, na * m2 * 4) || overlaps(sigma, s_bytes, tb, nb * m2 * 4) ||
+        overlaps(sigma, s_bytes, work, 2 * panel) || overlaps(work, 2 * panel, c, s_bytes) || overlaps(work, 2 * panel, W, m2 * m2 * hs) ||
+        overlaps(work, 2 * panel, k, m2 * hs) || overlaps(work, 2 * panel, ta, na * m2 * 4) || overlaps(work, 2 * panel, tb, nb * m2 * 4))
+        return QS_ERR_ALIAS;
+
+    hipStream_t s = (hipStream_t)stream;
+    const FormWidths fw = form_widths(form);
+    char* D = (char*)work;
+    char* G = D + panel;
+    ScArgs a = sc_args(ta, tb, c, m, na, nb, K);
+    int rc = sc_expand(fw.aw, a, D, s);
+    if (rc) return rc;
+    // real W against complex c: the re / im pairs of D are columns of a real product
+    rc = gemm(packed(h_dtype, W, D, G, m2, K * na * nb * (fw.aw / fw.uw), m2), s);
+    if (rc) return rc;
+    a.kk = (const double*)k; a.G = (const double*)G; a.out = (double*)sigma;
+    const int threads = sc_threads(nb);
+    const unsigned grid = (unsigned)(K * na * a.ntile);
+    with_form(form, [&](auto FORM) {
+        hipLaunchKernelGGL((string_ci_fold_kernel<FORM>), dim3(grid), dim3(threads), sc_lds(threads), s, a);
+        note_dispatch("qs::string_ci_fold_kernel<%d>", (int)FORM);
+    });
+    return launch_status("string CI fold launch");
+}
+
+int qs_string_ci_density1(int c_dtype, const int32_t* ta, const int32_t* tb, int64_t m, int64_t na, int64_t nb,
+                          const void* bra, const void* ket, void* rho, void* work, int64_t work_bytes, void* stream) {
+    dispatch_reset();
+    if (!dtype_ok(c_dtype)) return QS_ERR_BAD_DTYPE;
+    const int form = c_dtype == QS_C128 ? 1 : 0;
+    if (!sc_extents_ok(form, m, na, nb, 1)) return QS_ERR_BAD_EXTENT;
+    if (!ta || !tb || !bra || !ket || !rho || !work) return QS_ERR_NULL_POINTER;
+    const int64_t cs = (int64_t)elem_size(c_dtype);
+    if (!aligned(ta, 4) || !aligned(tb, 4) || !aligned(bra, (size_t)cs) || !aligned(ket, (size_t)cs) || !aligned(rho, (size_t)cs) ||
+        !aligned(work, 16))
+        return QS_ERR_MISALIGNED;
+    const int64_t panel = sc_panel_bytes(form, m, na, nb, 1);
+    if (work_bytes < panel) return QS_ERR_WORKSPACE;
+    const int64_t m2 = m * m, r_bytes = m2 * cs, v_bytes = na * nb * cs;
+    if (overlaps(rho, r_bytes, bra, v_bytes) || overlaps(rho, r_bytes, ket, v_bytes) || overlaps(rho, r_bytes, ta, na * m2 * 4) ||
+        overlaps(rho, r_bytes, tb, nb * m2 * 4) || overlaps(rho, r_bytes, work, panel) || overlaps(work, panel, bra, v_bytes) ||
+        overlaps(work, panel, ket, v_bytes) || overlaps(work, panel, ta, na * m2 * 4) || overlaps(work, panel, tb, nb * m2 * 4))
+        return QS_ERR_ALIAS;
+    hipStream_t s = (hipStream_t)stream;
+    const int cw = form_widths(form).aw;
+    const int rc = sc_expand(cw, sc_args(ta, tb, ket, m, na, nb, 1), work, s);
+    if (rc) return rc;
+    if (cw == 1)
+        hipLaunchKernelGGL((string_ci_dot_kernel<1>), dim3((unsigned)m2), dim3(kScRhoBlock), 0, s, (const double*)bra, (const double*)work, (double*)rho, (int)m, na * nb);
+    else
+        hipLaunchKernelGGL((string_ci_dot_kernel<2>), dim3((unsigned)m2), dim3(kScRhoBlock), 0, s, (const double*)bra, (const double*)work, (double*)rho, (int)m, na * nb);
+    note_dispatch("qs::string_ci_dot_kernel<%d>", cw);
+    return launch_status("string CI density launch");
+}
+
+}  // extern "C"

@@ -158,3 +158,16 @@ class HartreeFock:
                 "the system is in its Hartree-Fock basis already (change_system_basis): C no longer refers to it -- "
                 "call configuration_interaction.CIS(system)")
         return CIS(self.system, self.C, self.epsilon, **kw)
+
+    def string_ci(self, **kw):
+        """Exact states of a restricted (``SpatialOrbitalSystem``) solution in the converged orbitals:
+        ``string_ci.StringCI(system, C, **kw)``."""
+        from .string_ci import StringCI
+
+        if self.C is None:
+            raise RuntimeError("run scf() first")
+        if self._basis_changed:
+            raise RuntimeError(
+                "the system is in its Hartree-Fock basis already (change_system_basis): C no longer refers to it -- "
+                "call string_ci.StringCI(system)")
+        return StringCI(self.system, self.C, **kw)

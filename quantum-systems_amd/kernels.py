@@ -946,6 +946,147 @@ def det_ci_density2(dets, bra, ket, m, N, out=None):
     return out
 
 
+# Byte budget of the D and G panels of ONE qs_string_ci_sigma call: ``string_ci_sigma`` sends a batch in groups of as
+# many vectors as fit it (at least one).  The tuning key ``string_ci_bytes`` overrides it for the calling thread.
+STRING_CI_BYTES = 2 << 30
+
+
+def _strings_checked(strings, what):
+    if not isinstance(strings, torch.Tensor) or strings.dtype != torch.int64 or strings.dim() != 1 or strings.numel() < 1:
+        raise ValueError(f"{what} must be a non-empty 1-D int64 tensor of occupation strings")
+    return _dev(strings)
+
+
+def _string_tables(ta, tb, m):
+    """The two replacement tables (n, m^2) int32 of the string kernels; the SAME tensor twice stays one."""
+    for t in (ta, tb):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != m * m or t.shape[0] < 1:
+            raise ValueError(f"a replacement table must be an (n, {m * m}) int32 tensor (string_ci_table)")
+    same = ta is tb
+    ta = _dev(ta)
+    return ta, (ta if same else _dev(tb))
+
+
+@_plain
+def string_ci_table(strings, m, N, out=None):
+    """Replacement table ``T[K, p m + q]`` (n, m^2) int32 of the ascending int64 occupation ``strings`` (``N`` bits over
+    ``m`` spatial orbitals) on ``qs_string_ci_table``: ``+-(index of J + 1)`` where ``<K|E_pq|J> = +-1``, 0 where the
+    replacement is empty or its target is not in the list."""
+    lib = _lib.load()
+    strings = _strings_checked(strings, "strings")
+    n, m = strings.numel(), int(m)
+    if out is None:
+        out = torch.empty((n, m * m) if 1 <= m <= 63 else (0, 0), dtype=torch.int32, device=strings.device)
+    else:
+        _check_out(out, (n, m * m), torch.int32, "string_ci_table")
+    with _on_device_of(strings, out):
+        _ran(lib.qs_string_ci_table(strings.data_ptr(), n, m, int(N), out.data_ptr(), _stream()), "qs_string_ci_table")
+    return out
+
+
+@_plain
+def string_ci_diagonal(ht, ut, strings_a, Na, strings_b, Nb, out=None):
+    """``D[Ia, Ib] = <I|H|I>`` (na, nb), real fp64, of the determinants of two string lists over the m spatial orbitals of
+    ``ht`` (m, m) and the plain ``ut = <pq|rs>`` (m, m, m, m), on ``qs_string_ci_diagonal``."""
+    lib = _lib.load()
+    dt = result_dtype(ht, ut)
+    ht, ut = _dev(ht, dt), _dev(ut, dt)
+    sa, sb = _strings_checked(strings_a, "strings_a"), _strings_checked(strings_b, "strings_b")
+    m = ht.shape[-1]
+    if tuple(ht.shape) != (m, m) or tuple(ut.shape) != (m, m, m, m):
+        raise ValueError(f"need ht (m, m) and ut (m, m, m, m), got {tuple(ht.shape)}, {tuple(ut.shape)}")
+    na, nb = sa.numel(), sb.numel()
+    if out is None:
+        out = torch.empty((na, nb), dtype=_F64, device=sa.device)
+    else:
+        _check_out(out, (na, nb), _F64, "string_ci_diagonal")
+    with _on_device_of(ht, ut, sa, sb, out):
+        _ran(
+            lib.qs_string_ci_diagonal(dtype_code(dt), ht.data_ptr(), ut.data_ptr(), sa.data_ptr(), na, int(Na),
+                                      sb.data_ptr(), nb, int(Nb), m, out.data_ptr(), _stream()),
+            "qs_string_ci_diagonal",
+        )
+    return out
+
+
+@_plain
+def string_ci_sigma(k, W, ta, tb, c, out=None):
+    """``sigma[j] = H c[j]`` for ``c`` (K, na, nb) or (na, nb) on ``qs_string_ci_sigma``: ``k`` (m, m) and ``W``
+    (m^2, m^2) as in ``include/qs_amd.h``, ``ta`` (na, m^2) and ``tb`` (nb, m^2) from ``string_ci_table``.  Per group of
+    vectors one expand, ONE product ``W . D`` on the product dispatcher and one fold; the groups are as large as
+    ``STRING_CI_BYTES`` of workspace allow.  A real ``k`` and ``W`` with a complex ``c`` stay real (fp64 product on the
+    re / im pairs).  Repeating a call gives the same bits; another grouping agrees to rounding.  One ``dispatch_log``
+    entry names the kernels of the whole call."""
+    lib = _lib.load()
+    if not isinstance(c, torch.Tensor) or c.dim() not in (2, 3):
+        raise ValueError("c must be (K, na, nb) or (na, nb)")
+    hdt = result_dtype(k, W)
+    dt = result_dtype(k, W, c)
+    k, W, c = _dev(k, hdt), _dev(W, hdt), _dev(c, dt)
+    m = k.shape[-1]
+    if tuple(k.shape) != (m, m) or tuple(W.shape) != (m * m, m * m):
+        raise ValueError(f"need k (m, m) and W (m^2, m^2), got {tuple(k.shape)}, {tuple(W.shape)}")
+    ta, tb = _string_tables(ta, tb, m)
+    single = c.dim() == 2
+    c3 = c[None] if single else c
+    K, na, nb = c3.shape
+    if (na, nb) != (ta.shape[0], tb.shape[0]) or K < 1:
+        raise ValueError(f"c has shape {tuple(c.shape)}: need (K, {ta.shape[0]}, {tb.shape[0]}) with K >= 1")
+    hcode, ccode = dtype_code(hdt), dtype_code(dt)
+    group = check(lib.qs_string_ci_group(hcode, ccode, m, na, nb, K, STRING_CI_BYTES), "group query")
+    if out is None:
+        out = torch.empty(tuple(c.shape), dtype=dt, device=c.device)
+    else:
+        _check_out(out, tuple(c.shape), dt, "string_ci_sigma")
+    o3 = out[None] if single else out
+    ran = []
+    with _on_device_of(k, W, ta, tb, c, out):
+        for k0 in range(0, K, group):
+            kg = min(group, K - k0)
+            nbytes = check(lib.qs_string_ci_workspace(hcode, ccode, m, na, nb, kg), "workspace query")
+            check(
+                lib.qs_string_ci_sigma(hcode, ccode, k.data_ptr(), W.data_ptr(), ta.data_ptr(), tb.data_ptr(), m, na, nb,
+                                       c3[k0:k0 + kg].data_ptr(), kg, o3[k0:k0 + kg].data_ptr(),
+                                       *_work(nbytes, c.device), _stream()),
+                "qs_string_ci_sigma",
+            )
+            if dispatch_log is not None:
+                ran.append(lib.qs_last_dispatch().decode())
+    if dispatch_log is not None:
+        dispatch_log.append(" | ".join(ran))
+    return out
+
+
+@_plain
+def string_ci_density1(ta, tb, m, bra, ket, out=None):
+    """Spin-summed ``rho[q, p] = <bra| E_pq |ket>`` (m, m) of two vectors (na, nb) on ``qs_string_ci_density1``: one
+    expand of ``ket`` and one fixed-order sum per element; ``bra is ket`` is the density of a state, in the index order
+    ``compute_particle_density(rho_qp)`` takes."""
+    lib = _lib.load()
+    m = int(m)
+    ta, tb = _string_tables(ta, tb, m)
+    dt = result_dtype(bra, ket)
+    same = bra is ket
+    bra = _dev(bra, dt)
+    ket = bra if same else _dev(ket, dt)
+    na, nb = ta.shape[0], tb.shape[0]
+    if tuple(bra.shape) != (na, nb) or tuple(ket.shape) != (na, nb):
+        raise ValueError(f"bra and ket have shapes {tuple(bra.shape)}, {tuple(ket.shape)}: need ({na}, {nb}) each")
+    code = dtype_code(dt)
+    nbytes = check(lib.qs_string_ci_workspace(code, code, m, na, nb, 1), "workspace query")
+    if out is None:
+        out = torch.empty((m, m), dtype=dt, device=bra.device)
+    else:
+        _check_out(out, (m, m), dt, "string_ci_density1")
+    with _on_device_of(ta, tb, bra, ket, out):
+        _ran(
+            lib.qs_string_ci_density1(code, ta.data_ptr(), tb.data_ptr(), m, na, nb, bra.data_ptr(), ket.data_ptr(),
+                                      out.data_ptr(), *_work(nbytes, bra.device), _stream()),
+            "qs_string_ci_density1",
+        )
+    return out
+
+
 @_plain
 def transform_two_body_blocks(u, Ct0, Ct1, C2, C3, out=None):
     """``out[pqrs] = Ct0[pa] Ct1[qb] u[abcd] C2[cr] C3[ds]``: one coefficient matrix per index

@@ -1,0 +1,254 @@
+"""Exact states of a ``SpatialOrbitalSystem``: spin-free configuration interaction on alpha and beta occupation strings
+(Knowles-Handy) with the two-body part of ``H c`` as ONE dense product (``kernels.string_ci_sigma``,
+``csrc/qs_string_ci.hip``).
+
+In orbitals ``psi = chi C`` with ``C^H s C = 1`` and ``E_pq = sum_spin a+_p,spin a_q,spin``
+
+    H = sum_pr k[p,r] E_pr + sum_(pr),(qs) W[(pr),(qs)] E_pr E_qs,
+    k[p,r] = ht[p,r] - 1/2 sum_q ut[p,q,q,r],     W[(pr),(qs)] = 1/2 ut[p,q,r,s],
+    ht = C^H h C,     ut = <pq|rs> in the orbitals C (NOT anti-symmetrised, never spin-doubled)
+
+and a state is ``c[Ia, Ib]`` over a list of alpha and a list of beta strings: ascending 64-bit masks over the m <= 63
+SPATIAL orbitals with ``n_up`` and ``n_down`` bits.  The determinant is all alpha creators first, ascending within each
+spin.  The lists are data (default: all of them); a replacement whose target string is missing contributes nothing.
+
+    ci = StringCI(system, C)                          # a SpatialOrbitalSystem, e.g. RHF orbitals: hf.string_ci()
+    E, c = ci.solve(n_roots=3)                        # c: (n_roots, na, nb)
+    rho = ci.one_body_density(0)                      # spin-summed, for system.compute_particle_density(rho, C=C)
+    masks, v = ci.to_determinants(c[0])               # the same state in DeterminantCI's convention
+
+Out of scope here: two-body densities, <S^2>, a sharded ``u``, and chunking the expanded vectors over rows of ``W``.
+"""
+
+import numpy
+import torch
+
+from . import kernels
+from .basis_set import _deliver
+from .determinant_ci import M_MAX, _dagger, _plain, block_davidson, full_space, popcounts
+from .general_orbital_system import GeneralOrbitalSystem
+from .sharded_module import is_sharded
+from .spatial_orbital_system import SpatialOrbitalSystem
+
+
+def full_strings(m, N):
+    """All C(m, N) occupation strings of N particles of one spin in m spatial orbitals, ascending int64 masks; ``N = 0``
+    is the single empty string ``[0]``."""
+    m, N = int(m), int(N)
+    if not 1 <= m <= M_MAX:
+        raise ValueError(f"strings are 64-bit masks: 1 <= m <= {M_MAX} orbitals, got m = {m}")
+    if not 0 <= N <= m:
+        raise ValueError(f"need 0 <= N <= m particles of one spin, got N = {N}, m = {m}")
+    return numpy.zeros(1, dtype=numpy.int64) if N == 0 else full_space(m, N)
+
+
+def checked_strings(strings, m, N):
+    """``strings`` as an ascending, duplicate-free int64 array of masks with ``N`` bits below ``m`` (``None``: all)."""
+    if strings is None:
+        return full_strings(m, N)
+    full_strings(m, 0)                                              # the extents of m
+    if isinstance(strings, torch.Tensor):
+        strings = strings.detach().cpu().numpy()
+    strings = numpy.asarray(strings)
+    if strings.ndim != 1 or strings.size < 1 or strings.dtype.kind not in "iu":
+        raise ValueError("a string list must be a non-empty 1-D integer array of occupation masks")
+    if strings.dtype.kind == "u" and (strings >> numpy.uint64(63)).any():
+        raise ValueError("a mask has bits at or above m")
+    strings = numpy.ascontiguousarray(strings, dtype=numpy.int64)
+    if (strings < 0).any() or (strings >> numpy.int64(m)).any():
+        raise ValueError(f"a mask has bits at or above m = {m}")
+    if (numpy.diff(strings) <= 0).any():
+        raise ValueError("a string list must be ascending and free of duplicates")
+    if (popcounts(strings) != int(N)).any():
+        raise ValueError(f"every mask must have exactly N = {N} bits set")
+    return strings
+
+
+def _spread(strings):
+    """Bit p of every mask moved to bit 2 p."""
+    out = numpy.zeros_like(strings)
+    for p in range(32):
+        out |= ((strings >> numpy.int64(p)) & numpy.int64(1)) << numpy.int64(2 * p)
+    return out
+
+
+def determinant_order(strings_up, strings_down):
+    """``(masks, perm, phase)`` that take a vector over ``(Ia, Ib)`` to ``DeterminantCI``'s convention -- spin orbital
+    ``2 p + sigma`` with alpha = 0, ascending interleaved masks --: ``v = (phase * c.reshape(-1))[perm]`` belongs to
+    ``masks``.  ``phase[Ia, Ib] = (-1)^(sum_{q in Ib} #{p in Ia : p > q})`` takes "all alpha creators first" to ascending
+    spin orbitals."""
+    sa = numpy.ascontiguousarray(strings_up, dtype=numpy.int64)
+    sb = numpy.ascontiguousarray(strings_down, dtype=numpy.int64)
+    if (sa >> numpy.int64(31)).any() or (sb >> numpy.int64(31)).any():
+        raise ValueError("interleaved determinants are 64-bit masks over 2 m <= 62 spin orbitals: m <= 31")
+    masks = (_spread(sa)[:, None] | (_spread(sb)[None, :] << numpy.int64(1))).reshape(-1)
+    swaps = numpy.zeros((len(sa), len(sb)), dtype=numpy.int64)
+    for q in range(31):
+        above = popcounts(sa >> numpy.int64(q + 1))                  # alpha particles in orbitals p > q
+        swaps += above[:, None] * ((sb >> numpy.int64(q)) & numpy.int64(1))[None, :]
+    phase = numpy.where(swaps & 1, -1.0, 1.0).reshape(-1)
+    perm = numpy.argsort(masks, kind="stable")
+    return masks[perm], perm, phase
+
+
+class StringCI:
+    """The lowest exact states of ``n_up`` alpha and ``n_down`` beta particles (default: ``system.n`` each) of a
+    ``SpatialOrbitalSystem`` on the string lists ``strings_up`` x ``strings_down`` (default: all strings) in the
+    orbitals ``C`` (l, m) with ``C^H s C = 1`` -- or, with ``C=None``, in the system's own basis, which must then be
+    orthonormal.  ``ht``, ``ut``, ``k``, ``W``, the replacement tables and the diagonal are built once, here."""
+
+    def __init__(self, system, C=None, n_up=None, n_down=None, strings_up=None, strings_down=None):
+        if isinstance(system, GeneralOrbitalSystem):
+            raise TypeError("StringCI works on spatial orbitals: a GeneralOrbitalSystem goes to DeterminantCI")
+        if not isinstance(system, SpatialOrbitalSystem):
+            raise TypeError("StringCI needs a SpatialOrbitalSystem")
+        if is_sharded(system.u):
+            raise NotImplementedError("StringCI does not take a sharded u: the string kernels are not sharded")
+        self.system = system
+        self.n_up = int(system.n if n_up is None else n_up)
+        self.n_down = int(system.n if n_down is None else n_down)
+        with torch._C.DisableTorchFunctionSubclass():
+            u = _plain(system.u)
+            h, s = _plain(system.h), _plain(system.s)
+            l = h.shape[0]
+            if C is None:
+                eye = torch.eye(l, dtype=s.dtype, device=s.device)
+                if float((s - eye).abs().max().item()) > 1e-12:
+                    raise ValueError("the basis is not orthonormal (s != 1): give orbitals C with C^H s C = 1")
+                C = torch.eye(l, dtype=h.dtype, device=h.device)
+            else:
+                C = _plain(C)
+                if C.dim() != 2 or C.shape[0] != l:
+                    raise ValueError(f"C must be (l, m) with l = {l}, got {tuple(C.shape)}")
+            self.m = m = int(C.shape[1])
+            self._sa_host = checked_strings(strings_up, m, self.n_up)
+            same = strings_down is strings_up and self.n_down == self.n_up
+            self._sb_host = self._sa_host if same else checked_strings(strings_down, m, self.n_down)
+            same = same or numpy.array_equal(self._sa_host, self._sb_host)
+            self.na, self.nb = int(self._sa_host.shape[0]), int(self._sb_host.shape[0])
+            self.dim = self.na * self.nb
+            self._dt = torch.complex128 if (C.is_complex() or u.is_complex() or h.is_complex()) else torch.float64
+            self._C = C.to(self._dt).contiguous()
+            ht = _dagger(self._C) @ h.to(self._dt) @ self._C
+            self._ht = (0.5 * (ht + _dagger(ht))).contiguous()
+            self._ut = kernels.transform_two_body(u, self._C).to(self._dt).contiguous()     # a new tensor: system.u is left alone
+            self._k = (self._ht - 0.5 * torch.einsum("pqqr->pr", self._ut)).contiguous()
+            self._W = (0.5 * self._ut.permute(0, 2, 1, 3)).reshape(m * m, m * m).contiguous()  # the one permuted, scaled copy
+            dev = self._ut.device
+            self._sa = torch.from_numpy(self._sa_host).to(dev)
+            self._sb = self._sa if same else torch.from_numpy(self._sb_host).to(dev)
+            self._ta = kernels.string_ci_table(self._sa, m, self.n_up)
+            self._tb = self._ta if same else kernels.string_ci_table(self._sb, m, self.n_down)
+            self._diag = kernels.string_ci_diagonal(self._ht, self._ut, self._sa, self.n_up, self._sb, self.n_down).reshape(-1)
+        self.E = self.c = self._c = None
+        self.converged, self.iterations, self.residuals = False, 0, None
+        self.sigma_history = []              # trial vectors per Davidson iteration
+
+    @property
+    def strings_up(self):
+        """The alpha string list, ascending int64 masks (host array)."""
+        return self._sa_host
+
+    @property
+    def strings_down(self):
+        """The beta string list, ascending int64 masks (host array)."""
+        return self._sb_host
+
+    def sigma(self, c):
+        """``H c_k`` (without the nuclear repulsion) for ``c`` (k, na, nb) or (na, nb), device tensor in and out; a
+        complex ``c`` on a real Hamiltonian keeps ``W`` real."""
+        with torch._C.DisableTorchFunctionSubclass():
+            c = _plain(c)
+            if self._dt == torch.complex128:
+                c = c.to(self._dt)
+            return kernels.string_ci_sigma(self._k, self._W, self._ta, self._tb, c)
+
+    def _sigma_rows(self, V):
+        return self.sigma(V.reshape(V.shape[0], self.na, self.nb)).reshape(V.shape[0], self.dim)
+
+    def solve(self, n_roots, tol=1e-9, max_iter=100, max_space=None):
+        """The ``n_roots`` lowest energies and their vectors by ``determinant_ci.block_davidson``: unit guesses on the
+        ``min(dim, 2 n_roots)`` lowest diagonal elements.  Returns ``(E, c)`` in the system's array module, ``E``
+        ascending and including the nuclear repulsion, ``c`` (n_roots, na, nb) of unit norm; sets ``converged``,
+        ``iterations``, ``residuals`` and ``sigma_history``."""
+        if not 1 <= n_roots <= self.dim:
+            raise ValueError(f"n_roots = {n_roots} does not fit the {self.dim} determinants of the space")
+        n_guess = min(self.dim, 2 * n_roots)
+        with torch._C.DisableTorchFunctionSubclass():
+            dev = self._diag.device
+            order = torch.argsort(self._diag, stable=True)[:n_guess]
+            V = torch.zeros(n_guess, self.dim, dtype=self._dt, device=dev)
+            V[torch.arange(n_guess, device=dev), order] = 1.0
+            theta, X, info = block_davidson(self._sigma_rows, self._diag, V, n_roots, tol, max_iter, max_space)
+            self.converged, self.iterations = info["converged"], info["iterations"]
+            self.residuals, self.sigma_history = info["residuals"], info["sigma_history"]
+            self._c = X.reshape(n_roots, self.na, self.nb).contiguous()
+            E = theta + float(self.system.nuclear_repulsion_energy)
+            self.E = _deliver(E.contiguous(), self.system.np)
+            self.c = _deliver(self._c, self.system.np)
+        return self.E, self.c
+
+    def _rho(self, k, l=None):
+        if self._c is None:
+            raise RuntimeError("call solve() first")
+        bra = self._c[k]
+        ket = bra if l is None or l == k else self._c[l]
+        return kernels.string_ci_density1(self._ta, self._tb, self.m, bra, ket)
+
+    def one_body_density(self, k=0):
+        """Spin-summed ``rho[q, p] = <c_k| E_pq |c_k>`` of solved state ``k`` in the orbitals ``C``: what
+        ``system.compute_particle_density(rho, C=C)`` takes."""
+        with torch._C.DisableTorchFunctionSubclass():
+            rho = self._rho(k)
+        return _deliver(rho, self.system.np)
+
+    def transition_density(self, k, l):
+        """Spin-summed ``rho[q, p] = <c_k| E_pq |c_l>`` between two solved states."""
+        with torch._C.DisableTorchFunctionSubclass():
+            rho = self._rho(k, l)
+        return _deliver(rho, self.system.np)
+
+    def _in_orbitals(self, A):
+        """``C^H A C`` of a matrix (l, l) or a stack (d, l, l) given in the system's basis."""
+        A = _plain(A)
+        if A.dim() not in (2, 3) or tuple(A.shape[-2:]) != (self._C.shape[0],) * 2:
+            raise ValueError(f"need an (l, l) matrix or a (d, l, l) stack with l = {self._C.shape[0]}, got {tuple(A.shape)}")
+        dt = torch.complex128 if (A.is_complex() or self._dt == torch.complex128) else torch.float64
+        C = self._C.to(dt)
+        return _dagger(C) @ A.to(dt) @ C
+
+    def expectation_one_body(self, A, k=0, l=None):
+        """``<c_k| A |c_l>`` (``l`` defaults to ``k``) of a spin-free one-body operator given in the system's basis as a
+        matrix (l, l) or a stack (d, l, l): ``sum_pq (C^H A C)[p,q] rho[q,p]``, one value or d of them."""
+        with torch._C.DisableTorchFunctionSubclass():
+            At = self._in_orbitals(A)
+            rho = self._rho(k, l)
+            value = (At * rho.transpose(0, 1).to(At.dtype)).sum(dim=(-2, -1))
+        return _deliver(value, self.system.np)
+
+    def transition_dipole(self, k, l):
+        """``<c_k| dipole_moment |c_l>``, one value per spatial dimension."""
+        return self.expectation_one_body(self.system.dipole_moment, k, l)
+
+    def natural_orbitals(self, k=0):
+        """``(n, C_nat)`` of solved state ``k``: the occupations ``n`` (descending eigenvalues of the Hermitian part of
+        the spin-summed ``rho[q, p]``, between 0 and 2) and ``C_nat = C U`` with its eigenvectors as columns."""
+        with torch._C.DisableTorchFunctionSubclass():
+            rho = self._rho(k)
+            n, U = torch.linalg.eigh(0.5 * (rho + _dagger(rho)))
+            n, U = n.flip(0).contiguous(), U.flip(1)
+            C_nat = (self._C @ U.to(self._dt)).contiguous()
+        return _deliver(n, self.system.np), _deliver(C_nat, self.system.np)
+
+    def to_determinants(self, c):
+        """``(masks, v)``: the vector(s) ``c`` (na, nb) or (k, na, nb) in ``DeterminantCI``'s convention -- spin orbital
+        ``2 p + sigma`` with alpha = 0, ``masks`` the ascending interleaved determinants (host int64 array), ``v`` (dim,)
+        or (k, dim) on the device and in the dtype of ``c``, every entry multiplied by
+        ``(-1)^(sum_{q in Ib} #{p in Ia : p > q})``.  Needs m <= 31."""
+        masks, perm, phase = determinant_order(self._sa_host, self._sb_host)
+        with torch._C.DisableTorchFunctionSubclass():
+            c = _plain(c)
+            flat = c.reshape(*c.shape[:-2], self.dim)
+            ph = torch.from_numpy(phase).to(flat.device).to(flat.dtype)
+            v = (flat * ph)[..., torch.from_numpy(perm).to(flat.device)].contiguous()
+        return masks, v
