@@ -774,6 +774,35 @@ int qs_det_ci_density2(int c_dtype, const int64_t* dets, const void* bra, const 
  *       = sum_K conj(bra[K]) (E_pq ket)[K], spin-summed, one expand of ket and one
  *       fixed-order sum per (p, q); bra == ket (the same pointer is allowed) is a
  *       state's density.
+ *   qs_string_ci_density2 : the spin-summed two-body density
+ *         gamma[((p*m + q)*m + r)*m + s] = sum_spins <bra| a+_p a+_q a_s a_r |ket>
+ *                                        = X[(pr),(qs)] - delta_qr <bra| E_ps |ket>,
+ *         X[(pr),(qs)] = <bra| E_pr E_qs |ket>
+ *                      = sum_K conj((E_rp bra)[K]) (E_qs ket)[K],
+ *       and rho[q * m + p] = <bra| E_pq |ket> from the same pass; fp64 and
+ *       complex128, bra == ket (the same pointer is allowed) is a state.  X is a
+ *       Gram product of two expanded panels over the determinants, in passes over
+ *       alpha rows so that both panels fit a byte budget: the tuning key
+ *       "string_ci_bytes" when it is positive, else budget_bytes, else 2 GiB; at
+ *       least one alpha row per pass.  A pass is ONE batched product over T slices
+ *       of kc determinants (split-k) that adds into T partial results; a closing
+ *       kernel sums them in ascending t.  No atomics: a repeated call gives the
+ *       same bits; another budget agrees to rounding.  With the plain ut
+ *       <bra|H|ket> = sum ht[p,q] rho[q,p] + 1/2 sum ut[p,q,r,s] gamma[p,q,r,s].
+ *   qs_string_ci_density2_plan : plan[0 ... 4] = alpha rows per pass, passes,
+ *       slices T, slice length kc, workspace bytes; T kc >= rows nb > (T - 1) kc.
+ *   qs_string_ci_density2_workspace : bytes of `work` under that budget,
+ *         T (m^2 + 1) m^2 e + (2 m^2 + 1) T kc e,   e = sizeof(element of c):
+ *       the partial results, the bra panel (m^2 + 1 rows: conj(bra) is the last)
+ *       and the ket panel.  The budget bounds the panels (or is the panels of one
+ *       alpha row when it is smaller); the partial results come on top and stay
+ *       below an eighth of the panels wherever T > 1.
+ *   qs_string_ci_spin_squared : out[k] = S^2 c[k] for c (K, na, nb),
+ *         S^2 = S_z (S_z + 1) + N_beta - sum_pq E^alpha_qp E^beta_pq,
+ *         S_z = (Na - Nb) / 2,
+ *       one gather through both tables per (p, q) in a fixed order; no workspace.
+ *       On a truncated list a missing target contributes nothing: like H, S^2 is
+ *       then the operator of the truncated formulation.
  * dtype pairs (ht, ut, k, W; c): (F64, F64), (C128, C128) and (F64, C128), which
  * runs the product in fp64 on the re / im pairs of D as 2 K na nb columns (no
  * complex copy of W); (C128, F64) is QS_ERR_BAD_DTYPE.
@@ -795,6 +824,13 @@ int qs_string_ci_sigma(int h_dtype, int c_dtype, const void* k, const void* W, c
                        void* work, int64_t work_bytes, void* stream);
 int qs_string_ci_density1(int c_dtype, const int32_t* ta, const int32_t* tb, int64_t m, int64_t na, int64_t nb,
                           const void* bra, const void* ket, void* rho, void* work, int64_t work_bytes, void* stream);
+int64_t qs_string_ci_density2_workspace(int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes);
+int qs_string_ci_density2_plan(int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes, int64_t* plan);
+int qs_string_ci_density2(int c_dtype, const int32_t* ta, const int32_t* tb, int64_t m, int64_t na, int64_t nb,
+                          const void* bra, const void* ket, void* gamma, void* rho, void* work, int64_t work_bytes,
+                          int64_t budget_bytes, void* stream);
+int qs_string_ci_spin_squared(int c_dtype, const int32_t* ta, const int32_t* tb, int64_t m, int64_t na, int64_t nb,
+                              int64_t Na, int64_t Nb, const void* c, int64_t K, void* out, void* stream);
 int qs_probe_mfma_f64(void* sink, int64_t blocks, int64_t iters, void* stream);
 int qs_probe_stream_copy(const void* src, void* dst, int64_t bytes, void* stream);
 

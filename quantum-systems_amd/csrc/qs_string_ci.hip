@@ -37,7 +37,8 @@ constexpr int kScChunk = 16;          // table columns staged per step
 constexpr int kScBlock = 256;         // most beta strings (threads) of a workgroup; 64 or 128 for shorter lists
 constexpr int kScRhoBlock = 256;      // threads of the density's and of the diagonal's workgroup
 // Shipped byte budget of the D and G of one qs_string_ci_sigma call: qs_string_ci_group() splits a batch by it when
-// the caller passes 0 (kernels.STRING_CI_BYTES passes its own).  Not measured yet.
+// the caller passes 0 (kernels.STRING_CI_BYTES passes its own).  Not measured yet.  Also the budget of
+// the two panels of one pass of qs_string_ci_density2.
 constexpr int64_t kScBytes = int64_t(2) << 30;
 
 struct ScArgs {
@@ -308,6 +309,282 @@ static unsigned sc_stride_grid(int64_t total) {
     return (unsigned)(want < 65536 ? want : 65536);
 }
 
+// ---- two-body density and S^2 ------------------------------------------------------------------------------------------
+//   X[(pr),(qs)]  = <bra| E_pr E_qs |ket> = sum_K conj((E_rp bra)[K]) (E_qs ket)[K]          (E_pr^+ = E_rp, E real)
+//   Gamma[p,q,r,s] = sum_spins <bra| a+_p a+_q a_s a_r |ket> = X[(pr),(qs)] - delta_qr <bra| E_ps |ket>
+// X is a Gram product of two expanded panels over the determinants, cut into passes over alpha rows so that both panels
+// fit a byte budget.  Per pass: the bra panel A[(pq), K] (K fastest) = conj(E_pq bra), stored at (pq) as it stands, with
+// conj(bra) itself as row m^2; the ket panel B[K, (qs)] ((qs) fastest) = E_qs ket; ONE batched product over T slices of
+// kc determinants that adds into T partial results (m^2 + 1, m^2).  The close sums the partials in ascending t, reads X
+// at the transposed row (rp), and takes the delta term and rho from the last row <bra| E_qs |ket>.  No atomics.
+//   S^2 = S_z (S_z + 1) + N_beta - sum_pq E^alpha_qp E^beta_pq,      S_z = (N_alpha - N_beta) / 2
+// is one gather through both tables per (p, q).  On a truncated list a missing target contributes nothing: like H, S^2 is
+// then the operator of the truncated formulation, not the projection of the full one.
+
+constexpr int64_t kSc2Cus = 256;      // compute units the slices of one pass are meant to cover
+constexpr int kScSpinG = 4;           // vectors that share the table reads of one S^2 workgroup
+
+struct Sc2Args {
+    const int32_t* tb;        // (nb, m^2)
+    const double* c;          // (na, nb): bra or ket
+    int64_t na, nb;
+    int64_t ia0;              // first alpha row of the pass
+    int64_t pitch;            // elements between rows of the bra panel, T kc
+    unsigned ntile;
+    int m2;
+};
+
+// (E_pq c)[Ia, Ib] from the two table entries of (Ia, pq) and (Ib, pq)
+template <int CW>
+__device__ __forceinline__ void sc_replaced(double (&v)[CW], const double* __restrict__ c, int32_t ea, int32_t eb, int64_t ia,
+                                            int64_t ib, int64_t na, int64_t nb) {
+    const int64_t ja = ea ? sc_target(ea, na) : -1, jb = eb ? sc_target(eb, nb) : -1;
+#pragma unroll
+    for (int w = 0; w < CW; ++w) v[w] = 0.0;
+    if (ja >= 0) {
+        const double* x = c + (ja * nb + ib) * CW;
+#pragma unroll
+        for (int w = 0; w < CW; ++w) v[w] = ea < 0 ? -x[w] : x[w];
+    }
+    if (jb >= 0) {
+        const double* x = c + (ia * nb + jb) * CW;
+#pragma unroll
+        for (int w = 0; w < CW; ++w) v[w] += eb < 0 ? -x[w] : x[w];
+    }
+}
+
+// The expand of one pass, alpha rows ia0 ... ia0 + gridDim.x / ntile - 1, in the layout of one operand of the Gram product.
+// KET: P[K, (pq)] -- a thread keeps the 16 values of a table chunk and writes them as one line of its determinant with
+// 16-byte stores (8-byte ones where an odd m^2 leaves the line on an 8-byte boundary).  Otherwise P[(pq), K], conjugated,
+// and conj(c) as row m^2.  K = (Ia - ia0) nb + Ib counts the determinants of the pass.
+template <int CW, bool KET>
+__global__ __launch_bounds__(kScBlock) void string_ci_expand_rows_kernel(const Sc2Args a, const int32_t* __restrict__ ta,
+                                                                        double* __restrict__ P) {
+    extern __shared__ __attribute__((aligned(16))) int32_t sc_tb[];
+    const int B = blockDim.x, t = threadIdx.x, m2 = a.m2;
+    const int64_t il = blockIdx.x / a.ntile;                              // uniform
+    const int64_t ia = a.ia0 + il;
+    const int64_t ib0 = (int64_t)(blockIdx.x % a.ntile) * B;
+    const int64_t ib = ib0 + t, nb = a.nb;
+    const bool live = ib < nb;
+    const int64_t kl = il * nb + ib;
+    const int32_t* __restrict__ ta_row = ta + ia * m2;
+    const double* __restrict__ c = a.c;
+    const bool wide = CW == 2 || !(m2 & 1);                               // every line starts on a 16-byte boundary
+    for (int pq0 = 0; pq0 < m2; pq0 += kScChunk) {
+        __syncthreads();
+        sc_stage(sc_tb, a.tb, ib0, nb, pq0, m2);
+        __syncthreads();
+        if (!live) continue;
+        double v[kScChunk][CW];
+#pragma unroll
+        for (int j = 0; j < kScChunk; ++j) {
+            const int pq = pq0 + j;
+            if (pq < m2) {                                                // uniform
+                const int32_t ea = ta_row[pq];                            // uniform address: a scalar load
+                sc_replaced<CW>(v[j], c, ea, sc_tb[j * (B + 1) + t], ia, ib, a.na, nb);
+            } else {
+#pragma unroll
+                for (int w = 0; w < CW; ++w) v[j][w] = 0.0;
+            }
+        }
+        if constexpr (KET) {
+            double* line = P + (kl * m2 + pq0) * CW;
+            if (wide) {
+                // an even m^2 ends on an even column: the pairs of an fp64 line are whole
+#pragma unroll
+                for (int j = 0; j < kScChunk; j += 2 / CW) {
+                    if (pq0 + j < m2) {
+                        double2 x;
+                        if constexpr (CW == 2) { x.x = v[j][0]; x.y = v[j][CW - 1]; }
+                        else { x.x = v[j][0]; x.y = v[j + 2 / CW - 1][0]; }
+                        *reinterpret_cast<double2*>(line + j * CW) = x;
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < kScChunk; ++j)
+                    if (pq0 + j < m2) line[j] = v[j][0];
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < kScChunk; ++j) {
+                if (pq0 + j < m2) {
+                    double* d = P + ((int64_t)(pq0 + j) * a.pitch + kl) * CW;
+                    d[0] = v[j][0];
+                    if constexpr (CW == 2) d[CW - 1] = -v[j][CW - 1];
+                }
+            }
+        }
+    }
+    if constexpr (!KET) {
+        if (live) {
+            const double* x = c + (ia * nb + ib) * CW;
+            double* d = P + ((int64_t)m2 * a.pitch + kl) * CW;
+            d[0] = x[0];
+            if constexpr (CW == 2) d[CW - 1] = -x[CW - 1];
+        }
+    }
+}
+
+// Gamma[p,q,r,s] and rho[q m + p] from the T partial results part[t] (m^2 + 1, m^2): one thread per element of Gamma
+// (grid-stride), the partials summed in ascending t, the delta term one subtraction.
+template <int CW>
+__global__ __launch_bounds__(kScRhoBlock) void string_ci_gamma_close_kernel(const double* __restrict__ part, int64_t T, int m,
+                                                                            double* __restrict__ gamma, double* __restrict__ rho) {
+    const int64_t m2 = (int64_t)m * m, total = m2 * m2, sc = (m2 + 1) * m2, step = (int64_t)gridDim.x * kScRhoBlock;
+    for (int64_t idx = (int64_t)blockIdx.x * kScRhoBlock + threadIdx.x; idx < total; idx += step) {
+        const int s = (int)(idx % m), r = (int)((idx / m) % m), q = (int)((idx / m2) % m), p = (int)(idx / (m2 * m));
+        const int64_t ex = ((int64_t)r * m + p) * m2 + q * m + s;          // X[(pr),(qs)] lies at row (rp)
+        double x[CW];
+#pragma unroll
+        for (int w = 0; w < CW; ++w) x[w] = 0.0;
+        for (int64_t t = 0; t < T; ++t) {
+#pragma unroll
+            for (int w = 0; w < CW; ++w) x[w] += part[(t * sc + ex) * CW + w];
+        }
+        if (q == r) {
+            const int64_t ee = total + p * m + s;                          // <bra| E_ps |ket>
+            double e[CW];
+#pragma unroll
+            for (int w = 0; w < CW; ++w) e[w] = 0.0;
+            for (int64_t t = 0; t < T; ++t) {
+#pragma unroll
+                for (int w = 0; w < CW; ++w) e[w] += part[(t * sc + ee) * CW + w];
+            }
+#pragma unroll
+            for (int w = 0; w < CW; ++w) x[w] = x[w] - e[w];
+        }
+#pragma unroll
+        for (int w = 0; w < CW; ++w) gamma[idx * CW + w] = x[w];
+        if (r == 0 && s == 0) {
+            const int64_t ee = total + p * m + q;                          // <bra| E_pq |ket>
+            double e[CW];
+#pragma unroll
+            for (int w = 0; w < CW; ++w) e[w] = 0.0;
+            for (int64_t t = 0; t < T; ++t) {
+#pragma unroll
+                for (int w = 0; w < CW; ++w) e[w] += part[(t * sc + ee) * CW + w];
+            }
+#pragma unroll
+            for (int w = 0; w < CW; ++w) rho[((int64_t)q * m + p) * CW + w] = e[w];
+        }
+    }
+}
+
+// out_k = S^2 c_k for the vectors k0 ... k0 + kScSpinG - 1 of a workgroup: pq ascending over the staged beta columns, the
+// alpha entry at the transposed column q m + p, every term an explicit fma, the diagonal term last.
+template <int CW>
+__global__ __launch_bounds__(kScBlock) void string_ci_spin_kernel(const ScArgs a, const int32_t* __restrict__ ta,
+                                                                 double* __restrict__ out, double s0, int m) {
+    extern __shared__ __attribute__((aligned(16))) int32_t sc_tb[];
+    const int B = blockDim.x, t = threadIdx.x, m2 = a.m2;
+    const unsigned row = blockIdx.x / a.ntile;                            // (vector group, ia), uniform
+    const int64_t k0 = (int64_t)(row / (unsigned)a.na) * kScSpinG, ia = row % (unsigned)a.na;
+    const int64_t ib0 = (int64_t)(blockIdx.x % a.ntile) * B;
+    const int64_t ib = ib0 + t, nb = a.nb, dim = a.na * a.nb;
+    const bool live = ib < nb;
+    const int32_t* __restrict__ ta_row = ta + ia * m2;
+    const double* __restrict__ c = a.c;
+    const int nk = a.K - k0 < kScSpinG ? (int)(a.K - k0) : kScSpinG;
+    double acc[kScSpinG][CW];
+#pragma unroll
+    for (int g = 0; g < kScSpinG; ++g)
+#pragma unroll
+        for (int w = 0; w < CW; ++w) acc[g][w] = 0.0;
+    for (int pq0 = 0; pq0 < m2; pq0 += kScChunk) {
+        __syncthreads();
+        sc_stage(sc_tb, a.tb, ib0, nb, pq0, m2);
+        __syncthreads();
+        if (!live) continue;
+        const int nj = m2 - pq0 < kScChunk ? m2 - pq0 : kScChunk;
+        for (int j = 0; j < nj; ++j) {
+            const int pq = pq0 + j, p = pq / m, q = pq % m;
+            const int32_t ea = ta_row[q * m + p];                         // uniform address: a scalar load
+            const int32_t eb = sc_tb[j * (B + 1) + t];
+            if (!ea || !eb) continue;
+            const int64_t ja = sc_target(ea, a.na), jb = sc_target(eb, nb);
+            if (ja < 0 || jb < 0) continue;
+            const double sg = ((ea < 0) != (eb < 0)) ? 1.0 : -1.0;        // -sgn_a sgn_b
+#pragma unroll
+            for (int g = 0; g < kScSpinG; ++g) {
+                if (g < nk) {
+                    const double* x = c + ((k0 + g) * dim + ja * nb + jb) * CW;
+#pragma unroll
+                    for (int w = 0; w < CW; ++w) acc[g][w] = fma(sg, x[w], acc[g][w]);
+                }
+            }
+        }
+    }
+    if (live) {
+#pragma unroll
+        for (int g = 0; g < kScSpinG; ++g) {
+            if (g < nk) {
+                const int64_t at = ((k0 + g) * dim + ia * nb + ib) * CW;
+#pragma unroll
+                for (int w = 0; w < CW; ++w) out[at + w] = fma(s0, c[at + w], acc[g][w]);
+            }
+        }
+    }
+}
+
+// The schedule and the workspace of one qs_string_ci_density2 call: the one place that carves it.
+struct Sc2Plan {
+    int64_t rows, passes;     // alpha rows per pass (the last pass may have fewer), passes
+    int64_t T, kc, pitch;     // slices of kc determinants per pass, pitch = T kc >= rows nb
+    int64_t off_a, off_b;     // byte offsets of the bra and ket panels behind the partial results at 0
+    int64_t bytes;
+};
+
+static Sc2Plan sc2_layout(int cw, int64_t m, int64_t nb, int64_t rows) {
+    const int64_t m2 = m * m, es = 8 * cw, R = rows * nb;
+    Sc2Plan p{};
+    p.rows = rows;
+    // slices: tiles x T covers the compute units, the partial results stay below an eighth of the panels
+    int64_t T = cdiv(kSc2Cus, cdiv(m2 + 1, 128) * cdiv(m2, 128));
+    const int64_t cap = R / (4 * (m2 + 1));
+    T = T < cap ? T : cap;
+    T = T < 1 ? 1 : T;
+    p.kc = (cdiv(R, T) + 1) & ~int64_t(1);                               // even: every slice starts on a 16-byte boundary
+    p.T = cdiv(R, p.kc);
+    p.pitch = p.T * p.kc;
+    p.off_a = p.T * (m2 + 1) * m2 * es;                                   // (m^2 + 1) m^2 is even
+    p.off_b = p.off_a + (m2 + 1) * p.pitch * es;
+    p.bytes = p.off_b + p.pitch * m2 * es;
+    return p;
+}
+
+static inline int64_t sc2_panel_bytes(const Sc2Plan& p) { return p.bytes - p.off_a; }
+
+static Sc2Plan sc2_plan(int cw, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes) {
+    const int64_t budget = g_tune.string_ci_bytes > 0 ? g_tune.string_ci_bytes : (budget_bytes > 0 ? budget_bytes : kScBytes);
+    int64_t rows = budget / ((2 * m * m + 1) * nb * 8 * cw);
+    rows = rows < 1 ? 1 : (rows < na ? rows : na);
+    Sc2Plan p = sc2_layout(cw, m, nb, rows);
+    while (p.rows > 1 && sc2_panel_bytes(p) > budget) p = sc2_layout(cw, m, nb, p.rows - 1);     // the padding of the slices
+    const int64_t passes = cdiv(na, p.rows);
+    const Sc2Plan even = sc2_layout(cw, m, nb, cdiv(na, passes));         // the same passes, of equal length
+    if (sc2_panel_bytes(even) <= sc2_panel_bytes(p)) p = even;
+    p.passes = cdiv(na, p.rows);
+    return p;
+}
+
+static int sc2_check(int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes) {
+    if (!dtype_ok(c_dtype)) return QS_ERR_BAD_DTYPE;
+    if (!sc_extents_ok(c_dtype == QS_C128 ? 1 : 0, m, na, nb, 1) || budget_bytes < 0) return QS_ERR_BAD_EXTENT;
+    return QS_OK;
+}
+
+template <int CW>
+static int sc2_expand(bool ket, const Sc2Args& a, const int32_t* ta, int64_t rows, void* P, hipStream_t s) {
+    const int threads = sc_threads(a.nb);
+    const unsigned grid = (unsigned)(rows * a.ntile);
+    if (ket) hipLaunchKernelGGL((string_ci_expand_rows_kernel<CW, true>), dim3(grid), dim3(threads), sc_lds(threads), s, a, ta, (double*)P);
+    else hipLaunchKernelGGL((string_ci_expand_rows_kernel<CW, false>), dim3(grid), dim3(threads), sc_lds(threads), s, a, ta, (double*)P);
+    note_dispatch(ket ? "qs::string_ci_expand_rows_kernel<%d, true>" : "qs::string_ci_expand_rows_kernel<%d, false>", CW);
+    return launch_status("string CI row expand launch");
+}
+
 }  // namespace qs
 
 using namespace qs;
@@ -436,6 +713,106 @@ int qs_string_ci_density1(int c_dtype, const int32_t* ta, const int32_t* tb, int
         hipLaunchKernelGGL((string_ci_dot_kernel<2>), dim3((unsigned)m2), dim3(kScRhoBlock), 0, s, (const double*)bra, (const double*)work, (double*)rho, (int)m, na * nb);
     note_dispatch("qs::string_ci_dot_kernel<%d>", cw);
     return launch_status("string CI density launch");
+}
+
+int64_t qs_string_ci_density2_workspace(int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes) {
+    const int rc = sc2_check(c_dtype, m, na, nb, budget_bytes);
+    if (rc) return rc;
+    return sc2_plan(c_dtype == QS_C128 ? 2 : 1, m, na, nb, budget_bytes).bytes;
+}
+
+int qs_string_ci_density2_plan(int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes, int64_t* plan) {
+    const int rc = sc2_check(c_dtype, m, na, nb, budget_bytes);
+    if (rc) return rc;
+    if (!plan) return QS_ERR_NULL_POINTER;
+    const Sc2Plan p = sc2_plan(c_dtype == QS_C128 ? 2 : 1, m, na, nb, budget_bytes);
+    plan[0] = p.rows; plan[1] = p.passes; plan[2] = p.T; plan[3] = p.kc; plan[4] = p.bytes;
+    return QS_OK;
+}
+
+int qs_string_ci_density2(int c_dtype, const int32_t* ta, const int32_t* tb, int64_t m, int64_t na, int64_t nb,
+                          const void* bra, const void* ket, void* gamma, void* rho, void* work, int64_t work_bytes,
+                          int64_t budget_bytes, void* stream) {
+    dispatch_reset();
+    int rc = sc2_check(c_dtype, m, na, nb, budget_bytes);
+    if (rc) return rc;
+    if (!ta || !tb || !bra || !ket || !gamma || !rho || !work) return QS_ERR_NULL_POINTER;
+    const int64_t cs = (int64_t)elem_size(c_dtype);
+    if (!aligned(ta, 4) || !aligned(tb, 4) || !aligned(bra, (size_t)cs) || !aligned(ket, (size_t)cs) || !aligned(gamma, (size_t)cs) ||
+        !aligned(rho, (size_t)cs) || !aligned(work, 16))
+        return QS_ERR_MISALIGNED;
+    const int cw = c_dtype == QS_C128 ? 2 : 1;
+    const Sc2Plan p = sc2_plan(cw, m, na, nb, budget_bytes);
+    if (work_bytes < p.bytes) return QS_ERR_WORKSPACE;
+    const int64_t m2 = m * m, g_bytes = m2 * m2 * cs, r_bytes = m2 * cs, v_bytes = na * nb * cs;
+    const struct { const void* at; int64_t bytes; } in[] = {{bra, v_bytes}, {ket, v_bytes}, {ta, na * m2 * 4}, {tb, nb * m2 * 4}};
+    for (const auto& x : in)
+        if (overlaps(gamma, g_bytes, x.at, x.bytes) || overlaps(rho, r_bytes, x.at, x.bytes) || overlaps(work, p.bytes, x.at, x.bytes))
+            return QS_ERR_ALIAS;
+    if (overlaps(gamma, g_bytes, rho, r_bytes) || overlaps(gamma, g_bytes, work, p.bytes) || overlaps(rho, r_bytes, work, p.bytes))
+        return QS_ERR_ALIAS;
+
+    hipStream_t s = (hipStream_t)stream;
+    char* part = (char*)work;
+    char* A = part + p.off_a;
+    char* B = part + p.off_b;
+    Sc2Args a{};
+    a.tb = tb; a.na = na; a.nb = nb; a.pitch = p.pitch; a.m2 = (int)m2;
+    a.ntile = (unsigned)cdiv(nb, sc_threads(nb));
+    for (int64_t pass = 0; pass < p.passes; ++pass) {
+        a.ia0 = pass * p.rows;
+        const int64_t rows = na - a.ia0 < p.rows ? na - a.ia0 : p.rows, R = rows * nb;
+        if (R < p.pitch) {
+            // the tail of the last slice, and of a ragged last pass: zeros in both operands
+            rc = hip_status(hipMemset2DAsync(A + R * cs, (size_t)(p.pitch * cs), 0, (size_t)((p.pitch - R) * cs), (size_t)(m2 + 1), s),
+                            "string CI bra panel tail");
+            if (rc) return rc;
+            rc = hip_status(hipMemsetAsync(B + R * m2 * cs, 0, (size_t)((p.pitch - R) * m2 * cs), s), "string CI ket panel tail");
+            if (rc) return rc;
+        }
+        a.c = (const double*)bra;
+        rc = cw == 1 ? sc2_expand<1>(false, a, ta, rows, A, s) : sc2_expand<2>(false, a, ta, rows, A, s);
+        if (rc) return rc;
+        a.c = (const double*)ket;
+        rc = cw == 1 ? sc2_expand<1>(true, a, ta, rows, B, s) : sc2_expand<2>(true, a, ta, rows, B, s);
+        if (rc) return rc;
+        // split-k as a batch: slice t is columns t kc ... of A and rows t kc ... of B, every pass adds into the same partials
+        rc = gemm(Product{c_dtype, (const double*)A, (const double*)B, (double*)part, m2 + 1, m2, p.kc, p.pitch, m2, m2, p.T, p.kc,
+                          p.kc * m2, (m2 + 1) * m2, pass > 0 ? 1 : 0},
+                  s);
+        if (rc) return rc;
+    }
+    const unsigned grid = sc_stride_grid(m2 * m2);
+    if (cw == 1)
+        hipLaunchKernelGGL((string_ci_gamma_close_kernel<1>), dim3(grid), dim3(kScRhoBlock), 0, s, (const double*)part, p.T, (int)m, (double*)gamma, (double*)rho);
+    else
+        hipLaunchKernelGGL((string_ci_gamma_close_kernel<2>), dim3(grid), dim3(kScRhoBlock), 0, s, (const double*)part, p.T, (int)m, (double*)gamma, (double*)rho);
+    note_dispatch("qs::string_ci_gamma_close_kernel<%d>", cw);
+    return launch_status("string CI two-body density close launch");
+}
+
+int qs_string_ci_spin_squared(int c_dtype, const int32_t* ta, const int32_t* tb, int64_t m, int64_t na, int64_t nb,
+                              int64_t Na, int64_t Nb, const void* c, int64_t K, void* out, void* stream) {
+    dispatch_reset();
+    if (!dtype_ok(c_dtype)) return QS_ERR_BAD_DTYPE;
+    if (!sc_extents_ok(c_dtype == QS_C128 ? 1 : 0, m, na, nb, K) || Na < 0 || Na > m || Nb < 0 || Nb > m) return QS_ERR_BAD_EXTENT;
+    if (!ta || !tb || !c || !out) return QS_ERR_NULL_POINTER;
+    const int64_t cs = (int64_t)elem_size(c_dtype);
+    if (!aligned(ta, 4) || !aligned(tb, 4) || !aligned(c, (size_t)cs) || !aligned(out, (size_t)cs)) return QS_ERR_MISALIGNED;
+    const int64_t m2 = m * m, o_bytes = K * na * nb * cs;
+    if (overlaps(out, o_bytes, c, o_bytes) || overlaps(out, o_bytes, ta, na * m2 * 4) || overlaps(out, o_bytes, tb, nb * m2 * 4))
+        return QS_ERR_ALIAS;
+    const double sz = 0.5 * (double)(Na - Nb), s0 = sz * (sz + 1.0) + (double)Nb;       // multiples of 1/4: exact
+    const ScArgs a = sc_args(ta, tb, c, m, na, nb, K);
+    const int threads = sc_threads(nb);
+    const unsigned grid = (unsigned)(cdiv(K, kScSpinG) * na * a.ntile);
+    hipStream_t s = (hipStream_t)stream;
+    if (c_dtype == QS_F64)
+        hipLaunchKernelGGL((string_ci_spin_kernel<1>), dim3(grid), dim3(threads), sc_lds(threads), s, a, ta, (double*)out, s0, (int)m);
+    else
+        hipLaunchKernelGGL((string_ci_spin_kernel<2>), dim3(grid), dim3(threads), sc_lds(threads), s, a, ta, (double*)out, s0, (int)m);
+    note_dispatch("qs::string_ci_spin_kernel<%d>", c_dtype == QS_F64 ? 1 : 2);
+    return launch_status("string CI spin launch");
 }
 
 }  // extern "C"

@@ -947,7 +947,9 @@ def det_ci_density2(dets, bra, ket, m, N, out=None):
 
 
 # Byte budget of the D and G panels of ONE qs_string_ci_sigma call: ``string_ci_sigma`` sends a batch in groups of as
-# many vectors as fit it (at least one).  The tuning key ``string_ci_bytes`` overrides it for the calling thread.
+# many vectors as fit it (at least one); also of the two panels of one pass of ``string_ci_density2``, which takes as
+# many alpha rows per pass as fit it (at least one).  The tuning key ``string_ci_bytes`` overrides it for the calling
+# thread.
 STRING_CI_BYTES = 2 << 30
 
 
@@ -1083,6 +1085,74 @@ def string_ci_density1(ta, tb, m, bra, ket, out=None):
             lib.qs_string_ci_density1(code, ta.data_ptr(), tb.data_ptr(), m, na, nb, bra.data_ptr(), ket.data_ptr(),
                                       out.data_ptr(), *_work(nbytes, bra.device), _stream()),
             "qs_string_ci_density1",
+        )
+    return out
+
+
+@_plain
+def string_ci_density2(ta, tb, m, bra, ket, out=None):
+    """``(gamma, rho)`` of two vectors (na, nb) on ``qs_string_ci_density2``: the spin-summed two-body density
+    ``gamma[p, q, r, s] = sum_spins <bra| a+_p a+_q a_s a_r |ket>`` (m, m, m, m) and ``rho[q, p] = <bra| E_pq |ket>``
+    (m, m) from the same pass; ``bra is ket`` is a state.  The expanded panels are cut into passes over alpha rows that
+    fit ``STRING_CI_BYTES`` (tuning key ``string_ci_bytes``); every pass is one batched product on the product
+    dispatcher.  With the plain ``ut``, ``<bra|H|ket> = sum ht[p,q] rho[q,p] + 1/2 sum ut[p,q,r,s] gamma[p,q,r,s]``.
+    ``out`` is a pair ``(gamma, rho)`` of buffers.  Repeating a call gives the same bits; another budget agrees to
+    rounding."""
+    lib = _lib.load()
+    m = int(m)
+    ta, tb = _string_tables(ta, tb, m)
+    dt = result_dtype(bra, ket)
+    same = bra is ket
+    bra = _dev(bra, dt)
+    ket = bra if same else _dev(ket, dt)
+    na, nb = ta.shape[0], tb.shape[0]
+    if tuple(bra.shape) != (na, nb) or tuple(ket.shape) != (na, nb):
+        raise ValueError(f"bra and ket have shapes {tuple(bra.shape)}, {tuple(ket.shape)}: need ({na}, {nb}) each")
+    code = dtype_code(dt)
+    nbytes = check(lib.qs_string_ci_density2_workspace(code, m, na, nb, STRING_CI_BYTES), "workspace query")
+    if out is None:
+        gamma = torch.empty((m, m, m, m), dtype=dt, device=bra.device)
+        rho = torch.empty((m, m), dtype=dt, device=bra.device)
+    else:
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise ValueError("string_ci_density2: `out` must be a pair (gamma, rho)")
+        gamma = _check_out(out[0], (m, m, m, m), dt, "string_ci_density2")
+        rho = _check_out(out[1], (m, m), dt, "string_ci_density2")
+    with _on_device_of(ta, tb, bra, ket, gamma, rho):
+        _ran(
+            lib.qs_string_ci_density2(code, ta.data_ptr(), tb.data_ptr(), m, na, nb, bra.data_ptr(), ket.data_ptr(),
+                                      gamma.data_ptr(), rho.data_ptr(), *_work(nbytes, bra.device), STRING_CI_BYTES,
+                                      _stream()),
+            "qs_string_ci_density2",
+        )
+    return gamma, rho
+
+
+@_plain
+def string_ci_spin_squared(ta, tb, m, Na, Nb, c, out=None):
+    """``out[k] = S^2 c[k]`` for ``c`` (K, na, nb) or (na, nb) with ``Na`` alpha and ``Nb`` beta particles on
+    ``qs_string_ci_spin_squared``: ``S^2 = S_z (S_z + 1) + N_beta - sum_pq E^alpha_qp E^beta_pq`` as one gather through
+    both replacement tables per (p, q).  On a truncated list a missing target contributes nothing."""
+    lib = _lib.load()
+    m = int(m)
+    ta, tb = _string_tables(ta, tb, m)
+    if not isinstance(c, torch.Tensor) or c.dim() not in (2, 3):
+        raise ValueError("c must be (K, na, nb) or (na, nb)")
+    dt = result_dtype(c)
+    c = _dev(c, dt)
+    na, nb = ta.shape[0], tb.shape[0]
+    K = 1 if c.dim() == 2 else c.shape[0]
+    if tuple(c.shape[-2:]) != (na, nb) or K < 1:
+        raise ValueError(f"c has shape {tuple(c.shape)}: need (K, {na}, {nb}) with K >= 1")
+    if out is None:
+        out = torch.empty(tuple(c.shape), dtype=dt, device=c.device)
+    else:
+        _check_out(out, tuple(c.shape), dt, "string_ci_spin_squared")
+    with _on_device_of(ta, tb, c, out):
+        _ran(
+            lib.qs_string_ci_spin_squared(dtype_code(dt), ta.data_ptr(), tb.data_ptr(), m, na, nb, int(Na), int(Nb),
+                                          c.data_ptr(), K, out.data_ptr(), _stream()),
+            "qs_string_ci_spin_squared",
         )
     return out
 

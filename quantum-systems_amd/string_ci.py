@@ -16,8 +16,11 @@ spin.  The lists are data (default: all of them); a replacement whose target str
     E, c = ci.solve(n_roots=3)                        # c: (n_roots, na, nb)
     rho = ci.one_body_density(0)                      # spin-summed, for system.compute_particle_density(rho, C=C)
     masks, v = ci.to_determinants(c[0])               # the same state in DeterminantCI's convention
+    G = ci.two_body_density(0)                        # spin-summed, ci.energy_from_densities(0) == E[0]
+    S2 = ci.spin_squared(0)                           # S (S + 1): which root is a singlet, which a triplet
 
-Out of scope here: two-body densities, <S^2>, a sharded ``u``, and chunking the expanded vectors over rows of ``W``.
+Out of scope here: spin-resolved two-body densities, a spin penalty or spin-adapted guesses in ``solve``, a sharded
+``u``, and chunking sigma's expanded vectors over rows of ``W``.
 """
 
 import numpy
@@ -207,6 +210,51 @@ class StringCI:
         with torch._C.DisableTorchFunctionSubclass():
             rho = self._rho(k, l)
         return _deliver(rho, self.system.np)
+
+    def _pair(self, k, l=None):
+        if self._c is None:
+            raise RuntimeError("call solve() first")
+        bra = self._c[k]
+        return bra, (bra if l is None or l == k else self._c[l])
+
+    def two_body_density(self, k=0, l=None):
+        """Spin-summed ``Gamma[p,q,r,s] = sum_spins <c_k| a+_p a+_q a_s a_r |c_l>`` (m, m, m, m) in the orbitals ``C``
+        (``l`` defaults to ``k``: the density of solved state ``k``), on ``kernels.string_ci_density2``.  Symmetries:
+        ``Gamma[p,q,r,s] = Gamma[q,p,s,r]``; for a state it is Hermitian, ``Gamma[p,q,r,s] = conj(Gamma[r,s,p,q])``;
+        ``sum_q Gamma[p,q,r,q] = (N - 1) rho[r,p]`` with ``rho`` of ``one_body_density`` / ``transition_density`` and
+        ``N = n_up + n_down``, so ``sum_pq Gamma[p,q,p,q] = N (N - 1)`` for a state and 0 between two of them."""
+        with torch._C.DisableTorchFunctionSubclass():
+            gamma, _ = kernels.string_ci_density2(self._ta, self._tb, self.m, *self._pair(k, l))
+        return _deliver(gamma, self.system.np)
+
+    def energy_from_densities(self, k=0):
+        """``sum ht[p,q] rho[q,p] + 1/2 sum ut[p,q,r,s] Gamma[p,q,r,s] + nuclear repulsion`` of solved state ``k``
+        (real part): the factor is 1/2 with the plain ``ut``, where ``DeterminantCI`` has 1/4 with the anti-symmetrised
+        one.  Equals ``E[k]`` to the accuracy of the state."""
+        with torch._C.DisableTorchFunctionSubclass():
+            gamma, rho = kernels.string_ci_density2(self._ta, self._tb, self.m, *self._pair(k))
+            e = (self._ht * rho.transpose(0, 1)).sum() + 0.5 * (self._ut * gamma).sum()
+            return float(e.real.item()) + float(self.system.nuclear_repulsion_energy)
+
+    def apply_spin_squared(self, c):
+        """``S^2 c_k`` for ``c`` (k, na, nb) or (na, nb), device tensor in and out
+        (``kernels.string_ci_spin_squared``).  On truncated string lists a missing target contributes nothing: ``S^2``
+        is then the operator of the truncated formulation, as ``H`` is."""
+        with torch._C.DisableTorchFunctionSubclass():
+            c = _plain(c)
+            if tuple(c.shape[-2:]) != (self.na, self.nb) or c.dim() not in (2, 3):
+                raise ValueError(f"c has shape {tuple(c.shape)}: need (k, {self.na}, {self.nb}) or ({self.na}, {self.nb})")
+            return kernels.string_ci_spin_squared(self._ta, self._tb, self.m, self.n_up, self.n_down, c)
+
+    def spin_squared(self, k=0):
+        """``Re <c_k| S^2 |c_k>`` of solved state ``k``: ``S (S + 1)`` for a spin eigenstate."""
+        with torch._C.DisableTorchFunctionSubclass():
+            bra, _ = self._pair(k)
+            return float(torch.vdot(bra.reshape(-1), self.apply_spin_squared(bra).reshape(-1)).real.item())
+
+    def spin_multiplicity(self, k=0):
+        """``2 S + 1 = sqrt(1 + 4 <S^2>)`` of solved state ``k``."""
+        return float(numpy.sqrt(max(0.0, 1.0 + 4.0 * self.spin_squared(k))))
 
     def _in_orbitals(self, A):
         """``C^H A C`` of a matrix (l, l) or a stack (d, l, l) given in the system's basis."""
