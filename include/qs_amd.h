@@ -770,6 +770,27 @@ int qs_det_ci_density2(int c_dtype, const int64_t* dets, const void* bra, const 
  *       when both are 0) and its product within 2^31 - 1 columns; at least 1.
  *       A positive tuning key takes precedence over budget_bytes: it is the
  *       override of a tuning run, not a default.
+ *   qs_string_ci_sigma_rows : the same sigma in passes over alpha rows of the
+ *       INTERMEDIATE, for vectors whose D and G do not fit a byte budget.  A pass
+ *       owns the alpha rows r0 <= Ka < r1, R = r1 - r0:
+ *         expand : D_p[(qs), k, Ka - r0, Kb] = (E_qs c_k)[Ka, Kb]   (m^2 x K R nb)
+ *         product: G_p = W . D_p
+ *         fold   : sigma_k[Ia, Ib] (+)= the terms of the fold above whose source
+ *                  row (Ta[Ia,pr] for alpha, Ia for beta) lies in the pass
+ *       c stays whole; the passes follow one another on the stream and add into
+ *       sigma, the first one from 0: sigma need not be initialised, every element
+ *       is written.  No atomics; the order of one element's sum is pass ascending,
+ *       pr ascending, alpha before beta: repeating a call gives the same bits, and
+ *       a call of one pass gives the bits of qs_string_ci_sigma.  budget_bytes as
+ *       in qs_string_ci_group (tuning key, else the argument, else 2 GiB);
+ *       budget_bytes < 0 is QS_ERR_BAD_EXTENT.  work holds plan[3] bytes.
+ *   qs_string_ci_sigma_plan : plan[0 ... 3] = alpha rows per pass, passes, columns
+ *       of one (full) pass's product, workspace bytes.  rows is the largest count
+ *       with 2 * ceil16(m^2 * K * rows * nb * sizeof(element of c)) <= budget and
+ *       K rows nb (twice that for (F64, C128)) <= 2^31 - 1, at least 1; then
+ *       passes = ceil(na / rows) and rows = ceil(na / passes), so that the passes
+ *       are of equal length where that costs no extra pass.  The workspace is
+ *       2 * ceil16(m^2 * K * rows * nb * sizeof(element of c)) of the final rows.
  *   qs_string_ci_density1 : rho[q * m + p] = <bra| E_pq |ket>
  *       = sum_K conj(bra[K]) (E_pq ket)[K], spin-summed, one expand of ket and one
  *       fixed-order sum per (p, q); bra == ket (the same pointer is allowed) is a
@@ -822,6 +843,11 @@ int64_t qs_string_ci_group(int h_dtype, int c_dtype, int64_t m, int64_t na, int6
 int qs_string_ci_sigma(int h_dtype, int c_dtype, const void* k, const void* W, const int32_t* ta, const int32_t* tb,
                        int64_t m, int64_t na, int64_t nb, const void* c, int64_t K, void* sigma,
                        void* work, int64_t work_bytes, void* stream);
+int qs_string_ci_sigma_plan(int h_dtype, int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t K, int64_t budget_bytes,
+                            int64_t* plan);
+int qs_string_ci_sigma_rows(int h_dtype, int c_dtype, const void* k, const void* W, const int32_t* ta, const int32_t* tb,
+                            int64_t m, int64_t na, int64_t nb, const void* c, int64_t K, void* sigma,
+                            void* work, int64_t work_bytes, int64_t budget_bytes, void* stream);
 int qs_string_ci_density1(int c_dtype, const int32_t* ta, const int32_t* tb, int64_t m, int64_t na, int64_t nb,
                           const void* bra, const void* ket, void* rho, void* work, int64_t work_bytes, void* stream);
 int64_t qs_string_ci_density2_workspace(int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes);

@@ -38,7 +38,8 @@ constexpr int kScBlock = 256;         // most beta strings (threads) of a workgr
 constexpr int kScRhoBlock = 256;      // threads of the density's and of the diagonal's workgroup
 // Shipped byte budget of the D and G of one qs_string_ci_sigma call: qs_string_ci_group() splits a batch by it when
 // the caller passes 0 (kernels.STRING_CI_BYTES passes its own).  Not measured yet.  Also the budget of
-// the two panels of one pass of qs_string_ci_density2.
+// the two panels of one pass of qs_string_ci_density2 and of the D_p and G_p of one pass of
+// qs_string_ci_sigma_rows.
 constexpr int64_t kScBytes = int64_t(2) << 30;
 
 struct ScArgs {
@@ -182,6 +183,126 @@ __global__ __launch_bounds__(kScBlock) void string_ci_fold_kernel(const ScArgs a
     }
 }
 
+// ---- sigma in passes over alpha rows of the intermediate (qs_string_ci_sigma_rows) -------------------------------------
+// A pass owns the alpha rows r0 <= Ka < r1 of D and G, R = r1 - r0: D_p[(qs), k, Ka - r0, Kb], panel stride R nb.  c stays
+// whole.  The fold runs over every (k, Ia, tile) in every pass and keeps the terms whose SOURCE row lies in the pass -- the
+// alpha term of pr when r0 <= Ta[Ia,pr] < r1, the beta terms when r0 <= Ia < r1 --, so nothing is scattered: a pass adds
+// into sigma, the first one (r0 = 0) starts from 0 and never reads it.  The order of one element's sum is pass ascending,
+// pr ascending, alpha before beta; a pass boundary stores and reloads the accumulator exactly, so one pass over all rows
+// gives the bits of string_ci_fold_kernel.
+
+template <int CW>
+__global__ __launch_bounds__(kScBlock) void string_ci_expand_range_kernel(const ScArgs a, const int32_t* __restrict__ ta,
+                                                                         double* __restrict__ D, int64_t r0, int64_t r1) {
+    // the mapping of string_ci_expand_kernel on the rows of the pass; ta and D are arguments of their own for its reason
+    extern __shared__ __attribute__((aligned(16))) int32_t sc_tb[];
+    const int B = blockDim.x, t = threadIdx.x, m2 = a.m2;
+    const int64_t il = blockIdx.x / a.ntile;                              // uniform
+    const int64_t ia = r0 + il;
+    const int64_t ib0 = (int64_t)(blockIdx.x % a.ntile) * B;
+    const int64_t ib = ib0 + t, nb = a.nb, dim = a.na * a.nb, pdim = (r1 - r0) * nb;
+    const bool live = ib < nb;
+    const int32_t* __restrict__ ta_row = ta + ia * m2;
+    const double* __restrict__ c = a.c;
+    for (int pq0 = 0; pq0 < m2; pq0 += kScChunk) {
+        __syncthreads();
+        sc_stage(sc_tb, a.tb, ib0, nb, pq0, m2);
+        __syncthreads();
+        if (!live) continue;
+        const int nj = m2 - pq0 < kScChunk ? m2 - pq0 : kScChunk;
+        for (int j = 0; j < nj; ++j) {
+            const int pq = pq0 + j;
+            const int32_t ea = ta_row[pq];                                // uniform address: a scalar load
+            const int32_t eb = sc_tb[j * (B + 1) + t];
+            const int64_t ja = ea ? sc_target(ea, a.na) : -1, jb = eb ? sc_target(eb, nb) : -1;
+            for (int k = 0; k < a.K; ++k) {
+                const double* __restrict__ ck = c + (int64_t)k * dim * CW;        // the whole vector: targets lie anywhere
+                double v[CW];
+#pragma unroll
+                for (int w = 0; w < CW; ++w) v[w] = 0.0;
+                if (ja >= 0) {
+                    const double* x = ck + (ja * nb + ib) * CW;
+#pragma unroll
+                    for (int w = 0; w < CW; ++w) v[w] = ea < 0 ? -x[w] : x[w];
+                }
+                if (jb >= 0) {
+                    const double* x = ck + (ia * nb + jb) * CW;
+#pragma unroll
+                    for (int w = 0; w < CW; ++w) v[w] += eb < 0 ? -x[w] : x[w];
+                }
+                double* d = D + (((int64_t)pq * a.K + k) * pdim + il * nb + ib) * CW;
+#pragma unroll
+                for (int w = 0; w < CW; ++w) d[w] = v[w];
+            }
+        }
+    }
+}
+
+template <int FORM>
+__global__ __launch_bounds__(kScBlock) void string_ci_fold_range_kernel(const ScArgs a, const int32_t* __restrict__ ta,
+                                                                       double* __restrict__ sigma, int64_t r0, int64_t r1) {
+    constexpr int HW = form_widths(FORM).uw, CW = form_widths(FORM).aw;
+    extern __shared__ __attribute__((aligned(16))) int32_t sc_tb[];
+    const int B = blockDim.x, t = threadIdx.x, m2 = a.m2;
+    const unsigned row = blockIdx.x / a.ntile;                            // (k, ia), uniform
+    const int64_t k = row / (unsigned)a.na, ia = row % (unsigned)a.na;
+    const int64_t ib0 = (int64_t)(blockIdx.x % a.ntile) * B;
+    const int64_t ib = ib0 + t, nb = a.nb, dim = a.na * a.nb, pdim = (r1 - r0) * nb;
+    const bool live = ib < nb;
+    const int32_t* __restrict__ ta_row = ta + ia * m2;
+    const double* __restrict__ ck = a.c + k * dim * CW;
+    const double* __restrict__ kk = a.kk;
+    const double* __restrict__ Gk = a.G + k * pdim * CW;                  // X_p[(pr), k, :, :] = Gk + pr K pdim
+    double* __restrict__ out = sigma + (k * dim + ia * nb + ib) * CW;
+    double acc[CW];
+#pragma unroll
+    for (int w = 0; w < CW; ++w) acc[w] = (r0 > 0 && live) ? out[w] : 0.0;        // the first pass never reads sigma
+    if (ia >= r0 && ia < r1) {                                            // uniform: the row Ia itself is in the pass
+        const int64_t il = ia - r0;
+        for (int pr0 = 0; pr0 < m2; pr0 += kScChunk) {
+            __syncthreads();
+            sc_stage(sc_tb, a.tb, ib0, nb, pr0, m2);
+            __syncthreads();
+            if (!live) continue;
+            const int nj = m2 - pr0 < kScChunk ? m2 - pr0 : kScChunk;
+            for (int j = 0; j < nj; ++j) {
+                const int pr = pr0 + j;
+                const int32_t ea = ta_row[pr];                            // uniform address: a scalar load
+                const int32_t eb = sc_tb[j * (B + 1) + t];
+                double kpr[HW];
+#pragma unroll
+                for (int w = 0; w < HW; ++w) kpr[w] = kk[pr * HW + w];
+                const double* __restrict__ g = Gk + (int64_t)pr * a.K * pdim * CW;
+                if (ea) {
+                    const int64_t ja = sc_target(ea, a.na);               // -1 (past the list) is below every r0
+                    if (ja >= r0 && ja < r1) sc_feed<HW, CW>(acc, kpr, g + ((ja - r0) * nb + ib) * CW, ck + (ja * nb + ib) * CW, ea < 0);
+                }
+                if (eb) {
+                    const int64_t jb = sc_target(eb, nb);
+                    if (jb >= 0) sc_feed<HW, CW>(acc, kpr, g + (il * nb + jb) * CW, ck + (ia * nb + jb) * CW, eb < 0);
+                }
+            }
+        }
+    } else if (live) {
+        // outside the pass: no beta term, no staging, no barrier; the alpha entries and their range test are scalar
+        for (int pr = 0; pr < m2; ++pr) {
+            const int32_t ea = ta_row[pr];                                // uniform address: a scalar load
+            if (!ea) continue;
+            const int64_t ja = sc_target(ea, a.na);
+            if (ja < r0 || ja >= r1) continue;
+            double kpr[HW];
+#pragma unroll
+            for (int w = 0; w < HW; ++w) kpr[w] = kk[pr * HW + w];
+            const double* __restrict__ g = Gk + (int64_t)pr * a.K * pdim * CW;
+            sc_feed<HW, CW>(acc, kpr, g + ((ja - r0) * nb + ib) * CW, ck + (ja * nb + ib) * CW, ea < 0);
+        }
+    }
+    if (live) {
+#pragma unroll
+        for (int w = 0; w < CW; ++w) out[w] = acc[w];
+    }
+}
+
 // T[K, p * m + q] of one string list: one thread per entry (grid-stride).
 __global__ __launch_bounds__(kScRhoBlock) void string_ci_table_kernel(const int64_t* __restrict__ strings, int64_t n, int m,
                                                                       int32_t* __restrict__ table) {
@@ -302,6 +423,38 @@ static int sc_expand(int cw, ScArgs a, void* D, hipStream_t s) {
     else hipLaunchKernelGGL((string_ci_expand_kernel<2>), dim3(grid), dim3(threads), sc_lds(threads), s, a, a.ta, a.out);
     note_dispatch("qs::string_ci_expand_kernel<%d>", cw);
     return launch_status("string CI expand launch");
+}
+
+// The schedule and the workspace of one qs_string_ci_sigma_rows call, fixed by its arguments and the calling thread's
+// string_ci_bytes alone: the one place that carves it.
+struct ScRowsPlan {
+    int64_t rows, passes;     // alpha rows per pass (the last pass may have fewer), passes
+    int64_t cols;             // columns of a full pass's product
+    int64_t panel;            // bytes of D_p (and of G_p) of a full pass
+};
+
+static ScRowsPlan sc_rows_plan(int form, int64_t m, int64_t na, int64_t nb, int64_t K, int64_t budget_bytes) {
+    const int64_t budget = g_tune.string_ci_bytes > 0 ? g_tune.string_ci_bytes : (budget_bytes > 0 ? budget_bytes : kScBytes);
+    // 2 ceil16(x) <= budget  <=>  x <= the multiple of 16 at or below budget / 2
+    int64_t rows = ((budget / 2) & ~int64_t(15)) / (m * m * K * nb * 8 * form_widths(form).aw);
+    // rows <= na also keeps a pass's product within 2^31 - 1 columns: sc_extents_ok has bounded those of all na rows
+    rows = rows < 1 ? 1 : (rows < na ? rows : na);
+    ScRowsPlan p{};
+    p.passes = cdiv(na, rows);
+    p.rows = cdiv(na, p.passes);                                          // the same passes, of equal length
+    p.cols = K * p.rows * nb * (form == 2 ? 2 : 1);
+    p.panel = sc_panel_bytes(form, m, p.rows, nb, K);
+    return p;
+}
+
+// D_p = expand(c) on the alpha rows r0 ... r1 - 1, for the K vectors of c
+static int sc_expand_range(int cw, const ScArgs& a, void* D, int64_t r0, int64_t r1, hipStream_t s) {
+    const int threads = sc_threads(a.nb);
+    const unsigned grid = (unsigned)((r1 - r0) * a.ntile);
+    if (cw == 1) hipLaunchKernelGGL((string_ci_expand_range_kernel<1>), dim3(grid), dim3(threads), sc_lds(threads), s, a, a.ta, (double*)D, r0, r1);
+    else hipLaunchKernelGGL((string_ci_expand_range_kernel<2>), dim3(grid), dim3(threads), sc_lds(threads), s, a, a.ta, (double*)D, r0, r1);
+    note_dispatch("qs::string_ci_expand_range_kernel<%d>", cw);
+    return launch_status("string CI range expand launch");
 }
 
 static unsigned sc_stride_grid(int64_t total) {
@@ -683,6 +836,64 @@ int qs_string_ci_sigma(int h_dtype, int c_dtype, const void* k, const void* W, c
         note_dispatch("qs::string_ci_fold_kernel<%d>", (int)FORM);
     });
     return launch_status("string CI fold launch");
+}
+
+int qs_string_ci_sigma_plan(int h_dtype, int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t K, int64_t budget_bytes,
+                            int64_t* plan) {
+    const int form = tensor_form(h_dtype, c_dtype);
+    if (form < 0) return form;
+    if (!sc_extents_ok(form, m, na, nb, K) || budget_bytes < 0) return QS_ERR_BAD_EXTENT;
+    if (!plan) return QS_ERR_NULL_POINTER;
+    const ScRowsPlan p = sc_rows_plan(form, m, na, nb, K, budget_bytes);
+    plan[0] = p.rows; plan[1] = p.passes; plan[2] = p.cols; plan[3] = 2 * p.panel;
+    return QS_OK;
+}
+
+int qs_string_ci_sigma_rows(int h_dtype, int c_dtype, const void* k, const void* W, const int32_t* ta, const int32_t* tb,
+                            int64_t m, int64_t na, int64_t nb, const void* c, int64_t K, void* sigma, void* work,
+                            int64_t work_bytes, int64_t budget_bytes, void* stream) {
+    dispatch_reset();
+    const int form = tensor_form(h_dtype, c_dtype);
+    if (form < 0) return form;
+    if (!sc_extents_ok(form, m, na, nb, K) || budget_bytes < 0) return QS_ERR_BAD_EXTENT;
+    if (!k || !W || !ta || !tb || !c || !sigma || !work) return QS_ERR_NULL_POINTER;
+    const int64_t hs = (int64_t)elem_size(h_dtype), cs = (int64_t)elem_size(c_dtype);
+    if (!aligned(k, (size_t)hs) || !aligned(W, (size_t)hs) || !aligned(ta, 4) || !aligned(tb, 4) || !aligned(c, (size_t)cs) ||
+        !aligned(sigma, (size_t)cs) || !aligned(work, 16))
+        return QS_ERR_MISALIGNED;
+    const ScRowsPlan p = sc_rows_plan(form, m, na, nb, K, budget_bytes);
+    const int64_t w_bytes = 2 * p.panel;
+    if (work_bytes < w_bytes) return QS_ERR_WORKSPACE;
+    const int64_t m2 = m * m, s_bytes = K * na * nb * cs;
+    const struct { const void* at; int64_t bytes; } in[] = {{c, s_bytes}, {W, m2 * m2 * hs}, {k, m2 * hs}, {ta, na * m2 * 4}, {tb, nb * m2 * 4}};
+    for (const auto& x : in)
+        if (overlaps(sigma, s_bytes, x.at, x.bytes) || overlaps(work, w_bytes, x.at, x.bytes)) return QS_ERR_ALIAS;
+    if (overlaps(sigma, s_bytes, work, w_bytes)) return QS_ERR_ALIAS;
+
+    hipStream_t s = (hipStream_t)stream;
+    const FormWidths fw = form_widths(form);
+    char* D = (char*)work;
+    char* G = D + p.panel;
+    ScArgs a = sc_args(ta, tb, c, m, na, nb, K);
+    a.kk = (const double*)k; a.G = (const double*)G;
+    const int threads = sc_threads(nb);
+    const unsigned grid = (unsigned)(K * na * a.ntile);
+    for (int64_t r0 = 0; r0 < na; r0 += p.rows) {
+        const int64_t r1 = r0 + p.rows < na ? r0 + p.rows : na;
+        int rc = sc_expand_range(fw.aw, a, D, r0, r1, s);
+        if (rc) return rc;
+        // real W against complex c: the re / im pairs of D_p are columns of a real product
+        rc = gemm(packed(h_dtype, W, D, G, m2, K * (r1 - r0) * nb * (fw.aw / fw.uw), m2), s);
+        if (rc) return rc;
+        with_form(form, [&](auto FORM) {
+            hipLaunchKernelGGL((string_ci_fold_range_kernel<FORM>), dim3(grid), dim3(threads), sc_lds(threads), s, a, a.ta,
+                               (double*)sigma, r0, r1);
+            note_dispatch("qs::string_ci_fold_range_kernel<%d>", (int)FORM);
+        });
+        rc = launch_status("string CI range fold launch");
+        if (rc) return rc;
+    }
+    return QS_OK;
 }
 
 int qs_string_ci_density1(int c_dtype, const int32_t* ta, const int32_t* tb, int64_t m, int64_t na, int64_t nb,

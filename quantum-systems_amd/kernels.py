@@ -947,9 +947,10 @@ def det_ci_density2(dets, bra, ket, m, N, out=None):
 
 
 # Byte budget of the D and G panels of ONE qs_string_ci_sigma call: ``string_ci_sigma`` sends a batch in groups of as
-# many vectors as fit it (at least one); also of the two panels of one pass of ``string_ci_density2``, which takes as
-# many alpha rows per pass as fit it (at least one).  The tuning key ``string_ci_bytes`` overrides it for the calling
-# thread.
+# many vectors as fit it, and where one vector alone is over it, in passes over as many alpha rows of that vector's D
+# and G as fit it (``qs_string_ci_sigma_rows``, at least one row); also of the two panels of one pass of
+# ``string_ci_density2``, which takes as many alpha rows per pass as fit it (at least one).  The tuning key
+# ``string_ci_bytes`` overrides it for the calling thread.
 STRING_CI_BYTES = 2 << 30
 
 
@@ -1011,14 +1012,28 @@ def string_ci_diagonal(ht, ut, strings_a, Na, strings_b, Nb, out=None):
     return out
 
 
+def string_ci_sigma_plan(m, na, nb, c_dtype, K=1, h_dtype=None):
+    """``(rows, passes, columns, work_bytes)`` of ``qs_string_ci_sigma_rows`` on ``K`` vectors of ``c_dtype`` (``h_dtype``:
+    the dtype of ``k`` and ``W``, default the same) under ``STRING_CI_BYTES`` or the calling thread's ``string_ci_bytes``:
+    alpha rows per pass, passes, columns of one pass's product, workspace bytes.  ``passes == 1`` exactly where the D
+    and G of the K vectors fit the budget; ``string_ci_sigma`` takes the passes where one vector does not."""
+    plan = (ctypes.c_int64 * 4)()
+    hcode = dtype_code(c_dtype if h_dtype is None else h_dtype)
+    check(_lib.load().qs_string_ci_sigma_plan(hcode, dtype_code(c_dtype), int(m), int(na), int(nb), int(K), STRING_CI_BYTES,
+                                              ctypes.addressof(plan)), "plan query")
+    return tuple(plan)
+
+
 @_plain
 def string_ci_sigma(k, W, ta, tb, c, out=None):
     """``sigma[j] = H c[j]`` for ``c`` (K, na, nb) or (na, nb) on ``qs_string_ci_sigma``: ``k`` (m, m) and ``W``
     (m^2, m^2) as in ``include/qs_amd.h``, ``ta`` (na, m^2) and ``tb`` (nb, m^2) from ``string_ci_table``.  Per group of
     vectors one expand, ONE product ``W . D`` on the product dispatcher and one fold; the groups are as large as
     ``STRING_CI_BYTES`` of workspace allow.  A real ``k`` and ``W`` with a complex ``c`` stay real (fp64 product on the
-    re / im pairs).  Repeating a call gives the same bits; another grouping agrees to rounding.  One ``dispatch_log``
-    entry names the kernels of the whole call."""
+    re / im pairs).  Where the D and G of ONE vector are over the budget, each vector goes to
+    ``qs_string_ci_sigma_rows`` instead: passes over as many alpha rows of the intermediate as fit, which add into
+    ``sigma`` on the stream.  Repeating a call gives the same bits; another grouping or another budget agrees to
+    rounding.  One ``dispatch_log`` entry names the kernels of the whole call."""
     lib = _lib.load()
     if not isinstance(c, torch.Tensor) or c.dim() not in (2, 3):
         raise ValueError("c must be (K, na, nb) or (na, nb)")
@@ -1042,16 +1057,22 @@ def string_ci_sigma(k, W, ta, tb, c, out=None):
         _check_out(out, tuple(c.shape), dt, "string_ci_sigma")
     o3 = out[None] if single else out
     ran = []
+    # one vector alone is over the budget: passes over alpha rows (qs_string_ci_sigma_rows), one vector per call, so that
+    # the fold's extra walks of the alpha table and round trips of sigma stay linear in K
+    _, passes, _, rows_bytes = string_ci_sigma_plan(m, na, nb, dt, 1, hdt)
+    if passes > 1:
+        group = 1
     with _on_device_of(k, W, ta, tb, c, out):
         for k0 in range(0, K, group):
             kg = min(group, K - k0)
-            nbytes = check(lib.qs_string_ci_workspace(hcode, ccode, m, na, nb, kg), "workspace query")
-            check(
-                lib.qs_string_ci_sigma(hcode, ccode, k.data_ptr(), W.data_ptr(), ta.data_ptr(), tb.data_ptr(), m, na, nb,
-                                       c3[k0:k0 + kg].data_ptr(), kg, o3[k0:k0 + kg].data_ptr(),
-                                       *_work(nbytes, c.device), _stream()),
-                "qs_string_ci_sigma",
-            )
+            args = (hcode, ccode, k.data_ptr(), W.data_ptr(), ta.data_ptr(), tb.data_ptr(), m, na, nb,
+                    c3[k0:k0 + kg].data_ptr(), kg, o3[k0:k0 + kg].data_ptr())
+            if passes > 1:
+                check(lib.qs_string_ci_sigma_rows(*args, *_work(rows_bytes, c.device), STRING_CI_BYTES, _stream()),
+                      "qs_string_ci_sigma_rows")
+            else:
+                nbytes = check(lib.qs_string_ci_workspace(hcode, ccode, m, na, nb, kg), "workspace query")
+                check(lib.qs_string_ci_sigma(*args, *_work(nbytes, c.device), _stream()), "qs_string_ci_sigma")
             if dispatch_log is not None:
                 ran.append(lib.qs_last_dispatch().decode())
     if dispatch_log is not None:

@@ -19,8 +19,12 @@ spin.  The lists are data (default: all of them); a replacement whose target str
     G = ci.two_body_density(0)                        # spin-summed, ci.energy_from_densities(0) == E[0]
     S2 = ci.spin_squared(0)                           # S (S + 1): which root is a singlet, which a triplet
 
-Out of scope here: spin-resolved two-body densities, a spin penalty or spin-adapted guesses in ``solve``, a sharded
-``u``, and chunking sigma's expanded vectors over rows of ``W``.
+A vector whose expanded intermediate is over ``kernels.STRING_CI_BYTES`` goes through sigma in passes over alpha rows,
+and its one-body quantities come from the pass-wise ``kernels.string_ci_density2``: the largest state is set by the
+vectors themselves.
+
+Out of scope here: spin-resolved two-body densities, a spin penalty or spin-adapted guesses in ``solve``, and a sharded
+``u``.
 """
 
 import numpy
@@ -196,6 +200,9 @@ class StringCI:
             raise RuntimeError("call solve() first")
         bra = self._c[k]
         ket = bra if l is None or l == k else self._c[l]
+        if kernels.string_ci_sigma_plan(self.m, self.na, self.nb, self._dt)[1] > 1:
+            # a state that sigma reaches in passes: the pass-wise route, whose panels stay within the budget
+            return kernels.string_ci_density2(self._ta, self._tb, self.m, bra, ket)[1]
         return kernels.string_ci_density1(self._ta, self._tb, self.m, bra, ket)
 
     def one_body_density(self, k=0):
