@@ -791,6 +791,32 @@ int qs_det_ci_density2(int c_dtype, const int64_t* dets, const void* bra, const 
  *       passes = ceil(na / rows) and rows = ceil(na / passes), so that the passes
  *       are of equal length where that costs no extra pass.  The workspace is
  *       2 * ceil16(m^2 * K * rows * nb * sizeof(element of c)) of the final rows.
+ *   qs_string_ci_sigma_sym : sigma of vectors of definite parity under the exchange
+ *       of the two spins, c_k[Ia, Ib] = parity * c_k[Ib, Ia] (parity = +-1), for
+ *       na = nb = n strings and ONE table t for both spins.  In this determinant
+ *       convention an eigenstate of spin S has parity (-1)^S.  Every row of D, G
+ *       and X = G + k c then has the same parity in (Ka, Kb), and only the columns
+ *       Kb <= Ka are formed: packed row Ka at off(Ka) = Ka (Ka + 1) / 2.  Always in
+ *       passes over packed rows r0 <= Ka < r1, L = off(r1) - off(r0):
+ *         expand : D_p[(qs), k, off(Ka) - off(r0) + Kb] = (E_qs c_k)[Ka, Kb]
+ *         product: G_p = W . D_p                          (m^2 x K L, the dispatcher)
+ *         fold   : S_k[Ia, Ib] (+)= the stored terms of the fold whose source row
+ *                  lies in the pass, a diagonal element of X weighted 1/2
+ *         close  : sigma_k = S_k + parity * S_k^T, in place, after the last pass
+ *       c and sigma are full (K, n, n).  sigma need not be initialised.  The
+ *       result has the parity bit for bit: sigma[a,b] == parity * sigma[b,a], the
+ *       diagonal +0.0 for parity = -1; repeating a call gives the same bits.  The
+ *       precondition on c is NOT checked: for another c the result is
+ *       deterministic and unspecified.  budget_bytes as in qs_string_ci_sigma_rows;
+ *       parity other than +-1 or budget_bytes < 0 is QS_ERR_BAD_EXTENT.  work
+ *       holds plan[3] bytes, D_p then G_p.
+ *   qs_string_ci_sigma_sym_plan : plan[0 ... 3] = passes, the largest packed length
+ *       L, the columns of the largest product (K L, twice that for (F64, C128)),
+ *       workspace bytes 2 * ceil16(m^2 * K * L * sizeof(element of c)).  The
+ *       boundaries are greedy from b_0 = 0: b_i+1 is the largest r <= n with
+ *       2 * ceil16(m^2 * K * (off(r) - off(b_i)) * sizeof(element)) <= budget, at
+ *       least b_i + 1.  bounds may be null; otherwise it receives the passes + 1
+ *       boundaries, and bounds_len < passes + 1 is QS_ERR_BAD_EXTENT.
  *   qs_string_ci_density1 : rho[q * m + p] = <bra| E_pq |ket>
  *       = sum_K conj(bra[K]) (E_pq ket)[K], spin-summed, one expand of ket and one
  *       fixed-order sum per (p, q); bra == ket (the same pointer is allowed) is a
@@ -848,6 +874,11 @@ int qs_string_ci_sigma_plan(int h_dtype, int c_dtype, int64_t m, int64_t na, int
 int qs_string_ci_sigma_rows(int h_dtype, int c_dtype, const void* k, const void* W, const int32_t* ta, const int32_t* tb,
                             int64_t m, int64_t na, int64_t nb, const void* c, int64_t K, void* sigma,
                             void* work, int64_t work_bytes, int64_t budget_bytes, void* stream);
+int qs_string_ci_sigma_sym_plan(int h_dtype, int c_dtype, int64_t m, int64_t n, int64_t K, int64_t budget_bytes,
+                                int64_t* plan, int64_t* bounds, int64_t bounds_len);
+int qs_string_ci_sigma_sym(int h_dtype, int c_dtype, const void* k, const void* W, const int32_t* t, int64_t m, int64_t n,
+                           int64_t parity, const void* c, int64_t K, void* sigma, void* work, int64_t work_bytes,
+                           int64_t budget_bytes, void* stream);
 int qs_string_ci_density1(int c_dtype, const int32_t* ta, const int32_t* tb, int64_t m, int64_t na, int64_t nb,
                           const void* bra, const void* ket, void* rho, void* work, int64_t work_bytes, void* stream);
 int64_t qs_string_ci_density2_workspace(int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes);

@@ -101,6 +101,8 @@ SIGNATURES = {
     "qs_string_ci_sigma": (c_int, [c_int, c_int] + [c_ptr] * 4 + [c_i64] * 3 + [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr]),
     "qs_string_ci_sigma_plan": (c_int, [c_int, c_int] + [c_i64] * 5 + [c_ptr]),
     "qs_string_ci_sigma_rows": (c_int, [c_int, c_int] + [c_ptr] * 4 + [c_i64] * 3 + [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i64, c_ptr]),
+    "qs_string_ci_sigma_sym_plan": (c_int, [c_int, c_int] + [c_i64] * 4 + [c_ptr, c_ptr, c_i64]),
+    "qs_string_ci_sigma_sym": (c_int, [c_int, c_int] + [c_ptr] * 3 + [c_i64] * 3 + [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i64, c_ptr]),
     "qs_string_ci_density1": (c_int, [c_int, c_ptr, c_ptr] + [c_i64] * 3 + [c_ptr] * 4 + [c_i64, c_ptr]),
     "qs_string_ci_density2_workspace": (c_i64, [c_int] + [c_i64] * 4),
     "qs_string_ci_density2_plan": (c_int, [c_int] + [c_i64] * 4 + [c_ptr]),

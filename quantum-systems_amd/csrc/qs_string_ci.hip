@@ -39,7 +39,7 @@ constexpr int kScRhoBlock = 256;      // threads of the density's and of the dia
 // Shipped byte budget of the D and G of one qs_string_ci_sigma call: qs_string_ci_group() splits a batch by it when
 // the caller passes 0 (kernels.STRING_CI_BYTES passes its own).  Not measured yet.  Also the budget of
 // the two panels of one pass of qs_string_ci_density2 and of the D_p and G_p of one pass of
-// qs_string_ci_sigma_rows.
+// qs_string_ci_sigma_rows and of qs_string_ci_sigma_sym (3.12).
 constexpr int64_t kScBytes = int64_t(2) << 30;
 
 struct ScArgs {
@@ -303,6 +303,205 @@ __global__ __launch_bounds__(kScBlock) void string_ci_fold_range_kernel(const Sc
     }
 }
 
+// ---- sigma on the lower triangle for c = tau c^T (qs_string_ci_sigma_sym) ------------------------------------------------
+// One table T and n strings for both spins, (P c)[Ia, Ib] = c[Ib, Ia], tau = +-1.  For c = tau P c every row D[(qs), k, :, :]
+// and with it G = W . D and X = G + k c have the parity tau in (Ka, Kb): the columns Kb <= Ka carry everything.  A packed row
+// Ka holds them at off(Ka) = Ka (Ka + 1) / 2; a pass owns the rows r0 <= Ka < r1, off(r1) - off(r0) elements per (qs) and
+// vector, row Ka at off(Ka) - off(r0).  c and sigma stay full (n, n).
+//   expand : D_p[(qs), k, off(Ka) - off(r0) + Kb] = sgn c_k[T[Ka,qs], Kb] + sgn c_k[Ka, T[Kb,qs]]            Kb <= Ka
+//   fold   : S_k[Ia, Ib] (+)= sum_pr ( w(Ja, Ib) sgn X[(pr), k, off(Ja) + Ib]     Ja = T[Ia,pr] in the pass, Ja >= Ib
+//                                    + w(Ia, Jb) sgn X[(pr), k, off(Ia) + Jb] )   Jb = T[Ib,pr], Ia in the pass, Jb <= Ia
+//            w(r, c) = 1 for r > c, 1/2 for r == c
+//   close  : sigma_k = S_k + tau S_k^T
+// The fold runs over the whole square and reads only stored elements: the terms it drops are tau times the kept terms of
+// the transposed element, and a diagonal element of X is met from both sides, hence the exact 1/2.  Its two reads are those
+// of the fold above -- contiguous over the lanes for alpha, a gather inside ONE packed row for beta --; nothing is strided by
+// n.  The order of one element's sum is pass ascending, pr ascending, alpha before beta.  The close makes
+// sigma[a, b] == tau sigma[b, a] hold bit for bit, with +0.0 on the diagonal for tau = -1.
+
+__host__ __device__ __forceinline__ int64_t sc_off(int64_t r) { return r * (r + 1) / 2; }
+
+template <int CW>
+__global__ __launch_bounds__(kScBlock) void string_ci_expand_tri_kernel(const ScArgs a, const int32_t* __restrict__ ta,
+                                                                       double* __restrict__ D, int64_t r0, int64_t r1) {
+    // the mapping of string_ci_expand_range_kernel; ta and D are arguments of their own for the reason given at
+    // string_ci_expand_kernel
+    extern __shared__ __attribute__((aligned(16))) int32_t sc_tb[];
+    const int B = blockDim.x, t = threadIdx.x, m2 = a.m2;
+    const int64_t ia = r0 + blockIdx.x / a.ntile;                         // uniform
+    const int64_t ib0 = (int64_t)(blockIdx.x % a.ntile) * B;
+    if (ib0 > ia) return;                                                 // uniform: the tile lies above the diagonal
+    const int64_t ib = ib0 + t, n = a.nb, dim = n * n, pdim = sc_off(r1) - sc_off(r0);
+    const int64_t at = sc_off(ia) - sc_off(r0) + ib;
+    const bool live = ib <= ia;                                           // the others only stage
+    const int32_t* __restrict__ ta_row = ta + ia * m2;
+    const double* __restrict__ c = a.c;
+    for (int pq0 = 0; pq0 < m2; pq0 += kScChunk) {
+        __syncthreads();
+        sc_stage(sc_tb, a.tb, ib0, n, pq0, m2);
+        __syncthreads();
+        if (!live) continue;
+        const int nj = m2 - pq0 < kScChunk ? m2 - pq0 : kScChunk;
+        for (int j = 0; j < nj; ++j) {
+            const int pq = pq0 + j;
+            const int32_t ea = ta_row[pq];                                // uniform address: a scalar load
+            const int32_t eb = sc_tb[j * (B + 1) + t];
+            const int64_t ja = ea ? sc_target(ea, n) : -1, jb = eb ? sc_target(eb, n) : -1;
+            for (int k = 0; k < a.K; ++k) {
+                const double* __restrict__ ck = c + (int64_t)k * dim * CW;        // the full vector
+                double v[CW];
+#pragma unroll
+                for (int w = 0; w < CW; ++w) v[w] = 0.0;
+                if (ja >= 0) {
+                    const double* x = ck + (ja * n + ib) * CW;
+#pragma unroll
+                    for (int w = 0; w < CW; ++w) v[w] = ea < 0 ? -x[w] : x[w];
+                }
+                if (jb >= 0) {
+                    const double* x = ck + (ia * n + jb) * CW;
+#pragma unroll
+                    for (int w = 0; w < CW; ++w) v[w] += eb < 0 ? -x[w] : x[w];
+                }
+                double* d = D + (((int64_t)pq * a.K + k) * pdim + at) * CW;
+#pragma unroll
+                for (int w = 0; w < CW; ++w) d[w] = v[w];
+            }
+        }
+    }
+}
+
+// acc += w s (g + kk c), w = 1/2 on the diagonal of X: the term s (g + kk c) through sc_feed from 0, which is exact, and the
+// weight a power of two, so the one rounding is that of the sum
+template <int HW, int CW>
+__device__ __forceinline__ void sc_feed_tri(double (&acc)[CW], const double (&kk)[HW], const double* __restrict__ g,
+                                            const double* __restrict__ c, bool minus, bool diagonal) {
+    double x[CW];
+#pragma unroll
+    for (int w = 0; w < CW; ++w) x[w] = 0.0;
+    sc_feed<HW, CW>(x, kk, g, c, minus);
+    const double wt = diagonal ? 0.5 : 1.0;
+#pragma unroll
+    for (int w = 0; w < CW; ++w) acc[w] = fma(wt, x[w], acc[w]);
+}
+
+template <int FORM>
+__global__ __launch_bounds__(kScBlock) void string_ci_fold_tri_kernel(const ScArgs a, const int32_t* __restrict__ ta,
+                                                                     double* __restrict__ sigma, int64_t r0, int64_t r1) {
+    constexpr int HW = form_widths(FORM).uw, CW = form_widths(FORM).aw;
+    extern __shared__ __attribute__((aligned(16))) int32_t sc_tb[];
+    const int B = blockDim.x, t = threadIdx.x, m2 = a.m2;
+    const unsigned row = blockIdx.x / a.ntile;                            // (k, ia), uniform
+    const int64_t k = row / (unsigned)a.na, ia = row % (unsigned)a.na;
+    const int64_t ib0 = (int64_t)(blockIdx.x % a.ntile) * B;
+    const int64_t ib = ib0 + t, n = a.nb, dim = n * n, base = sc_off(r0), pdim = sc_off(r1) - base;
+    const bool live = ib < n;
+    const int32_t* __restrict__ ta_row = ta + ia * m2;
+    const double* __restrict__ ck = a.c + k * dim * CW;
+    const double* __restrict__ kk = a.kk;
+    const double* __restrict__ Gk = a.G + k * pdim * CW;                  // X_p[(pr), k, :] = Gk + pr K pdim
+    double* __restrict__ out = sigma + (k * dim + ia * n + ib) * CW;
+    double acc[CW];
+#pragma unroll
+    for (int w = 0; w < CW; ++w) acc[w] = (r0 > 0 && live) ? out[w] : 0.0;        // the first pass never reads sigma
+    if (ia >= r0 && ia < r1) {                                            // uniform: the packed row Ia is in the pass
+        const int64_t own = sc_off(ia) - base;
+        for (int pr0 = 0; pr0 < m2; pr0 += kScChunk) {
+            __syncthreads();
+            sc_stage(sc_tb, a.tb, ib0, n, pr0, m2);
+            __syncthreads();
+            if (!live) continue;
+            const int nj = m2 - pr0 < kScChunk ? m2 - pr0 : kScChunk;
+            for (int j = 0; j < nj; ++j) {
+                const int pr = pr0 + j;
+                const int32_t ea = ta_row[pr];                            // uniform address: a scalar load
+                const int32_t eb = sc_tb[j * (B + 1) + t];
+                double kpr[HW];
+#pragma unroll
+                for (int w = 0; w < HW; ++w) kpr[w] = kk[pr * HW + w];
+                const double* __restrict__ g = Gk + (int64_t)pr * a.K * pdim * CW;
+                if (ea) {
+                    const int64_t ja = sc_target(ea, n);                  // -1 (past the list) is below every r0
+                    // uniform: the row Ja is in the pass and reaches the tile; per lane: the stored columns Ib <= Ja
+                    if (ja >= r0 && ja < r1 && ja >= ib0 && ja >= ib)
+                        sc_feed_tri<HW, CW>(acc, kpr, g + (sc_off(ja) - base + ib) * CW, ck + (ja * n + ib) * CW, ea < 0, ja == ib);
+                }
+                if (eb) {
+                    const int64_t jb = sc_target(eb, n);
+                    if (jb >= 0 && jb <= ia)
+                        sc_feed_tri<HW, CW>(acc, kpr, g + (own + jb) * CW, ck + (ia * n + jb) * CW, eb < 0, jb == ia);
+                }
+            }
+        }
+    } else if (live) {
+        // outside the pass: no beta term, no staging, no barrier; the alpha entries and their tests on the pass and on the
+        // tile are scalar
+        for (int pr = 0; pr < m2; ++pr) {
+            const int32_t ea = ta_row[pr];                                // uniform address: a scalar load
+            if (!ea) continue;
+            const int64_t ja = sc_target(ea, n);
+            if (ja < r0 || ja >= r1 || ja < ib0) continue;
+            if (ja < ib) continue;
+            double kpr[HW];
+#pragma unroll
+            for (int w = 0; w < HW; ++w) kpr[w] = kk[pr * HW + w];
+            const double* __restrict__ g = Gk + (int64_t)pr * a.K * pdim * CW;
+            sc_feed_tri<HW, CW>(acc, kpr, g + (sc_off(ja) - base + ib) * CW, ck + (ja * n + ib) * CW, ea < 0, ja == ib);
+        }
+    }
+    if (live) {
+#pragma unroll
+        for (int w = 0; w < CW; ++w) out[w] = acc[w];
+    }
+}
+
+constexpr int kScSymTile = 32;        // the close works on square tiles of 32 x 32 elements, 8 rows per sweep of the workgroup
+
+// sigma_k = S_k + tau S_k^T in place: one workgroup per vector and pair of mirrored tiles (ti, tj), tj <= ti.  Both tiles go
+// through LDS (rows padded by one element), so that every read and write of sigma runs along a row; a diagonal tile is its
+// own mirror image.  a + tau b and b + tau a are one rounding of the same sum: the two sides agree bit for bit.
+template <int CW>
+__global__ __launch_bounds__(kScRhoBlock) void string_ci_symmetrize_kernel(double* __restrict__ sigma, int64_t n, unsigned nt,
+                                                                           int minus) {
+    constexpr int TS = kScSymTile, RS = kScRhoBlock / kScSymTile;
+    __shared__ double lo[TS][TS + 1][CW], up[TS][TS + 1][CW];
+    const unsigned pair = blockIdx.x % (nt * nt);
+    const unsigned ti = pair / nt, tj = pair % nt;                        // uniform
+    if (tj > ti) return;
+    const bool mirror = ti != tj;
+    double* __restrict__ s = sigma + (int64_t)(blockIdx.x / (nt * nt)) * n * n * CW;
+    const int tx = threadIdx.x % TS, ty = threadIdx.x / TS;
+    const int64_t i0 = (int64_t)ti * TS, j0 = (int64_t)tj * TS;
+    for (int r = ty; r < TS; r += RS) {
+        if (i0 + r < n && j0 + tx < n) {
+#pragma unroll
+            for (int w = 0; w < CW; ++w) lo[r][tx][w] = s[((i0 + r) * n + j0 + tx) * CW + w];
+        }
+        if (mirror && j0 + r < n && i0 + tx < n) {
+#pragma unroll
+            for (int w = 0; w < CW; ++w) up[r][tx][w] = s[((j0 + r) * n + i0 + tx) * CW + w];
+        }
+    }
+    __syncthreads();
+    for (int r = ty; r < TS; r += RS) {
+        // the element (i0 + r, j0 + tx) and its mirror image (j0 + tx, i0 + r): loaded under the same two conditions
+        if (i0 + r < n && j0 + tx < n) {
+            const bool zero = !mirror && r == tx && minus;
+#pragma unroll
+            for (int w = 0; w < CW; ++w) {
+                const double x = lo[r][tx][w], y = mirror ? up[tx][r][w] : lo[tx][r][w];
+                s[((i0 + r) * n + j0 + tx) * CW + w] = zero ? 0.0 : (minus ? x - y : x + y);
+            }
+        }
+        if (mirror && j0 + r < n && i0 + tx < n) {
+#pragma unroll
+            for (int w = 0; w < CW; ++w) {
+                const double x = up[r][tx][w], y = lo[tx][r][w];
+                s[((j0 + r) * n + i0 + tx) * CW + w] = minus ? x - y : x + y;
+            }
+        }
+    }
+}
+
 // T[K, p * m + q] of one string list: one thread per entry (grid-stride).
 __global__ __launch_bounds__(kScRhoBlock) void string_ci_table_kernel(const int64_t* __restrict__ strings, int64_t n, int m,
                                                                       int32_t* __restrict__ table) {
@@ -455,6 +654,46 @@ static int sc_expand_range(int cw, const ScArgs& a, void* D, int64_t r0, int64_t
     else hipLaunchKernelGGL((string_ci_expand_range_kernel<2>), dim3(grid), dim3(threads), sc_lds(threads), s, a, a.ta, (double*)D, r0, r1);
     note_dispatch("qs::string_ci_expand_range_kernel<%d>", cw);
     return launch_status("string CI range expand launch");
+}
+
+// The passes of one qs_string_ci_sigma_sym call over the packed rows, fixed by its arguments and the calling thread's
+// string_ci_bytes alone: greedy from row 0, every pass as many rows as its D_p and G_p hold.
+struct ScTriPlan {
+    int64_t most;             // packed elements per (qs) and vector that a panel of half the budget holds
+    int64_t passes, longest;  // passes, the largest off(b_i+1) - off(b_i)
+    int64_t cols;             // columns of the largest product
+    int64_t panel;            // bytes of D_p (and of G_p) of the largest pass
+};
+
+// the end of the pass that starts at row b: the largest r <= n with off(r) - off(b) <= most, at least b + 1
+static int64_t sc_tri_next(int64_t b, int64_t n, int64_t most) {
+    int64_t lo = b + 1, hi = n;
+    while (lo < hi) {
+        const int64_t mid = lo + (hi - lo + 1) / 2;
+        if (sc_off(mid) - sc_off(b) <= most) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// bounds, where given, has room for the passes + 1 boundaries of a plan already known; the others stay within n + 1
+static ScTriPlan sc_tri_plan(int form, int64_t m, int64_t n, int64_t K, int64_t budget_bytes, int64_t* bounds, int64_t bounds_len) {
+    const int64_t budget = g_tune.string_ci_bytes > 0 ? g_tune.string_ci_bytes : (budget_bytes > 0 ? budget_bytes : kScBytes);
+    const int64_t per = m * m * K * 8 * form_widths(form).aw;             // bytes per packed element of a panel
+    ScTriPlan p{};
+    // 2 ceil16(x) <= budget  <=>  x <= the multiple of 16 at or below budget / 2
+    p.most = ((budget / 2) & ~int64_t(15)) / per;
+    for (int64_t b = 0; b < n; ++p.passes) {
+        if (bounds && p.passes < bounds_len) bounds[p.passes] = b;
+        const int64_t e = sc_tri_next(b, n, p.most), len = sc_off(e) - sc_off(b);
+        p.longest = len > p.longest ? len : p.longest;
+        b = e;
+    }
+    if (bounds && p.passes < bounds_len) bounds[p.passes] = n;
+    // longest <= off(n) <= n^2: sc_extents_ok has bounded the columns
+    p.cols = K * p.longest * (form == 2 ? 2 : 1);
+    p.panel = (per * p.longest + 15) & ~int64_t(15);
+    return p;
 }
 
 static unsigned sc_stride_grid(int64_t total) {
@@ -894,6 +1133,76 @@ int qs_string_ci_sigma_rows(int h_dtype, int c_dtype, const void* k, const void*
         if (rc) return rc;
     }
     return QS_OK;
+}
+
+int qs_string_ci_sigma_sym_plan(int h_dtype, int c_dtype, int64_t m, int64_t n, int64_t K, int64_t budget_bytes,
+                                int64_t* plan, int64_t* bounds, int64_t bounds_len) {
+    const int form = tensor_form(h_dtype, c_dtype);
+    if (form < 0) return form;
+    if (!sc_extents_ok(form, m, n, n, K) || budget_bytes < 0) return QS_ERR_BAD_EXTENT;
+    if (!plan) return QS_ERR_NULL_POINTER;
+    const ScTriPlan p = sc_tri_plan(form, m, n, K, budget_bytes, nullptr, 0);
+    if (bounds) {
+        if (bounds_len < p.passes + 1) return QS_ERR_BAD_EXTENT;
+        sc_tri_plan(form, m, n, K, budget_bytes, bounds, bounds_len);
+    }
+    plan[0] = p.passes; plan[1] = p.longest; plan[2] = p.cols; plan[3] = 2 * p.panel;
+    return QS_OK;
+}
+
+int qs_string_ci_sigma_sym(int h_dtype, int c_dtype, const void* k, const void* W, const int32_t* t, int64_t m, int64_t n,
+                           int64_t parity, const void* c, int64_t K, void* sigma, void* work, int64_t work_bytes,
+                           int64_t budget_bytes, void* stream) {
+    dispatch_reset();
+    const int form = tensor_form(h_dtype, c_dtype);
+    if (form < 0) return form;
+    if ((parity != 1 && parity != -1) || budget_bytes < 0 || !sc_extents_ok(form, m, n, n, K)) return QS_ERR_BAD_EXTENT;
+    if (!k || !W || !t || !c || !sigma || !work) return QS_ERR_NULL_POINTER;
+    const int64_t hs = (int64_t)elem_size(h_dtype), cs = (int64_t)elem_size(c_dtype);
+    if (!aligned(k, (size_t)hs) || !aligned(W, (size_t)hs) || !aligned(t, 4) || !aligned(c, (size_t)cs) ||
+        !aligned(sigma, (size_t)cs) || !aligned(work, 16))
+        return QS_ERR_MISALIGNED;
+    const ScTriPlan p = sc_tri_plan(form, m, n, K, budget_bytes, nullptr, 0);
+    const int64_t w_bytes = 2 * p.panel;
+    if (work_bytes < w_bytes) return QS_ERR_WORKSPACE;
+    const int64_t m2 = m * m, s_bytes = K * n * n * cs;
+    const struct { const void* at; int64_t bytes; } in[] = {{c, s_bytes}, {W, m2 * m2 * hs}, {k, m2 * hs}, {t, n * m2 * 4}};
+    for (const auto& x : in)
+        if (overlaps(sigma, s_bytes, x.at, x.bytes) || overlaps(work, w_bytes, x.at, x.bytes)) return QS_ERR_ALIAS;
+    if (overlaps(sigma, s_bytes, work, w_bytes)) return QS_ERR_ALIAS;
+
+    hipStream_t s = (hipStream_t)stream;
+    const FormWidths fw = form_widths(form);
+    char* D = (char*)work;
+    char* G = D + p.panel;
+    ScArgs a = sc_args(t, t, c, m, n, n, K);
+    a.kk = (const double*)k; a.G = (const double*)G;
+    const int threads = sc_threads(n);
+    const size_t lds = sc_lds(threads);
+    for (int64_t r0 = 0; r0 < n;) {
+        const int64_t r1 = sc_tri_next(r0, n, p.most), len = sc_off(r1) - sc_off(r0);
+        if (fw.aw == 1) hipLaunchKernelGGL((string_ci_expand_tri_kernel<1>), dim3((unsigned)((r1 - r0) * a.ntile)), dim3(threads), lds, s, a, t, (double*)D, r0, r1);
+        else hipLaunchKernelGGL((string_ci_expand_tri_kernel<2>), dim3((unsigned)((r1 - r0) * a.ntile)), dim3(threads), lds, s, a, t, (double*)D, r0, r1);
+        note_dispatch("qs::string_ci_expand_tri_kernel<%d>", fw.aw);
+        int rc = launch_status("string CI packed expand launch");
+        if (rc) return rc;
+        // real W against complex c: the re / im pairs of D_p are columns of a real product
+        rc = gemm(packed(h_dtype, W, D, G, m2, K * len * (fw.aw / fw.uw), m2), s);
+        if (rc) return rc;
+        with_form(form, [&](auto FORM) {
+            hipLaunchKernelGGL((string_ci_fold_tri_kernel<FORM>), dim3((unsigned)(K * n * a.ntile)), dim3(threads), lds, s, a, t,
+                               (double*)sigma, r0, r1);
+            note_dispatch("qs::string_ci_fold_tri_kernel<%d>", (int)FORM);
+        });
+        rc = launch_status("string CI packed fold launch");
+        if (rc) return rc;
+        r0 = r1;
+    }
+    const unsigned nt = (unsigned)cdiv(n, kScSymTile);
+    if (fw.aw == 1) hipLaunchKernelGGL((string_ci_symmetrize_kernel<1>), dim3((unsigned)K * nt * nt), dim3(kScRhoBlock), 0, s, (double*)sigma, n, nt, parity < 0 ? 1 : 0);
+    else hipLaunchKernelGGL((string_ci_symmetrize_kernel<2>), dim3((unsigned)K * nt * nt), dim3(kScRhoBlock), 0, s, (double*)sigma, n, nt, parity < 0 ? 1 : 0);
+    note_dispatch("qs::string_ci_symmetrize_kernel<%d>", fw.aw);
+    return launch_status("string CI symmetrise launch");
 }
 
 int qs_string_ci_density1(int c_dtype, const int32_t* ta, const int32_t* tb, int64_t m, int64_t na, int64_t nb,

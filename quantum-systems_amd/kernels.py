@@ -1080,6 +1080,97 @@ def string_ci_sigma(k, W, ta, tb, c, out=None):
     return out
 
 
+def _sym_plan(hcode, ccode, m, n, K, bounds=False):
+    """``(rc, plan, boundaries)`` of ``qs_string_ci_sigma_sym_plan``; the boundaries only where asked for."""
+    lib = _lib.load()
+    plan = (ctypes.c_int64 * 4)()
+    rc = lib.qs_string_ci_sigma_sym_plan(hcode, ccode, int(m), int(n), int(K), STRING_CI_BYTES, ctypes.addressof(plan), None, 0)
+    if rc or not bounds:
+        return rc, tuple(plan), None
+    cuts = (ctypes.c_int64 * (plan[0] + 1))()
+    rc = lib.qs_string_ci_sigma_sym_plan(hcode, ccode, int(m), int(n), int(K), STRING_CI_BYTES, ctypes.addressof(plan),
+                                         ctypes.addressof(cuts), len(cuts))
+    return rc, tuple(plan), tuple(cuts)
+
+
+def string_ci_sigma_sym_plan(m, n, c_dtype, K=1, h_dtype=None):
+    """``((passes, longest, columns, work_bytes), boundaries)`` of ``qs_string_ci_sigma_sym`` on ``K`` vectors (n, n) of
+    ``c_dtype`` (``h_dtype``: the dtype of ``k`` and ``W``, default the same) under ``STRING_CI_BYTES`` or the calling
+    thread's ``string_ci_bytes``: the passes over packed rows, the largest packed length ``off(b[i+1]) - off(b[i])`` with
+    ``off(r) = r (r + 1) / 2``, the columns of the largest product, the workspace bytes, and the ``passes + 1`` row
+    boundaries ``b``, greedy from row 0."""
+    hcode = dtype_code(c_dtype if h_dtype is None else h_dtype)
+    rc, plan, cuts = _sym_plan(hcode, dtype_code(c_dtype), m, n, K, bounds=True)
+    check(rc, "plan query")
+    return plan, cuts
+
+
+@_plain
+def string_ci_sigma_sym(k, W, t, c, parity, out=None):
+    """``sigma[j] = H c[j]`` for vectors of definite parity under the exchange of the two spins,
+    ``c[j] == parity * c[j].T`` with ``parity = +-1``, on ``qs_string_ci_sigma_sym``: ``c`` (K, n, n) or (n, n), ONE
+    table ``t`` (n, m^2) for both spins, ``k`` and ``W`` as for ``string_ci_sigma``.  Only the lower triangle of the
+    expanded intermediate is formed -- half of the expand, of the product and of the fold's gathers, half of the
+    workspace --, in passes over packed rows under ``STRING_CI_BYTES``; ``c`` and the result are full arrays, and the
+    result has the parity bit for bit.  The parity of ``c`` is NOT checked: for another ``c`` the result is
+    deterministic and unspecified (``StringCI.sigma`` symmetrises first).  All K vectors go in one call where their
+    plan is one pass; else, where one vector is one pass, in groups of the largest size whose plan is; else one vector
+    per call, for the reason given at ``string_ci_sigma``.  One ``dispatch_log`` entry names the kernels of the whole
+    call."""
+    lib = _lib.load()
+    if parity not in (1, -1):
+        raise ValueError(f"parity must be +1 or -1, got {parity!r}")
+    if not isinstance(c, torch.Tensor) or c.dim() not in (2, 3):
+        raise ValueError("c must be (K, n, n) or (n, n)")
+    hdt = result_dtype(k, W)
+    dt = result_dtype(k, W, c)
+    k, W, c = _dev(k, hdt), _dev(W, hdt), _dev(c, dt)
+    m = k.shape[-1]
+    if tuple(k.shape) != (m, m) or tuple(W.shape) != (m * m, m * m):
+        raise ValueError(f"need k (m, m) and W (m^2, m^2), got {tuple(k.shape)}, {tuple(W.shape)}")
+    t, _ = _string_tables(t, t, m)
+    single = c.dim() == 2
+    c3 = c[None] if single else c
+    K, n = c3.shape[0], t.shape[0]
+    if tuple(c3.shape[1:]) != (n, n) or K < 1:
+        raise ValueError(f"c has shape {tuple(c.shape)}: need (K, {n}, {n}) with K >= 1")
+    hcode, ccode = dtype_code(hdt), dtype_code(dt)
+
+    def one_pass(g):
+        rc, plan, _ = _sym_plan(hcode, ccode, m, n, g)
+        return rc == 0 and plan[0] == 1
+
+    check(_sym_plan(hcode, ccode, m, n, 1)[0], "plan query")              # the extents of one vector
+    group = 1
+    if one_pass(K):
+        group = K
+    elif one_pass(1):
+        lo, hi = 1, K                                                     # one_pass(lo) holds, one_pass(hi) does not
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            lo, hi = (mid, hi) if one_pass(mid) else (lo, mid)
+        group = lo
+    if out is None:
+        out = torch.empty(tuple(c.shape), dtype=dt, device=c.device)
+    else:
+        _check_out(out, tuple(c.shape), dt, "string_ci_sigma_sym")
+    o3 = out[None] if single else out
+    ran = []
+    with _on_device_of(k, W, t, c, out):
+        for k0 in range(0, K, group):
+            kg = min(group, K - k0)
+            rc, plan, _ = _sym_plan(hcode, ccode, m, n, kg)
+            check(rc, "plan query")
+            check(lib.qs_string_ci_sigma_sym(hcode, ccode, k.data_ptr(), W.data_ptr(), t.data_ptr(), m, n, int(parity),
+                                             c3[k0:k0 + kg].data_ptr(), kg, o3[k0:k0 + kg].data_ptr(),
+                                             *_work(plan[3], c.device), STRING_CI_BYTES, _stream()), "qs_string_ci_sigma_sym")
+            if dispatch_log is not None:
+                ran.append(lib.qs_last_dispatch().decode())
+    if dispatch_log is not None:
+        dispatch_log.append(" | ".join(ran))
+    return out
+
+
 @_plain
 def string_ci_density1(ta, tb, m, bra, ket, out=None):
     """Spin-summed ``rho[q, p] = <bra| E_pq |ket>`` (m, m) of two vectors (na, nb) on ``qs_string_ci_density1``: one

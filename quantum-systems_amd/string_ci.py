@@ -18,12 +18,19 @@ spin.  The lists are data (default: all of them); a replacement whose target str
     masks, v = ci.to_determinants(c[0])               # the same state in DeterminantCI's convention
     G = ci.two_body_density(0)                        # spin-summed, ci.energy_from_densities(0) == E[0]
     S2 = ci.spin_squared(0)                           # S (S + 1): which root is a singlet, which a triplet
+    ci = StringCI(system, C, spin_parity=+1)          # n_up == n_down: the states with c = +c^T, even S (singlets, ...)
+    E, c = ci.solve(n_roots=4)                        # spin_parity=-1: odd S (triplets, ...)
 
 A vector whose expanded intermediate is over ``kernels.STRING_CI_BYTES`` goes through sigma in passes over alpha rows,
 and its one-body quantities come from the pass-wise ``kernels.string_ci_density2``: the largest state is set by the
 vectors themselves.
 
-Out of scope here: spin-resolved two-body densities, a spin penalty or spin-adapted guesses in ``solve``, and a sharded
+With ``n_up == n_down`` and one string list for both spins the transposition ``(P c)[Ia, Ib] = c[Ib, Ia]`` commutes with
+``H`` and ``S^2``, and in this determinant convention a state of spin ``S`` has ``c = (-1)^S c^T``.  ``spin_parity = +-1``
+keeps ``solve`` inside that subspace -- the lowest singlets (and quintets, ...) or the lowest triplets alone -- and sends
+every ``H c`` through ``kernels.string_ci_sigma_sym``, which forms only the lower triangle of the intermediate.
+
+Out of scope here: spin-resolved two-body densities, full spin adaptation (``S = 0`` apart from ``S = 2``), and a sharded
 ``u``.
 """
 
@@ -102,9 +109,11 @@ class StringCI:
     """The lowest exact states of ``n_up`` alpha and ``n_down`` beta particles (default: ``system.n`` each) of a
     ``SpatialOrbitalSystem`` on the string lists ``strings_up`` x ``strings_down`` (default: all strings) in the
     orbitals ``C`` (l, m) with ``C^H s C = 1`` -- or, with ``C=None``, in the system's own basis, which must then be
-    orthonormal.  ``ht``, ``ut``, ``k``, ``W``, the replacement tables and the diagonal are built once, here."""
+    orthonormal.  ``ht``, ``ut``, ``k``, ``W``, the replacement tables and the diagonal are built once, here.
+    ``spin_parity`` = +1 or -1 (needs ``n_up == n_down`` and equal string lists) restricts ``sigma`` and ``solve`` to the
+    vectors with ``c = spin_parity * c^T``: the states of even or of odd spin ``S``."""
 
-    def __init__(self, system, C=None, n_up=None, n_down=None, strings_up=None, strings_down=None):
+    def __init__(self, system, C=None, n_up=None, n_down=None, strings_up=None, strings_down=None, spin_parity=None):
         if isinstance(system, GeneralOrbitalSystem):
             raise TypeError("StringCI works on spatial orbitals: a GeneralOrbitalSystem goes to DeterminantCI")
         if not isinstance(system, SpatialOrbitalSystem):
@@ -134,6 +143,12 @@ class StringCI:
             same = same or numpy.array_equal(self._sa_host, self._sb_host)
             self.na, self.nb = int(self._sa_host.shape[0]), int(self._sb_host.shape[0])
             self.dim = self.na * self.nb
+            if spin_parity is not None:
+                if spin_parity not in (1, -1):
+                    raise ValueError(f"spin_parity must be None, +1 or -1, got {spin_parity!r}")
+                if self.n_up != self.n_down or not same:
+                    raise ValueError("a spin parity needs n_up == n_down and the same string list for both spins")
+            self.spin_parity = None if spin_parity is None else int(spin_parity)
             self._dt = torch.complex128 if (C.is_complex() or u.is_complex() or h.is_complex()) else torch.float64
             self._C = C.to(self._dt).contiguous()
             ht = _dagger(self._C) @ h.to(self._dt) @ self._C
@@ -163,21 +178,79 @@ class StringCI:
 
     def sigma(self, c):
         """``H c_k`` (without the nuclear repulsion) for ``c`` (k, na, nb) or (na, nb), device tensor in and out; a
-        complex ``c`` on a real Hamiltonian keeps ``W`` real."""
+        complex ``c`` on a real Hamiltonian keeps ``W`` real.  Under a ``spin_parity`` tau it is ``H`` on the part of
+        ``c`` that has the parity, ``1/2 (c + tau c^T)``."""
         with torch._C.DisableTorchFunctionSubclass():
             c = _plain(c)
             if self._dt == torch.complex128:
                 c = c.to(self._dt)
+            if self.spin_parity is not None:
+                c = 0.5 * (c + self.spin_parity * c.transpose(-1, -2))
+                return kernels.string_ci_sigma_sym(self._k, self._W, self._ta, c, self.spin_parity)
             return kernels.string_ci_sigma(self._k, self._W, self._ta, self._tb, c)
 
     def _sigma_rows(self, V):
         return self.sigma(V.reshape(V.shape[0], self.na, self.nb)).reshape(V.shape[0], self.dim)
 
+    def _unpack(self, P):
+        """Full vectors (k, n, n) of packed ones (k, n (n + tau) / 2): the entries a > b scaled by sqrt 2 (an orthonormal
+        basis of the parity subspace), then the diagonal for tau = +1."""
+        n, tau = self.na, self.spin_parity
+        low = torch.ones(n, n, dtype=torch.bool, device=P.device).tril(-1)
+        pairs = n * (n - 1) // 2
+        c = torch.zeros(P.shape[0], n, n, dtype=P.dtype, device=P.device)
+        c[:, low] = P[:, :pairs] * (0.5 ** 0.5)
+        c = c + tau * c.transpose(1, 2)
+        if tau > 0:
+            c.diagonal(dim1=1, dim2=2).copy_(P[:, pairs:])
+        return c
+
+    def _pack(self, c):
+        n, tau = self.na, self.spin_parity
+        low = torch.ones(n, n, dtype=torch.bool, device=c.device).tril(-1)
+        parts = [c[:, low] * (2.0 ** 0.5)] + ([c.diagonal(dim1=1, dim2=2)] if tau > 0 else [])
+        return torch.cat(parts, dim=1)
+
+    def _sigma_packed(self, P):
+        c = self._unpack(P).contiguous()
+        return self._pack(kernels.string_ci_sigma_sym(self._k, self._W, self._ta, c, self.spin_parity))
+
+    def _solve_parity(self, n_roots, tol, max_iter, max_space):
+        n, tau = self.na, self.spin_parity
+        sub = n * (n + tau) // 2
+        if not 1 <= n_roots <= sub:
+            raise ValueError(f"n_roots = {n_roots} does not fit the {sub} dimensions of the subspace c = {tau:+d} c^T")
+        n_guess = min(sub, 2 * n_roots)
+        with torch._C.DisableTorchFunctionSubclass():
+            dev = self._diag.device
+            d = self._diag.reshape(n, n)                                # <I|H|I> is even under the exchange of the spins
+            low = torch.ones(n, n, dtype=torch.bool, device=dev).tril(-1)
+            diag = torch.cat([d[low]] + ([d.diagonal()] if tau > 0 else []))
+            order = torch.argsort(diag, stable=True)[:n_guess]
+            V = torch.zeros(n_guess, sub, dtype=self._dt, device=dev)
+            V[torch.arange(n_guess, device=dev), order] = 1.0
+            theta, X, info = block_davidson(self._sigma_packed, diag, V, n_roots, tol, max_iter, max_space)
+            c = self._unpack(X)
+            c = c / torch.linalg.vector_norm(c.reshape(n_roots, -1), dim=1)[:, None, None]
+        return theta, c.contiguous(), info
+
     def solve(self, n_roots, tol=1e-9, max_iter=100, max_space=None):
         """The ``n_roots`` lowest energies and their vectors by ``determinant_ci.block_davidson``: unit guesses on the
         ``min(dim, 2 n_roots)`` lowest diagonal elements.  Returns ``(E, c)`` in the system's array module, ``E``
         ascending and including the nuclear repulsion, ``c`` (n_roots, na, nb) of unit norm; sets ``converged``,
-        ``iterations``, ``residuals`` and ``sigma_history``."""
+        ``iterations``, ``residuals`` and ``sigma_history``.  Under a ``spin_parity`` tau the iteration runs unchanged in
+        packed coordinates of the subspace ``c = tau c^T`` (dimension ``n (n + tau) / 2``, the packed diagonal as
+        preconditioner): the lowest states of even (tau = +1) or odd (tau = -1) spin."""
+        if self.spin_parity is not None:
+            theta, c, info = self._solve_parity(n_roots, tol, max_iter, max_space)
+            with torch._C.DisableTorchFunctionSubclass():
+                self.converged, self.iterations = info["converged"], info["iterations"]
+                self.residuals, self.sigma_history = info["residuals"], info["sigma_history"]
+                self._c = c
+                E = theta + float(self.system.nuclear_repulsion_energy)
+                self.E = _deliver(E.contiguous(), self.system.np)
+                self.c = _deliver(self._c, self.system.np)
+            return self.E, self.c
         if not 1 <= n_roots <= self.dim:
             raise ValueError(f"n_roots = {n_roots} does not fit the {self.dim} determinants of the space")
         n_guess = min(self.dim, 2 * n_roots)
