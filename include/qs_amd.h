@@ -844,6 +844,33 @@ int qs_det_ci_density2(int c_dtype, const int64_t* dets, const void* bra, const 
  *       and the ket panel.  The budget bounds the panels (or is the panels of one
  *       alpha row when it is smaller); the partial results come on top and stay
  *       below an eighth of the panels wherever T > 1.
+ *   qs_string_ci_density2_spin : the spin-resolved densities of the same pair,
+ *       with E^s_pq = a+_ps a_qs on the strings of one spin (s, t = alpha, beta):
+ *         gamma_st[((p*m + q)*m + r)*m + s] = <bra| a+_ps a+_qt a_st a_rs |ket>
+ *                       = X^st[(pr),(qs)] - delta_st delta_qr <bra| E^s_ps |ket>,
+ *         X^st[(pr),(qs)] = sum_K conj((E^s_rp bra)[K]) (E^t_qs ket)[K],
+ *         rho_s[q * m + p] = <bra| E^s_pq |ket>
+ *       for st = aa, ab, bb; the beta-alpha block is gamma_ab[q,p,s,r] and is never
+ *       formed.  gamma_aa + gamma_bb + gamma_ab + gamma_ba and rho_a + rho_b are the
+ *       results of qs_string_ci_density2, and with the plain ut  <bra|H|ket> =
+ *       sum ht[p,q] (rho_a + rho_b)[q,p]
+ *       + 1/2 sum ut[p,q,r,s] (gamma_aa + gamma_bb + 2 gamma_ab)[p,q,r,s].
+ *       Passes, budget, slices and close as in qs_string_ci_density2, on panels
+ *       that keep the two replacements apart: with h = m^2 (fp64: rounded up to
+ *       even, the pad column zero) the ket panel is (K, 2 h) = E^a_qs ket | E^b_qs
+ *       ket, the bra panel (2 m^2 + 1, K) = conj(E^a_pq bra); conj(bra);
+ *       conj(E^b_pq bra).  Per pass two batched products over the T slices: rows
+ *       0 ... m^2 against all columns into part1[t] (m^2 + 1, 2 h), and the beta
+ *       rows against the beta columns into part2[t] (m^2, h).  Na = 0 or Nb = 0
+ *       (the list [0], a table of zeros) gives zero blocks.  No atomics: a repeated
+ *       call gives the same bits; another budget agrees to rounding.
+ *   qs_string_ci_density2_spin_plan : plan[0 ... 4] = alpha rows per pass, passes,
+ *       slices T, slice length kc, workspace bytes; T kc >= rows nb > (T - 1) kc.
+ *   qs_string_ci_density2_spin_workspace : bytes of `work` under that budget,
+ *         T ((m^2 + 1) 2 h + m^2 h) e + (2 m^2 + 1 + 2 h) T kc e:
+ *       part1, part2, the bra panel and the ket panel.  The budget bounds the
+ *       panels (or is the panels of one alpha row when it is smaller); the partial
+ *       results stay below an eighth of the panels wherever T > 1.
  *   qs_string_ci_spin_squared : out[k] = S^2 c[k] for c (K, na, nb),
  *         S^2 = S_z (S_z + 1) + N_beta - sum_pq E^alpha_qp E^beta_pq,
  *         S_z = (Na - Nb) / 2,
@@ -886,6 +913,11 @@ int qs_string_ci_density2_plan(int c_dtype, int64_t m, int64_t na, int64_t nb, i
 int qs_string_ci_density2(int c_dtype, const int32_t* ta, const int32_t* tb, int64_t m, int64_t na, int64_t nb,
                           const void* bra, const void* ket, void* gamma, void* rho, void* work, int64_t work_bytes,
                           int64_t budget_bytes, void* stream);
+int64_t qs_string_ci_density2_spin_workspace(int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes);
+int qs_string_ci_density2_spin_plan(int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes, int64_t* plan);
+int qs_string_ci_density2_spin(int c_dtype, const int32_t* ta, const int32_t* tb, int64_t m, int64_t na, int64_t nb,
+                               const void* bra, const void* ket, void* gamma_aa, void* gamma_ab, void* gamma_bb, void* rho_a,
+                               void* rho_b, void* work, int64_t work_bytes, int64_t budget_bytes, void* stream);
 int qs_string_ci_spin_squared(int c_dtype, const int32_t* ta, const int32_t* tb, int64_t m, int64_t na, int64_t nb,
                               int64_t Na, int64_t Nb, const void* c, int64_t K, void* out, void* stream);
 int qs_probe_mfma_f64(void* sink, int64_t blocks, int64_t iters, void* stream);

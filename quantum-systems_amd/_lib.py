@@ -107,6 +107,9 @@ SIGNATURES = {
     "qs_string_ci_density2_workspace": (c_i64, [c_int] + [c_i64] * 4),
     "qs_string_ci_density2_plan": (c_int, [c_int] + [c_i64] * 4 + [c_ptr]),
     "qs_string_ci_density2": (c_int, [c_int, c_ptr, c_ptr] + [c_i64] * 3 + [c_ptr] * 5 + [c_i64, c_i64, c_ptr]),
+    "qs_string_ci_density2_spin_workspace": (c_i64, [c_int] + [c_i64] * 4),
+    "qs_string_ci_density2_spin_plan": (c_int, [c_int] + [c_i64] * 4 + [c_ptr]),
+    "qs_string_ci_density2_spin": (c_int, [c_int, c_ptr, c_ptr] + [c_i64] * 3 + [c_ptr] * 8 + [c_i64, c_i64, c_ptr]),
     "qs_string_ci_spin_squared": (c_int, [c_int, c_ptr, c_ptr] + [c_i64] * 5 + [c_ptr, c_i64, c_ptr, c_ptr]),
 }
 

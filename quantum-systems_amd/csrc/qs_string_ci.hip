@@ -38,8 +38,8 @@ constexpr int kScBlock = 256;         // most beta strings (threads) of a workgr
 constexpr int kScRhoBlock = 256;      // threads of the density's and of the diagonal's workgroup
 // Shipped byte budget of the D and G of one qs_string_ci_sigma call: qs_string_ci_group() splits a batch by it when
 // the caller passes 0 (kernels.STRING_CI_BYTES passes its own).  Not measured yet.  Also the budget of
-// the two panels of one pass of qs_string_ci_density2 and of the D_p and G_p of one pass of
-// qs_string_ci_sigma_rows and of qs_string_ci_sigma_sym (3.12).
+// the two panels of one pass of qs_string_ci_density2 and of qs_string_ci_density2_spin (3.13), and of
+// the D_p and G_p of one pass of qs_string_ci_sigma_rows and of qs_string_ci_sigma_sym (3.12).
 constexpr int64_t kScBytes = int64_t(2) << 30;
 
 struct ScArgs {
@@ -946,19 +946,25 @@ static Sc2Plan sc2_layout(int cw, int64_t m, int64_t nb, int64_t rows) {
     return p;
 }
 
-static inline int64_t sc2_panel_bytes(const Sc2Plan& p) { return p.bytes - p.off_a; }
-
-static Sc2Plan sc2_plan(int cw, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes) {
+// The schedule of a pass-wise density: as many alpha rows per pass as keep the panels of `per_det` elements per determinant
+// within the budget (the calling thread's string_ci_bytes, else the argument, else the shipped one), at least one; then the
+// same passes of equal length where that costs no more.  layout(rows) carves the workspace; its panels lie behind off_a.
+template <class Layout>
+static auto sc2_schedule(int cw, int64_t na, int64_t nb, int64_t per_det, int64_t budget_bytes, Layout layout) {
     const int64_t budget = g_tune.string_ci_bytes > 0 ? g_tune.string_ci_bytes : (budget_bytes > 0 ? budget_bytes : kScBytes);
-    int64_t rows = budget / ((2 * m * m + 1) * nb * 8 * cw);
+    int64_t rows = budget / (per_det * nb * 8 * cw);
     rows = rows < 1 ? 1 : (rows < na ? rows : na);
-    Sc2Plan p = sc2_layout(cw, m, nb, rows);
-    while (p.rows > 1 && sc2_panel_bytes(p) > budget) p = sc2_layout(cw, m, nb, p.rows - 1);     // the padding of the slices
+    auto p = layout(rows);
+    while (p.rows > 1 && p.bytes - p.off_a > budget) p = layout(p.rows - 1);      // the padding of the slices
     const int64_t passes = cdiv(na, p.rows);
-    const Sc2Plan even = sc2_layout(cw, m, nb, cdiv(na, passes));         // the same passes, of equal length
-    if (sc2_panel_bytes(even) <= sc2_panel_bytes(p)) p = even;
+    const auto even = layout(cdiv(na, passes));                           // the same passes, of equal length
+    if (even.bytes - even.off_a <= p.bytes - p.off_a) p = even;
     p.passes = cdiv(na, p.rows);
     return p;
+}
+
+static Sc2Plan sc2_plan(int cw, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes) {
+    return sc2_schedule(cw, na, nb, 2 * m * m + 1, budget_bytes, [&](int64_t rows) { return sc2_layout(cw, m, nb, rows); });
 }
 
 static int sc2_check(int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes) {
@@ -975,6 +981,211 @@ static int sc2_expand(bool ket, const Sc2Args& a, const int32_t* ta, int64_t row
     else hipLaunchKernelGGL((string_ci_expand_rows_kernel<CW, false>), dim3(grid), dim3(threads), sc_lds(threads), s, a, ta, (double*)P);
     note_dispatch(ket ? "qs::string_ci_expand_rows_kernel<%d, true>" : "qs::string_ci_expand_rows_kernel<%d, false>", CW);
     return launch_status("string CI row expand launch");
+}
+
+// ---- spin-resolved densities (qs_string_ci_density2_spin) ----------------------------------------------------------------
+// E^s_pq = a+_ps a_qs acts on the strings of ONE spin: (E^a_pq c)[Ia, Ib] = sgn c[Ta[Ia,pq], Ib], (E^b_pq c)[Ia, Ib] =
+// sgn c[Ia, Tb[Ib,pq]].
+//   X^st[(pr),(qs)]   = <bra| E^s_pr E^t_qs |ket> = sum_K conj((E^s_rp bra)[K]) (E^t_qs ket)[K]
+//   Gamma^st[p,q,r,s] = <bra| a+_ps a+_qt a_st a_rs |ket> = X^st[(pr),(qs)] - delta_st delta_qr <bra| E^s_ps |ket>
+//   rho^s[q,p]        = <bra| E^s_pq |ket>
+// The two panels of the spin-summed density with the alpha and the beta replacement kept apart; h = m^2, for fp64 rounded
+// up to even so that every block below starts on a 16-byte boundary with an even leading dimension (the pad column holds
+// zeros and is never read by the close).  Per pass, K counting its determinants:
+//   ket panel B[K, 2 h]         : columns (qs) = E^a_qs ket, columns h + (qs) = E^b_qs ket
+//   bra panel A[2 m^2 + 1, K]   : rows (pq) = conj(E^a_pq bra), row m^2 = conj(bra), rows m^2 + 1 + (pq) = conj(E^b_pq bra)
+//   part1[t] (m^2 + 1, 2 h) (+)= A[0 ... m^2, slice t] . B[slice t, :]           X^aa | X^ab, last row <E^a_qs> | <E^b_qs>
+//   part2[t] (m^2, h)       (+)= A[m^2 + 1 ..., slice t] . B[slice t, h ...]     X^bb
+// The beta-alpha block is never formed: Gamma^ba[p,q,r,s] = Gamma^ab[q,p,s,r].  The close is that of the spin sum.
+
+struct Sc3Args {
+    const int32_t* tb;        // (nb, m^2)
+    const double* c;          // (na, nb): bra or ket
+    int64_t na, nb;
+    int64_t ia0;              // first alpha row of the pass
+    int64_t pitch;            // elements between rows of the bra panel, T kc
+    unsigned ntile;
+    int m2, h;                // h: columns of one spin in the ket panel
+};
+
+// (E^s_pq c)[Ia, Ib] of one spin from its table entry e: a signed copy, or 0
+template <int CW>
+__device__ __forceinline__ void sc_replaced_spin(double (&v)[CW], const double* __restrict__ c, int32_t e, bool beta, int64_t ia,
+                                                 int64_t ib, int64_t na, int64_t nb) {
+    const int64_t jt = e ? sc_target(e, beta ? nb : na) : -1;
+#pragma unroll
+    for (int w = 0; w < CW; ++w) v[w] = 0.0;
+    if (jt >= 0) {
+        const double* x = c + (beta ? ia * nb + jt : jt * nb + ib) * CW;
+#pragma unroll
+        for (int w = 0; w < CW; ++w) v[w] = e < 0 ? -x[w] : x[w];
+    }
+}
+
+// The mapping of string_ci_expand_rows_kernel.  A thread keeps the 16 values of one table chunk of ONE spin: alpha, written
+// out, then beta.  KET: both are runs of whole 16-byte stores in the determinant's line (the line, the beta half and the
+// chunk all start on even columns).  Otherwise the rows of the bra panel, conjugated, written as they are formed, and
+// conj(c) as row m^2.
+template <int CW, bool KET>
+__global__ __launch_bounds__(kScBlock) void string_ci_expand_spin_kernel(const Sc3Args a, const int32_t* __restrict__ ta,
+                                                                        double* __restrict__ P) {
+    extern __shared__ __attribute__((aligned(16))) int32_t sc_tb[];
+    const int B = blockDim.x, t = threadIdx.x, m2 = a.m2, h = a.h;
+    const int64_t il = blockIdx.x / a.ntile;                              // uniform
+    const int64_t ia = a.ia0 + il;
+    const int64_t ib0 = (int64_t)(blockIdx.x % a.ntile) * B;
+    const int64_t ib = ib0 + t, nb = a.nb;
+    const bool live = ib < nb;
+    const int64_t kl = il * nb + ib;
+    const int32_t* __restrict__ ta_row = ta + ia * m2;
+    const double* __restrict__ c = a.c;
+    for (int pq0 = 0; pq0 < m2; pq0 += kScChunk) {
+        __syncthreads();
+        sc_stage(sc_tb, a.tb, ib0, nb, pq0, m2);
+        __syncthreads();
+        if (!live) continue;
+#pragma unroll
+        for (int spin = 0; spin < 2; ++spin) {
+            if constexpr (KET) {
+                double v[kScChunk][CW];
+#pragma unroll
+                for (int j = 0; j < kScChunk; ++j) {
+                    const int pq = pq0 + j;
+                    // alpha: a uniform address, a scalar load; past m^2 (uniform) the pad column, zero
+                    const int32_t e = pq < m2 ? (spin == 0 ? ta_row[pq] : sc_tb[j * (B + 1) + t]) : 0;
+                    sc_replaced_spin<CW>(v[j], c, e, spin != 0, ia, ib, a.na, nb);
+                }
+                double* line = P + ((kl * 2 + spin) * h + pq0) * CW;
+#pragma unroll
+                for (int j = 0; j < kScChunk; j += 2 / CW) {
+                    if (pq0 + j < h) {                                    // h is even for fp64: the pairs are whole
+                        double2 x;
+                        if constexpr (CW == 2) { x.x = v[j][0]; x.y = v[j][CW - 1]; }
+                        else { x.x = v[j][0]; x.y = v[j + 2 / CW - 1][0]; }
+                        *reinterpret_cast<double2*>(line + j * CW) = x;
+                    }
+                }
+            } else {
+                // a row per column: nothing is kept, four columns in flight
+                const int nj = m2 - pq0 < kScChunk ? m2 - pq0 : kScChunk;
+#pragma unroll 4
+                for (int j = 0; j < nj; ++j) {
+                    const int32_t e = spin == 0 ? ta_row[pq0 + j] : sc_tb[j * (B + 1) + t];
+                    double v[CW];
+                    sc_replaced_spin<CW>(v, c, e, spin != 0, ia, ib, a.na, nb);
+                    double* d = P + ((int64_t)(spin * (m2 + 1) + pq0 + j) * a.pitch + kl) * CW;
+                    d[0] = v[0];
+                    if constexpr (CW == 2) d[CW - 1] = -v[CW - 1];
+                }
+            }
+        }
+    }
+    if constexpr (!KET) {
+        if (live) {
+            const double* x = c + (ia * nb + ib) * CW;
+            double* d = P + ((int64_t)m2 * a.pitch + kl) * CW;
+            d[0] = x[0];
+            if constexpr (CW == 2) d[CW - 1] = -x[CW - 1];
+        }
+    }
+}
+
+// x = sum over t of part[t * stride + at], ascending
+template <int CW>
+__device__ __forceinline__ void sc_sum_partials(double (&x)[CW], const double* __restrict__ part, int64_t T, int64_t stride,
+                                                int64_t at) {
+#pragma unroll
+    for (int w = 0; w < CW; ++w) x[w] = 0.0;
+    for (int64_t t = 0; t < T; ++t) {
+#pragma unroll
+        for (int w = 0; w < CW; ++w) x[w] += part[(t * stride + at) * CW + w];
+    }
+}
+
+// The three Gamma and the two rho from the partial results part1[t] (m^2 + 1, 2 h) and part2[t] (m^2, h): one thread per
+// element of a Gamma (grid-stride over the 3 m^4 of them, alpha-alpha, alpha-beta, beta-beta), X read at the transposed row
+// (rp), the delta term for equal spins only.
+template <int CW>
+__global__ __launch_bounds__(kScRhoBlock) void string_ci_gamma_spin_close_kernel(const double* __restrict__ part1,
+                                                                                 const double* __restrict__ part2, int64_t T, int m,
+                                                                                 int h, double* __restrict__ gaa,
+                                                                                 double* __restrict__ gab, double* __restrict__ gbb,
+                                                                                 double* __restrict__ rho_a, double* __restrict__ rho_b) {
+    const int64_t m2 = (int64_t)m * m, total = m2 * m2, s1 = (m2 + 1) * 2 * h, s2 = m2 * h, step = (int64_t)gridDim.x * kScRhoBlock;
+    for (int64_t idx = (int64_t)blockIdx.x * kScRhoBlock + threadIdx.x; idx < 3 * total; idx += step) {
+        const int blk = (int)(idx / total);                               // 0: aa, 1: ab, 2: bb
+        const int64_t el = idx % total;
+        const int s = (int)(el % m), r = (int)((el / m) % m), q = (int)((el / m2) % m), p = (int)(el / (m2 * m));
+        const int64_t row = (int64_t)r * m + p, col = (int64_t)q * m + s;
+        const int64_t last = m2 * 2 * h + (blk == 2 ? h : 0);             // <bra| E^s_.. |ket> of the block's spin, in part1
+        double x[CW];
+        if (blk == 2) sc_sum_partials<CW>(x, part2, T, s2, row * h + col);
+        else sc_sum_partials<CW>(x, part1, T, s1, row * 2 * h + (blk == 1 ? h : 0) + col);
+        if (blk != 1 && q == r) {
+            double e[CW];
+            sc_sum_partials<CW>(e, part1, T, s1, last + p * m + s);
+#pragma unroll
+            for (int w = 0; w < CW; ++w) x[w] = x[w] - e[w];
+        }
+        double* __restrict__ gamma = blk == 0 ? gaa : (blk == 1 ? gab : gbb);
+#pragma unroll
+        for (int w = 0; w < CW; ++w) gamma[el * CW + w] = x[w];
+        if (blk != 1 && r == 0 && s == 0) {
+            double e[CW];
+            sc_sum_partials<CW>(e, part1, T, s1, last + p * m + q);
+            double* __restrict__ rho = blk == 0 ? rho_a : rho_b;
+#pragma unroll
+            for (int w = 0; w < CW; ++w) rho[((int64_t)q * m + p) * CW + w] = e[w];
+        }
+    }
+}
+
+// The schedule and the workspace of one qs_string_ci_density2_spin call: the one place that carves it.
+struct Sc3Plan {
+    int64_t rows, passes;     // alpha rows per pass (the last pass may have fewer), passes
+    int64_t T, kc, pitch;     // slices of kc determinants per pass, pitch = T kc >= rows nb
+    int64_t h;                // columns of one spin in the ket panel
+    int64_t off_2;            // byte offset of part2 behind part1 at 0
+    int64_t off_a, off_b;     // byte offsets of the bra and ket panels
+    int64_t bytes;
+};
+
+static inline int64_t sc3_half(int cw, int64_t m) { return cw == 1 ? (m * m + 1) & ~int64_t(1) : m * m; }
+
+static Sc3Plan sc3_layout(int cw, int64_t m, int64_t nb, int64_t rows) {
+    const int64_t m2 = m * m, es = 8 * cw, R = rows * nb;
+    Sc3Plan p{};
+    p.rows = rows;
+    p.h = sc3_half(cw, m);
+    // slices: tiles of the first product x T covers the compute units, the partial results (3 h (m^2 + 1) at the most per
+    // slice) stay below an eighth of the panels (more than 4 m^2 R)
+    int64_t T = cdiv(kSc2Cus, cdiv(m2 + 1, 128) * cdiv(2 * p.h, 128));
+    const int64_t cap = (4 * m2 * R) / (24 * p.h * (m2 + 1));
+    T = T < cap ? T : cap;
+    T = T < 1 ? 1 : T;
+    p.kc = (cdiv(R, T) + 1) & ~int64_t(1);                               // even: every slice starts on a 16-byte boundary
+    p.T = cdiv(R, p.kc);
+    p.pitch = p.T * p.kc;
+    p.off_2 = p.T * (m2 + 1) * 2 * p.h * es;                              // 2 h is even
+    p.off_a = p.off_2 + p.T * m2 * p.h * es;                              // h or the element size is even
+    p.off_b = p.off_a + (2 * m2 + 1) * p.pitch * es;                      // pitch is even
+    p.bytes = p.off_b + p.pitch * 2 * p.h * es;
+    return p;
+}
+
+static Sc3Plan sc3_plan(int cw, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes) {
+    return sc2_schedule(cw, na, nb, 2 * m * m + 1 + 2 * sc3_half(cw, m), budget_bytes,
+                        [&](int64_t rows) { return sc3_layout(cw, m, nb, rows); });
+}
+
+template <int CW>
+static int sc3_expand(bool ket, const Sc3Args& a, const int32_t* ta, int64_t rows, void* P, hipStream_t s) {
+    const int threads = sc_threads(a.nb);
+    const unsigned grid = (unsigned)(rows * a.ntile);
+    if (ket) hipLaunchKernelGGL((string_ci_expand_spin_kernel<CW, true>), dim3(grid), dim3(threads), sc_lds(threads), s, a, ta, (double*)P);
+    else hipLaunchKernelGGL((string_ci_expand_spin_kernel<CW, false>), dim3(grid), dim3(threads), sc_lds(threads), s, a, ta, (double*)P);
+    note_dispatch(ket ? "qs::string_ci_expand_spin_kernel<%d, true>" : "qs::string_ci_expand_spin_kernel<%d, false>", CW);
+    return launch_status("string CI spin-resolved expand launch");
 }
 
 }  // namespace qs
@@ -1309,6 +1520,98 @@ int qs_string_ci_density2(int c_dtype, const int32_t* ta, const int32_t* tb, int
         hipLaunchKernelGGL((string_ci_gamma_close_kernel<2>), dim3(grid), dim3(kScRhoBlock), 0, s, (const double*)part, p.T, (int)m, (double*)gamma, (double*)rho);
     note_dispatch("qs::string_ci_gamma_close_kernel<%d>", cw);
     return launch_status("string CI two-body density close launch");
+}
+
+int64_t qs_string_ci_density2_spin_workspace(int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes) {
+    const int rc = sc2_check(c_dtype, m, na, nb, budget_bytes);
+    if (rc) return rc;
+    return sc3_plan(c_dtype == QS_C128 ? 2 : 1, m, na, nb, budget_bytes).bytes;
+}
+
+int qs_string_ci_density2_spin_plan(int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes, int64_t* plan) {
+    const int rc = sc2_check(c_dtype, m, na, nb, budget_bytes);
+    if (rc) return rc;
+    if (!plan) return QS_ERR_NULL_POINTER;
+    const Sc3Plan p = sc3_plan(c_dtype == QS_C128 ? 2 : 1, m, na, nb, budget_bytes);
+    plan[0] = p.rows; plan[1] = p.passes; plan[2] = p.T; plan[3] = p.kc; plan[4] = p.bytes;
+    return QS_OK;
+}
+
+int qs_string_ci_density2_spin(int c_dtype, const int32_t* ta, const int32_t* tb, int64_t m, int64_t na, int64_t nb,
+                               const void* bra, const void* ket, void* gamma_aa, void* gamma_ab, void* gamma_bb, void* rho_a,
+                               void* rho_b, void* work, int64_t work_bytes, int64_t budget_bytes, void* stream) {
+    dispatch_reset();
+    int rc = sc2_check(c_dtype, m, na, nb, budget_bytes);
+    if (rc) return rc;
+    if (!ta || !tb || !bra || !ket || !gamma_aa || !gamma_ab || !gamma_bb || !rho_a || !rho_b || !work) return QS_ERR_NULL_POINTER;
+    const int64_t cs = (int64_t)elem_size(c_dtype);
+    if (!aligned(ta, 4) || !aligned(tb, 4) || !aligned(bra, (size_t)cs) || !aligned(ket, (size_t)cs) || !aligned(gamma_aa, (size_t)cs) ||
+        !aligned(gamma_ab, (size_t)cs) || !aligned(gamma_bb, (size_t)cs) || !aligned(rho_a, (size_t)cs) || !aligned(rho_b, (size_t)cs) ||
+        !aligned(work, 16))
+        return QS_ERR_MISALIGNED;
+    const int cw = c_dtype == QS_C128 ? 2 : 1;
+    const Sc3Plan p = sc3_plan(cw, m, na, nb, budget_bytes);
+    if (work_bytes < p.bytes) return QS_ERR_WORKSPACE;
+    const int64_t m2 = m * m, g_bytes = m2 * m2 * cs, r_bytes = m2 * cs, v_bytes = na * nb * cs;
+    const struct { const void* at; int64_t bytes; } in[] = {{bra, v_bytes}, {ket, v_bytes}, {ta, na * m2 * 4}, {tb, nb * m2 * 4}};
+    // the workspace, then the five outputs: each against every input and against those before it
+    const struct { const void* at; int64_t bytes; } out[] = {{work, p.bytes}, {gamma_aa, g_bytes}, {gamma_ab, g_bytes}, {gamma_bb, g_bytes},
+                                                             {rho_a, r_bytes}, {rho_b, r_bytes}};
+    for (int i = 0; i < 6; ++i) {
+        for (const auto& x : in)
+            if (overlaps(out[i].at, out[i].bytes, x.at, x.bytes)) return QS_ERR_ALIAS;
+        for (int j = 0; j < i; ++j)
+            if (overlaps(out[i].at, out[i].bytes, out[j].at, out[j].bytes)) return QS_ERR_ALIAS;
+    }
+
+    hipStream_t s = (hipStream_t)stream;
+    char* part1 = (char*)work;
+    char* part2 = part1 + p.off_2;
+    char* A = part1 + p.off_a;
+    char* B = part1 + p.off_b;
+    const int64_t h = p.h;
+    Sc3Args a{};
+    a.tb = tb; a.na = na; a.nb = nb; a.pitch = p.pitch; a.m2 = (int)m2; a.h = (int)h;
+    a.ntile = (unsigned)cdiv(nb, sc_threads(nb));
+    for (int64_t pass = 0; pass < p.passes; ++pass) {
+        a.ia0 = pass * p.rows;
+        const int64_t rows = na - a.ia0 < p.rows ? na - a.ia0 : p.rows, R = rows * nb;
+        if (R < p.pitch) {
+            // the tail of the last slice, and of a ragged last pass: zeros in both operands
+            rc = hip_status(hipMemset2DAsync(A + R * cs, (size_t)(p.pitch * cs), 0, (size_t)((p.pitch - R) * cs), (size_t)(2 * m2 + 1), s),
+                            "string CI spin-resolved bra panel tail");
+            if (rc) return rc;
+            rc = hip_status(hipMemsetAsync(B + R * 2 * h * cs, 0, (size_t)((p.pitch - R) * 2 * h * cs), s),
+                            "string CI spin-resolved ket panel tail");
+            if (rc) return rc;
+        }
+        a.c = (const double*)bra;
+        rc = cw == 1 ? sc3_expand<1>(false, a, ta, rows, A, s) : sc3_expand<2>(false, a, ta, rows, A, s);
+        if (rc) return rc;
+        a.c = (const double*)ket;
+        rc = cw == 1 ? sc3_expand<1>(true, a, ta, rows, B, s) : sc3_expand<2>(true, a, ta, rows, B, s);
+        if (rc) return rc;
+        // split-k as a batch over the T slices, as in qs_string_ci_density2; every pass adds into the same partials.
+        // alpha rows and conj(bra) against all ket columns: X^aa | X^ab, and <E^a_qs> | <E^b_qs> in the last row
+        rc = gemm(Product{c_dtype, (const double*)A, (const double*)B, (double*)part1, m2 + 1, 2 * h, p.kc, p.pitch, 2 * h, 2 * h, p.T,
+                          p.kc, p.kc * 2 * h, (m2 + 1) * 2 * h, pass > 0 ? 1 : 0},
+                  s);
+        if (rc) return rc;
+        // beta rows against the beta columns: X^bb
+        rc = gemm(Product{c_dtype, (const double*)(A + (m2 + 1) * p.pitch * cs), (const double*)(B + h * cs), (double*)part2, m2, h, p.kc,
+                          p.pitch, 2 * h, h, p.T, p.kc, p.kc * 2 * h, m2 * h, pass > 0 ? 1 : 0},
+                  s);
+        if (rc) return rc;
+    }
+    const unsigned grid = sc_stride_grid(3 * m2 * m2);
+    if (cw == 1)
+        hipLaunchKernelGGL((string_ci_gamma_spin_close_kernel<1>), dim3(grid), dim3(kScRhoBlock), 0, s, (const double*)part1, (const double*)part2,
+                           p.T, (int)m, (int)h, (double*)gamma_aa, (double*)gamma_ab, (double*)gamma_bb, (double*)rho_a, (double*)rho_b);
+    else
+        hipLaunchKernelGGL((string_ci_gamma_spin_close_kernel<2>), dim3(grid), dim3(kScRhoBlock), 0, s, (const double*)part1, (const double*)part2,
+                           p.T, (int)m, (int)h, (double*)gamma_aa, (double*)gamma_ab, (double*)gamma_bb, (double*)rho_a, (double*)rho_b);
+    note_dispatch("qs::string_ci_gamma_spin_close_kernel<%d>", cw);
+    return launch_status("string CI spin-resolved density close launch");
 }
 
 int qs_string_ci_spin_squared(int c_dtype, const int32_t* ta, const int32_t* tb, int64_t m, int64_t na, int64_t nb,

@@ -949,7 +949,8 @@ def det_ci_density2(dets, bra, ket, m, N, out=None):
 # Byte budget of the D and G panels of ONE qs_string_ci_sigma call: ``string_ci_sigma`` sends a batch in groups of as
 # many vectors as fit it, and where one vector alone is over it, in passes over as many alpha rows of that vector's D
 # and G as fit it (``qs_string_ci_sigma_rows``, at least one row); also of the two panels of one pass of
-# ``string_ci_density2``, which takes as many alpha rows per pass as fit it (at least one).  The tuning key
+# ``string_ci_density2`` and of ``string_ci_density2_spin``, which take as many alpha rows per pass as fit it (at least
+# one).  The tuning key
 # ``string_ci_bytes`` overrides it for the calling thread.
 STRING_CI_BYTES = 2 << 30
 
@@ -1238,6 +1239,54 @@ def string_ci_density2(ta, tb, m, bra, ket, out=None):
             "qs_string_ci_density2",
         )
     return gamma, rho
+
+
+def string_ci_density2_spin_plan(m, na, nb, c_dtype):
+    """``(rows, passes, T, kc, work_bytes)`` of ``qs_string_ci_density2_spin`` on vectors of ``c_dtype`` under
+    ``STRING_CI_BYTES`` or the calling thread's ``string_ci_bytes``: alpha rows per pass, passes, slices of ``kc``
+    determinants per pass, workspace bytes."""
+    plan = (ctypes.c_int64 * 5)()
+    check(_lib.load().qs_string_ci_density2_spin_plan(dtype_code(c_dtype), int(m), int(na), int(nb), STRING_CI_BYTES,
+                                                      ctypes.addressof(plan)), "qs_string_ci_density2_spin_plan")
+    return tuple(int(x) for x in plan)
+
+
+@_plain
+def string_ci_density2_spin(ta, tb, m, bra, ket, out=None):
+    """``(gamma_aa, gamma_ab, gamma_bb, rho_a, rho_b)`` of two vectors (na, nb) on ``qs_string_ci_density2_spin``: the
+    spin-resolved two-body densities ``gamma_st[p, q, r, s] = <bra| a+_ps a+_qt a_st a_rs |ket>`` (m, m, m, m) and the
+    one-body densities ``rho_s[q, p] = <bra| a+_ps a_qs |ket>`` (m, m) from the same passes; ``bra is ket`` is a state.
+    The beta-alpha block is ``gamma_ab.permute(1, 0, 3, 2)``; the four blocks add up to ``string_ci_density2``'s
+    ``gamma``, the two ``rho`` to its ``rho``.  Passes and budget as there (``STRING_CI_BYTES``, tuning key
+    ``string_ci_bytes``); every pass is two batched products on the product dispatcher.  ``out`` is a 5-tuple of
+    buffers.  Repeating a call gives the same bits; another budget agrees to rounding."""
+    lib = _lib.load()
+    m = int(m)
+    ta, tb = _string_tables(ta, tb, m)
+    dt = result_dtype(bra, ket)
+    same = bra is ket
+    bra = _dev(bra, dt)
+    ket = bra if same else _dev(ket, dt)
+    na, nb = ta.shape[0], tb.shape[0]
+    if tuple(bra.shape) != (na, nb) or tuple(ket.shape) != (na, nb):
+        raise ValueError(f"bra and ket have shapes {tuple(bra.shape)}, {tuple(ket.shape)}: need ({na}, {nb}) each")
+    code = dtype_code(dt)
+    nbytes = check(lib.qs_string_ci_density2_spin_workspace(code, m, na, nb, STRING_CI_BYTES), "workspace query")
+    shapes = ((m, m, m, m),) * 3 + ((m, m),) * 2
+    if out is None:
+        out = tuple(torch.empty(shape, dtype=dt, device=bra.device) for shape in shapes)
+    else:
+        if not isinstance(out, (tuple, list)) or len(out) != 5:
+            raise ValueError("string_ci_density2_spin: `out` must be a 5-tuple (gamma_aa, gamma_ab, gamma_bb, rho_a, rho_b)")
+        out = tuple(_check_out(o, shape, dt, "string_ci_density2_spin") for o, shape in zip(out, shapes))
+    with _on_device_of(ta, tb, bra, ket, *out):
+        _ran(
+            lib.qs_string_ci_density2_spin(code, ta.data_ptr(), tb.data_ptr(), m, na, nb, bra.data_ptr(), ket.data_ptr(),
+                                           *(o.data_ptr() for o in out), *_work(nbytes, bra.device), STRING_CI_BYTES,
+                                           _stream()),
+            "qs_string_ci_density2_spin",
+        )
+    return out
 
 
 @_plain

@@ -30,8 +30,14 @@ With ``n_up == n_down`` and one string list for both spins the transposition ``(
 keeps ``solve`` inside that subspace -- the lowest singlets (and quintets, ...) or the lowest triplets alone -- and sends
 every ``H c`` through ``kernels.string_ci_sigma_sym``, which forms only the lower triangle of the intermediate.
 
-Out of scope here: spin-resolved two-body densities, full spin adaptation (``S = 0`` apart from ``S = 2``), and a sharded
-``u``.
+Where the up and the down particles are comes from ``kernels.string_ci_density2_spin``, the same passes with the alpha and
+the beta replacement kept apart:
+
+    rho_a, rho_b = ci.one_body_density_spin(0)        # rho_a + rho_b == ci.one_body_density(0)
+    Gaa, Gab, Gbb = ci.two_body_density_spin(0)       # Gamma^ba[p,q,r,s] = Gab[q,p,s,r]; the four add up to G
+    M = ci.pair_density_matrix(phi0, 0, spins="ab")   # up density given a down particle where the orbitals take phi0
+
+Out of scope here: full spin adaptation (``S = 0`` apart from ``S = 2``) and a sharded ``u``.
 """
 
 import numpy
@@ -315,6 +321,72 @@ class StringCI:
             gamma, rho = kernels.string_ci_density2(self._ta, self._tb, self.m, *self._pair(k))
             e = (self._ht * rho.transpose(0, 1)).sum() + 0.5 * (self._ut * gamma).sum()
             return float(e.real.item()) + float(self.system.nuclear_repulsion_energy)
+
+    def _spin_blocks(self, k, l=None):
+        return kernels.string_ci_density2_spin(self._ta, self._tb, self.m, *self._pair(k, l))
+
+    def one_body_density_spin(self, k=0, l=None):
+        """``(rho_a, rho_b)``, ``rho_s[q, p] = <c_k| a+_ps a_qs |c_l>`` (``l`` defaults to ``k``) in the orbitals ``C``, each
+        in the index order of ``one_body_density``; they add up to it."""
+        with torch._C.DisableTorchFunctionSubclass():
+            blocks = self._spin_blocks(k, l)
+        return tuple(_deliver(x, self.system.np) for x in blocks[3:])
+
+    def spin_density(self, k=0):
+        """``rho_a - rho_b`` of solved state ``k``, in the index order ``system.compute_particle_density(rho, C=C)``
+        takes; its trace is ``n_up - n_down``."""
+        with torch._C.DisableTorchFunctionSubclass():
+            blocks = self._spin_blocks(k)
+            rho = blocks[3] - blocks[4]
+        return _deliver(rho, self.system.np)
+
+    def two_body_density_spin(self, k=0, l=None):
+        """``(Gamma_aa, Gamma_ab, Gamma_bb)``, ``Gamma_st[p,q,r,s] = <c_k| a+_ps a+_qt a_st a_rs |c_l>`` (m, m, m, m) in the
+        orbitals ``C`` (``l`` defaults to ``k``), on ``kernels.string_ci_density2_spin``.  The beta-alpha block is
+        ``Gamma_ab[q,p,s,r]``; the four add up to ``two_body_density``.  ``Gamma_aa`` and ``Gamma_bb`` change sign under
+        ``p <-> q`` and under ``r <-> s``; ``sum_q Gamma_st[p,q,r,q] = (N_t - delta_st) rho_s[r,p]``."""
+        with torch._C.DisableTorchFunctionSubclass():
+            blocks = self._spin_blocks(k, l)
+        return tuple(_deliver(x, self.system.np) for x in blocks[:3])
+
+    def spin_squared_from_densities(self, k=0):
+        """``<S^2> = S_z (S_z + 1) + N_b - sum_pq Gamma_ab[q,p,p,q]`` of solved state ``k`` (real part), read off the
+        opposite-spin pair density; equals ``spin_squared(k)`` to rounding."""
+        with torch._C.DisableTorchFunctionSubclass():
+            gab = self._spin_blocks(k)[1]
+            sz = 0.5 * (self.n_up - self.n_down)
+            return sz * (sz + 1.0) + self.n_down - float(torch.einsum("qppq->", gab).real.item())
+
+    def natural_spin_orbitals(self, k=0):
+        """``(n_a, C_a, n_b, C_b)`` of solved state ``k``: per spin the occupations (descending eigenvalues of the
+        Hermitian part of ``rho_s[q, p]``, between 0 and 1) and ``C_s = C U_s`` with its eigenvectors as columns."""
+        out = []
+        with torch._C.DisableTorchFunctionSubclass():
+            for rho in self._spin_blocks(k)[3:]:
+                n, U = torch.linalg.eigh(0.5 * (rho + _dagger(rho)))
+                out += [n.flip(0).contiguous(), (self._C @ U.flip(1).to(self._dt)).contiguous()]
+        return tuple(_deliver(x, self.system.np) for x in out)
+
+    def pair_density_matrix(self, phi0, k=0, spins="ab"):
+        """``M[r, p] = sum_qs Gamma_st[p,q,r,s] conj(phi0[q]) phi0[s]`` of solved state ``k``, with ``phi0`` the m values
+        of the orbitals ``C`` at a reference point: ``system.compute_particle_density(M, C=C)`` is the density of s
+        particles given a t particle at that point (the conditional density up to the density at the point).  ``spins``
+        = ``"aa"``, ``"ab"``, ``"ba"``, ``"bb"`` names ``st``; ``"sum"`` adds the four."""
+        if spins not in ("aa", "ab", "ba", "bb", "sum"):
+            raise ValueError(f"spins must be one of 'aa', 'ab', 'ba', 'bb', 'sum', got {spins!r}")
+        with torch._C.DisableTorchFunctionSubclass():
+            gaa, gab, gbb = self._spin_blocks(k)[:3]
+            phi = torch.as_tensor(phi0, device=gaa.device) if not isinstance(phi0, torch.Tensor) else _plain(phi0).to(gaa.device)
+            if tuple(phi.shape) != (self.m,):
+                raise ValueError(f"phi0 must hold the m = {self.m} orbital values at the reference point, got {tuple(phi.shape)}")
+            dt = torch.complex128 if (phi.is_complex() or self._dt == torch.complex128) else torch.float64
+            phi = phi.to(dt)
+            gba = gab.permute(1, 0, 3, 2)
+            gamma = {"aa": gaa, "ab": gab, "ba": gba, "bb": gbb}.get(spins)
+            if gamma is None:
+                gamma = gaa + gbb + gab + gba
+            M = torch.einsum("pqrs,q,s->rp", gamma.to(dt), phi.conj(), phi).contiguous()
+        return _deliver(M, self.system.np)
 
     def apply_spin_squared(self, c):
         """``S^2 c_k`` for ``c`` (k, na, nb) or (na, nb), device tensor in and out
