@@ -617,7 +617,9 @@ def test_fitted_tile_shapes_vs_oracle(K, m, n, k, batch):
     (253, 600, 253, 2), (256, 384, 256, 2),         # sixteen row blocks (one register set)
     (20, 300, 20, 5), (1, 7, 1, 3), (17, 33, 5, 2),
     (300, 700, 300, 2), (288, 288 * 3, 288, 1), (3000, 300, 300, 1), (700, 513, 40, 1), (520, 300, 77, 3),   # SEVERAL tiles along the small extent
-    (70000, 130, 130, 1),      # contraction d: the rows of the tensor against the coefficient matrix (wide tiles)
+    # contraction d: the rows of the tensor against the coefficient matrix (tiles of 128 rows: the 256-row form takes over
+    # at 1024 such tiles, from 262144 rows)
+    (70000, 130, 130, 1),
     (4097, 100, 100, 1), (2000, 97, 97, 1), (1500, 253, 253, 1), (1000, 256, 256, 1), (300, 7, 3, 1), (129, 16, 4, 1),
 ])
 def test_strip_kernels_vs_oracle_and_bit_identical_to_the_general_kernel(K, m, n, k, batch):
