@@ -39,6 +39,13 @@ inline auto with_form(int form, F&& f) {
     return f(std::integral_constant<int, 2>{});
 }
 
+// f(std::integral_constant<int, W>) for the run-time width W = 1 or 2 doubles per element.
+template <class F>
+inline auto with_width(int w, F&& f) {
+    if (w == 1) return f(std::integral_constant<int, 1>{});
+    return f(std::integral_constant<int, 2>{});
+}
+
 // f(std::integral_constant<int, G>) for the smallest instantiation G of 1, 2, 4, 8 that holds ng <= 8 vectors.
 template <class F>
 inline auto with_group(int ng, F&& f) {

@@ -28,6 +28,8 @@
 // A table entry that points at or past the end of its list is treated as 0: a wrong table gives wrong numbers, never
 // an access outside the arguments.
 
+#include <initializer_list>
+
 #include "qs_contract_common.h"
 #include "qs_strings.h"
 
@@ -43,12 +45,12 @@ constexpr int kScRhoBlock = 256;      // threads of the density's and of the dia
 constexpr int64_t kScBytes = int64_t(2) << 30;
 
 struct ScArgs {
-    const int32_t* ta;        // (na, m^2)
+    const int32_t* ta;        // (na, m^2); the kernels read it through an argument of their own (string_ci_expand_kernel)
     const int32_t* tb;        // (nb, m^2)
     const double* c;          // (K, na, nb)
     const double* kk;         // (m, m), fold only
-    const double* G;          // (m^2, K, na, nb), fold only
-    double* out;              // expand: D (m^2, K, na, nb); fold: sigma (K, na, nb)
+    const double* G;          // the panel G_p of the pass, (m^2, K, pdim), fold only
+    double* out;              // sigma (K, na, nb); the fold writes it through an argument of its own
     int64_t na, nb;
     unsigned ntile;           // tiles of blockDim.x beta strings
     int m2, K;
@@ -72,17 +74,71 @@ __device__ __forceinline__ int64_t sc_target(int32_t e, int64_t n) {
     return j < n ? j : -1;
 }
 
+// (E_pq c)[Ia, Ib] from the two table entries of (Ia, pq) and (Ib, pq)
 template <int CW>
+__device__ __forceinline__ void sc_replaced(double (&v)[CW], const double* __restrict__ c, int32_t ea, int32_t eb, int64_t ia,
+                                            int64_t ib, int64_t na, int64_t nb) {
+    const int64_t ja = ea ? sc_target(ea, na) : -1, jb = eb ? sc_target(eb, nb) : -1;
+#pragma unroll
+    for (int w = 0; w < CW; ++w) v[w] = 0.0;
+    if (ja >= 0) {
+        const double* x = c + (ja * nb + ib) * CW;
+#pragma unroll
+        for (int w = 0; w < CW; ++w) v[w] = ea < 0 ? -x[w] : x[w];
+    }
+    if (jb >= 0) {
+        const double* x = c + (ia * nb + jb) * CW;
+#pragma unroll
+        for (int w = 0; w < CW; ++w) v[w] += eb < 0 ? -x[w] : x[w];
+    }
+}
+
+// ---- the panel of one pass -----------------------------------------------------------------------------------------------
+// A pass owns the alpha rows r0 <= Ka < r1 of D and G; c and sigma stay whole.  A layout says where the element (Ka, Kb) of
+// such a row lies in the panel of one (qs) and vector, which elements are stored at all, and which of them carry the weight
+// 1/2 in the fold; expand and fold below are written once over it.
+//   ScRect: every column, D_p[(qs), k, Ka - r0, Kb], panel stride (r1 - r0) nb.  One pass [0, na) is qs_string_ci_sigma, passes
+//           of equal length are qs_string_ci_sigma_rows.
+//   ScTri : the columns Kb <= Ka of a packed row at off(Ka) = Ka (Ka + 1) / 2, off(r1) - off(r0) elements per (qs) and
+//           vector (qs_string_ci_sigma_sym, below).
+
+__host__ __device__ __forceinline__ int64_t sc_off(int64_t r) { return r * (r + 1) / 2; }
+
+struct ScRect {
+    static constexpr bool kPacked = false;
+    int64_t r0, r1, nb;
+    __host__ __device__ int64_t pdim() const { return (r1 - r0) * nb; }
+    __device__ int64_t at(int64_t row, int64_t col) const { return (row - r0) * nb + col; }
+    __device__ bool tile(int64_t, int64_t) const { return true; }        // the tile that starts at col0 holds a stored column
+    __device__ bool holds(int64_t, int64_t) const { return true; }
+    __device__ bool diagonal(int64_t, int64_t) const { return false; }
+};
+
+struct ScTri {
+    static constexpr bool kPacked = true;
+    int64_t r0, r1, nb;
+    __host__ __device__ int64_t pdim() const { return sc_off(r1) - sc_off(r0); }
+    __device__ int64_t at(int64_t row, int64_t col) const { return sc_off(row) - sc_off(r0) + col; }
+    __device__ bool tile(int64_t row, int64_t col0) const { return col0 <= row; }
+    __device__ bool holds(int64_t row, int64_t col) const { return col <= row; }
+    __device__ bool diagonal(int64_t row, int64_t col) const { return col == row; }
+};
+
+// D_p = expand(c) on the rows of the pass: one workgroup per alpha string of the pass and tile of beta strings.  c is the
+// whole vector: the targets lie anywhere.
+template <int CW, class Layout>
 __global__ __launch_bounds__(kScBlock) void string_ci_expand_kernel(const ScArgs a, const int32_t* __restrict__ ta,
-                                                                   double* __restrict__ D) {
+                                                                   double* __restrict__ D, const Layout lay) {
     // ta and D are kernel arguments of their own: only there does __restrict__ tell the compiler that the stores of D
     // cannot change the table, which lets the uniform read below be a scalar load
     extern __shared__ __attribute__((aligned(16))) int32_t sc_tb[];
     const int B = blockDim.x, t = threadIdx.x, m2 = a.m2;
-    const int64_t ia = blockIdx.x / a.ntile;                              // uniform
+    const int64_t ia = lay.r0 + blockIdx.x / a.ntile;                     // uniform
     const int64_t ib0 = (int64_t)(blockIdx.x % a.ntile) * B;
-    const int64_t ib = ib0 + t, nb = a.nb, dim = a.na * a.nb;
-    const bool live = ib < nb;
+    if (!lay.tile(ia, ib0)) return;                                       // uniform: the tile lies above the diagonal
+    const int64_t ib = ib0 + t, nb = a.nb, dim = a.na * a.nb, pdim = lay.pdim();
+    const bool live = ib < nb && lay.holds(ia, ib);                       // the others only stage
+    const int64_t at = lay.at(ia, ib);
     const int32_t* __restrict__ ta_row = ta + ia * m2;
     const double* __restrict__ c = a.c;
     for (int pq0 = 0; pq0 < m2; pq0 += kScChunk) {
@@ -95,23 +151,10 @@ __global__ __launch_bounds__(kScBlock) void string_ci_expand_kernel(const ScArgs
             const int pq = pq0 + j;
             const int32_t ea = ta_row[pq];                                // uniform address: a scalar load
             const int32_t eb = sc_tb[j * (B + 1) + t];
-            const int64_t ja = ea ? sc_target(ea, a.na) : -1, jb = eb ? sc_target(eb, nb) : -1;
             for (int k = 0; k < a.K; ++k) {
-                const double* __restrict__ ck = c + (int64_t)k * dim * CW;
                 double v[CW];
-#pragma unroll
-                for (int w = 0; w < CW; ++w) v[w] = 0.0;
-                if (ja >= 0) {
-                    const double* x = ck + (ja * nb + ib) * CW;
-#pragma unroll
-                    for (int w = 0; w < CW; ++w) v[w] = ea < 0 ? -x[w] : x[w];
-                }
-                if (jb >= 0) {
-                    const double* x = ck + (ia * nb + jb) * CW;
-#pragma unroll
-                    for (int w = 0; w < CW; ++w) v[w] += eb < 0 ? -x[w] : x[w];
-                }
-                double* d = D + (((int64_t)pq * a.K + k) * dim + ia * nb + ib) * CW;
+                sc_replaced<CW>(v, c + (int64_t)k * dim * CW, ea, eb, ia, ib, a.na, nb);
+                double* d = D + (((int64_t)pq * a.K + k) * pdim + at) * CW;
 #pragma unroll
                 for (int w = 0; w < CW; ++w) d[w] = v[w];
             }
@@ -137,128 +180,71 @@ __device__ __forceinline__ void sc_feed(double (&acc)[CW], const double (&kk)[HW
     }
 }
 
-template <int FORM>
-__global__ __launch_bounds__(kScBlock) void string_ci_fold_kernel(const ScArgs a) {
-    constexpr int HW = form_widths(FORM).uw, CW = form_widths(FORM).aw;
-    extern __shared__ __attribute__((aligned(16))) int32_t sc_tb[];
-    const int B = blockDim.x, t = threadIdx.x, m2 = a.m2;
-    const unsigned row = blockIdx.x / a.ntile;                            // (k, ia), uniform
-    const int64_t k = row / (unsigned)a.na, ia = row % (unsigned)a.na;
-    const int64_t ib0 = (int64_t)(blockIdx.x % a.ntile) * B;
-    const int64_t ib = ib0 + t, nb = a.nb, dim = a.na * a.nb;
-    const bool live = ib < nb;
-    const int32_t* __restrict__ ta_row = a.ta + ia * m2;
-    const double* __restrict__ ck = a.c + k * dim * CW;
-    const double* __restrict__ kk = a.kk;
-    double acc[CW];
+// acc += w s (g + kk c), w = 1/2 on the diagonal of X: the term s (g + kk c) through sc_feed from 0, which is exact, and the
+// weight a power of two, so the one rounding is that of the sum
+template <int HW, int CW>
+__device__ __forceinline__ void sc_feed_tri(double (&acc)[CW], const double (&kk)[HW], const double* __restrict__ g,
+                                            const double* __restrict__ c, bool minus, bool diagonal) {
+    double x[CW];
 #pragma unroll
-    for (int w = 0; w < CW; ++w) acc[w] = 0.0;
-    for (int pr0 = 0; pr0 < m2; pr0 += kScChunk) {
-        __syncthreads();
-        sc_stage(sc_tb, a.tb, ib0, nb, pr0, m2);
-        __syncthreads();
-        if (!live) continue;
-        const int nj = m2 - pr0 < kScChunk ? m2 - pr0 : kScChunk;
-        for (int j = 0; j < nj; ++j) {
-            const int pr = pr0 + j;
-            const int32_t ea = ta_row[pr];                                // uniform address: a scalar load
-            const int32_t eb = sc_tb[j * (B + 1) + t];
-            double kpr[HW];
+    for (int w = 0; w < CW; ++w) x[w] = 0.0;
+    sc_feed<HW, CW>(x, kk, g, c, minus);
+    const double wt = diagonal ? 0.5 : 1.0;
 #pragma unroll
-            for (int w = 0; w < HW; ++w) kpr[w] = kk[pr * HW + w];
-            const double* __restrict__ g = a.G + ((int64_t)pr * a.K + k) * dim * CW;
-            if (ea) {
-                const int64_t ja = sc_target(ea, a.na);
-                if (ja >= 0) sc_feed<HW, CW>(acc, kpr, g + (ja * nb + ib) * CW, ck + (ja * nb + ib) * CW, ea < 0);
-            }
-            if (eb) {
-                const int64_t jb = sc_target(eb, nb);
-                if (jb >= 0) sc_feed<HW, CW>(acc, kpr, g + (ia * nb + jb) * CW, ck + (ia * nb + jb) * CW, eb < 0);
-            }
-        }
-    }
-    if (live) {
-#pragma unroll
-        for (int w = 0; w < CW; ++w) a.out[(k * dim + ia * nb + ib) * CW + w] = acc[w];
-    }
+    for (int w = 0; w < CW; ++w) acc[w] = fma(wt, x[w], acc[w]);
+}
+
+// the term of the source element (row, col) = k c + G_p there: the plain chain for the rectangle, the weighted one for the triangle
+template <int HW, int CW, class Layout>
+__device__ __forceinline__ void sc_feed_at(double (&acc)[CW], const double (&kk)[HW], const double* __restrict__ g,
+                                           const double* __restrict__ ck, const Layout& lay, int64_t row, int64_t col, int64_t nb,
+                                           bool minus) {
+    const double* __restrict__ x = g + lay.at(row, col) * CW;
+    const double* __restrict__ y = ck + (row * nb + col) * CW;
+    if constexpr (Layout::kPacked) sc_feed_tri<HW, CW>(acc, kk, x, y, minus, lay.diagonal(row, col));
+    else sc_feed<HW, CW>(acc, kk, x, y, minus);
 }
 
 // ---- sigma in passes over alpha rows of the intermediate (qs_string_ci_sigma_rows) -------------------------------------
-// A pass owns the alpha rows r0 <= Ka < r1 of D and G, R = r1 - r0: D_p[(qs), k, Ka - r0, Kb], panel stride R nb.  c stays
-// whole.  The fold runs over every (k, Ia, tile) in every pass and keeps the terms whose SOURCE row lies in the pass -- the
-// alpha term of pr when r0 <= Ta[Ia,pr] < r1, the beta terms when r0 <= Ia < r1 --, so nothing is scattered: a pass adds
-// into sigma, the first one (r0 = 0) starts from 0 and never reads it.  The order of one element's sum is pass ascending,
-// pr ascending, alpha before beta; a pass boundary stores and reloads the accumulator exactly, so one pass over all rows
-// gives the bits of string_ci_fold_kernel.
+// The fold runs over every (k, Ia, tile) in every pass and keeps the terms whose SOURCE row lies in the pass -- the alpha
+// term of pr when r0 <= Ta[Ia,pr] < r1, the beta terms when r0 <= Ia < r1 --, so nothing is scattered: a pass adds into
+// sigma, the first one (r0 = 0) starts from 0 and never reads it.  The order of one element's sum is pass ascending, pr
+// ascending, alpha before beta; a pass boundary stores and reloads the accumulator exactly, so the passes of any schedule
+// give the bits of the one pass [0, na).
+//
+// ---- sigma on the lower triangle for c = tau c^T (qs_string_ci_sigma_sym) ------------------------------------------------
+// One table T and n strings for both spins, (P c)[Ia, Ib] = c[Ib, Ia], tau = +-1.  For c = tau P c every row D[(qs), k, :, :]
+// and with it G = W . D and X = G + k c have the parity tau in (Ka, Kb): the columns Kb <= Ka carry everything (ScTri).
+//   expand : D_p[(qs), k, off(Ka) - off(r0) + Kb] = sgn c_k[T[Ka,qs], Kb] + sgn c_k[Ka, T[Kb,qs]]            Kb <= Ka
+//   fold   : S_k[Ia, Ib] (+)= sum_pr ( w(Ja, Ib) sgn X[(pr), k, off(Ja) + Ib]     Ja = T[Ia,pr] in the pass, Ja >= Ib
+//                                    + w(Ia, Jb) sgn X[(pr), k, off(Ia) + Jb] )   Jb = T[Ib,pr], Ia in the pass, Jb <= Ia
+//            w(r, c) = 1 for r > c, 1/2 for r == c
+//   close  : sigma_k = S_k + tau S_k^T
+// The fold runs over the whole square and reads only stored elements: the terms it drops are tau times the kept terms of
+// the transposed element, and a diagonal element of X is met from both sides, hence the exact 1/2.  Its two reads are those
+// of the rectangle -- contiguous over the lanes for alpha, a gather inside ONE packed row for beta --; nothing is strided by
+// n.  The close makes sigma[a, b] == tau sigma[b, a] hold bit for bit, with +0.0 on the diagonal for tau = -1.
 
-template <int CW>
-__global__ __launch_bounds__(kScBlock) void string_ci_expand_range_kernel(const ScArgs a, const int32_t* __restrict__ ta,
-                                                                         double* __restrict__ D, int64_t r0, int64_t r1) {
-    // the mapping of string_ci_expand_kernel on the rows of the pass; ta and D are arguments of their own for its reason
-    extern __shared__ __attribute__((aligned(16))) int32_t sc_tb[];
-    const int B = blockDim.x, t = threadIdx.x, m2 = a.m2;
-    const int64_t il = blockIdx.x / a.ntile;                              // uniform
-    const int64_t ia = r0 + il;
-    const int64_t ib0 = (int64_t)(blockIdx.x % a.ntile) * B;
-    const int64_t ib = ib0 + t, nb = a.nb, dim = a.na * a.nb, pdim = (r1 - r0) * nb;
-    const bool live = ib < nb;
-    const int32_t* __restrict__ ta_row = ta + ia * m2;
-    const double* __restrict__ c = a.c;
-    for (int pq0 = 0; pq0 < m2; pq0 += kScChunk) {
-        __syncthreads();
-        sc_stage(sc_tb, a.tb, ib0, nb, pq0, m2);
-        __syncthreads();
-        if (!live) continue;
-        const int nj = m2 - pq0 < kScChunk ? m2 - pq0 : kScChunk;
-        for (int j = 0; j < nj; ++j) {
-            const int pq = pq0 + j;
-            const int32_t ea = ta_row[pq];                                // uniform address: a scalar load
-            const int32_t eb = sc_tb[j * (B + 1) + t];
-            const int64_t ja = ea ? sc_target(ea, a.na) : -1, jb = eb ? sc_target(eb, nb) : -1;
-            for (int k = 0; k < a.K; ++k) {
-                const double* __restrict__ ck = c + (int64_t)k * dim * CW;        // the whole vector: targets lie anywhere
-                double v[CW];
-#pragma unroll
-                for (int w = 0; w < CW; ++w) v[w] = 0.0;
-                if (ja >= 0) {
-                    const double* x = ck + (ja * nb + ib) * CW;
-#pragma unroll
-                    for (int w = 0; w < CW; ++w) v[w] = ea < 0 ? -x[w] : x[w];
-                }
-                if (jb >= 0) {
-                    const double* x = ck + (ia * nb + jb) * CW;
-#pragma unroll
-                    for (int w = 0; w < CW; ++w) v[w] += eb < 0 ? -x[w] : x[w];
-                }
-                double* d = D + (((int64_t)pq * a.K + k) * pdim + il * nb + ib) * CW;
-#pragma unroll
-                for (int w = 0; w < CW; ++w) d[w] = v[w];
-            }
-        }
-    }
-}
-
-template <int FORM>
-__global__ __launch_bounds__(kScBlock) void string_ci_fold_range_kernel(const ScArgs a, const int32_t* __restrict__ ta,
-                                                                       double* __restrict__ sigma, int64_t r0, int64_t r1) {
+template <int FORM, class Layout>
+__global__ __launch_bounds__(kScBlock) void string_ci_fold_kernel(const ScArgs a, const int32_t* __restrict__ ta,
+                                                                 double* __restrict__ sigma, const Layout lay) {
     constexpr int HW = form_widths(FORM).uw, CW = form_widths(FORM).aw;
     extern __shared__ __attribute__((aligned(16))) int32_t sc_tb[];
     const int B = blockDim.x, t = threadIdx.x, m2 = a.m2;
     const unsigned row = blockIdx.x / a.ntile;                            // (k, ia), uniform
     const int64_t k = row / (unsigned)a.na, ia = row % (unsigned)a.na;
     const int64_t ib0 = (int64_t)(blockIdx.x % a.ntile) * B;
-    const int64_t ib = ib0 + t, nb = a.nb, dim = a.na * a.nb, pdim = (r1 - r0) * nb;
+    const int64_t ib = ib0 + t, nb = a.nb, dim = a.na * a.nb, r0 = lay.r0, r1 = lay.r1, pdim = lay.pdim();
     const bool live = ib < nb;
     const int32_t* __restrict__ ta_row = ta + ia * m2;
     const double* __restrict__ ck = a.c + k * dim * CW;
     const double* __restrict__ kk = a.kk;
-    const double* __restrict__ Gk = a.G + k * pdim * CW;                  // X_p[(pr), k, :, :] = Gk + pr K pdim
+    const double* __restrict__ Gk = a.G + k * pdim * CW;                  // X_p[(pr), k, :] = Gk + pr K pdim
     double* __restrict__ out = sigma + (k * dim + ia * nb + ib) * CW;
     double acc[CW];
 #pragma unroll
     for (int w = 0; w < CW; ++w) acc[w] = (r0 > 0 && live) ? out[w] : 0.0;        // the first pass never reads sigma
     if (ia >= r0 && ia < r1) {                                            // uniform: the row Ia itself is in the pass
-        const int64_t il = ia - r0;
         for (int pr0 = 0; pr0 < m2; pr0 += kScChunk) {
             __syncthreads();
             sc_stage(sc_tb, a.tb, ib0, nb, pr0, m2);
@@ -275,160 +261,13 @@ __global__ __launch_bounds__(kScBlock) void string_ci_fold_range_kernel(const Sc
                 const double* __restrict__ g = Gk + (int64_t)pr * a.K * pdim * CW;
                 if (ea) {
                     const int64_t ja = sc_target(ea, a.na);               // -1 (past the list) is below every r0
-                    if (ja >= r0 && ja < r1) sc_feed<HW, CW>(acc, kpr, g + ((ja - r0) * nb + ib) * CW, ck + (ja * nb + ib) * CW, ea < 0);
+                    // uniform: the row Ja is in the pass and reaches the tile; per lane: the stored columns
+                    if (ja >= r0 && ja < r1 && lay.tile(ja, ib0) && lay.holds(ja, ib))
+                        sc_feed_at<HW, CW>(acc, kpr, g, ck, lay, ja, ib, nb, ea < 0);
                 }
                 if (eb) {
                     const int64_t jb = sc_target(eb, nb);
-                    if (jb >= 0) sc_feed<HW, CW>(acc, kpr, g + (il * nb + jb) * CW, ck + (ia * nb + jb) * CW, eb < 0);
-                }
-            }
-        }
-    } else if (live) {
-        // outside the pass: no beta term, no staging, no barrier; the alpha entries and their range test are scalar
-        for (int pr = 0; pr < m2; ++pr) {
-            const int32_t ea = ta_row[pr];                                // uniform address: a scalar load
-            if (!ea) continue;
-            const int64_t ja = sc_target(ea, a.na);
-            if (ja < r0 || ja >= r1) continue;
-            double kpr[HW];
-#pragma unroll
-            for (int w = 0; w < HW; ++w) kpr[w] = kk[pr * HW + w];
-            const double* __restrict__ g = Gk + (int64_t)pr * a.K * pdim * CW;
-            sc_feed<HW, CW>(acc, kpr, g + ((ja - r0) * nb + ib) * CW, ck + (ja * nb + ib) * CW, ea < 0);
-        }
-    }
-    if (live) {
-#pragma unroll
-        for (int w = 0; w < CW; ++w) out[w] = acc[w];
-    }
-}
-
-// ---- sigma on the lower triangle for c = tau c^T (qs_string_ci_sigma_sym) ------------------------------------------------
-// One table T and n strings for both spins, (P c)[Ia, Ib] = c[Ib, Ia], tau = +-1.  For c = tau P c every row D[(qs), k, :, :]
-// and with it G = W . D and X = G + k c have the parity tau in (Ka, Kb): the columns Kb <= Ka carry everything.  A packed row
-// Ka holds them at off(Ka) = Ka (Ka + 1) / 2; a pass owns the rows r0 <= Ka < r1, off(r1) - off(r0) elements per (qs) and
-// vector, row Ka at off(Ka) - off(r0).  c and sigma stay full (n, n).
-//   expand : D_p[(qs), k, off(Ka) - off(r0) + Kb] = sgn c_k[T[Ka,qs], Kb] + sgn c_k[Ka, T[Kb,qs]]            Kb <= Ka
-//   fold   : S_k[Ia, Ib] (+)= sum_pr ( w(Ja, Ib) sgn X[(pr), k, off(Ja) + Ib]     Ja = T[Ia,pr] in the pass, Ja >= Ib
-//                                    + w(Ia, Jb) sgn X[(pr), k, off(Ia) + Jb] )   Jb = T[Ib,pr], Ia in the pass, Jb <= Ia
-//            w(r, c) = 1 for r > c, 1/2 for r == c
-//   close  : sigma_k = S_k + tau S_k^T
-// The fold runs over the whole square and reads only stored elements: the terms it drops are tau times the kept terms of
-// the transposed element, and a diagonal element of X is met from both sides, hence the exact 1/2.  Its two reads are those
-// of the fold above -- contiguous over the lanes for alpha, a gather inside ONE packed row for beta --; nothing is strided by
-// n.  The order of one element's sum is pass ascending, pr ascending, alpha before beta.  The close makes
-// sigma[a, b] == tau sigma[b, a] hold bit for bit, with +0.0 on the diagonal for tau = -1.
-
-__host__ __device__ __forceinline__ int64_t sc_off(int64_t r) { return r * (r + 1) / 2; }
-
-template <int CW>
-__global__ __launch_bounds__(kScBlock) void string_ci_expand_tri_kernel(const ScArgs a, const int32_t* __restrict__ ta,
-                                                                       double* __restrict__ D, int64_t r0, int64_t r1) {
-    // the mapping of string_ci_expand_range_kernel; ta and D are arguments of their own for the reason given at
-    // string_ci_expand_kernel
-    extern __shared__ __attribute__((aligned(16))) int32_t sc_tb[];
-    const int B = blockDim.x, t = threadIdx.x, m2 = a.m2;
-    const int64_t ia = r0 + blockIdx.x / a.ntile;                         // uniform
-    const int64_t ib0 = (int64_t)(blockIdx.x % a.ntile) * B;
-    if (ib0 > ia) return;                                                 // uniform: the tile lies above the diagonal
-    const int64_t ib = ib0 + t, n = a.nb, dim = n * n, pdim = sc_off(r1) - sc_off(r0);
-    const int64_t at = sc_off(ia) - sc_off(r0) + ib;
-    const bool live = ib <= ia;                                           // the others only stage
-    const int32_t* __restrict__ ta_row = ta + ia * m2;
-    const double* __restrict__ c = a.c;
-    for (int pq0 = 0; pq0 < m2; pq0 += kScChunk) {
-        __syncthreads();
-        sc_stage(sc_tb, a.tb, ib0, n, pq0, m2);
-        __syncthreads();
-        if (!live) continue;
-        const int nj = m2 - pq0 < kScChunk ? m2 - pq0 : kScChunk;
-        for (int j = 0; j < nj; ++j) {
-            const int pq = pq0 + j;
-            const int32_t ea = ta_row[pq];                                // uniform address: a scalar load
-            const int32_t eb = sc_tb[j * (B + 1) + t];
-            const int64_t ja = ea ? sc_target(ea, n) : -1, jb = eb ? sc_target(eb, n) : -1;
-            for (int k = 0; k < a.K; ++k) {
-                const double* __restrict__ ck = c + (int64_t)k * dim * CW;        // the full vector
-                double v[CW];
-#pragma unroll
-                for (int w = 0; w < CW; ++w) v[w] = 0.0;
-                if (ja >= 0) {
-                    const double* x = ck + (ja * n + ib) * CW;
-#pragma unroll
-                    for (int w = 0; w < CW; ++w) v[w] = ea < 0 ? -x[w] : x[w];
-                }
-                if (jb >= 0) {
-                    const double* x = ck + (ia * n + jb) * CW;
-#pragma unroll
-                    for (int w = 0; w < CW; ++w) v[w] += eb < 0 ? -x[w] : x[w];
-                }
-                double* d = D + (((int64_t)pq * a.K + k) * pdim + at) * CW;
-#pragma unroll
-                for (int w = 0; w < CW; ++w) d[w] = v[w];
-            }
-        }
-    }
-}
-
-// acc += w s (g + kk c), w = 1/2 on the diagonal of X: the term s (g + kk c) through sc_feed from 0, which is exact, and the
-// weight a power of two, so the one rounding is that of the sum
-template <int HW, int CW>
-__device__ __forceinline__ void sc_feed_tri(double (&acc)[CW], const double (&kk)[HW], const double* __restrict__ g,
-                                            const double* __restrict__ c, bool minus, bool diagonal) {
-    double x[CW];
-#pragma unroll
-    for (int w = 0; w < CW; ++w) x[w] = 0.0;
-    sc_feed<HW, CW>(x, kk, g, c, minus);
-    const double wt = diagonal ? 0.5 : 1.0;
-#pragma unroll
-    for (int w = 0; w < CW; ++w) acc[w] = fma(wt, x[w], acc[w]);
-}
-
-template <int FORM>
-__global__ __launch_bounds__(kScBlock) void string_ci_fold_tri_kernel(const ScArgs a, const int32_t* __restrict__ ta,
-                                                                     double* __restrict__ sigma, int64_t r0, int64_t r1) {
-    constexpr int HW = form_widths(FORM).uw, CW = form_widths(FORM).aw;
-    extern __shared__ __attribute__((aligned(16))) int32_t sc_tb[];
-    const int B = blockDim.x, t = threadIdx.x, m2 = a.m2;
-    const unsigned row = blockIdx.x / a.ntile;                            // (k, ia), uniform
-    const int64_t k = row / (unsigned)a.na, ia = row % (unsigned)a.na;
-    const int64_t ib0 = (int64_t)(blockIdx.x % a.ntile) * B;
-    const int64_t ib = ib0 + t, n = a.nb, dim = n * n, base = sc_off(r0), pdim = sc_off(r1) - base;
-    const bool live = ib < n;
-    const int32_t* __restrict__ ta_row = ta + ia * m2;
-    const double* __restrict__ ck = a.c + k * dim * CW;
-    const double* __restrict__ kk = a.kk;
-    const double* __restrict__ Gk = a.G + k * pdim * CW;                  // X_p[(pr), k, :] = Gk + pr K pdim
-    double* __restrict__ out = sigma + (k * dim + ia * n + ib) * CW;
-    double acc[CW];
-#pragma unroll
-    for (int w = 0; w < CW; ++w) acc[w] = (r0 > 0 && live) ? out[w] : 0.0;        // the first pass never reads sigma
-    if (ia >= r0 && ia < r1) {                                            // uniform: the packed row Ia is in the pass
-        const int64_t own = sc_off(ia) - base;
-        for (int pr0 = 0; pr0 < m2; pr0 += kScChunk) {
-            __syncthreads();
-            sc_stage(sc_tb, a.tb, ib0, n, pr0, m2);
-            __syncthreads();
-            if (!live) continue;
-            const int nj = m2 - pr0 < kScChunk ? m2 - pr0 : kScChunk;
-            for (int j = 0; j < nj; ++j) {
-                const int pr = pr0 + j;
-                const int32_t ea = ta_row[pr];                            // uniform address: a scalar load
-                const int32_t eb = sc_tb[j * (B + 1) + t];
-                double kpr[HW];
-#pragma unroll
-                for (int w = 0; w < HW; ++w) kpr[w] = kk[pr * HW + w];
-                const double* __restrict__ g = Gk + (int64_t)pr * a.K * pdim * CW;
-                if (ea) {
-                    const int64_t ja = sc_target(ea, n);                  // -1 (past the list) is below every r0
-                    // uniform: the row Ja is in the pass and reaches the tile; per lane: the stored columns Ib <= Ja
-                    if (ja >= r0 && ja < r1 && ja >= ib0 && ja >= ib)
-                        sc_feed_tri<HW, CW>(acc, kpr, g + (sc_off(ja) - base + ib) * CW, ck + (ja * n + ib) * CW, ea < 0, ja == ib);
-                }
-                if (eb) {
-                    const int64_t jb = sc_target(eb, n);
-                    if (jb >= 0 && jb <= ia)
-                        sc_feed_tri<HW, CW>(acc, kpr, g + (own + jb) * CW, ck + (ia * n + jb) * CW, eb < 0, jb == ia);
+                    if (jb >= 0 && lay.holds(ia, jb)) sc_feed_at<HW, CW>(acc, kpr, g, ck, lay, ia, jb, nb, eb < 0);
                 }
             }
         }
@@ -438,14 +277,13 @@ __global__ __launch_bounds__(kScBlock) void string_ci_fold_tri_kernel(const ScAr
         for (int pr = 0; pr < m2; ++pr) {
             const int32_t ea = ta_row[pr];                                // uniform address: a scalar load
             if (!ea) continue;
-            const int64_t ja = sc_target(ea, n);
-            if (ja < r0 || ja >= r1 || ja < ib0) continue;
-            if (ja < ib) continue;
+            const int64_t ja = sc_target(ea, a.na);
+            if (ja < r0 || ja >= r1 || !lay.tile(ja, ib0)) continue;
+            if (!lay.holds(ja, ib)) continue;
             double kpr[HW];
 #pragma unroll
             for (int w = 0; w < HW; ++w) kpr[w] = kk[pr * HW + w];
-            const double* __restrict__ g = Gk + (int64_t)pr * a.K * pdim * CW;
-            sc_feed_tri<HW, CW>(acc, kpr, g + (sc_off(ja) - base + ib) * CW, ck + (ja * n + ib) * CW, ea < 0, ja == ib);
+            sc_feed_at<HW, CW>(acc, kpr, Gk + (int64_t)pr * a.K * pdim * CW, ck, lay, ja, ib, nb, ea < 0);
         }
     }
     if (live) {
@@ -597,6 +435,11 @@ static inline bool sc_extents_ok(int form, int64_t m, int64_t na, int64_t nb, in
     return cols <= 0x7fffffffLL;
 }
 
+// The byte budget of a call: the calling thread's string_ci_bytes, else the argument, else the shipped one.
+static inline int64_t sc_budget(int64_t budget_bytes) {
+    return g_tune.string_ci_bytes > 0 ? g_tune.string_ci_bytes : (budget_bytes > 0 ? budget_bytes : kScBytes);
+}
+
 // bytes of D (and of G): m^2 K na nb elements of c, to the next multiple of 16
 static inline int64_t sc_panel_bytes(int form, int64_t m, int64_t na, int64_t nb, int64_t K) {
     return (m * m * K * na * nb * 8 * form_widths(form).aw + 15) & ~int64_t(15);      // < 2^12 * 2^31 * 16; G stays 16-byte aligned
@@ -613,15 +456,82 @@ static ScArgs sc_args(const int32_t* ta, const int32_t* tb, const void* c, int64
     return a;
 }
 
-// D = expand(c) for the K vectors of c
-static int sc_expand(int cw, ScArgs a, void* D, hipStream_t s) {
-    a.out = (double*)D;
+struct ScSpan {
+    const void* at;
+    int64_t bytes;
+};
+
+// The alias rule of every entry: no output shares a byte with an input or with an output before it.
+static int sc_alias(std::initializer_list<ScSpan> out, std::initializer_list<ScSpan> in) {
+    for (const ScSpan* o = out.begin(); o != out.end(); ++o) {
+        for (const ScSpan& x : in)
+            if (overlaps(o->at, o->bytes, x.at, x.bytes)) return QS_ERR_ALIAS;
+        for (const ScSpan* b = out.begin(); b != o; ++b)
+            if (overlaps(o->at, o->bytes, b->at, b->bytes)) return QS_ERR_ALIAS;
+    }
+    return QS_OK;
+}
+
+// The refusals of the three sigma entries, in their order: form, extents (extra_ok: those of the entry's own arguments),
+// null, alignment, workspace, aliases.  need() gives the bytes of the workspace; it runs on valid extents only.
+template <class Need>
+static int sc_sigma_check(int form, int h_dtype, int c_dtype, const void* k, const void* W, const int32_t* ta, const int32_t* tb,
+                          int64_t m, int64_t na, int64_t nb, const void* c, int64_t K, const void* sigma, const void* work,
+                          int64_t work_bytes, bool extra_ok, Need need) {
+    if (form < 0) return form;
+    if (!extra_ok || !sc_extents_ok(form, m, na, nb, K)) return QS_ERR_BAD_EXTENT;
+    if (!k || !W || !ta || !tb || !c || !sigma || !work) return QS_ERR_NULL_POINTER;
+    const int64_t hs = (int64_t)elem_size(h_dtype), cs = (int64_t)elem_size(c_dtype);
+    if (!aligned(k, (size_t)hs) || !aligned(W, (size_t)hs) || !aligned(ta, 4) || !aligned(tb, 4) || !aligned(c, (size_t)cs) ||
+        !aligned(sigma, (size_t)cs) || !aligned(work, 16))
+        return QS_ERR_MISALIGNED;
+    const int64_t w_bytes = need();
+    if (work_bytes < w_bytes) return QS_ERR_WORKSPACE;
+    const int64_t m2 = m * m, s_bytes = K * na * nb * cs;
+    return sc_alias({{sigma, s_bytes}, {work, w_bytes}},
+                    {{c, s_bytes}, {W, m2 * m2 * hs}, {k, m2 * hs}, {ta, na * m2 * 4}, {tb, nb * m2 * 4}});
+}
+
+// D_p = expand(c) on the rows of the layout's pass, for the K vectors of a.c
+template <class Layout>
+static int sc_expand(int cw, const ScArgs& a, void* D, const Layout& lay, hipStream_t s) {
     const int threads = sc_threads(a.nb);
-    const unsigned grid = (unsigned)(a.na * a.ntile);
-    if (cw == 1) hipLaunchKernelGGL((string_ci_expand_kernel<1>), dim3(grid), dim3(threads), sc_lds(threads), s, a, a.ta, a.out);
-    else hipLaunchKernelGGL((string_ci_expand_kernel<2>), dim3(grid), dim3(threads), sc_lds(threads), s, a, a.ta, a.out);
-    note_dispatch("qs::string_ci_expand_kernel<%d>", cw);
+    const unsigned grid = (unsigned)((lay.r1 - lay.r0) * a.ntile);
+    with_width(cw, [&](auto CW) {
+        hipLaunchKernelGGL((string_ci_expand_kernel<CW, Layout>), dim3(grid), dim3(threads), sc_lds(threads), s, a, a.ta, (double*)D, lay);
+    });
+    note_dispatch(Layout::kPacked ? "qs::string_ci_expand_kernel<%d, qs::ScTri>" : "qs::string_ci_expand_kernel<%d, qs::ScRect>", cw);
     return launch_status("string CI expand launch");
+}
+
+// One sigma: for every pass [r0, next(r0)) of the layout's rows, D_p = expand(c), G_p = W . D_p, sigma (+)= fold(G_p + k c),
+// D_p and G_p the two panels of `panel` bytes in work.
+template <class Layout, class Next>
+static int sc_sigma_passes(int form, int h_dtype, const void* k, const void* W, ScArgs a, void* sigma, void* work, int64_t panel,
+                           Next next, hipStream_t s) {
+    const FormWidths fw = form_widths(form);
+    char* D = (char*)work;
+    char* G = D + panel;
+    a.kk = (const double*)k; a.G = (const double*)G; a.out = (double*)sigma;
+    const int threads = sc_threads(a.nb);
+    const unsigned grid = (unsigned)(a.K * a.na * a.ntile);
+    for (int64_t r0 = 0; r0 < a.na;) {
+        const Layout lay{r0, next(r0), a.nb};
+        int rc = sc_expand(fw.aw, a, D, lay, s);
+        if (rc) return rc;
+        // real W against complex c: the re / im pairs of D_p are columns of a real product
+        rc = gemm(packed(h_dtype, W, D, G, a.m2, a.K * lay.pdim() * (fw.aw / fw.uw), a.m2), s);
+        if (rc) return rc;
+        with_form(form, [&](auto FORM) {
+            hipLaunchKernelGGL((string_ci_fold_kernel<FORM, Layout>), dim3(grid), dim3(threads), sc_lds(threads), s, a, a.ta, a.out, lay);
+            note_dispatch(Layout::kPacked ? "qs::string_ci_fold_kernel<%d, qs::ScTri>" : "qs::string_ci_fold_kernel<%d, qs::ScRect>",
+                          (int)FORM);
+        });
+        rc = launch_status("string CI fold launch");
+        if (rc) return rc;
+        r0 = lay.r1;
+    }
+    return QS_OK;
 }
 
 // The schedule and the workspace of one qs_string_ci_sigma_rows call, fixed by its arguments and the calling thread's
@@ -633,7 +543,7 @@ struct ScRowsPlan {
 };
 
 static ScRowsPlan sc_rows_plan(int form, int64_t m, int64_t na, int64_t nb, int64_t K, int64_t budget_bytes) {
-    const int64_t budget = g_tune.string_ci_bytes > 0 ? g_tune.string_ci_bytes : (budget_bytes > 0 ? budget_bytes : kScBytes);
+    const int64_t budget = sc_budget(budget_bytes);
     // 2 ceil16(x) <= budget  <=>  x <= the multiple of 16 at or below budget / 2
     int64_t rows = ((budget / 2) & ~int64_t(15)) / (m * m * K * nb * 8 * form_widths(form).aw);
     // rows <= na also keeps a pass's product within 2^31 - 1 columns: sc_extents_ok has bounded those of all na rows
@@ -644,16 +554,6 @@ static ScRowsPlan sc_rows_plan(int form, int64_t m, int64_t na, int64_t nb, int6
     p.cols = K * p.rows * nb * (form == 2 ? 2 : 1);
     p.panel = sc_panel_bytes(form, m, p.rows, nb, K);
     return p;
-}
-
-// D_p = expand(c) on the alpha rows r0 ... r1 - 1, for the K vectors of c
-static int sc_expand_range(int cw, const ScArgs& a, void* D, int64_t r0, int64_t r1, hipStream_t s) {
-    const int threads = sc_threads(a.nb);
-    const unsigned grid = (unsigned)((r1 - r0) * a.ntile);
-    if (cw == 1) hipLaunchKernelGGL((string_ci_expand_range_kernel<1>), dim3(grid), dim3(threads), sc_lds(threads), s, a, a.ta, (double*)D, r0, r1);
-    else hipLaunchKernelGGL((string_ci_expand_range_kernel<2>), dim3(grid), dim3(threads), sc_lds(threads), s, a, a.ta, (double*)D, r0, r1);
-    note_dispatch("qs::string_ci_expand_range_kernel<%d>", cw);
-    return launch_status("string CI range expand launch");
 }
 
 // The passes of one qs_string_ci_sigma_sym call over the packed rows, fixed by its arguments and the calling thread's
@@ -678,7 +578,7 @@ static int64_t sc_tri_next(int64_t b, int64_t n, int64_t most) {
 
 // bounds, where given, has room for the passes + 1 boundaries of a plan already known; the others stay within n + 1
 static ScTriPlan sc_tri_plan(int form, int64_t m, int64_t n, int64_t K, int64_t budget_bytes, int64_t* bounds, int64_t bounds_len) {
-    const int64_t budget = g_tune.string_ci_bytes > 0 ? g_tune.string_ci_bytes : (budget_bytes > 0 ? budget_bytes : kScBytes);
+    const int64_t budget = sc_budget(budget_bytes);
     const int64_t per = m * m * K * 8 * form_widths(form).aw;             // bytes per packed element of a panel
     ScTriPlan p{};
     // 2 ceil16(x) <= budget  <=>  x <= the multiple of 16 at or below budget / 2
@@ -723,27 +623,8 @@ struct Sc2Args {
     int64_t ia0;              // first alpha row of the pass
     int64_t pitch;            // elements between rows of the bra panel, T kc
     unsigned ntile;
-    int m2;
+    int m2, h;                // h: columns of one spin in the ket panel of the spin-resolved density, else unused
 };
-
-// (E_pq c)[Ia, Ib] from the two table entries of (Ia, pq) and (Ib, pq)
-template <int CW>
-__device__ __forceinline__ void sc_replaced(double (&v)[CW], const double* __restrict__ c, int32_t ea, int32_t eb, int64_t ia,
-                                            int64_t ib, int64_t na, int64_t nb) {
-    const int64_t ja = ea ? sc_target(ea, na) : -1, jb = eb ? sc_target(eb, nb) : -1;
-#pragma unroll
-    for (int w = 0; w < CW; ++w) v[w] = 0.0;
-    if (ja >= 0) {
-        const double* x = c + (ja * nb + ib) * CW;
-#pragma unroll
-        for (int w = 0; w < CW; ++w) v[w] = ea < 0 ? -x[w] : x[w];
-    }
-    if (jb >= 0) {
-        const double* x = c + (ia * nb + jb) * CW;
-#pragma unroll
-        for (int w = 0; w < CW; ++w) v[w] += eb < 0 ? -x[w] : x[w];
-    }
-}
 
 // The expand of one pass, alpha rows ia0 ... ia0 + gridDim.x / ntile - 1, in the layout of one operand of the Gram product.
 // KET: P[K, (pq)] -- a thread keeps the 16 values of a table chunk and writes them as one line of its determinant with
@@ -819,6 +700,18 @@ __global__ __launch_bounds__(kScBlock) void string_ci_expand_rows_kernel(const S
     }
 }
 
+// x = sum over t of part[t * stride + at], ascending
+template <int CW>
+__device__ __forceinline__ void sc_sum_partials(double (&x)[CW], const double* __restrict__ part, int64_t T, int64_t stride,
+                                                int64_t at) {
+#pragma unroll
+    for (int w = 0; w < CW; ++w) x[w] = 0.0;
+    for (int64_t t = 0; t < T; ++t) {
+#pragma unroll
+        for (int w = 0; w < CW; ++w) x[w] += part[(t * stride + at) * CW + w];
+    }
+}
+
 // Gamma[p,q,r,s] and rho[q m + p] from the T partial results part[t] (m^2 + 1, m^2): one thread per element of Gamma
 // (grid-stride), the partials summed in ascending t, the delta term one subtraction.
 template <int CW>
@@ -827,37 +720,19 @@ __global__ __launch_bounds__(kScRhoBlock) void string_ci_gamma_close_kernel(cons
     const int64_t m2 = (int64_t)m * m, total = m2 * m2, sc = (m2 + 1) * m2, step = (int64_t)gridDim.x * kScRhoBlock;
     for (int64_t idx = (int64_t)blockIdx.x * kScRhoBlock + threadIdx.x; idx < total; idx += step) {
         const int s = (int)(idx % m), r = (int)((idx / m) % m), q = (int)((idx / m2) % m), p = (int)(idx / (m2 * m));
-        const int64_t ex = ((int64_t)r * m + p) * m2 + q * m + s;          // X[(pr),(qs)] lies at row (rp)
         double x[CW];
-#pragma unroll
-        for (int w = 0; w < CW; ++w) x[w] = 0.0;
-        for (int64_t t = 0; t < T; ++t) {
-#pragma unroll
-            for (int w = 0; w < CW; ++w) x[w] += part[(t * sc + ex) * CW + w];
-        }
+        sc_sum_partials<CW>(x, part, T, sc, ((int64_t)r * m + p) * m2 + q * m + s);      // X[(pr),(qs)] lies at row (rp)
         if (q == r) {
-            const int64_t ee = total + p * m + s;                          // <bra| E_ps |ket>
             double e[CW];
-#pragma unroll
-            for (int w = 0; w < CW; ++w) e[w] = 0.0;
-            for (int64_t t = 0; t < T; ++t) {
-#pragma unroll
-                for (int w = 0; w < CW; ++w) e[w] += part[(t * sc + ee) * CW + w];
-            }
+            sc_sum_partials<CW>(e, part, T, sc, total + p * m + s);                      // <bra| E_ps |ket>
 #pragma unroll
             for (int w = 0; w < CW; ++w) x[w] = x[w] - e[w];
         }
 #pragma unroll
         for (int w = 0; w < CW; ++w) gamma[idx * CW + w] = x[w];
         if (r == 0 && s == 0) {
-            const int64_t ee = total + p * m + q;                          // <bra| E_pq |ket>
             double e[CW];
-#pragma unroll
-            for (int w = 0; w < CW; ++w) e[w] = 0.0;
-            for (int64_t t = 0; t < T; ++t) {
-#pragma unroll
-                for (int w = 0; w < CW; ++w) e[w] += part[(t * sc + ee) * CW + w];
-            }
+            sc_sum_partials<CW>(e, part, T, sc, total + p * m + q);                      // <bra| E_pq |ket>
 #pragma unroll
             for (int w = 0; w < CW; ++w) rho[((int64_t)q * m + p) * CW + w] = e[w];
         }
@@ -920,69 +795,6 @@ __global__ __launch_bounds__(kScBlock) void string_ci_spin_kernel(const ScArgs a
     }
 }
 
-// The schedule and the workspace of one qs_string_ci_density2 call: the one place that carves it.
-struct Sc2Plan {
-    int64_t rows, passes;     // alpha rows per pass (the last pass may have fewer), passes
-    int64_t T, kc, pitch;     // slices of kc determinants per pass, pitch = T kc >= rows nb
-    int64_t off_a, off_b;     // byte offsets of the bra and ket panels behind the partial results at 0
-    int64_t bytes;
-};
-
-static Sc2Plan sc2_layout(int cw, int64_t m, int64_t nb, int64_t rows) {
-    const int64_t m2 = m * m, es = 8 * cw, R = rows * nb;
-    Sc2Plan p{};
-    p.rows = rows;
-    // slices: tiles x T covers the compute units, the partial results stay below an eighth of the panels
-    int64_t T = cdiv(kSc2Cus, cdiv(m2 + 1, 128) * cdiv(m2, 128));
-    const int64_t cap = R / (4 * (m2 + 1));
-    T = T < cap ? T : cap;
-    T = T < 1 ? 1 : T;
-    p.kc = (cdiv(R, T) + 1) & ~int64_t(1);                               // even: every slice starts on a 16-byte boundary
-    p.T = cdiv(R, p.kc);
-    p.pitch = p.T * p.kc;
-    p.off_a = p.T * (m2 + 1) * m2 * es;                                   // (m^2 + 1) m^2 is even
-    p.off_b = p.off_a + (m2 + 1) * p.pitch * es;
-    p.bytes = p.off_b + p.pitch * m2 * es;
-    return p;
-}
-
-// The schedule of a pass-wise density: as many alpha rows per pass as keep the panels of `per_det` elements per determinant
-// within the budget (the calling thread's string_ci_bytes, else the argument, else the shipped one), at least one; then the
-// same passes of equal length where that costs no more.  layout(rows) carves the workspace; its panels lie behind off_a.
-template <class Layout>
-static auto sc2_schedule(int cw, int64_t na, int64_t nb, int64_t per_det, int64_t budget_bytes, Layout layout) {
-    const int64_t budget = g_tune.string_ci_bytes > 0 ? g_tune.string_ci_bytes : (budget_bytes > 0 ? budget_bytes : kScBytes);
-    int64_t rows = budget / (per_det * nb * 8 * cw);
-    rows = rows < 1 ? 1 : (rows < na ? rows : na);
-    auto p = layout(rows);
-    while (p.rows > 1 && p.bytes - p.off_a > budget) p = layout(p.rows - 1);      // the padding of the slices
-    const int64_t passes = cdiv(na, p.rows);
-    const auto even = layout(cdiv(na, passes));                           // the same passes, of equal length
-    if (even.bytes - even.off_a <= p.bytes - p.off_a) p = even;
-    p.passes = cdiv(na, p.rows);
-    return p;
-}
-
-static Sc2Plan sc2_plan(int cw, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes) {
-    return sc2_schedule(cw, na, nb, 2 * m * m + 1, budget_bytes, [&](int64_t rows) { return sc2_layout(cw, m, nb, rows); });
-}
-
-static int sc2_check(int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes) {
-    if (!dtype_ok(c_dtype)) return QS_ERR_BAD_DTYPE;
-    if (!sc_extents_ok(c_dtype == QS_C128 ? 1 : 0, m, na, nb, 1) || budget_bytes < 0) return QS_ERR_BAD_EXTENT;
-    return QS_OK;
-}
-
-template <int CW>
-static int sc2_expand(bool ket, const Sc2Args& a, const int32_t* ta, int64_t rows, void* P, hipStream_t s) {
-    const int threads = sc_threads(a.nb);
-    const unsigned grid = (unsigned)(rows * a.ntile);
-    if (ket) hipLaunchKernelGGL((string_ci_expand_rows_kernel<CW, true>), dim3(grid), dim3(threads), sc_lds(threads), s, a, ta, (double*)P);
-    else hipLaunchKernelGGL((string_ci_expand_rows_kernel<CW, false>), dim3(grid), dim3(threads), sc_lds(threads), s, a, ta, (double*)P);
-    note_dispatch(ket ? "qs::string_ci_expand_rows_kernel<%d, true>" : "qs::string_ci_expand_rows_kernel<%d, false>", CW);
-    return launch_status("string CI row expand launch");
-}
-
 // ---- spin-resolved densities (qs_string_ci_density2_spin) ----------------------------------------------------------------
 // E^s_pq = a+_ps a_qs acts on the strings of ONE spin: (E^a_pq c)[Ia, Ib] = sgn c[Ta[Ia,pq], Ib], (E^b_pq c)[Ia, Ib] =
 // sgn c[Ia, Tb[Ib,pq]].
@@ -997,16 +809,6 @@ static int sc2_expand(bool ket, const Sc2Args& a, const int32_t* ta, int64_t row
 //   part1[t] (m^2 + 1, 2 h) (+)= A[0 ... m^2, slice t] . B[slice t, :]           X^aa | X^ab, last row <E^a_qs> | <E^b_qs>
 //   part2[t] (m^2, h)       (+)= A[m^2 + 1 ..., slice t] . B[slice t, h ...]     X^bb
 // The beta-alpha block is never formed: Gamma^ba[p,q,r,s] = Gamma^ab[q,p,s,r].  The close is that of the spin sum.
-
-struct Sc3Args {
-    const int32_t* tb;        // (nb, m^2)
-    const double* c;          // (na, nb): bra or ket
-    int64_t na, nb;
-    int64_t ia0;              // first alpha row of the pass
-    int64_t pitch;            // elements between rows of the bra panel, T kc
-    unsigned ntile;
-    int m2, h;                // h: columns of one spin in the ket panel
-};
 
 // (E^s_pq c)[Ia, Ib] of one spin from its table entry e: a signed copy, or 0
 template <int CW>
@@ -1027,7 +829,7 @@ __device__ __forceinline__ void sc_replaced_spin(double (&v)[CW], const double* 
 // chunk all start on even columns).  Otherwise the rows of the bra panel, conjugated, written as they are formed, and
 // conj(c) as row m^2.
 template <int CW, bool KET>
-__global__ __launch_bounds__(kScBlock) void string_ci_expand_spin_kernel(const Sc3Args a, const int32_t* __restrict__ ta,
+__global__ __launch_bounds__(kScBlock) void string_ci_expand_spin_kernel(const Sc2Args a, const int32_t* __restrict__ ta,
                                                                         double* __restrict__ P) {
     extern __shared__ __attribute__((aligned(16))) int32_t sc_tb[];
     const int B = blockDim.x, t = threadIdx.x, m2 = a.m2, h = a.h;
@@ -1090,18 +892,6 @@ __global__ __launch_bounds__(kScBlock) void string_ci_expand_spin_kernel(const S
     }
 }
 
-// x = sum over t of part[t * stride + at], ascending
-template <int CW>
-__device__ __forceinline__ void sc_sum_partials(double (&x)[CW], const double* __restrict__ part, int64_t T, int64_t stride,
-                                                int64_t at) {
-#pragma unroll
-    for (int w = 0; w < CW; ++w) x[w] = 0.0;
-    for (int64_t t = 0; t < T; ++t) {
-#pragma unroll
-        for (int w = 0; w < CW; ++w) x[w] += part[(t * stride + at) * CW + w];
-    }
-}
-
 // The three Gamma and the two rho from the partial results part1[t] (m^2 + 1, 2 h) and part2[t] (m^2, h): one thread per
 // element of a Gamma (grid-stride over the 3 m^4 of them, alpha-alpha, alpha-beta, beta-beta), X read at the transposed row
 // (rp), the delta term for equal spins only.
@@ -1140,21 +930,40 @@ __global__ __launch_bounds__(kScRhoBlock) void string_ci_gamma_spin_close_kernel
     }
 }
 
-// The schedule and the workspace of one qs_string_ci_density2_spin call: the one place that carves it.
-struct Sc3Plan {
+// The schedule and the workspace of one qs_string_ci_density2 or qs_string_ci_density2_spin call: the one place that carves
+// it.  The spin-summed density has one block of partial results and leaves h and off_2 at 0.
+struct Sc2Plan {
     int64_t rows, passes;     // alpha rows per pass (the last pass may have fewer), passes
     int64_t T, kc, pitch;     // slices of kc determinants per pass, pitch = T kc >= rows nb
     int64_t h;                // columns of one spin in the ket panel
     int64_t off_2;            // byte offset of part2 behind part1 at 0
-    int64_t off_a, off_b;     // byte offsets of the bra and ket panels
+    int64_t off_a, off_b;     // byte offsets of the bra and ket panels behind the partial results
     int64_t bytes;
 };
 
+static Sc2Plan sc2_layout(int cw, int64_t m, int64_t nb, int64_t rows) {
+    const int64_t m2 = m * m, es = 8 * cw, R = rows * nb;
+    Sc2Plan p{};
+    p.rows = rows;
+    // slices: tiles x T covers the compute units, the partial results stay below an eighth of the panels
+    int64_t T = cdiv(kSc2Cus, cdiv(m2 + 1, 128) * cdiv(m2, 128));
+    const int64_t cap = R / (4 * (m2 + 1));
+    T = T < cap ? T : cap;
+    T = T < 1 ? 1 : T;
+    p.kc = (cdiv(R, T) + 1) & ~int64_t(1);                               // even: every slice starts on a 16-byte boundary
+    p.T = cdiv(R, p.kc);
+    p.pitch = p.T * p.kc;
+    p.off_a = p.T * (m2 + 1) * m2 * es;                                   // (m^2 + 1) m^2 is even
+    p.off_b = p.off_a + (m2 + 1) * p.pitch * es;
+    p.bytes = p.off_b + p.pitch * m2 * es;
+    return p;
+}
+
 static inline int64_t sc3_half(int cw, int64_t m) { return cw == 1 ? (m * m + 1) & ~int64_t(1) : m * m; }
 
-static Sc3Plan sc3_layout(int cw, int64_t m, int64_t nb, int64_t rows) {
+static Sc2Plan sc3_layout(int cw, int64_t m, int64_t nb, int64_t rows) {
     const int64_t m2 = m * m, es = 8 * cw, R = rows * nb;
-    Sc3Plan p{};
+    Sc2Plan p{};
     p.rows = rows;
     p.h = sc3_half(cw, m);
     // slices: tiles of the first product x T covers the compute units, the partial results (3 h (m^2 + 1) at the most per
@@ -1173,19 +982,109 @@ static Sc3Plan sc3_layout(int cw, int64_t m, int64_t nb, int64_t rows) {
     return p;
 }
 
-static Sc3Plan sc3_plan(int cw, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes) {
-    return sc2_schedule(cw, na, nb, 2 * m * m + 1 + 2 * sc3_half(cw, m), budget_bytes,
-                        [&](int64_t rows) { return sc3_layout(cw, m, nb, rows); });
+// The schedule of a pass-wise density: as many alpha rows per pass as keep the panels of `per_det` elements per determinant
+// within the budget, at least one; then the same passes of equal length where that costs no more.  layout(rows) carves the
+// workspace; its panels lie behind off_a.
+template <class Layout>
+static Sc2Plan sc2_schedule(int cw, int64_t na, int64_t nb, int64_t per_det, int64_t budget_bytes, Layout layout) {
+    const int64_t budget = sc_budget(budget_bytes);
+    int64_t rows = budget / (per_det * nb * 8 * cw);
+    rows = rows < 1 ? 1 : (rows < na ? rows : na);
+    Sc2Plan p = layout(rows);
+    while (p.rows > 1 && p.bytes - p.off_a > budget) p = layout(p.rows - 1);      // the padding of the slices
+    const int64_t passes = cdiv(na, p.rows);
+    const Sc2Plan even = layout(cdiv(na, passes));                        // the same passes, of equal length
+    if (even.bytes - even.off_a <= p.bytes - p.off_a) p = even;
+    p.passes = cdiv(na, p.rows);
+    return p;
 }
 
-template <int CW>
-static int sc3_expand(bool ket, const Sc3Args& a, const int32_t* ta, int64_t rows, void* P, hipStream_t s) {
+static Sc2Plan sc2_plan(bool spin, int cw, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes) {
+    if (spin)
+        return sc2_schedule(cw, na, nb, 2 * m * m + 1 + 2 * sc3_half(cw, m), budget_bytes,
+                            [&](int64_t rows) { return sc3_layout(cw, m, nb, rows); });
+    return sc2_schedule(cw, na, nb, 2 * m * m + 1, budget_bytes, [&](int64_t rows) { return sc2_layout(cw, m, nb, rows); });
+}
+
+static int sc2_check(int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes) {
+    if (!dtype_ok(c_dtype)) return QS_ERR_BAD_DTYPE;
+    if (!sc_extents_ok(c_dtype == QS_C128 ? 1 : 0, m, na, nb, 1) || budget_bytes < 0) return QS_ERR_BAD_EXTENT;
+    return QS_OK;
+}
+
+// the plan query of either density
+static int sc2_plan_query(bool spin, int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes, int64_t* plan) {
+    const int rc = sc2_check(c_dtype, m, na, nb, budget_bytes);
+    if (rc) return rc;
+    if (!plan) return QS_ERR_NULL_POINTER;
+    const Sc2Plan p = sc2_plan(spin, c_dtype == QS_C128 ? 2 : 1, m, na, nb, budget_bytes);
+    plan[0] = p.rows; plan[1] = p.passes; plan[2] = p.T; plan[3] = p.kc; plan[4] = p.bytes;
+    return QS_OK;
+}
+
+// one operand panel of a pass of `rows` alpha rows: the bra or the ket, spin-summed or spin-resolved
+static int sc2_expand(int cw, bool spin, bool ket, const Sc2Args& a, const int32_t* ta, int64_t rows, void* P, hipStream_t s) {
     const int threads = sc_threads(a.nb);
     const unsigned grid = (unsigned)(rows * a.ntile);
-    if (ket) hipLaunchKernelGGL((string_ci_expand_spin_kernel<CW, true>), dim3(grid), dim3(threads), sc_lds(threads), s, a, ta, (double*)P);
-    else hipLaunchKernelGGL((string_ci_expand_spin_kernel<CW, false>), dim3(grid), dim3(threads), sc_lds(threads), s, a, ta, (double*)P);
-    note_dispatch(ket ? "qs::string_ci_expand_spin_kernel<%d, true>" : "qs::string_ci_expand_spin_kernel<%d, false>", CW);
-    return launch_status("string CI spin-resolved expand launch");
+    auto launch = [&](auto kernel, const char* name) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), sc_lds(threads), s, a, ta, (double*)P);
+        note_dispatch("%s<%d, %s>", name, cw, ket ? "true" : "false");
+    };
+    with_width(cw, [&](auto CW) {
+        if (spin) ket ? launch(string_ci_expand_spin_kernel<CW, true>, "qs::string_ci_expand_spin_kernel")
+                      : launch(string_ci_expand_spin_kernel<CW, false>, "qs::string_ci_expand_spin_kernel");
+        else ket ? launch(string_ci_expand_rows_kernel<CW, true>, "qs::string_ci_expand_rows_kernel")
+                 : launch(string_ci_expand_rows_kernel<CW, false>, "qs::string_ci_expand_rows_kernel");
+    });
+    return launch_status("string CI density expand launch");
+}
+
+// The passes of either two-body density over alpha rows.  Per pass: zeros in the ragged tails of both panels, the bra panel
+// A (arows rows of pitch determinants), the ket panel B (bcols columns per determinant), and the batched product(s) that add
+// into the partial results at the head of work (split-k as a batch: slice t is columns t kc ... of A and rows t kc ... of B).
+static int sc2_passes(int c_dtype, bool spin, const Sc2Plan& p, const int32_t* ta, const int32_t* tb, int64_t m, int64_t na,
+                      int64_t nb, const void* bra, const void* ket, void* work, hipStream_t s) {
+    const int cw = c_dtype == QS_C128 ? 2 : 1;
+    const int64_t cs = 8 * cw, m2 = m * m, h = p.h;
+    const int64_t arows = spin ? 2 * m2 + 1 : m2 + 1, bcols = spin ? 2 * h : m2;
+    char* part = (char*)work;
+    char* A = part + p.off_a;
+    char* B = part + p.off_b;
+    Sc2Args a{};
+    a.tb = tb; a.na = na; a.nb = nb; a.pitch = p.pitch; a.m2 = (int)m2; a.h = (int)h;
+    a.ntile = (unsigned)cdiv(nb, sc_threads(nb));
+    for (int64_t pass = 0; pass < p.passes; ++pass) {
+        a.ia0 = pass * p.rows;
+        const int64_t rows = na - a.ia0 < p.rows ? na - a.ia0 : p.rows, R = rows * nb;
+        int rc;
+        if (R < p.pitch) {
+            // the tail of the last slice, and of a ragged last pass: zeros in both operands
+            rc = hip_status(hipMemset2DAsync(A + R * cs, (size_t)(p.pitch * cs), 0, (size_t)((p.pitch - R) * cs), (size_t)arows, s),
+                            "string CI bra panel tail");
+            if (rc) return rc;
+            rc = hip_status(hipMemsetAsync(B + R * bcols * cs, 0, (size_t)((p.pitch - R) * bcols * cs), s), "string CI ket panel tail");
+            if (rc) return rc;
+        }
+        a.c = (const double*)bra;
+        rc = sc2_expand(cw, spin, false, a, ta, rows, A, s);
+        if (rc) return rc;
+        a.c = (const double*)ket;
+        rc = sc2_expand(cw, spin, true, a, ta, rows, B, s);
+        if (rc) return rc;
+        // the first m^2 + 1 rows of A against all ket columns; spin-resolved, these are the alpha rows and conj(bra):
+        // X^aa | X^ab, and <E^a_qs> | <E^b_qs> in the last row
+        rc = gemm(Product{c_dtype, (const double*)A, (const double*)B, (double*)part, m2 + 1, bcols, p.kc, p.pitch, bcols, bcols, p.T,
+                          p.kc, p.kc * bcols, (m2 + 1) * bcols, pass > 0 ? 1 : 0},
+                  s);
+        if (rc) return rc;
+        if (!spin) continue;
+        // beta rows against the beta columns: X^bb
+        rc = gemm(Product{c_dtype, (const double*)(A + (m2 + 1) * p.pitch * cs), (const double*)(B + h * cs),
+                          (double*)(part + p.off_2), m2, h, p.kc, p.pitch, bcols, h, p.T, p.kc, p.kc * bcols, m2 * h, pass > 0 ? 1 : 0},
+                  s);
+        if (rc) return rc;
+    }
+    return QS_OK;
 }
 
 }  // namespace qs
@@ -1215,16 +1114,12 @@ int qs_string_ci_diagonal(int h_dtype, const void* ht, const void* ut, const int
     const int64_t es = (int64_t)elem_size(h_dtype);
     if (!aligned(ht, (size_t)es) || !aligned(ut, (size_t)es) || !aligned(sa, 8) || !aligned(sb, 8) || !aligned(D, 8))
         return QS_ERR_MISALIGNED;
-    const int64_t d_bytes = na * nb * 8;
-    if (overlaps(D, d_bytes, ht, m * m * es) || overlaps(D, d_bytes, ut, m * m * m * m * es) ||
-        overlaps(D, d_bytes, sa, na * 8) || overlaps(D, d_bytes, sb, nb * 8))
-        return QS_ERR_ALIAS;
+    if (int rc = sc_alias({{D, na * nb * 8}}, {{ht, m * m * es}, {ut, m * m * m * m * es}, {sa, na * 8}, {sb, nb * 8}})) return rc;
     const unsigned grid = sc_stride_grid(na * nb);
     hipStream_t s = (hipStream_t)stream;
-    if (h_dtype == QS_F64)
-        hipLaunchKernelGGL((string_ci_diagonal_kernel<1>), dim3(grid), dim3(kScRhoBlock), 0, s, (const double*)ht, (const double*)ut, sa, sb, na, nb, (int)m, D);
-    else
-        hipLaunchKernelGGL((string_ci_diagonal_kernel<2>), dim3(grid), dim3(kScRhoBlock), 0, s, (const double*)ht, (const double*)ut, sa, sb, na, nb, (int)m, D);
+    with_width(h_dtype == QS_F64 ? 1 : 2, [&](auto HW) {
+        hipLaunchKernelGGL((string_ci_diagonal_kernel<HW>), dim3(grid), dim3(kScRhoBlock), 0, s, (const double*)ht, (const double*)ut, sa, sb, na, nb, (int)m, D);
+    });
     note_dispatch("qs::string_ci_diagonal_kernel<%d>", h_dtype == QS_F64 ? 1 : 2);
     return launch_status("string CI diagonal launch");
 }
@@ -1240,8 +1135,7 @@ int64_t qs_string_ci_group(int h_dtype, int c_dtype, int64_t m, int64_t na, int6
     const int form = tensor_form(h_dtype, c_dtype);
     if (form < 0) return form;
     if (!sc_extents_ok(form, m, na, nb, 1) || K < 1 || budget_bytes < 0) return QS_ERR_BAD_EXTENT;
-    const int64_t budget = g_tune.string_ci_bytes > 0 ? g_tune.string_ci_bytes : (budget_bytes > 0 ? budget_bytes : kScBytes);
-    int64_t g = budget / (2 * sc_panel_bytes(form, m, na, nb, 1));
+    int64_t g = sc_budget(budget_bytes) / (2 * sc_panel_bytes(form, m, na, nb, 1));
     const int64_t cols = 0x7fffffffLL / (na * nb * (form == 2 ? 2 : 1));      // the product's 32-bit extent
     g = g < cols ? g : cols;
     return g < 1 ? 1 : (g < K ? g : K);
@@ -1252,40 +1146,13 @@ int qs_string_ci_sigma(int h_dtype, int c_dtype, const void* k, const void* W, c
                        int64_t work_bytes, void* stream) {
     dispatch_reset();
     const int form = tensor_form(h_dtype, c_dtype);
-    if (form < 0) return form;
-    if (!sc_extents_ok(form, m, na, nb, K)) return QS_ERR_BAD_EXTENT;
-    if (!k || !W || !ta || !tb || !c || !sigma || !work) return QS_ERR_NULL_POINTER;
-    const int64_t hs = (int64_t)elem_size(h_dtype), cs = (int64_t)elem_size(c_dtype);
-    if (!aligned(k, (size_t)hs) || !aligned(W, (size_t)hs) || !aligned(ta, 4) || !aligned(tb, 4) || !aligned(c, (size_t)cs) ||
-        !aligned(sigma, (size_t)cs) || !aligned(work, 16))
-        return QS_ERR_MISALIGNED;
-    const int64_t panel = sc_panel_bytes(form, m, na, nb, K);
-    if (work_bytes < 2 * panel) return QS_ERR_WORKSPACE;
-    const int64_t m2 = m * m, s_bytes = K * na * nb * cs;
-    if (overlaps(sigma, s_bytes, c, s_bytes) || overlaps(sigma, s_bytes, W, m2 * m2 * hs) || overlaps(sigma, s_bytes, k, m2 * hs) ||
-        overlaps(sigma, s_bytes, ta, na * m2 * 4) || overlaps(sigma, s_bytes, tb, nb * m2 * 4) ||
-        overlaps(sigma, s_bytes, work, 2 * panel) || overlaps(work, 2 * panel, c, s_bytes) || overlaps(work, 2 * panel, W, m2 * m2 * hs) ||
-        overlaps(work, 2 * panel, k, m2 * hs) || overlaps(work, 2 * panel, ta, na * m2 * 4) || overlaps(work, 2 * panel, tb, nb * m2 * 4))
-        return QS_ERR_ALIAS;
-
-    hipStream_t s = (hipStream_t)stream;
-    const FormWidths fw = form_widths(form);
-    char* D = (char*)work;
-    char* G = D + panel;
-    ScArgs a = sc_args(ta, tb, c, m, na, nb, K);
-    int rc = sc_expand(fw.aw, a, D, s);
-    if (rc) return rc;
-    // real W against complex c: the re / im pairs of D are columns of a real product
-    rc = gemm(packed(h_dtype, W, D, G, m2, K * na * nb * (fw.aw / fw.uw), m2), s);
-    if (rc) return rc;
-    a.kk = (const double*)k; a.G = (const double*)G; a.out = (double*)sigma;
-    const int threads = sc_threads(nb);
-    const unsigned grid = (unsigned)(K * na * a.ntile);
-    with_form(form, [&](auto FORM) {
-        hipLaunchKernelGGL((string_ci_fold_kernel<FORM>), dim3(grid), dim3(threads), sc_lds(threads), s, a);
-        note_dispatch("qs::string_ci_fold_kernel<%d>", (int)FORM);
-    });
-    return launch_status("string CI fold launch");
+    int64_t panel = 0;
+    if (int rc = sc_sigma_check(form, h_dtype, c_dtype, k, W, ta, tb, m, na, nb, c, K, sigma, work, work_bytes, true,
+                                [&] { return 2 * (panel = sc_panel_bytes(form, m, na, nb, K)); }))
+        return rc;
+    // one pass over all rows
+    return sc_sigma_passes<ScRect>(form, h_dtype, k, W, sc_args(ta, tb, c, m, na, nb, K), sigma, work, panel,
+                                   [&](int64_t) { return na; }, (hipStream_t)stream);
 }
 
 int qs_string_ci_sigma_plan(int h_dtype, int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t K, int64_t budget_bytes,
@@ -1304,46 +1171,12 @@ int qs_string_ci_sigma_rows(int h_dtype, int c_dtype, const void* k, const void*
                             int64_t work_bytes, int64_t budget_bytes, void* stream) {
     dispatch_reset();
     const int form = tensor_form(h_dtype, c_dtype);
-    if (form < 0) return form;
-    if (!sc_extents_ok(form, m, na, nb, K) || budget_bytes < 0) return QS_ERR_BAD_EXTENT;
-    if (!k || !W || !ta || !tb || !c || !sigma || !work) return QS_ERR_NULL_POINTER;
-    const int64_t hs = (int64_t)elem_size(h_dtype), cs = (int64_t)elem_size(c_dtype);
-    if (!aligned(k, (size_t)hs) || !aligned(W, (size_t)hs) || !aligned(ta, 4) || !aligned(tb, 4) || !aligned(c, (size_t)cs) ||
-        !aligned(sigma, (size_t)cs) || !aligned(work, 16))
-        return QS_ERR_MISALIGNED;
-    const ScRowsPlan p = sc_rows_plan(form, m, na, nb, K, budget_bytes);
-    const int64_t w_bytes = 2 * p.panel;
-    if (work_bytes < w_bytes) return QS_ERR_WORKSPACE;
-    const int64_t m2 = m * m, s_bytes = K * na * nb * cs;
-    const struct { const void* at; int64_t bytes; } in[] = {{c, s_bytes}, {W, m2 * m2 * hs}, {k, m2 * hs}, {ta, na * m2 * 4}, {tb, nb * m2 * 4}};
-    for (const auto& x : in)
-        if (overlaps(sigma, s_bytes, x.at, x.bytes) || overlaps(work, w_bytes, x.at, x.bytes)) return QS_ERR_ALIAS;
-    if (overlaps(sigma, s_bytes, work, w_bytes)) return QS_ERR_ALIAS;
-
-    hipStream_t s = (hipStream_t)stream;
-    const FormWidths fw = form_widths(form);
-    char* D = (char*)work;
-    char* G = D + p.panel;
-    ScArgs a = sc_args(ta, tb, c, m, na, nb, K);
-    a.kk = (const double*)k; a.G = (const double*)G;
-    const int threads = sc_threads(nb);
-    const unsigned grid = (unsigned)(K * na * a.ntile);
-    for (int64_t r0 = 0; r0 < na; r0 += p.rows) {
-        const int64_t r1 = r0 + p.rows < na ? r0 + p.rows : na;
-        int rc = sc_expand_range(fw.aw, a, D, r0, r1, s);
-        if (rc) return rc;
-        // real W against complex c: the re / im pairs of D_p are columns of a real product
-        rc = gemm(packed(h_dtype, W, D, G, m2, K * (r1 - r0) * nb * (fw.aw / fw.uw), m2), s);
-        if (rc) return rc;
-        with_form(form, [&](auto FORM) {
-            hipLaunchKernelGGL((string_ci_fold_range_kernel<FORM>), dim3(grid), dim3(threads), sc_lds(threads), s, a, a.ta,
-                               (double*)sigma, r0, r1);
-            note_dispatch("qs::string_ci_fold_range_kernel<%d>", (int)FORM);
-        });
-        rc = launch_status("string CI range fold launch");
-        if (rc) return rc;
-    }
-    return QS_OK;
+    ScRowsPlan p{};
+    if (int rc = sc_sigma_check(form, h_dtype, c_dtype, k, W, ta, tb, m, na, nb, c, K, sigma, work, work_bytes, budget_bytes >= 0,
+                                [&] { return 2 * (p = sc_rows_plan(form, m, na, nb, K, budget_bytes)).panel; }))
+        return rc;
+    return sc_sigma_passes<ScRect>(form, h_dtype, k, W, sc_args(ta, tb, c, m, na, nb, K), sigma, work, p.panel,
+                                   [&](int64_t r0) { return r0 + p.rows < na ? r0 + p.rows : na; }, (hipStream_t)stream);
 }
 
 int qs_string_ci_sigma_sym_plan(int h_dtype, int c_dtype, int64_t m, int64_t n, int64_t K, int64_t budget_bytes,
@@ -1366,53 +1199,21 @@ int qs_string_ci_sigma_sym(int h_dtype, int c_dtype, const void* k, const void* 
                            int64_t budget_bytes, void* stream) {
     dispatch_reset();
     const int form = tensor_form(h_dtype, c_dtype);
-    if (form < 0) return form;
-    if ((parity != 1 && parity != -1) || budget_bytes < 0 || !sc_extents_ok(form, m, n, n, K)) return QS_ERR_BAD_EXTENT;
-    if (!k || !W || !t || !c || !sigma || !work) return QS_ERR_NULL_POINTER;
-    const int64_t hs = (int64_t)elem_size(h_dtype), cs = (int64_t)elem_size(c_dtype);
-    if (!aligned(k, (size_t)hs) || !aligned(W, (size_t)hs) || !aligned(t, 4) || !aligned(c, (size_t)cs) ||
-        !aligned(sigma, (size_t)cs) || !aligned(work, 16))
-        return QS_ERR_MISALIGNED;
-    const ScTriPlan p = sc_tri_plan(form, m, n, K, budget_bytes, nullptr, 0);
-    const int64_t w_bytes = 2 * p.panel;
-    if (work_bytes < w_bytes) return QS_ERR_WORKSPACE;
-    const int64_t m2 = m * m, s_bytes = K * n * n * cs;
-    const struct { const void* at; int64_t bytes; } in[] = {{c, s_bytes}, {W, m2 * m2 * hs}, {k, m2 * hs}, {t, n * m2 * 4}};
-    for (const auto& x : in)
-        if (overlaps(sigma, s_bytes, x.at, x.bytes) || overlaps(work, w_bytes, x.at, x.bytes)) return QS_ERR_ALIAS;
-    if (overlaps(sigma, s_bytes, work, w_bytes)) return QS_ERR_ALIAS;
-
+    ScTriPlan p{};
+    if (int rc = sc_sigma_check(form, h_dtype, c_dtype, k, W, t, t, m, n, n, c, K, sigma, work, work_bytes,
+                                (parity == 1 || parity == -1) && budget_bytes >= 0,
+                                [&] { return 2 * (p = sc_tri_plan(form, m, n, K, budget_bytes, nullptr, 0)).panel; }))
+        return rc;
     hipStream_t s = (hipStream_t)stream;
-    const FormWidths fw = form_widths(form);
-    char* D = (char*)work;
-    char* G = D + p.panel;
-    ScArgs a = sc_args(t, t, c, m, n, n, K);
-    a.kk = (const double*)k; a.G = (const double*)G;
-    const int threads = sc_threads(n);
-    const size_t lds = sc_lds(threads);
-    for (int64_t r0 = 0; r0 < n;) {
-        const int64_t r1 = sc_tri_next(r0, n, p.most), len = sc_off(r1) - sc_off(r0);
-        if (fw.aw == 1) hipLaunchKernelGGL((string_ci_expand_tri_kernel<1>), dim3((unsigned)((r1 - r0) * a.ntile)), dim3(threads), lds, s, a, t, (double*)D, r0, r1);
-        else hipLaunchKernelGGL((string_ci_expand_tri_kernel<2>), dim3((unsigned)((r1 - r0) * a.ntile)), dim3(threads), lds, s, a, t, (double*)D, r0, r1);
-        note_dispatch("qs::string_ci_expand_tri_kernel<%d>", fw.aw);
-        int rc = launch_status("string CI packed expand launch");
-        if (rc) return rc;
-        // real W against complex c: the re / im pairs of D_p are columns of a real product
-        rc = gemm(packed(h_dtype, W, D, G, m2, K * len * (fw.aw / fw.uw), m2), s);
-        if (rc) return rc;
-        with_form(form, [&](auto FORM) {
-            hipLaunchKernelGGL((string_ci_fold_tri_kernel<FORM>), dim3((unsigned)(K * n * a.ntile)), dim3(threads), lds, s, a, t,
-                               (double*)sigma, r0, r1);
-            note_dispatch("qs::string_ci_fold_tri_kernel<%d>", (int)FORM);
-        });
-        rc = launch_status("string CI packed fold launch");
-        if (rc) return rc;
-        r0 = r1;
-    }
+    if (int rc = sc_sigma_passes<ScTri>(form, h_dtype, k, W, sc_args(t, t, c, m, n, n, K), sigma, work, p.panel,
+                                        [&](int64_t r0) { return sc_tri_next(r0, n, p.most); }, s))
+        return rc;
+    const int cw = form_widths(form).aw;
     const unsigned nt = (unsigned)cdiv(n, kScSymTile);
-    if (fw.aw == 1) hipLaunchKernelGGL((string_ci_symmetrize_kernel<1>), dim3((unsigned)K * nt * nt), dim3(kScRhoBlock), 0, s, (double*)sigma, n, nt, parity < 0 ? 1 : 0);
-    else hipLaunchKernelGGL((string_ci_symmetrize_kernel<2>), dim3((unsigned)K * nt * nt), dim3(kScRhoBlock), 0, s, (double*)sigma, n, nt, parity < 0 ? 1 : 0);
-    note_dispatch("qs::string_ci_symmetrize_kernel<%d>", fw.aw);
+    with_width(cw, [&](auto CW) {
+        hipLaunchKernelGGL((string_ci_symmetrize_kernel<CW>), dim3((unsigned)K * nt * nt), dim3(kScRhoBlock), 0, s, (double*)sigma, n, nt, parity < 0 ? 1 : 0);
+    });
+    note_dispatch("qs::string_ci_symmetrize_kernel<%d>", cw);
     return launch_status("string CI symmetrise launch");
 }
 
@@ -1429,19 +1230,15 @@ int qs_string_ci_density1(int c_dtype, const int32_t* ta, const int32_t* tb, int
         return QS_ERR_MISALIGNED;
     const int64_t panel = sc_panel_bytes(form, m, na, nb, 1);
     if (work_bytes < panel) return QS_ERR_WORKSPACE;
-    const int64_t m2 = m * m, r_bytes = m2 * cs, v_bytes = na * nb * cs;
-    if (overlaps(rho, r_bytes, bra, v_bytes) || overlaps(rho, r_bytes, ket, v_bytes) || overlaps(rho, r_bytes, ta, na * m2 * 4) ||
-        overlaps(rho, r_bytes, tb, nb * m2 * 4) || overlaps(rho, r_bytes, work, panel) || overlaps(work, panel, bra, v_bytes) ||
-        overlaps(work, panel, ket, v_bytes) || overlaps(work, panel, ta, na * m2 * 4) || overlaps(work, panel, tb, nb * m2 * 4))
-        return QS_ERR_ALIAS;
+    const int64_t m2 = m * m, v_bytes = na * nb * cs;
+    if (int rc = sc_alias({{rho, m2 * cs}, {work, panel}}, {{bra, v_bytes}, {ket, v_bytes}, {ta, na * m2 * 4}, {tb, nb * m2 * 4}})) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int cw = form_widths(form).aw;
-    const int rc = sc_expand(cw, sc_args(ta, tb, ket, m, na, nb, 1), work, s);
-    if (rc) return rc;
-    if (cw == 1)
-        hipLaunchKernelGGL((string_ci_dot_kernel<1>), dim3((unsigned)m2), dim3(kScRhoBlock), 0, s, (const double*)bra, (const double*)work, (double*)rho, (int)m, na * nb);
-    else
-        hipLaunchKernelGGL((string_ci_dot_kernel<2>), dim3((unsigned)m2), dim3(kScRhoBlock), 0, s, (const double*)bra, (const double*)work, (double*)rho, (int)m, na * nb);
+    // D of the ket, whole: the rectangle's one pass
+    if (int rc = sc_expand(cw, sc_args(ta, tb, ket, m, na, nb, 1), work, ScRect{0, na, nb}, s)) return rc;
+    with_width(cw, [&](auto CW) {
+        hipLaunchKernelGGL((string_ci_dot_kernel<CW>), dim3((unsigned)m2), dim3(kScRhoBlock), 0, s, (const double*)bra, (const double*)work, (double*)rho, (int)m, na * nb);
+    });
     note_dispatch("qs::string_ci_dot_kernel<%d>", cw);
     return launch_status("string CI density launch");
 }
@@ -1449,16 +1246,11 @@ int qs_string_ci_density1(int c_dtype, const int32_t* ta, const int32_t* tb, int
 int64_t qs_string_ci_density2_workspace(int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes) {
     const int rc = sc2_check(c_dtype, m, na, nb, budget_bytes);
     if (rc) return rc;
-    return sc2_plan(c_dtype == QS_C128 ? 2 : 1, m, na, nb, budget_bytes).bytes;
+    return sc2_plan(false, c_dtype == QS_C128 ? 2 : 1, m, na, nb, budget_bytes).bytes;
 }
 
 int qs_string_ci_density2_plan(int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes, int64_t* plan) {
-    const int rc = sc2_check(c_dtype, m, na, nb, budget_bytes);
-    if (rc) return rc;
-    if (!plan) return QS_ERR_NULL_POINTER;
-    const Sc2Plan p = sc2_plan(c_dtype == QS_C128 ? 2 : 1, m, na, nb, budget_bytes);
-    plan[0] = p.rows; plan[1] = p.passes; plan[2] = p.T; plan[3] = p.kc; plan[4] = p.bytes;
-    return QS_OK;
+    return sc2_plan_query(false, c_dtype, m, na, nb, budget_bytes, plan);
 }
 
 int qs_string_ci_density2(int c_dtype, const int32_t* ta, const int32_t* tb, int64_t m, int64_t na, int64_t nb,
@@ -1473,51 +1265,18 @@ int qs_string_ci_density2(int c_dtype, const int32_t* ta, const int32_t* tb, int
         !aligned(rho, (size_t)cs) || !aligned(work, 16))
         return QS_ERR_MISALIGNED;
     const int cw = c_dtype == QS_C128 ? 2 : 1;
-    const Sc2Plan p = sc2_plan(cw, m, na, nb, budget_bytes);
+    const Sc2Plan p = sc2_plan(false, cw, m, na, nb, budget_bytes);
     if (work_bytes < p.bytes) return QS_ERR_WORKSPACE;
-    const int64_t m2 = m * m, g_bytes = m2 * m2 * cs, r_bytes = m2 * cs, v_bytes = na * nb * cs;
-    const struct { const void* at; int64_t bytes; } in[] = {{bra, v_bytes}, {ket, v_bytes}, {ta, na * m2 * 4}, {tb, nb * m2 * 4}};
-    for (const auto& x : in)
-        if (overlaps(gamma, g_bytes, x.at, x.bytes) || overlaps(rho, r_bytes, x.at, x.bytes) || overlaps(work, p.bytes, x.at, x.bytes))
-            return QS_ERR_ALIAS;
-    if (overlaps(gamma, g_bytes, rho, r_bytes) || overlaps(gamma, g_bytes, work, p.bytes) || overlaps(rho, r_bytes, work, p.bytes))
-        return QS_ERR_ALIAS;
+    const int64_t m2 = m * m, v_bytes = na * nb * cs;
+    rc = sc_alias({{work, p.bytes}, {gamma, m2 * m2 * cs}, {rho, m2 * cs}}, {{bra, v_bytes}, {ket, v_bytes}, {ta, na * m2 * 4}, {tb, nb * m2 * 4}});
+    if (rc) return rc;
 
     hipStream_t s = (hipStream_t)stream;
-    char* part = (char*)work;
-    char* A = part + p.off_a;
-    char* B = part + p.off_b;
-    Sc2Args a{};
-    a.tb = tb; a.na = na; a.nb = nb; a.pitch = p.pitch; a.m2 = (int)m2;
-    a.ntile = (unsigned)cdiv(nb, sc_threads(nb));
-    for (int64_t pass = 0; pass < p.passes; ++pass) {
-        a.ia0 = pass * p.rows;
-        const int64_t rows = na - a.ia0 < p.rows ? na - a.ia0 : p.rows, R = rows * nb;
-        if (R < p.pitch) {
-            // the tail of the last slice, and of a ragged last pass: zeros in both operands
-            rc = hip_status(hipMemset2DAsync(A + R * cs, (size_t)(p.pitch * cs), 0, (size_t)((p.pitch - R) * cs), (size_t)(m2 + 1), s),
-                            "string CI bra panel tail");
-            if (rc) return rc;
-            rc = hip_status(hipMemsetAsync(B + R * m2 * cs, 0, (size_t)((p.pitch - R) * m2 * cs), s), "string CI ket panel tail");
-            if (rc) return rc;
-        }
-        a.c = (const double*)bra;
-        rc = cw == 1 ? sc2_expand<1>(false, a, ta, rows, A, s) : sc2_expand<2>(false, a, ta, rows, A, s);
-        if (rc) return rc;
-        a.c = (const double*)ket;
-        rc = cw == 1 ? sc2_expand<1>(true, a, ta, rows, B, s) : sc2_expand<2>(true, a, ta, rows, B, s);
-        if (rc) return rc;
-        // split-k as a batch: slice t is columns t kc ... of A and rows t kc ... of B, every pass adds into the same partials
-        rc = gemm(Product{c_dtype, (const double*)A, (const double*)B, (double*)part, m2 + 1, m2, p.kc, p.pitch, m2, m2, p.T, p.kc,
-                          p.kc * m2, (m2 + 1) * m2, pass > 0 ? 1 : 0},
-                  s);
-        if (rc) return rc;
-    }
-    const unsigned grid = sc_stride_grid(m2 * m2);
-    if (cw == 1)
-        hipLaunchKernelGGL((string_ci_gamma_close_kernel<1>), dim3(grid), dim3(kScRhoBlock), 0, s, (const double*)part, p.T, (int)m, (double*)gamma, (double*)rho);
-    else
-        hipLaunchKernelGGL((string_ci_gamma_close_kernel<2>), dim3(grid), dim3(kScRhoBlock), 0, s, (const double*)part, p.T, (int)m, (double*)gamma, (double*)rho);
+    rc = sc2_passes(c_dtype, false, p, ta, tb, m, na, nb, bra, ket, work, s);
+    if (rc) return rc;
+    with_width(cw, [&](auto CW) {
+        hipLaunchKernelGGL((string_ci_gamma_close_kernel<CW>), dim3(sc_stride_grid(m2 * m2)), dim3(kScRhoBlock), 0, s, (const double*)work, p.T, (int)m, (double*)gamma, (double*)rho);
+    });
     note_dispatch("qs::string_ci_gamma_close_kernel<%d>", cw);
     return launch_status("string CI two-body density close launch");
 }
@@ -1525,16 +1284,11 @@ int qs_string_ci_density2(int c_dtype, const int32_t* ta, const int32_t* tb, int
 int64_t qs_string_ci_density2_spin_workspace(int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes) {
     const int rc = sc2_check(c_dtype, m, na, nb, budget_bytes);
     if (rc) return rc;
-    return sc3_plan(c_dtype == QS_C128 ? 2 : 1, m, na, nb, budget_bytes).bytes;
+    return sc2_plan(true, c_dtype == QS_C128 ? 2 : 1, m, na, nb, budget_bytes).bytes;
 }
 
 int qs_string_ci_density2_spin_plan(int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes, int64_t* plan) {
-    const int rc = sc2_check(c_dtype, m, na, nb, budget_bytes);
-    if (rc) return rc;
-    if (!plan) return QS_ERR_NULL_POINTER;
-    const Sc3Plan p = sc3_plan(c_dtype == QS_C128 ? 2 : 1, m, na, nb, budget_bytes);
-    plan[0] = p.rows; plan[1] = p.passes; plan[2] = p.T; plan[3] = p.kc; plan[4] = p.bytes;
-    return QS_OK;
+    return sc2_plan_query(true, c_dtype, m, na, nb, budget_bytes, plan);
 }
 
 int qs_string_ci_density2_spin(int c_dtype, const int32_t* ta, const int32_t* tb, int64_t m, int64_t na, int64_t nb,
@@ -1550,66 +1304,21 @@ int qs_string_ci_density2_spin(int c_dtype, const int32_t* ta, const int32_t* tb
         !aligned(work, 16))
         return QS_ERR_MISALIGNED;
     const int cw = c_dtype == QS_C128 ? 2 : 1;
-    const Sc3Plan p = sc3_plan(cw, m, na, nb, budget_bytes);
+    const Sc2Plan p = sc2_plan(true, cw, m, na, nb, budget_bytes);
     if (work_bytes < p.bytes) return QS_ERR_WORKSPACE;
     const int64_t m2 = m * m, g_bytes = m2 * m2 * cs, r_bytes = m2 * cs, v_bytes = na * nb * cs;
-    const struct { const void* at; int64_t bytes; } in[] = {{bra, v_bytes}, {ket, v_bytes}, {ta, na * m2 * 4}, {tb, nb * m2 * 4}};
-    // the workspace, then the five outputs: each against every input and against those before it
-    const struct { const void* at; int64_t bytes; } out[] = {{work, p.bytes}, {gamma_aa, g_bytes}, {gamma_ab, g_bytes}, {gamma_bb, g_bytes},
-                                                             {rho_a, r_bytes}, {rho_b, r_bytes}};
-    for (int i = 0; i < 6; ++i) {
-        for (const auto& x : in)
-            if (overlaps(out[i].at, out[i].bytes, x.at, x.bytes)) return QS_ERR_ALIAS;
-        for (int j = 0; j < i; ++j)
-            if (overlaps(out[i].at, out[i].bytes, out[j].at, out[j].bytes)) return QS_ERR_ALIAS;
-    }
+    rc = sc_alias({{work, p.bytes}, {gamma_aa, g_bytes}, {gamma_ab, g_bytes}, {gamma_bb, g_bytes}, {rho_a, r_bytes}, {rho_b, r_bytes}},
+                  {{bra, v_bytes}, {ket, v_bytes}, {ta, na * m2 * 4}, {tb, nb * m2 * 4}});
+    if (rc) return rc;
 
     hipStream_t s = (hipStream_t)stream;
-    char* part1 = (char*)work;
-    char* part2 = part1 + p.off_2;
-    char* A = part1 + p.off_a;
-    char* B = part1 + p.off_b;
-    const int64_t h = p.h;
-    Sc3Args a{};
-    a.tb = tb; a.na = na; a.nb = nb; a.pitch = p.pitch; a.m2 = (int)m2; a.h = (int)h;
-    a.ntile = (unsigned)cdiv(nb, sc_threads(nb));
-    for (int64_t pass = 0; pass < p.passes; ++pass) {
-        a.ia0 = pass * p.rows;
-        const int64_t rows = na - a.ia0 < p.rows ? na - a.ia0 : p.rows, R = rows * nb;
-        if (R < p.pitch) {
-            // the tail of the last slice, and of a ragged last pass: zeros in both operands
-            rc = hip_status(hipMemset2DAsync(A + R * cs, (size_t)(p.pitch * cs), 0, (size_t)((p.pitch - R) * cs), (size_t)(2 * m2 + 1), s),
-                            "string CI spin-resolved bra panel tail");
-            if (rc) return rc;
-            rc = hip_status(hipMemsetAsync(B + R * 2 * h * cs, 0, (size_t)((p.pitch - R) * 2 * h * cs), s),
-                            "string CI spin-resolved ket panel tail");
-            if (rc) return rc;
-        }
-        a.c = (const double*)bra;
-        rc = cw == 1 ? sc3_expand<1>(false, a, ta, rows, A, s) : sc3_expand<2>(false, a, ta, rows, A, s);
-        if (rc) return rc;
-        a.c = (const double*)ket;
-        rc = cw == 1 ? sc3_expand<1>(true, a, ta, rows, B, s) : sc3_expand<2>(true, a, ta, rows, B, s);
-        if (rc) return rc;
-        // split-k as a batch over the T slices, as in qs_string_ci_density2; every pass adds into the same partials.
-        // alpha rows and conj(bra) against all ket columns: X^aa | X^ab, and <E^a_qs> | <E^b_qs> in the last row
-        rc = gemm(Product{c_dtype, (const double*)A, (const double*)B, (double*)part1, m2 + 1, 2 * h, p.kc, p.pitch, 2 * h, 2 * h, p.T,
-                          p.kc, p.kc * 2 * h, (m2 + 1) * 2 * h, pass > 0 ? 1 : 0},
-                  s);
-        if (rc) return rc;
-        // beta rows against the beta columns: X^bb
-        rc = gemm(Product{c_dtype, (const double*)(A + (m2 + 1) * p.pitch * cs), (const double*)(B + h * cs), (double*)part2, m2, h, p.kc,
-                          p.pitch, 2 * h, h, p.T, p.kc, p.kc * 2 * h, m2 * h, pass > 0 ? 1 : 0},
-                  s);
-        if (rc) return rc;
-    }
-    const unsigned grid = sc_stride_grid(3 * m2 * m2);
-    if (cw == 1)
-        hipLaunchKernelGGL((string_ci_gamma_spin_close_kernel<1>), dim3(grid), dim3(kScRhoBlock), 0, s, (const double*)part1, (const double*)part2,
-                           p.T, (int)m, (int)h, (double*)gamma_aa, (double*)gamma_ab, (double*)gamma_bb, (double*)rho_a, (double*)rho_b);
-    else
-        hipLaunchKernelGGL((string_ci_gamma_spin_close_kernel<2>), dim3(grid), dim3(kScRhoBlock), 0, s, (const double*)part1, (const double*)part2,
-                           p.T, (int)m, (int)h, (double*)gamma_aa, (double*)gamma_ab, (double*)gamma_bb, (double*)rho_a, (double*)rho_b);
+    rc = sc2_passes(c_dtype, true, p, ta, tb, m, na, nb, bra, ket, work, s);
+    if (rc) return rc;
+    with_width(cw, [&](auto CW) {
+        hipLaunchKernelGGL((string_ci_gamma_spin_close_kernel<CW>), dim3(sc_stride_grid(3 * m2 * m2)), dim3(kScRhoBlock), 0, s,
+                           (const double*)work, (const double*)((char*)work + p.off_2), p.T, (int)m, (int)p.h, (double*)gamma_aa,
+                           (double*)gamma_ab, (double*)gamma_bb, (double*)rho_a, (double*)rho_b);
+    });
     note_dispatch("qs::string_ci_gamma_spin_close_kernel<%d>", cw);
     return launch_status("string CI spin-resolved density close launch");
 }
@@ -1623,18 +1332,17 @@ int qs_string_ci_spin_squared(int c_dtype, const int32_t* ta, const int32_t* tb,
     const int64_t cs = (int64_t)elem_size(c_dtype);
     if (!aligned(ta, 4) || !aligned(tb, 4) || !aligned(c, (size_t)cs) || !aligned(out, (size_t)cs)) return QS_ERR_MISALIGNED;
     const int64_t m2 = m * m, o_bytes = K * na * nb * cs;
-    if (overlaps(out, o_bytes, c, o_bytes) || overlaps(out, o_bytes, ta, na * m2 * 4) || overlaps(out, o_bytes, tb, nb * m2 * 4))
-        return QS_ERR_ALIAS;
+    if (int rc = sc_alias({{out, o_bytes}}, {{c, o_bytes}, {ta, na * m2 * 4}, {tb, nb * m2 * 4}})) return rc;
     const double sz = 0.5 * (double)(Na - Nb), s0 = sz * (sz + 1.0) + (double)Nb;       // multiples of 1/4: exact
     const ScArgs a = sc_args(ta, tb, c, m, na, nb, K);
     const int threads = sc_threads(nb);
     const unsigned grid = (unsigned)(cdiv(K, kScSpinG) * na * a.ntile);
     hipStream_t s = (hipStream_t)stream;
-    if (c_dtype == QS_F64)
-        hipLaunchKernelGGL((string_ci_spin_kernel<1>), dim3(grid), dim3(threads), sc_lds(threads), s, a, ta, (double*)out, s0, (int)m);
-    else
-        hipLaunchKernelGGL((string_ci_spin_kernel<2>), dim3(grid), dim3(threads), sc_lds(threads), s, a, ta, (double*)out, s0, (int)m);
-    note_dispatch("qs::string_ci_spin_kernel<%d>", c_dtype == QS_F64 ? 1 : 2);
+    const int cw = c_dtype == QS_F64 ? 1 : 2;
+    with_width(cw, [&](auto CW) {
+        hipLaunchKernelGGL((string_ci_spin_kernel<CW>), dim3(grid), dim3(threads), sc_lds(threads), s, a, ta, (double*)out, s0, (int)m);
+    });
+    note_dispatch("qs::string_ci_spin_kernel<%d>", cw);
     return launch_status("string CI spin launch");
 }
 

@@ -1025,6 +1025,29 @@ def string_ci_sigma_plan(m, na, nb, c_dtype, K=1, h_dtype=None):
     return tuple(plan)
 
 
+def _sigma_operands(k, W, ta, tb, c, out, dims, name):
+    """The operands of a sigma on the device: ``k`` (m, m), ``W`` (m^2, m^2), the tables, ``c`` as (K, na, nb) and the
+    result buffer in the same view.  Returns ``(k, W, ta, tb, c3, out, o3, hcode, ccode)``."""
+    if not isinstance(c, torch.Tensor) or c.dim() not in (2, 3):
+        raise ValueError(f"c must be (K, {dims}) or ({dims})")
+    hdt = result_dtype(k, W)
+    dt = result_dtype(k, W, c)
+    k, W, c = _dev(k, hdt), _dev(W, hdt), _dev(c, dt)
+    m = k.shape[-1]
+    if tuple(k.shape) != (m, m) or tuple(W.shape) != (m * m, m * m):
+        raise ValueError(f"need k (m, m) and W (m^2, m^2), got {tuple(k.shape)}, {tuple(W.shape)}")
+    ta, tb = _string_tables(ta, tb, m)
+    single = c.dim() == 2
+    c3 = c[None] if single else c
+    if tuple(c3.shape[1:]) != (ta.shape[0], tb.shape[0]) or c3.shape[0] < 1:
+        raise ValueError(f"c has shape {tuple(c.shape)}: need (K, {ta.shape[0]}, {tb.shape[0]}) with K >= 1")
+    if out is None:
+        out = torch.empty(tuple(c.shape), dtype=dt, device=c.device)
+    else:
+        _check_out(out, tuple(c.shape), dt, name)
+    return k, W, ta, tb, c3, out, (out[None] if single else out), dtype_code(hdt), dtype_code(dt)
+
+
 @_plain
 def string_ci_sigma(k, W, ta, tb, c, out=None):
     """``sigma[j] = H c[j]`` for ``c`` (K, na, nb) or (na, nb) on ``qs_string_ci_sigma``: ``k`` (m, m) and ``W``
@@ -1036,44 +1059,26 @@ def string_ci_sigma(k, W, ta, tb, c, out=None):
     ``sigma`` on the stream.  Repeating a call gives the same bits; another grouping or another budget agrees to
     rounding.  One ``dispatch_log`` entry names the kernels of the whole call."""
     lib = _lib.load()
-    if not isinstance(c, torch.Tensor) or c.dim() not in (2, 3):
-        raise ValueError("c must be (K, na, nb) or (na, nb)")
-    hdt = result_dtype(k, W)
-    dt = result_dtype(k, W, c)
-    k, W, c = _dev(k, hdt), _dev(W, hdt), _dev(c, dt)
-    m = k.shape[-1]
-    if tuple(k.shape) != (m, m) or tuple(W.shape) != (m * m, m * m):
-        raise ValueError(f"need k (m, m) and W (m^2, m^2), got {tuple(k.shape)}, {tuple(W.shape)}")
-    ta, tb = _string_tables(ta, tb, m)
-    single = c.dim() == 2
-    c3 = c[None] if single else c
-    K, na, nb = c3.shape
-    if (na, nb) != (ta.shape[0], tb.shape[0]) or K < 1:
-        raise ValueError(f"c has shape {tuple(c.shape)}: need (K, {ta.shape[0]}, {tb.shape[0]}) with K >= 1")
-    hcode, ccode = dtype_code(hdt), dtype_code(dt)
+    k, W, ta, tb, c3, out, o3, hcode, ccode = _sigma_operands(k, W, ta, tb, c, out, "na, nb", "string_ci_sigma")
+    m, (K, na, nb) = k.shape[-1], c3.shape
     group = check(lib.qs_string_ci_group(hcode, ccode, m, na, nb, K, STRING_CI_BYTES), "group query")
-    if out is None:
-        out = torch.empty(tuple(c.shape), dtype=dt, device=c.device)
-    else:
-        _check_out(out, tuple(c.shape), dt, "string_ci_sigma")
-    o3 = out[None] if single else out
     ran = []
     # one vector alone is over the budget: passes over alpha rows (qs_string_ci_sigma_rows), one vector per call, so that
     # the fold's extra walks of the alpha table and round trips of sigma stay linear in K
-    _, passes, _, rows_bytes = string_ci_sigma_plan(m, na, nb, dt, 1, hdt)
+    _, passes, _, rows_bytes = string_ci_sigma_plan(m, na, nb, c3.dtype, 1, k.dtype)
     if passes > 1:
         group = 1
-    with _on_device_of(k, W, ta, tb, c, out):
+    with _on_device_of(k, W, ta, tb, c3, out):
         for k0 in range(0, K, group):
             kg = min(group, K - k0)
             args = (hcode, ccode, k.data_ptr(), W.data_ptr(), ta.data_ptr(), tb.data_ptr(), m, na, nb,
                     c3[k0:k0 + kg].data_ptr(), kg, o3[k0:k0 + kg].data_ptr())
             if passes > 1:
-                check(lib.qs_string_ci_sigma_rows(*args, *_work(rows_bytes, c.device), STRING_CI_BYTES, _stream()),
+                check(lib.qs_string_ci_sigma_rows(*args, *_work(rows_bytes, c3.device), STRING_CI_BYTES, _stream()),
                       "qs_string_ci_sigma_rows")
             else:
                 nbytes = check(lib.qs_string_ci_workspace(hcode, ccode, m, na, nb, kg), "workspace query")
-                check(lib.qs_string_ci_sigma(*args, *_work(nbytes, c.device), _stream()), "qs_string_ci_sigma")
+                check(lib.qs_string_ci_sigma(*args, *_work(nbytes, c3.device), _stream()), "qs_string_ci_sigma")
             if dispatch_log is not None:
                 ran.append(lib.qs_last_dispatch().decode())
     if dispatch_log is not None:
@@ -1121,21 +1126,8 @@ def string_ci_sigma_sym(k, W, t, c, parity, out=None):
     lib = _lib.load()
     if parity not in (1, -1):
         raise ValueError(f"parity must be +1 or -1, got {parity!r}")
-    if not isinstance(c, torch.Tensor) or c.dim() not in (2, 3):
-        raise ValueError("c must be (K, n, n) or (n, n)")
-    hdt = result_dtype(k, W)
-    dt = result_dtype(k, W, c)
-    k, W, c = _dev(k, hdt), _dev(W, hdt), _dev(c, dt)
-    m = k.shape[-1]
-    if tuple(k.shape) != (m, m) or tuple(W.shape) != (m * m, m * m):
-        raise ValueError(f"need k (m, m) and W (m^2, m^2), got {tuple(k.shape)}, {tuple(W.shape)}")
-    t, _ = _string_tables(t, t, m)
-    single = c.dim() == 2
-    c3 = c[None] if single else c
-    K, n = c3.shape[0], t.shape[0]
-    if tuple(c3.shape[1:]) != (n, n) or K < 1:
-        raise ValueError(f"c has shape {tuple(c.shape)}: need (K, {n}, {n}) with K >= 1")
-    hcode, ccode = dtype_code(hdt), dtype_code(dt)
+    k, W, t, _, c3, out, o3, hcode, ccode = _sigma_operands(k, W, t, t, c, out, "n, n", "string_ci_sigma_sym")
+    m, K, n = k.shape[-1], c3.shape[0], t.shape[0]
 
     def one_pass(g):
         rc, plan, _ = _sym_plan(hcode, ccode, m, n, g)
@@ -1151,20 +1143,15 @@ def string_ci_sigma_sym(k, W, t, c, parity, out=None):
             mid = (lo + hi) // 2
             lo, hi = (mid, hi) if one_pass(mid) else (lo, mid)
         group = lo
-    if out is None:
-        out = torch.empty(tuple(c.shape), dtype=dt, device=c.device)
-    else:
-        _check_out(out, tuple(c.shape), dt, "string_ci_sigma_sym")
-    o3 = out[None] if single else out
     ran = []
-    with _on_device_of(k, W, t, c, out):
+    with _on_device_of(k, W, t, c3, out):
         for k0 in range(0, K, group):
             kg = min(group, K - k0)
             rc, plan, _ = _sym_plan(hcode, ccode, m, n, kg)
             check(rc, "plan query")
             check(lib.qs_string_ci_sigma_sym(hcode, ccode, k.data_ptr(), W.data_ptr(), t.data_ptr(), m, n, int(parity),
                                              c3[k0:k0 + kg].data_ptr(), kg, o3[k0:k0 + kg].data_ptr(),
-                                             *_work(plan[3], c.device), STRING_CI_BYTES, _stream()), "qs_string_ci_sigma_sym")
+                                             *_work(plan[3], c3.device), STRING_CI_BYTES, _stream()), "qs_string_ci_sigma_sym")
             if dispatch_log is not None:
                 ran.append(lib.qs_last_dispatch().decode())
     if dispatch_log is not None:
@@ -1172,12 +1159,9 @@ def string_ci_sigma_sym(k, W, t, c, parity, out=None):
     return out
 
 
-@_plain
-def string_ci_density1(ta, tb, m, bra, ket, out=None):
-    """Spin-summed ``rho[q, p] = <bra| E_pq |ket>`` (m, m) of two vectors (na, nb) on ``qs_string_ci_density1``: one
-    expand of ``ket`` and one fixed-order sum per element; ``bra is ket`` is the density of a state, in the index order
-    ``compute_particle_density(rho_qp)`` takes."""
-    lib = _lib.load()
+def _bra_ket(ta, tb, m, bra, ket):
+    """The operands of a density on the device: the tables and two vectors (na, nb) of one dtype; ``bra is ket`` stays one
+    tensor.  Returns ``(m, ta, tb, bra, ket, na, nb, dtype, dtype code)``."""
     m = int(m)
     ta, tb = _string_tables(ta, tb, m)
     dt = result_dtype(bra, ket)
@@ -1188,6 +1172,16 @@ def string_ci_density1(ta, tb, m, bra, ket, out=None):
     if tuple(bra.shape) != (na, nb) or tuple(ket.shape) != (na, nb):
         raise ValueError(f"bra and ket have shapes {tuple(bra.shape)}, {tuple(ket.shape)}: need ({na}, {nb}) each")
     code = dtype_code(dt)
+    return m, ta, tb, bra, ket, na, nb, dt, code
+
+
+@_plain
+def string_ci_density1(ta, tb, m, bra, ket, out=None):
+    """Spin-summed ``rho[q, p] = <bra| E_pq |ket>`` (m, m) of two vectors (na, nb) on ``qs_string_ci_density1``: one
+    expand of ``ket`` and one fixed-order sum per element; ``bra is ket`` is the density of a state, in the index order
+    ``compute_particle_density(rho_qp)`` takes."""
+    lib = _lib.load()
+    m, ta, tb, bra, ket, na, nb, dt, code = _bra_ket(ta, tb, m, bra, ket)
     nbytes = check(lib.qs_string_ci_workspace(code, code, m, na, nb, 1), "workspace query")
     if out is None:
         out = torch.empty((m, m), dtype=dt, device=bra.device)
@@ -1212,16 +1206,7 @@ def string_ci_density2(ta, tb, m, bra, ket, out=None):
     ``out`` is a pair ``(gamma, rho)`` of buffers.  Repeating a call gives the same bits; another budget agrees to
     rounding."""
     lib = _lib.load()
-    m = int(m)
-    ta, tb = _string_tables(ta, tb, m)
-    dt = result_dtype(bra, ket)
-    same = bra is ket
-    bra = _dev(bra, dt)
-    ket = bra if same else _dev(ket, dt)
-    na, nb = ta.shape[0], tb.shape[0]
-    if tuple(bra.shape) != (na, nb) or tuple(ket.shape) != (na, nb):
-        raise ValueError(f"bra and ket have shapes {tuple(bra.shape)}, {tuple(ket.shape)}: need ({na}, {nb}) each")
-    code = dtype_code(dt)
+    m, ta, tb, bra, ket, na, nb, dt, code = _bra_ket(ta, tb, m, bra, ket)
     nbytes = check(lib.qs_string_ci_density2_workspace(code, m, na, nb, STRING_CI_BYTES), "workspace query")
     if out is None:
         gamma = torch.empty((m, m, m, m), dtype=dt, device=bra.device)
@@ -1261,16 +1246,7 @@ def string_ci_density2_spin(ta, tb, m, bra, ket, out=None):
     ``string_ci_bytes``); every pass is two batched products on the product dispatcher.  ``out`` is a 5-tuple of
     buffers.  Repeating a call gives the same bits; another budget agrees to rounding."""
     lib = _lib.load()
-    m = int(m)
-    ta, tb = _string_tables(ta, tb, m)
-    dt = result_dtype(bra, ket)
-    same = bra is ket
-    bra = _dev(bra, dt)
-    ket = bra if same else _dev(ket, dt)
-    na, nb = ta.shape[0], tb.shape[0]
-    if tuple(bra.shape) != (na, nb) or tuple(ket.shape) != (na, nb):
-        raise ValueError(f"bra and ket have shapes {tuple(bra.shape)}, {tuple(ket.shape)}: need ({na}, {nb}) each")
-    code = dtype_code(dt)
+    m, ta, tb, bra, ket, na, nb, dt, code = _bra_ket(ta, tb, m, bra, ket)
     nbytes = check(lib.qs_string_ci_density2_spin_workspace(code, m, na, nb, STRING_CI_BYTES), "workspace query")
     shapes = ((m, m, m, m),) * 3 + ((m, m),) * 2
     if out is None:

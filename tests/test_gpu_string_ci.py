@@ -252,8 +252,11 @@ def test_groups_under_a_small_byte_budget():
         calls = entry[0].split(" | ")
         assert len(calls) == -(-K // group)
         for call in calls:
-            assert "string_ci_expand_kernel<1>" in call and "string_ci_fold_kernel<0>" in call and "det_ci" not in call
-            assert call.index("expand") < call.index("fold") and "gemm" in call
+            # one pass of the rectangular layout: one expand, the product, one fold
+            assert call.count("string_ci_expand_kernel<1, qs::ScRect>") == call.count("string_ci_expand_kernel") == 1
+            assert call.count("string_ci_fold_kernel<0, qs::ScRect>") == call.count("string_ci_fold_kernel") == 1
+            assert "ScTri" not in call and "symmetrize" not in call and "det_ci" not in call
+            assert call.index("expand") < call.index("gemm") < call.index("fold")
     for group in (1, 4):
         assert ratio_of(H((results[group] - results[9]).abs()), np.float64(bound), f"groups of {group} against 9") <= 1.0
 

@@ -179,6 +179,8 @@ def test_passes_of_one_and_of_two_rows_against_the_dense_oracle(m, Na, Nb, form)
 @pytest.mark.parametrize("form", list(FORMS))
 @pytest.mark.parametrize("m,Na,Nb", [(9, 4, 4), (11, 4, 4)])
 def test_one_pass_gives_the_bits_of_the_one_piece_sigma(m, Na, Nb, form):
+    """The two entries run the same expand and fold kernels: this pins their drivers -- pass boundaries, product extents and
+    the carving of the workspace -- against each other."""
     hc, cc = FORMS[form]
     k, W = operands(m, 900 + 10 * m + Na, hc)
     ta = tb = table(m, Na)
@@ -269,12 +271,11 @@ def test_python_routing_by_the_budget_of_one_vector():
         assert len(calls) == K                                                    # one vector per call on either route
         for call in calls:
             assert "gemm" in call and "det_ci" not in call
-            if passes == 1:
-                assert "string_ci_expand_kernel<1>" in call and "string_ci_fold_kernel<0>" in call and "range" not in call
-            else:
-                assert "string_ci_expand_range_kernel<1>" in call and "string_ci_fold_range_kernel<0>" in call
-                assert "string_ci_expand_kernel" not in call and "string_ci_fold_kernel" not in call
-                assert call.index("expand_range") < call.index("gemm") < call.index("fold_range")
+            # as many expands and folds of the rectangular layout as passes, each pass expand, product, fold
+            assert call.count("string_ci_expand_kernel<1, qs::ScRect>") == call.count("string_ci_expand_kernel") == passes
+            assert call.count("string_ci_fold_kernel<0, qs::ScRect>") == call.count("string_ci_fold_kernel") == passes
+            assert "ScTri" not in call and "symmetrize" not in call
+            assert call.index("expand") < call.index("gemm") < call.index("fold")
     bound = 2 * device_bound(k, W, ta, tb, c)
     assert ratio_of(H((results[3] - results[1]).abs()), bound, "three passes against the one-piece route") <= 1.0
     assert float(results[1].abs().max()) > 1e3 * float(bound.max())
@@ -343,7 +344,11 @@ def test_solver_and_one_body_density_under_a_fifth_of_one_vector(form):
     E = H(E)
     print(f"{form}: max |dE| = {np.abs(E - e_nuc - lam[:3]).max():.2e} (bound {bound:.1e}), {ci.iterations} iterations")
     assert ci.converged and np.abs(E - e_nuc - lam[:3]).max() <= bound
-    assert steps == ci.iterations and all("string_ci_fold_range_kernel" in e and "string_ci_fold_kernel" not in e for e in log[:steps])
+    assert steps == ci.iterations
+    for e in log[:steps]:                                                         # every call of every step: the plan's 5 passes
+        for call in e.split(" | "):
+            assert call.count("string_ci_expand_kernel") == call.count("string_ci_fold_kernel") == 5 and "ScTri" not in call
+            assert call.index("expand") < call.index("gemm") < call.index("fold")
     density = log[steps]
     assert "string_ci_expand_rows_kernel" in density and "string_ci_expand_kernel<" not in density and plan[1] > 1
 

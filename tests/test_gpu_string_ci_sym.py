@@ -262,10 +262,11 @@ def test_python_routing_one_call_groups_and_one_vector_per_call():
         calls = log[0].split(" | ")
         assert len(calls) == len(sizes)
         for call, g in zip(calls, sizes):
-            assert "string_ci_expand_tri_kernel<1>" in call and "string_ci_fold_tri_kernel<0>" in call and "gemm" in call
-            assert "string_ci_symmetrize_kernel<1>" in call and "range" not in call and "string_ci_fold_kernel" not in call
-            assert call.index("expand_tri") < call.index("gemm") < call.index("fold_tri") < call.index("symmetrize")
-            assert call.count("symmetrize") == 1 and call.count("expand_tri") == call.count("fold_tri") == count[g]
+            assert "string_ci_expand_kernel<1, qs::ScTri>" in call and "string_ci_fold_kernel<0, qs::ScTri>" in call and "gemm" in call
+            assert "string_ci_symmetrize_kernel<1>" in call and "ScRect" not in call
+            assert call.index("expand") < call.index("gemm") < call.index("fold") < call.index("symmetrize")
+            assert call.count("symmetrize") == 1
+            assert call.count("string_ci_expand_kernel<1, qs::ScTri>") == call.count("string_ci_fold_kernel<0, qs::ScTri>") == count[g]
         assert_parity(out, tau)
     bound = 2 * device_bound(k, W, t, t, c)
     base = results[(5,)]
@@ -334,7 +335,11 @@ def test_solver_returns_the_lowest_states_of_each_parity(form):
         E = H(E)
         print(f"{form} tau={tau:+d}: max |dE| = {np.abs(E - e_nuc - want).max():.2e} (bound {bound:.1e}), {ci.iterations} iterations")
         assert ci.converged and np.abs(E - e_nuc - want).max() <= bound
-        assert steps == ci.iterations and all("string_ci_fold_tri_kernel" in e and "string_ci_fold_kernel" not in e for e in log)
+        assert steps == ci.iterations
+        for e in log:
+            for call in e.split(" | "):
+                assert call.count("string_ci_expand_kernel") == call.count("string_ci_fold_kernel") >= 1 and "ScRect" not in call
+                assert call.index("expand") < call.index("gemm") < call.index("fold") < call.index("symmetrize")
         states = ci._c
         assert tuple(states.shape) == (3, 20, 20)
         assert torch.equal(states, tau * states.transpose(1, 2))
@@ -364,7 +369,11 @@ def test_solver_returns_the_lowest_states_of_each_parity(form):
     finally:
         kernels.dispatch_log = None
     assert ci.converged and np.abs(H(E) - e_nuc - lam[:3]).max() <= bound
-    assert all("string_ci_fold_kernel" in e and "_tri_" not in e and "symmetrize" not in e for e in log)
+    for e in log:                                                                 # one pass of the rectangular layout per call
+        for call in e.split(" | "):
+            assert call.count("string_ci_expand_kernel") == call.count("string_ci_fold_kernel") == 1
+            assert call.index("expand") < call.index("gemm") < call.index("fold")
+            assert "ScTri" not in call and "symmetrize" not in call
     with pytest.raises(ValueError):
         StringCI(system, hip.asarray(X), n_up=3, n_down=2, spin_parity=1)
     with pytest.raises(ValueError):

@@ -66,7 +66,7 @@ def pair_leg(m, N, cplx, reps, emit):
     ts = measure(lambda: kernels.string_ci_sigma_sym(k, W, t, c, 1), reps)
     ran = kernels.last_dispatch()
     sym = kernels.string_ci_sigma_sym(k, W, t, c, 1)
-    assert "fold_tri" in ran, ran
+    assert "string_ci_fold_kernel<" in ran and "qs::ScRect" not in ran, ran
     diff = float((sym - full).abs().max() / full.abs().max())
     pf, route_f = products_alone(W, [min(rows, n - p * rows) * n for p in range(passes)], reps)
     ps, route_s = products_alone(W, [off(b) - off(a) for a, b in zip(cuts, cuts[1:])], reps)
