@@ -127,6 +127,53 @@ int qs_transform_two_body_inplace(int dtype, void* u, const void* C,
                                   int64_t L, int64_t M, void* stream);
 
 /*
+ * The transform of a tensor with PARTICLE-EXCHANGE SYMMETRY,
+ *   u[a,b,c,d] == u[b,a,d,c]  bit for bit
+ * (random_basis.py:52; every physical two-body tensor has it).  Both leading
+ * indices meet Ct and both trailing ones C, so every intermediate that treats
+ * the members of a pair alike keeps the symmetry: the d and c contractions run
+ * on the pairs b >= a only, the last product on q >= the block of p, and a
+ * byte-moving mirror writes the other half -- about 2.9 products' worth of
+ * matrix work instead of 4.  The symmetry has no conjugation in it and Ct may
+ * be any matrix.  (No ABI version change: these are additions.)
+ *
+ *   qs_two_body_exchange_symmetric: 1 if u (L,L,L,L) has the symmetry, 0 if
+ *     not, negative QS_ERR_* on error.  Bit patterns are compared: -0.0 against
+ *     +0.0 is "not symmetric", equal NaNs are symmetric.  `scratch`: 4 bytes
+ *     of device memory.  THIS CALL BLOCKS: it launches the check on `stream`,
+ *     copies the verdict back and synchronises the stream -- the only blocking
+ *     call of the transform path.  A non-symmetric tensor costs microseconds
+ *     (the grid stops reading once a difference is known), a symmetric one
+ *     one pass over u.  On a capturing stream it launches nothing and
+ *     returns 0.  The verdict is not cached anywhere.
+ *   qs_transform_two_body_exchange / qs_transform_two_body_inplace_exchange:
+ *     arguments, workspace, aliasing rules and asynchrony of
+ *     qs_transform_two_body / qs_transform_two_body_inplace.  PRECONDITION: u
+ *     has the symmetry (otherwise the result is that of the symmetrised half
+ *     that was read, not an error).  Results agree with the plain entries to
+ *     rounding, not bit for bit (the a contraction runs before the b one).
+ *   qs_transform_two_body_exchange_wanted: 1 where this route is the faster
+ *     one for (dtype, L, M) under the calling thread's tuning keys, else 0;
+ *     never for min(L, M) <= 128.
+ *   qs_exchange_mirror: in place on t (n,n,m,m),
+ *     t[a,b,r,s] = t[b,a,s,r] for every pair with a / block > b / block
+ *     (block = 1: the lower triangle a > b); nothing else is written.
+ */
+int qs_two_body_exchange_symmetric(int dtype, const void* u, int64_t L,
+                                   void* scratch, void* stream);
+int qs_transform_two_body_exchange(int dtype, const void* u, const void* C,
+                                   const void* Ct, void* out, void* work,
+                                   int64_t work_bytes, int64_t L, int64_t M,
+                                   void* stream);
+int qs_transform_two_body_inplace_exchange(int dtype, void* u, const void* C,
+                                           const void* Ct, void* work,
+                                           int64_t work_bytes, int64_t L,
+                                           int64_t M, void* stream);
+int qs_transform_two_body_exchange_wanted(int dtype, int64_t L, int64_t M);
+int qs_exchange_mirror(int dtype, void* t, int64_t n, int64_t m, int64_t block,
+                       void* stream);
+
+/*
  * Same transform restricted to rows [a_lo, a_hi) of the leading index of `u`
  * for the contractions over d, c, b only:
  *   v[a,q,r,s] = sum_bcd Ct[q,b] u[a,b,c,d] C[c,r] C[d,s],  a in [a_lo,a_hi)
@@ -467,7 +514,11 @@ const char* qs_last_dispatch(void);
  *     excitations, 0 = shipped, 1, 2, 4 or 8 for tuning runs),
  *     "string_ci_bytes" (qs_string_ci_group: the byte budget of the D and G
  *     panels of one qs_string_ci_sigma call, 0 = the caller's shipped value;
- *     a negative value is refused with QS_ERR_BAD_EXTENT).
+ *     a negative value is refused with QS_ERR_BAD_EXTENT),
+ *     "exchange" (qs_transform_two_body_exchange_wanted: 0 = never, 1 = where
+ *     the exchange route measured faster, 2 = wherever it exists, any size),
+ *     "exchange_block" / "exchange_block_d" (rows per block of that route's
+ *     closing product and mirror / of its d contraction, 0 = automatic).
  *   qs_probe_mfma_f64: register-resident fp64 MFMA loop, `blocks` workgroups
  *     of 4 waves, each wave issuing iters*8 v_mfma_f64_16x16x4_f64
  *     (flops = blocks*4*iters*8*2048); `sink` is a device scratch of

@@ -239,6 +239,16 @@ int qs_tuning_set(const char* key, int64_t value) {
     if (!strcmp(key, "sandwich_mode")) { g_tune.sandwich_mode = (int)value; return QS_OK; }
     if (!strcmp(key, "sandwich_t2")) { g_tune.sandwich_t2 = (int)value; return QS_OK; }
     if (!strcmp(key, "sandwich_v2")) { g_tune.sandwich_v2 = (int)value; return QS_OK; }
+    if (!strcmp(key, "exchange")) {
+        if (value < 0 || value > 2) return QS_ERR_BAD_EXTENT;
+        g_tune.exchange = (int)value;
+        return QS_OK;
+    }
+    if (!strcmp(key, "exchange_block") || !strcmp(key, "exchange_block_d")) {
+        if (value < 0 || value > 4096) return QS_ERR_BAD_EXTENT;
+        (key[14] ? g_tune.exchange_block_d : g_tune.exchange_block) = (int)value;
+        return QS_OK;
+    }
     if (!strcmp(key, "mean_field_batch_g")) {
         if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8) return QS_ERR_BAD_EXTENT;
         g_tune.mean_field_batch_g = (int)value;
@@ -406,8 +416,64 @@ static int transform_two_body_fused(int in_dtype, int dtype, const void* u, cons
     return 1;
 }
 
+// ---- the route for a tensor with particle-exchange symmetry, u[a,b,c,d] == u[b,a,d,c] bit for bit.
+// Both leading indices meet the same Ct and both trailing ones the same C, so T2[a,b,r,s] == T2[b,a,s,r] and
+// out[p,q,r,s] == out[q,p,s,r]: the d and c contractions run on the pairs b >= a only, the closing product on q >= the
+// block of p, and a mirror (qs_permute.hip) writes the other half.  The a contraction comes BEFORE the b contraction here
+// (the closing product then has M - p0 rows, mostly on the 128-row form):
+//   d:  T1[a][(b >= a0, c), s] = u[a][(b >= a0, c), d] C[d, s]       per block [a0, a1) of rows a, batched over a
+//   c:  T2[a, b][r, s]         = CT[r, c] T1[a, b][c, s]             per a, batched over b >= a;  then the mirror, a > b
+//   a:  X[p, (b r s)]          = Ct[p, a] T2[a, (b r s)]             one product
+//   b:  out[p][q >= p0, (r s)] = Ct[q >= p0, b] X[p][b, (r s)]       per block [p0, p1) of rows p, batched over p; then the mirror
+// T1 (L, L, L, M), T2 (L, L, M, M), X (M, L, M, M); T1 and X may share storage, so may T2 and out.
+
+// smallest basis (both sizes) that takes the route by itself: where it measured >= 5 % faster (profiles/exchange_route_sweep.txt)
+static constexpr int64_t kExchangeMin = 192;
+
+static bool exchange_wanted(int dtype, int64_t L, int64_t M) {
+    if (!dtype_ok(dtype) || !extents_ok(L, M) || !g_tune.exchange || !exchange_grids_fit(L, M)) return false;
+    if (g_tune.exchange == 2) return true;
+    return (L < M ? L : M) >= kExchangeMin;
+}
+
+static int transform_two_body_exchange_route(int dtype, const void* u, const void* C, const void* Ct, void* CT, void* T1,
+                                             void* T2, void* X, void* out, int64_t L, int64_t M, hipStream_t s) {
+    const size_t es = elem_size(dtype);
+    const int64_t MM = M * M;
+    // blocks (same-call sweep at l = 192 ... 256, profiles/exchange_route_sweep.txt): 64 rows keep the closing product of fp64 on
+    // its exact forms (32: level at 256, -1 % at 192; 128: -1.4 %); complex128 gains 1 % from 32; d is flat from 8 to 32
+    const int64_t blk = g_tune.exchange_block > 0 ? g_tune.exchange_block : (dtype == QS_C128 ? 32 : 64);
+    const int64_t blk_d = g_tune.exchange_block_d > 0 ? g_tune.exchange_block_d : (blk < 16 ? blk : 16);
+    auto cat = [&](const void* base, int64_t elems) { return (const double*)((const char*)base + (size_t)elems * es); };
+    auto mat = [&](void* base, int64_t elems) { return (double*)at(base, elems, es); };
+    int rc = transpose_small(dtype, C, CT, L, M, s);
+    if (rc) return rc;
+    for (int64_t a0 = 0; a0 < L; a0 += blk_d) {
+        const int64_t rows = (a0 + blk_d < L ? a0 + blk_d : L) - a0;
+        rc = gemm(Product{dtype, cat(u, a0 * L * L * L + a0 * L * L), (const double*)C, mat(T1, a0 * L * L * M + a0 * L * M),
+                          (L - a0) * L, M, L, L, M, M, rows, L * L * L, 0, L * L * M, 0}, s);
+        if (rc) return rc;
+    }
+    for (int64_t a = 0; a < L; ++a) {
+        rc = gemm(packed(dtype, CT, cat(T1, (a * L + a) * L * M), mat(T2, (a * L + a) * MM), M, M, L, L - a), s);
+        if (rc) return rc;
+    }
+    rc = exchange_mirror(dtype, T2, L, M, 1, s);
+    if (rc) return rc;
+    rc = gemm(packed(dtype, Ct, T2, X, M, L * MM, L), s);
+    if (rc) return rc;
+    for (int64_t p0 = 0; p0 < M; p0 += blk) {
+        const int64_t rows = (p0 + blk < M ? p0 + blk : M) - p0;
+        rc = gemm(Product{dtype, cat(Ct, p0 * L), cat(X, p0 * L * MM), mat(out, p0 * M * MM + p0 * MM),
+                          M - p0, MM, L, L, MM, MM, rows, 0, L * MM, M * MM, 0}, s);
+        if (rc) return rc;
+    }
+    return exchange_mirror(dtype, out, M, M, blk, s);
+}
+
+// Argument checks and buffers of qs_transform_two_body; `exchange`: the route above, for a tensor that has the symmetry.
 static int transform_two_body_impl(int in_dtype, int dtype, const void* u, const void* C, const void* Ct, void* out,
-                                   void* work, int64_t work_bytes, int64_t L, int64_t M, void* stream) {
+                                   void* work, int64_t work_bytes, int64_t L, int64_t M, void* stream, bool exchange = false) {
     dispatch_reset();
     if (!dtype_ok(dtype) || !dtype_ok(in_dtype) || (in_dtype == QS_C128 && dtype == QS_F64)) return QS_ERR_BAD_DTYPE;
     if (!extents_ok(L, M)) return QS_ERR_BAD_EXTENT;
@@ -425,6 +491,11 @@ static int transform_two_body_impl(int in_dtype, int dtype, const void* u, const
     const int64_t wa = (L * L * L * M > L * M * M * M) ? L * L * L * M : L * M * M * M;
     void* WB = (M < L) ? at(WA, wa, es) : out;
 
+    if (exchange) {
+        if (in_dtype != dtype) return QS_ERR_BAD_DTYPE;
+        if (!exchange_grids_fit(L, M)) return QS_ERR_BAD_EXTENT;
+        return transform_two_body_exchange_route(dtype, u, C, Ct, CT, /*T1*/ WA, /*T2*/ WB, /*X*/ WA, out, L, M, s);
+    }
     int rc = transform_two_body_fused(in_dtype, dtype, u, C, Ct, out, CT, WA, WB, L, M, s);
     if (rc != 1) return rc;
     rc = contract_dcb(in_dtype, dtype, u, C, CT, Ct, /*T1*/ WA, /*T2*/ WB, /*T3*/ WA, L, L, M, s);
@@ -454,8 +525,10 @@ int64_t qs_transform_two_body_inplace_workspace(int dtype, int64_t L, int64_t M)
     return (even_up(L * M) + L * L * L * M) * (int64_t)elem_size(dtype);
 }
 
-int qs_transform_two_body_inplace(int dtype, void* u, const void* C, const void* Ct, void* work,
-                                  int64_t work_bytes, int64_t L, int64_t M, void* stream) {
+}  // extern "C"
+
+static int transform_two_body_inplace_impl(int dtype, void* u, const void* C, const void* Ct, void* work,
+                                           int64_t work_bytes, int64_t L, int64_t M, void* stream, bool exchange) {
     dispatch_reset();
     if (!dtype_ok(dtype)) return QS_ERR_BAD_DTYPE;
     if (!extents_ok(L, M) || M > L) return QS_ERR_BAD_EXTENT;
@@ -470,6 +543,11 @@ int qs_transform_two_body_inplace(int dtype, void* u, const void* C, const void*
     // the four contractions ping-pong between the tensor's own storage (A) and ONE spare buffer (B): every
     // product reads one and writes the other, and each intermediate fits where it goes (M <= L):
     //   d: A (L^4) -> B (L^3 M)   c: B -> A (L^2 M^2)   b: A -> B (L M^3)   a: B -> A (M^4)
+    // (the exchange route the same way: T1 and X in B, T2 and the result in A)
+    if (exchange) {
+        if (!exchange_grids_fit(L, M)) return QS_ERR_BAD_EXTENT;
+        return transform_two_body_exchange_route(dtype, u, C, Ct, CT, /*T1*/ B, /*T2*/ u, /*X*/ B, /*out*/ u, L, M, s);
+    }
     int rc = transpose_small(dtype, C, CT, L, M, s);
     if (rc) return rc;
     rc = gemm(packed(dtype, u, C, B, L * L * L, M, L), s);
@@ -479,6 +557,53 @@ int qs_transform_two_body_inplace(int dtype, void* u, const void* C, const void*
     rc = gemm(packed(dtype, Ct, u, B, M, M * M, L, L), s);
     if (rc) return rc;
     return gemm(packed(dtype, Ct, B, u, M, M * M * M, L), s);
+}
+
+extern "C" {
+
+int qs_transform_two_body_inplace(int dtype, void* u, const void* C, const void* Ct, void* work,
+                                  int64_t work_bytes, int64_t L, int64_t M, void* stream) {
+    return transform_two_body_inplace_impl(dtype, u, C, Ct, work, work_bytes, L, M, stream, false);
+}
+
+int qs_transform_two_body_exchange_wanted(int dtype, int64_t L, int64_t M) { return exchange_wanted(dtype, L, M) ? 1 : 0; }
+
+int qs_two_body_exchange_symmetric(int dtype, const void* u, int64_t L, void* scratch, void* stream) {
+    dispatch_reset();
+    if (!dtype_ok(dtype)) return QS_ERR_BAD_DTYPE;
+    if (L <= 0 || L > 4096) return QS_ERR_BAD_EXTENT;
+    if (!u || !scratch) return QS_ERR_NULL_POINTER;
+    if (!aligned(u, elem_size(dtype)) || !aligned(scratch, 4)) return QS_ERR_MISALIGNED;
+    hipStream_t s = (hipStream_t)stream;
+    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+    if (int rc = hip_status(hipStreamIsCapturing(s, &capture), "hipStreamIsCapturing")) return rc;
+    if (capture != hipStreamCaptureStatusNone) return 0;      // the verdict cannot be read back inside a capture: "not known to be symmetric"
+    int* flag = (int*)scratch;
+    if (int rc = hip_status(hipMemsetAsync(flag, 0, sizeof(int), s), "hipMemsetAsync(flag)")) return rc;
+    if (int rc = exchange_check(dtype, u, L, flag, s)) return rc;
+    int differs = 1;
+    if (int rc = hip_status(hipMemcpyAsync(&differs, flag, sizeof(int), hipMemcpyDeviceToHost, s), "hipMemcpyAsync(flag)")) return rc;
+    if (int rc = hip_status(hipStreamSynchronize(s), "hipStreamSynchronize")) return rc;
+    return differs ? 0 : 1;
+}
+
+int qs_transform_two_body_exchange(int dtype, const void* u, const void* C, const void* Ct, void* out,
+                                   void* work, int64_t work_bytes, int64_t L, int64_t M, void* stream) {
+    return transform_two_body_impl(dtype, dtype, u, C, Ct, out, work, work_bytes, L, M, stream, true);
+}
+
+int qs_transform_two_body_inplace_exchange(int dtype, void* u, const void* C, const void* Ct, void* work,
+                                           int64_t work_bytes, int64_t L, int64_t M, void* stream) {
+    return transform_two_body_inplace_impl(dtype, u, C, Ct, work, work_bytes, L, M, stream, true);
+}
+
+int qs_exchange_mirror(int dtype, void* t, int64_t n, int64_t m, int64_t block, void* stream) {
+    dispatch_reset();
+    if (!dtype_ok(dtype)) return QS_ERR_BAD_DTYPE;
+    if (n <= 0 || m <= 0 || block <= 0 || n > 4096 || m > 4096) return QS_ERR_BAD_EXTENT;
+    if (!t) return QS_ERR_NULL_POINTER;
+    if (!aligned(t, elem_size(dtype))) return QS_ERR_MISALIGNED;
+    return exchange_mirror(dtype, t, n, m, block < n ? block : n, (hipStream_t)stream);
 }
 
 int64_t qs_transform_two_body_partial_workspace(int dtype, int64_t L, int64_t M, int64_t rows) {

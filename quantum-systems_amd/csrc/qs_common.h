@@ -190,6 +190,12 @@ int kron_eye2(int in_dtype, int out_dtype, const void* h, void* out, int64_t nma
               hipStream_t stream);
 int spin2_two_body(const void* S, void* out, int64_t n, int64_t p_lo, int64_t p_hi, int as,
                    hipStream_t stream);
+// Particle-exchange symmetry t[a,b,r,s] == t[b,a,s,r].  Check: *flag (zeroed by the caller) becomes nonzero iff u (l, l, l, l)
+// lacks it bit for bit.  Mirror, in place on t (n, n, m, m): t[a,b,r,s] = t[b,a,s,r] where a / block > b / block.
+int exchange_check(int dtype, const void* u, int64_t l, int* flag, hipStream_t stream);
+int exchange_mirror(int dtype, void* t, int64_t n, int64_t m, int64_t block, hipStream_t stream);
+// Do the grids of the check and of both mirrors of an (L -> M) transform fit their 31 bits?
+bool exchange_grids_fit(int64_t L, int64_t M);
 
 // Tuning knobs (qs_tuning_set / qs_tuning_reset): state of the CALLING THREAD only, so a tuning
 // run or a test cannot change the dispatch of another thread's calls; every thread starts from the
@@ -233,6 +239,10 @@ struct Tuning {
     int det_ci_g = 0;            // qs_det_ci_sigma: vectors per walk of a determinant's excitations, 0 = the shipped group size of the form;
                                  // 1, 2, 4, 8 = tuning runs (every setting gives the same bits: a vector's fma chain does not know G)
     int64_t string_ci_bytes = 0; // qs_string_ci_group: byte budget of the D and G panels of one qs_string_ci_sigma call, 0 = the caller's shipped value
+    int exchange = 1;            // the transform's route for a tensor with particle-exchange symmetry (qs_transform_two_body_exchange_wanted):
+                                 // 0 never, 1 where it measured faster, 2 wherever it exists (any size, ahead of the fused small-basis routes)
+    int exchange_block = 0;      // rows per block of that route's closing product (and of its mirror), 0 = automatic
+    int exchange_block_d = 0;    // rows per block of that route's d contraction, 0 = automatic (never above exchange_block when that is set)
     int sandwich = 1;            // 4-wide fused passes of a small-basis transform: 0 off, 1 both (d, c) and (b, a), 2 (d, c) only, 3 (b, a) only;
                                  // tuning runs, wherever the kernel exists (not only where it measured faster): 4 both, 5 (d, c) only, 6 (b, a) only
 };

@@ -243,6 +243,81 @@ __global__ void transpose_kernel(const T* __restrict__ in, T* __restrict__ out, 
     }
 }
 
+// ----------------------------------------------------------------------------
+// Particle-exchange symmetry  t[a,b,r,s] == t[b,a,s,r]  (random_basis.py:52; every physical two-body tensor has it):
+// the check of an input tensor and the mirror that completes an (n, n, m, m) tensor computed on `a <= b` only.  Both
+// names carry "transpose": they move bytes, and a dispatch record counts products by the names that lack the word.
+// ----------------------------------------------------------------------------
+__device__ __forceinline__ bool same_bits(double x, double y) { return __double_as_longlong(x) == __double_as_longlong(y); }
+__device__ __forceinline__ bool same_bits(f64x2 x, f64x2 y) { return same_bits(x[0], y[0]) && same_bits(x[1], y[1]); }
+
+// Row a of the upper triangle of an n x n grid (rows of n, n - 1, ... entries) that holds linear index idx.
+__device__ __forceinline__ int64_t triangle_row(int64_t idx, int64_t n) {
+    const double w = 2.0 * (double)n + 1.0;
+    int64_t a = (int64_t)((w - sqrt(w * w - 8.0 * (double)idx)) * 0.5);
+    if (a < 0) a = 0;
+    if (a > n - 1) a = n - 1;
+    while (a > 0 && a * n - a * (a - 1) / 2 > idx) --a;
+    while (a + 1 < n && (a + 1) * n - (a + 1) * a / 2 <= idx) ++a;
+    return a;
+}
+
+// *flag |= 1 iff some u[a,b,c,d] differs BITWISE from u[b,a,d,c] (-0.0 against +0.0 differs, equal NaNs do not).  A
+// workgroup takes one pair a <= b and one 32 x 32 tile (ti, tj) of u[a,b] together with tile (tj, ti) of u[b,a]; on the
+// diagonal a == b that is the test that u[a,a] is a symmetric matrix.  It looks at the flag first: once a difference
+// is known, the rest of the grid costs no memory traffic.
+template <typename T>
+__global__ __launch_bounds__(256) void exchange_transpose_check_kernel(const T* __restrict__ u, int* flag, int l, int nt) {
+    __shared__ T t1[PT][PS];
+    __shared__ T t2[PT][PS];
+    if (__atomic_load_n(flag, __ATOMIC_RELAXED)) return;
+    const int ntiles = nt * nt;
+    const int64_t pair = blockIdx.x / ntiles;
+    const int tile = blockIdx.x % ntiles;
+    const int ti = tile / nt, tj = tile % nt;
+    const int64_t a = triangle_row(pair, l);
+    const int64_t b = a + (pair - (a * l - a * (a - 1) / 2));
+    const int64_t ll = (int64_t)l * l;
+    load_tile(t1, u + (a * l + b) * ll, l, ti * PT, tj * PT);
+    load_tile(t2, u + (b * l + a) * ll, l, tj * PT, ti * PT);
+    __syncthreads();
+    const int tx = threadIdx.x & (PT - 1), ty = threadIdx.x / PT;
+    bool same = true;
+#pragma unroll
+    for (int rr = ty; rr < PT; rr += 8) same = same && same_bits(t1[rr][tx], t2[tx][rr]);   // (both zero past the edge)
+    if (!same) *flag = 1;
+}
+
+// In place on t (n, n, m, m):  t[a,b,r,s] = t[b,a,s,r]  for every pair with a / block > b / block; nothing else is
+// written.  A workgroup takes one such pair and one 32 x 32 tile (ti, tj) of t[a,b]: it reads tile (tj, ti) of t[b,a]
+// by rows, turns it in LDS and writes whole rows of 32 elements (two 128-byte lines of fp64 where m is a multiple of 16).
+template <typename T>
+__global__ __launch_bounds__(256) void exchange_transpose_kernel(T* t, int n, int m, int nt, int block) {
+    __shared__ T t1[PT][PS];
+    const int ntiles = nt * nt;
+    const int64_t pair = blockIdx.x / ntiles;
+    const int tile = blockIdx.x % ntiles;
+    const int ti = tile / nt, tj = tile % nt;
+    // pairs row by row: the rows of block row A = a / block hold A * block pairs each
+    const int64_t bb = (int64_t)block * block;
+    int64_t A = (int64_t)((1.0 + sqrt(1.0 + 8.0 * (double)pair / (double)bb)) * 0.5);
+    if (A < 1) A = 1;
+    while (A > 1 && bb * (A * (A - 1) / 2) > pair) --A;
+    while (bb * ((A + 1) * A / 2) <= pair) ++A;
+    const int64_t rem = pair - bb * (A * (A - 1) / 2), row_len = A * block;
+    const int64_t a = A * block + rem / row_len, b = rem % row_len;
+    const int64_t mm = (int64_t)m * m;
+    load_tile(t1, (const T*)t + (b * n + a) * mm, m, tj * PT, ti * PT);
+    __syncthreads();
+    T* o = t + (a * n + b) * mm;
+    const int tx = threadIdx.x & (PT - 1), ty = threadIdx.x / PT;
+#pragma unroll
+    for (int rr = ty; rr < PT; rr += 8) {
+        const int r = ti * PT + rr, c = tj * PT + tx;
+        if (r < m && c < m) stream_store(&o[(int64_t)r * m + c], t1[tx][rr]);
+    }
+}
+
 // ------------------------------------------------------------------ launchers
 
 static inline unsigned stream_grid(int64_t total, int block) {
@@ -274,6 +349,47 @@ int antisymmetrize(int dtype, const void* u, void* out, int64_t npq, int64_t l, 
                            (const f64x2*)u, (f64x2*)out, (int)l, nt, (int)npairs);
     note_dispatch("qs::antisym_kernel<%s>", dtype == QS_F64 ? "double" : "f64x2");
     return launch_status("antisymmetrize launch");
+}
+
+// pairs (a, b) of an n x n grid with a / block > b / block
+static inline int64_t exchange_lower_pairs(int64_t n, int64_t block) {
+    const int64_t full = n / block, rest = n % block;
+    return block * block * (full * (full - 1) / 2) + rest * full * block;
+}
+
+bool exchange_grids_fit(int64_t L, int64_t M) {
+    const int64_t nl = cdiv(L, PT), nm = cdiv(M, PT), top = int64_t(1) << 31, big = L > M ? L : M;
+    return L * (L + 1) / 2 * nl * nl < top && big * (big - 1) / 2 * nm * nm < top;
+}
+
+int exchange_check(int dtype, const void* u, int64_t l, int* flag, hipStream_t stream) {
+    const int nt = (int)cdiv(l, PT);
+    const int64_t nwg = l * (l + 1) / 2 * nt * nt;
+    if (nwg >= (int64_t(1) << 31)) return QS_ERR_BAD_EXTENT;
+    if (dtype == QS_F64)
+        hipLaunchKernelGGL(exchange_transpose_check_kernel<double>, dim3((unsigned)nwg), dim3(256), 0, stream,
+                           (const double*)u, flag, (int)l, nt);
+    else
+        hipLaunchKernelGGL(exchange_transpose_check_kernel<f64x2>, dim3((unsigned)nwg), dim3(256), 0, stream,
+                           (const f64x2*)u, flag, (int)l, nt);
+    note_dispatch("qs::exchange_transpose_check_kernel<%s>", dtype == QS_F64 ? "double" : "f64x2");
+    return launch_status("exchange_check launch");
+}
+
+int exchange_mirror(int dtype, void* t, int64_t n, int64_t m, int64_t block, hipStream_t stream) {
+    const int nt = (int)cdiv(m, PT);
+    const int64_t pairs = exchange_lower_pairs(n, block);
+    if (pairs == 0) return QS_OK;                          // one block row: nothing lies below it
+    const int64_t nwg = pairs * nt * nt;
+    if (nwg >= (int64_t(1) << 31)) return QS_ERR_BAD_EXTENT;
+    if (dtype == QS_F64)
+        hipLaunchKernelGGL(exchange_transpose_kernel<double>, dim3((unsigned)nwg), dim3(256), 0, stream,
+                           (double*)t, (int)n, (int)m, nt, (int)block);
+    else
+        hipLaunchKernelGGL(exchange_transpose_kernel<f64x2>, dim3((unsigned)nwg), dim3(256), 0, stream,
+                           (f64x2*)t, (int)n, (int)m, nt, (int)block);
+    note_dispatch("qs::exchange_transpose_kernel<%s>", dtype == QS_F64 ? "double" : "f64x2");
+    return launch_status("exchange_mirror launch");
 }
 
 int spin_expand(int in_dtype, int out_dtype, const void* u, void* out, int64_t l, int64_t nq, int64_t p_lo,

@@ -53,9 +53,10 @@ dispatch_log = None
 
 
 def _ran(code, what):
-    check(code, what)
+    code = check(code, what)
     if dispatch_log is not None:
         dispatch_log.append(_lib.load().qs_last_dispatch().decode())
+    return code
 
 
 def _dev(t, dtype=None):
@@ -236,9 +237,24 @@ def matmul(A, B, out=None, accumulate=False):
     return gemm_raw(dt, A, B, out, m, n, k, k, n, n, batch, 0, k * n, m * n, accumulate)
 
 
+def _takes_exchange_route(lib, code, u, L, M, work, exchange):
+    """Does this transform take the route for a tensor with particle-exchange symmetry, ``u[a,b,c,d] == u[b,a,d,c]``
+    (qs_amd.h)?  Only where the library's policy wants it for the size (``qs_transform_two_body_exchange_wanted``, which
+    honours the tuning keys) and the check kernel finds the symmetry bit for bit -- the check is the ONE blocking call of
+    the path: it synchronises the current stream, and on a capturing stream it answers "no" without launching.  Nothing
+    is remembered between calls (a tensor written through a raw pointer would keep a stale verdict)."""
+    if exchange is False or not lib.qs_transform_two_body_exchange_wanted(code, L, M):
+        return False
+    return _ran(lib.qs_two_body_exchange_symmetric(code, u.data_ptr(), L, work.data_ptr(), _stream()),
+                "qs_two_body_exchange_symmetric") == 1
+
+
 @_plain
-def transform_two_body(u, C, C_tilde=None, out=None):
-    """out[pqrs] = Ct[pa] Ct[qb] u[abcd] C[cr] C[ds]  (basis_set.py:336-350)."""
+def transform_two_body(u, C, C_tilde=None, out=None, exchange=None):
+    """out[pqrs] = Ct[pa] Ct[qb] u[abcd] C[cr] C[ds]  (basis_set.py:336-350).
+
+    ``exchange=None``: a tensor with particle-exchange symmetry takes the route that skips the half the symmetry
+    repeats, where that is faster (``_takes_exchange_route``); ``exchange=False``: the four full products always."""
     lib = _lib.load()
     if C_tilde is None:
         C_tilde = default_bra(C)
@@ -271,21 +287,23 @@ def transform_two_body(u, C, C_tilde=None, out=None):
                 "qs_transform_two_body_mixed",
             )
         else:
+            route = "qs_transform_two_body" + ("_exchange" if _takes_exchange_route(lib, code, u, L, M, work, exchange) else "")
             _ran(
-                lib.qs_transform_two_body(
+                getattr(lib, route)(
                     code, u.data_ptr(), C.data_ptr(), Ct.data_ptr(), out.data_ptr(),
                     work.data_ptr(), work.numel(), L, M, _stream(),
                 ),
-                "qs_transform_two_body",
+                route,
             )
     return out
 
 
 @_plain
-def transform_two_body_(u, C, C_tilde=None):
+def transform_two_body_(u, C, C_tilde=None, exchange=None):
     """The transform IN PLACE: ``u`` (L,L,L,L; float64 / complex128, contiguous, owning its storage) is overwritten
     and the result (M,M,M,M), M <= L, is returned as a view of the start of its storage.  One L^3 M spare buffer
-    instead of workspace + result (qs_transform_two_body_inplace): for callers that drop the old tensor."""
+    instead of workspace + result (qs_transform_two_body_inplace): for callers that drop the old tensor.
+    ``exchange``: as in ``transform_two_body``."""
     lib = _lib.load()
     if C_tilde is None:
         C_tilde = default_bra(C)
@@ -300,10 +318,10 @@ def transform_two_body_(u, C, C_tilde=None):
     nbytes = check(lib.qs_transform_two_body_inplace_workspace(code, L, M), "workspace query")
     with _on_device_of(u, C, Ct):
         work = workspace.get(nbytes, u.device)
+        route = "qs_transform_two_body_inplace" + ("_exchange" if _takes_exchange_route(lib, code, u, L, M, work, exchange) else "")
         _ran(
-            lib.qs_transform_two_body_inplace(code, u.data_ptr(), C.data_ptr(), Ct.data_ptr(), work.data_ptr(),
-                                              work.numel(), L, M, _stream()),
-            "qs_transform_two_body_inplace",
+            getattr(lib, route)(code, u.data_ptr(), C.data_ptr(), Ct.data_ptr(), work.data_ptr(), work.numel(), L, M, _stream()),
+            route,
         )
     # (the tensor itself when the size does not change: no view object keeps a second handle on the storage, so
     # the next change_basis can reuse it again)
@@ -324,9 +342,12 @@ class TransformPlan:
             plan.C_tilde.copy_(Ct_t)
             out = plan.replay()             # valid until the next replay
 
-    The captured launches are exactly those of ``transform_two_body``
+    The captured launches are exactly those of ``transform_two_body(..., exchange=False)``
     (``qs_transform_two_body`` on the capture stream); buffers, workspace and the
-    output are owned by the plan."""
+    output are owned by the plan.  The plan stays on the four full products: the
+    exchange-symmetry check reads its verdict back, which a capture cannot do
+    (``qs_two_body_exchange_symmetric`` and ``qs_transform_two_body_exchange`` are
+    separate calls so that a plan could run the check once, before capturing)."""
 
     def __init__(self, u, C, C_tilde=None):
         lib = _lib.load()
@@ -370,6 +391,36 @@ class TransformPlan:
     def replay(self):
         self.graph.replay()
         return self.out
+
+
+@_plain
+def two_body_exchange_symmetric(u):
+    """Does ``u`` (l,l,l,l; float64 / complex128 on the device) have particle-exchange symmetry,
+    ``u[a,b,c,d] == u[b,a,d,c]``, bit for bit?  Blocks (``qs_two_body_exchange_symmetric``); False on a capturing stream."""
+    lib = _lib.load()
+    u = _dev(u)
+    code = dtype_code(u.dtype)
+    l = u.shape[0] if u.dim() == 4 else 0
+    if tuple(u.shape) != (l, l, l, l):
+        raise ValueError(f"u has shape {tuple(u.shape)}, expected (l, l, l, l)")
+    with _on_device_of(u):
+        work = workspace.get(16, u.device)
+        return _ran(lib.qs_two_body_exchange_symmetric(code, u.data_ptr(), l, work.data_ptr(), _stream()),
+                    "qs_two_body_exchange_symmetric") == 1
+
+
+@_plain
+def exchange_mirror_(t, block=1):
+    """In place on ``t`` (n,n,m,m), contiguous: ``t[a,b,r,s] = t[b,a,s,r]`` wherever ``a // block > b // block``
+    (``qs_exchange_mirror``); returns ``t``."""
+    lib = _lib.load()
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or not t.is_contiguous() or t.dim() != 4 \
+            or t.shape[0] != t.shape[1] or t.shape[2] != t.shape[3]:
+        raise ValueError("exchange_mirror_ needs a contiguous device tensor of shape (n, n, m, m)")
+    with _on_device_of(t):
+        _ran(lib.qs_exchange_mirror(dtype_code(t.dtype), t.data_ptr(), t.shape[0], t.shape[2], int(block), _stream()),
+             "qs_exchange_mirror")
+    return t
 
 
 @_plain

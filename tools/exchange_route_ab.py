@@ -1,0 +1,155 @@
+"""Same-process A/B of the transform's exchange-symmetry route against the plain route, and the route's phases.
+
+    python tools/exchange_route_ab.py --sizes 160,192,224,256 --dtype f64 [--blocks 32,64,128] [--blocks-d 8,16,64]
+                                      [--reps 5] [--phases [--c-blocks 16,64]]
+
+Per size: one symmetric tensor (bench.make_inputs), then the plain route (`exchange=0`) and every (block, block_d)
+of the forced route (`exchange=2`) in ALTERNATING repetitions (NOTES.md "How to measure here"), HIP-event time per
+call; the route's time includes the check kernel and its read-back, as `kernels.transform_two_body` pays them.
+`--phases` replays the route's launches one phase at a time through `qs_matmul` / `qs_exchange_mirror` with an event
+pair around each (the phases of qs_api.hip's transform_two_body_exchange_route, same shapes and strides)."""
+
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def timed(torch, fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def med(xs):
+    s = sorted(xs)
+    return s[len(s) // 2] if len(s) % 2 else 0.5 * (s[len(s) // 2 - 1] + s[len(s) // 2])
+
+
+def phases(torch, K, u, C, Ct, out, blk, blk_d, reps, c_blocks=(), other_order=False):
+    """The route's launches, phase by phase (T1 and X in one spare buffer, T2 in `out`).  `c_blocks`: also time the c phase
+    with every row a of a block [a0, a1) batched over b >= a0 instead of b >= a (needs blk_d to divide those blocks)."""
+    L = C.shape[0]
+    dt = u.dtype
+    W = torch.empty(L**4, dtype=dt, device=u.device)
+    CT = C.t().contiguous()
+    scratch = torch.zeros(4, dtype=torch.int32, device=u.device)
+    lib = K._lib.load()
+    code = K.dtype_code(dt)
+    st = K._stream()
+    L2, L3 = L * L, L**3
+
+    def check():
+        assert lib.qs_two_body_exchange_symmetric(code, u.data_ptr(), L, scratch.data_ptr(), st) == 1
+
+    def d():
+        for a0 in range(0, L, blk_d):
+            rows = min(L, a0 + blk_d) - a0
+            K.gemm_raw(dt, u, C, W, (L - a0) * L, L, L, L, L, L, rows, L3, 0, L3,
+                       a_off=a0 * L3 + a0 * L2, c_off=a0 * L3 + a0 * L2)
+
+    def c(cb=1):
+        for a in range(L):
+            b0 = a // cb * cb
+            K.gemm_raw(dt, CT, W, out, L, L, L, L, L, L, L - b0, 0, L2, L2, b_off=(a * L + b0) * L2, c_off=(a * L + b0) * L2)
+
+    def a_():
+        K.gemm_raw(dt, Ct, out, W, L, L3, L, L, L3, L3)
+
+    def b():
+        for p0 in range(0, L, blk):
+            rows = min(L, p0 + blk) - p0
+            K.gemm_raw(dt, Ct, W, out, L - p0, L2, L, L, L2, L2, rows, 0, L3, L3,
+                       a_off=p0 * L, b_off=p0 * L3, c_off=p0 * L3 + p0 * L2)
+
+    def b_full():      # the other order: b as one full product, then a per block of rows p on the columns q >= p0
+        K.gemm_raw(dt, Ct, out, W, L, L2, L, L, L2, L2, L, 0, L3, L3)
+
+    def a_blocks():
+        for p0 in range(0, L, blk):
+            rows = min(L, p0 + blk) - p0
+            K.gemm_raw(dt, Ct, W, out, rows, (L - p0) * L2, L, L, L3, L3, a_off=p0 * L, b_off=p0 * L2, c_off=p0 * L3 + p0 * L2)
+
+    other = [("other order: b full", b_full), ("other order: a blocks", a_blocks)] if other_order else []
+    steps = [("check", check), ("d", d)] + [(f"c, b >= block {cb}", lambda cb=cb: c(cb)) for cb in c_blocks] + [("c", c), ("mirror T2", lambda: K.exchange_mirror_(out.view(L, L, L, L), 1)),
+             ] + other + [("a", a_), ("closing product", b), ("mirror out", lambda: K.exchange_mirror_(out.view(L, L, L, L), blk))]
+    times = {name: [] for name, _ in steps}
+    for _ in range(reps + 1):
+        for name, fn in steps:
+            times[name].append(timed(torch, fn))
+    total = 0.0
+    for name, _ in steps:
+        t = med(times[name][1:])
+        total += 0.0 if name.startswith(("c, ", "other order")) else t
+        print(f"    phase {name:20s} {t:8.3f} ms   (runs: {' '.join('%.3f' % x for x in times[name][1:])})")
+    print(f"    phases total     {total:8.3f} ms")
+    del W
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", default="256")
+    ap.add_argument("--dtype", choices=["f64", "c128"], default="f64")
+    ap.add_argument("--blocks", default="64")
+    ap.add_argument("--blocks-d", default="16")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--phases", action="store_true")
+    ap.add_argument("--other-order", action="store_true", help="with --phases: also time b full, then a per block of rows")
+    ap.add_argument("--c-blocks", default="", help="with --phases: also time the c phase at this block granularity")
+    args = ap.parse_args()
+    import torch
+
+    import bench
+    from quantum_systems_amd import kernels as K
+
+    dev = torch.device("cuda:0")
+    dtype = torch.float64 if args.dtype == "f64" else torch.complex128
+    configs = [(int(b), int(bd)) for b in args.blocks.split(",") for bd in args.blocks_d.split(",")]
+    for l in [int(x) for x in args.sizes.split(",")]:
+        u, C, Ct = bench.make_inputs(torch, l, dtype, dev)
+        out = torch.empty_like(u)
+        assert K.two_body_exchange_symmetric(u)
+
+        def plain():
+            with K.tuning(exchange=0):
+                K.transform_two_body(u, C, Ct, out=out)
+
+        def route(b, bd):
+            with K.tuning(exchange=2, exchange_block=b, exchange_block_d=bd):
+                K.transform_two_body(u, C, Ct, out=out)
+
+        plain()
+        ref = out.clone() if l <= 192 else out[:: max(1, l // 8)].clone()
+        route(*configs[0])
+        got = out if l <= 192 else out[:: max(1, l // 8)]
+        err = (got - ref).abs().max().item() / ref.abs().max().item()
+        del ref, got
+        runs = {"plain": []}
+        for cfg in configs:
+            runs[cfg] = []
+        for _ in range(args.reps):
+            runs["plain"].append(timed(torch, plain))
+            for cfg in configs:
+                runs[cfg].append(timed(torch, lambda: route(*cfg)))
+        base = med(runs["plain"])
+        print(f"l={l} {args.dtype}: route vs plain max rel diff {err:.2e}")
+        print(f"  plain                       median {base:8.3f} ms   runs {' '.join('%.3f' % x for x in runs['plain'])}")
+        for cfg in configs:
+            m = med(runs[cfg])
+            print(f"  route block={cfg[0]:3d} block_d={cfg[1]:3d} median {m:8.3f} ms   runs {' '.join('%.3f' % x for x in runs[cfg])}"
+                  f"   plain/route {base / m:.3f}")
+        sys.stdout.flush()
+        if args.phases:
+            phases(torch, K, u, C, Ct, out, configs[0][0], configs[0][1], args.reps, [int(x) for x in args.c_blocks.split(",") if x], args.other_order)
+        del u, out
+        K.workspace.release()
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
