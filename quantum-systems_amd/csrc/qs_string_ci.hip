@@ -93,6 +93,21 @@ __device__ __forceinline__ void sc_replaced(double (&v)[CW], const double* __res
     }
 }
 
+// (E^s_pq c)[Ia, Ib] of ONE spin, E^s_pq = a+_ps a_qs, from its table entry e: a signed copy, or 0.  Not sc_replaced with the
+// other entry 0: its 0.0 + (-0.0) is +0.0, and this value keeps the sign of a zero.
+template <int CW>
+__device__ __forceinline__ void sc_replaced_spin(double (&v)[CW], const double* __restrict__ c, int32_t e, bool beta, int64_t ia,
+                                                 int64_t ib, int64_t na, int64_t nb) {
+    const int64_t jt = e ? sc_target(e, beta ? nb : na) : -1;
+#pragma unroll
+    for (int w = 0; w < CW; ++w) v[w] = 0.0;
+    if (jt >= 0) {
+        const double* x = c + (beta ? ia * nb + jt : jt * nb + ib) * CW;
+#pragma unroll
+        for (int w = 0; w < CW; ++w) v[w] = e < 0 ? -x[w] : x[w];
+    }
+}
+
 // ---- the panel of one pass -----------------------------------------------------------------------------------------------
 // A pass owns the alpha rows r0 <= Ka < r1 of D and G; c and sigma stay whole.  A layout says where the element (Ka, Kb) of
 // such a row lies in the panel of one (qs) and vector, which elements are stored at all, and which of them carry the weight
@@ -462,14 +477,18 @@ struct ScSpan {
 };
 
 // The alias rule of every entry: no output shares a byte with an input or with an output before it.
-static int sc_alias(std::initializer_list<ScSpan> out, std::initializer_list<ScSpan> in) {
-    for (const ScSpan* o = out.begin(); o != out.end(); ++o) {
+static int sc_alias(const ScSpan* out, const ScSpan* out_end, std::initializer_list<ScSpan> in) {
+    for (const ScSpan* o = out; o != out_end; ++o) {
         for (const ScSpan& x : in)
             if (overlaps(o->at, o->bytes, x.at, x.bytes)) return QS_ERR_ALIAS;
-        for (const ScSpan* b = out.begin(); b != o; ++b)
+        for (const ScSpan* b = out; b != o; ++b)
             if (overlaps(o->at, o->bytes, b->at, b->bytes)) return QS_ERR_ALIAS;
     }
     return QS_OK;
+}
+
+static int sc_alias(std::initializer_list<ScSpan> out, std::initializer_list<ScSpan> in) {
+    return sc_alias(out.begin(), out.end(), in);
 }
 
 // The refusals of the three sigma entries, in their order: form, extents (extra_ok: those of the entry's own arguments),
@@ -613,6 +632,22 @@ static unsigned sc_stride_grid(int64_t total) {
 // is one gather through both tables per (p, q).  On a truncated list a missing target contributes nothing: like H, S^2 is
 // then the operator of the truncated formulation, not the projection of the full one.
 
+// Spin-resolved (qs_string_ci_density2_spin):
+// E^s_pq = a+_ps a_qs acts on the strings of ONE spin: (E^a_pq c)[Ia, Ib] = sgn c[Ta[Ia,pq], Ib], (E^b_pq c)[Ia, Ib] =
+// sgn c[Ia, Tb[Ib,pq]].
+//   X^st[(pr),(qs)]   = <bra| E^s_pr E^t_qs |ket> = sum_K conj((E^s_rp bra)[K]) (E^t_qs ket)[K]
+//   Gamma^st[p,q,r,s] = <bra| a+_ps a+_qt a_st a_rs |ket> = X^st[(pr),(qs)] - delta_st delta_qr <bra| E^s_ps |ket>
+//   rho^s[q,p]        = <bra| E^s_pq |ket>
+// The two panels of the spin-summed density with the alpha and the beta replacement kept apart; h = m^2, for fp64 rounded
+// up to even so that every block below starts on a 16-byte boundary with an even leading dimension (the pad column holds
+// zeros and is never read by the close).  Per pass, K counting its determinants:
+//   ket panel B[K, 2 h]         : columns (qs) = E^a_qs ket, columns h + (qs) = E^b_qs ket
+//   bra panel A[2 m^2 + 1, K]   : rows (pq) = conj(E^a_pq bra), row m^2 = conj(bra), rows m^2 + 1 + (pq) = conj(E^b_pq bra)
+//   part1[t] (m^2 + 1, 2 h) (+)= A[0 ... m^2, slice t] . B[slice t, :]           X^aa | X^ab, last row <E^a_qs> | <E^b_qs>
+//   part2[t] (m^2, h)       (+)= A[m^2 + 1 ..., slice t] . B[slice t, h ...]     X^bb
+// The beta-alpha block is never formed: Gamma^ba[p,q,r,s] = Gamma^ab[q,p,s,r].  Expand, layout, passes and
+// close are those of the spin sum, over S = 2 blocks instead of 1 (Sc2Shape).
+
 constexpr int64_t kSc2Cus = 256;      // compute units the slices of one pass are meant to cover
 constexpr int kScSpinG = 4;           // vectors that share the table reads of one S^2 workgroup
 
@@ -623,18 +658,21 @@ struct Sc2Args {
     int64_t ia0;              // first alpha row of the pass
     int64_t pitch;            // elements between rows of the bra panel, T kc
     unsigned ntile;
-    int m2, h;                // h: columns of one spin in the ket panel of the spin-resolved density, else unused
+    int m2, h, S;             // Sc2Shape's: S spin blocks of h columns per determinant of the ket panel
 };
 
-// The expand of one pass, alpha rows ia0 ... ia0 + gridDim.x / ntile - 1, in the layout of one operand of the Gram product.
-// KET: P[K, (pq)] -- a thread keeps the 16 values of a table chunk and writes them as one line of its determinant with
-// 16-byte stores (8-byte ones where an odd m^2 leaves the line on an 8-byte boundary).  Otherwise P[(pq), K], conjugated,
-// and conj(c) as row m^2.  K = (Ia - ia0) nb + Ib counts the determinants of the pass.
-template <int CW, bool KET>
-__global__ __launch_bounds__(kScBlock) void string_ci_expand_rows_kernel(const Sc2Args a, const int32_t* __restrict__ ta,
-                                                                        double* __restrict__ P) {
+// The expand of one pass, alpha rows ia0 ... ia0 + gridDim.x / ntile - 1, in the layout of one operand of the Gram product(s).
+// S = 1: one block per determinant, the spin sum E_pq c.  S = 2: the alpha replacement E^a_pq c, then the beta one.
+// KET: P[K, s h + (pq)] -- a thread keeps the 16 values of a table chunk of one block and writes them into the line of its
+// determinant with 16-byte stores (8-byte ones where an odd h leaves the line on an 8-byte boundary: S = 1 in fp64 only, for
+// S = 2 rounds h up to even and the pad columns m^2 <= pq < h receive zeros).  Otherwise P[s (m^2 + 1) + (pq), K], conjugated,
+// every row written as it is formed, four columns in flight, and conj(c) as row m^2.  K = (Ia - ia0) nb + Ib counts the
+// determinants of the pass.
+template <int CW, bool KET, int S>
+__global__ __launch_bounds__(kScBlock) void string_ci_expand_panel_kernel(const Sc2Args a, const int32_t* __restrict__ ta,
+                                                                         double* __restrict__ P) {
     extern __shared__ __attribute__((aligned(16))) int32_t sc_tb[];
-    const int B = blockDim.x, t = threadIdx.x, m2 = a.m2;
+    const int B = blockDim.x, t = threadIdx.x, m2 = a.m2, h = a.h;
     const int64_t il = blockIdx.x / a.ntile;                              // uniform
     const int64_t ia = a.ia0 + il;
     const int64_t ib0 = (int64_t)(blockIdx.x % a.ntile) * B;
@@ -643,49 +681,52 @@ __global__ __launch_bounds__(kScBlock) void string_ci_expand_rows_kernel(const S
     const int64_t kl = il * nb + ib;
     const int32_t* __restrict__ ta_row = ta + ia * m2;
     const double* __restrict__ c = a.c;
-    const bool wide = CW == 2 || !(m2 & 1);                               // every line starts on a 16-byte boundary
+    const bool wide = CW == 2 || S == 2 || !(h & 1);                      // every line and block starts on a 16-byte boundary
+    // column pq of block s, j its place in the staged chunk; the alpha entry has a uniform address: a scalar load.  Past m^2
+    // (uniform) the entries are 0 and so is the value: the pad columns
+    auto value = [&](double (&v)[CW], int s, int pq, int j) {
+        const int32_t ea = pq < m2 && (S == 1 || s == 0) ? ta_row[pq] : 0;
+        const int32_t eb = pq < m2 && (S == 1 || s == 1) ? sc_tb[j * (B + 1) + t] : 0;
+        if constexpr (S == 1) sc_replaced<CW>(v, c, ea, eb, ia, ib, a.na, nb);
+        else sc_replaced_spin<CW>(v, c, s == 0 ? ea : eb, s != 0, ia, ib, a.na, nb);
+    };
     for (int pq0 = 0; pq0 < m2; pq0 += kScChunk) {
         __syncthreads();
         sc_stage(sc_tb, a.tb, ib0, nb, pq0, m2);
         __syncthreads();
         if (!live) continue;
-        double v[kScChunk][CW];
 #pragma unroll
-        for (int j = 0; j < kScChunk; ++j) {
-            const int pq = pq0 + j;
-            if (pq < m2) {                                                // uniform
-                const int32_t ea = ta_row[pq];                            // uniform address: a scalar load
-                sc_replaced<CW>(v[j], c, ea, sc_tb[j * (B + 1) + t], ia, ib, a.na, nb);
-            } else {
+        for (int s = 0; s < S; ++s) {
+            if constexpr (KET) {
+                double v[kScChunk][CW];
 #pragma unroll
-                for (int w = 0; w < CW; ++w) v[j][w] = 0.0;
-            }
-        }
-        if constexpr (KET) {
-            double* line = P + (kl * m2 + pq0) * CW;
-            if (wide) {
-                // an even m^2 ends on an even column: the pairs of an fp64 line are whole
+                for (int j = 0; j < kScChunk; ++j) value(v[j], s, pq0 + j, j);
+                double* line = P + ((kl * S + s) * h + pq0) * CW;
+                if (wide) {
+                    // an even h ends on an even column: the pairs of an fp64 line are whole
 #pragma unroll
-                for (int j = 0; j < kScChunk; j += 2 / CW) {
-                    if (pq0 + j < m2) {
-                        double2 x;
-                        if constexpr (CW == 2) { x.x = v[j][0]; x.y = v[j][CW - 1]; }
-                        else { x.x = v[j][0]; x.y = v[j + 2 / CW - 1][0]; }
-                        *reinterpret_cast<double2*>(line + j * CW) = x;
+                    for (int j = 0; j < kScChunk; j += 2 / CW) {
+                        if (pq0 + j < h) {
+                            double2 x;
+                            if constexpr (CW == 2) { x.x = v[j][0]; x.y = v[j][CW - 1]; }
+                            else { x.x = v[j][0]; x.y = v[j + 2 / CW - 1][0]; }
+                            *reinterpret_cast<double2*>(line + j * CW) = x;
+                        }
                     }
+                } else {
+#pragma unroll
+                    for (int j = 0; j < kScChunk; ++j)
+                        if (pq0 + j < h) line[j] = v[j][0];
                 }
             } else {
-#pragma unroll
-                for (int j = 0; j < kScChunk; ++j)
-                    if (pq0 + j < m2) line[j] = v[j][0];
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < kScChunk; ++j) {
-                if (pq0 + j < m2) {
-                    double* d = P + ((int64_t)(pq0 + j) * a.pitch + kl) * CW;
-                    d[0] = v[j][0];
-                    if constexpr (CW == 2) d[CW - 1] = -v[j][CW - 1];
+                const int nj = m2 - pq0 < kScChunk ? m2 - pq0 : kScChunk;
+#pragma unroll 4
+                for (int j = 0; j < nj; ++j) {
+                    double v[CW];
+                    value(v, s, pq0 + j, j);
+                    double* d = P + ((int64_t)(s * (m2 + 1) + pq0 + j) * a.pitch + kl) * CW;
+                    d[0] = v[0];
+                    if constexpr (CW == 2) d[CW - 1] = -v[CW - 1];
                 }
             }
         }
@@ -712,29 +753,47 @@ __device__ __forceinline__ void sc_sum_partials(double (&x)[CW], const double* _
     }
 }
 
-// Gamma[p,q,r,s] and rho[q m + p] from the T partial results part[t] (m^2 + 1, m^2): one thread per element of Gamma
-// (grid-stride), the partials summed in ascending t, the delta term one subtraction.
+// One Gamma of a close: where its X lies in the partial results, and what it writes.
+struct Sc2Block {
+    const double* part;       // the block's partial results, slice t at part + t stride
+    int64_t stride;
+    int64_t ld, col0;         // X[(pr),(qs)] lies at (rp) ld + col0 + (qs)
+    int64_t erow;             // <bra| E_pq |ket> of the block's spin lies at erow + (pq) in the partials of block 0; -1: no delta
+                              // term and no rho (the alpha-beta block)
+    double* gamma;
+    double* rho;
+};
+
+struct Sc2Close {
+    Sc2Block b[3];
+};
+
+// The nblk Gamma[p,q,r,s] and their rho[q m + p] from the partial results: one thread per element of a Gamma (grid-stride over
+// the nblk m^4 of them), the partials summed in ascending t, X read at the transposed row (rp), the delta term one subtraction.
 template <int CW>
-__global__ __launch_bounds__(kScRhoBlock) void string_ci_gamma_close_kernel(const double* __restrict__ part, int64_t T, int m,
-                                                                            double* __restrict__ gamma, double* __restrict__ rho) {
-    const int64_t m2 = (int64_t)m * m, total = m2 * m2, sc = (m2 + 1) * m2, step = (int64_t)gridDim.x * kScRhoBlock;
-    for (int64_t idx = (int64_t)blockIdx.x * kScRhoBlock + threadIdx.x; idx < total; idx += step) {
-        const int s = (int)(idx % m), r = (int)((idx / m) % m), q = (int)((idx / m2) % m), p = (int)(idx / (m2 * m));
+__global__ __launch_bounds__(kScRhoBlock) void string_ci_gamma_close_kernel(const Sc2Close tab, int nblk, int64_t T, int m) {
+    const int64_t m2 = (int64_t)m * m, total = m2 * m2, step = (int64_t)gridDim.x * kScRhoBlock;
+    const double* __restrict__ epart = tab.b[0].part;
+    const int64_t es = tab.b[0].stride;
+    for (int64_t idx = (int64_t)blockIdx.x * kScRhoBlock + threadIdx.x; idx < nblk * total; idx += step) {
+        const Sc2Block& b = tab.b[idx / total];
+        const int64_t el = idx % total;
+        const int s = (int)(el % m), r = (int)((el / m) % m), q = (int)((el / m2) % m), p = (int)(el / (m2 * m));
         double x[CW];
-        sc_sum_partials<CW>(x, part, T, sc, ((int64_t)r * m + p) * m2 + q * m + s);      // X[(pr),(qs)] lies at row (rp)
-        if (q == r) {
+        sc_sum_partials<CW>(x, b.part, T, b.stride, ((int64_t)r * m + p) * b.ld + b.col0 + q * m + s);
+        if (b.erow >= 0 && q == r) {
             double e[CW];
-            sc_sum_partials<CW>(e, part, T, sc, total + p * m + s);                      // <bra| E_ps |ket>
+            sc_sum_partials<CW>(e, epart, T, es, b.erow + p * m + s);                     // <bra| E_ps |ket>
 #pragma unroll
             for (int w = 0; w < CW; ++w) x[w] = x[w] - e[w];
         }
 #pragma unroll
-        for (int w = 0; w < CW; ++w) gamma[idx * CW + w] = x[w];
-        if (r == 0 && s == 0) {
+        for (int w = 0; w < CW; ++w) b.gamma[el * CW + w] = x[w];
+        if (b.erow >= 0 && r == 0 && s == 0) {
             double e[CW];
-            sc_sum_partials<CW>(e, part, T, sc, total + p * m + q);                      // <bra| E_pq |ket>
+            sc_sum_partials<CW>(e, epart, T, es, b.erow + p * m + q);                     // <bra| E_pq |ket>
 #pragma unroll
-            for (int w = 0; w < CW; ++w) rho[((int64_t)q * m + p) * CW + w] = e[w];
+            for (int w = 0; w < CW; ++w) b.rho[((int64_t)q * m + p) * CW + w] = e[w];
         }
     }
 }
@@ -795,215 +854,68 @@ __global__ __launch_bounds__(kScBlock) void string_ci_spin_kernel(const ScArgs a
     }
 }
 
-// ---- spin-resolved densities (qs_string_ci_density2_spin) ----------------------------------------------------------------
-// E^s_pq = a+_ps a_qs acts on the strings of ONE spin: (E^a_pq c)[Ia, Ib] = sgn c[Ta[Ia,pq], Ib], (E^b_pq c)[Ia, Ib] =
-// sgn c[Ia, Tb[Ib,pq]].
-//   X^st[(pr),(qs)]   = <bra| E^s_pr E^t_qs |ket> = sum_K conj((E^s_rp bra)[K]) (E^t_qs ket)[K]
-//   Gamma^st[p,q,r,s] = <bra| a+_ps a+_qt a_st a_rs |ket> = X^st[(pr),(qs)] - delta_st delta_qr <bra| E^s_ps |ket>
-//   rho^s[q,p]        = <bra| E^s_pq |ket>
-// The two panels of the spin-summed density with the alpha and the beta replacement kept apart; h = m^2, for fp64 rounded
-// up to even so that every block below starts on a 16-byte boundary with an even leading dimension (the pad column holds
-// zeros and is never read by the close).  Per pass, K counting its determinants:
-//   ket panel B[K, 2 h]         : columns (qs) = E^a_qs ket, columns h + (qs) = E^b_qs ket
-//   bra panel A[2 m^2 + 1, K]   : rows (pq) = conj(E^a_pq bra), row m^2 = conj(bra), rows m^2 + 1 + (pq) = conj(E^b_pq bra)
-//   part1[t] (m^2 + 1, 2 h) (+)= A[0 ... m^2, slice t] . B[slice t, :]           X^aa | X^ab, last row <E^a_qs> | <E^b_qs>
-//   part2[t] (m^2, h)       (+)= A[m^2 + 1 ..., slice t] . B[slice t, h ...]     X^bb
-// The beta-alpha block is never formed: Gamma^ba[p,q,r,s] = Gamma^ab[q,p,s,r].  The close is that of the spin sum.
+// The panels of one pass of either density, filled here from (spin, cw, m) and nowhere else.
+struct Sc2Shape {
+    int64_t S;                // spin blocks: 1 (the spin sum) or 2 (alpha | beta)
+    int64_t m2, h;            // h: columns of one block of the ket panel, m^2, for S = 2 in fp64 rounded up to even
+    int64_t arows, bcols;     // rows of the bra panel S m^2 + 1, columns of the ket panel S h
+};
 
-// (E^s_pq c)[Ia, Ib] of one spin from its table entry e: a signed copy, or 0
-template <int CW>
-__device__ __forceinline__ void sc_replaced_spin(double (&v)[CW], const double* __restrict__ c, int32_t e, bool beta, int64_t ia,
-                                                 int64_t ib, int64_t na, int64_t nb) {
-    const int64_t jt = e ? sc_target(e, beta ? nb : na) : -1;
-#pragma unroll
-    for (int w = 0; w < CW; ++w) v[w] = 0.0;
-    if (jt >= 0) {
-        const double* x = c + (beta ? ia * nb + jt : jt * nb + ib) * CW;
-#pragma unroll
-        for (int w = 0; w < CW; ++w) v[w] = e < 0 ? -x[w] : x[w];
-    }
+static Sc2Shape sc2_shape(bool spin, int cw, int64_t m) {
+    Sc2Shape g{};
+    g.S = spin ? 2 : 1;
+    g.m2 = m * m;
+    g.h = spin && cw == 1 ? (g.m2 + 1) & ~int64_t(1) : g.m2;
+    g.arows = g.S * g.m2 + 1;
+    g.bcols = g.S * g.h;
+    return g;
 }
 
-// The mapping of string_ci_expand_rows_kernel.  A thread keeps the 16 values of one table chunk of ONE spin: alpha, written
-// out, then beta.  KET: both are runs of whole 16-byte stores in the determinant's line (the line, the beta half and the
-// chunk all start on even columns).  Otherwise the rows of the bra panel, conjugated, written as they are formed, and
-// conj(c) as row m^2.
-template <int CW, bool KET>
-__global__ __launch_bounds__(kScBlock) void string_ci_expand_spin_kernel(const Sc2Args a, const int32_t* __restrict__ ta,
-                                                                        double* __restrict__ P) {
-    extern __shared__ __attribute__((aligned(16))) int32_t sc_tb[];
-    const int B = blockDim.x, t = threadIdx.x, m2 = a.m2, h = a.h;
-    const int64_t il = blockIdx.x / a.ntile;                              // uniform
-    const int64_t ia = a.ia0 + il;
-    const int64_t ib0 = (int64_t)(blockIdx.x % a.ntile) * B;
-    const int64_t ib = ib0 + t, nb = a.nb;
-    const bool live = ib < nb;
-    const int64_t kl = il * nb + ib;
-    const int32_t* __restrict__ ta_row = ta + ia * m2;
-    const double* __restrict__ c = a.c;
-    for (int pq0 = 0; pq0 < m2; pq0 += kScChunk) {
-        __syncthreads();
-        sc_stage(sc_tb, a.tb, ib0, nb, pq0, m2);
-        __syncthreads();
-        if (!live) continue;
-#pragma unroll
-        for (int spin = 0; spin < 2; ++spin) {
-            if constexpr (KET) {
-                double v[kScChunk][CW];
-#pragma unroll
-                for (int j = 0; j < kScChunk; ++j) {
-                    const int pq = pq0 + j;
-                    // alpha: a uniform address, a scalar load; past m^2 (uniform) the pad column, zero
-                    const int32_t e = pq < m2 ? (spin == 0 ? ta_row[pq] : sc_tb[j * (B + 1) + t]) : 0;
-                    sc_replaced_spin<CW>(v[j], c, e, spin != 0, ia, ib, a.na, nb);
-                }
-                double* line = P + ((kl * 2 + spin) * h + pq0) * CW;
-#pragma unroll
-                for (int j = 0; j < kScChunk; j += 2 / CW) {
-                    if (pq0 + j < h) {                                    // h is even for fp64: the pairs are whole
-                        double2 x;
-                        if constexpr (CW == 2) { x.x = v[j][0]; x.y = v[j][CW - 1]; }
-                        else { x.x = v[j][0]; x.y = v[j + 2 / CW - 1][0]; }
-                        *reinterpret_cast<double2*>(line + j * CW) = x;
-                    }
-                }
-            } else {
-                // a row per column: nothing is kept, four columns in flight
-                const int nj = m2 - pq0 < kScChunk ? m2 - pq0 : kScChunk;
-#pragma unroll 4
-                for (int j = 0; j < nj; ++j) {
-                    const int32_t e = spin == 0 ? ta_row[pq0 + j] : sc_tb[j * (B + 1) + t];
-                    double v[CW];
-                    sc_replaced_spin<CW>(v, c, e, spin != 0, ia, ib, a.na, nb);
-                    double* d = P + ((int64_t)(spin * (m2 + 1) + pq0 + j) * a.pitch + kl) * CW;
-                    d[0] = v[0];
-                    if constexpr (CW == 2) d[CW - 1] = -v[CW - 1];
-                }
-            }
-        }
-    }
-    if constexpr (!KET) {
-        if (live) {
-            const double* x = c + (ia * nb + ib) * CW;
-            double* d = P + ((int64_t)m2 * a.pitch + kl) * CW;
-            d[0] = x[0];
-            if constexpr (CW == 2) d[CW - 1] = -x[CW - 1];
-        }
-    }
-}
-
-// The three Gamma and the two rho from the partial results part1[t] (m^2 + 1, 2 h) and part2[t] (m^2, h): one thread per
-// element of a Gamma (grid-stride over the 3 m^4 of them, alpha-alpha, alpha-beta, beta-beta), X read at the transposed row
-// (rp), the delta term for equal spins only.
-template <int CW>
-__global__ __launch_bounds__(kScRhoBlock) void string_ci_gamma_spin_close_kernel(const double* __restrict__ part1,
-                                                                                 const double* __restrict__ part2, int64_t T, int m,
-                                                                                 int h, double* __restrict__ gaa,
-                                                                                 double* __restrict__ gab, double* __restrict__ gbb,
-                                                                                 double* __restrict__ rho_a, double* __restrict__ rho_b) {
-    const int64_t m2 = (int64_t)m * m, total = m2 * m2, s1 = (m2 + 1) * 2 * h, s2 = m2 * h, step = (int64_t)gridDim.x * kScRhoBlock;
-    for (int64_t idx = (int64_t)blockIdx.x * kScRhoBlock + threadIdx.x; idx < 3 * total; idx += step) {
-        const int blk = (int)(idx / total);                               // 0: aa, 1: ab, 2: bb
-        const int64_t el = idx % total;
-        const int s = (int)(el % m), r = (int)((el / m) % m), q = (int)((el / m2) % m), p = (int)(el / (m2 * m));
-        const int64_t row = (int64_t)r * m + p, col = (int64_t)q * m + s;
-        const int64_t last = m2 * 2 * h + (blk == 2 ? h : 0);             // <bra| E^s_.. |ket> of the block's spin, in part1
-        double x[CW];
-        if (blk == 2) sc_sum_partials<CW>(x, part2, T, s2, row * h + col);
-        else sc_sum_partials<CW>(x, part1, T, s1, row * 2 * h + (blk == 1 ? h : 0) + col);
-        if (blk != 1 && q == r) {
-            double e[CW];
-            sc_sum_partials<CW>(e, part1, T, s1, last + p * m + s);
-#pragma unroll
-            for (int w = 0; w < CW; ++w) x[w] = x[w] - e[w];
-        }
-        double* __restrict__ gamma = blk == 0 ? gaa : (blk == 1 ? gab : gbb);
-#pragma unroll
-        for (int w = 0; w < CW; ++w) gamma[el * CW + w] = x[w];
-        if (blk != 1 && r == 0 && s == 0) {
-            double e[CW];
-            sc_sum_partials<CW>(e, part1, T, s1, last + p * m + q);
-            double* __restrict__ rho = blk == 0 ? rho_a : rho_b;
-#pragma unroll
-            for (int w = 0; w < CW; ++w) rho[((int64_t)q * m + p) * CW + w] = e[w];
-        }
-    }
-}
-
-// The schedule and the workspace of one qs_string_ci_density2 or qs_string_ci_density2_spin call: the one place that carves
-// it.  The spin-summed density has one block of partial results and leaves h and off_2 at 0.
+// The schedule and the workspace of one qs_string_ci_density2 or qs_string_ci_density2_spin call.
 struct Sc2Plan {
     int64_t rows, passes;     // alpha rows per pass (the last pass may have fewer), passes
     int64_t T, kc, pitch;     // slices of kc determinants per pass, pitch = T kc >= rows nb
-    int64_t h;                // columns of one spin in the ket panel
-    int64_t off_2;            // byte offset of part2 behind part1 at 0
+    int64_t off_2;            // byte offset of the second block of partial results (S = 2: X^bb) behind the first at 0
     int64_t off_a, off_b;     // byte offsets of the bra and ket panels behind the partial results
     int64_t bytes;
 };
 
-static Sc2Plan sc2_layout(int cw, int64_t m, int64_t nb, int64_t rows) {
-    const int64_t m2 = m * m, es = 8 * cw, R = rows * nb;
+// The one place that carves the workspace: T slices of (m^2 + 1, bcols) partial results, for S = 2 T more of (m^2, h), the bra
+// panel, the ket panel.
+static Sc2Plan sc2_layout(const Sc2Shape& g, int cw, int64_t nb, int64_t rows) {
+    const int64_t m2 = g.m2, es = 8 * cw, R = rows * nb;
     Sc2Plan p{};
     p.rows = rows;
-    // slices: tiles x T covers the compute units, the partial results stay below an eighth of the panels
-    int64_t T = cdiv(kSc2Cus, cdiv(m2 + 1, 128) * cdiv(m2, 128));
-    const int64_t cap = R / (4 * (m2 + 1));
+    // slices: tiles of the first product x T covers the compute units, the partial results stay below an eighth of the panels
+    // (S = 2: 3 h (m^2 + 1) at the most per slice against more than 4 m^2 R)
+    int64_t T = cdiv(kSc2Cus, cdiv(m2 + 1, 128) * cdiv(g.bcols, 128));
+    const int64_t cap = g.S == 1 ? R / (4 * (m2 + 1)) : (4 * m2 * R) / (24 * g.h * (m2 + 1));
     T = T < cap ? T : cap;
     T = T < 1 ? 1 : T;
     p.kc = (cdiv(R, T) + 1) & ~int64_t(1);                               // even: every slice starts on a 16-byte boundary
     p.T = cdiv(R, p.kc);
     p.pitch = p.T * p.kc;
-    p.off_a = p.T * (m2 + 1) * m2 * es;                                   // (m^2 + 1) m^2 is even
-    p.off_b = p.off_a + (m2 + 1) * p.pitch * es;
-    p.bytes = p.off_b + p.pitch * m2 * es;
+    p.off_2 = p.T * (m2 + 1) * g.bcols * es;                              // (m^2 + 1) m^2 and 2 h are even
+    p.off_a = p.off_2 + (g.S == 2 ? p.T * m2 * g.h * es : 0);             // h or the element size is even
+    p.off_b = p.off_a + g.arows * p.pitch * es;                           // pitch is even
+    p.bytes = p.off_b + p.pitch * g.bcols * es;
     return p;
 }
 
-static inline int64_t sc3_half(int cw, int64_t m) { return cw == 1 ? (m * m + 1) & ~int64_t(1) : m * m; }
-
-static Sc2Plan sc3_layout(int cw, int64_t m, int64_t nb, int64_t rows) {
-    const int64_t m2 = m * m, es = 8 * cw, R = rows * nb;
-    Sc2Plan p{};
-    p.rows = rows;
-    p.h = sc3_half(cw, m);
-    // slices: tiles of the first product x T covers the compute units, the partial results (3 h (m^2 + 1) at the most per
-    // slice) stay below an eighth of the panels (more than 4 m^2 R)
-    int64_t T = cdiv(kSc2Cus, cdiv(m2 + 1, 128) * cdiv(2 * p.h, 128));
-    const int64_t cap = (4 * m2 * R) / (24 * p.h * (m2 + 1));
-    T = T < cap ? T : cap;
-    T = T < 1 ? 1 : T;
-    p.kc = (cdiv(R, T) + 1) & ~int64_t(1);                               // even: every slice starts on a 16-byte boundary
-    p.T = cdiv(R, p.kc);
-    p.pitch = p.T * p.kc;
-    p.off_2 = p.T * (m2 + 1) * 2 * p.h * es;                              // 2 h is even
-    p.off_a = p.off_2 + p.T * m2 * p.h * es;                              // h or the element size is even
-    p.off_b = p.off_a + (2 * m2 + 1) * p.pitch * es;                      // pitch is even
-    p.bytes = p.off_b + p.pitch * 2 * p.h * es;
-    return p;
-}
-
-// The schedule of a pass-wise density: as many alpha rows per pass as keep the panels of `per_det` elements per determinant
-// within the budget, at least one; then the same passes of equal length where that costs no more.  layout(rows) carves the
-// workspace; its panels lie behind off_a.
-template <class Layout>
-static Sc2Plan sc2_schedule(int cw, int64_t na, int64_t nb, int64_t per_det, int64_t budget_bytes, Layout layout) {
+// The schedule of a pass-wise density: as many alpha rows per pass as keep the two panels, arows + bcols elements per
+// determinant, within the budget, at least one; then the same passes of equal length where that costs no more.  The panels
+// lie behind off_a.
+static Sc2Plan sc2_plan(const Sc2Shape& g, int cw, int64_t na, int64_t nb, int64_t budget_bytes) {
     const int64_t budget = sc_budget(budget_bytes);
-    int64_t rows = budget / (per_det * nb * 8 * cw);
+    int64_t rows = budget / ((g.arows + g.bcols) * nb * 8 * cw);
     rows = rows < 1 ? 1 : (rows < na ? rows : na);
-    Sc2Plan p = layout(rows);
-    while (p.rows > 1 && p.bytes - p.off_a > budget) p = layout(p.rows - 1);      // the padding of the slices
+    Sc2Plan p = sc2_layout(g, cw, nb, rows);
+    while (p.rows > 1 && p.bytes - p.off_a > budget) p = sc2_layout(g, cw, nb, p.rows - 1);      // the padding of the slices
     const int64_t passes = cdiv(na, p.rows);
-    const Sc2Plan even = layout(cdiv(na, passes));                        // the same passes, of equal length
+    const Sc2Plan even = sc2_layout(g, cw, nb, cdiv(na, passes));         // the same passes, of equal length
     if (even.bytes - even.off_a <= p.bytes - p.off_a) p = even;
     p.passes = cdiv(na, p.rows);
     return p;
-}
-
-static Sc2Plan sc2_plan(bool spin, int cw, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes) {
-    if (spin)
-        return sc2_schedule(cw, na, nb, 2 * m * m + 1 + 2 * sc3_half(cw, m), budget_bytes,
-                            [&](int64_t rows) { return sc3_layout(cw, m, nb, rows); });
-    return sc2_schedule(cw, na, nb, 2 * m * m + 1, budget_bytes, [&](int64_t rows) { return sc2_layout(cw, m, nb, rows); });
 }
 
 static int sc2_check(int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes) {
@@ -1012,46 +924,52 @@ static int sc2_check(int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t bud
     return QS_OK;
 }
 
+// the workspace query of either density
+static int64_t sc2_workspace(bool spin, int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes) {
+    const int rc = sc2_check(c_dtype, m, na, nb, budget_bytes);
+    if (rc) return rc;
+    const int cw = c_dtype == QS_C128 ? 2 : 1;
+    return sc2_plan(sc2_shape(spin, cw, m), cw, na, nb, budget_bytes).bytes;
+}
+
 // the plan query of either density
 static int sc2_plan_query(bool spin, int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes, int64_t* plan) {
     const int rc = sc2_check(c_dtype, m, na, nb, budget_bytes);
     if (rc) return rc;
     if (!plan) return QS_ERR_NULL_POINTER;
-    const Sc2Plan p = sc2_plan(spin, c_dtype == QS_C128 ? 2 : 1, m, na, nb, budget_bytes);
+    const int cw = c_dtype == QS_C128 ? 2 : 1;
+    const Sc2Plan p = sc2_plan(sc2_shape(spin, cw, m), cw, na, nb, budget_bytes);
     plan[0] = p.rows; plan[1] = p.passes; plan[2] = p.T; plan[3] = p.kc; plan[4] = p.bytes;
     return QS_OK;
 }
 
-// one operand panel of a pass of `rows` alpha rows: the bra or the ket, spin-summed or spin-resolved
-static int sc2_expand(int cw, bool spin, bool ket, const Sc2Args& a, const int32_t* ta, int64_t rows, void* P, hipStream_t s) {
+// one operand panel of a pass of `rows` alpha rows: the bra or the ket, of a.S blocks
+static int sc2_expand(int cw, bool ket, const Sc2Args& a, const int32_t* ta, int64_t rows, void* P, hipStream_t s) {
     const int threads = sc_threads(a.nb);
     const unsigned grid = (unsigned)(rows * a.ntile);
-    auto launch = [&](auto kernel, const char* name) {
+    auto launch = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), sc_lds(threads), s, a, ta, (double*)P);
-        note_dispatch("%s<%d, %s>", name, cw, ket ? "true" : "false");
     };
     with_width(cw, [&](auto CW) {
-        if (spin) ket ? launch(string_ci_expand_spin_kernel<CW, true>, "qs::string_ci_expand_spin_kernel")
-                      : launch(string_ci_expand_spin_kernel<CW, false>, "qs::string_ci_expand_spin_kernel");
-        else ket ? launch(string_ci_expand_rows_kernel<CW, true>, "qs::string_ci_expand_rows_kernel")
-                 : launch(string_ci_expand_rows_kernel<CW, false>, "qs::string_ci_expand_rows_kernel");
+        if (a.S == 2) ket ? launch(string_ci_expand_panel_kernel<CW, true, 2>) : launch(string_ci_expand_panel_kernel<CW, false, 2>);
+        else ket ? launch(string_ci_expand_panel_kernel<CW, true, 1>) : launch(string_ci_expand_panel_kernel<CW, false, 1>);
     });
+    note_dispatch("qs::string_ci_expand_panel_kernel<%d, %s, %d>", cw, ket ? "true" : "false", a.S);
     return launch_status("string CI density expand launch");
 }
 
 // The passes of either two-body density over alpha rows.  Per pass: zeros in the ragged tails of both panels, the bra panel
 // A (arows rows of pitch determinants), the ket panel B (bcols columns per determinant), and the batched product(s) that add
 // into the partial results at the head of work (split-k as a batch: slice t is columns t kc ... of A and rows t kc ... of B).
-static int sc2_passes(int c_dtype, bool spin, const Sc2Plan& p, const int32_t* ta, const int32_t* tb, int64_t m, int64_t na,
+static int sc2_passes(int c_dtype, const Sc2Shape& g, const Sc2Plan& p, const int32_t* ta, const int32_t* tb, int64_t na,
                       int64_t nb, const void* bra, const void* ket, void* work, hipStream_t s) {
     const int cw = c_dtype == QS_C128 ? 2 : 1;
-    const int64_t cs = 8 * cw, m2 = m * m, h = p.h;
-    const int64_t arows = spin ? 2 * m2 + 1 : m2 + 1, bcols = spin ? 2 * h : m2;
+    const int64_t cs = 8 * cw, m2 = g.m2, h = g.h, arows = g.arows, bcols = g.bcols;
     char* part = (char*)work;
     char* A = part + p.off_a;
     char* B = part + p.off_b;
     Sc2Args a{};
-    a.tb = tb; a.na = na; a.nb = nb; a.pitch = p.pitch; a.m2 = (int)m2; a.h = (int)h;
+    a.tb = tb; a.na = na; a.nb = nb; a.pitch = p.pitch; a.m2 = (int)m2; a.h = (int)h; a.S = (int)g.S;
     a.ntile = (unsigned)cdiv(nb, sc_threads(nb));
     for (int64_t pass = 0; pass < p.passes; ++pass) {
         a.ia0 = pass * p.rows;
@@ -1066,10 +984,10 @@ static int sc2_passes(int c_dtype, bool spin, const Sc2Plan& p, const int32_t* t
             if (rc) return rc;
         }
         a.c = (const double*)bra;
-        rc = sc2_expand(cw, spin, false, a, ta, rows, A, s);
+        rc = sc2_expand(cw, false, a, ta, rows, A, s);
         if (rc) return rc;
         a.c = (const double*)ket;
-        rc = sc2_expand(cw, spin, true, a, ta, rows, B, s);
+        rc = sc2_expand(cw, true, a, ta, rows, B, s);
         if (rc) return rc;
         // the first m^2 + 1 rows of A against all ket columns; spin-resolved, these are the alpha rows and conj(bra):
         // X^aa | X^ab, and <E^a_qs> | <E^b_qs> in the last row
@@ -1077,7 +995,7 @@ static int sc2_passes(int c_dtype, bool spin, const Sc2Plan& p, const int32_t* t
                           p.kc, p.kc * bcols, (m2 + 1) * bcols, pass > 0 ? 1 : 0},
                   s);
         if (rc) return rc;
-        if (!spin) continue;
+        if (g.S == 1) continue;
         // beta rows against the beta columns: X^bb
         rc = gemm(Product{c_dtype, (const double*)(A + (m2 + 1) * p.pitch * cs), (const double*)(B + h * cs),
                           (double*)(part + p.off_2), m2, h, p.kc, p.pitch, bcols, h, p.T, p.kc, p.kc * bcols, m2 * h, pass > 0 ? 1 : 0},
@@ -1085,6 +1003,51 @@ static int sc2_passes(int c_dtype, bool spin, const Sc2Plan& p, const int32_t* t
         if (rc) return rc;
     }
     return QS_OK;
+}
+
+// Either two-body density.  out: the 2 S - 1 Gamma (the spin sum, or alpha-alpha, alpha-beta, beta-beta), then the S rho.  The
+// refusals in their order: dtype, extents and budget, null, alignment, workspace, aliases.
+static int sc2_density(bool spin, int c_dtype, const int32_t* ta, const int32_t* tb, int64_t m, int64_t na, int64_t nb, const void* bra,
+                       const void* ket, std::initializer_list<void*> out, void* work, int64_t work_bytes, int64_t budget_bytes,
+                       hipStream_t s) {
+    dispatch_reset();
+    int rc = sc2_check(c_dtype, m, na, nb, budget_bytes);
+    if (rc) return rc;
+    const int64_t cs = (int64_t)elem_size(c_dtype);
+    bool null = !ta || !tb || !bra || !ket || !work;
+    bool skew = !aligned(ta, 4) || !aligned(tb, 4) || !aligned(bra, (size_t)cs) || !aligned(ket, (size_t)cs) || !aligned(work, 16);
+    for (void* x : out) null = null || !x, skew = skew || !aligned(x, (size_t)cs);
+    if (null) return QS_ERR_NULL_POINTER;
+    if (skew) return QS_ERR_MISALIGNED;
+    const int cw = c_dtype == QS_C128 ? 2 : 1;
+    const Sc2Shape g = sc2_shape(spin, cw, m);
+    const Sc2Plan p = sc2_plan(g, cw, na, nb, budget_bytes);
+    if (work_bytes < p.bytes) return QS_ERR_WORKSPACE;
+    const int64_t m2 = g.m2, v_bytes = na * nb * cs;
+    const int nblk = (int)(2 * g.S - 1);
+    ScSpan span[6] = {{work, p.bytes}};
+    void* const* o = out.begin();
+    for (int i = 0; i < (int)out.size(); ++i) span[1 + i] = {o[i], (i < nblk ? m2 * m2 : m2) * cs};
+    rc = sc_alias(span, span + 1 + out.size(), {{bra, v_bytes}, {ket, v_bytes}, {ta, na * m2 * 4}, {tb, nb * m2 * 4}});
+    if (rc) return rc;
+
+    rc = sc2_passes(c_dtype, g, p, ta, tb, na, nb, bra, ket, work, s);
+    if (rc) return rc;
+    // block 0 reads the first product, X | <E_qs> in its last row; S = 2 adds X^ab beside it (no delta term, no rho) and X^bb from
+    // the second product with <E^b_qs> from the last row of the first
+    const double* part = (const double*)work;
+    Sc2Close tab{};
+    tab.b[0] = {part, (m2 + 1) * g.bcols, g.bcols, 0, m2 * g.bcols, (double*)o[0], (double*)o[nblk]};
+    if (g.S == 2) {
+        tab.b[1] = {part, (m2 + 1) * g.bcols, g.bcols, g.h, -1, (double*)o[1], nullptr};
+        tab.b[2] = {(const double*)((const char*)work + p.off_2), m2 * g.h, g.h, 0, m2 * g.bcols + g.h, (double*)o[2], (double*)o[4]};
+    }
+    with_width(cw, [&](auto CW) {
+        hipLaunchKernelGGL((string_ci_gamma_close_kernel<CW>), dim3(sc_stride_grid(nblk * m2 * m2)), dim3(kScRhoBlock), 0, s, tab, nblk,
+                           p.T, (int)m);
+    });
+    note_dispatch("qs::string_ci_gamma_close_kernel<%d>", cw);
+    return launch_status(spin ? "string CI spin-resolved density close launch" : "string CI two-body density close launch");
 }
 
 }  // namespace qs
@@ -1244,9 +1207,7 @@ int qs_string_ci_density1(int c_dtype, const int32_t* ta, const int32_t* tb, int
 }
 
 int64_t qs_string_ci_density2_workspace(int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes) {
-    const int rc = sc2_check(c_dtype, m, na, nb, budget_bytes);
-    if (rc) return rc;
-    return sc2_plan(false, c_dtype == QS_C128 ? 2 : 1, m, na, nb, budget_bytes).bytes;
+    return sc2_workspace(false, c_dtype, m, na, nb, budget_bytes);
 }
 
 int qs_string_ci_density2_plan(int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes, int64_t* plan) {
@@ -1256,35 +1217,11 @@ int qs_string_ci_density2_plan(int c_dtype, int64_t m, int64_t na, int64_t nb, i
 int qs_string_ci_density2(int c_dtype, const int32_t* ta, const int32_t* tb, int64_t m, int64_t na, int64_t nb,
                           const void* bra, const void* ket, void* gamma, void* rho, void* work, int64_t work_bytes,
                           int64_t budget_bytes, void* stream) {
-    dispatch_reset();
-    int rc = sc2_check(c_dtype, m, na, nb, budget_bytes);
-    if (rc) return rc;
-    if (!ta || !tb || !bra || !ket || !gamma || !rho || !work) return QS_ERR_NULL_POINTER;
-    const int64_t cs = (int64_t)elem_size(c_dtype);
-    if (!aligned(ta, 4) || !aligned(tb, 4) || !aligned(bra, (size_t)cs) || !aligned(ket, (size_t)cs) || !aligned(gamma, (size_t)cs) ||
-        !aligned(rho, (size_t)cs) || !aligned(work, 16))
-        return QS_ERR_MISALIGNED;
-    const int cw = c_dtype == QS_C128 ? 2 : 1;
-    const Sc2Plan p = sc2_plan(false, cw, m, na, nb, budget_bytes);
-    if (work_bytes < p.bytes) return QS_ERR_WORKSPACE;
-    const int64_t m2 = m * m, v_bytes = na * nb * cs;
-    rc = sc_alias({{work, p.bytes}, {gamma, m2 * m2 * cs}, {rho, m2 * cs}}, {{bra, v_bytes}, {ket, v_bytes}, {ta, na * m2 * 4}, {tb, nb * m2 * 4}});
-    if (rc) return rc;
-
-    hipStream_t s = (hipStream_t)stream;
-    rc = sc2_passes(c_dtype, false, p, ta, tb, m, na, nb, bra, ket, work, s);
-    if (rc) return rc;
-    with_width(cw, [&](auto CW) {
-        hipLaunchKernelGGL((string_ci_gamma_close_kernel<CW>), dim3(sc_stride_grid(m2 * m2)), dim3(kScRhoBlock), 0, s, (const double*)work, p.T, (int)m, (double*)gamma, (double*)rho);
-    });
-    note_dispatch("qs::string_ci_gamma_close_kernel<%d>", cw);
-    return launch_status("string CI two-body density close launch");
+    return sc2_density(false, c_dtype, ta, tb, m, na, nb, bra, ket, {gamma, rho}, work, work_bytes, budget_bytes, (hipStream_t)stream);
 }
 
 int64_t qs_string_ci_density2_spin_workspace(int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes) {
-    const int rc = sc2_check(c_dtype, m, na, nb, budget_bytes);
-    if (rc) return rc;
-    return sc2_plan(true, c_dtype == QS_C128 ? 2 : 1, m, na, nb, budget_bytes).bytes;
+    return sc2_workspace(true, c_dtype, m, na, nb, budget_bytes);
 }
 
 int qs_string_ci_density2_spin_plan(int c_dtype, int64_t m, int64_t na, int64_t nb, int64_t budget_bytes, int64_t* plan) {
@@ -1294,33 +1231,8 @@ int qs_string_ci_density2_spin_plan(int c_dtype, int64_t m, int64_t na, int64_t 
 int qs_string_ci_density2_spin(int c_dtype, const int32_t* ta, const int32_t* tb, int64_t m, int64_t na, int64_t nb,
                                const void* bra, const void* ket, void* gamma_aa, void* gamma_ab, void* gamma_bb, void* rho_a,
                                void* rho_b, void* work, int64_t work_bytes, int64_t budget_bytes, void* stream) {
-    dispatch_reset();
-    int rc = sc2_check(c_dtype, m, na, nb, budget_bytes);
-    if (rc) return rc;
-    if (!ta || !tb || !bra || !ket || !gamma_aa || !gamma_ab || !gamma_bb || !rho_a || !rho_b || !work) return QS_ERR_NULL_POINTER;
-    const int64_t cs = (int64_t)elem_size(c_dtype);
-    if (!aligned(ta, 4) || !aligned(tb, 4) || !aligned(bra, (size_t)cs) || !aligned(ket, (size_t)cs) || !aligned(gamma_aa, (size_t)cs) ||
-        !aligned(gamma_ab, (size_t)cs) || !aligned(gamma_bb, (size_t)cs) || !aligned(rho_a, (size_t)cs) || !aligned(rho_b, (size_t)cs) ||
-        !aligned(work, 16))
-        return QS_ERR_MISALIGNED;
-    const int cw = c_dtype == QS_C128 ? 2 : 1;
-    const Sc2Plan p = sc2_plan(true, cw, m, na, nb, budget_bytes);
-    if (work_bytes < p.bytes) return QS_ERR_WORKSPACE;
-    const int64_t m2 = m * m, g_bytes = m2 * m2 * cs, r_bytes = m2 * cs, v_bytes = na * nb * cs;
-    rc = sc_alias({{work, p.bytes}, {gamma_aa, g_bytes}, {gamma_ab, g_bytes}, {gamma_bb, g_bytes}, {rho_a, r_bytes}, {rho_b, r_bytes}},
-                  {{bra, v_bytes}, {ket, v_bytes}, {ta, na * m2 * 4}, {tb, nb * m2 * 4}});
-    if (rc) return rc;
-
-    hipStream_t s = (hipStream_t)stream;
-    rc = sc2_passes(c_dtype, true, p, ta, tb, m, na, nb, bra, ket, work, s);
-    if (rc) return rc;
-    with_width(cw, [&](auto CW) {
-        hipLaunchKernelGGL((string_ci_gamma_spin_close_kernel<CW>), dim3(sc_stride_grid(3 * m2 * m2)), dim3(kScRhoBlock), 0, s,
-                           (const double*)work, (const double*)((char*)work + p.off_2), p.T, (int)m, (int)p.h, (double*)gamma_aa,
-                           (double*)gamma_ab, (double*)gamma_bb, (double*)rho_a, (double*)rho_b);
-    });
-    note_dispatch("qs::string_ci_gamma_spin_close_kernel<%d>", cw);
-    return launch_status("string CI spin-resolved density close launch");
+    return sc2_density(true, c_dtype, ta, tb, m, na, nb, bra, ket, {gamma_aa, gamma_ab, gamma_bb, rho_a, rho_b}, work, work_bytes,
+                       budget_bytes, (hipStream_t)stream);
 }
 
 int qs_string_ci_spin_squared(int c_dtype, const int32_t* ta, const int32_t* tb, int64_t m, int64_t na, int64_t nb,

@@ -1247,6 +1247,29 @@ def string_ci_density1(ta, tb, m, bra, ket, out=None):
     return out
 
 
+def _string_ci_density2(entry, ngamma, nrho, outs, ta, tb, m, bra, ket, out):
+    """Either two-body density on ``qs_<entry>``: the operands, the workspace query, ``out`` -- a tuple of ``ngamma``
+    buffers (m, m, m, m) and ``nrho`` buffers (m, m), allocated here or checked; ``outs`` names it in the error -- and the
+    call.  Returns the tuple."""
+    lib = _lib.load()
+    m, ta, tb, bra, ket, na, nb, dt, code = _bra_ket(ta, tb, m, bra, ket)
+    nbytes = check(getattr(lib, f"qs_{entry}_workspace")(code, m, na, nb, STRING_CI_BYTES), "workspace query")
+    shapes = ((m, m, m, m),) * ngamma + ((m, m),) * nrho
+    if out is None:
+        out = tuple(torch.empty(shape, dtype=dt, device=bra.device) for shape in shapes)
+    else:
+        if not isinstance(out, (tuple, list)) or len(out) != len(shapes):
+            raise ValueError(f"{entry}: `out` must be {outs}")
+        out = tuple(_check_out(o, shape, dt, entry) for o, shape in zip(out, shapes))
+    with _on_device_of(ta, tb, bra, ket, *out):
+        _ran(
+            getattr(lib, f"qs_{entry}")(code, ta.data_ptr(), tb.data_ptr(), m, na, nb, bra.data_ptr(), ket.data_ptr(),
+                                        *(o.data_ptr() for o in out), *_work(nbytes, bra.device), STRING_CI_BYTES, _stream()),
+            f"qs_{entry}",
+        )
+    return out
+
+
 @_plain
 def string_ci_density2(ta, tb, m, bra, ket, out=None):
     """``(gamma, rho)`` of two vectors (na, nb) on ``qs_string_ci_density2``: the spin-summed two-body density
@@ -1256,25 +1279,7 @@ def string_ci_density2(ta, tb, m, bra, ket, out=None):
     dispatcher.  With the plain ``ut``, ``<bra|H|ket> = sum ht[p,q] rho[q,p] + 1/2 sum ut[p,q,r,s] gamma[p,q,r,s]``.
     ``out`` is a pair ``(gamma, rho)`` of buffers.  Repeating a call gives the same bits; another budget agrees to
     rounding."""
-    lib = _lib.load()
-    m, ta, tb, bra, ket, na, nb, dt, code = _bra_ket(ta, tb, m, bra, ket)
-    nbytes = check(lib.qs_string_ci_density2_workspace(code, m, na, nb, STRING_CI_BYTES), "workspace query")
-    if out is None:
-        gamma = torch.empty((m, m, m, m), dtype=dt, device=bra.device)
-        rho = torch.empty((m, m), dtype=dt, device=bra.device)
-    else:
-        if not isinstance(out, (tuple, list)) or len(out) != 2:
-            raise ValueError("string_ci_density2: `out` must be a pair (gamma, rho)")
-        gamma = _check_out(out[0], (m, m, m, m), dt, "string_ci_density2")
-        rho = _check_out(out[1], (m, m), dt, "string_ci_density2")
-    with _on_device_of(ta, tb, bra, ket, gamma, rho):
-        _ran(
-            lib.qs_string_ci_density2(code, ta.data_ptr(), tb.data_ptr(), m, na, nb, bra.data_ptr(), ket.data_ptr(),
-                                      gamma.data_ptr(), rho.data_ptr(), *_work(nbytes, bra.device), STRING_CI_BYTES,
-                                      _stream()),
-            "qs_string_ci_density2",
-        )
-    return gamma, rho
+    return _string_ci_density2("string_ci_density2", 1, 1, "a pair (gamma, rho)", ta, tb, m, bra, ket, out)
 
 
 def string_ci_density2_spin_plan(m, na, nb, c_dtype):
@@ -1296,24 +1301,8 @@ def string_ci_density2_spin(ta, tb, m, bra, ket, out=None):
     ``gamma``, the two ``rho`` to its ``rho``.  Passes and budget as there (``STRING_CI_BYTES``, tuning key
     ``string_ci_bytes``); every pass is two batched products on the product dispatcher.  ``out`` is a 5-tuple of
     buffers.  Repeating a call gives the same bits; another budget agrees to rounding."""
-    lib = _lib.load()
-    m, ta, tb, bra, ket, na, nb, dt, code = _bra_ket(ta, tb, m, bra, ket)
-    nbytes = check(lib.qs_string_ci_density2_spin_workspace(code, m, na, nb, STRING_CI_BYTES), "workspace query")
-    shapes = ((m, m, m, m),) * 3 + ((m, m),) * 2
-    if out is None:
-        out = tuple(torch.empty(shape, dtype=dt, device=bra.device) for shape in shapes)
-    else:
-        if not isinstance(out, (tuple, list)) or len(out) != 5:
-            raise ValueError("string_ci_density2_spin: `out` must be a 5-tuple (gamma_aa, gamma_ab, gamma_bb, rho_a, rho_b)")
-        out = tuple(_check_out(o, shape, dt, "string_ci_density2_spin") for o, shape in zip(out, shapes))
-    with _on_device_of(ta, tb, bra, ket, *out):
-        _ran(
-            lib.qs_string_ci_density2_spin(code, ta.data_ptr(), tb.data_ptr(), m, na, nb, bra.data_ptr(), ket.data_ptr(),
-                                           *(o.data_ptr() for o in out), *_work(nbytes, bra.device), STRING_CI_BYTES,
-                                           _stream()),
-            "qs_string_ci_density2_spin",
-        )
-    return out
+    return _string_ci_density2("string_ci_density2_spin", 3, 2, "a 5-tuple (gamma_aa, gamma_ab, gamma_bb, rho_a, rho_b)", ta, tb, m,
+                               bra, ket, out)
 
 
 @_plain

@@ -208,7 +208,7 @@ def test_passes_under_three_byte_budgets(form):
         entry = [e for e in log if "string_ci" in e]
         assert len(entry) == 1 and len(log) == 1, log                             # one entry names the whole call
         w = 2 if cc else 1
-        for name in (f"string_ci_expand_rows_kernel<{w}, false>", f"string_ci_expand_rows_kernel<{w}, true>", "gemm",
+        for name in (f"string_ci_expand_panel_kernel<{w}, false, 1>", f"string_ci_expand_panel_kernel<{w}, true, 1>", "gemm",
                      f"string_ci_gamma_close_kernel<{w}>"):
             assert name in entry[0], (name, entry[0])
         assert "det_ci" not in entry[0] and "string_ci_expand_kernel" not in entry[0]

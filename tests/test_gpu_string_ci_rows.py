@@ -350,7 +350,7 @@ def test_solver_and_one_body_density_under_a_fifth_of_one_vector(form):
             assert call.count("string_ci_expand_kernel") == call.count("string_ci_fold_kernel") == 5 and "ScTri" not in call
             assert call.index("expand") < call.index("gemm") < call.index("fold")
     density = log[steps]
-    assert "string_ci_expand_rows_kernel" in density and "string_ci_expand_kernel<" not in density and plan[1] > 1
+    assert f"string_ci_expand_panel_kernel<{code + 1}, false, 1>" in density and "string_ci_expand_kernel<" not in density and plan[1] > 1
 
     want = H(ci.one_body_density(0))                                              # the shipped budget: qs_string_ci_density1
     state = H(ci._c[0])

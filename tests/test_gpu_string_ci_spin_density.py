@@ -246,8 +246,8 @@ def test_passes_under_three_byte_budgets(form):
         print(f"{form} {kind}: {passes} passes of {rows} rows, T = {T}, kc = {kc}, last pass {(na - (passes - 1) * rows) * nb} of {T * kc}")
         assert len(log) == 1 and "string_ci" in log[0], log                       # one entry names the whole call
         w = 2 if cc else 1
-        for name in (f"string_ci_expand_spin_kernel<{w}, false>", f"string_ci_expand_spin_kernel<{w}, true>", "gemm",
-                     f"string_ci_gamma_spin_close_kernel<{w}>"):
+        for name in (f"string_ci_expand_panel_kernel<{w}, false, 2>", f"string_ci_expand_panel_kernel<{w}, true, 2>", "gemm",
+                     f"string_ci_gamma_close_kernel<{w}>"):
             assert name in log[0], (name, log[0])
         assert "det_ci" not in log[0] and "string_ci_expand_kernel" not in log[0]
         got[kind] = G
@@ -263,6 +263,67 @@ def test_passes_under_three_byte_budgets(form):
             assert ratio_of(np.abs(got[kind][st] - got["one"][st]), 2 * B[st], f"{form} {kind} against one pass, Gamma^{st}") <= 1.0
     for st in spref.BLOCKS:
         assert float(np.abs(got["one"][st]).max()) > 1e3 * float(B[st].max())
+
+
+@pytest.mark.parametrize("form", list(FORMS))
+def test_the_close_past_its_grid_cap_on_one_particle_per_spin(form):
+    """m = 49, one particle per spin, the 49 strings ``1 << i`` on either side: 3 m^4 = 17 294 403 elements of the three Gamma
+    against the close's cap of 65 536 workgroups of 256 threads = 16 777 216, so its grid-stride loop takes a second trip (the
+    last 517 187 elements of Gamma^bb, and the rho^b they write).  One pass of 2401 determinants.  The outputs are handed in
+    full of NaN: an element the close does not write fails.
+
+    String i is orbital i and every sign is +, so (E^a_pq c)[Ia, Ib] = delta(Ia, p) c[q, Ib] and (E^b_pq c)[Ia, Ib] =
+    delta(Ib, p) c[Ia, q], and the densities have closed forms (host: longdouble):
+      * Gamma^ab[p,q,r,s] = conj(bra[p,q]) ket[r,s]: ONE non-zero term in the dot product over the determinants, every other
+        term and every partial sum an exact zero.  fp64: one rounding, that of the product.  complex128: the two products and
+        one addition of a real or imaginary part are at most two roundings, sqrt 2 gamma_2 for the modulus.  The bound is
+        gamma_2 |bra[p,q]| |ket[r,s]|, times the suite's 2 sqrt 2 for complex128.
+      * rho^a[q,p] = sum_b conj(bra[p,b]) ket[q,b], rho^b[q,p] = sum_a conj(bra[a,p]) ket[a,q]: nb (na) non-zero terms, spread
+        over at most T partial sums that are then added: at most nb + T - 1 additions and one product rounding each,
+        gamma_(nb+T+1) sum |bra| |ket| for any order (the exact zeros among the terms add nothing).
+      * Gamma^aa[p,q,r,s] = delta_qr (X - <E^a_ps>) with X = <E^a_ps> = sum_b conj(bra[p,b]) ket[s,b] in exact arithmetic:
+        zero, and on the device the difference of two such sums, each within gamma_(nb+T+1) sum_b |bra[p,b]| |ket[s,b]| of
+        the same number (the final subtraction rounds a difference that small by less than the slack between gamma_(nb+T)
+        and gamma_(nb+T+1)): twice that.  For q != r every term is an exact zero: exact zeros.  Gamma^bb likewise over a."""
+    from quantum_systems_amd import kernels
+
+    cc = FORMS[form]
+    m = 49
+    cap = 65536 * 256
+    assert 2 * m ** 4 < cap < 3 * m ** 4                                          # the second trip exists, in Gamma^bb
+    s = np.array([1 << i for i in range(m)], dtype=np.int64)
+    ta = kernels.string_ci_table(dev(s), m, 1)
+    assert np.array_equal(H(ta).reshape(m, m, m), np.eye(m, dtype=np.int32)[:, :, None] * (np.arange(m, dtype=np.int32) + 1))
+    rows, passes, T, kc, _ = plan(m, m, m, cc)
+    assert passes == 1 and rows == m
+    bra, ket = unit_pair(m, m, cc, 49)
+    dt = torch.complex128 if cc else torch.float64
+    out = tuple(torch.full(shape, float("nan"), dtype=dt, device="cuda") for shape in ((m,) * 4,) * 3 + ((m, m),) * 2)
+    got = kernels.string_ci_density2_spin(ta, ta, m, dev(bra), dev(ket), out=out)
+    assert all(g is o for g, o in zip(got, out))
+    G = dict(zip(spref.BLOCKS, (H(x) for x in out[:3])))
+    rho = (H(out[3]), H(out[4]))
+    # every element is compared below; those of the loop's second trip lie past cap - 2 m^4 in Gamma^bb
+    assert all(x.size == m ** 4 and np.isfinite(x.reshape(-1)[cap // 3:]).all() for x in G.values())
+    cx = S2 if cc else 1.0
+    bw, kw, ab, ak = ref._wide(bra), ref._wide(ket), np.abs(bra), np.abs(ket)
+    tag = f"m = 49 {form}, T = {T}"
+    want = np.multiply.outer(bw.conj(), kw)
+    bound = ref.gamma(2) * cx * np.multiply.outer(ab, ak)
+    assert ratio_of(np.abs(G["ab"] - want), bound, f"{tag} Gamma^ab") <= 1.0
+    assert float(np.abs(G["ab"]).max()) > 1e3 * float(bound.max())                # the comparison sees the result
+    del want, bound
+    # e[p, q] = <bra| E^s_pq |ket> and sum |bra| |E^s_pq ket|, alpha over b and beta over a
+    e = {"a": bw.conj() @ kw.T, "b": bw.conj().T @ kw}
+    eb = {"a": ab @ ak.T, "b": ab.T @ ak}
+    scale = ref.gamma(m + T + 1) * cx
+    for spin, r in zip("ab", rho):
+        assert ratio_of(np.abs(r - e[spin].T), scale * eb[spin].T, f"{tag} rho^{spin}") <= 1.0
+        assert float(np.abs(r).max()) > 1e3 * float(scale * eb[spin].max())
+        g = G[spin + spin].transpose(1, 2, 0, 3)                                  # [q, r, p, s]
+        assert not g[~np.eye(m, dtype=bool)].any()                                # q != r: exact zeros
+        diag = g[np.arange(m), np.arange(m)]                                      # [q, p, s], X - <E^s_ps>
+        assert ratio_of(np.abs(diag), np.broadcast_to(2 * scale * eb[spin], diag.shape), f"{tag} Gamma^{spin}{spin}") <= 1.0
 
 
 @pytest.mark.parametrize("form", list(FORMS))
