@@ -79,6 +79,29 @@ int qs_matmul(int dtype, const void* A, const void* B, void* out,
               int64_t stride_c, int accumulate, void* stream);
 
 /*
+ * qs_matmul over a TRIANGULAR batch: the entries are the grid_n (grid_n + 1) / 2
+ * pairs (i, j >= i) of a grid_n x grid_n grid, in row-major order, and the
+ * operands of pair (i, j) sit at its flat index f = i * grid_n + j:
+ *   A + f * stride_a,  B + f * stride_b,  out + f * stride_c   (0 = shared).
+ * Nothing is written at the flat indices of the pairs j < i, and nothing read
+ * there reaches an output (a border tile of the edge forms loads past its own
+ * entry, inside the operand, into rows that are never stored).  One launch on
+ * exactly the pairs (the d and c contractions of the exchange route below).
+ */
+int qs_matmul_pairs(int dtype, const void* A, const void* B, void* out,
+                    int64_t m, int64_t n, int64_t k,
+                    int64_t lda, int64_t ldb, int64_t ldc,
+                    int64_t grid_n, int64_t stride_a, int64_t stride_b,
+                    int64_t stride_c, int accumulate, void* stream);
+
+/*
+ * Host only: pair number t (0 <= t < n (n + 1) / 2) of that order -> (*i, *j),
+ * by the same remap the kernels use.  QS_ERR_BAD_EXTENT for n <= 0 or t out
+ * of range.
+ */
+int qs_triangle_pair(int64_t n, int64_t t, int64_t* i, int64_t* j);
+
+/*
  * Bytes of workspace qs_transform_two_body needs for u:(L,L,L,L) -> (M,M,M,M).
  * Returns a negative QS_ERR_* on bad extents.
  */
@@ -518,7 +541,10 @@ const char* qs_last_dispatch(void);
  *     "exchange" (qs_transform_two_body_exchange_wanted: 0 = never, 1 = where
  *     the exchange route measured faster, 2 = wherever it exists, any size),
  *     "exchange_block" / "exchange_block_d" (rows per block of that route's
- *     closing product and mirror / of its d contraction, 0 = automatic).
+ *     closing product and mirror / of its d contraction, 0 = automatic),
+ *     "exchange_pairs" (1 = that route's c contraction, and its d contraction
+ *     where that pads no more, as one qs_matmul_pairs launch; 0 = one launch
+ *     per row / per block of rows, the same bits).
  *   qs_probe_mfma_f64: register-resident fp64 MFMA loop, `blocks` workgroups
  *     of 4 waves, each wave issuing iters*8 v_mfma_f64_16x16x4_f64
  *     (flops = blocks*4*iters*8*2048); `sink` is a device scratch of

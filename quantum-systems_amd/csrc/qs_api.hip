@@ -17,6 +17,7 @@
 #include <mutex>
 
 #include "qs_common.h"
+#include "qs_triangle.h"
 
 namespace qs {
 
@@ -249,6 +250,11 @@ int qs_tuning_set(const char* key, int64_t value) {
         (key[14] ? g_tune.exchange_block_d : g_tune.exchange_block) = (int)value;
         return QS_OK;
     }
+    if (!strcmp(key, "exchange_pairs")) {
+        if (value < 0 || value > 1) return QS_ERR_BAD_EXTENT;
+        g_tune.exchange_pairs = (int)value;
+        return QS_OK;
+    }
     if (!strcmp(key, "mean_field_batch_g")) {
         if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8) return QS_ERR_BAD_EXTENT;
         g_tune.mean_field_batch_g = (int)value;
@@ -289,6 +295,30 @@ int qs_matmul(int dtype, const void* A, const void* B, void* out, int64_t m, int
     return gemm(Product{dtype, (const double*)A, (const double*)B, (double*)out, m, n, k, lda, ldb, ldc, batch,
                         stride_a, stride_b, stride_c, accumulate},
                 (hipStream_t)stream);
+}
+
+int qs_matmul_pairs(int dtype, const void* A, const void* B, void* out, int64_t m, int64_t n, int64_t k,
+                    int64_t lda, int64_t ldb, int64_t ldc, int64_t grid_n, int64_t stride_a,
+                    int64_t stride_b, int64_t stride_c, int accumulate, void* stream) {
+    dispatch_reset();
+    if (!dtype_ok(dtype)) return QS_ERR_BAD_DTYPE;
+    if (!A || !B || !out) return QS_ERR_NULL_POINTER;
+    const size_t es = elem_size(dtype);
+    if (!aligned(A, es) || !aligned(B, es) || !aligned(out, es)) return QS_ERR_MISALIGNED;
+    if (stride_a < 0 || stride_b < 0 || stride_c < 0) return QS_ERR_BAD_EXTENT;
+    if (grid_n <= 0 || grid_n > kTriangleMax) return QS_ERR_BAD_EXTENT;
+    return gemm(Product{dtype, (const double*)A, (const double*)B, (double*)out, m, n, k, lda, ldb, ldc,
+                        grid_n * (grid_n + 1) / 2, stride_a, stride_b, stride_c, accumulate, grid_n},
+                (hipStream_t)stream);
+}
+
+int qs_triangle_pair(int64_t n, int64_t t, int64_t* i, int64_t* j) {
+    if (!i || !j) return QS_ERR_NULL_POINTER;
+    if (n <= 0 || n > kTriangleMax || t < 0 || t >= n * (n + 1) / 2) return QS_ERR_BAD_EXTENT;
+    const int64_t f = triangle_flat((uint32_t)t, (uint32_t)n);
+    *i = f / n;
+    *j = f % n;
+    return QS_OK;
 }
 
 int64_t qs_transform_two_body_workspace(int dtype, int64_t L, int64_t M) {
@@ -421,19 +451,21 @@ static int transform_two_body_fused(int in_dtype, int dtype, const void* u, cons
 // out[p,q,r,s] == out[q,p,s,r]: the d and c contractions run on the pairs b >= a only, the closing product on q >= the
 // block of p, and a mirror (qs_permute.hip) writes the other half.  The a contraction comes BEFORE the b contraction here
 // (the closing product then has M - p0 rows, mostly on the 128-row form):
-//   d:  T1[a][(b >= a0, c), s] = u[a][(b >= a0, c), d] C[d, s]       per block [a0, a1) of rows a, batched over a
-//   c:  T2[a, b][r, s]         = CT[r, c] T1[a, b][c, s]             per a, batched over b >= a;  then the mirror, a > b
+//   d:  T1[a, b][c, s]         = u[a, b][c, d] C[d, s]               one product over the pairs b >= a (or, where that pads
+//                                                                    more, per block [a0, a1) of rows a on b >= a0)
+//   c:  T2[a, b][r, s]         = CT[r, c] T1[a, b][c, s]             one product over the pairs b >= a;  then the mirror, a > b
 //   a:  X[p, (b r s)]          = Ct[p, a] T2[a, (b r s)]             one product
 //   b:  out[p][q >= p0, (r s)] = Ct[q >= p0, b] X[p][b, (r s)]       per block [p0, p1) of rows p, batched over p; then the mirror
 // T1 (L, L, L, M), T2 (L, L, M, M), X (M, L, M, M); T1 and X may share storage, so may T2 and out.
 
-// smallest basis (both sizes) that takes the route by itself: where it measured >= 5 % faster (profiles/exchange_route_sweep.txt)
-static constexpr int64_t kExchangeMin = 192;
+// smallest basis (both sizes) that takes the route by itself: the smallest measured size where it is >= 5 % faster than the plain
+// route (profiles/exchange_pairs_ab.txt, plain / route: fp64 160 1.036, 192 1.179; complex128 160 1.258)
+static constexpr int64_t kExchangeMin = 192, kExchangeMinC128 = 160;
 
 static bool exchange_wanted(int dtype, int64_t L, int64_t M) {
     if (!dtype_ok(dtype) || !extents_ok(L, M) || !g_tune.exchange || !exchange_grids_fit(L, M)) return false;
     if (g_tune.exchange == 2) return true;
-    return (L < M ? L : M) >= kExchangeMin;
+    return (L < M ? L : M) >= (dtype == QS_C128 ? kExchangeMinC128 : kExchangeMin);
 }
 
 static int transform_two_body_exchange_route(int dtype, const void* u, const void* C, const void* Ct, void* CT, void* T1,
@@ -448,15 +480,44 @@ static int transform_two_body_exchange_route(int dtype, const void* u, const voi
     auto mat = [&](void* base, int64_t elems) { return (double*)at(base, elems, es); };
     int rc = transpose_small(dtype, C, CT, L, M, s);
     if (rc) return rc;
-    for (int64_t a0 = 0; a0 < L; a0 += blk_d) {
+    // d and c are one product per pair (a, b >= a) on operands that are contiguous in the flat pair index a L + b: a
+    // triangular batch (Product::pairs) runs each as ONE launch on exactly the L (L + 1) / 2 pairs.  For c that is the
+    // per-row launches' tile list in one grid.  For d it pads the L rows of EVERY pair to whole tiles where the blocks'
+    // flat (L - a0) L rows pad once, so the dispatch's own estimates of the two forms decide (at L a multiple of 128
+    // neither pads: the single launch, 0.502 of a product where the blocks compute 0.53).
+    // g_tune.exchange_pairs == 0: the launches per block and per row.  Same bits: for c the same kernel on the same tiles;
+    // for d the tiles differ where L is no whole number of them (L rows per pair against (L - a0) L flat rows), possibly
+    // the instantiation too, and the bits agree because every tiled form sums along k in the same order.
+    const int64_t npairs = L * (L + 1) / 2;
+    auto d_block = [&](int64_t a0) {
         const int64_t rows = (a0 + blk_d < L ? a0 + blk_d : L) - a0;
-        rc = gemm(Product{dtype, cat(u, a0 * L * L * L + a0 * L * L), (const double*)C, mat(T1, a0 * L * L * M + a0 * L * M),
-                          (L - a0) * L, M, L, L, M, M, rows, L * L * L, 0, L * L * M, 0}, s);
-        if (rc) return rc;
+        return Product{dtype, cat(u, a0 * L * L * L + a0 * L * L), (const double*)C, mat(T1, a0 * L * L * M + a0 * L * M),
+                       (L - a0) * L, M, L, L, M, M, rows, L * L * L, 0, L * L * M, 0};
+    };
+    const Product d_pairs{dtype, (const double*)u, (const double*)C, (double*)T1, L, M, L, L, M, M, npairs, L * L, 0, L * M, 0, L};
+    bool d_single = g_tune.exchange_pairs != 0;
+    if (d_single) {
+        double blocks_cost = 0.0;
+        for (int64_t a0 = 0; a0 < L; a0 += blk_d) blocks_cost += gemm_cost(d_block(a0));
+        d_single = gemm_cost(d_pairs) <= blocks_cost;
     }
-    for (int64_t a = 0; a < L; ++a) {
-        rc = gemm(packed(dtype, CT, cat(T1, (a * L + a) * L * M), mat(T2, (a * L + a) * MM), M, M, L, L - a), s);
+    if (d_single) {
+        rc = gemm(d_pairs, s);
         if (rc) return rc;
+    } else {
+        for (int64_t a0 = 0; a0 < L; a0 += blk_d) {
+            rc = gemm(d_block(a0), s);
+            if (rc) return rc;
+        }
+    }
+    if (g_tune.exchange_pairs) {
+        rc = gemm(Product{dtype, (const double*)CT, (const double*)T1, (double*)T2, M, M, L, L, M, M, npairs, 0, L * M, MM, 0, L}, s);
+        if (rc) return rc;
+    } else {
+        for (int64_t a = 0; a < L; ++a) {
+            rc = gemm(packed(dtype, CT, cat(T1, (a * L + a) * L * M), mat(T2, (a * L + a) * MM), M, M, L, L - a), s);
+            if (rc) return rc;
+        }
     }
     rc = exchange_mirror(dtype, T2, L, M, 1, s);
     if (rc) return rc;

@@ -91,6 +91,10 @@ struct Product {
     double* C;
     int64_t m, n, k, lda, ldb, ldc, batch, sa, sb, sc;
     int accumulate;
+    // Triangular batch: pairs = n > 0 makes entry t < batch = n (n + 1) / 2 the t-th pair (i, j >= i) of an n x n grid in
+    // row-major order, with its operands at the pair's FLAT index f = i n + j (qs_triangle.h): A + f sa, B + f sb,
+    // C + f sc.  0 = a plain batch, entry t at t.
+    int64_t pairs = 0;
     // which operand is the stream that neighbouring tiles should share in L2: a shared (stride-0) A, or a short-and-wide
     // product, streams B (the tiled kernels walk the tiles of one B panel first)
     int group_along_m() const { return ((sa == 0 && batch > 1) || m < n) ? 1 : 0; }
@@ -103,6 +107,11 @@ inline Product packed(int dtype, const void* A, const void* B, void* C, int64_t 
 
 // Validates the extents and strides, then launches the product on the first route that takes it (qs_gemm.hip).
 int gemm(const Product& p, hipStream_t stream);
+
+// The dispatch's own estimate of a product's time on its tiled kernels (the smaller of the general kernel's best shape
+// and qs_gemm_fast.hip's best form, in the latter's units: rounds of the tile list x tile area / relative rate).  For a
+// caller that may cut the same work into launches in two ways; launches nothing.
+double gemm_cost(const Product& p);
 
 // A real (m x k, fp64) times B complex (k x n) -> out complex (m x n), packed row-major.  Interleaved complex storage makes
 // this EXACTLY the real product A . [B as k x 2n] -> [out as m x 2n]: the real kernels run it with 2 MFMAs per fragment
@@ -243,6 +252,9 @@ struct Tuning {
                                  // 0 never, 1 where it measured faster, 2 wherever it exists (any size, ahead of the fused small-basis routes)
     int exchange_block = 0;      // rows per block of that route's closing product (and of its mirror), 0 = automatic
     int exchange_block_d = 0;    // rows per block of that route's d contraction, 0 = automatic (never above exchange_block when that is set)
+    int exchange_pairs = 1;      // that route's c contraction (and d, where it pads no more) as ONE product over the pairs b >= a (Product::pairs):
+                                 // 0 = one launch per row a / per block of exchange_block_d rows (the A/B baseline.  Same bits: c runs the same
+                                 // kernel on the same tiles; d may tile differently, and every tiled form sums along k in the same order)
     int sandwich = 1;            // 4-wide fused passes of a small-basis transform: 0 off, 1 both (d, c) and (b, a), 2 (d, c) only, 3 (b, a) only;
                                  // tuning runs, wherever the kernel exists (not only where it measured faster): 4 both, 5 (d, c) only, 6 (b, a) only
 };

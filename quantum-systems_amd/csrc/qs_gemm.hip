@@ -39,6 +39,7 @@
 
 #include "qs_common.h"
 #include "qs_fast_items.h"
+#include "qs_triangle.h"
 
 namespace qs {
 
@@ -57,6 +58,7 @@ struct GemmArgs {
     int tiles_m, tiles_n;
     int group_along_m;   // 1: tiles that share a B panel (same n-tile) are adjacent
     int accumulate;      // 1: C += A.B (C is read in the epilogue), 0: C = A.B
+    unsigned pairs;      // n > 0: the batch is the upper triangle of an n x n grid, entry t at its flat index (Product::pairs)
 };
 
 // Work index of a workgroup: XCD x gets the x-th contiguous chunk of the work
@@ -110,7 +112,8 @@ void gemm_kernel(const GemmArgs g) {
         nt = w % g.tiles_n; w /= g.tiles_n;
         mt = w % g.tiles_m; w /= g.tiles_m;
     }
-    const int64_t b = w;
+    // (triangular batch: the remap runs on the scalar unit, on the wave-uniform entry index)
+    const int64_t b = g.pairs ? (unsigned)__builtin_amdgcn_readfirstlane((int)triangle_flat((unsigned)__builtin_amdgcn_readfirstlane((int)w), g.pairs)) : w;
     const int m0 = mt * BM, n0 = nt * BN;
     const double* __restrict__ A = g.A + b * g.sa * ES;
     const double* __restrict__ B = g.B + b * g.sb * ES;
@@ -446,11 +449,77 @@ static int dispatch_f64(int cfg, const GemmArgs& g, int64_t batch, hipStream_t s
 #endif
 }
 
+// the general kernel's automatic candidates
+static const TileShape f64_cand[] = {
+    {1, 128, 128, 1.00}, {12, 96, 128, 0.98}, {13, 128, 96, 0.98}, {8, 96, 96, 0.96},
+    {5, 64, 64, 0.95},   {9, 128, 64, 0.90},  {10, 64, 128, 0.90}, {11, 32, 32, 0.73},
+};
+static const TileShape c128_cand[] = {
+    {1, 64, 128, 1.00}, {2, 128, 64, 1.00}, {6, 64, 64, 1.00}, {9, 96, 96, 0.97},
+    {7, 96, 64, 0.95},  {8, 64, 96, 0.95},  {4, 32, 32, 0.94},
+};
+
+// fp64: 16-byte loads need even extents/strides and 16-byte aligned bases (complex elements are 16 bytes by themselves)
+static bool f64_vec(const Product& p) {
+    return p.dtype != QS_C128 && aligned(p.A, 16) && aligned(p.B, 16) && !(p.lda & 1) && !(p.ldb & 1) && !(p.k & 1) &&
+           !(p.n & 1) && !(p.sa & 1) && !(p.sb & 1);
+}
+
+// 16-byte layout of all three operands, as the VALU-free and the strip kernels ask it (`vec`: f64_vec above)
+static bool even_layout(const Product& p, bool vec) {
+    return p.dtype == QS_C128 || (vec && aligned(p.C, 16) && !(p.ldc & 1) && !(p.sc & 1));
+}
+
+// The general kernel's automatic choice for a product and its estimated time (this kernel's units): *cfg the best candidate
+// shape, *fit_cfg a fitted shape that beats it (0 = none).  The ONE cost chain of gemm() and gemm_cost().
+static double general_estimate(const Product& p, bool vec, int* cfg, int* fit_cfg) {
+    const bool cx = p.dtype == QS_C128;
+    const int64_t m = p.m, n = p.n, batch = p.batch;
+    double cost = 0.0;
+    *cfg = cx ? pick_shape(c128_cand, sizeof(c128_cand) / sizeof(c128_cand[0]), m, n, batch, &cost)
+              : pick_shape(f64_cand, sizeof(f64_cand) / sizeof(f64_cand[0]), m, n, batch, &cost);
+    // Fitted shapes, fp64 only (see dispatch_f64): a basis size between 65 and 256 as m or as n.  Measured (same-box sweep
+    // with the shapes forced, profiles/r03_mid_size_shapes.txt): on their plain schedule they reach ~0.7 of the VALU-free
+    // kernel's rate -- they pay where everything is on 8-byte staging anyway (odd basis sizes) and the tile they save is
+    // large: l = 65 +14 %, 97 +12 %, 105 +11 %, 129 +4 %; with 16-byte staging available the other kernels win.
+    *fit_cfg = 0;
+    if (!cx && !vec) cost /= kScalarStagingRate;
+    if (!cx && (g_tune.gemm_fit == 2 || (g_tune.gemm_fit == 1 && !vec))) {
+        const int tm = (int)cdiv(m, 16), tn = (int)cdiv(n, 16);
+        TileShape fit[2];
+        int nfit = 0;
+        // (from 13 tiles up the stages of a tile take more than half of a CU's LDS: one workgroup per CU)
+        auto weight = [](int t) { return t <= 9 ? 1.10 * kFitWeight : t <= 12 ? kFitWeight : 0.75 * kFitWeight; };
+        if (m <= 256 && tm >= 5) fit[nfit++] = TileShape{100 + tm, 16 * tm, 64, weight(tm)};
+        if (n <= 256 && tn >= 5) fit[nfit++] = TileShape{200 + tn, 64, 16 * tn, weight(tn)};
+        if (nfit) {
+            double fcost = 0.0;
+            const int fc = pick_shape(fit, nfit, m, n, batch, &fcost);
+            if (g_tune.gemm_fit == 2 || fcost < cost) { *fit_cfg = fc; cost = fcost; }
+        }
+    }
+    return cost;
+}
+
+// the general kernel's estimate in the units of qs_gemm_fast.hip (complex128 as it stands)
+static double in_fast_units(const Product& p, double cost) { return p.dtype == QS_C128 ? cost : cost / kGeneralRelativeRate; }
+
+// (the strip kernels keep their estimate to themselves: a launch that they would take is costed as the better of the
+// other two here)
+double gemm_cost(const Product& p) {
+    const bool vec = f64_vec(p);
+    int cfg = 0, fit_cfg = 0;
+    const double cost = general_estimate(p, vec, &cfg, &fit_cfg);
+    return std::min(in_fast_units(p, cost), gemm_fast_estimate(p, even_layout(p, vec)));
+}
+
 int gemm(const Product& p, hipStream_t stream) {
     if (!dtype_ok(p.dtype)) return QS_ERR_BAD_DTYPE;
     if (p.m <= 0 || p.n <= 0 || p.k <= 0 || p.batch <= 0) return QS_ERR_BAD_EXTENT;
     if (p.m > INT32_MAX || p.n > INT32_MAX || p.k > INT32_MAX) return QS_ERR_BAD_EXTENT;
     if (p.lda < p.k || p.ldb < p.n || p.ldc < p.n) return QS_ERR_BAD_EXTENT;
+    // a triangular batch names every pair of its grid exactly once
+    if (p.pairs < 0 || p.pairs > kTriangleMax || (p.pairs && p.batch != p.pairs * (p.pairs + 1) / 2)) return QS_ERR_BAD_EXTENT;
     const bool cx = p.dtype == QS_C128;
     const int64_t m = p.m, n = p.n, batch = p.batch;
     GemmArgs g;
@@ -461,53 +530,21 @@ int gemm(const Product& p, hipStream_t stream) {
     g.tiles_m = g.tiles_n = 0;
     g.group_along_m = p.group_along_m();
     g.accumulate = p.accumulate ? 1 : 0;
-    // fp64: 16-byte loads need even extents/strides and 16-byte aligned bases (complex elements are 16 bytes by themselves)
-    const bool vec = !cx && aligned(p.A, 16) && aligned(p.B, 16) && !(p.lda & 1) && !(p.ldb & 1) && !(p.k & 1) &&
-                     !(n & 1) && !(p.sa & 1) && !(p.sb & 1);
+    g.pairs = (unsigned)p.pairs;
+    const bool vec = f64_vec(p);
     int cfg = cx ? g_tune.gemm_c128_cfg : g_tune.gemm_f64_cfg;      // a forced shape skips every other route
     if (cfg == 0) {
         int rc = gemm_skinny_try(p, stream);
         if (rc != 1) return rc;
         rc = gemm_stream_try(p, stream);
         if (rc != 1) return rc;
-        static const TileShape f64_cand[] = {
-            {1, 128, 128, 1.00}, {12, 96, 128, 0.98}, {13, 128, 96, 0.98}, {8, 96, 96, 0.96},
-            {5, 64, 64, 0.95},   {9, 128, 64, 0.90},  {10, 64, 128, 0.90}, {11, 32, 32, 0.73},
-        };
-        static const TileShape c128_cand[] = {
-            {1, 64, 128, 1.00}, {2, 128, 64, 1.00}, {6, 64, 64, 1.00}, {9, 96, 96, 0.97},
-            {7, 96, 64, 0.95},  {8, 64, 96, 0.95},  {4, 32, 32, 0.94},
-        };
-        double cost = 0.0;
-        cfg = cx ? pick_shape(c128_cand, sizeof(c128_cand) / sizeof(c128_cand[0]), m, n, batch, &cost)
-                 : pick_shape(f64_cand, sizeof(f64_cand) / sizeof(f64_cand[0]), m, n, batch, &cost);
-        // Fitted shapes, fp64 only (see dispatch_f64): a basis size between 65 and 256 as m or as n.  Measured (same-box sweep
-        // with the shapes forced, profiles/r03_mid_size_shapes.txt): on their plain schedule they reach ~0.7 of the VALU-free
-        // kernel's rate -- they pay where everything is on 8-byte staging anyway (odd basis sizes) and the tile they save is
-        // large: l = 65 +14 %, 97 +12 %, 105 +11 %, 129 +4 %; with 16-byte staging available the other kernels win.
         int fit_cfg = 0;
-        if (!cx && !vec) cost /= kScalarStagingRate;
-        if (!cx && (g_tune.gemm_fit == 2 || (g_tune.gemm_fit == 1 && !vec))) {
-            const int tm = (int)cdiv(m, 16), tn = (int)cdiv(n, 16);
-            TileShape fit[2];
-            int nfit = 0;
-            // (from 13 tiles up the stages of a tile take more than half of a CU's LDS: one workgroup per CU)
-            auto weight = [](int t) { return t <= 9 ? 1.10 * kFitWeight : t <= 12 ? kFitWeight : 0.75 * kFitWeight; };
-            if (m <= 256 && tm >= 5) fit[nfit++] = TileShape{100 + tm, 16 * tm, 64, weight(tm)};
-            if (n <= 256 && tn >= 5) fit[nfit++] = TileShape{200 + tn, 64, 16 * tn, weight(tn)};
-            if (nfit) {
-                double fcost = 0.0;
-                const int fc = pick_shape(fit, nfit, m, n, batch, &fcost);
-                if (g_tune.gemm_fit == 2 || fcost < cost) { fit_cfg = fc; cost = fcost; }
-            }
-        }
+        const double cost = general_estimate(p, vec, &cfg, &fit_cfg);
         if (g_tune.gemm_strip == 2 || g_tune.gemm_fast == 1) {
             // strip kernels (qs_gemm_strip.hip): the small extent of the product covered by one tile to the next multiple of 16
             // (not when a tuning key forces one of the other tiled kernels).  fp64 compares with the general kernel's cost in
             // the fast kernel's units; complex128 takes its cost as it stands and a 16-byte layout for granted.
-            const bool even = cx || (vec && aligned(p.C, 16) && !(p.ldc & 1) && !(p.sc & 1));
-            const double other = cx ? cost : cost / kGeneralRelativeRate;
-            rc = gemm_strip_try(p, std::min(gemm_fast_estimate(p, even), other), stream);
+            rc = gemm_strip_try(p, std::min(gemm_fast_estimate(p, even_layout(p, vec)), in_fast_units(p, cost)), stream);
             if (rc != 1) return rc;
         }
         rc = gemm_fast_try(p, cx || (g_tune.gemm_fit == 2 && fit_cfg) ? 0.0 : cost / kGeneralRelativeRate, stream);

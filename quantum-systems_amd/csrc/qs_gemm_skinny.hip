@@ -178,6 +178,7 @@ static int launch_skinny(const Product& p, hipStream_t stream) {
 // QS_OK / error after launching, 1 = not eligible (caller falls back).
 int gemm_skinny_try(const Product& p, hipStream_t stream) {
     if (!g_tune.gemm_skinny || p.batch != 1 || p.accumulate) return 1;
+    if (p.pairs) return 1;                               // (a triangular batch: the tiled kernels remap it)
     const bool cx = p.dtype == QS_C128;
     const int64_t m = p.m, n = p.n, k = p.k;
     // m = 64 is MFMA-bound (16 flop/B) and runs better on the tiled kernel (9.8 vs 15.3 ms at

@@ -373,6 +373,7 @@ static int launch_stream_cx(const StreamArgs& g0, int64_t batch, hipStream_t str
 // QS_OK / error after launching, 1 = not eligible (caller falls back).
 int gemm_stream_try(const Product& p, hipStream_t stream) {
     if (!g_tune.gemm_stream || p.accumulate) return 1;
+    if (p.pairs) return 1;                               // (a triangular batch: the tiled kernels remap it)
     const bool cx = p.dtype == QS_C128;
     const int64_t esz = cx ? 16 : 8;
     const int64_t m = p.m, n = p.n, k = p.k, ldb = p.ldb, ldc = p.ldc, batch = p.batch;

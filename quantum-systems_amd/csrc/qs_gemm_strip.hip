@@ -581,6 +581,7 @@ int launch_strip_t(bool cx, int t, bool wide, const StripArgs& g, hipStream_t st
 // area / relative rate over two workgroups per CU).
 int gemm_strip_try(const Product& p, double other_cost, hipStream_t stream) {
     if (!g_tune.gemm_strip || p.accumulate) return 1;
+    if (p.pairs) return 1;                               // (a triangular batch: the tiled kernels remap it)
     if (p.k >= (int64_t(1) << 30)) return 1;
     const bool cx = p.dtype == QS_C128;
     const int64_t esz = cx ? 16 : 8;

@@ -13,6 +13,7 @@
 // real tensor into complex128: 8*l^4 read + 16*(2l)^4 written = 264*l^4.
 
 #include "qs_common.h"
+#include "qs_triangle.h"
 
 namespace qs {
 
@@ -251,16 +252,7 @@ __global__ void transpose_kernel(const T* __restrict__ in, T* __restrict__ out, 
 __device__ __forceinline__ bool same_bits(double x, double y) { return __double_as_longlong(x) == __double_as_longlong(y); }
 __device__ __forceinline__ bool same_bits(f64x2 x, f64x2 y) { return same_bits(x[0], y[0]) && same_bits(x[1], y[1]); }
 
-// Row a of the upper triangle of an n x n grid (rows of n, n - 1, ... entries) that holds linear index idx.
-__device__ __forceinline__ int64_t triangle_row(int64_t idx, int64_t n) {
-    const double w = 2.0 * (double)n + 1.0;
-    int64_t a = (int64_t)((w - sqrt(w * w - 8.0 * (double)idx)) * 0.5);
-    if (a < 0) a = 0;
-    if (a > n - 1) a = n - 1;
-    while (a > 0 && a * n - a * (a - 1) / 2 > idx) --a;
-    while (a + 1 < n && (a + 1) * n - (a + 1) * a / 2 <= idx) ++a;
-    return a;
-}
+// (the pair decode, triangle_row, is qs_triangle.h's: the products' triangular batch uses the same one)
 
 // *flag |= 1 iff some u[a,b,c,d] differs BITWISE from u[b,a,d,c] (-0.0 against +0.0 differs, equal NaNs do not).  A
 // workgroup takes one pair a <= b and one 32 x 32 tile (ti, tj) of u[a,b] together with tile (tj, ti) of u[b,a]; on the
@@ -275,7 +267,7 @@ __global__ __launch_bounds__(256) void exchange_transpose_check_kernel(const T* 
     const int64_t pair = blockIdx.x / ntiles;
     const int tile = blockIdx.x % ntiles;
     const int ti = tile / nt, tj = tile % nt;
-    const int64_t a = triangle_row(pair, l);
+    const int64_t a = triangle_row((uint32_t)pair, (uint32_t)l);
     const int64_t b = a + (pair - (a * l - a * (a - 1) / 2));
     const int64_t ll = (int64_t)l * l;
     load_tile(t1, u + (a * l + b) * ll, l, ti * PT, tj * PT);

@@ -190,19 +190,23 @@ mixed_real_u = True
 
 @_plain
 def gemm_raw(dt, A, B, out, m, n, k, lda, ldb, ldc, batch=1, sa=0, sb=0, sc=0,
-             accumulate=False, a_off=0, b_off=0, c_off=0):
+             accumulate=False, a_off=0, b_off=0, c_off=0, pairs=None):
     """Thin call of ``qs_matmul`` on tensors already prepared by the caller
-    (contiguous storage, matching dtype); offsets and strides in elements."""
+    (contiguous storage, matching dtype); offsets and strides in elements.
+
+    ``pairs=n``: ``qs_matmul_pairs`` -- the batch is the upper triangle of an n x n grid (``batch`` is not used), the
+    operands of pair (i, j >= i) at ``(i * n + j)`` strides."""
     lib = _lib.load()
     es = 16 if dt == _C128 else 8
+    fn, name, count = (lib.qs_matmul, "qs_matmul", batch) if pairs is None else (lib.qs_matmul_pairs, "qs_matmul_pairs", pairs)
     with _on_device_of(A, B, out):
         _ran(
-            lib.qs_matmul(
+            fn(
                 dtype_code(dt), A.data_ptr() + a_off * es, B.data_ptr() + b_off * es,
-                out.data_ptr() + c_off * es, m, n, k, lda, ldb, ldc, batch, sa, sb, sc,
+                out.data_ptr() + c_off * es, m, n, k, lda, ldb, ldc, count, sa, sb, sc,
                 1 if accumulate else 0, _stream(),
             ),
-            "qs_matmul",
+            name,
         )
     return out
 

@@ -1,13 +1,15 @@
 """Same-process A/B of the transform's exchange-symmetry route against the plain route, and the route's phases.
 
     python tools/exchange_route_ab.py --sizes 160,192,224,256 --dtype f64 [--blocks 32,64,128] [--blocks-d 8,16,64]
-                                      [--reps 5] [--phases [--c-blocks 16,64]]
+                                      [--pairs 0,1] [--reps 5] [--phases [--c-blocks 16,64]]
 
 Per size: one symmetric tensor (bench.make_inputs), then the plain route (`exchange=0`) and every (block, block_d)
 of the forced route (`exchange=2`) in ALTERNATING repetitions (NOTES.md "How to measure here"), HIP-event time per
 call; the route's time includes the check kernel and its read-back, as `kernels.transform_two_body` pays them.
 `--phases` replays the route's launches one phase at a time through `qs_matmul` / `qs_exchange_mirror` with an event
-pair around each (the phases of qs_api.hip's transform_two_body_exchange_route, same shapes and strides)."""
+pair around each (the phases of qs_api.hip's transform_two_body_exchange_route, same shapes and strides): d and c both as
+the launches per block / per row of `exchange_pairs=0` and as the one triangular-batch launch (`qs_matmul_pairs`) of
+`exchange_pairs=1`.  `--pairs 0,1` times the whole route at both settings of that key."""
 
 import argparse
 import os
@@ -58,6 +60,12 @@ def phases(torch, K, u, C, Ct, out, blk, blk_d, reps, c_blocks=(), other_order=F
             b0 = a // cb * cb
             K.gemm_raw(dt, CT, W, out, L, L, L, L, L, L, L - b0, 0, L2, L2, b_off=(a * L + b0) * L2, c_off=(a * L + b0) * L2)
 
+    def d_pairs():
+        K.gemm_raw(dt, u, C, W, L, L, L, L, L, L, 0, L2, 0, L2, pairs=L)
+
+    def c_pairs():
+        K.gemm_raw(dt, CT, W, out, L, L, L, L, L, L, 0, 0, L2, L2, pairs=L)
+
     def a_():
         K.gemm_raw(dt, Ct, out, W, L, L3, L, L, L3, L3)
 
@@ -76,7 +84,7 @@ def phases(torch, K, u, C, Ct, out, blk, blk_d, reps, c_blocks=(), other_order=F
             K.gemm_raw(dt, Ct, W, out, rows, (L - p0) * L2, L, L, L3, L3, a_off=p0 * L, b_off=p0 * L2, c_off=p0 * L3 + p0 * L2)
 
     other = [("other order: b full", b_full), ("other order: a blocks", a_blocks)] if other_order else []
-    steps = [("check", check), ("d", d)] + [(f"c, b >= block {cb}", lambda cb=cb: c(cb)) for cb in c_blocks] + [("c", c), ("mirror T2", lambda: K.exchange_mirror_(out.view(L, L, L, L), 1)),
+    steps = [("check", check), ("d, per block", d), ("d", d_pairs)] + [(f"c, b >= block {cb}", lambda cb=cb: c(cb)) for cb in c_blocks] + [("c, per row", c), ("c", c_pairs), ("mirror T2", lambda: K.exchange_mirror_(out.view(L, L, L, L), 1)),
              ] + other + [("a", a_), ("closing product", b), ("mirror out", lambda: K.exchange_mirror_(out.view(L, L, L, L), blk))]
     times = {name: [] for name, _ in steps}
     for _ in range(reps + 1):
@@ -85,7 +93,7 @@ def phases(torch, K, u, C, Ct, out, blk, blk_d, reps, c_blocks=(), other_order=F
     total = 0.0
     for name, _ in steps:
         t = med(times[name][1:])
-        total += 0.0 if name.startswith(("c, ", "other order")) else t
+        total += 0.0 if name.startswith(("c, ", "d, ", "other order")) else t
         print(f"    phase {name:20s} {t:8.3f} ms   (runs: {' '.join('%.3f' % x for x in times[name][1:])})")
     print(f"    phases total     {total:8.3f} ms")
     del W
@@ -97,6 +105,7 @@ def main():
     ap.add_argument("--dtype", choices=["f64", "c128"], default="f64")
     ap.add_argument("--blocks", default="64")
     ap.add_argument("--blocks-d", default="16")
+    ap.add_argument("--pairs", default="1", help="exchange_pairs settings of the route to time, e.g. 0,1")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--phases", action="store_true")
     ap.add_argument("--other-order", action="store_true", help="with --phases: also time b full, then a per block of rows")
@@ -109,7 +118,7 @@ def main():
 
     dev = torch.device("cuda:0")
     dtype = torch.float64 if args.dtype == "f64" else torch.complex128
-    configs = [(int(b), int(bd)) for b in args.blocks.split(",") for bd in args.blocks_d.split(",")]
+    configs = [(int(b), int(bd), int(pr)) for b in args.blocks.split(",") for bd in args.blocks_d.split(",") for pr in args.pairs.split(",")]
     for l in [int(x) for x in args.sizes.split(",")]:
         u, C, Ct = bench.make_inputs(torch, l, dtype, dev)
         out = torch.empty_like(u)
@@ -119,8 +128,8 @@ def main():
             with K.tuning(exchange=0):
                 K.transform_two_body(u, C, Ct, out=out)
 
-        def route(b, bd):
-            with K.tuning(exchange=2, exchange_block=b, exchange_block_d=bd):
+        def route(b, bd, pr):
+            with K.tuning(exchange=2, exchange_block=b, exchange_block_d=bd, exchange_pairs=pr):
                 K.transform_two_body(u, C, Ct, out=out)
 
         plain()
@@ -141,7 +150,7 @@ def main():
         print(f"  plain                       median {base:8.3f} ms   runs {' '.join('%.3f' % x for x in runs['plain'])}")
         for cfg in configs:
             m = med(runs[cfg])
-            print(f"  route block={cfg[0]:3d} block_d={cfg[1]:3d} median {m:8.3f} ms   runs {' '.join('%.3f' % x for x in runs[cfg])}"
+            print(f"  route block={cfg[0]:3d} block_d={cfg[1]:3d} pairs={cfg[2]} median {m:8.3f} ms   runs {' '.join('%.3f' % x for x in runs[cfg])}"
                   f"   plain/route {base / m:.3f}")
         sys.stdout.flush()
         if args.phases:
