@@ -522,7 +522,14 @@ const char* qs_last_dispatch(void);
  *     kernels, which cover the small extent of a product with one tile to the
  *     next multiple of 16: 0 never, 1 by estimated time, 2 wherever they
  *     exist), "gemm_strip_w" (tuning runs: their relative rate in percent,
- *     0 = built-in weights), "gemm_fast_unaligned" (0 = 8-byte global items at
+ *     0 = built-in weights), "gemm_strip_wide" (their 256-wide form: 0 =
+ *     automatic, where the tile list fills the chip a few times over, 1 = never,
+ *     2 = wherever it exists, fp64 up to 10 blocks of 16; any other value is
+ *     refused with QS_ERR_BAD_EXTENT), "gemm_strip_wgs" (the most workgroups of
+ *     a strip launch: 0 = one per CU, 1 ... 4096 = at most that many, each
+ *     walking more tiles; any other value is refused with QS_ERR_BAD_EXTENT;
+ *     the result does not depend on either key),
+ *     "gemm_fast_unaligned" (0 = 8-byte global items at
  *     odd strides as in rounds 1-3, 1 = 16-byte items at any 8-byte-aligned
  *     address), "comm_drop_wait" (TEST HOOK of the sharded entry points: a bit
  *     mask of stream waits between the caller's stream and the communicator's

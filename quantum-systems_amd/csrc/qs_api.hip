@@ -235,6 +235,16 @@ int qs_tuning_set(const char* key, int64_t value) {
     if (!strcmp(key, "sandwich")) { g_tune.sandwich = (int)value; return QS_OK; }
     if (!strcmp(key, "gemm_strip")) { g_tune.gemm_strip = (int)value; return QS_OK; }
     if (!strcmp(key, "gemm_strip_w")) { g_tune.gemm_strip_w = (int)value; return QS_OK; }
+    if (!strcmp(key, "gemm_strip_wide")) {
+        if (value < 0 || value > 2) return QS_ERR_BAD_EXTENT;
+        g_tune.gemm_strip_wide = (int)value;
+        return QS_OK;
+    }
+    if (!strcmp(key, "gemm_strip_wgs")) {
+        if (value < 0 || value > 4096) return QS_ERR_BAD_EXTENT;
+        g_tune.gemm_strip_wgs = (int)value;
+        return QS_OK;
+    }
     if (!strcmp(key, "gemm_fast_unaligned")) { g_tune.gemm_fast_unaligned = (int)value; return QS_OK; }
     if (!strcmp(key, "comm_drop_wait")) { g_tune.comm_drop_wait = (int)value; return QS_OK; }
     if (!strcmp(key, "sandwich_mode")) { g_tune.sandwich_mode = (int)value; return QS_OK; }

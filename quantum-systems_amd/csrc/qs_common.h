@@ -235,6 +235,9 @@ struct Tuning {
     int gemm_strip = 1;          // strip kernels (qs_gemm_strip.hip: the small extent of a product, <= 256, covered by ONE tile to the next
                                  // multiple of 16, eight waves): 0 never, 1 by estimated time, 2 wherever they exist
     int gemm_strip_w = 0;        // (tuning runs: relative rate of the strip kernels in percent, 0 = the built-in weights)
+    int gemm_strip_wide = 0;     // the strip kernels' 256-wide form (fp64, up to 10 blocks): 0 automatic (where the tile list fills the chip a few
+                                 // times over), 1 never, 2 wherever it exists -- tests reach it at kilobyte sizes (tests/test_gpu_strip_forms.py)
+    int gemm_strip_wgs = 0;      // most workgroups of a strip launch, 1 ... 4096 (0 = one per CU): a short tile list walks on few workgroups
     int gemm_fast_unaligned = 1; // 16-byte items of the VALU-free kernel's edge form also at odd strides / extents (0: 8-byte items there)
     int comm_drop_wait = 0;      // TEST HOOK (qs_comm.hip): bit mask of stream waits of the sharded entry points to leave out -- the negative
                                  // test of the asynchronous stand-in transport; never set outside tests/

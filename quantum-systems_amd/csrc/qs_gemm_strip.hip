@@ -530,6 +530,8 @@ int launch_strip(StripArgs g, hipStream_t stream) {
     P -= P % 8;
     if (P < 8) P = 8;
     if (P > tiles) P = tiles;
+    // (g_tune.gemm_strip_wgs: fewer workgroups, each walking more tiles -- the walk takes any P, xcd_chunked_index_fast knows the total only)
+    if (g_tune.gemm_strip_wgs > 0 && P > g_tune.gemm_strip_wgs) P = g_tune.gemm_strip_wgs;
     auto kern = gemm_strip_kernel<CX, FORM, T, WN, SETS>;
     static PerDeviceLds lds_opt_in;
     if (int rc = opt_in_dynamic_lds((const void*)kern, lds, lds_opt_in, "hipFuncSetAttribute(gemm_strip)")) return rc;
@@ -586,7 +588,7 @@ int gemm_strip_try(const Product& p, double other_cost, hipStream_t stream) {
     const bool cx = p.dtype == QS_C128;
     const int64_t esz = cx ? 16 : 8;
     const int64_t m = p.m, n = p.n, k = p.k, lda = p.lda, ldb = p.ldb, ldc = p.ldc, batch = p.batch;
-#ifdef QS_STRIP_TUNING_ENV      // development: tuning runs set the tile height limit / the wide form (read once)
+#ifdef QS_STRIP_TUNING_ENV      // development: tuning runs set the tile height limit (read once; the wide form: tuning key gemm_strip_wide)
     static const int max_t_env = [] { const char* e = getenv("QS_STRIP_MAXT"); return e ? atoi(e) : 0; }();
 #else
     constexpr int max_t_env = 0;
@@ -635,11 +637,9 @@ int gemm_strip_try(const Product& p, double other_cost, hipStream_t stream) {
     g.c_end = reinterpret_cast<uint64_t>(p.C) + (uint64_t)(((batch - 1) * sc + (m - 1) * ldc + n) * esz);
     // wide tiles (256 of the big extent) where the accumulators fit and the list still fills the chip a few times over
     const double slots = device_cu_count();
-    bool wide = !cx && t <= kWideMaxT && cdiv(g.big, 256) >= 4 * (int64_t)slots;
-#ifdef QS_STRIP_TUNING_ENV
-    static const int wide_env = [] { const char* e = getenv("QS_STRIP_WIDE"); return e ? atoi(e) : -1; }();
-    if (wide_env >= 0) wide = !cx && wide_env != 0 && t <= kWideMaxT;
-#endif
+    // (g_tune.gemm_strip_wide: 1 never, 2 wherever the form exists)
+    const bool wide = !cx && t <= kWideMaxT && g_tune.gemm_strip_wide != 1 &&
+                      (g_tune.gemm_strip_wide == 2 || cdiv(g.big, 256) >= 4 * (int64_t)slots);
     const int64_t tiles = cdiv(g.big, wide ? 256 : 128) * g.nsmall;
     if (g_tune.gemm_strip == 1 && t * g.nsmall < 3) return 1;      // (up to 32 rows / columns: the other kernels' ground, not measured here)
     if (g_tune.gemm_strip == 1) {
