@@ -961,6 +961,18 @@ int qs_det_ci_density2(int c_dtype, const int64_t* dets, const void* bra, const 
  *       one gather through both tables per (p, q) in a fixed order; no workspace.
  *       On a truncated list a missing target contributes nothing: like H, S^2 is
  *       then the operator of the truncated formulation.
+ *   qs_string_ci_one_body : d one-body operators on K vectors, no workspace and no
+ *       intermediate:
+ *         out[x, k, Ia, Ib] = sum_pq ( A_up[x,p,q]   sgn c_k[Ta[Ia,pq], Ib]
+ *                                    + A_down[x,p,q] sgn c_k[Ia, Tb[Ib,pq]] )
+ *       for A_up, A_down (d, m, m) row-major, c (K, na, nb) and out (d, K, na, nb).
+ *       A_down == NULL means A_down = A_up: the spin-free sum_pq A[p,q] E_pq.  One
+ *       gather through the tables per (p, q) serves a group of up to 4 operators;
+ *       the order of one element's sum is pq ascending, alpha before beta, every
+ *       term an fma: a repeated call gives the same bits.  dtype pairs (A; c) as
+ *       for sigma.  d < 1, d K na nb elements past int64 bytes, or a grid
+ *       ceil(d / 4) K na ceil(nb / threads) past 2^31 - 1 is QS_ERR_BAD_EXTENT;
+ *       out may share no byte with c, A_up, A_down or a table (QS_ERR_ALIAS).
  * dtype pairs (ht, ut, k, W; c): (F64, F64), (C128, C128) and (F64, C128), which
  * runs the product in fp64 on the re / im pairs of D as 2 K na nb columns (no
  * complex copy of W); (C128, F64) is QS_ERR_BAD_DTYPE.
@@ -1004,6 +1016,9 @@ int qs_string_ci_density2_spin(int c_dtype, const int32_t* ta, const int32_t* tb
                                void* rho_b, void* work, int64_t work_bytes, int64_t budget_bytes, void* stream);
 int qs_string_ci_spin_squared(int c_dtype, const int32_t* ta, const int32_t* tb, int64_t m, int64_t na, int64_t nb,
                               int64_t Na, int64_t Nb, const void* c, int64_t K, void* out, void* stream);
+int qs_string_ci_one_body(int h_dtype, int c_dtype, const void* A_up, const void* A_down, int64_t d, const int32_t* ta,
+                          const int32_t* tb, int64_t m, int64_t na, int64_t nb, const void* c, int64_t K, void* out,
+                          void* stream);
 int qs_probe_mfma_f64(void* sink, int64_t blocks, int64_t iters, void* stream);
 int qs_probe_stream_copy(const void* src, void* dst, int64_t bytes, void* stream);
 

@@ -11,7 +11,7 @@ The directory is named ``quantum-systems_amd`` after the upstream project;
 import it as ``quantum_systems_amd`` (the sibling shim package aliases it).
 """
 
-from . import _lib, configuration_interaction, determinant_ci, kernels, moller_plesset, sharded, string_ci, two_particle  # noqa: F401
+from . import _lib, configuration_interaction, determinant_ci, kernels, moller_plesset, response, sharded, string_ci, two_particle  # noqa: F401
 from .array_module import DeviceArray, DeviceModule, hip
 from .sharded_module import ShardedDeviceModule, ShardedTensor4
 from .basis_set import BasisSet, ChangeBasisPlan
@@ -32,7 +32,7 @@ from .two_dim_ho import TwoDimensionalDoubleWell, TwoDimensionalHarmonicOscillat
 
 __all__ = [
     "BasisSet", "RandomBasisSet", "QuantumSystem", "SpatialOrbitalSystem",
-    "GeneralOrbitalSystem", "HartreeFock", "mp2_energy", "CIS", "configuration_interaction", "TwoParticleCI", "two_particle", "DeterminantCI", "determinant_ci", "full_space", "sz_sector", "truncated_space", "StringCI", "string_ci", "full_strings", "setup_basis_set", "construct_custom_system",
+    "GeneralOrbitalSystem", "HartreeFock", "mp2_energy", "CIS", "configuration_interaction", "TwoParticleCI", "two_particle", "DeterminantCI", "determinant_ci", "full_space", "sz_sector", "truncated_space", "StringCI", "string_ci", "full_strings", "response", "setup_basis_set", "construct_custom_system",
     "TwoDimensionalHarmonicOscillator", "TwoDimensionalDoubleWell", "TwoDimHarmonicOscB", "ODQD", "ODSincDVR",
     "ChangeBasisPlan", "hip", "DeviceModule", "DeviceArray", "ShardedDeviceModule", "ShardedTensor4", "kernels", "sharded",
 ]

@@ -120,6 +120,7 @@ SIGNATURES = {
     "qs_string_ci_density2_spin_plan": (c_int, [c_int] + [c_i64] * 4 + [c_ptr]),
     "qs_string_ci_density2_spin": (c_int, [c_int, c_ptr, c_ptr] + [c_i64] * 3 + [c_ptr] * 8 + [c_i64, c_i64, c_ptr]),
     "qs_string_ci_spin_squared": (c_int, [c_int, c_ptr, c_ptr] + [c_i64] * 5 + [c_ptr, c_i64, c_ptr, c_ptr]),
+    "qs_string_ci_one_body": (c_int, [c_int, c_int, c_ptr, c_ptr, c_i64, c_ptr, c_ptr] + [c_i64] * 3 + [c_ptr, c_i64, c_ptr, c_ptr]),
 }
 
 ABI_VERSION = 4

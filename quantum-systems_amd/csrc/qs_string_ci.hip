@@ -854,6 +854,100 @@ __global__ __launch_bounds__(kScBlock) void string_ci_spin_kernel(const ScArgs a
     }
 }
 
+// ---- a one-body operator on a state (qs_string_ci_one_body) ----------------------------------------------------------------
+//   out[x, k, Ia, Ib] = sum_pq ( Au[x,p,q] sgn c_k[Ta[Ia,pq], Ib] + Ad[x,p,q] sgn c_k[Ia, Tb[Ib,pq]] )
+// A gather with the geometry of the fold and of S^2, and no intermediate: one workgroup per group of up to kScObG operators,
+// vector, alpha string and tile of beta strings.  One read of the two table entries and one gather of c per replacement serve
+// the whole group.  The order of one element's sum is pq ascending, alpha before beta, every product an explicit fma on the
+// signed copy of c (exact); the table's zeros are skipped.
+
+constexpr int kScObG = 4;             // operators that share the table reads and the gathers of one workgroup
+
+// acc += a v: HW doubles per element of a, CW per element of v and acc
+template <int HW, int CW>
+__device__ __forceinline__ void sc_ob_feed(double (&acc)[CW], const double* __restrict__ a, const double (&v)[CW]) {
+    acc[0] = fma(a[0], v[0], acc[0]);
+    if constexpr (CW == 2) {
+        acc[CW - 1] = fma(a[0], v[CW - 1], acc[CW - 1]);
+        if constexpr (HW == 2) {
+            acc[0] = fma(-a[HW - 1], v[CW - 1], acc[0]);
+            acc[CW - 1] = fma(a[HW - 1], v[0], acc[CW - 1]);
+        }
+    }
+}
+
+template <int FORM>
+__global__ __launch_bounds__(kScBlock) void string_ci_one_body_kernel(const ScArgs a, const int32_t* __restrict__ ta,
+                                                                     const double* __restrict__ Au, const double* __restrict__ Ad,
+                                                                     double* __restrict__ out, int64_t d) {
+    constexpr int HW = form_widths(FORM).uw, CW = form_widths(FORM).aw;
+    extern __shared__ __attribute__((aligned(16))) int32_t sc_tb[];
+    const int B = blockDim.x, t = threadIdx.x, m2 = a.m2;
+    const unsigned row = blockIdx.x / a.ntile;                            // (operator group, k, ia), uniform
+    const int64_t ia = row % (unsigned)a.na;
+    const unsigned gk = row / (unsigned)a.na;
+    const int64_t k = gk % (unsigned)a.K, x0 = (int64_t)(gk / (unsigned)a.K) * kScObG;
+    const int64_t ib0 = (int64_t)(blockIdx.x % a.ntile) * B;
+    const int64_t ib = ib0 + t, nb = a.nb, dim = a.na * a.nb;
+    const bool live = ib < nb;
+    const int nx = d - x0 < kScObG ? (int)(d - x0) : kScObG;
+    const int32_t* __restrict__ ta_row = ta + ia * m2;
+    const double* __restrict__ ck = a.c + k * dim * CW;
+    const double* __restrict__ au = Au + x0 * m2 * HW;                    // A[x0 + g][pq] at (g m2 + pq) HW: uniform addresses
+    const double* __restrict__ ad = Ad + x0 * m2 * HW;
+    double acc[kScObG][CW];
+#pragma unroll
+    for (int g = 0; g < kScObG; ++g)
+#pragma unroll
+        for (int w = 0; w < CW; ++w) acc[g][w] = 0.0;
+    for (int pq0 = 0; pq0 < m2; pq0 += kScChunk) {
+        __syncthreads();
+        sc_stage(sc_tb, a.tb, ib0, nb, pq0, m2);
+        __syncthreads();
+        if (!live) continue;
+        const int nj = m2 - pq0 < kScChunk ? m2 - pq0 : kScChunk;
+        for (int j = 0; j < nj; ++j) {
+            const int pq = pq0 + j;
+            const int32_t ea = ta_row[pq];                                // uniform address: a scalar load
+            const int32_t eb = sc_tb[j * (B + 1) + t];
+            if (ea) {                                                     // uniform
+                const int64_t ja = sc_target(ea, a.na);
+                if (ja >= 0) {
+                    const double* x = ck + (ja * nb + ib) * CW;           // contiguous over the lanes
+                    double v[CW];
+#pragma unroll
+                    for (int w = 0; w < CW; ++w) v[w] = ea < 0 ? -x[w] : x[w];
+#pragma unroll
+                    for (int g = 0; g < kScObG; ++g)
+                        if (g < nx) sc_ob_feed<HW, CW>(acc[g], au + ((int64_t)g * m2 + pq) * HW, v);
+                }
+            }
+            if (eb) {
+                const int64_t jb = sc_target(eb, nb);
+                if (jb >= 0) {
+                    const double* x = ck + (ia * nb + jb) * CW;           // a gather inside the row c[Ia, :]
+                    double v[CW];
+#pragma unroll
+                    for (int w = 0; w < CW; ++w) v[w] = eb < 0 ? -x[w] : x[w];
+#pragma unroll
+                    for (int g = 0; g < kScObG; ++g)
+                        if (g < nx) sc_ob_feed<HW, CW>(acc[g], ad + ((int64_t)g * m2 + pq) * HW, v);
+                }
+            }
+        }
+    }
+    if (live) {
+#pragma unroll
+        for (int g = 0; g < kScObG; ++g) {
+            if (g < nx) {
+                double* o = out + (((x0 + g) * a.K + k) * dim + ia * nb + ib) * CW;
+#pragma unroll
+                for (int w = 0; w < CW; ++w) o[w] = acc[g][w];
+            }
+        }
+    }
+}
+
 // The panels of one pass of either density, filled here from (spin, cw, m) and nowhere else.
 struct Sc2Shape {
     int64_t S;                // spin blocks: 1 (the spin sum) or 2 (alpha | beta)
@@ -1256,6 +1350,38 @@ int qs_string_ci_spin_squared(int c_dtype, const int32_t* ta, const int32_t* tb,
     });
     note_dispatch("qs::string_ci_spin_kernel<%d>", cw);
     return launch_status("string CI spin launch");
+}
+
+int qs_string_ci_one_body(int h_dtype, int c_dtype, const void* A_up, const void* A_down, int64_t d, const int32_t* ta,
+                          const int32_t* tb, int64_t m, int64_t na, int64_t nb, const void* c, int64_t K, void* out, void* stream) {
+    dispatch_reset();
+    const int form = tensor_form(h_dtype, c_dtype);
+    if (form < 0) return form;
+    if (!sc_extents_ok(form, m, na, nb, K) || d < 1) return QS_ERR_BAD_EXTENT;
+    const int64_t hs = (int64_t)elem_size(h_dtype), cs = (int64_t)elem_size(c_dtype);
+    const int64_t m2 = m * m, v_elems = K * na * nb, ntile = cdiv(nb, sc_threads(nb));
+    int64_t o_bytes, a_bytes, grid;
+    if (__builtin_mul_overflow(d, v_elems, &o_bytes) || __builtin_mul_overflow(o_bytes, cs, &o_bytes) ||
+        __builtin_mul_overflow(d, m2 * hs, &a_bytes))
+        return QS_ERR_BAD_EXTENT;
+    if (__builtin_mul_overflow(cdiv(d, kScObG), K * na * ntile, &grid) || grid > 0x7fffffffLL) return QS_ERR_BAD_EXTENT;
+    if (!A_up || !ta || !tb || !c || !out) return QS_ERR_NULL_POINTER;
+    if (!aligned(A_up, (size_t)hs) || !aligned(A_down, (size_t)hs) || !aligned(ta, 4) || !aligned(tb, 4) || !aligned(c, (size_t)cs) ||
+        !aligned(out, (size_t)cs))
+        return QS_ERR_MISALIGNED;
+    // a null A_down has no bytes: it overlaps nothing
+    if (int rc = sc_alias({{out, o_bytes}}, {{c, v_elems * cs}, {A_up, a_bytes}, {A_down, A_down ? a_bytes : 0}, {ta, na * m2 * 4},
+                                             {tb, nb * m2 * 4}}))
+        return rc;
+    const ScArgs a = sc_args(ta, tb, c, m, na, nb, K);
+    const int threads = sc_threads(nb);
+    hipStream_t s = (hipStream_t)stream;
+    with_form(form, [&](auto FORM) {
+        hipLaunchKernelGGL((string_ci_one_body_kernel<FORM>), dim3((unsigned)grid), dim3(threads), sc_lds(threads), s, a, ta,
+                           (const double*)A_up, (const double*)(A_down ? A_down : A_up), (double*)out, d);
+    });
+    note_dispatch("qs::string_ci_one_body_kernel<%d>", form);
+    return launch_status("string CI one-body launch");
 }
 
 }  // extern "C"

@@ -1010,6 +1010,13 @@ def det_ci_density2(dets, bra, ket, m, N, out=None):
 STRING_CI_BYTES = 2 << 30
 
 
+def string_ci_budget():
+    """The byte budget in force on the calling thread -- the tuning key ``string_ci_bytes`` where it is set, else
+    ``STRING_CI_BYTES`` --, read off ``qs_string_ci_group`` on lists of one string, whose two panels are 32 bytes per
+    vector: exact to 32 bytes, at most 64 GiB."""
+    return 32 * check(_lib.load().qs_string_ci_group(QS_F64, QS_F64, 1, 1, 1, (1 << 31) - 1, STRING_CI_BYTES), "group query")
+
+
 def _strings_checked(strings, what):
     if not isinstance(strings, torch.Tensor) or strings.dtype != torch.int64 or strings.dim() != 1 or strings.numel() < 1:
         raise ValueError(f"{what} must be a non-empty 1-D int64 tensor of occupation strings")
@@ -1334,6 +1341,49 @@ def string_ci_spin_squared(ta, tb, m, Na, Nb, c, out=None):
             lib.qs_string_ci_spin_squared(dtype_code(dt), ta.data_ptr(), tb.data_ptr(), m, na, nb, int(Na), int(Nb),
                                           c.data_ptr(), K, out.data_ptr(), _stream()),
             "qs_string_ci_spin_squared",
+        )
+    return out
+
+
+@_plain
+def string_ci_one_body(A_up, ta, tb, m, c, A_down=None, out=None):
+    """``out[x, k] = (sum_pq A_up[x,p,q] E^alpha_pq + A_down[x,p,q] E^beta_pq) c[k]`` on ``qs_string_ci_one_body``: ``A_up``
+    (m, m) or (d, m, m), ``c`` (na, nb) or (K, na, nb); the result has the leading axis of ``A_up`` (if present), then that of
+    ``c`` (if present), then (na, nb).  ``A_down=None`` is the spin-free operator ``sum_pq A[p,q] E_pq``.  One gather
+    through the replacement tables, no intermediate and no workspace.  The result is complex if ``A`` or ``c`` is; a real
+    ``A`` with a complex ``c`` stays real, a real ``c`` under a complex ``A`` is converted once.  Repeating a call gives the
+    same bits."""
+    lib = _lib.load()
+    m = int(m)
+    ta, tb = _string_tables(ta, tb, m)
+    if not isinstance(c, torch.Tensor) or c.dim() not in (2, 3):
+        raise ValueError("c must be (K, na, nb) or (na, nb)")
+    ops = (A_up,) if A_down is None else (A_up, A_down)
+    hdt = result_dtype(*ops)
+    dt = result_dtype(*ops, c)
+    A_up = _dev(A_up, hdt)
+    if A_up.dim() not in (2, 3) or tuple(A_up.shape[-2:]) != (m, m) or A_up.shape[0] < 1:
+        raise ValueError(f"A_up has shape {tuple(A_up.shape)}: need ({m}, {m}) or (d, {m}, {m}) with d >= 1")
+    if A_down is not None:
+        A_down = _dev(A_down, hdt)
+        if tuple(A_down.shape) != tuple(A_up.shape):
+            raise ValueError(f"A_down has shape {tuple(A_down.shape)}: need that of A_up, {tuple(A_up.shape)}")
+    c = _dev(c, dt)
+    na, nb = ta.shape[0], tb.shape[0]
+    K = 1 if c.dim() == 2 else c.shape[0]
+    d = 1 if A_up.dim() == 2 else A_up.shape[0]
+    if tuple(c.shape[-2:]) != (na, nb) or K < 1:
+        raise ValueError(f"c has shape {tuple(c.shape)}: need (K, {na}, {nb}) with K >= 1")
+    shape = tuple(A_up.shape[:-2]) + tuple(c.shape[:-2]) + (na, nb)
+    if out is None:
+        out = torch.empty(shape, dtype=dt, device=c.device)
+    else:
+        _check_out(out, shape, dt, "string_ci_one_body")
+    with _on_device_of(A_up, *(() if A_down is None else (A_down,)), ta, tb, c, out):
+        _ran(
+            lib.qs_string_ci_one_body(dtype_code(hdt), dtype_code(dt), A_up.data_ptr(), None if A_down is None else A_down.data_ptr(),
+                                      d, ta.data_ptr(), tb.data_ptr(), m, na, nb, c.data_ptr(), K, out.data_ptr(), _stream()),
+            "qs_string_ci_one_body",
         )
     return out
 

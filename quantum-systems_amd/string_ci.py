@@ -37,13 +37,22 @@ the beta replacement kept apart:
     Gaa, Gab, Gbb = ci.two_body_density_spin(0)       # Gamma^ba[p,q,r,s] = Gab[q,p,s,r]; the four add up to G
     M = ci.pair_density_matrix(phi0, 0, spins="ab")   # up density given a down particle where the orbitals take phi0
 
-Out of scope here: full spin adaptation (``S = 0`` apart from ``S = 2``) and a sharded ``u``.
+A one-body operator on a state is one gather through the tables (``kernels.string_ci_one_body``, no intermediate), and the
+response of a state to it a Lanczos recurrence on ``H`` from ``(A - <A>) c`` (``response.lanczos``), three vectors of memory:
+
+    phi = ci.apply_one_body(A, c)                     # A (l, l) or (d, l, l) in the system's basis; A_down= for the other spin
+    S = ci.spectral_function(A, k=0, n_steps=64)      # response.SpectralFunction: S.poles, S.weights, S.moment(p), S.response(w)
+    Sx, Sy = ci.dipole_spectrum(0)                    # one per spatial dimension: the dipole absorption lines
+    a = ci.polarizability(0.0)                        # alpha_xx(omega) per dimension
+
+Out of scope here: full spin adaptation (``S = 0`` apart from ``S = 2``), a sharded ``u`` (refused in the constructor), the
+off-diagonal polarizability ``alpha_xy`` (it needs a block recurrence), and the same calls on ``DeterminantCI``.
 """
 
 import numpy
 import torch
 
-from . import kernels
+from . import kernels, response
 from .basis_set import _deliver
 from .determinant_ci import M_MAX, _dagger, _plain, block_davidson, full_space, popcounts
 from .general_orbital_system import GeneralOrbitalSystem
@@ -429,6 +438,70 @@ class StringCI:
     def transition_dipole(self, k, l):
         """``<c_k| dipole_moment |c_l>``, one value per spatial dimension."""
         return self.expectation_one_body(self.system.dipole_moment, k, l)
+
+    def _vectors_checked(self, c, what):
+        c = _plain(c)
+        if c.dim() not in (2, 3) or tuple(c.shape[-2:]) != (self.na, self.nb):
+            raise ValueError(f"{what} has shape {tuple(c.shape)}: need (k, {self.na}, {self.nb}) or ({self.na}, {self.nb})")
+        return c
+
+    def apply_one_body(self, A, c, A_down=None):
+        """``A c_k`` for ``c`` (k, na, nb) or (na, nb), device tensor in and out (``kernels.string_ci_one_body``): ``A`` is a
+        matrix (l, l) or a stack (d, l, l) in the system's basis, as in ``expectation_one_body``, and acts as
+        ``sum_pq (C^H A C)[p,q] E_pq``; the result has the leading axis of ``A`` (if present), then that of ``c``.  With
+        ``A_down`` the up particles see ``A`` and the down particles ``A_down``.  Under a ``spin_parity`` only the spin-free
+        form is taken (it commutes with the transposition, so the result keeps the parity)."""
+        with torch._C.DisableTorchFunctionSubclass():
+            c = self._vectors_checked(c, "c")
+            if A_down is not None and self.spin_parity is not None:
+                raise ValueError("under a spin parity the operator must be spin-free: A_down would leave the subspace")
+            At = self._in_orbitals(A)
+            Ad = None if A_down is None else self._in_orbitals(A_down)
+            if Ad is not None and tuple(Ad.shape) != tuple(At.shape):
+                raise ValueError(f"A_down has shape {tuple(Ad.shape)}: need that of A, {tuple(At.shape)}")
+            return kernels.string_ci_one_body(At, self._ta, self._tb, self.m, c, A_down=Ad)
+
+    def spectral_function(self, A, k=0, n_steps=64, A_down=None, reorthogonalize=False, beta_tol=0.0, state=None):
+        """The ``response.SpectralFunction`` of ONE one-body operator ``A`` (l, l) on solved state ``k`` -- or, with
+        ``state=``, on a given vector (na, nb), which is normalised here and whose energy is ``Re <c|H c>`` from one
+        ``sigma`` (no ``solve()`` needed) --: ``n_steps`` of ``response.lanczos`` on ``H`` from
+        ``phi = A c - <c|A c> c``.  Poles are excitation energies ``E_j - E_k`` (the nuclear repulsion cancels), weights
+        ``|<j|A|c>|^2``; ``phi = 0`` gives the empty spectrum.  ``reorthogonalize`` and ``beta_tol`` as in
+        ``response.lanczos``."""
+        with torch._C.DisableTorchFunctionSubclass():
+            if _plain(A).dim() != 2 or (A_down is not None and _plain(A_down).dim() != 2):
+                raise ValueError("spectral_function takes ONE operator (l, l): a stack goes operator by operator")
+            if state is None:
+                if self._c is None:
+                    raise RuntimeError("call solve() first, or give state=")
+                c = self._c[k]
+                energy = float(self.E[k]) - float(self.system.nuclear_repulsion_energy)
+            else:
+                c = _plain(state)
+                if tuple(c.shape) != (self.na, self.nb):
+                    raise ValueError(f"state has shape {tuple(c.shape)}: need ({self.na}, {self.nb})")
+                c = c.to(self._dt) if self._dt == torch.complex128 else c
+                c = (c / torch.linalg.vector_norm(c)).contiguous()
+                energy = float(torch.vdot(c.reshape(-1), self.sigma(c).to(c.dtype).reshape(-1)).real.item())
+            Ac = self.apply_one_body(A, c, A_down)
+            c = c.to(Ac.dtype)
+            phi = Ac - torch.vdot(c.reshape(-1), Ac.reshape(-1)) * c
+            alpha, beta, norm2 = response.lanczos(self._sigma_rows, phi.reshape(1, self.dim), n_steps, reorthogonalize, beta_tol)
+        return response.SpectralFunction(alpha, beta, norm2, energy)
+
+    def dipole_spectrum(self, k=0, n_steps=64, **kw):
+        """One ``response.SpectralFunction`` per spatial dimension of ``system.dipole_moment`` on solved state ``k``: the
+        dipole absorption lines and their weights (``kw``: ``reorthogonalize``, ``beta_tol``, ``state``)."""
+        return [self.spectral_function(x, k, n_steps, **kw) for x in _plain(self.system.dipole_moment)]
+
+    def polarizability(self, omega, k=0, n_steps=64, eta=0.0, **kw):
+        """The diagonal dynamic polarizability ``alpha_xx(omega)`` per spatial dimension, (dims,) + the shape of
+        ``omega``, from ``dipole_spectrum``: ``sum_j w_j (1 / (omega_j - omega - i eta) + 1 / (omega_j + omega + i eta))``;
+        real for ``eta == 0``."""
+        value = numpy.stack([numpy.asarray(S.response(omega, eta)) for S in self.dipole_spectrum(k, n_steps, **kw)])
+        with torch._C.DisableTorchFunctionSubclass():
+            value = torch.from_numpy(numpy.ascontiguousarray(value)).to(self._ta.device)
+        return _deliver(value, self.system.np)
 
     def natural_orbitals(self, k=0):
         """``(n, C_nat)`` of solved state ``k``: the occupations ``n`` (descending eigenvalues of the Hermitian part of
