@@ -973,6 +973,31 @@ int qs_det_ci_density2(int c_dtype, const int64_t* dets, const void* bra, const 
  *       for sigma.  d < 1, d K na nb elements past int64 bytes, or a grid
  *       ceil(d / 4) K na ceil(nb / threads) past 2^31 - 1 is QS_ERR_BAD_EXTENT;
  *       out may share no byte with c, A_up, A_down or a table (QS_ERR_ALIAS).
+ *   qs_string_ci_ladder_table : the ladder table L (n_t, m) int32 between two
+ *       ascending, duplicate-free lists of ONE spin,
+ *         L[J, p] = +-(index in source of target[J] ^ bit p, plus 1),
+ *       sign (-1)^(bits of target[J] below p), the sign of a_p and of a+_p on a
+ *       string; 0 where that mask is not in source.  With source one particle
+ *       richer than target it is the table of annihilation (out of source, into
+ *       target), with source one particle poorer that of creation.  Errors in this
+ *       order: m outside 1 ... 63 or a list length refused as above, null
+ *       pointer, alignment, table sharing a byte with a list.
+ *   qs_string_ci_ladder : d combinations of ladder operators of one spin on K
+ *       vectors, sum_p phi[x,p] a_p or sum_p phi[x,p] a+_p as the table says:
+ *         spin 0: out[x,k,Ja,Jb] = sum_p phi[x,p] sgn(L[Ja,p]) c_k[|L[Ja,p]| - 1, Jb]
+ *         spin 1: out[x,k,Ja,Jb] = (-1)^n_alpha
+ *                                  sum_p phi[x,p] sgn(L[Jb,p]) c_k[Ja, |L[Jb,p]| - 1]
+ *       for phi (d, m) (not conjugated), c (K, na_s, nb_s) on the source lists and
+ *       out (d, K, na_t, nb_t) on the target lists, (na_t, nb_t) = (n_t, nb_s) for
+ *       spin 0 and (na_s, n_t) for spin 1; the determinant is all alpha creators
+ *       first, so a beta ladder passes n_alpha alpha particles.  No workspace, no
+ *       intermediate; p ascending, every term one fma, zero coefficients skipped:
+ *       a repeated call, a vector alone or in a batch and an operator alone or in
+ *       a group give the same bits.  dtype pairs (phi; c) as for sigma.  Errors in
+ *       this order: dtype pair; extents (those of sigma on the source and on the
+ *       target lists, d < 1, spin not 0 or 1, n_alpha outside 0 ... m, the bytes
+ *       of out past int64, a grid ceil(d / 4) K na_t ceil(nb_t / threads) past
+ *       2^31 - 1); null pointer; alignment; out sharing a byte with c, phi or L.
  * dtype pairs (ht, ut, k, W; c): (F64, F64), (C128, C128) and (F64, C128), which
  * runs the product in fp64 on the re / im pairs of D as 2 K na nb columns (no
  * complex copy of W); (C128, F64) is QS_ERR_BAD_DTYPE.
@@ -1019,6 +1044,11 @@ int qs_string_ci_spin_squared(int c_dtype, const int32_t* ta, const int32_t* tb,
 int qs_string_ci_one_body(int h_dtype, int c_dtype, const void* A_up, const void* A_down, int64_t d, const int32_t* ta,
                           const int32_t* tb, int64_t m, int64_t na, int64_t nb, const void* c, int64_t K, void* out,
                           void* stream);
+int qs_string_ci_ladder_table(const int64_t* target, int64_t n_t, const int64_t* source, int64_t n_s, int64_t m, int32_t* table,
+                              void* stream);
+int qs_string_ci_ladder(int h_dtype, int c_dtype, const void* phi, int64_t d, int64_t spin, const int32_t* table, int64_t m,
+                        int64_t n_alpha, int64_t na_s, int64_t nb_s, int64_t n_t, const void* c, int64_t K, void* out,
+                        void* stream);
 int qs_probe_mfma_f64(void* sink, int64_t blocks, int64_t iters, void* stream);
 int qs_probe_stream_copy(const void* src, void* dst, int64_t bytes, void* stream);
 

@@ -121,6 +121,8 @@ SIGNATURES = {
     "qs_string_ci_density2_spin": (c_int, [c_int, c_ptr, c_ptr] + [c_i64] * 3 + [c_ptr] * 8 + [c_i64, c_i64, c_ptr]),
     "qs_string_ci_spin_squared": (c_int, [c_int, c_ptr, c_ptr] + [c_i64] * 5 + [c_ptr, c_i64, c_ptr, c_ptr]),
     "qs_string_ci_one_body": (c_int, [c_int, c_int, c_ptr, c_ptr, c_i64, c_ptr, c_ptr] + [c_i64] * 3 + [c_ptr, c_i64, c_ptr, c_ptr]),
+    "qs_string_ci_ladder_table": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
+    "qs_string_ci_ladder": (c_int, [c_int, c_int, c_ptr, c_i64, c_i64, c_ptr] + [c_i64] * 5 + [c_ptr, c_i64, c_ptr, c_ptr]),
 }
 
 ABI_VERSION = 4

@@ -375,6 +375,28 @@ __global__ __launch_bounds__(kScRhoBlock) void string_ci_table_kernel(const int6
     }
 }
 
+// The ladder table L[J, p] (n_t, m) between two lists of ONE spin, one thread per entry (grid-stride): +-(index in source of
+// target[J] ^ bit p, plus 1), sign (-1)^(bits of target[J] below p), the sign of a_p and of a+_p alike (source and target
+// differ in bit p alone); 0 where that mask is not in source.  Against a source one particle richer only p outside J can hit
+// (annihilation, out of source into target), against one a particle poorer only p in J (creation).
+__global__ __launch_bounds__(kScRhoBlock) void string_ci_ladder_table_kernel(const int64_t* __restrict__ target, int64_t n_t,
+                                                                             const int64_t* __restrict__ source, int64_t n_s, int m,
+                                                                             int32_t* __restrict__ table) {
+    const int64_t total = n_t * m, step = (int64_t)gridDim.x * kScRhoBlock;
+    for (int64_t idx = (int64_t)blockIdx.x * kScRhoBlock + threadIdx.x; idx < total; idx += step) {
+        const int64_t row = idx / m;
+        const int p = (int)(idx % m);
+        const uint64_t J = (uint64_t)target[row] & (dc_bit(m) - 1);
+        const int64_t pos = dc_find(source, n_s, J ^ dc_bit(p));
+        int32_t e = 0;
+        if (pos >= 0) {
+            const bool minus = (__popcll((unsigned long long)(J & (dc_bit(p) - 1))) & 1) != 0;
+            e = minus ? -(int32_t)(pos + 1) : (int32_t)(pos + 1);
+        }
+        table[idx] = e;
+    }
+}
+
 // D[Ia, Ib] = sum_p n_p ht[p,p] + 1/2 sum_pq n_p n_q ut[p,q,p,q] - 1/2 sum_pq (n_pa n_qa + n_pb n_qb) ut[p,q,q,p]  (real
 // parts): one thread per determinant (grid-stride), p and q ascending over the occupied orbitals.
 template <int HW>
@@ -948,6 +970,125 @@ __global__ __launch_bounds__(kScBlock) void string_ci_one_body_kernel(const ScAr
     }
 }
 
+// ---- particle removal and addition (qs_string_ci_ladder) -------------------------------------------------------------------
+//   spin 0: out[x, k, Ja, Jb] = sum_p phi[x,p] sgn(L[Ja,p]) c_k[|L[Ja,p]| - 1, Jb]
+//   spin 1: out[x, k, Ja, Jb] = (-1)^n_alpha sum_p phi[x,p] sgn(L[Jb,p]) c_k[Ja, |L[Jb,p]| - 1]
+// c lives on the source lists (na_s, nb_s), out on the target lists: (n_t, nb_s) for spin 0, (na_s, n_t) for spin 1; L is the
+// ladder table (n_t, m) of the changed spin, and it alone says whether the call annihilates or creates.  The geometry is
+// that of the one-body kernel: one workgroup per group of up to kScLadG operators, vector, target alpha string and tile of
+// target beta strings.  For spin 0 the table entry and phi[x][p] have uniform addresses and c is read contiguously over the
+// lanes; for spin 1 the table columns go through LDS in chunks of kScChunk and c is gathered inside the row c[Ja, :].  The
+// order of one element's sum is p ascending, every term ONE fma of a coefficient with the exactly signed copy of c.  Skipped:
+// the table's zeros, entries past the source list, and -- a uniform test -- every coefficient that is zero, so that a p whose
+// coefficients vanish for the whole group costs no read of c (phi = 1, d = m: m row reads, not m^2 / 4) and an operator has
+// the same terms alone and in a group.
+
+constexpr int kScLadG = 4;            // operators that share the table reads and the gathers of one workgroup
+
+struct ScLadArgs {
+    const double* c;          // (K, na_s, nb_s)
+    int64_t na_s, nb_s;       // the source lists
+    int64_t na_t, nb_t;       // the target lists
+    int64_t d;
+    unsigned ntile;           // tiles of blockDim.x target beta strings
+    int m, K, spin;
+    int flip;                 // 1 where (-1)^n_alpha = -1 goes with a beta ladder
+};
+
+// bit g set where the coefficient phi[x0 + g][p] is not zero: uniform
+template <int HW>
+__device__ __forceinline__ unsigned sc_lad_live(const double* __restrict__ ph, int m, int p, int nx) {
+    unsigned mask = 0;
+#pragma unroll
+    for (int g = 0; g < kScLadG; ++g) {
+        if (g < nx) {
+            const double* x = ph + ((int64_t)g * m + p) * HW;
+            bool nz = x[0] != 0.0;
+            if constexpr (HW == 2) nz = nz || x[HW - 1] != 0.0;
+            mask |= nz ? 1u << g : 0u;
+        }
+    }
+    return mask;
+}
+
+// acc[g] += phi[x0 + g][p] (+-x) for the operators of mask
+template <int HW, int CW>
+__device__ __forceinline__ void sc_lad_feed(double (&acc)[kScLadG][CW], const double* __restrict__ ph, int m, int p, unsigned mask,
+                                            const double* __restrict__ x, bool minus) {
+    double v[CW];
+#pragma unroll
+    for (int w = 0; w < CW; ++w) v[w] = minus ? -x[w] : x[w];
+#pragma unroll
+    for (int g = 0; g < kScLadG; ++g)
+        if ((mask >> g) & 1u) sc_ob_feed<HW, CW>(acc[g], ph + ((int64_t)g * m + p) * HW, v);
+}
+
+template <int FORM>
+__global__ __launch_bounds__(kScBlock) void string_ci_ladder_kernel(const ScLadArgs a, const int32_t* __restrict__ table,
+                                                                   const double* __restrict__ phi, double* __restrict__ out) {
+    constexpr int HW = form_widths(FORM).uw, CW = form_widths(FORM).aw;
+    extern __shared__ __attribute__((aligned(16))) int32_t sc_tb[];
+    const int B = blockDim.x, t = threadIdx.x, m = a.m;
+    const unsigned row = blockIdx.x / a.ntile;                            // (operator group, k, ja), uniform
+    const int64_t ja = row % (unsigned)a.na_t;
+    const unsigned gk = row / (unsigned)a.na_t;
+    const int64_t k = gk % (unsigned)a.K, x0 = (int64_t)(gk / (unsigned)a.K) * kScLadG;
+    const int64_t jb0 = (int64_t)(blockIdx.x % a.ntile) * B;
+    const int64_t jb = jb0 + t, nb_s = a.nb_s, nb_t = a.nb_t;
+    const bool live = jb < nb_t;
+    const int nx = a.d - x0 < kScLadG ? (int)(a.d - x0) : kScLadG;
+    const double* __restrict__ ck = a.c + k * a.na_s * nb_s * CW;
+    const double* __restrict__ ph = phi + x0 * m * HW;                    // phi[x0 + g][p] at (g m + p) HW: uniform addresses
+    double acc[kScLadG][CW];
+#pragma unroll
+    for (int g = 0; g < kScLadG; ++g)
+#pragma unroll
+        for (int w = 0; w < CW; ++w) acc[g][w] = 0.0;
+    if (a.spin == 0) {                                                    // uniform; nb_t == nb_s
+        if (live) {
+            const int32_t* __restrict__ t_row = table + ja * m;
+            for (int p = 0; p < m; ++p) {
+                const int32_t e = t_row[p];                               // uniform address: a scalar load
+                if (!e) continue;
+                const int64_t ia = sc_target(e, a.na_s);
+                if (ia < 0) continue;
+                const unsigned mask = sc_lad_live<HW>(ph, m, p, nx);
+                if (!mask) continue;
+                sc_lad_feed<HW, CW>(acc, ph, m, p, mask, ck + (ia * nb_s + jb) * CW, e < 0);      // contiguous over the lanes
+            }
+        }
+    } else {                                                              // na_t == na_s: the row c[Ja, :]
+        const bool flip = a.flip != 0;
+        for (int p0 = 0; p0 < m; p0 += kScChunk) {
+            __syncthreads();
+            sc_stage(sc_tb, table, jb0, nb_t, p0, m);
+            __syncthreads();
+            if (!live) continue;
+            const int nj = m - p0 < kScChunk ? m - p0 : kScChunk;
+            for (int j = 0; j < nj; ++j) {
+                const int p = p0 + j;
+                const unsigned mask = sc_lad_live<HW>(ph, m, p, nx);
+                if (!mask) continue;
+                const int32_t e = sc_tb[j * (B + 1) + t];
+                if (!e) continue;
+                const int64_t ib = sc_target(e, nb_s);
+                if (ib < 0) continue;
+                sc_lad_feed<HW, CW>(acc, ph, m, p, mask, ck + (ja * nb_s + ib) * CW, (e < 0) != flip);      // a gather inside the row
+            }
+        }
+    }
+    if (live) {
+#pragma unroll
+        for (int g = 0; g < kScLadG; ++g) {
+            if (g < nx) {
+                double* o = out + ((((x0 + g) * a.K + k) * a.na_t + ja) * nb_t + jb) * CW;
+#pragma unroll
+                for (int w = 0; w < CW; ++w) o[w] = acc[g][w];
+            }
+        }
+    }
+}
+
 // The panels of one pass of either density, filled here from (spin, cw, m) and nowhere else.
 struct Sc2Shape {
     int64_t S;                // spin blocks: 1 (the spin sum) or 2 (alpha | beta)
@@ -1382,6 +1523,56 @@ int qs_string_ci_one_body(int h_dtype, int c_dtype, const void* A_up, const void
     });
     note_dispatch("qs::string_ci_one_body_kernel<%d>", form);
     return launch_status("string CI one-body launch");
+}
+
+int qs_string_ci_ladder_table(const int64_t* target, int64_t n_t, const int64_t* source, int64_t n_s, int64_t m, int32_t* table,
+                              void* stream) {
+    dispatch_reset();
+    if (m < 1 || m > 63 || !sc_list_ok(n_t) || !sc_list_ok(n_s)) return QS_ERR_BAD_EXTENT;
+    if (!target || !source || !table) return QS_ERR_NULL_POINTER;
+    if (!aligned(target, 8) || !aligned(source, 8) || !aligned(table, 4)) return QS_ERR_MISALIGNED;
+    if (int rc = sc_alias({{table, n_t * m * 4}}, {{target, n_t * 8}, {source, n_s * 8}})) return rc;
+    hipLaunchKernelGGL(string_ci_ladder_table_kernel, dim3(sc_stride_grid(n_t * m)), dim3(kScRhoBlock), 0, (hipStream_t)stream,
+                       target, n_t, source, n_s, (int)m, table);
+    note_dispatch("qs::string_ci_ladder_table_kernel");
+    return launch_status("string CI ladder table launch");
+}
+
+int qs_string_ci_ladder(int h_dtype, int c_dtype, const void* phi, int64_t d, int64_t spin, const int32_t* table, int64_t m,
+                        int64_t n_alpha, int64_t na_s, int64_t nb_s, int64_t n_t, const void* c, int64_t K, void* out,
+                        void* stream) {
+    dispatch_reset();
+    const int form = tensor_form(h_dtype, c_dtype);
+    if (form < 0) return form;
+    if (spin != 0 && spin != 1) return QS_ERR_BAD_EXTENT;
+    const int64_t na_t = spin == 0 ? n_t : na_s, nb_t = spin == 0 ? nb_s : n_t;
+    if (!sc_extents_ok(form, m, na_s, nb_s, K) || !sc_extents_ok(form, m, na_t, nb_t, K)) return QS_ERR_BAD_EXTENT;
+    if (d < 1 || n_alpha < 0 || n_alpha > m) return QS_ERR_BAD_EXTENT;
+    const int64_t hs = (int64_t)elem_size(h_dtype), cs = (int64_t)elem_size(c_dtype);
+    const int threads = sc_threads(nb_t);
+    const int64_t ntile = cdiv(nb_t, threads);
+    int64_t o_bytes, p_bytes, grid;
+    if (__builtin_mul_overflow(d, K * na_t * nb_t, &o_bytes) || __builtin_mul_overflow(o_bytes, cs, &o_bytes) ||
+        __builtin_mul_overflow(d, m * hs, &p_bytes))
+        return QS_ERR_BAD_EXTENT;
+    if (__builtin_mul_overflow(cdiv(d, kScLadG), K * na_t * ntile, &grid) || grid > 0x7fffffffLL) return QS_ERR_BAD_EXTENT;
+    if (!phi || !table || !c || !out) return QS_ERR_NULL_POINTER;
+    if (!aligned(phi, (size_t)hs) || !aligned(table, 4) || !aligned(c, (size_t)cs) || !aligned(out, (size_t)cs))
+        return QS_ERR_MISALIGNED;
+    if (int rc = sc_alias({{out, o_bytes}}, {{c, K * na_s * nb_s * cs}, {phi, p_bytes}, {table, n_t * m * 4}})) return rc;
+    ScLadArgs a{};
+    a.c = (const double*)c;
+    a.na_s = na_s; a.nb_s = nb_s; a.na_t = na_t; a.nb_t = nb_t; a.d = d;
+    a.ntile = (unsigned)ntile;
+    a.m = (int)m; a.K = (int)K; a.spin = (int)spin;
+    a.flip = (spin == 1 && (n_alpha & 1)) ? 1 : 0;
+    hipStream_t s = (hipStream_t)stream;
+    with_form(form, [&](auto FORM) {
+        hipLaunchKernelGGL((string_ci_ladder_kernel<FORM>), dim3((unsigned)grid), dim3(threads), spin == 1 ? sc_lds(threads) : 0, s, a,
+                           table, (const double*)phi, (double*)out);
+    });
+    note_dispatch("qs::string_ci_ladder_kernel<%d>", form);
+    return launch_status("string CI ladder launch");
 }
 
 }  // extern "C"

@@ -1389,6 +1389,67 @@ def string_ci_one_body(A_up, ta, tb, m, c, A_down=None, out=None):
 
 
 @_plain
+def string_ci_ladder_table(target, source, m, out=None):
+    """Ladder table ``L[J, p]`` (n_t, m) int32 between two ascending int64 string lists of ONE spin on
+    ``qs_string_ci_ladder_table``: ``+-(index in source of target[J] ^ bit p, plus 1)`` with the sign
+    ``(-1)^(bits of target[J] below p)``, 0 where that string is not in ``source``.  A ``source`` one particle richer than
+    ``target`` gives the table of annihilation, one a particle poorer that of creation."""
+    lib = _lib.load()
+    target, source = _strings_checked(target, "target"), _strings_checked(source, "source")
+    n_t, m = target.numel(), int(m)
+    if out is None:
+        out = torch.empty((n_t, m) if 1 <= m <= 63 else (0, 0), dtype=torch.int32, device=target.device)
+    else:
+        _check_out(out, (n_t, m), torch.int32, "string_ci_ladder_table")
+    with _on_device_of(target, source, out):
+        _ran(lib.qs_string_ci_ladder_table(target.data_ptr(), n_t, source.data_ptr(), source.numel(), m, out.data_ptr(), _stream()),
+             "qs_string_ci_ladder_table")
+    return out
+
+
+@_plain
+def string_ci_ladder(phi, table, spin, n_alpha, c, out=None):
+    """``out[x, k] = sum_p phi[x, p] a_p c[k]`` or ``sum_p phi[x, p] a+_p c[k]`` for the particles of ``spin`` (0: alpha, 1:
+    beta) on ``qs_string_ci_ladder``: ``table`` (n_t, m) from ``string_ci_ladder_table`` decides which, ``phi`` is (m,) or
+    (d, m) and is not conjugated, ``c`` (na, nb) or (K, na, nb) lives on the source lists, ``n_alpha`` is the number of
+    alpha particles (the sign a beta ladder picks up).  The result has the leading axis of ``phi`` (if present), then that
+    of ``c`` (if present), then (n_t, nb) for alpha or (na, n_t) for beta.  No intermediate, no workspace.  The result is
+    complex if ``phi`` or ``c`` is; a real ``phi`` with a complex ``c`` stays real, a real ``c`` under a complex ``phi`` is
+    converted once.  Repeating a call gives the same bits."""
+    lib = _lib.load()
+    spin = int(spin)
+    if spin not in (0, 1):
+        raise ValueError(f"spin must be 0 (alpha) or 1 (beta), got {spin}")
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.int32 or table.dim() != 2 or table.shape[0] < 1:
+        raise ValueError("a ladder table must be an (n_t, m) int32 tensor (string_ci_ladder_table)")
+    if not isinstance(c, torch.Tensor) or c.dim() not in (2, 3):
+        raise ValueError("c must be (K, na, nb) or (na, nb)")
+    n_t, m = table.shape
+    hdt = result_dtype(phi)
+    dt = result_dtype(phi, c)
+    phi, table, c = _dev(phi, hdt), _dev(table), _dev(c, dt)
+    if phi.dim() not in (1, 2) or phi.shape[-1] != m or phi.shape[0] < 1:
+        raise ValueError(f"phi has shape {tuple(phi.shape)}: need ({m},) or (d, {m}) with d >= 1")
+    na, nb = c.shape[-2:]
+    K = 1 if c.dim() == 2 else c.shape[0]
+    d = 1 if phi.dim() == 1 else phi.shape[0]
+    if K < 1 or na < 1 or nb < 1:
+        raise ValueError(f"c has shape {tuple(c.shape)}: need (K, na, nb) with K, na, nb >= 1")
+    shape = tuple(phi.shape[:-1]) + tuple(c.shape[:-2]) + ((n_t, nb) if spin == 0 else (na, n_t))
+    if out is None:
+        out = torch.empty(shape, dtype=dt, device=c.device)
+    else:
+        _check_out(out, shape, dt, "string_ci_ladder")
+    with _on_device_of(phi, table, c, out):
+        _ran(
+            lib.qs_string_ci_ladder(dtype_code(hdt), dtype_code(dt), phi.data_ptr(), d, spin, table.data_ptr(), m, int(n_alpha), na, nb,
+                                    n_t, c.data_ptr(), K, out.data_ptr(), _stream()),
+            "qs_string_ci_ladder",
+        )
+    return out
+
+
+@_plain
 def transform_two_body_blocks(u, Ct0, Ct1, C2, C3, out=None):
     """``out[pqrs] = Ct0[pa] Ct1[qb] u[abcd] C2[cr] C3[ds]``: one coefficient matrix per index
     (``qs_transform_two_body_blocks``), contracted in the order a, b, d, c so that small blocks in front shrink the

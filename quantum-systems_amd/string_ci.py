@@ -45,9 +45,24 @@ response of a state to it a Lanczos recurrence on ``H`` from ``(A - <A>) c`` (``
     Sx, Sy = ci.dipole_spectrum(0)                    # one per spatial dimension: the dipole absorption lines
     a = ci.polarizability(0.0)                        # alpha_xx(omega) per dimension
 
+Removing or adding a particle is one gather through a ladder table between the string lists of two sectors
+(``kernels.string_ci_ladder``); the neighbouring sector shares the transformed integrals, and a Lanczos recurrence on its
+``H`` gives ionisation energies, affinities and the one-particle Green's function.  ``v`` holds coefficients in the orbitals
+``C``:
+
+    ion = ci.neighbour(d_up=-1)                       # the StringCI of (n_up - 1, n_down): no transform is repeated
+    phi = ci.annihilate(v, c, spin="up")              # sum_p v[p] a_p c on the lists of ion; ci.create(...) likewise
+    S = ci.removal_spectrum(v, k=0, n_steps=64)       # poles E_j(N - 1) - E_k(N), weights |<j| a(v) |Psi_k>|^2
+    A = ci.addition_spectrum(v)                       # poles E_j(N + 1) - E_k(N)
+    G = ci.green_function(omega, v, eta=0.05)         # retarded G_vv(omega)
+    ion.solve(4); g, orbitals = ci.dyson_orbitals(ion)   # g[j, p] = <Psi_j(ion)| a_p |Psi_0>, pole strengths sum_p |g|^2
+
 Out of scope here: full spin adaptation (``S = 0`` apart from ``S = 2``), a sharded ``u`` (refused in the constructor), the
-off-diagonal polarizability ``alpha_xy`` (it needs a block recurrence), and the same calls on ``DeterminantCI``.
+off-diagonal polarizability ``alpha_xy`` and the off-diagonal ``G_vw`` (they need a block recurrence), and the same calls on
+``DeterminantCI``.
 """
+
+import weakref
 
 import numpy
 import torch
@@ -135,9 +150,8 @@ class StringCI:
             raise TypeError("StringCI needs a SpatialOrbitalSystem")
         if is_sharded(system.u):
             raise NotImplementedError("StringCI does not take a sharded u: the string kernels are not sharded")
-        self.system = system
-        self.n_up = int(system.n if n_up is None else n_up)
-        self.n_down = int(system.n if n_down is None else n_down)
+        n_up = int(system.n if n_up is None else n_up)
+        n_down = int(system.n if n_down is None else n_down)
         with torch._C.DisableTorchFunctionSubclass():
             u = _plain(system.u)
             h, s = _plain(system.h), _plain(system.s)
@@ -151,35 +165,60 @@ class StringCI:
                 C = _plain(C)
                 if C.dim() != 2 or C.shape[0] != l:
                     raise ValueError(f"C must be (l, m) with l = {l}, got {tuple(C.shape)}")
-            self.m = m = int(C.shape[1])
-            self._sa_host = checked_strings(strings_up, m, self.n_up)
-            same = strings_down is strings_up and self.n_down == self.n_up
-            self._sb_host = self._sa_host if same else checked_strings(strings_down, m, self.n_down)
-            same = same or numpy.array_equal(self._sa_host, self._sb_host)
-            self.na, self.nb = int(self._sa_host.shape[0]), int(self._sb_host.shape[0])
-            self.dim = self.na * self.nb
-            if spin_parity is not None:
-                if spin_parity not in (1, -1):
-                    raise ValueError(f"spin_parity must be None, +1 or -1, got {spin_parity!r}")
-                if self.n_up != self.n_down or not same:
-                    raise ValueError("a spin parity needs n_up == n_down and the same string list for both spins")
-            self.spin_parity = None if spin_parity is None else int(spin_parity)
-            self._dt = torch.complex128 if (C.is_complex() or u.is_complex() or h.is_complex()) else torch.float64
-            self._C = C.to(self._dt).contiguous()
-            ht = _dagger(self._C) @ h.to(self._dt) @ self._C
-            self._ht = (0.5 * (ht + _dagger(ht))).contiguous()
-            self._ut = kernels.transform_two_body(u, self._C).to(self._dt).contiguous()     # a new tensor: system.u is left alone
-            self._k = (self._ht - 0.5 * torch.einsum("pqqr->pr", self._ut)).contiguous()
-            self._W = (0.5 * self._ut.permute(0, 2, 1, 3)).reshape(m * m, m * m).contiguous()  # the one permuted, scaled copy
+            m = int(C.shape[1])
+            sa_host = checked_strings(strings_up, m, n_up)
+            sb_host = sa_host if (strings_down is strings_up and n_down == n_up) else checked_strings(strings_down, m, n_down)
+            self._set_lists(n_up, n_down, sa_host, sb_host, spin_parity)
+            dt = torch.complex128 if (C.is_complex() or u.is_complex() or h.is_complex()) else torch.float64
+            C = C.to(dt).contiguous()
+            ht = _dagger(C) @ h.to(dt) @ C
+            ht = (0.5 * (ht + _dagger(ht))).contiguous()
+            ut = kernels.transform_two_body(u, C).to(dt).contiguous()                       # a new tensor: system.u is left alone
+            k = (ht - 0.5 * torch.einsum("pqqr->pr", ut)).contiguous()
+            W = (0.5 * ut.permute(0, 2, 1, 3)).reshape(m * m, m * m).contiguous()          # the one permuted, scaled copy
+        self._set_integrals(system, m, dt, C, ht, ut, k, W)
+        self._build()
+
+    # What a StringCI is made of, set in three steps that ``__init__`` and ``neighbour`` share: the sector and its host lists,
+    # the orbitals with the transformed integrals, and what is built from both on the device.
+
+    def _set_lists(self, n_up, n_down, sa_host, sb_host, spin_parity):
+        self.n_up, self.n_down = n_up, n_down
+        self._sa_host, self._sb_host = sa_host, sb_host
+        self._same = sb_host is sa_host or numpy.array_equal(sa_host, sb_host)
+        self.na, self.nb = int(sa_host.shape[0]), int(sb_host.shape[0])
+        self.dim = self.na * self.nb
+        if spin_parity is not None:
+            if spin_parity not in (1, -1):
+                raise ValueError(f"spin_parity must be None, +1 or -1, got {spin_parity!r}")
+            if n_up != n_down or not self._same:
+                raise ValueError("a spin parity needs n_up == n_down and the same string list for both spins")
+        self.spin_parity = None if spin_parity is None else int(spin_parity)
+
+    def _set_integrals(self, system, m, dt, C, ht, ut, k, W):
+        self.system, self.m, self._dt = system, m, dt
+        self._C, self._ht, self._ut, self._k, self._W = C, ht, ut, k, W
+
+    def _build(self, alpha=None, beta=None):
+        """The device lists, the replacement tables and the diagonal; ``alpha`` / ``beta`` = (device list, table) of that
+        spin where they exist already.  Ends with no state solved and empty caches."""
+        with torch._C.DisableTorchFunctionSubclass():
             dev = self._ut.device
-            self._sa = torch.from_numpy(self._sa_host).to(dev)
-            self._sb = self._sa if same else torch.from_numpy(self._sb_host).to(dev)
-            self._ta = kernels.string_ci_table(self._sa, m, self.n_up)
-            self._tb = self._ta if same else kernels.string_ci_table(self._sb, m, self.n_down)
+            if alpha is None:
+                sa = torch.from_numpy(self._sa_host).to(dev)
+                alpha = (sa, kernels.string_ci_table(sa, self.m, self.n_up))
+            if beta is None and self._same:
+                beta = alpha
+            if beta is None:
+                sb = torch.from_numpy(self._sb_host).to(dev)
+                beta = (sb, kernels.string_ci_table(sb, self.m, self.n_down))
+            (self._sa, self._ta), (self._sb, self._tb) = alpha, beta
             self._diag = kernels.string_ci_diagonal(self._ht, self._ut, self._sa, self.n_up, self._sb, self.n_down).reshape(-1)
         self.E = self.c = self._c = None
         self.converged, self.iterations, self.residuals = False, 0, None
         self.sigma_history = []              # trial vectors per Davidson iteration
+        self._neighbours = {}                # (d_up, d_down) -> the StringCI of that sector on all strings
+        self._ladders = {}                   # (id(other), spin, direction) -> (weak reference to other, ladder table)
 
     @property
     def strings_up(self):
@@ -461,6 +500,20 @@ class StringCI:
                 raise ValueError(f"A_down has shape {tuple(Ad.shape)}: need that of A, {tuple(At.shape)}")
             return kernels.string_ci_one_body(At, self._ta, self._tb, self.m, c, A_down=Ad)
 
+    def _reference(self, k, state):
+        """``(c, energy)`` a spectrum starts from: solved state ``k`` and ``E[k]`` without the nuclear repulsion, or the
+        given vector (na, nb), normalised, with ``Re <c|H c>`` from one ``sigma``."""
+        if state is None:
+            if self._c is None:
+                raise RuntimeError("call solve() first, or give state=")
+            return self._c[k], float(self.E[k]) - float(self.system.nuclear_repulsion_energy)
+        c = _plain(state)
+        if tuple(c.shape) != (self.na, self.nb):
+            raise ValueError(f"state has shape {tuple(c.shape)}: need ({self.na}, {self.nb})")
+        c = c.to(self._dt) if self._dt == torch.complex128 else c
+        c = (c / torch.linalg.vector_norm(c)).contiguous()
+        return c, float(torch.vdot(c.reshape(-1), self.sigma(c).to(c.dtype).reshape(-1)).real.item())
+
     def spectral_function(self, A, k=0, n_steps=64, A_down=None, reorthogonalize=False, beta_tol=0.0, state=None):
         """The ``response.SpectralFunction`` of ONE one-body operator ``A`` (l, l) on solved state ``k`` -- or, with
         ``state=``, on a given vector (na, nb), which is normalised here and whose energy is ``Re <c|H c>`` from one
@@ -471,18 +524,7 @@ class StringCI:
         with torch._C.DisableTorchFunctionSubclass():
             if _plain(A).dim() != 2 or (A_down is not None and _plain(A_down).dim() != 2):
                 raise ValueError("spectral_function takes ONE operator (l, l): a stack goes operator by operator")
-            if state is None:
-                if self._c is None:
-                    raise RuntimeError("call solve() first, or give state=")
-                c = self._c[k]
-                energy = float(self.E[k]) - float(self.system.nuclear_repulsion_energy)
-            else:
-                c = _plain(state)
-                if tuple(c.shape) != (self.na, self.nb):
-                    raise ValueError(f"state has shape {tuple(c.shape)}: need ({self.na}, {self.nb})")
-                c = c.to(self._dt) if self._dt == torch.complex128 else c
-                c = (c / torch.linalg.vector_norm(c)).contiguous()
-                energy = float(torch.vdot(c.reshape(-1), self.sigma(c).to(c.dtype).reshape(-1)).real.item())
+            c, energy = self._reference(k, state)
             Ac = self.apply_one_body(A, c, A_down)
             c = c.to(Ac.dtype)
             phi = Ac - torch.vdot(c.reshape(-1), Ac.reshape(-1)) * c
@@ -502,6 +544,141 @@ class StringCI:
         with torch._C.DisableTorchFunctionSubclass():
             value = torch.from_numpy(numpy.ascontiguousarray(value)).to(self._ta.device)
         return _deliver(value, self.system.np)
+
+    def neighbour(self, d_up=0, d_down=0, strings=None):
+        """The ``StringCI`` of ``(n_up + d_up, n_down + d_down)`` particles in the same orbitals, exactly one of the two
+        steps being +1 or -1.  It shares ``C``, ``ht``, ``ut``, ``k`` and ``W`` with this one (no transform is repeated) and
+        keeps the string list and the table of the unchanged spin; the changed spin takes ``strings`` (default: all).  It
+        has no spin parity.  Without ``strings`` it is built once per ``(d_up, d_down)``."""
+        d_up, d_down = int(d_up), int(d_down)
+        if sorted((abs(d_up), abs(d_down))) != [0, 1]:
+            raise ValueError(f"exactly one of d_up, d_down must be +1 or -1, got ({d_up}, {d_down})")
+        n_up, n_down = self.n_up + d_up, self.n_down + d_down
+        if not (0 <= n_up <= self.m and 0 <= n_down <= self.m):
+            raise ValueError(f"there is no sector of ({n_up}, {n_down}) particles in {self.m} orbitals")
+        if strings is None and (d_up, d_down) in self._neighbours:
+            return self._neighbours[(d_up, d_down)]
+        other = object.__new__(StringCI)
+        changed = checked_strings(strings, self.m, n_up if d_up else n_down)
+        other._set_lists(n_up, n_down, changed if d_up else self._sa_host, self._sb_host if d_up else changed, None)
+        other._set_integrals(self.system, self.m, self._dt, self._C, self._ht, self._ut, self._k, self._W)
+        other._build(alpha=None if d_up else (self._sa, self._ta), beta=(self._sb, self._tb) if d_up else None)
+        if strings is None:
+            self._neighbours[(d_up, d_down)] = other
+        return other
+
+    def _ladder_to(self, other, spin, step):
+        """``(other, spin index, table)`` of the ladder of ``spin`` from this sector to ``other`` (default: the neighbour),
+        which must hold ``step`` = +1 or -1 more particles of that spin, as many of the other spin, and that spin's list."""
+        if spin not in ("up", "down"):
+            raise ValueError(f"spin must be 'up' or 'down', got {spin!r}")
+        s = 0 if spin == "up" else 1
+        if other is None:
+            other = self.neighbour(d_up=step) if s == 0 else self.neighbour(d_down=step)
+        key = (id(other), s, step)
+        cached = self._ladders.get(key)
+        if cached is not None and cached[0]() is other:
+            return other, s, cached[1]
+        want = (self.n_up + (step if s == 0 else 0), self.n_down + (step if s == 1 else 0))
+        if not isinstance(other, StringCI) or other.m != self.m or (other.n_up, other.n_down) != want:
+            raise ValueError(f"other must be a StringCI of ({want[0]}, {want[1]}) particles in the same {self.m} orbitals")
+        kept = (self._sb_host, other._sb_host) if s == 0 else (self._sa_host, other._sa_host)
+        if not numpy.array_equal(*kept):
+            raise ValueError("other must have this sector's string list of the unchanged spin")
+        target, source = (other._sa, self._sa) if s == 0 else (other._sb, self._sb)
+        table = kernels.string_ci_ladder_table(target, source, self.m)
+        # a weak reference: the cache keeps no sector alive, and an id that a later object took over is seen and replaced
+        self._ladders = {k_: v_ for k_, v_ in self._ladders.items() if v_[0]() is not None}
+        self._ladders[key] = (weakref.ref(other), table)
+        return other, s, table
+
+    def _ladder(self, v, c, spin, other, step):
+        with torch._C.DisableTorchFunctionSubclass():
+            c = self._vectors_checked(c, "c")
+            other, s, table = self._ladder_to(other, spin, step)
+            v = _plain(v)
+            v = v.to(device=c.device, dtype=torch.complex128 if v.is_complex() else torch.float64)
+            if v.dim() not in (1, 2) or v.shape[-1] != self.m:
+                raise ValueError(f"v has shape {tuple(v.shape)}: need ({self.m},) or (d, {self.m}) coefficients in the orbitals C")
+            return kernels.string_ci_ladder(v, table, s, self.n_up, c), other
+
+    def annihilate(self, v, c, spin="up", other=None):
+        """``sum_p v[p] a_p,spin c_k`` for ``c`` (k, na, nb) or (na, nb), device tensor in and out
+        (``kernels.string_ci_ladder``): ``v`` (m,) or (d, m) holds coefficients in the orbitals ``C`` and is not conjugated;
+        the result lives on the string lists of ``other`` (default: ``neighbour`` with one particle of ``spin`` less) and
+        has the leading axis of ``v`` (if present), then that of ``c``."""
+        return self._ladder(v, c, spin, other, -1)[0]
+
+    def create(self, v, c, spin="up", other=None):
+        """``sum_p v[p] a+_p,spin c_k``, as ``annihilate``, on the lists of ``other`` (default: ``neighbour`` with one
+        particle of ``spin`` more)."""
+        return self._ladder(v, c, spin, other, +1)[0]
+
+    def _ladder_spectrum(self, step, v, spin, k, n_steps, state, reorthogonalize, beta_tol, other):
+        with torch._C.DisableTorchFunctionSubclass():
+            c, energy = self._reference(k, state)
+            phi, other = self._ladder(v, c, spin, other, step)
+            if phi.dim() != 2:
+                raise ValueError("a spectrum takes ONE combination v (m,): a stack goes row by row")
+            if other._dt == torch.complex128:
+                phi = phi.to(other._dt)
+            alpha, beta, norm2 = response.lanczos(other._sigma_rows, phi.reshape(1, other.dim), n_steps, reorthogonalize, beta_tol)
+        return response.SpectralFunction(alpha, beta, norm2, energy)
+
+    def removal_spectrum(self, v, spin="up", k=0, n_steps=64, state=None, reorthogonalize=False, beta_tol=0.0, other=None):
+        """The ``response.SpectralFunction`` of removing a particle of ``spin`` in the orbital ``sum_p v[p] C[:, p]`` from
+        solved state ``k`` (or from ``state=``, as in ``spectral_function``): ``n_steps`` of ``response.lanczos`` on the
+        ``H`` of ``other`` (default: the neighbour) from ``phi = a(v) c``, not mean-subtracted.  Poles are
+        ``E_j(N - 1) - E_k(N)``, the ionisation energies, weights ``|<j| a(v) |c>|^2``; ``phi = 0`` gives the empty
+        spectrum."""
+        return self._ladder_spectrum(-1, v, spin, k, n_steps, state, reorthogonalize, beta_tol, other)
+
+    def addition_spectrum(self, v, spin="up", k=0, n_steps=64, state=None, reorthogonalize=False, beta_tol=0.0, other=None):
+        """As ``removal_spectrum`` for ``phi = a+(v) c``: poles ``E_j(N + 1) - E_k(N)``, minus the electron affinities,
+        weights ``|<j| a+(v) |c>|^2``."""
+        return self._ladder_spectrum(+1, v, spin, k, n_steps, state, reorthogonalize, beta_tol, other)
+
+    def green_function(self, omega, v, spin="up", eta=0.0, k=0, n_steps=64, **kw):
+        """The retarded one-particle Green's function ``G_vv(omega)`` of solved state ``k``, the shape of ``omega``,
+        complex: ``sum_j w+_j / (omega - p+_j + i eta) + sum_j w-_j / (omega + p-_j + i eta)`` over the poles and weights of
+        ``addition_spectrum`` (+) and ``removal_spectrum`` (-); a sector that does not exist adds nothing (``kw``:
+        ``reorthogonalize``, ``beta_tol``, ``state``)."""
+        n = self.n_up if spin == "up" else self.n_down
+        z = numpy.asarray(omega, dtype=numpy.float64)[..., None] + 1j * float(eta)
+        value = numpy.zeros(z.shape[:-1], dtype=numpy.complex128)
+        if n < self.m:
+            S = self.addition_spectrum(v, spin, k, n_steps, **kw)
+            value = value + numpy.sum(S.weights / (z - S.poles), axis=-1)
+        if n > 0:
+            S = self.removal_spectrum(v, spin, k, n_steps, **kw)
+            value = value + numpy.sum(S.weights / (z + S.poles), axis=-1)
+        with torch._C.DisableTorchFunctionSubclass():
+            value = torch.as_tensor(numpy.asarray(value, dtype=numpy.complex128)).to(self._ta.device)
+        return _deliver(value, self.system.np)
+
+    def dyson_orbitals(self, other, k=0, spin="up"):
+        """``(g, C @ g.T)`` between solved state ``k`` and every solved state of the neighbour ``other``:
+        ``g[j, p] = <Psi_j(other)| a_p,spin |Psi_k>`` where ``other`` has one particle of ``spin`` less,
+        ``<Psi_j(other)| a+_p,spin |Psi_k>`` where it has one more -- one ladder call with the m unit vectors and one
+        product --, and the same amplitudes in the system's basis, one column per state of ``other``.  The pole strength of
+        state j is ``sum_p |g[j, p]|^2``."""
+        if not isinstance(other, StringCI):
+            raise ValueError("other must be a StringCI of a neighbouring sector")
+        if self._c is None:
+            raise RuntimeError("call solve() first")
+        if other._c is None:
+            raise ValueError("other has no states yet: call other.solve() first")
+        step = (other.n_up - self.n_up) if spin == "up" else (other.n_down - self.n_down)
+        if step not in (1, -1):
+            raise ValueError(f"other must hold one particle of spin {spin!r} more or less than this sector")
+        with torch._C.DisableTorchFunctionSubclass():
+            unit = torch.eye(self.m, dtype=torch.float64, device=self._c.device)
+            X, _ = self._ladder(unit, self._c[k], spin, other, step)               # (m, na_t, nb_t)
+            bra = other._c.reshape(other._c.shape[0], other.dim)
+            dt = torch.complex128 if (bra.is_complex() or X.is_complex()) else torch.float64
+            g = (bra.to(dt).conj() @ X.reshape(self.m, other.dim).to(dt).transpose(0, 1)).contiguous()
+            orbitals = (self._C.to(dt) @ g.transpose(0, 1)).contiguous()
+        return _deliver(g, self.system.np), _deliver(orbitals, self.system.np)
 
     def natural_orbitals(self, k=0):
         """``(n, C_nat)`` of solved state ``k``: the occupations ``n`` (descending eigenvalues of the Hermitian part of
