@@ -23,6 +23,8 @@ typedef double f64x2 __attribute__((ext_vector_type(2)));
 // anti-symmetrisation: 5.41 -> 5.77 TB/s at l = 256; the spin expansion, whose lanes fill a line from
 // several instructions, LOSES 4 % with it and keeps plain stores).
 template <typename T> __device__ __forceinline__ void stream_store(T* p, T v) { __builtin_nontemporal_store(v, p); }
+// Load of what this launch reads once (the exchange check and mirrors at l = 256: 4-5 % faster than plain loads).
+template <typename T> __device__ __forceinline__ T stream_load(const T* p) { return __builtin_nontemporal_load(p); }
 #ifndef QS_SPIN_NT
 #define QS_SPIN_NT 0          // non-temporal stores in the spin-expansion / two-body S^2 kernels (A/B switch, profiles/r03_*)
 #endif
@@ -47,14 +49,15 @@ __device__ __forceinline__ void tile_pair(int idx, int nt, int& ti, int& tj) {
     ti = i; tj = i + idx;
 }
 
-// Load a PT x PT tile of the l x l matrix `m` (row r0.., col c0..) into LDS.
-template <typename T>
+// Load a PT x PT tile of the l x l matrix `m` (row r0.., col c0..) into LDS; STREAM: with non-temporal loads.
+template <typename T, bool STREAM = false>
 __device__ __forceinline__ void load_tile(T (*t)[PS], const T* m, int l, int r0, int c0) {
     const int tx = threadIdx.x & (PT - 1), ty = threadIdx.x / PT;   // 256 threads: ty in 0..7
 #pragma unroll
     for (int rr = ty; rr < PT; rr += 8) {
         const int r = r0 + rr, c = c0 + tx;
-        t[rr][tx] = (r < l && c < l) ? m[(int64_t)r * l + c] : zero_of<T>();
+        const T* p = &m[(int64_t)r * l + c];
+        t[rr][tx] = (r < l && c < l) ? (STREAM ? stream_load(p) : *p) : zero_of<T>();
     }
 }
 
@@ -257,10 +260,12 @@ __device__ __forceinline__ bool same_bits(f64x2 x, f64x2 y) { return same_bits(x
 // *flag |= 1 iff some u[a,b,c,d] differs BITWISE from u[b,a,d,c] (-0.0 against +0.0 differs, equal NaNs do not).  A
 // workgroup takes one pair a <= b and one 32 x 32 tile (ti, tj) of u[a,b] together with tile (tj, ti) of u[b,a]; on the
 // diagonal a == b that is the test that u[a,a] is a symmetric matrix.  It looks at the flag first: once a difference
-// is known, the rest of the grid costs no memory traffic.
+// is known, the rest of the grid costs no memory traffic.  Only the tile of u[b,a] is turned in LDS: a thread compares
+// the four elements of u[a,b] that it loaded itself, from its registers.  Nothing here is read twice: the loads are
+// non-temporal.  (l = 256 fp64, same call: both tiles through LDS 6.78 ms, this 5.41, with non-temporal loads 5.15 =
+// 6.7 TB/s; profiles/exchange_overlap_ab.txt.)
 template <typename T>
 __global__ __launch_bounds__(256) void exchange_transpose_check_kernel(const T* __restrict__ u, int* flag, int l, int nt) {
-    __shared__ T t1[PT][PS];
     __shared__ T t2[PT][PS];
     if (__atomic_load_n(flag, __ATOMIC_RELAXED)) return;
     const int ntiles = nt * nt;
@@ -270,19 +275,26 @@ __global__ __launch_bounds__(256) void exchange_transpose_check_kernel(const T* 
     const int64_t a = triangle_row((uint32_t)pair, (uint32_t)l);
     const int64_t b = a + (pair - (a * l - a * (a - 1) / 2));
     const int64_t ll = (int64_t)l * l;
-    load_tile(t1, u + (a * l + b) * ll, l, ti * PT, tj * PT);
-    load_tile(t2, u + (b * l + a) * ll, l, tj * PT, ti * PT);
-    __syncthreads();
+    const T* uab = u + (a * l + b) * ll;
     const int tx = threadIdx.x & (PT - 1), ty = threadIdx.x / PT;
+    T mine[PT / 8];
+#pragma unroll
+    for (int j = 0; j < PT / 8; ++j) {
+        const int r = ti * PT + ty + 8 * j, c = tj * PT + tx;
+        mine[j] = (r < l && c < l) ? stream_load(&uab[(int64_t)r * l + c]) : zero_of<T>();
+    }
+    load_tile<T, true>(t2, u + (b * l + a) * ll, l, tj * PT, ti * PT);
+    __syncthreads();
     bool same = true;
 #pragma unroll
-    for (int rr = ty; rr < PT; rr += 8) same = same && same_bits(t1[rr][tx], t2[tx][rr]);   // (both zero past the edge)
+    for (int j = 0; j < PT / 8; ++j) same = same && same_bits(mine[j], t2[tx][ty + 8 * j]);   // (both zero past the edge)
     if (!same) *flag = 1;
 }
 
 // In place on t (n, n, m, m):  t[a,b,r,s] = t[b,a,s,r]  for every pair with a / block > b / block; nothing else is
 // written.  A workgroup takes one such pair and one 32 x 32 tile (ti, tj) of t[a,b]: it reads tile (tj, ti) of t[b,a]
 // by rows, turns it in LDS and writes whole rows of 32 elements (two 128-byte lines of fp64 where m is a multiple of 16).
+// Non-temporal loads as well as stores (l = 256 fp64, same call: block 1 6.25 -> 5.93 ms, block 64 4.57 -> 4.33).
 template <typename T>
 __global__ __launch_bounds__(256) void exchange_transpose_kernel(T* t, int n, int m, int nt, int block) {
     __shared__ T t1[PT][PS];
@@ -299,7 +311,7 @@ __global__ __launch_bounds__(256) void exchange_transpose_kernel(T* t, int n, in
     const int64_t rem = pair - bb * (A * (A - 1) / 2), row_len = A * block;
     const int64_t a = A * block + rem / row_len, b = rem % row_len;
     const int64_t mm = (int64_t)m * m;
-    load_tile(t1, (const T*)t + (b * n + a) * mm, m, tj * PT, ti * PT);
+    load_tile<T, true>(t1, (const T*)t + (b * n + a) * mm, m, tj * PT, ti * PT);
     __syncthreads();
     T* o = t + (a * n + b) * mm;
     const int tx = threadIdx.x & (PT - 1), ty = threadIdx.x / PT;
