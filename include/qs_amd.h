@@ -95,6 +95,26 @@ int qs_matmul_pairs(int dtype, const void* A, const void* B, void* out,
                     int64_t stride_c, int accumulate, void* stream);
 
 /*
+ * ... which ALSO stores every entry (i, j > i) transposed at the flat index of
+ * (j, i): element (r, c) of the pair's m x m result at
+ *   out + (j * grid_n + i) * stride_c + c * ldc + r.
+ * Entries (i, i) are stored once.  The transposes come out of the registers
+ * that hold the result, so they are its bits.  Requires m == n and
+ * accumulate == 0, and a product that the dispatch puts on a kernel with this
+ * epilogue -- today float64 on the exact 128 x 128 form: m and n multiples of
+ * 128, k a multiple of 16, under the calling thread's tuning keys; anything
+ * else is refused with QS_ERR_BAD_EXTENT before a launch (no fallback).  The
+ * dispatch record names the launch
+ * "qs::gemm_fast_kernel<...>(qs::FastPairsMirrorArgs)".  (An addition: the ABI
+ * version stays 4.)
+ */
+int qs_matmul_pairs_mirrored(int dtype, const void* A, const void* B, void* out,
+                             int64_t m, int64_t n, int64_t k,
+                             int64_t lda, int64_t ldb, int64_t ldc,
+                             int64_t grid_n, int64_t stride_a, int64_t stride_b,
+                             int64_t stride_c, int accumulate, void* stream);
+
+/*
  * Host only: pair number t (0 <= t < n (n + 1) / 2) of that order -> (*i, *j),
  * by the same remap the kernels use.  QS_ERR_BAD_EXTENT for n <= 0 or t out
  * of range.
@@ -158,7 +178,11 @@ int qs_transform_two_body_inplace(int dtype, void* u, const void* C,
  * on the pairs b >= a only, the last product on q >= the block of p, and a
  * byte-moving mirror writes the other half -- about 2.9 products' worth of
  * matrix work instead of 4.  The symmetry has no conjugation in it and Ct may
- * be any matrix.  (No ABI version change: these are additions.)
+ * be any matrix.  (No ABI version change: these are additions.)  Where the
+ * tuning key "exchange_order" (below) says so, the leading indices are
+ * contracted first instead: a on all of u, the b product on q >= the block of
+ * p, d and c on the pairs q >= p -- the same matrix work, and one mirror, of
+ * the result, where the other order has one of an intermediate as well.
  *
  *   qs_two_body_exchange_symmetric: 1 if u (L,L,L,L) has the symmetry, 0 if
  *     not, negative QS_ERR_* on error.  Bit patterns are compared: -0.0 against
@@ -551,7 +575,14 @@ const char* qs_last_dispatch(void);
  *     closing product and mirror / of its d contraction, 0 = automatic),
  *     "exchange_pairs" (1 = that route's c contraction, and its d contraction
  *     where that pads no more, as one qs_matmul_pairs launch; 0 = one launch
- *     per row / per block of rows, the same bits).
+ *     per row / per block of rows, the same bits),
+ *     "exchange_order" (that route's order of the contractions: 0 = d and c
+ *     on the pairs b >= a of u, a mirror, a, the closing blocks, a mirror;
+ *     2 = a, the closing blocks, d and c on the pairs q >= p of the result's
+ *     grid, one mirror; 1, the default = 2 where M >= L and L is at least the
+ *     smallest size measured to gain, never below the route's own thresholds,
+ *     else 0.  The two orders agree to rounding, not bit for bit; a value
+ *     outside 0 ... 2 is refused with QS_ERR_BAD_EXTENT).
  *   qs_probe_mfma_f64: register-resident fp64 MFMA loop, `blocks` workgroups
  *     of 4 waves, each wave issuing iters*8 v_mfma_f64_16x16x4_f64
  *     (flops = blocks*4*iters*8*2048); `sink` is a device scratch of

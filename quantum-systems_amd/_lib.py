@@ -27,6 +27,7 @@ SIGNATURES = {
     "qs_last_hip_error": (ctypes.c_char_p, []),
     "qs_matmul": (c_int, [c_int, c_ptr, c_ptr, c_ptr] + [c_i64] * 10 + [c_int, c_ptr]),
     "qs_matmul_pairs": (c_int, [c_int, c_ptr, c_ptr, c_ptr] + [c_i64] * 10 + [c_int, c_ptr]),
+    "qs_matmul_pairs_mirrored": (c_int, [c_int, c_ptr, c_ptr, c_ptr] + [c_i64] * 10 + [c_int, c_ptr]),
     "qs_triangle_pair": (c_int, [c_i64, c_i64, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
     "qs_transform_two_body_workspace": (c_i64, [c_int, c_i64, c_i64]),
     "qs_transform_two_body": (

@@ -265,6 +265,11 @@ int qs_tuning_set(const char* key, int64_t value) {
         g_tune.exchange_pairs = (int)value;
         return QS_OK;
     }
+    if (!strcmp(key, "exchange_order")) {
+        if (value < 0 || value > 2) return QS_ERR_BAD_EXTENT;
+        g_tune.exchange_order = (int)value;
+        return QS_OK;
+    }
     if (!strcmp(key, "mean_field_batch_g")) {
         if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8) return QS_ERR_BAD_EXTENT;
         g_tune.mean_field_batch_g = (int)value;
@@ -307,9 +312,9 @@ int qs_matmul(int dtype, const void* A, const void* B, void* out, int64_t m, int
                 (hipStream_t)stream);
 }
 
-int qs_matmul_pairs(int dtype, const void* A, const void* B, void* out, int64_t m, int64_t n, int64_t k,
-                    int64_t lda, int64_t ldb, int64_t ldc, int64_t grid_n, int64_t stride_a,
-                    int64_t stride_b, int64_t stride_c, int accumulate, void* stream) {
+static int matmul_pairs(int dtype, const void* A, const void* B, void* out, int64_t m, int64_t n, int64_t k,
+                        int64_t lda, int64_t ldb, int64_t ldc, int64_t grid_n, int64_t stride_a,
+                        int64_t stride_b, int64_t stride_c, int accumulate, void* stream, bool mirror) {
     dispatch_reset();
     if (!dtype_ok(dtype)) return QS_ERR_BAD_DTYPE;
     if (!A || !B || !out) return QS_ERR_NULL_POINTER;
@@ -318,8 +323,20 @@ int qs_matmul_pairs(int dtype, const void* A, const void* B, void* out, int64_t 
     if (stride_a < 0 || stride_b < 0 || stride_c < 0) return QS_ERR_BAD_EXTENT;
     if (grid_n <= 0 || grid_n > kTriangleMax) return QS_ERR_BAD_EXTENT;
     return gemm(Product{dtype, (const double*)A, (const double*)B, (double*)out, m, n, k, lda, ldb, ldc,
-                        grid_n * (grid_n + 1) / 2, stride_a, stride_b, stride_c, accumulate, grid_n},
+                        grid_n * (grid_n + 1) / 2, stride_a, stride_b, stride_c, accumulate, grid_n, mirror},
                 (hipStream_t)stream);
+}
+
+int qs_matmul_pairs(int dtype, const void* A, const void* B, void* out, int64_t m, int64_t n, int64_t k,
+                    int64_t lda, int64_t ldb, int64_t ldc, int64_t grid_n, int64_t stride_a,
+                    int64_t stride_b, int64_t stride_c, int accumulate, void* stream) {
+    return matmul_pairs(dtype, A, B, out, m, n, k, lda, ldb, ldc, grid_n, stride_a, stride_b, stride_c, accumulate, stream, false);
+}
+
+int qs_matmul_pairs_mirrored(int dtype, const void* A, const void* B, void* out, int64_t m, int64_t n, int64_t k,
+                             int64_t lda, int64_t ldb, int64_t ldc, int64_t grid_n, int64_t stride_a,
+                             int64_t stride_b, int64_t stride_c, int accumulate, void* stream) {
+    return matmul_pairs(dtype, A, B, out, m, n, k, lda, ldb, ldc, grid_n, stride_a, stride_b, stride_c, accumulate, stream, true);
 }
 
 int qs_triangle_pair(int64_t n, int64_t t, int64_t* i, int64_t* j) {
@@ -467,6 +484,15 @@ static int transform_two_body_fused(int in_dtype, int dtype, const void* u, cons
 //   a:  X[p, (b r s)]          = Ct[p, a] T2[a, (b r s)]             one product
 //   b:  out[p][q >= p0, (r s)] = Ct[q >= p0, b] X[p][b, (r s)]       per block [p0, p1) of rows p, batched over p; then the mirror
 // T1 (L, L, L, M), T2 (L, L, M, M), X (M, L, M, M); T1 and X may share storage, so may T2 and out.
+// The other order contracts the leading indices first (u arrives complete, so nothing between the products needs its
+// other half: X2[p,q,c,d] == X2[q,p,d,c] for any Ct, and each pair-wise step needs its own pair alone):
+//   a:  X1[p, (b c d)]         = Ct[p, a] u[a, (b c d)]              one product
+//   b:  X2[p][q >= p0, (c d)]  = Ct[q >= p0, b] X1[p][b, (c d)]      per block [p0, p1) of rows p, batched over p
+//   d:  Y[p, q][c, s]          = X2[p, q][c, d] C[d, s]              over the pairs q >= p of the M x M grid
+//   c:  out[p, q][r, s]        = CT[r, c] Y[p, q][c, s]              over the same pairs; then ONE mirror, q < p -- stored
+//                                                                    by the c launch itself where its kernel can (gemm_mirrors)
+// X1 (M, L, L, L), X2 (M, M, L, L), Y (M, M, L, M): the same flops (1 + 0.625 + 0.502 + 0.502 of a product at L == M), at
+// L == M the very launches of the first order, and one mirror (of out, over all pairs) instead of two.
 
 // smallest basis (both sizes) that takes the route by itself: the smallest measured size where it is >= 5 % faster than the plain
 // route (profiles/exchange_pairs_ab.txt, plain / route: fp64 160 1.036, 192 1.179; complex128 160 1.258)
@@ -478,6 +504,24 @@ static bool exchange_wanted(int dtype, int64_t L, int64_t M) {
     return (L < M ? L : M) >= (dtype == QS_C128 ? kExchangeMinC128 : kExchangeMin);
 }
 
+// g_tune.exchange_order: which of the two orders above a call takes (0 the first, 2 the second).
+// 1, the automatic rule: the leading indices first only where M >= L (for M < L the half the symmetry saves falls on the
+// larger products in the other order) and from the smallest size measured to gain (profiles/exchange_order_ab.txt),
+// never below the route's own thresholds.
+static constexpr int64_t kExchangeOrderMin = 192, kExchangeOrderMinC128 = 160;
+
+// (-DQS_EXCHANGE_FUSED_MIRROR=0 builds the route with the separate mirror everywhere: the A/B baseline)
+#ifndef QS_EXCHANGE_FUSED_MIRROR
+#define QS_EXCHANGE_FUSED_MIRROR 1
+#endif
+
+static bool exchange_leading_first(int dtype, int64_t L, int64_t M) {
+    if (g_tune.exchange_order != 1) return g_tune.exchange_order == 2;
+    return M >= L && L >= (dtype == QS_C128 ? kExchangeOrderMinC128 : kExchangeOrderMin);
+}
+
+// T1, T2, X: the three buffers of the comment above.  The a, b, d, c order keeps X1 where X goes, X2 where T2 goes and Y
+// where T1 goes; in either order every product reads one of the two storages and writes the other.
 static int transform_two_body_exchange_route(int dtype, const void* u, const void* C, const void* Ct, void* CT, void* T1,
                                              void* T2, void* X, void* out, int64_t L, int64_t M, hipStream_t s) {
     const size_t es = elem_size(dtype);
@@ -490,55 +534,77 @@ static int transform_two_body_exchange_route(int dtype, const void* u, const voi
     auto mat = [&](void* base, int64_t elems) { return (double*)at(base, elems, es); };
     int rc = transpose_small(dtype, C, CT, L, M, s);
     if (rc) return rc;
-    // d and c are one product per pair (a, b >= a) on operands that are contiguous in the flat pair index a L + b: a
-    // triangular batch (Product::pairs) runs each as ONE launch on exactly the L (L + 1) / 2 pairs.  For c that is the
+    // The trailing indices, on the pairs j >= i of a G x G grid of (L, L) matrices (G = L on u, G = M on X2):
+    //   mid[i, j][c, s] = src[i, j][c, d] C[d, s],   dst[i, j][r, s] = CT[r, c] mid[i, j][c, s]
+    // d and c are one product per pair on operands that are contiguous in the flat pair index i G + j: a
+    // triangular batch (Product::pairs) runs each as ONE launch on exactly the G (G + 1) / 2 pairs.  For c that is the
     // per-row launches' tile list in one grid.  For d it pads the L rows of EVERY pair to whole tiles where the blocks'
-    // flat (L - a0) L rows pad once, so the dispatch's own estimates of the two forms decide (at L a multiple of 128
+    // flat (G - i0) L rows pad once, so the dispatch's own estimates of the two forms decide (at L a multiple of 128
     // neither pads: the single launch, 0.502 of a product where the blocks compute 0.53).
     // g_tune.exchange_pairs == 0: the launches per block and per row.  Same bits: for c the same kernel on the same tiles;
-    // for d the tiles differ where L is no whole number of them (L rows per pair against (L - a0) L flat rows), possibly
+    // for d the tiles differ where L is no whole number of them (L rows per pair against (G - i0) L flat rows), possibly
     // the instantiation too, and the bits agree because every tiled form sums along k in the same order.
-    const int64_t npairs = L * (L + 1) / 2;
-    auto d_block = [&](int64_t a0) {
-        const int64_t rows = (a0 + blk_d < L ? a0 + blk_d : L) - a0;
-        return Product{dtype, cat(u, a0 * L * L * L + a0 * L * L), (const double*)C, mat(T1, a0 * L * L * M + a0 * L * M),
-                       (L - a0) * L, M, L, L, M, M, rows, L * L * L, 0, L * L * M, 0};
+    // (A block of rows i computes the pairs j >= i0: for j < i that is work nobody reads -- on X2, whose closing blocks
+    // need not line up with these, possibly from storage nothing has written; a row of a product depends on its own row of
+    // the operand alone.)
+    // `mirrored` (null: not wanted): dst is the result and its other half is wanted too -- where the dispatch can, the c
+    // launch stores it from its own registers (Product::mirror) and *mirrored says so; otherwise the caller launches the
+    // mirror.
+    auto trailing = [&](const void* src, void* mid, void* dst, int64_t G, bool* mirrored) -> int {
+        const int64_t npairs = G * (G + 1) / 2, LL = L * L, LM = L * M;
+        auto d_block = [&](int64_t i0) {
+            const int64_t rows = (i0 + blk_d < G ? i0 + blk_d : G) - i0;
+            return Product{dtype, cat(src, (i0 * G + i0) * LL), (const double*)C, mat(mid, (i0 * G + i0) * LM),
+                           (G - i0) * L, M, L, L, M, M, rows, G * LL, 0, G * LM, 0};
+        };
+        const Product d_pairs{dtype, (const double*)src, (const double*)C, (double*)mid, L, M, L, L, M, M, npairs, LL, 0, LM, 0, G};
+        bool d_single = g_tune.exchange_pairs != 0;
+        if (d_single) {
+            double blocks_cost = 0.0;
+            for (int64_t i0 = 0; i0 < G; i0 += blk_d) blocks_cost += gemm_cost(d_block(i0));
+            d_single = gemm_cost(d_pairs) <= blocks_cost;
+        }
+        if (d_single) {
+            if (int rc = gemm(d_pairs, s)) return rc;
+        } else {
+            for (int64_t i0 = 0; i0 < G; i0 += blk_d)
+                if (int rc = gemm(d_block(i0), s)) return rc;
+        }
+        if (g_tune.exchange_pairs) {
+            Product c{dtype, (const double*)CT, (const double*)mid, (double*)dst, M, M, L, L, M, M, npairs, 0, LM, MM, 0, G};
+            if (mirrored) c.mirror = *mirrored = QS_EXCHANGE_FUSED_MIRROR && gemm_mirrors(c);
+            return gemm(c, s);
+        }
+        for (int64_t i = 0; i < G; ++i)
+            if (int rc = gemm(packed(dtype, CT, cat(mid, (i * G + i) * LM), mat(dst, (i * G + i) * MM), M, M, L, G - i), s)) return rc;
+        return QS_OK;
     };
-    const Product d_pairs{dtype, (const double*)u, (const double*)C, (double*)T1, L, M, L, L, M, M, npairs, L * L, 0, L * M, 0, L};
-    bool d_single = g_tune.exchange_pairs != 0;
-    if (d_single) {
-        double blocks_cost = 0.0;
-        for (int64_t a0 = 0; a0 < L; a0 += blk_d) blocks_cost += gemm_cost(d_block(a0));
-        d_single = gemm_cost(d_pairs) <= blocks_cost;
-    }
-    if (d_single) {
-        rc = gemm(d_pairs, s);
-        if (rc) return rc;
-    } else {
-        for (int64_t a0 = 0; a0 < L; a0 += blk_d) {
-            rc = gemm(d_block(a0), s);
-            if (rc) return rc;
+    // The leading indices, on matrices of W elements (W = M M on T2, W = L L on u):
+    //   mid[p, (b w)] = Ct[p, a] src[a, (b w)],   dst[p][q >= p0, w] = Ct[q >= p0, b] mid[p][b, w]  per block [p0, p1) of rows p
+    auto leading = [&](const void* src, void* mid, void* dst, int64_t W) -> int {
+        if (int rc = gemm(packed(dtype, Ct, src, mid, M, L * W, L), s)) return rc;
+        for (int64_t p0 = 0; p0 < M; p0 += blk) {
+            const int64_t rows = (p0 + blk < M ? p0 + blk : M) - p0;
+            if (int rc = gemm(Product{dtype, cat(Ct, p0 * L), cat(mid, p0 * L * W), mat(dst, (p0 * M + p0) * W),
+                                      M - p0, W, L, L, W, W, rows, 0, L * W, M * W, 0}, s))
+                return rc;
         }
-    }
-    if (g_tune.exchange_pairs) {
-        rc = gemm(Product{dtype, (const double*)CT, (const double*)T1, (double*)T2, M, M, L, L, M, M, npairs, 0, L * M, MM, 0, L}, s);
+        return QS_OK;
+    };
+    if (exchange_leading_first(dtype, L, M)) {
+        rc = leading(u, /*X1*/ X, /*X2*/ T2, L * L);
         if (rc) return rc;
-    } else {
-        for (int64_t a = 0; a < L; ++a) {
-            rc = gemm(packed(dtype, CT, cat(T1, (a * L + a) * L * M), mat(T2, (a * L + a) * MM), M, M, L, L - a), s);
-            if (rc) return rc;
-        }
+        bool mirrored = false;
+        rc = trailing(/*X2*/ T2, /*Y*/ T1, out, M, &mirrored);
+        if (rc || mirrored) return rc;
+        return exchange_mirror(dtype, out, M, M, 1, s);
     }
+    rc = trailing(u, T1, T2, L, nullptr);
+    if (rc) return rc;
     rc = exchange_mirror(dtype, T2, L, M, 1, s);
     if (rc) return rc;
-    rc = gemm(packed(dtype, Ct, T2, X, M, L * MM, L), s);
+    rc = leading(T2, X, out, MM);
     if (rc) return rc;
-    for (int64_t p0 = 0; p0 < M; p0 += blk) {
-        const int64_t rows = (p0 + blk < M ? p0 + blk : M) - p0;
-        rc = gemm(Product{dtype, cat(Ct, p0 * L), cat(X, p0 * L * MM), mat(out, p0 * M * MM + p0 * MM),
-                          M - p0, MM, L, L, MM, MM, rows, 0, L * MM, M * MM, 0}, s);
-        if (rc) return rc;
-    }
     return exchange_mirror(dtype, out, M, M, blk, s);
 }
 

@@ -95,6 +95,9 @@ struct Product {
     // row-major order, with its operands at the pair's FLAT index f = i n + j (qs_triangle.h): A + f sa, B + f sb,
     // C + f sc.  0 = a plain batch, entry t at t.
     int64_t pairs = 0;
+    // ... whose entry (i, j > i) is ALSO stored transposed at entry (j, i): element (r, c) at C + (j n + i) sc + c ldc + r.  Needs
+    // pairs, m == n and no accumulate; entries (i, i) are stored once.  Only where gemm_mirrors() says yes.
+    bool mirror = false;
     // which operand is the stream that neighbouring tiles should share in L2: a shared (stride-0) A, or a short-and-wide
     // product, streams B (the tiled kernels walk the tiles of one B panel first)
     int group_along_m() const { return ((sa == 0 && batch > 1) || m < n) ? 1 : 0; }
@@ -107,6 +110,11 @@ inline Product packed(int dtype, const void* A, const void* B, void* C, int64_t 
 
 // Validates the extents and strides, then launches the product on the first route that takes it (qs_gemm.hip).
 int gemm(const Product& p, hipStream_t stream);
+
+// Can gemm() honour Product::mirror for this product (read with the flag set or not) under the calling thread's tuning
+// keys?  Only the exact fp64 128 x 128 form of qs_gemm_fast.hip has the mirrored epilogue; gemm() refuses a mirrored product
+// that fails this with QS_ERR_BAD_EXTENT and launches nothing.
+bool gemm_mirrors(const Product& p);
 
 // The dispatch's own estimate of a product's time on its tiled kernels (the smaller of the general kernel's best shape
 // and qs_gemm_fast.hip's best form, in the latter's units: rounds of the tile list x tile area / relative rate).  For a
@@ -128,6 +136,8 @@ int gemm_d(int in_dtype, int dtype, const void* u, const void* C, void* T1, int6
 // VALU-free fast path, exact and edge forms (qs_gemm_fast.hip).  general_cost: the general kernel's estimated time for
 // this product (its best shape, in this kernel's units): the edge form runs when its own estimate is not worse.
 int gemm_fast_try(const Product& p, double general_cost, hipStream_t stream);
+// ... and whether that would be the form with the mirrored epilogue (Product::mirror)
+bool gemm_fast_mirrors(const Product& p);
 
 // Small-coefficient streaming product, m, k <= 64 (qs_gemm_stream.hip).
 int gemm_stream_try(const Product& p, hipStream_t stream);
@@ -258,6 +268,9 @@ struct Tuning {
     int exchange_pairs = 1;      // that route's c contraction (and d, where it pads no more) as ONE product over the pairs b >= a (Product::pairs):
                                  // 0 = one launch per row a / per block of exchange_block_d rows (the A/B baseline.  Same bits: c runs the same
                                  // kernel on the same tiles; d may tile differently, and every tiled form sums along k in the same order)
+    int exchange_order = 1;      // that route's order of the contractions: 0 = the trailing indices first (d, c on the pairs of u, mirror, a, closing
+                                 // blocks, mirror), 2 = the leading ones first (a, closing blocks, d, c on the pairs of the result's grid, ONE
+                                 // mirror), 1 = the second where M >= L from the smallest size measured to gain, else the first
     int sandwich = 1;            // 4-wide fused passes of a small-basis transform: 0 off, 1 both (d, c) and (b, a), 2 (d, c) only, 3 (b, a) only;
                                  // tuning runs, wherever the kernel exists (not only where it measured faster): 4 both, 5 (d, c) only, 6 (b, a) only
 };

@@ -513,13 +513,25 @@ double gemm_cost(const Product& p) {
     return std::min(in_fast_units(p, cost), gemm_fast_estimate(p, even_layout(p, vec)));
 }
 
+// The extents and strides gemm() accepts.
+static bool product_ok(const Product& p) {
+    if (p.m <= 0 || p.n <= 0 || p.k <= 0 || p.batch <= 0) return false;
+    if (p.m > INT32_MAX || p.n > INT32_MAX || p.k > INT32_MAX) return false;
+    if (p.lda < p.k || p.ldb < p.n || p.ldc < p.n) return false;
+    // a triangular batch names every pair of its grid exactly once
+    return p.pairs >= 0 && p.pairs <= kTriangleMax && (!p.pairs || p.batch == p.pairs * (p.pairs + 1) / 2);
+}
+
+// (a forced shape of the general kernel skips the fast kernel; the skinny, stream and strip families refuse every
+// triangular batch, so a product that passes here reaches gemm_fast_try and its exact 128 x 128 form)
+bool gemm_mirrors(const Product& p) {
+    return dtype_ok(p.dtype) && product_ok(p) && g_tune.gemm_f64_cfg == 0 && gemm_fast_mirrors(p);
+}
+
 int gemm(const Product& p, hipStream_t stream) {
     if (!dtype_ok(p.dtype)) return QS_ERR_BAD_DTYPE;
-    if (p.m <= 0 || p.n <= 0 || p.k <= 0 || p.batch <= 0) return QS_ERR_BAD_EXTENT;
-    if (p.m > INT32_MAX || p.n > INT32_MAX || p.k > INT32_MAX) return QS_ERR_BAD_EXTENT;
-    if (p.lda < p.k || p.ldb < p.n || p.ldc < p.n) return QS_ERR_BAD_EXTENT;
-    // a triangular batch names every pair of its grid exactly once
-    if (p.pairs < 0 || p.pairs > kTriangleMax || (p.pairs && p.batch != p.pairs * (p.pairs + 1) / 2)) return QS_ERR_BAD_EXTENT;
+    if (!product_ok(p)) return QS_ERR_BAD_EXTENT;
+    if (p.mirror && !gemm_mirrors(p)) return QS_ERR_BAD_EXTENT;
     const bool cx = p.dtype == QS_C128;
     const int64_t m = p.m, n = p.n, batch = p.batch;
     GemmArgs g;
@@ -549,6 +561,7 @@ int gemm(const Product& p, hipStream_t stream) {
         }
         rc = gemm_fast_try(p, cx || (g_tune.gemm_fit == 2 && fit_cfg) ? 0.0 : cost / kGeneralRelativeRate, stream);
         if (rc != 1) return rc;
+        if (p.mirror) return QS_ERR_BAD_EXTENT;      // not reached (gemm_mirrors above): no other kernel stores the mirror
         if (fit_cfg) {
             // 16-byte staging only for an even tile count; an odd one takes the 8-byte form whatever the alignment
             const bool odd = (fit_cfg % 100) & 1;

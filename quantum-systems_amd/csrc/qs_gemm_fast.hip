@@ -95,6 +95,10 @@ struct FastPairsArgs : FastArgs {
     unsigned pairs;          // n > 0
 };
 
+// ... whose epilogue also stores the tile of pair (i, j > i) transposed at pair (j, i) (Product::mirror): a third overload,
+// for the same reason.  Only what fast_mirror_form() names is ever instantiated.
+struct FastPairsMirrorArgs : FastPairsArgs {};
+
 template <bool CX, int TM, int TN, bool VEC, bool EDGE>
 __global__ __launch_bounds__(256, 2)
 void gemm_fast_kernel(const FastArgs g) {
@@ -107,6 +111,14 @@ template <bool CX, int TM, int TN, bool VEC, bool EDGE>
 __global__ __launch_bounds__(256, 2)
 void gemm_fast_kernel(const FastPairsArgs g) {
 #define QS_FAST_PAIRS 1
+#include "qs_gemm_fast_body.h"
+#undef QS_FAST_PAIRS
+}
+
+template <bool CX, int TM, int TN, bool VEC, bool EDGE>
+__global__ __launch_bounds__(256, 2)
+void gemm_fast_kernel(const FastPairsMirrorArgs g) {
+#define QS_FAST_PAIRS 2
 #include "qs_gemm_fast_body.h"
 #undef QS_FAST_PAIRS
 }
@@ -165,7 +177,23 @@ static int launch_fast(const Product& p, hipStream_t stream) {
     constexpr bool DMA = QS_FAST_DMA && !CX && VEC && !EDGE;     // unpadded A rows (the kernel's kDma)
     const size_t lds = sizeof(double) * 2 * NP * (BM * (CX || DMA ? KT : KT + 2) + KT * (CX ? BN + 16 : BN));
 #endif
-    static PerDeviceLds lds_opt_in[2];   // per instantiation, batch kind and device
+    static PerDeviceLds lds_opt_in[3];   // per instantiation, batch kind and device
+    constexpr bool kMirrors = !CX && TM == 4 && TN == 4 && VEC && !EDGE;      // (fast_mirror_form)
+    if (p.mirror) {
+        if constexpr (kMirrors) {
+            FastPairsMirrorArgs gm;
+            static_cast<FastArgs&>(gm) = g;
+            gm.pairs = (unsigned)p.pairs;
+            void (*kern)(const FastPairsMirrorArgs) = gemm_fast_kernel<CX, TM, TN, VEC, EDGE>;
+            if (int rc = opt_in_dynamic_lds((const void*)kern, lds, lds_opt_in[2], "hipFuncSetAttribute(gemm_fast)")) return rc;
+            hipLaunchKernelGGL(kern, dim3((unsigned)P), dim3(256), lds, stream, gm);
+            // (same name and template arguments as the other two: the record says which overload ran)
+            note_dispatch("qs::gemm_fast_kernel<false, 4, 4, true, false>(qs::FastPairsMirrorArgs)");
+            return launch_status("gemm_fast launch");
+        } else {
+            return QS_ERR_BAD_EXTENT;      // not reached: gemm() asks gemm_fast_mirrors() first
+        }
+    }
     if (p.pairs) {
         FastPairsArgs gp;
         static_cast<FastArgs&>(gp) = g;
@@ -255,6 +283,18 @@ static int launch_edge_f64(int shape, const Product& p, hipStream_t stream) {
         case 9: return launch_fast<false, 3, 2, VEC, true>(p, stream);
         default: return launch_fast<false, 2, 2, VEC, true>(p, stream);
     }
+}
+
+// Is this product one that gemm_fast_try() below puts on the exact fp64 128 x 128 form -- the one form that has a mirrored
+// epilogue?  (m == n, so the 64 x 128 form, which needs n % 128 == 0 too, is never what a mirrored product gets; complex128:
+// not built.)  The conditions are those of gemm_fast_try and launch_fast up to that form, in their order.
+bool gemm_fast_mirrors(const Product& p) {
+    if (!g_tune.gemm_fast || p.dtype != QS_F64 || !p.pairs || p.m != p.n || p.accumulate) return false;
+    if (32 * p.lda * 8 + 256 >= (int64_t(1) << 32)) return false;
+    if (p.m >= (int64_t(1) << 31) - 256 || p.k >= (int64_t(1) << 31) - 256) return false;
+    const bool even = aligned(p.A, 16) && aligned(p.B, 16) && aligned(p.C, 16) && !(p.lda & 1) && !(p.ldb & 1) &&
+                      !(p.ldc & 1) && !(p.sa & 1) && !(p.sb & 1) && !(p.sc & 1) && !(p.n & 1);
+    return (even || g_tune.gemm_fast_unaligned != 0) && p.k % 16 == 0 && p.m % 128 == 0;
 }
 
 // Returns QS_OK after launching, or 1 when the product does not qualify

@@ -1,5 +1,6 @@
 // Body of gemm_fast_kernel (qs_gemm_fast.hip), included once per overload inside the kernel's braces: `g` is the kernel's
-// argument, QS_FAST_PAIRS says whether it is a FastPairsArgs (triangular batch: the remap in `decode`, nothing else).  Text
+// argument, QS_FAST_PAIRS says whether it is a FastPairsArgs (triangular batch: the remap in `decode`, nothing else) or, 2, a
+// FastPairsMirrorArgs (the same, and the epilogue of pair (i, j > i) also stores the tile transposed at pair (j, i)).  Text
 // inclusion, not a shared device function: the plain batch's kernels then compile exactly as they did before the
 // triangular batch existed (through a forced-inline function eight of them spilled other scalar registers).
 // No include guard on purpose.
@@ -64,6 +65,10 @@
     // edge form: valid k-steps of a tile's last stage (KT when K is a whole number of stages)
     const int k_tail = EDGE ? g.k - (nk - 1) * KT : KT;
 
+#if QS_FAST_PAIRS == 2
+    static_assert(!CX && VEC && !EDGE, "the mirrored epilogue exists for the exact fp64 forms");
+    int64_t b_mirror = 0;        // flat index j n + i of the pair that the last decode()'s pair (i, j) mirrors to
+#endif
     // tile coordinates of virtual block v
     auto decode = [&](unsigned v, int& m0, int& n0, int64_t& b) {
         unsigned w = xcd_chunked_index_fast(v, g.total);
@@ -79,8 +84,14 @@
         // scalar registers so that every pointer derived from them stays an SGPR base
         b = __builtin_amdgcn_readfirstlane((int)w);
         // triangular batch: entry b is a pair (i, j >= i), its operands sit at the flat index i n + j
-#if QS_FAST_PAIRS
+#if QS_FAST_PAIRS == 1
         b = (uint32_t)__builtin_amdgcn_readfirstlane((int)triangle_flat((uint32_t)b, g.pairs));
+#elif QS_FAST_PAIRS == 2
+        {
+            const uint32_t pi = triangle_row((uint32_t)b, g.pairs), pj = pi + ((uint32_t)b - triangle_row_start(pi, g.pairs));
+            b = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pi * g.pairs + pj));
+            b_mirror = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pj * g.pairs + pi));
+        }
 #endif
         m0 = __builtin_amdgcn_readfirstlane(mt) * BM;
         n0 = __builtin_amdgcn_readfirstlane(nt) * BN;
@@ -294,6 +305,9 @@
     // epilogue of the tile at virtual block v: reg r of a lane -> row (lane>>4) + 4r of
     // each 16-row block; 16 bytes per lane (8-byte pieces in the !VEC form).  `guard`:
     // border tile of the edge form, rows >= m and columns >= n are not stored.
+#if QS_FAST_PAIRS == 2
+    bool mirrored = false;       // the last epilogue stored its tile twice (wave-uniform)
+#endif
     auto epilogue = [&](unsigned v) __attribute__((always_inline)) {
         int m0, n0; int64_t b;
         decode(v, m0, n0, b);
@@ -361,6 +375,29 @@
             if (g.accumulate) store_all(std::true_type{}, std::false_type{});
             else store_all(std::false_type{}, std::false_type{});
         }
+#if QS_FAST_PAIRS == 2
+        // The mirror: entry (row, col) of pair (i, j > i) also goes to (col, row) of pair (j, i), which no tile of the launch
+        // reads or writes (m == n, no accumulate: the host checks).  A lane holds rows (lane >> 4) + 4 r + 16 i and two
+        // adjacent columns, so one 8-byte store at fixed (i, jp, h, r) writes 16 runs of 32 bytes -- the four lane groups are
+        // four consecutive transposed columns -- and the four r, issued back to back, complete 16 whole 128-byte lines.  The
+        // column offsets are wave-uniform; the skip of a diagonal pair is a scalar branch.
+        mirrored = b_mirror != b;
+        if (mirrored) {
+            double* __restrict__ T = g.C + b_mirror * g.sc + (int64_t)col_l * g.ldc + row_l;
+#pragma unroll
+            for (int jp = 0; jp < TN / 2; ++jp) {
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    double* tcol = T + (int64_t)(jp * 32 + h) * g.ldc;
+#pragma unroll
+                    for (int i = 0; i < TM; ++i) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) QS_FAST_STORE(tcol + i * 16 + 4 * r, acc[0][i][2 * jp + h][r]);
+                    }
+                }
+            }
+        }
+#endif
     };
 
     using B0 = std::integral_constant<int, 0>;
@@ -397,6 +434,11 @@
     bool after_epi = false;      // DMA form: the previous stage ended with an epilogue
     constexpr int EPI_ST = TM * 4 * (TN / 2);   // its stores per wave (VEC form)
     static_assert(EPI_ST < 64, "the vmcnt field holds 0..63");
+#if QS_FAST_PAIRS == 2
+    // A mirrored epilogue issues EPI_ST + TM * 4 * TN stores, more than the field counts: the wait below then asks for at
+    // most 63 operations in flight, which is the DMA (older than every store) and the oldest EPI_ST + TM * 4 * TN - 63 stores.
+    static_assert(EPI_ST + TM * 4 * TN > 63, "otherwise count the mirror stores exactly");
+#endif
 
     // one global stage: k-steps 0 .. KS-2, [stash the next stage], barrier, [fetch the
     // stage after next], [first fragments of the next stage], k-step KS-1, and at a tile's
@@ -425,6 +467,10 @@
             // vector-memory work issued since is the previous stage's epilogue (EPI_ST stores), which is not waited for.
             // lgkmcnt(0): this wave's fragment reads of buffer `cur` are done before anyone's DMA overwrites it.  A raw
             // s_barrier, because __syncthreads() would also wait for the DMA of the stage after.
+#if QS_FAST_PAIRS == 2
+            if (after_epi && mirrored) asm volatile("s_waitcnt vmcnt(63) lgkmcnt(0)" ::: "memory");
+            else
+#endif
             if (after_epi) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"i"(EPI_ST) : "memory");
             else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();

@@ -1,7 +1,7 @@
 """Same-process A/B of the transform's exchange-symmetry route against the plain route, and the route's phases.
 
     python tools/exchange_route_ab.py --sizes 160,192,224,256 --dtype f64 [--blocks 32,64,128] [--blocks-d 8,16,64]
-                                      [--pairs 0,1] [--reps 5] [--phases [--c-blocks 16,64]]
+                                      [--pairs 0,1] [--orders 0,2] [--reps 5] [--phases [--c-blocks 16,64]]
 
 Per size: one symmetric tensor (bench.make_inputs), then the plain route (`exchange=0`) and every (block, block_d)
 of the forced route (`exchange=2`) in ALTERNATING repetitions (NOTES.md "How to measure here"), HIP-event time per
@@ -9,7 +9,8 @@ call; the route's time includes the check kernel and its read-back, as `kernels.
 `--phases` replays the route's launches one phase at a time through `qs_matmul` / `qs_exchange_mirror` with an event
 pair around each (the phases of qs_api.hip's transform_two_body_exchange_route, same shapes and strides): d and c both as
 the launches per block / per row of `exchange_pairs=0` and as the one triangular-batch launch (`qs_matmul_pairs`) of
-`exchange_pairs=1`.  `--pairs 0,1` times the whole route at both settings of that key."""
+`exchange_pairs=1`.  `--pairs 0,1` times the whole route at both settings of that key, `--orders 0,2` at both orders of the contractions
+(`exchange_order`); `--phases` then replays each of those orders' launches."""
 
 import argparse
 import os
@@ -33,8 +34,9 @@ def med(xs):
     return s[len(s) // 2] if len(s) % 2 else 0.5 * (s[len(s) // 2 - 1] + s[len(s) // 2])
 
 
-def phases(torch, K, u, C, Ct, out, blk, blk_d, reps, c_blocks=(), other_order=False):
-    """The route's launches, phase by phase (T1 and X in one spare buffer, T2 in `out`).  `c_blocks`: also time the c phase
+def phases(torch, K, u, C, Ct, out, blk, blk_d, reps, c_blocks=(), other_order=False, order=0):
+    """The route's launches, phase by phase (T1 and X in one spare buffer, T2 in `out`), in the order `order` takes (0: d, c,
+    mirror, a, closing, mirror; 2: a, closing, d, c, mirror -- X1 and Y in the spare buffer, X2 in `out`).  `c_blocks`: also time the c phase
     with every row a of a block [a0, a1) batched over b >= a0 instead of b >= a (needs blk_d to divide those blocks)."""
     L = C.shape[0]
     dt = u.dtype
@@ -49,10 +51,10 @@ def phases(torch, K, u, C, Ct, out, blk, blk_d, reps, c_blocks=(), other_order=F
     def check():
         assert lib.qs_two_body_exchange_symmetric(code, u.data_ptr(), L, scratch.data_ptr(), st) == 1
 
-    def d():
+    def d(src=u):
         for a0 in range(0, L, blk_d):
             rows = min(L, a0 + blk_d) - a0
-            K.gemm_raw(dt, u, C, W, (L - a0) * L, L, L, L, L, L, rows, L3, 0, L3,
+            K.gemm_raw(dt, src, C, W, (L - a0) * L, L, L, L, L, L, rows, L3, 0, L3,
                        a_off=a0 * L3 + a0 * L2, c_off=a0 * L3 + a0 * L2)
 
     def c(cb=1):
@@ -60,14 +62,14 @@ def phases(torch, K, u, C, Ct, out, blk, blk_d, reps, c_blocks=(), other_order=F
             b0 = a // cb * cb
             K.gemm_raw(dt, CT, W, out, L, L, L, L, L, L, L - b0, 0, L2, L2, b_off=(a * L + b0) * L2, c_off=(a * L + b0) * L2)
 
-    def d_pairs():
-        K.gemm_raw(dt, u, C, W, L, L, L, L, L, L, 0, L2, 0, L2, pairs=L)
+    def d_pairs(src=u):
+        K.gemm_raw(dt, src, C, W, L, L, L, L, L, L, 0, L2, 0, L2, pairs=L)
 
-    def c_pairs():
-        K.gemm_raw(dt, CT, W, out, L, L, L, L, L, L, 0, 0, L2, L2, pairs=L)
+    def c_pairs(mirror=False):
+        K.gemm_raw(dt, CT, W, out, L, L, L, L, L, L, 0, 0, L2, L2, pairs=L, mirror=mirror)
 
-    def a_():
-        K.gemm_raw(dt, Ct, out, W, L, L3, L, L, L3, L3)
+    def a_(src=out):
+        K.gemm_raw(dt, Ct, src, W, L, L3, L, L, L3, L3)
 
     def b():
         for p0 in range(0, L, blk):
@@ -83,9 +85,20 @@ def phases(torch, K, u, C, Ct, out, blk, blk_d, reps, c_blocks=(), other_order=F
             rows = min(L, p0 + blk) - p0
             K.gemm_raw(dt, Ct, W, out, rows, (L - p0) * L2, L, L, L3, L3, a_off=p0 * L, b_off=p0 * L2, c_off=p0 * L3 + p0 * L2)
 
-    other = [("other order: b full", b_full), ("other order: a blocks", a_blocks)] if other_order else []
-    steps = [("check", check), ("d, per block", d), ("d", d_pairs)] + [(f"c, b >= block {cb}", lambda cb=cb: c(cb)) for cb in c_blocks] + [("c, per row", c), ("c", c_pairs), ("mirror T2", lambda: K.exchange_mirror_(out.view(L, L, L, L), 1)),
-             ] + other + [("a", a_), ("closing product", b), ("mirror out", lambda: K.exchange_mirror_(out.view(L, L, L, L), blk))]
+    mirror = lambda block: K.exchange_mirror_(out.view(L, L, L, L), block)     # noqa: E731
+    if order == 2:
+        # exchange_order=2, the leading indices first: a on u, the closing blocks, then d and c on the pairs of X2 (in
+        # `out`), and the one mirror of the result over all pairs.  Same buffers: every product reads one and writes the other.
+        steps = [("check", check), ("a", lambda: a_(u)), ("closing product", b), ("d, per block", lambda: d(out)),
+                 ("d", lambda: d_pairs(out)), ("c, per row", c), ("c", c_pairs), ("mirror out", lambda: mirror(1))]
+        if not dt.is_complex and L % 128 == 0:      # where the c launch can store the mirror itself: against "c" + "mirror out"
+            steps.append(("c, storing the mirror", lambda: c_pairs(True)))
+    else:
+        other = [("other order: b full", b_full), ("other order: a blocks", a_blocks)] if other_order else []
+        steps = [("check", check), ("d, per block", d), ("d", d_pairs)] + [(f"c, b >= block {cb}", lambda cb=cb: c(cb)) for cb in c_blocks] + [
+            ("c, per row", c), ("c", c_pairs), ("mirror T2", lambda: mirror(1))] + other + [
+            ("a", a_), ("closing product", b), ("mirror out", lambda: mirror(blk))]
+    print(f"    phases of exchange_order={order}")
     times = {name: [] for name, _ in steps}
     for _ in range(reps + 1):
         for name, fn in steps:
@@ -106,6 +119,7 @@ def main():
     ap.add_argument("--blocks", default="64")
     ap.add_argument("--blocks-d", default="16")
     ap.add_argument("--pairs", default="1", help="exchange_pairs settings of the route to time, e.g. 0,1")
+    ap.add_argument("--orders", default="1", help="exchange_order settings of the route to time, e.g. 0,2 (1: the automatic rule)")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--phases", action="store_true")
     ap.add_argument("--other-order", action="store_true", help="with --phases: also time b full, then a per block of rows")
@@ -118,7 +132,7 @@ def main():
 
     dev = torch.device("cuda:0")
     dtype = torch.float64 if args.dtype == "f64" else torch.complex128
-    configs = [(int(b), int(bd), int(pr)) for b in args.blocks.split(",") for bd in args.blocks_d.split(",") for pr in args.pairs.split(",")]
+    configs = [(int(b), int(bd), int(pr), int(od)) for b in args.blocks.split(",") for bd in args.blocks_d.split(",") for pr in args.pairs.split(",") for od in args.orders.split(",")]
     for l in [int(x) for x in args.sizes.split(",")]:
         u, C, Ct = bench.make_inputs(torch, l, dtype, dev)
         out = torch.empty_like(u)
@@ -128,8 +142,8 @@ def main():
             with K.tuning(exchange=0):
                 K.transform_two_body(u, C, Ct, out=out)
 
-        def route(b, bd, pr):
-            with K.tuning(exchange=2, exchange_block=b, exchange_block_d=bd, exchange_pairs=pr):
+        def route(b, bd, pr, od):
+            with K.tuning(exchange=2, exchange_block=b, exchange_block_d=bd, exchange_pairs=pr, exchange_order=od):
                 K.transform_two_body(u, C, Ct, out=out)
 
         plain()
@@ -150,11 +164,16 @@ def main():
         print(f"  plain                       median {base:8.3f} ms   runs {' '.join('%.3f' % x for x in runs['plain'])}")
         for cfg in configs:
             m = med(runs[cfg])
-            print(f"  route block={cfg[0]:3d} block_d={cfg[1]:3d} pairs={cfg[2]} median {m:8.3f} ms   runs {' '.join('%.3f' % x for x in runs[cfg])}"
+            print(f"  route block={cfg[0]:3d} block_d={cfg[1]:3d} pairs={cfg[2]} order={cfg[3]} median {m:8.3f} ms   runs {' '.join('%.3f' % x for x in runs[cfg])}"
                   f"   plain/route {base / m:.3f}")
         sys.stdout.flush()
         if args.phases:
-            phases(torch, K, u, C, Ct, out, configs[0][0], configs[0][1], args.reps, [int(x) for x in args.c_blocks.split(",") if x], args.other_order)
+            for od in sorted({cfg[3] for cfg in configs}):       # (1, the automatic rule, reads as the order it takes here)
+                if od == 1:
+                    route(configs[0][0], configs[0][1], 1, 1)
+                    od = 2 if K.last_dispatch().count("exchange_transpose_kernel") == 1 else 0
+                phases(torch, K, u, C, Ct, out, configs[0][0], configs[0][1], args.reps,
+                       [int(x) for x in args.c_blocks.split(",") if x], args.other_order, od)
         del u, out
         K.workspace.release()
         torch.cuda.empty_cache()
