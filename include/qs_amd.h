@@ -1080,6 +1080,56 @@ int qs_string_ci_ladder_table(const int64_t* target, int64_t n_t, const int64_t*
 int qs_string_ci_ladder(int h_dtype, int c_dtype, const void* phi, int64_t d, int64_t spin, const int32_t* table, int64_t m,
                         int64_t n_alpha, int64_t na_s, int64_t nb_s, int64_t n_t, const void* c, int64_t K, void* out,
                         void* stream);
+/*
+ * Pivoted Cholesky decomposition of the two-body tensor (csrc/qs_cholesky.hip).
+ * With G[(r,p),(q,s)] = u[p,q,r,s], an m^2 x m^2 matrix (flat index first * m +
+ * second) that is Hermitian positive semidefinite for a positive interaction and a
+ * plain, NOT anti-symmetrised u (m, m, m, m), the vectors L_x (m x m) satisfy
+ *   u[p,q,r,s] = sum_x conj(L_x[r,p]) L_x[q,s]  + R,   0 <= R[(i),(i)] <= tau:
+ * the residual R is positive semidefinite, so every element of it is bounded by
+ * its largest diagonal element.  For the Coulomb tensor of a quantum dot the rank
+ * is about 4 m, not m^2.  u is read in place (the pivot column of (q*, s*) is the
+ * conjugated row u[s*, r, q*, p], contiguous in p); no m^4 copy is made.
+ * Left-looking, one vector per step:
+ *   piv = argmax d (the LOWEST flat index on ties);  stop when d[piv] <= tau or
+ *   the capacity is reached;
+ *   L_j[i] = (u[s*, r, q*, p] - sum_{x<j} L_x[i] conj(L_x[piv])) / sqrt(d[piv]),
+ *   i = r m + p;   d[i] -= |L_j[i]|^2;   d[piv] = 0 exactly.
+ * Hermiticity of G is the caller's contract and is not checked; an indefinite
+ * tensor shows as a negative residual diagonal (extremes[1]).
+ *   vectors  : (capacity, m, m) of dtype, device; rows 0 ... rank - 1 are L_x
+ *   rank     : HOST pointer, in and out.  In: the vectors already in the buffer
+ *              (0 = a fresh run, which fills diag from u).  Out: the vectors
+ *              there now.  A call with rank > 0 CONTINUES the run that left
+ *              vectors, diag and pivots: a caller whose run ended on the capacity
+ *              copies the rows into a larger buffer and calls again.  Every sum
+ *              has a fixed order that depends on neither the capacity nor the
+ *              interruption: a resumed run, a fresh run and a repeated run give
+ *              the same bits.
+ *   diag     : m^2 doubles, device: the residual diagonal d[(r,p)], in and out
+ *   pivots   : capacity int64, device: the flat index (q*, s*) of every step
+ *   extremes : HOST pointer, 2 doubles out: the largest and the smallest residual
+ *              diagonal at exit (largest <= tau: converged; smallest < 0 beyond
+ *              rounding: G is not positive semidefinite)
+ *   work     : qs_cholesky_two_body_workspace bytes, device, 16-byte aligned
+ * Two plain launches per step, in stream order (no grid-wide barrier, no spin
+ * wait): the pivot, the rank and a stop flag stay in device memory and every
+ * launch after the stop returns at once.  THIS CALL BLOCKS: it enqueues
+ * qs_cholesky_two_body_block() steps at a time and reads the state back once
+ * after each such block (hipMemcpyAsync + hipStreamSynchronize on `stream`); on
+ * a capturing stream it launches nothing and returns QS_ERR_HIP.
+ * Errors, checked in this order before any HIP call: dtype; extents (m < 1,
+ * m^2 > 2^31 - 1, capacity < 1 or its bytes past int64, tau < 0 or NaN); null
+ * pointer; *rank < 0 or > capacity (QS_ERR_BAD_EXTENT); misaligned pointer
+ * (element size for u and vectors, 8 for rank, diag, pivots and extremes, 16 for
+ * work); work_bytes below the query (QS_ERR_WORKSPACE).  (Additions: the ABI
+ * version stays 4.)
+ */
+int64_t qs_cholesky_two_body_workspace(int dtype, int64_t m, int64_t capacity);
+int64_t qs_cholesky_two_body_block(void);
+int qs_cholesky_two_body(int dtype, const void* u, int64_t m, double tau, void* vectors, int64_t capacity,
+                         int64_t* rank, double* diag, int64_t* pivots, double* extremes, void* work,
+                         int64_t work_bytes, void* stream);
 int qs_probe_mfma_f64(void* sink, int64_t blocks, int64_t iters, void* stream);
 int qs_probe_stream_copy(const void* src, void* dst, int64_t bytes, void* stream);
 

@@ -124,6 +124,11 @@ SIGNATURES = {
     "qs_string_ci_one_body": (c_int, [c_int, c_int, c_ptr, c_ptr, c_i64, c_ptr, c_ptr] + [c_i64] * 3 + [c_ptr, c_i64, c_ptr, c_ptr]),
     "qs_string_ci_ladder_table": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
     "qs_string_ci_ladder": (c_int, [c_int, c_int, c_ptr, c_i64, c_i64, c_ptr] + [c_i64] * 5 + [c_ptr, c_i64, c_ptr, c_ptr]),
+    "qs_cholesky_two_body_workspace": (c_i64, [c_int, c_i64, c_i64]),
+    "qs_cholesky_two_body_block": (c_i64, []),
+    "qs_cholesky_two_body": (
+        c_int, [c_int, c_ptr, c_i64, ctypes.c_double, c_ptr, c_i64, ctypes.POINTER(c_i64), c_ptr, c_ptr,
+                ctypes.POINTER(ctypes.c_double), c_ptr, c_i64, c_ptr]),
 }
 
 ABI_VERSION = 4

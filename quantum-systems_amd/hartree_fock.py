@@ -12,6 +12,9 @@ one ``qs_mean_field`` launch, one read of ``u`` -- and everything else is O(l^3)
     omega, X = hf.cis().solve(4)        # lowest excited states (configuration interaction singles)
     hf.change_system_basis()            # system.change_basis(C): the Fock matrix is diagonal now
 
+    chol = system.cholesky_two_body(tol)            # RHF on Cholesky vectors of u (cholesky.py): the mean field is a
+    hf = HartreeFock(system, two_body=chol)         # few products on about 4 l matrices, u is not read again
+
 ``system.change_to_hf_basis()`` keeps raising ``NotImplementedError`` as in the reference.
 """
 
@@ -20,6 +23,7 @@ import torch
 
 from . import kernels, sharded_basis
 from .basis_set import _deliver, _stage
+from .cholesky import CholeskyTwoBody
 from .general_orbital_system import GeneralOrbitalSystem
 from .sharded_module import is_sharded
 from .spatial_orbital_system import SpatialOrbitalSystem
@@ -33,13 +37,23 @@ class HartreeFock:
     """SCF driver: core-Hamiltonian guess, Loewdin orthogonalisation with the basis set's overlap ``s``, DIIS on
     ``F rho s - s rho F``.  ``system.n`` lowest orbitals are occupied (doubly for spatial orbitals)."""
 
-    def __init__(self, system):
+    def __init__(self, system, two_body=None):
         if isinstance(system, SpatialOrbitalSystem):
             self.occupation = 2.0
         elif isinstance(system, GeneralOrbitalSystem):
             self.occupation = 1.0
         else:
             raise TypeError("HartreeFock needs a SpatialOrbitalSystem (RHF) or a GeneralOrbitalSystem (GHF)")
+        if two_body is not None:
+            # Cholesky vectors (cholesky.CholeskyTwoBody) of the system's plain u: the mean field is a few products on
+            # them and u is never read.  RHF only: the vectors of a spin-expanded, anti-symmetrised tensor do not exist.
+            if not isinstance(system, SpatialOrbitalSystem):
+                raise TypeError("two_body= (Cholesky vectors) is supported for a SpatialOrbitalSystem (RHF) only")
+            if not isinstance(two_body, CholeskyTwoBody):
+                raise TypeError("two_body must be a cholesky.CholeskyTwoBody")
+            if two_body.m != system.l:
+                raise ValueError(f"two_body has {two_body.m} orbitals, the system {system.l}")
+        self.two_body = two_body
         self.system = system
         self.C = self.epsilon = None
         self.energies = []
@@ -50,6 +64,8 @@ class HartreeFock:
     # -- the one O(l^4) step of an iteration
     def _mean_field(self, u, rho):
         cj, ck = self.system._mean_field_weights()
+        if self.two_body is not None:
+            return self.two_body.mean_field(rho, cj=cj, ck=ck)
         if is_sharded(u):
             return sharded_basis.mean_field(u, rho, cj, ck, self.system.np).as_subclass(torch.Tensor)
         return kernels.mean_field(u, rho, cj=cj, ck=ck)

@@ -1491,6 +1491,79 @@ def transform_two_body_blocks(u, Ct0, Ct1, C2, C3, out=None):
     return out
 
 
+class CholeskyState:
+    """What a run of ``cholesky_two_body`` leaves behind and a later call continues from: the vector buffer
+    ``(capacity, m, m)``, the residual diagonal ``(m*m,)``, the pivots ``(capacity,)`` int64 and the rank."""
+
+    __slots__ = ("vectors", "diag", "pivots", "rank")
+
+    def __init__(self, vectors, diag, pivots, rank):
+        self.vectors, self.diag, self.pivots, self.rank = vectors, diag, pivots, rank
+
+    @property
+    def capacity(self):
+        return self.vectors.shape[0]
+
+
+@_plain
+def cholesky_two_body(u, tol, max_rank=None, state=None):
+    """Pivoted Cholesky vectors of the two-body tensor (``qs_cholesky_two_body``): ``L`` with
+
+        u[p,q,r,s] = sum_x conj(L[x,r,p]) L[x,q,s]   to within ``tol`` per element,
+
+    for a plain (not anti-symmetrised) ``u`` (m, m, m, m) whose ``G[(r,p),(q,s)] = u[p,q,r,s]`` is Hermitian positive
+    semidefinite; ``u`` is read in place.  The run stops when the largest residual diagonal is ``<= tol`` or at
+    ``max_rank`` vectors (the capacity of the buffer; default ``min(8 m, m*m)``).  With ``state`` (of an earlier call on
+    the same ``u`` and ``tol``) the run CONTINUES from ``state.rank``; a ``max_rank`` above the state's capacity moves
+    the vectors to a larger buffer first.  The bits do not depend on where a run was interrupted.
+
+    Returns ``(L, pivots, (dmax, dmin), state)``: views ``(rank, m, m)`` and ``(rank,)`` of the state's buffers, the
+    largest and the smallest residual diagonal at exit, and the state.  The call blocks (one read-back of the device's
+    stop flag per ``qs_cholesky_two_body_block()`` steps)."""
+    lib = _lib.load()
+    if not isinstance(u, torch.Tensor):
+        raise TypeError("expected a torch.Tensor")
+    dt = _C128 if u.dtype in (torch.complex64, _C128) else _F64
+    u = _dev(u, dt)
+    if u.dim() != 4 or len(set(u.shape)) != 1:
+        raise ValueError(f"u must be (m, m, m, m), got {tuple(u.shape)}")
+    m = u.shape[0]
+    n = m * m
+    have = 0 if state is None else state.capacity
+    cap = max(have, min(8 * m, n)) if max_rank is None else int(max_rank)
+    if cap < 1 or (state is not None and cap < state.rank):
+        raise ValueError(f"max_rank = {cap} must be at least 1 and at least the rank of the state")
+    code = dtype_code(dt)
+    nbytes = check(lib.qs_cholesky_two_body_workspace(code, m, cap), "workspace query")
+    if state is None:
+        state = CholeskyState(torch.empty((cap, m, m), dtype=dt, device=u.device),
+                              torch.empty(n, dtype=_F64, device=u.device),
+                              torch.empty(cap, dtype=torch.int64, device=u.device), 0)
+    else:
+        if state.vectors.dtype != dt or tuple(state.vectors.shape[1:]) != (m, m) or state.vectors.device != u.device:
+            raise ValueError("state does not belong to this tensor")
+        if cap != have:
+            r = state.rank
+            vectors = torch.empty((cap, m, m), dtype=dt, device=u.device)
+            pivots = torch.empty(cap, dtype=torch.int64, device=u.device)
+            vectors[:r].copy_(state.vectors[:r])
+            pivots[:r].copy_(state.pivots[:r])
+            state = CholeskyState(vectors, state.diag, pivots, r)
+    rank = ctypes.c_int64(state.rank)
+    extremes = (ctypes.c_double * 2)()
+    with _on_device_of(u, state.vectors, state.diag, state.pivots):
+        work = workspace.get(nbytes, u.device)
+        _ran(
+            lib.qs_cholesky_two_body(
+                code, u.data_ptr(), m, float(tol), state.vectors.data_ptr(), cap, ctypes.byref(rank),
+                state.diag.data_ptr(), state.pivots.data_ptr(), extremes, work.data_ptr(), work.numel(), _stream(),
+            ),
+            "qs_cholesky_two_body",
+        )
+    state.rank = r = int(rank.value)
+    return state.vectors[:r], state.pivots[:r], (float(extremes[0]), float(extremes[1])), state
+
+
 class RcclComm:
     """The C ABI's communicator (``qs_comm_init``: RCCL over xGMI, one process per GPU) for hosts that drive the
     library from Python without ``torch.distributed``.  ``unique_id()`` on one rank, the 128 bytes to the others by

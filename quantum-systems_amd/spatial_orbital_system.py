@@ -85,5 +85,11 @@ class SpatialOrbitalSystem(QuantumSystem):
         # closed shell, spin-summed density: f = h + J(rho) - K(rho) / 2
         return 1.0, -0.5
 
+    def cholesky_two_body(self, tol, max_rank=None):
+        """Cholesky vectors of this system's two-body tensor: ``cholesky.decompose(self, tol, max_rank)``."""
+        from .cholesky import decompose
+
+        return decompose(self, tol, max_rank=max_rank)
+
     def change_to_hf_basis(self, *args, **kwargs):
         raise NotImplementedError("There is currently no RHF implementation")
