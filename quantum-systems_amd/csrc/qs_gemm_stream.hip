@@ -36,7 +36,7 @@
 
 #include <type_traits>
 
-#include "qs_common.h"
+#include "qs_mfma4.h"      // vector typedefs, uniform_rsrc
 
 namespace qs {
 
@@ -49,10 +49,6 @@ __device__ __forceinline__ void static_for(F&& f) {
     }
 }
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 struct StreamArgs {
     const double* A;
@@ -135,11 +131,7 @@ void gemm_stream_left_kernel(const StreamArgs g) {
 
     // descriptor of batch slice b of B / C, and the lane offsets inside column block cb
     auto slice = [&](const double* base, int64_t stride, unsigned b, unsigned room) __attribute__((always_inline)) {
-        const uint64_t p = reinterpret_cast<uint64_t>(base + (int64_t)b * stride);
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)p);
-        const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(p >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)hi << 32) | lo), (short)0,
-                                                 (int)room, 0x00020000);
+        return uniform_rsrc(reinterpret_cast<uint64_t>(base + (int64_t)b * stride), (int)room);
     };
     auto b_offsets = [&](unsigned cb, unsigned (&off)[NLD]) __attribute__((always_inline)) {
 #pragma unroll
@@ -255,11 +247,7 @@ void gemm_stream_left_cx_kernel(const StreamArgs g) {
     const unsigned rstep = (unsigned)(4 * g.ldc * 16);
 
     auto slice = [&](const double* base, int64_t stride, unsigned b, unsigned room) __attribute__((always_inline)) {
-        const uint64_t p = reinterpret_cast<uint64_t>(base + (int64_t)b * stride * 2);
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)p);
-        const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(p >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)hi << 32) | lo), (short)0,
-                                                 (int)room, 0x00020000);
+        return uniform_rsrc(reinterpret_cast<uint64_t>(base + (int64_t)b * stride * 2), (int)room);
     };
     auto b_offsets = [&](unsigned cb, unsigned (&off)[NT]) __attribute__((always_inline)) {
 #pragma unroll

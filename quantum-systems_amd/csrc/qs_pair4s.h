@@ -10,9 +10,9 @@
 // Two launches, two passes over the tensor instead of four (basis_set.py:341-348).  RandomBasisSet (random_basis.py:52-69) and
 // every spin-doubled tensor are complex.
 //
-// v_mfma_f64_4x4x4_4b_f64 multiplies four independent 4 x 4 x 4 blocks per instruction (lane = x + 4 y + 16 z: A row x /
-// block y / k z, B k z / block y / column x, D row z / block y / column x), and BOTH operands may differ from block to
-// block.  The four blocks here are (item, part) for TWO items and part = re / im of the RESULT:
+// v_mfma_f64_4x4x4_4b_f64 multiplies four independent 4 x 4 x 4 blocks per instruction (the lane layouts and the parked-lane
+// convention: qs_mfma4.h), and BOTH operands may differ from block to block.  The four blocks here are (item, part) for TWO
+// items and part = re / im of the RESULT:
 //
 //     Y = In . R      MFMA 1:  A = In_re (both parts)            B = R_re (part re),  R_im (part im)
 //                     MFMA 2:  A = In_im (both parts)            B = -R_im (part re), R_re (part im)
@@ -34,22 +34,21 @@
 // above 40 orbitals (12-26 % of a launch).  The streamed form below replaced it at every size and the whole-pair kernel is gone.
 #pragma once
 
-#include <type_traits>
-
-#include "qs_common.h"
+#include "qs_mfma4.h"
 
 namespace qs {
 
+typedef int i32x2 __attribute__((ext_vector_type(2)));
+
+// unroll() of qs_mfma4.h one at a time.  This kernel was written on this form and keeps it: on the halving form the compiler
+// schedules its one-group instantiations (N4 = 4 ... 12) differently (profiles/mfma4_toolkit_isa.txt).
 template <int I, int N, class F>
-__device__ __forceinline__ void unroll(F&& f) {
+__device__ __forceinline__ void unroll_chain(F&& f) {
     if constexpr (I < N) {
         f(std::integral_constant<int, I>{});
-        unroll<I + 1, N>(f);
+        unroll_chain<I + 1, N>(f);
     }
 }
-
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-typedef int i32x2 __attribute__((ext_vector_type(2)));
 
 struct Pair4Args : FusedPass {      // R and Lm in complex elements; ntuples = item pairs
     int tensor_is_b;      // the 16-wide kernels' call for the FIRST product has the tensor as its B operand (the b contraction)
@@ -60,9 +59,8 @@ struct Pair4Args : FusedPass {      // R and Lm in complex elements; ntuples = i
 #define QS_PAIR4C_ABLATE 0
 #endif
 
-__device__ __forceinline__ double mfma4(double a, double b, double c) {
-    if constexpr (QS_PAIR4C_ABLATE & 4) return a + b + c;
-    return __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, c, 0, 0, 0);
+__device__ __forceinline__ double mfma4_or_sum(double a, double b, double c) {
+    return (QS_PAIR4C_ABLATE & 4) ? a + b + c : mfma4(a, b, c);
 }
 
 // value of lane ^ 4 (the other part of the same item)
@@ -111,23 +109,20 @@ __global__ __launch_bounds__(64 * stream_waves(N4)) void pair4s_kernel(const Pai
     const int L = g.L, M = g.M;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int x = lane & 3, y = (lane >> 2) & 3, z = lane >> 4;
+    const Lane4 l4 = lane4(lane);
+    const int x = l4.x, y = l4.y, z = l4.z, e_lane = l4.e;
     const int item = y >> 1, part = y & 1;
-    const int e_lane = z * 4 + x;
     const bool tb = g.tensor_is_b != 0;
     const bool slab = g.in_col == 1;
 
-    const unsigned n_xcd = 8, xcd = blockIdx.x % n_xcd, slot = blockIdx.x / n_xcd, slots = gridDim.x / n_xcd;
-    const unsigned per = (g.ntuples + n_xcd - 1) / n_xcd;
-    const unsigned u_end = (xcd + 1) * per < g.ntuples ? (xcd + 1) * per : g.ntuples;
-    unsigned unit = xcd * per + slot;
+    const XcdRange units = xcd_range(g.ntuples);
+    const unsigned u_end = units.end, slots = units.stride;
+    unsigned unit = units.first;
     if (unit >= u_end) return;                              // (the whole workgroup, before any barrier)
 
     // ---- the fetch: thread t < 8 K4 owns element (item, row, k) of every row quad.  Buffer loads: the pair's base in the
-    // descriptor (scalar), the element's place in the lane offset (a lane without an element is parked past num_records:
-    // the hardware returns 0.0), the row quad in the scalar offset -- no vector ALU work per fetch.
-    constexpr unsigned kParked = 0x80000000u;
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    // descriptor (scalar), the element's place in the lane offset (a lane without an element is parked), the row quad in the
+    // scalar offset -- no vector ALU work per fetch.
     int f_it, f_r, f_k;
     if (REAL_IN) { f_k = 2 * (tid % (K4 / 2)); f_r = (tid / (K4 / 2)) & 3; f_it = tid / (2 * K4); }      // (slabs only)
     else if (slab) { f_k = tid % K4; f_r = (tid / K4) & 3; f_it = tid / (4 * K4); }
@@ -141,10 +136,7 @@ __global__ __launch_bounds__(64 * stream_waves(N4)) void pair4s_kernel(const Pai
     // can start 8 bytes earlier -- its second half is that k, the missing one's place gets 0.0)
     const bool shift_k = REAL_IN && f_k < L && !(f_k + 1 < L);
     auto rsrc_of = [&](unsigned u) __attribute__((always_inline)) {
-        const uint64_t pb = reinterpret_cast<uint64_t>(g.in + (int64_t)(u < u_end ? u : 0) * 2 * g.in_item * (REAL_IN ? 1 : 2)) - (REAL_IN ? 8 : 0);
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)pb);
-        const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(pb >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)hi << 32) | lo), (short)0, 0x7fffffff, 0x00020000);
+        return uniform_rsrc(reinterpret_cast<uint64_t>(g.in + (int64_t)(u < u_end ? u : 0) * 2 * g.in_item * (REAL_IN ? 1 : 2)) - (REAL_IN ? 8 : 0));
     };
     // lane offsets of pair u: [0] its row quads but the last, [1] the last one (rows beyond L do not exist)
     auto voffs_of = [&](unsigned u, unsigned (&v)[2]) __attribute__((always_inline)) {
@@ -190,7 +182,7 @@ __global__ __launch_bounds__(64 * stream_waves(N4)) void pair4s_kernel(const Pai
     {
         constexpr int NF = (TABLE + NTH - 1) / NTH;
         double l_re[NF], l_im[NF];
-        unroll<0, NF>([&](auto I) __attribute__((always_inline)) {
+        unroll_chain<0, NF>([&](auto I) __attribute__((always_inline)) {
             constexpr int i = decltype(I)::value;
             const int f = tid + NTH * i;
             const int e = f & 15, blk = f >> 4, hi = blk / N4, lo = blk % N4, ez = e >> 2, ex = e & 3;
@@ -202,9 +194,9 @@ __global__ __launch_bounds__(64 * stream_waves(N4)) void pair4s_kernel(const Pai
             }
             l_re[i] = re; l_im[i] = im;
         });
-        unroll<0, N4>([&](auto KS) __attribute__((always_inline)) {
+        unroll_chain<0, N4>([&](auto KS) __attribute__((always_inline)) {
             constexpr int ks = decltype(KS)::value;
-            unroll<0, NJ>([&](auto J) __attribute__((always_inline)) {
+            unroll_chain<0, NJ>([&](auto J) __attribute__((always_inline)) {
                 constexpr int j = decltype(J)::value;
                 const int k = 4 * ks + z, col = 4 * (jg0 + j) + x;
                 double re = 0.0, im = 0.0;
@@ -217,10 +209,10 @@ __global__ __launch_bounds__(64 * stream_waves(N4)) void pair4s_kernel(const Pai
             });
         });
         const f64x2 q0 = fetch(rs_cur, v_cur, std::integral_constant<int, 0>{});
-        unroll<0, P>([&](auto I) __attribute__((always_inline)) {
+        unroll_chain<0, P>([&](auto I) __attribute__((always_inline)) {
             pf[decltype(I)::value] = fetch(rs_cur, v_cur, std::integral_constant<int, 1 + decltype(I)::value>{});
         });
-        unroll<0, NF>([&](auto I) __attribute__((always_inline)) {
+        unroll_chain<0, NF>([&](auto I) __attribute__((always_inline)) {
             constexpr int i = decltype(I)::value;
             const int f = tid + NTH * i;
             if (f < TABLE) { ltab[f] = l_re[i]; ltab[TABLE + f] = l_im[i]; }
@@ -252,14 +244,14 @@ __global__ __launch_bounds__(64 * stream_waves(N4)) void pair4s_kernel(const Pai
         constexpr int AHEAD = N4 > 2 ? 2 : 1;               // groups between the read of the operands and their MFMAs
         static_assert(AHEAD < N4, "the read-ahead into the next row quad's slot starts behind the step's barrier");
         double opr[AHEAD + 1][2];
-        unroll<0, AHEAD>([&](auto T) __attribute__((always_inline)) {
+        unroll_chain<0, AHEAD>([&](auto T) __attribute__((always_inline)) {
             constexpr int t = decltype(T)::value;
             operands(T, opr[t % (AHEAD + 1)][0], opr[t % (AHEAD + 1)][1]);
         });
         const unsigned it_g = unit * 2 + item;              // D: row z, block (item, part), column x
         double* orow = g.out + ((int64_t)it_g * g.out_item + z * g.out_row + x * g.out_col + (int64_t)(4 * jg0) * g.out_col) * 2 + part;
         const bool st_ok = it_g < g.nitems && 4 * jg0 + x < M;
-        unroll<0, 2 * NG>([&](auto T) __attribute__((always_inline)) {
+        unroll_chain<0, 2 * NG>([&](auto T) __attribute__((always_inline)) {
             constexpr int t = decltype(T)::value, sl = t % (AHEAD + 1);
             if constexpr (t < NG && t % N4 == 0) {
                 // step start: row quad ka + 1 (the next pair's first after the last step) leaves its registers for its slot,
@@ -276,16 +268,15 @@ __global__ __launch_bounds__(64 * stream_waves(N4)) void pair4s_kernel(const Pai
                 // barrier; and it was last read in step ka - 2, which every wave had finished when it arrived at the barrier
                 // of step ka - 1 (three slots: with two, a wave still in step ka - 1 would be reading it).  It waits for the
                 // wave's LDS traffic only: the fetches stay in flight.
-                __builtin_amdgcn_s_waitcnt(0xC07F);         // lgkmcnt(0), vmcnt / expcnt untouched
-                __builtin_amdgcn_s_barrier();
+                lds_barrier();
             }
             if constexpr (t + AHEAD < 2 * NG)
                 operands(std::integral_constant<int, t + AHEAD>{}, opr[(t + AHEAD) % (AHEAD + 1)][0], opr[(t + AHEAD) % (AHEAD + 1)][1]);
             const double cur0 = opr[sl][0], cur1 = opr[sl][1];
             if constexpr (t < NG) {                         // Y[ka] += In[ka][ks] . R[ks]
                 constexpr int ka = t / N4, ks = t % N4;
-                Y[ka] = mfma4(cur0, b1[ks][0], ks == 0 ? 0.0 : Y[ka]);
-                if constexpr (!REAL_IN) Y[ka] = mfma4(cur1, b2[ks][0], Y[ka]);
+                Y[ka] = mfma4_or_sum(cur0, b1[ks][0], ks == 0 ? 0.0 : Y[ka]);
+                if constexpr (!REAL_IN) Y[ka] = mfma4_or_sum(cur1, b2[ks][0], Y[ka]);
                 if constexpr (ks == N4 - 1) {
                     // second operand of Lm_im: the other part of the same item, the block that feeds the real part negated
                     const double other = other_part(Y[ka]);
@@ -293,8 +284,8 @@ __global__ __launch_bounds__(64 * stream_waves(N4)) void pair4s_kernel(const Pai
                 }
             } else {                                        // Out[pg] += Lm[pg][ka] . Y[ka]
                 constexpr int pg = (t - NG) / N4, ka = (t - NG) % N4;
-                o2[pg & 1] = mfma4(cur0, Y[ka], ka == 0 ? 0.0 : o2[pg & 1]);
-                o2[pg & 1] = mfma4(cur1, Ys[ka], o2[pg & 1]);
+                o2[pg & 1] = mfma4_or_sum(cur0, Y[ka], ka == 0 ? 0.0 : o2[pg & 1]);
+                o2[pg & 1] = mfma4_or_sum(cur1, Ys[ka], o2[pg & 1]);
                 if constexpr (ka == N4 - 1) {
                     if (st_ok && 4 * pg + z < M && (!(QS_PAIR4C_ABLATE & 2) || o2[pg & 1] == 12345.678))
                         orow[(int64_t)(4 * pg) * g.out_row * 2] = o2[pg & 1];
@@ -320,11 +311,11 @@ __global__ __launch_bounds__(64 * stream_waves(N4)) void pair4s_kernel(const Pai
         constexpr int AHEAD = (NJ == 1 && N4 > 2) ? 2 : 1;  // groups between the read of the operands and their MFMAs
         static_assert(AHEAD < N4, "the read-ahead of a step's last groups stays behind its barrier");
         double opr[AHEAD + 1][2];
-        unroll<0, AHEAD>([&](auto T) __attribute__((always_inline)) {
+        unroll_chain<0, AHEAD>([&](auto T) __attribute__((always_inline)) {
             constexpr int t = decltype(T)::value;
             operands(T, opr[t % (AHEAD + 1)][0], opr[t % (AHEAD + 1)][1]);
         });
-        unroll<0, N4 * GPK>([&](auto T) __attribute__((always_inline)) {
+        unroll_chain<0, N4 * GPK>([&](auto T) __attribute__((always_inline)) {
             constexpr int t = decltype(T)::value, ka = t / GPK, gi = t % GPK, sl = t % (AHEAD + 1);
             if constexpr (gi == 0) {
                 // step start: row quad ka + 1 (the next pair's first after the last step) leaves its registers for its slot,
@@ -335,8 +326,7 @@ __global__ __launch_bounds__(64 * stream_waves(N4)) void pair4s_kernel(const Pai
                 else pf[ka % P] = fetch(rs_nx, v_nx, std::integral_constant<int, tq - N4>{});
             }
             if constexpr (gi == N4) {                       // between the two products: the step's barrier (see above)
-                __builtin_amdgcn_s_waitcnt(0xC07F);         // lgkmcnt(0); vmcnt untouched: the fetches stay in flight
-                __builtin_amdgcn_s_barrier();
+                lds_barrier();                              // (vmcnt untouched: the fetches stay in flight)
             }
             // (the read-ahead of the last groups of the LAST step reaches into the next pair's first row quad: slot
             // N4 & 1 of this unit's numbering, written at the start of that step, behind its barrier)
@@ -345,18 +335,18 @@ __global__ __launch_bounds__(64 * stream_waves(N4)) void pair4s_kernel(const Pai
             const double cur0 = opr[sl][0], cur1 = opr[sl][1];
             if constexpr (gi < N4) {                        // Y[ka] += In[ka][ks] . R[ks]
                 constexpr int ks = gi;
-                unroll<0, NJ>([&](auto J) __attribute__((always_inline)) {
+                unroll_chain<0, NJ>([&](auto J) __attribute__((always_inline)) {
                     constexpr int j = decltype(J)::value;
-                    yv[j] = mfma4(cur0, b1[ks][j], ks == 0 ? 0.0 : yv[j]);
+                    yv[j] = mfma4_or_sum(cur0, b1[ks][j], ks == 0 ? 0.0 : yv[j]);
                 });
                 if constexpr (!REAL_IN) {
-                    unroll<0, NJ>([&](auto J) __attribute__((always_inline)) {
+                    unroll_chain<0, NJ>([&](auto J) __attribute__((always_inline)) {
                         constexpr int j = decltype(J)::value;
-                        yv[j] = mfma4(cur1, b2[ks][j], yv[j]);
+                        yv[j] = mfma4_or_sum(cur1, b2[ks][j], yv[j]);
                     });
                 }
                 if constexpr (ks == N4 - 1) {
-                    unroll<0, NJ>([&](auto J) __attribute__((always_inline)) {
+                    unroll_chain<0, NJ>([&](auto J) __attribute__((always_inline)) {
                         constexpr int j = decltype(J)::value;
                         const double other = other_part(yv[j]);
                         ys[j] = part ? other : -other;
@@ -364,13 +354,13 @@ __global__ __launch_bounds__(64 * stream_waves(N4)) void pair4s_kernel(const Pai
                 }
             } else {                                        // Out[pg] += Lm[pg][ka] . Y[ka]
                 constexpr int pg = gi - N4;
-                unroll<0, NJ>([&](auto J) __attribute__((always_inline)) {
+                unroll_chain<0, NJ>([&](auto J) __attribute__((always_inline)) {
                     constexpr int j = decltype(J)::value;
-                    o[pg][j] = mfma4(cur0, yv[j], ka == 0 ? 0.0 : o[pg][j]);
+                    o[pg][j] = mfma4_or_sum(cur0, yv[j], ka == 0 ? 0.0 : o[pg][j]);
                 });
-                unroll<0, NJ>([&](auto J) __attribute__((always_inline)) {
+                unroll_chain<0, NJ>([&](auto J) __attribute__((always_inline)) {
                     constexpr int j = decltype(J)::value;
-                    o[pg][j] = mfma4(cur1, ys[j], o[pg][j]);
+                    o[pg][j] = mfma4_or_sum(cur1, ys[j], o[pg][j]);
                 });
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -378,10 +368,10 @@ __global__ __launch_bounds__(64 * stream_waves(N4)) void pair4s_kernel(const Pai
         // ---- store.  D: row z, block (item, part), column x.
         const unsigned it_g = unit * 2 + item;
         double* orow = g.out + ((int64_t)it_g * g.out_item + z * g.out_row + x * g.out_col) * 2 + part;
-        unroll<0, N4>([&](auto PG) __attribute__((always_inline)) {
+        unroll_chain<0, N4>([&](auto PG) __attribute__((always_inline)) {
             constexpr int pg = decltype(PG)::value;
             const int row = 4 * pg + z;
-            unroll<0, NJ>([&](auto J) __attribute__((always_inline)) {
+            unroll_chain<0, NJ>([&](auto J) __attribute__((always_inline)) {
                 constexpr int j = decltype(J)::value;
                 const int col = 4 * (jg0 + j) + x;
                 if (has(j) && it_g < g.nitems && row < M && col < M && (!(QS_PAIR4C_ABLATE & 2) || o[pg][j] == 12345.678))
@@ -397,16 +387,16 @@ __global__ __launch_bounds__(64 * stream_waves(N4)) void pair4s_kernel(const Pai
         voffs_of(unit + 2 * slots, v_nx);
         if constexpr (N4 % P != 0) {
             f64x2 t_[P];
-            unroll<0, P>([&](auto I) __attribute__((always_inline)) { t_[decltype(I)::value] = pf[(N4 + decltype(I)::value) % P]; });
-            unroll<0, P>([&](auto I) __attribute__((always_inline)) { pf[decltype(I)::value] = t_[decltype(I)::value]; });
+            unroll_chain<0, P>([&](auto I) __attribute__((always_inline)) { t_[decltype(I)::value] = pf[(N4 + decltype(I)::value) % P]; });
+            unroll_chain<0, P>([&](auto I) __attribute__((always_inline)) { pf[decltype(I)::value] = t_[decltype(I)::value]; });
         }
         if constexpr (N4 % NR != 0) {                       // the next pair's first row quad sits in slot N4 % NR of this numbering
             int t1[NR], t2[NR], tw[NR];
-            unroll<0, NR>([&](auto I) __attribute__((always_inline)) {
+            unroll_chain<0, NR>([&](auto I) __attribute__((always_inline)) {
                 constexpr int i = decltype(I)::value;
                 t1[i] = a1_of[(i + N4) % NR]; t2[i] = a2_of[(i + N4) % NR]; tw[i] = w_of[(i + N4) % NR];
             });
-            unroll<0, NR>([&](auto I) __attribute__((always_inline)) {
+            unroll_chain<0, NR>([&](auto I) __attribute__((always_inline)) {
                 constexpr int i = decltype(I)::value;
                 a1_of[i] = t1[i]; a2_of[i] = t2[i]; w_of[i] = tw[i];
             });

@@ -7,10 +7,9 @@
 //   (b, a):  item t = column (r, s), In_t = T2[:, :, r, s]       R = Ct^T, Lm = Ct     -> out[:, :, r, s]
 //
 // The fp64 sibling of the streamed complex kernel (qs_pair4c.hip, pair4s_kernel; basis_set.py:341-348).  The four blocks of
-// v_mfma_f64_4x4x4_4b_f64 (lane = x + 4 y + 16 z: A row x / block y / k z, B k z / block y / column x, D row z / block y /
-// column x) are four ITEMS.  Row quad ka of an item quad is used by one step only -- Y[ka] = In[ka] . R, then
-// Out[pg] += Lm[pg][ka] . Y[ka] for every row quad pg of the result (Y[ka] leaves the accumulators as the B operand of the
-// second product) -- so the item quads are not staged whole: they pass through a ring of TWO row-quad slots in LDS, fetched
+// v_mfma_f64_4x4x4_4b_f64 (the lane layouts and the parked-lane convention: qs_mfma4.h) are four ITEMS.  Row quad ka of an
+// item quad is used by one step only -- Y[ka] = In[ka] . R, then Out[pg] += Lm[pg][ka] . Y[ka] for every row quad pg of the
+// result (Y[ka] leaves the accumulators as the B operand of the second product) -- so the item quads are not staged whole: they pass through a ring of TWO row-quad slots in LDS, fetched
 // three row quads ahead through registers (one 16-byte buffer load per thread and row quad, across quad boundaries, no
 // vector ALU work), with one LDS-only workgroup barrier per step between its two products.  One wave per column group
 // (N4 waves, up to 1024 threads): three to four waves per SIMD cover each other's LDS latency and the dependent MFMAs.
@@ -24,27 +23,9 @@
 
 #pragma once
 
-#include <type_traits>
-
-#include "qs_common.h"
+#include "qs_mfma4.h"
 
 namespace qs {
-
-// f(I), f(I + 1), ... f(N - 1) with compile-time arguments, in this order (halving: the 1152 groups of a 96-orbital quad would
-// exceed the template recursion depth one at a time)
-template <int I, int N, class F>
-__device__ __forceinline__ void unroll_q(F&& f) {
-    if constexpr (N - I == 1) {
-        f(std::integral_constant<int, I>{});
-    } else if constexpr (N - I > 1) {
-        constexpr int MID = I + (N - I) / 2;
-        unroll_q<I, MID>(f);
-        unroll_q<MID, N>(f);
-    }
-}
-
-typedef double f64x2q __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4q __attribute__((ext_vector_type(4)));
 
 struct Quad4Args : FusedPass {};     // (its own name: the kernel symbols carry it)
 
@@ -52,10 +33,6 @@ struct Quad4Args : FusedPass {};     // (its own name: the kernel symbols carry 
 #ifndef QS_QUAD4S_ABLATE
 #define QS_QUAD4S_ABLATE 0
 #endif
-
-__device__ __forceinline__ double mfma4q(double a, double b, double c) {
-    return __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, c, 0, 0, 0);
-}
 
 // N4 = ceil(L / 4) = ceil(M / 4), 2 ... 24.  H = 1: a workgroup takes whole item quads, one wave per column group (N4 <= 16:
 // 1024 threads).  H = 2 (65 ... 96 orbitals): TWO workgroups per item quad, neighbours on one XCD, each with ceil(N4 / 2)
@@ -85,24 +62,21 @@ __global__ __launch_bounds__(64 * ((N4 + H - 1) / H)) void quad4s_kernel(const Q
     const int L = g.L, M = g.M;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int x = lane & 3, y = (lane >> 2) & 3, z = lane >> 4;
-    const int e_lane = z * 4 + x;
+    const Lane4 l4 = lane4(lane);
+    const int x = l4.x, y = l4.y, z = l4.z, e_lane = l4.e;
     const bool slab = g.in_col == 1;
 
     // units (item quads): every XCD a contiguous range, its workgroups neighbouring quads
     // (H = 2: workgroups 8 (2 q) + x and 8 (2 q + 1) + x of XCD x are the halves of the same quads)
-    const unsigned n_xcd = 8, xcd = blockIdx.x % n_xcd, slot = (blockIdx.x / n_xcd) / H, slots = (gridDim.x / n_xcd) / H;
-    const int half = (int)((blockIdx.x / n_xcd) % H);
-    const unsigned per = (g.ntuples + n_xcd - 1) / n_xcd;
-    const unsigned u_end = (xcd + 1) * per < g.ntuples ? (xcd + 1) * per : g.ntuples;
-    unsigned unit = xcd * per + slot;
+    const int half = (int)((blockIdx.x / 8) % H);
+    const XcdRange units = xcd_range(g.ntuples, H);
+    const unsigned u_end = units.end, slots = units.stride;
+    unsigned unit = units.first;
     if (unit >= u_end) return;                              // (the whole workgroup, before any barrier)
 
     // ---- the fetch: thread t < 8 K4 owns one 16-byte piece of every row quad -- two adjacent k of (item, row) when the
     // items are slabs, two adjacent items of (row, k) when they are columns.  Buffer loads: the quad's base in the
-    // descriptor, the piece's place in the lane offset (a lane without a piece is parked past num_records: the hardware
-    // returns 0.0), the row quad in the scalar offset.
-    constexpr unsigned kParked = 0x80000000u;
+    // descriptor, the piece's place in the lane offset (a lane without a piece is parked), the row quad in the scalar offset.
     int f_it, f_r, f_k;                                     // first element of the piece
     if (slab) { f_k = 2 * (tid % (K4 / 2)); f_r = (tid / (K4 / 2)) & 3; f_it = tid / (2 * K4); }
     else { f_it = 2 * (tid & 1); f_k = (tid >> 1) % K4; f_r = (tid >> 1) / K4; }
@@ -113,10 +87,7 @@ __global__ __launch_bounds__(64 * ((N4 + H - 1) / H)) void quad4s_kernel(const Q
     const int f_pos0 = pos_of(f_it, f_r, f_k);
     const int f_pos1 = slab ? f_pos0 + 1 : pos_of(f_it + 1, f_r, f_k);
     auto rsrc_of = [&](unsigned u) __attribute__((always_inline)) {
-        const uint64_t pb = reinterpret_cast<uint64_t>(g.in + (int64_t)(u < u_end ? u : 0) * 4 * g.in_item);
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)pb);
-        const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(pb >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)hi << 32) | lo), (short)0, 0x7fffffff, 0x00020000);
+        return tuple_rsrc(g.in, u < u_end ? u : 0, 4, g.in_item);
     };
     // Lane offsets of quad u: [0] its row quads but the last, [1] the last one (rows beyond L do not exist).  A piece whose
     // FIRST element exists and whose second does not -- the last k of an odd L in a slab, the last item of an odd item
@@ -133,15 +104,15 @@ __global__ __launch_bounds__(64 * ((N4 + H - 1) / H)) void quad4s_kernel(const Q
     };
     auto fetch = [&](auto rs, const unsigned (&v)[2], auto KA) __attribute__((always_inline)) {
         constexpr int ka = decltype(KA)::value;
-        if constexpr (QS_QUAD4S_ABLATE & 1) return f64x2q{1.0 + ka, 0.5};
-        const u32x4q q = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)v[ka == N4 - 1], (int)(ka * quad_step), 0);
-        return __builtin_bit_cast(f64x2q, q);
+        if constexpr (QS_QUAD4S_ABLATE & 1) return f64x2{1.0 + ka, 0.5};
+        const u32x4 q = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)v[ka == N4 - 1], (int)(ka * quad_step), 0);
+        return __builtin_bit_cast(f64x2, q);
     };
-    auto settle = [&](int w0, int w1, f64x2q v, bool shifted) __attribute__((always_inline)) {
+    auto settle = [&](int w0, int w1, f64x2 v, bool shifted) __attribute__((always_inline)) {
         if (loader) {
-            const f64x2q pr = shifted ? f64x2q{v.y, 0.0} : v;
+            const f64x2 pr = shifted ? f64x2{v.y, 0.0} : v;
             // (slabs: the two elements are neighbours in the slot -- w0 is even, Lp, ITEM, PLANE and SLOT are -- one 16-byte write)
-            if (slab) *reinterpret_cast<f64x2q*>(ring + w0) = pr;
+            if (slab) *reinterpret_cast<f64x2*>(ring + w0) = pr;
             else { ring[w0] = pr.x; ring[w1] = pr.y; }
         }
     };
@@ -158,7 +129,7 @@ __global__ __launch_bounds__(64 * ((N4 + H - 1) / H)) void quad4s_kernel(const Q
     // ---- this wave's column group and its B operands of the first product: registers for the whole launch
     const int jg = half * NW + wave;             // (a wave past the last group -- odd N4, second half -- multiplies zeros and stores nothing)
     double bq[N4];
-    f64x2q pf[P];                                // pf[ka % P] holds row quad ka + 1 at the start of step ka
+    f64x2 pf[P];                                // pf[ka % P] holds row quad ka + 1 at the start of step ka
     auto rs_cur = rsrc_of(unit), rs_nx = rsrc_of(unit + slots);
     unsigned v_cur[2], v_nx[2];
     bool sh_cur, sh_nx;
@@ -167,23 +138,23 @@ __global__ __launch_bounds__(64 * ((N4 + H - 1) / H)) void quad4s_kernel(const Q
     {
         constexpr int NF = (TABLE + NTH - 1) / NTH;
         double l_v[NF];
-        unroll_q<0, NF>([&](auto I) __attribute__((always_inline)) {
+        unroll<0, NF>([&](auto I) __attribute__((always_inline)) {
             constexpr int i = decltype(I)::value;
             const int f = tid + NTH * i;
             const int e = f & 15, blk = f >> 4, hi = blk / N4, lo = blk % N4, ez = e >> 2, ex = e & 3;
             const int p_ = 4 * hi + ex, a = 4 * lo + ez;                    // Lm[4 hi + ex][4 lo + ez]
             l_v[i] = (f < TABLE && p_ < M && a < L) ? g.Lm[p_ * g.l_sp + a * g.l_sa] : 0.0;
         });
-        unroll_q<0, N4>([&](auto KS) __attribute__((always_inline)) {
+        unroll<0, N4>([&](auto KS) __attribute__((always_inline)) {
             constexpr int ks = decltype(KS)::value;
             const int k = 4 * ks + z, col = 4 * jg + x;
             bq[ks] = (k < L && col < M) ? g.R[k * g.r_sk + col * g.r_sj] : 0.0;
         });
-        const f64x2q q0 = fetch(rs_cur, v_cur, std::integral_constant<int, 0>{});
-        unroll_q<0, P>([&](auto I) __attribute__((always_inline)) {
+        const f64x2 q0 = fetch(rs_cur, v_cur, std::integral_constant<int, 0>{});
+        unroll<0, P>([&](auto I) __attribute__((always_inline)) {
             pf[decltype(I)::value] = fetch(rs_cur, v_cur, std::integral_constant<int, 1 + decltype(I)::value>{});
         });
-        unroll_q<0, NF>([&](auto I) __attribute__((always_inline)) {
+        unroll<0, NF>([&](auto I) __attribute__((always_inline)) {
             constexpr int i = decltype(I)::value;
             const int f = tid + NTH * i;
             if (f < TABLE) ltab[f] = l_v[i];
@@ -210,11 +181,11 @@ __global__ __launch_bounds__(64 * ((N4 + H - 1) / H)) void quad4s_kernel(const Q
         constexpr int AHEAD = N4 > QS_QUAD4S_AHEAD ? QS_QUAD4S_AHEAD : N4 - 1;          // groups between the read of an operand and its MFMA
         static_assert(AHEAD < N4, "the read-ahead into the next row quad's slot starts behind the step's barrier");
         double opr[AHEAD + 1];
-        unroll_q<0, AHEAD>([&](auto T) __attribute__((always_inline)) { opr[decltype(T)::value % (AHEAD + 1)] = operand(T); });
+        unroll<0, AHEAD>([&](auto T) __attribute__((always_inline)) { opr[decltype(T)::value % (AHEAD + 1)] = operand(T); });
         const unsigned it_g = unit * 4 + y;                 // D: row z, block y = item, column x
         double* orow = g.out + (int64_t)it_g * g.out_item + z * g.out_row + x * g.out_col + (int64_t)(4 * jg) * g.out_col;
         const bool st_ok = it_g < g.nitems && 4 * jg + x < M;
-        unroll_q<0, 2 * NG>([&](auto T) __attribute__((always_inline)) {
+        unroll<0, 2 * NG>([&](auto T) __attribute__((always_inline)) {
             constexpr int t = decltype(T)::value, sl = t % (AHEAD + 1);
             if constexpr (t < NG && t % N4 == 0) {
                 // step start: row quad ka + 1 (the next quad's first after the last step) leaves its registers for its slot,
@@ -231,17 +202,16 @@ __global__ __launch_bounds__(64 * ((N4 + H - 1) / H)) void quad4s_kernel(const Q
                 // barrier; and it was last read in step ka - 2, which every wave had finished when it arrived at the barrier
                 // of step ka - 1 (three slots: with two, a wave still in step ka - 1 would be reading it).  It waits for the
                 // wave's LDS traffic only: the fetches stay in flight.
-                __builtin_amdgcn_s_waitcnt(0xC07F);         // lgkmcnt(0), vmcnt / expcnt untouched
-                __builtin_amdgcn_s_barrier();
+                lds_barrier();
             }
             if constexpr (t + AHEAD < 2 * NG) opr[(t + AHEAD) % (AHEAD + 1)] = operand(std::integral_constant<int, t + AHEAD>{});
             const double cur = opr[sl];
             if constexpr (t < NG) {                         // Y[ka] += In[ka][ks] . R[ks]
                 constexpr int ka = t / N4, ks = t % N4;
-                Y[ka] = mfma4q(cur, bq[ks], ks == 0 ? 0.0 : Y[ka]);
+                Y[ka] = mfma4(cur, bq[ks], ks == 0 ? 0.0 : Y[ka]);
             } else {                                        // Out[pg] += Lm[pg][ka] . Y[ka]
                 constexpr int pg = (t - NG) / N4, ka = (t - NG) % N4;
-                o2[pg & 1] = mfma4q(cur, Y[ka], ka == 0 ? 0.0 : o2[pg & 1]);
+                o2[pg & 1] = mfma4(cur, Y[ka], ka == 0 ? 0.0 : o2[pg & 1]);
                 if constexpr (ka == N4 - 1) {
                     if (st_ok && 4 * pg + z < M && (!(QS_QUAD4S_ABLATE & 2) || o2[pg & 1] == 12345.678))
                         orow[(int64_t)(4 * pg) * g.out_row] = o2[pg & 1];
@@ -256,17 +226,17 @@ __global__ __launch_bounds__(64 * ((N4 + H - 1) / H)) void quad4s_kernel(const Q
         rs_nx = rsrc_of(unit + 2 * slots);
         voffs_of(unit + 2 * slots, v_nx, sh_nx);
         if constexpr (N4 % P != 0) {
-            f64x2q t_[P];
-            unroll_q<0, P>([&](auto I) __attribute__((always_inline)) { t_[decltype(I)::value] = pf[(N4 + decltype(I)::value) % P]; });
-            unroll_q<0, P>([&](auto I) __attribute__((always_inline)) { pf[decltype(I)::value] = t_[decltype(I)::value]; });
+            f64x2 t_[P];
+            unroll<0, P>([&](auto I) __attribute__((always_inline)) { t_[decltype(I)::value] = pf[(N4 + decltype(I)::value) % P]; });
+            unroll<0, P>([&](auto I) __attribute__((always_inline)) { pf[decltype(I)::value] = t_[decltype(I)::value]; });
         }
         if constexpr (N4 % NR != 0) {                       // the next quad's first row quad sits in slot N4 % NR of this numbering
             int ta[NR], t0[NR], t1[NR];
-            unroll_q<0, NR>([&](auto I) __attribute__((always_inline)) {
+            unroll<0, NR>([&](auto I) __attribute__((always_inline)) {
                 constexpr int i = decltype(I)::value;
                 ta[i] = a_of[(i + N4) % NR]; t0[i] = w0_of[(i + N4) % NR]; t1[i] = w1_of[(i + N4) % NR];
             });
-            unroll_q<0, NR>([&](auto I) __attribute__((always_inline)) {
+            unroll<0, NR>([&](auto I) __attribute__((always_inline)) {
                 constexpr int i = decltype(I)::value;
                 a_of[i] = ta[i]; w0_of[i] = t0[i]; w1_of[i] = t1[i];
             });

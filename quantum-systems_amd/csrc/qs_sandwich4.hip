@@ -14,10 +14,9 @@
 //     16-wide form per product (1.38x -> 1.06x of the unpadded work);
 //   * the four blocks are four ITEMS (four adjacent slabs / four adjacent columns), so nothing is replicated in
 //     the tensor operand and no remainder logic exists anywhere: every loop runs ceil(l / 4) times;
-//   * its accumulator layout is its own B-operand layout (lane = x + 4 y + 16 z: A holds row x, block y, k z;
-//     B holds k z, block y, column x; D holds row z, block y, column x -- tools/probe_mfma4_layout.hip), so
-//     Y = In . R goes from the accumulators straight into Lm . Y: no LDS round trip, no shuffle -- and the
-//     per-element sums are the same k-ordered FMA chains as in the 16-wide kernels (bit-identical results).
+//   * its accumulator layout is its own B-operand layout (the lane layouts: qs_mfma4.h), so Y = In . R goes from
+//     the accumulators straight into Lm . Y: no LDS round trip, no shuffle -- and the per-element sums are the
+//     same k-ordered FMA chains as in the 16-wide kernels (bit-identical results).
 //
 // Work split: a workgroup takes an item quad; its four waves (one per SIMD) take the column groups of R in
 // chunks of <= 4 groups and rotate the chunks from round to round (14 groups = 4 + 4 + 3 + 3 would otherwise
@@ -34,14 +33,12 @@
 //   * s_waitcnt, SALU: free; s_nop n: n + 1 cycles; ANY VALU instruction (v_add_u32): 12 cycles.
 // Hence: fragments are fetched two at a time (16 bytes per lane), every memory instruction has an MFMA of its
 // own to hide behind (a sched_barrier after each), and the steady state has no VALU instruction: addresses are one
-// lane offset (variants: interior / last row quad / last k pair / both, with out-of-range lanes parked past
-// num_records so that the hardware returns 0.0 / drops the store) plus scalar offsets.
+// lane offset (variants: interior / last row quad / last k pair / both, with out-of-range lanes parked, kParked of
+// qs_mfma4.h) plus scalar offsets.
 // Algorithmic bytes per launch: 8 (L^2 + M^2) per item; roofline: HBM below l ~ 64 (the matrix pipe needs
 // 2 x 2 x ceil(l/4)^3 x 16 cycles per item quad per CU).
 
-#include <type_traits>
-
-#include "qs_common.h"
+#include "qs_mfma4.h"
 #include "qs_sandwich4.h"
 
 // Development builds only (never defined in the shipped library): bit mask of parts to leave out, to find
@@ -55,42 +52,11 @@ namespace qs {
 
 namespace {
 
-template <int I, int N, class F>
-__device__ __forceinline__ void unroll(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        unroll<I + 1, N>(f);
-    }
-}
+QS_TRACE_SYMBOLS(qs_s4_trace)
+#define QS_S4_STAMP(tag) QS_TRACE_STAMP(qs_s4_trace, tag)
 
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-
-#ifdef QS_S4_TRACE      // development: shader-clock stamps of one workgroup's wave 0 at every step (qs_s4_trace symbol)
-__device__ unsigned long long qs_s4_trace[4096];
-__device__ unsigned qs_s4_trace_n;
-// the stamp index lives in a register (a counter in memory would put a global load in front of every stamp)
-#define QS_S4_STAMP(tag)                                                                                  \
-    if (blockIdx.x == QS_S4_TRACE && wave == 0) {                                                         \
-        if (lane == 0 && tr_n < 4096) qs_s4_trace[tr_n] = (__builtin_amdgcn_s_memtime() << 8) | (tag);    \
-        ++tr_n;                                                                                           \
-    }
-#define QS_S4_TRACE_DONE                                                                     \
-    if (blockIdx.x == QS_S4_TRACE && wave == 0 && lane == 0) {                                \
-        qs_s4_trace_n = tr_n;                                                                \
-        qs_s4_trace[4095] = __builtin_amdgcn_s_memrealtime() - tr_real0;     /* 100 MHz ticks, entry to exit */ \
-    }
-#else
-#define QS_S4_STAMP(tag)
-#define QS_S4_TRACE_DONE
-#endif
-
-constexpr unsigned kParked = 0x80000000u;     // lane offset of an out-of-range lane (>= num_records)
-
-__device__ __forceinline__ double mfma4(double a, double b, double c) {
-    if constexpr (QS_S4_ABLATE & 16) return a + b + c;
-    return __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, c, 0, 0, 0);
+__device__ __forceinline__ double mfma4_or_sum(double a, double b, double c) {
+    return (QS_S4_ABLATE & 16) ? a + b + c : mfma4(a, b, c);
 }
 
 }  // namespace
@@ -116,13 +82,10 @@ __global__ __launch_bounds__(256, 1) void sandwich4_kernel(const S4Args g) {
     const int L = g.L, M = g.M;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    unsigned tr_n = 0;
-    (void)tr_n;
-#ifdef QS_S4_TRACE
-    const unsigned long long tr_real0 = __builtin_amdgcn_s_memrealtime();
-#endif
+    QS_TRACE_BEGIN
     if constexpr (QS_S4_ABLATE & 64) return;
     QS_S4_STAMP(253)
+    // (lane4() of qs_mfma4.h spelled out: through the struct the compiler schedules this kernel differently)
     const int x = lane & 3, y = (lane >> 2) & 3, z = lane >> 4;
     const int e_lane = z * 4 + x;
     const int rl = L & 3, rm = M & 3;      // valid rows / columns of the last quad (0 = all four)
@@ -135,11 +98,11 @@ __global__ __launch_bounds__(256, 1) void sandwich4_kernel(const S4Args g) {
     //                     (b, a) pass), and no fragment is fetched by more than one wave.  The chunk of a unit
     //                     rotates with the round, so every workgroup sees all chunk sizes.
     const bool grouped = g.mode & 1, step_barrier = (g.mode & 3) == 3;
-    const unsigned n_xcd = 8, xcd = blockIdx.x % n_xcd, slot = blockIdx.x / n_xcd, slots = gridDim.x / n_xcd;
     const unsigned ngroups = (g.ntuples + 3) / 4;
     const unsigned nunits = grouped ? ngroups * NCH : g.ntuples;
     // (grouped: the chunk units of a group must fall into the same round of the same XCD, or the rotation would
     // hand one chunk out twice: an XCD's range and the workgroup stride are whole groups)
+    const unsigned n_xcd = 8, xcd = blockIdx.x % n_xcd, slot = blockIdx.x / n_xcd, slots = gridDim.x / n_xcd;
     unsigned per = (nunits + n_xcd - 1) / n_xcd;
     if (grouped) per = (per + NCH - 1) / NCH * NCH;
     const unsigned u_end = (xcd + 1) * per < nunits ? (xcd + 1) * per : nunits;
@@ -155,13 +118,6 @@ __global__ __launch_bounds__(256, 1) void sandwich4_kernel(const S4Args g) {
     const unsigned ka_step = (unsigned)(4 * g.in_row * 8), pair_step = (unsigned)(8 * g.in_col * 8);
     const unsigned pg_step = (unsigned)(4 * g.out_row * 8), jg_step = (unsigned)(4 * g.out_col * 8);
 
-    auto rsrc = [&](const double* base, unsigned quad, int64_t item_stride) __attribute__((always_inline)) {
-        const uint64_t p = reinterpret_cast<uint64_t>(base + (int64_t)quad * 4 * item_stride);
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)p);
-        const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(p >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)hi << 32) | lo), (short)0,
-                                                 0x7fffffff, 0x00020000);
-    };
     // An In fragment (A operand: row x, block y, k z) is FETCHED in memory order and put into MFMA lane order on
     // its way through LDS: the texture-address unit only merges ADJACENT lanes, and in the MFMA order adjacent
     // lanes are rows (d, c: 440 bytes apart) -- 64 separate accesses per instruction, which bound the first
@@ -182,14 +138,6 @@ __global__ __launch_bounds__(256, 1) void sandwich4_kernel(const S4Args g) {
         f_item[0] = 2 * e; f_item[1] = 2 * e + 1;
         f_k[0] = f_k[1] = (lane >> 1) & 3;
     }
-    // Position of element (row, item, k) of a fragment in its 512-byte transit slot (slot parity par): 128-byte line
-    // k, 8-byte bank pair (row ^ 2 (k & 1)) + 4 (item ^ ((k >> 1) | 2 par)).  Any 16 adjacent lanes that go to LDS
-    // together -- (row, item) at fixed k when the MFMA lanes read, either of the two fetch layouts when the fetch
-    // lanes write their first or their second element -- hit 16 different bank pairs (searched over the XOR masks
-    // that are linear in (k, par)); the plain lane order would put four lanes of every write on each bank.
-    auto slot_pos = [](int row, int item, int k, int par) __attribute__((always_inline)) {
-        return (unsigned)(16 * k + ((row ^ ((k & 1) << 1)) + 4 * (item ^ ((k >> 1) | (par << 1)))));
-    };
     double* const my_transit = transit + wave * (2 * NS * 64);
     const unsigned rd_even = slot_pos(x, y, z, 0), rd_odd = slot_pos(x, y, z, 1);
     // Lane offsets of a fetch (v: bit 0 last row quad, bit 1 last k pair) and where its two elements go in the transit
@@ -243,10 +191,6 @@ __global__ __launch_bounds__(256, 1) void sandwich4_kernel(const S4Args g) {
 
     // (s_row: the row quad's offset, made opaque once per step -- or the compiler keeps all ceil(l/4)^2 sums of row
     // and pair offsets in SGPRs and spills them)
-    auto opaque = [](unsigned v) __attribute__((always_inline)) {
-        asm volatile("" : "+s"(v));
-        return v;
-    };
     // the fragment pair m of a row quad: lane offset v, scalar offset row quad + pair
     auto fetch_pair = [&](auto rs, unsigned v, unsigned s_row, auto MP, double& d0, double& d1) __attribute__((always_inline)) {
         if constexpr (QS_S4_ABLATE & 1) { d0 = 1.0 + decltype(MP)::value; d1 = 0.5; }
@@ -349,8 +293,8 @@ __global__ __launch_bounds__(256, 1) void sandwich4_kernel(const S4Args g) {
                     unroll<0, N4>([&](auto KS) __attribute__((always_inline)) {
                         constexpr int ks = decltype(KS)::value;
                         if constexpr (ka & 1)
-                            Y[ka - 1][JX] = mfma4(ring[st ^ 1][ks], bf[ks][JX], ks == 0 ? 0.0 : Y[ka - 1][JX]);
-                        Y[ka][JX] = mfma4(ring[st][ks], bf[ks][JX], ks == 0 ? 0.0 : Y[ka][JX]);
+                            Y[ka - 1][JX] = mfma4_or_sum(ring[st ^ 1][ks], bf[ks][JX], ks == 0 ? 0.0 : Y[ka - 1][JX]);
+                        Y[ka][JX] = mfma4_or_sum(ring[st][ks], bf[ks][JX], ks == 0 ? 0.0 : Y[ka][JX]);
                     });
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -359,7 +303,7 @@ __global__ __launch_bounds__(256, 1) void sandwich4_kernel(const S4Args g) {
                 constexpr int ks = decltype(KS)::value, m = ks / 2;
                 unroll<0, NJM>([&](auto J) __attribute__((always_inline)) {
                     constexpr int j = decltype(J)::value;
-                    Y[ka][j] = mfma4(ring[st][ks], bf[ks][j], ks == 0 ? 0.0 : Y[ka][j]);
+                    Y[ka][j] = mfma4_or_sum(ring[st][ks], bf[ks][j], ks == 0 ? 0.0 : Y[ka][j]);
                     if constexpr (!(ks & 1)) {
                         if constexpr (j == 0) my_transit[m * 128 + ws[m == NP - 1 ? 2 : 0]] = stg[sa][ks];
                         if constexpr (j == 1) my_transit[m * 128 + ws[m == NP - 1 ? 3 : 1]] = stg[sa][ks + 1];
@@ -398,8 +342,8 @@ __global__ __launch_bounds__(256, 1) void sandwich4_kernel(const S4Args g) {
                     unroll<0, N4>([&](auto KA) __attribute__((always_inline)) {
                         constexpr int ka = decltype(KA)::value;
                         if constexpr (pg & 1)
-                            ov[b ^ 1][JX] = mfma4(lf[b ^ 1][ka], Y[ka][JX], ka == 0 ? 0.0 : ov[b ^ 1][JX]);
-                        ov[b][JX] = mfma4(lf[b][ka], Y[ka][JX], ka == 0 ? 0.0 : ov[b][JX]);
+                            ov[b ^ 1][JX] = mfma4_or_sum(lf[b ^ 1][ka], Y[ka][JX], ka == 0 ? 0.0 : ov[b ^ 1][JX]);
+                        ov[b][JX] = mfma4_or_sum(lf[b][ka], Y[ka][JX], ka == 0 ? 0.0 : ov[b][JX]);
                     });
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -408,7 +352,7 @@ __global__ __launch_bounds__(256, 1) void sandwich4_kernel(const S4Args g) {
                 constexpr int ka = decltype(KA)::value;
                 unroll<0, NJM>([&](auto J) __attribute__((always_inline)) {
                     constexpr int j = decltype(J)::value;
-                    ov[b][j] = mfma4(lf[b][ka], Y[ka][j], ka == 0 ? 0.0 : ov[b][j]);
+                    ov[b][j] = mfma4_or_sum(lf[b][ka], Y[ka][j], ka == 0 ? 0.0 : ov[b][j]);
                     if constexpr (j == 0 && pg + 1 < N4) lf[b ^ 1][ka] = ltab[((pg + 1) * N4 + ka) * 16 + e_lane];
                     if constexpr (j == 1 && pg >= 1 && (ka & 1) && ka / 2 < NJ)
                         store_frag(std::integral_constant<int, pg - 1>{}, std::integral_constant<int, (ka / 2) % NJ>{},
@@ -433,7 +377,7 @@ __global__ __launch_bounds__(256, 1) void sandwich4_kernel(const S4Args g) {
     };
 
     unsigned v_in[4], v_nx[4], w_in[4], w_nx[4], v_out[4];
-    auto rs_in = rsrc(g.in - 1, iq < g.ntuples ? iq : 0, g.in_item);
+    auto rs_in = tuple_rsrc(g.in - 1, iq < g.ntuples ? iq : 0, 4, g.in_item);
     in_offsets(iq, !idle && iq < g.ntuples, v_in, w_in);
     {   // every thread issues all its loads before the first LDS write (a load-store-load chain would pay the
         // memory latency ceil(l/4)^2/16 times before the first MFMA).  Thread t takes element t & 15 of the 4 x 4
@@ -441,7 +385,7 @@ __global__ __launch_bounds__(256, 1) void sandwich4_kernel(const S4Args g) {
         // ~3.5k cycles here on 64-bit multiply-adds and divisions by N4), and a block or element that does not exist
         // is a parked buffer offset that reads 0.0.
         constexpr int NF = (N4 * N4 + 15) / 16;
-        const auto rs_R = rsrc(g.R, 0, 0), rs_L = rsrc(g.Lm, 0, 0);
+        const auto rs_R = uniform_rsrc((uint64_t)g.R), rs_L = uniform_rsrc((uint64_t)g.Lm);
         const int ez = (tid >> 2) & 3, ex = tid & 3, b0 = tid >> 4;        // b0 < 16 <= 3 N4
         int hi = (b0 >= N4) + (b0 >= 2 * N4), lo = b0 - hi * N4;
         const int r_sk = (int)g.r_sk, r_sj = (int)g.r_sj, l_sp = (int)g.l_sp, l_sa = (int)g.l_sa;
@@ -493,9 +437,9 @@ __global__ __launch_bounds__(256, 1) void sandwich4_kernel(const S4Args g) {
         const unsigned nu = unit + slots;
         const unsigned nq = nu < u_end ? quad_of(nu) : g.ntuples;
         const bool more = nq < g.ntuples;
-        auto rs_nx = rsrc(g.in - 1, more ? nq : 0, g.in_item);
+        auto rs_nx = tuple_rsrc(g.in - 1, more ? nq : 0, 4, g.in_item);
         in_offsets(nq, more, v_nx, w_nx);
-        auto rs_out = rsrc(g.out, iq < g.ntuples ? iq : 0, g.out_item);
+        auto rs_out = tuple_rsrc(g.out, iq < g.ntuples ? iq : 0, 4, g.out_item);
         out_offsets(iq, v_out);
         const int c = chunk_of(unit, round);
         const int jg0 = chunk_first(c);
@@ -516,7 +460,7 @@ __global__ __launch_bounds__(256, 1) void sandwich4_kernel(const S4Args g) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) { v_in[i] = v_nx[i]; w_in[i] = w_nx[i]; }
     }
-    QS_S4_TRACE_DONE
+    QS_TRACE_DONE(qs_s4_trace)
 }
 
 template <int N4>
@@ -621,18 +565,4 @@ int sandwich4_try(int dtype, const FusedPass& pass, int dry_run, hipStream_t str
 
 }  // namespace qs
 
-#ifdef QS_S4_TRACE
-extern "C" int qs_s4_trace_reset(void) {
-    unsigned zero = 0;
-    return (int)hipMemcpyToSymbol(HIP_SYMBOL(qs::qs_s4_trace_n), &zero, sizeof(zero));
-}
-extern "C" int qs_s4_trace_read(void* dst) {      // dst: device buffer of 4097 x 8 bytes: count, stamps
-    unsigned n = 0;
-    (void)hipMemcpyFromSymbol(&n, HIP_SYMBOL(qs::qs_s4_trace_n), sizeof(n));
-    unsigned long long nn = n;
-    (void)hipMemcpy(dst, &nn, 8, hipMemcpyHostToDevice);
-    void* src = nullptr;
-    (void)hipGetSymbolAddress(&src, HIP_SYMBOL(qs::qs_s4_trace));
-    return (int)hipMemcpy((char*)dst + 8, src, 4096 * 8, hipMemcpyDeviceToDevice);
-}
-#endif
+QS_TRACE_EXPORTS(qs_s4_trace)

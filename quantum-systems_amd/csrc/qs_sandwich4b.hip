@@ -1,5 +1,6 @@
 // Out_t = Lm . In_t . R for item quads of slabs (see qs_sandwich4.hip for the product, the 4-wide fp64 matrix
-// instruction, the lane layouts and what may ride between two MFMAs): the BALANCED form with a COOPERATIVE fetch.
+// instruction and what may ride between two MFMAs, qs_mfma4.h for the lane layouts and the parked-lane convention): the
+// BALANCED form with a COOPERATIVE fetch.
 //
 // In qs_sandwich4.hip the four waves of a workgroup take column chunks of 4, 4, 3, 3 groups of one item quad
 // (ceil(l/4) = 14) and every wave fetches every In fragment for itself: 28 vector memory instructions per step and
@@ -16,9 +17,7 @@
 //   * with two fragment pairs per wave in flight instead of seven, the fetch registers are a sixth of the old ones.
 // Per-element sums are the same k-ordered FMA chains: results are bit-identical to the other kernels'.
 
-#include <type_traits>
-
-#include "qs_common.h"
+#include "qs_mfma4.h"
 
 // cache policy of the stores of the result (development: -DQS_S4B_STORE_AUX=n; 0 = default, 2 = non-temporal, 1 / 16 / 17 = sc0 / sc1 / both)
 #ifndef QS_S4B_STORE_AUX
@@ -40,47 +39,8 @@ namespace qs {
 
 namespace {
 
-template <int I, int N, class F>
-__device__ __forceinline__ void unroll_b(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        unroll_b<I + 1, N>(f);
-    }
-}
-
-typedef unsigned u32x2b __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4b __attribute__((ext_vector_type(4)));
-typedef double f64x2b __attribute__((ext_vector_type(2)));
-
-constexpr unsigned kParkedB = 0x80000000u;     // lane offset of an out-of-range lane (>= num_records)
-
-#ifdef QS_S4_TRACE      // development: shader-clock stamps of one workgroup's wave 0 (tools/trace_s4.py)
-__device__ unsigned long long qs_s4b_trace[4096];
-__device__ unsigned qs_s4b_trace_n;
-#define QS_S4B_STAMP(tag)                                                                                 \
-    if (blockIdx.x == QS_S4_TRACE && wave == 0) {                                                         \
-        if (lane == 0 && tr_n < 4096) qs_s4b_trace[tr_n] = (__builtin_amdgcn_s_memtime() << 8) | (tag);   \
-        ++tr_n;                                                                                           \
-    }
-#define QS_S4B_TRACE_DONE                                                                    \
-    if (blockIdx.x == QS_S4_TRACE && wave == 0 && lane == 0) {                                \
-        qs_s4b_trace_n = tr_n;                                                               \
-        qs_s4b_trace[4095] = __builtin_amdgcn_s_memrealtime() - tr_real0;                    \
-    }
-#else
-#define QS_S4B_STAMP(tag)
-#define QS_S4B_TRACE_DONE
-#endif
-
-__device__ __forceinline__ double mfma4b(double a, double b, double c) {
-    return __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, c, 0, 0, 0);
-}
-
-// workgroup barrier that waits for this wave's LDS traffic only (a __syncthreads would also drain the fetches in flight)
-__device__ __forceinline__ void lds_barrier() {
-    __builtin_amdgcn_s_waitcnt(0xC07F);        // lgkmcnt(0), vmcnt / expcnt untouched
-    __builtin_amdgcn_s_barrier();
-}
+QS_TRACE_SYMBOLS(qs_s4b_trace)
+#define QS_S4B_STAMP(tag) QS_TRACE_STAMP(qs_s4b_trace, tag)
 
 }  // namespace
 
@@ -106,31 +66,24 @@ __global__ __launch_bounds__(256, 1) void sandwich4b_kernel(const S4Args g) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int pair = wave >> 1, mpar = wave & 1;
+    // (lane4() of qs_mfma4.h spelled out: through the struct the compiler schedules this kernel differently)
     const int x = lane & 3, y = (lane >> 2) & 3, z = lane >> 4;
     const int e_lane = z * 4 + x;
-    unsigned tr_n = 0;
-    (void)tr_n;
-#ifdef QS_S4_TRACE
-    const unsigned long long tr_real0 = __builtin_amdgcn_s_memrealtime();
-#endif
+    QS_TRACE_BEGIN
     QS_S4B_STAMP(253)
 
     // ---- work units = item quads.  Every XCD takes a contiguous range and neighbouring workgroups of an XCD take
     // neighbouring quads.
-    const unsigned n_xcd = 8, xcd = blockIdx.x % n_xcd, slot = blockIdx.x / n_xcd, slots = gridDim.x / n_xcd;
     const unsigned nmain = g.tail_parts ? g.tail_first : g.ntuples;      // (with a tail: a whole number of rounds of the grid)
-    const unsigned per = (nmain + n_xcd - 1) / n_xcd;
-    const unsigned u_end = (xcd + 1) * per < nmain ? (xcd + 1) * per : nmain;
-    unsigned iq = xcd * per + slot;
+    const XcdRange units = xcd_range(nmain);
+    const unsigned u_end = units.end, slots = units.stride;
+    unsigned iq = units.first;
     if (iq >= u_end) return;                           // (whole workgroup: before any barrier)
 
     const unsigned ka_step = (unsigned)(4 * g.in_row * 8), pair_step = 64u;      // (in_col == 1: a pair is 8 k)
     const unsigned pg_step = (unsigned)(4 * g.out_row * 8), jg_step = (unsigned)(4 * g.out_col * 8);
 
     auto rsrc = [&](const double* base, unsigned quad, int64_t item_stride) __attribute__((always_inline)) {
-        const uint64_t p = reinterpret_cast<uint64_t>(base + (int64_t)quad * 4 * item_stride);
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)p);
-        const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(p >> 32));
         // (development, round 4: -DQS_S4B_ABLATE_LOADS / _STORES give the tensor's descriptors a zero range -- loads answer with
         // zeros and stores are dropped without touching memory: the kernel's skeleton, profiles/r04_small_basis_bound.txt)
         int range = 0x7fffffff;
@@ -140,14 +93,11 @@ __global__ __launch_bounds__(256, 1) void sandwich4b_kernel(const S4Args g) {
 #ifdef QS_S4B_ABLATE_STORES
         if (base == g.out) range = 0;
 #endif
-        return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)hi << 32) | lo), (short)0, range, 0x00020000);
+        return tuple_rsrc(base, quad, 4, item_stride, range);
     };
     // Fetch layout of a fragment pair (qs_sandwich4.hip): lane = h + 4 row + 16 item; k = 8 m + 2 h, 2 h + 1 -- 16 bytes
     // per lane, 64-byte runs; fragment 2 m + (h >> 1).
     const int f_h = lane & 3, f_row = (lane >> 2) & 3, f_item = lane >> 4, f_par = f_h >> 1, f_k0 = 2 * (f_h & 1);
-    auto slot_pos = [](int row, int item, int k, int par) __attribute__((always_inline)) {
-        return (unsigned)(16 * k + ((row ^ ((k & 1) << 1)) + 4 * (item ^ ((k >> 1) | (par << 1)))));
-    };
     const unsigned rd_even = slot_pos(x, y, z, 0), rd_odd = slot_pos(x, y, z, 1);
     // Per item quad and per pair i of this wave (pair number wave + 4 i): the lane offset of its fetch for interior
     // row quads and for the last two (v[i][0 / 1 / 2]) and where its two elements go in the transit buffer (w[i][0 / 1][c],
@@ -172,12 +122,12 @@ __global__ __launch_bounds__(256, 1) void sandwich4b_kernel(const S4Args g) {
         for (int i = 0; i < PW; ++i) {
             const int m = wave + 4 * i;                            // (wave-uniform)
             const bool exists = m < NP, last = m == NP - 1;
-            const unsigned b = !exists || !item_ok ? kParkedB
+            const unsigned b = !exists || !item_ok ? kParked
                                : !last ? base
-                               : e0_ok ? (shift ? base - 8 : base) : kParkedB;
+                               : e0_ok ? (shift ? base - 8 : base) : kParked;
             v[i][0] = b;                                           // row quads below N4 - 2: every row exists
-            v[i][1] = 4 * (N4 - 2) + f_row < L ? b : kParkedB;     // row quad N4 - 2
-            v[i][2] = 4 * (N4 - 1) + f_row < L ? b : kParkedB;     // row quad N4 - 1
+            v[i][1] = 4 * (N4 - 2) + f_row < L ? b : kParked;      // row quad N4 - 2
+            v[i][2] = 4 * (N4 - 1) + f_row < L ? b : kParked;      // row quad N4 - 1
             const unsigned at = (exists ? m : 0) * 128;
             const bool divert = !exists || (last && shift);
             const unsigned w0 = at + (divert ? 4 * SET + p0 : p0);
@@ -193,18 +143,14 @@ __global__ __launch_bounds__(256, 1) void sandwich4b_kernel(const S4Args g) {
     auto out_offsets = [&](unsigned quad, unsigned (&v)[3]) __attribute__((always_inline)) {
         const unsigned base = (unsigned)((z * g.out_row + y * g.out_item + x * g.out_col) * 8);
         const bool item_ok = quad * 4 + y < g.nitems;
-        v[0] = item_ok ? base : kParkedB;
-        v[1] = item_ok && 4 * (N4 - 2) + z < M ? base : kParkedB;
-        v[2] = item_ok && 4 * (N4 - 1) + z < M ? base : kParkedB;
+        v[0] = item_ok ? base : kParked;
+        v[1] = item_ok && 4 * (N4 - 2) + z < M ? base : kParked;
+        v[2] = item_ok && 4 * (N4 - 1) + z < M ? base : kParked;
     };
 
     double ring[2][N4];         // In fragments of two row quads in MFMA lane order: parity of the row quad, k quad
     double stg[2][PW][2];       // this wave's pairs of two row quads as fetched: parity of the row quad, pair, element
 
-    auto opaque = [](unsigned v) __attribute__((always_inline)) {
-        asm volatile("" : "+s"(v));
-        return v;
-    };
     // Row quad r of an item quad (r a compile-time number, the quad behind rs / v / w / rd):
     //   load  -- this wave's pairs into the fetch registers of r's parity;
     //   write -- from there into r's transit set (the registers are free for row quad r + 2 afterwards);
@@ -213,8 +159,8 @@ __global__ __launch_bounds__(256, 1) void sandwich4b_kernel(const S4Args g) {
     auto load_into = [&](auto rs, const unsigned (&v)[PW][3], auto R_, auto I_, double (&dst)[2]) __attribute__((always_inline)) {
         constexpr int r = decltype(R_)::value, i = decltype(I_)::value;
         const unsigned s_off = opaque(r * ka_step) + pair0 + (unsigned)(4 * i) * pair_step;
-        const u32x4b q = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)v[i][r == N4 - 1 ? 2 : r == N4 - 2 ? 1 : 0], (int)s_off, 0);
-        const f64x2b d = __builtin_bit_cast(f64x2b, q);
+        const u32x4 q = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)v[i][r == N4 - 1 ? 2 : r == N4 - 2 ? 1 : 0], (int)s_off, 0);
+        const f64x2 d = __builtin_bit_cast(f64x2, q);
         dst[0] = d.x;
         dst[1] = d.y;
     };
@@ -240,14 +186,14 @@ __global__ __launch_bounds__(256, 1) void sandwich4b_kernel(const S4Args g) {
     double bf[N4][Q];
     double bx[E ? N4 : 1];
     auto load_r_fragments = [&]() __attribute__((always_inline)) {
-        unroll_b<0, N4>([&](auto KS) __attribute__((always_inline)) {
-            unroll_b<0, Q>([&](auto J) __attribute__((always_inline)) {
+        unroll<0, N4>([&](auto KS) __attribute__((always_inline)) {
+            unroll<0, Q>([&](auto J) __attribute__((always_inline)) {
                 bf[decltype(KS)::value][decltype(J)::value] =
                     rtab[(decltype(KS)::value * N4 + jg0 + decltype(J)::value) * 16 + e_lane];
             });
         });
         if constexpr (E != 0) {
-            unroll_b<0, N4>([&](auto KS) __attribute__((always_inline)) {
+            unroll<0, N4>([&](auto KS) __attribute__((always_inline)) {
                 bx[decltype(KS)::value] = rtab[(decltype(KS)::value * N4 + jx) * 16 + e_lane];
             });
         }
@@ -269,25 +215,25 @@ __global__ __launch_bounds__(256, 1) void sandwich4b_kernel(const S4Args g) {
         double ovx[2] = {0.0, 0.0};      // those of the shared group (parity of the row quad; only mpar's is computed here)
         // lane offsets of the groups' stores for the three kinds of row quad (a column that does not exist is parked)
         unsigned vo[3][Q], vox[2][3];
-        unroll_b<0, Q>([&](auto J) __attribute__((always_inline)) {
+        unroll<0, Q>([&](auto J) __attribute__((always_inline)) {
             constexpr int j = decltype(J)::value;
             const bool col_ok = 4 * (jg0 + j) + x < M;
 #pragma unroll
-            for (int rv = 0; rv < 3; ++rv) vo[rv][j] = col_ok ? v_out[rv] : kParkedB;
+            for (int rv = 0; rv < 3; ++rv) vo[rv][j] = col_ok ? v_out[rv] : kParked;
         });
         if constexpr (E != 0) {
             const bool col_ok = 4 * jx + x < M;
 #pragma unroll
             for (int par = 0; par < 2; ++par)                         // rows of the other parity are the partner's
 #pragma unroll
-                for (int rv = 0; rv < 3; ++rv) vox[par][rv] = (par == mpar && col_ok) ? v_out[rv] : kParkedB;
+                for (int rv = 0; rv < 3; ++rv) vox[par][rv] = (par == mpar && col_ok) ? v_out[rv] : kParked;
         }
         auto store_frag = [&](unsigned vofs, unsigned s_off, double val) __attribute__((always_inline)) {
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2b, val), rs_out, (int)vofs, (int)s_off, QS_S4B_STORE_AUX);
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, val), rs_out, (int)vofs, (int)s_off, QS_S4B_STORE_AUX);
         };
 
         // ---- phase 1
-        unroll_b<0, N4>([&](auto KA) __attribute__((always_inline)) {
+        unroll<0, N4>([&](auto KA) __attribute__((always_inline)) {
             constexpr int ka = decltype(KA)::value, st = ka & 1;
             QS_S4B_STAMP(ka)
             // An even step carries the barrier: behind its first two k quads, and all of the step's LDS traffic behind
@@ -296,9 +242,9 @@ __global__ __launch_bounds__(256, 1) void sandwich4b_kernel(const S4Args g) {
             constexpr int SH = (ka & 1) ? 0 : 2;
             if constexpr (E != 0) {
                 if (QS_S4B_OWNER((ka & 1))) {        // this wave's row quad of the shared group: one chain, a block of its own
-                    unroll_b<0, N4>([&](auto KS) __attribute__((always_inline)) {
+                    unroll<0, N4>([&](auto KS) __attribute__((always_inline)) {
                         constexpr int ks = decltype(KS)::value;
-                        Yh[ka / 2] = mfma4b(ring[st][ks], bx[ks], ks == 0 ? 0.0 : Yh[ka / 2]);
+                        Yh[ka / 2] = mfma4(ring[st][ks], bx[ks], ks == 0 ? 0.0 : Yh[ka / 2]);
                     });
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -307,15 +253,15 @@ __global__ __launch_bounds__(256, 1) void sandwich4b_kernel(const S4Args g) {
                 if constexpr (ka + 1 >= N4) read_frag(rd_nx, std::integral_constant<int, ka + 1 - N4>{}, F_);
                 else read_frag(rd_in, std::integral_constant<int, ka + 1>{}, F_);
             };
-            unroll_b<0, N4>([&](auto KS) __attribute__((always_inline)) {
+            unroll<0, N4>([&](auto KS) __attribute__((always_inline)) {
                 constexpr int ks = decltype(KS)::value;
-                unroll_b<0, Q>([&](auto J) __attribute__((always_inline)) {
+                unroll<0, Q>([&](auto J) __attribute__((always_inline)) {
                     constexpr int j = decltype(J)::value;
                     if constexpr (SH != 0 && ks == SH && j == 0) {
                         lds_barrier();
                         __builtin_amdgcn_sched_barrier(0);
                     }
-                    Y[ka][j] = mfma4b(ring[st][ks], bf[ks][j], ks == 0 ? 0.0 : Y[ka][j]);
+                    Y[ka][j] = mfma4(ring[st][ks], bf[ks][j], ks == 0 ? 0.0 : Y[ka][j]);
                     if constexpr (j == 0 && ks >= SH) {
                         read_next(std::integral_constant<int, (ks >= SH ? ks - SH : 0)>{});
                         // (the last SH fragments ride with the last k quads' reads: two LDS reads behind one MFMA are free)
@@ -336,7 +282,7 @@ __global__ __launch_bounds__(256, 1) void sandwich4b_kernel(const S4Args g) {
                         } else if constexpr (ka == N4 - 1 && Q == 2) {
                             // (two MFMAs per k quad: the first fragments of Lm share the gaps that are left)
                             constexpr int per = (N4 + (N4 - 3 * PW) - 1) / (N4 - 3 * PW), f0 = (ks - 3 * PW) * per;
-                            unroll_b<0, per>([&](auto T) __attribute__((always_inline)) {
+                            unroll<0, per>([&](auto T) __attribute__((always_inline)) {
                                 if constexpr (f0 + decltype(T)::value < N4)
                                     lf[0][f0 + decltype(T)::value] = ltab[(f0 + decltype(T)::value) * 16 + e_lane];
                             });
@@ -351,34 +297,34 @@ __global__ __launch_bounds__(256, 1) void sandwich4b_kernel(const S4Args g) {
         double Yx[E ? N4 : 1];
         if constexpr (E != 0) {
             double* const mine = xch + pair * SET + mpar * 64 + lane;
-            unroll_b<0, N4 / 2>([&](auto I_) __attribute__((always_inline)) {
+            unroll<0, N4 / 2>([&](auto I_) __attribute__((always_inline)) {
                 mine[decltype(I_)::value * 128] = Yh[decltype(I_)::value];
             });
             lds_barrier();
             const double* const both = xch + pair * SET + lane;
-            unroll_b<0, N4>([&](auto KA) __attribute__((always_inline)) {
+            unroll<0, N4>([&](auto KA) __attribute__((always_inline)) {
                 Yx[decltype(KA)::value] = both[decltype(KA)::value * 64];
             });
         }
         // ---- phase 2
-        unroll_b<0, N4>([&](auto PG) __attribute__((always_inline)) {
+        unroll<0, N4>([&](auto PG) __attribute__((always_inline)) {
             constexpr int pg = decltype(PG)::value, b = pg & 1;
             QS_S4B_STAMP(64 + pg)
             const unsigned s_prev = opaque((pg ? pg - 1 : 0) * pg_step);
             if constexpr (E != 0) {
                 if (QS_S4B_OWNER((pg & 1))) {
-                    unroll_b<0, N4>([&](auto KA) __attribute__((always_inline)) {
+                    unroll<0, N4>([&](auto KA) __attribute__((always_inline)) {
                         constexpr int ka = decltype(KA)::value;
-                        ovx[b] = mfma4b(lf[b][ka], Yx[ka], ka == 0 ? 0.0 : ovx[b]);
+                        ovx[b] = mfma4(lf[b][ka], Yx[ka], ka == 0 ? 0.0 : ovx[b]);
                     });
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
-            unroll_b<0, N4>([&](auto KA) __attribute__((always_inline)) {
+            unroll<0, N4>([&](auto KA) __attribute__((always_inline)) {
                 constexpr int ka = decltype(KA)::value;
-                unroll_b<0, Q>([&](auto J) __attribute__((always_inline)) {
+                unroll<0, Q>([&](auto J) __attribute__((always_inline)) {
                     constexpr int j = decltype(J)::value;
-                    ov[b][j] = mfma4b(lf[b][ka], Y[ka][j], ka == 0 ? 0.0 : ov[b][j]);
+                    ov[b][j] = mfma4(lf[b][ka], Y[ka][j], ka == 0 ? 0.0 : ov[b][j]);
                     if constexpr (j == 0 && pg + 1 < N4) lf[b ^ 1][ka] = ltab[((pg + 1) * N4 + ka) * 16 + e_lane];
                     // row quad pg - 1 leaves: one store per two row quads of MFMAs
                     if constexpr (j == 1 && pg >= 1 && (ka & 1) && ka / 2 < Q)
@@ -393,7 +339,7 @@ __global__ __launch_bounds__(256, 1) void sandwich4b_kernel(const S4Args g) {
         {
             constexpr int b = (N4 - 1) & 1;
             const unsigned s_row = opaque((N4 - 1) * pg_step);
-            unroll_b<0, Q>([&](auto J) __attribute__((always_inline)) {
+            unroll<0, Q>([&](auto J) __attribute__((always_inline)) {
                 constexpr int j = decltype(J)::value;
                 store_frag(vo[2][j], s_row + (unsigned)(jg0 + j) * jg_step, ov[b][j]);
             });
@@ -408,7 +354,8 @@ __global__ __launch_bounds__(256, 1) void sandwich4b_kernel(const S4Args g) {
     auto rs_in = rsrc(g.in - 1, iq, g.in_item);
     in_offsets(iq, true, ph, v_in, w_in, rd_in);
     double first2[PW][2];      // row quad 2 of the first item quad, fetched before the tables like 0 and 1
-    {   // tables (qs_sandwich4.hip): thread t takes element t & 15 of the 4 x 4 blocks t / 16, t / 16 + 16, ...
+    {   // tables (this block is kept in step with qs_sandwich4.hip by hand: no shared form compiles to the same schedule,
+        // profiles/mfma4_toolkit_isa.txt): thread t takes element t & 15 of the 4 x 4 blocks t / 16, t / 16 + 16, ...
         constexpr int NF = (N4 * N4 + 15) / 16;
         const auto rs_R = rsrc(g.R, 0, 0), rs_L = rsrc(g.Lm, 0, 0);
         const int ez = (tid >> 2) & 3, ex = tid & 3, b0 = tid >> 4;
@@ -421,8 +368,8 @@ __global__ __launch_bounds__(256, 1) void sandwich4b_kernel(const S4Args g) {
         for (int i = 0; i < NF; ++i) {
             const bool in = hi < N4;
             const bool r_ok = in && 4 * hi + ez < L && 4 * lo + ex < M, l_ok = in && 4 * hi + ex < M && 4 * lo + ez < L;
-            rv[i] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs_R, r_ok ? off_r * 8 : (int)kParkedB, 0, 0));
-            lv[i] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs_L, l_ok ? off_l * 8 : (int)kParkedB, 0, 0));
+            rv[i] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs_R, r_ok ? off_r * 8 : (int)kParked, 0, 0));
+            lv[i] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs_L, l_ok ? off_l * 8 : (int)kParked, 0, 0));
             hi += 16 / N4; lo += 16 % N4;
             off_r += (16 / N4) * 4 * r_sk + (16 % N4) * 4 * r_sj;
             off_l += (16 / N4) * 4 * l_sp + (16 % N4) * 4 * l_sa;
@@ -433,10 +380,10 @@ __global__ __launch_bounds__(256, 1) void sandwich4b_kernel(const S4Args g) {
         }
         __builtin_amdgcn_sched_barrier(0);
         // the first two row quads go out before the tables are built (behind the table loads: loads return in order)
-        unroll_b<0, 2>([&](auto R_) __attribute__((always_inline)) {
-            unroll_b<0, PW>([&](auto I_) __attribute__((always_inline)) { load_pair(rs_in, v_in, R_, I_); });
+        unroll<0, 2>([&](auto R_) __attribute__((always_inline)) {
+            unroll<0, PW>([&](auto I_) __attribute__((always_inline)) { load_pair(rs_in, v_in, R_, I_); });
         });
-        unroll_b<0, PW>([&](auto I_) __attribute__((always_inline)) {
+        unroll<0, PW>([&](auto I_) __attribute__((always_inline)) {
             load_into(rs_in, v_in, std::integral_constant<int, 2>{}, I_, first2[decltype(I_)::value]);
         });
         __builtin_amdgcn_sched_barrier(0);
@@ -451,13 +398,13 @@ __global__ __launch_bounds__(256, 1) void sandwich4b_kernel(const S4Args g) {
     __syncthreads();
     load_r_fragments();
     // row quads 0, 1, 2 into the transit buffer, 3 and 4 into the registers the first two leave, row quad 0 into the ring
-    unroll_b<0, 2>([&](auto R_) __attribute__((always_inline)) {
-        unroll_b<0, PW>([&](auto I_) __attribute__((always_inline)) {
+    unroll<0, 2>([&](auto R_) __attribute__((always_inline)) {
+        unroll<0, PW>([&](auto I_) __attribute__((always_inline)) {
             write_elem(w_in, R_, I_, std::integral_constant<int, 0>{});
             write_elem(w_in, R_, I_, std::integral_constant<int, 1>{});
         });
     });
-    unroll_b<0, PW>([&](auto I_) __attribute__((always_inline)) {
+    unroll<0, PW>([&](auto I_) __attribute__((always_inline)) {
         write_from(w_in, std::integral_constant<int, 2>{}, I_, std::integral_constant<int, 0>{}, first2[decltype(I_)::value][0]);
         write_from(w_in, std::integral_constant<int, 2>{}, I_, std::integral_constant<int, 1>{}, first2[decltype(I_)::value][1]);
         load_pair(rs_in, v_in, std::integral_constant<int, 3>{}, I_);
@@ -465,7 +412,7 @@ __global__ __launch_bounds__(256, 1) void sandwich4b_kernel(const S4Args g) {
     });
     lds_barrier();
     QS_S4B_STAMP(254)
-    unroll_b<0, N4>([&](auto KS) __attribute__((always_inline)) { read_frag(rd_in, std::integral_constant<int, 0>{}, KS); });
+    unroll<0, N4>([&](auto KS) __attribute__((always_inline)) { read_frag(rd_in, std::integral_constant<int, 0>{}, KS); });
 
     while (iq < u_end) {
         const unsigned nq = iq + slots;
@@ -506,7 +453,7 @@ __global__ __launch_bounds__(256, 1) void sandwich4b_kernel(const S4Args g) {
             const int jgc = has_group ? jg : 0;
             __syncthreads();                                      // everybody is through with the transit buffer
             double bt[N4];
-            unroll_b<0, N4>([&](auto KS) __attribute__((always_inline)) {
+            unroll<0, N4>([&](auto KS) __attribute__((always_inline)) {
                 bt[decltype(KS)::value] = rtab[(decltype(KS)::value * N4 + jgc) * 16 + e_lane];
             });
             auto set_of = [&](int r) __attribute__((always_inline)) {
@@ -516,8 +463,8 @@ __global__ __launch_bounds__(256, 1) void sandwich4b_kernel(const S4Args g) {
             in_offsets(tq, true, 0u, v_t, w_t, rd_t);             // (v_t: lane offsets; the positions are this block's own)
             auto rs_t = rsrc(g.in - 1, tq, g.in_item);
             double tl[N4][PW][2];
-            unroll_b<0, N4>([&](auto R_) __attribute__((always_inline)) {
-                unroll_b<0, PW>([&](auto I_) __attribute__((always_inline)) {
+            unroll<0, N4>([&](auto R_) __attribute__((always_inline)) {
+                unroll<0, PW>([&](auto I_) __attribute__((always_inline)) {
                     load_into(rs_t, v_t, R_, I_, tl[decltype(R_)::value][decltype(I_)::value]);
                 });
             });
@@ -526,10 +473,10 @@ __global__ __launch_bounds__(256, 1) void sandwich4b_kernel(const S4Args g) {
             const int k_last = 8 * (NP - 1) + 4 * f_par + f_k0;
             const bool shift = k_last < L && !(k_last + 1 < L);   // the last k of an odd L: fetched 8 bytes early (in_offsets)
             lds_barrier();                                        // the fragments of R are in registers: their table may go
-            unroll_b<0, N4>([&](auto R_) __attribute__((always_inline)) {
+            unroll<0, N4>([&](auto R_) __attribute__((always_inline)) {
                 constexpr int r = decltype(R_)::value;
                 double* const set = set_of(r);
-                unroll_b<0, PW>([&](auto I_) __attribute__((always_inline)) {
+                unroll<0, PW>([&](auto I_) __attribute__((always_inline)) {
                     constexpr int i = decltype(I_)::value;
                     const int m = wave + 4 * i;                   // (wave-uniform)
                     if (m < NP) {
@@ -543,15 +490,15 @@ __global__ __launch_bounds__(256, 1) void sandwich4b_kernel(const S4Args g) {
             if (has_group) {
                 // Y[ka] = In[ka] . R[:, group]: two chains at a time (a single one waits 4 cycles per link)
                 double Yt[N4];
-                unroll_b<0, N4 / 2>([&](auto H_) __attribute__((always_inline)) {
+                unroll<0, N4 / 2>([&](auto H_) __attribute__((always_inline)) {
                     constexpr int ka = 2 * decltype(H_)::value;
                     const double* const s0 = set_of(ka);
                     const double* const s1 = set_of(ka + 1);
-                    unroll_b<0, N4>([&](auto KS) __attribute__((always_inline)) {
+                    unroll<0, N4>([&](auto KS) __attribute__((always_inline)) {
                         constexpr int ks = decltype(KS)::value;
                         const unsigned rd = (ks & 1) ? rd_odd : rd_even;
-                        Yt[ka] = mfma4b(s0[ks * 64 + rd], bt[ks], ks == 0 ? 0.0 : Yt[ka]);
-                        Yt[ka + 1] = mfma4b(s1[ks * 64 + rd], bt[ks], ks == 0 ? 0.0 : Yt[ka + 1]);
+                        Yt[ka] = mfma4(s0[ks * 64 + rd], bt[ks], ks == 0 ? 0.0 : Yt[ka]);
+                        Yt[ka + 1] = mfma4(s1[ks * 64 + rd], bt[ks], ks == 0 ? 0.0 : Yt[ka + 1]);
                     });
                 });
                 // Out[pg] = sum_ka Lm[pg][ka] . Y[ka], stored as it is finished
@@ -559,24 +506,24 @@ __global__ __launch_bounds__(256, 1) void sandwich4b_kernel(const S4Args g) {
                 out_offsets(tq, v_o);
                 const auto rs_o = rsrc(g.out, tq, g.out_item);
                 const bool col_ok = 4 * jg + x < M;
-                unroll_b<0, N4 / 2>([&](auto H_) __attribute__((always_inline)) {
+                unroll<0, N4 / 2>([&](auto H_) __attribute__((always_inline)) {
                     constexpr int pg = 2 * decltype(H_)::value;
                     double o0 = 0.0, o1 = 0.0;
-                    unroll_b<0, N4>([&](auto KA) __attribute__((always_inline)) {
+                    unroll<0, N4>([&](auto KA) __attribute__((always_inline)) {
                         constexpr int ka = decltype(KA)::value;
-                        o0 = mfma4b(ltab[(pg * N4 + ka) * 16 + e_lane], Yt[ka], ka == 0 ? 0.0 : o0);
-                        o1 = mfma4b(ltab[((pg + 1) * N4 + ka) * 16 + e_lane], Yt[ka], ka == 0 ? 0.0 : o1);
+                        o0 = mfma4(ltab[(pg * N4 + ka) * 16 + e_lane], Yt[ka], ka == 0 ? 0.0 : o0);
+                        o1 = mfma4(ltab[((pg + 1) * N4 + ka) * 16 + e_lane], Yt[ka], ka == 0 ? 0.0 : o1);
                     });
                     const unsigned s_col = (unsigned)jg * jg_step;
-                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2b, o0), rs_o,
-                        (int)(col_ok ? v_o[pg == N4 - 2 ? 1 : 0] : kParkedB), (int)(pg * pg_step + s_col), QS_S4B_STORE_AUX);
-                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2b, o1), rs_o,
-                        (int)(col_ok ? v_o[pg + 1 == N4 - 1 ? 2 : 0] : kParkedB), (int)((pg + 1) * pg_step + s_col), QS_S4B_STORE_AUX);
+                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o0), rs_o,
+                        (int)(col_ok ? v_o[pg == N4 - 2 ? 1 : 0] : kParked), (int)(pg * pg_step + s_col), QS_S4B_STORE_AUX);
+                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o1), rs_o,
+                        (int)(col_ok ? v_o[pg + 1 == N4 - 1 ? 2 : 0] : kParked), (int)((pg + 1) * pg_step + s_col), QS_S4B_STORE_AUX);
                 });
             }
         }
     }
-    QS_S4B_TRACE_DONE
+    QS_TRACE_DONE(qs_s4b_trace)
 }
 
 unsigned sandwich4b_tail_quads(unsigned nquads, int M) {
@@ -633,18 +580,4 @@ int sandwich4b_launch(const S4Args& g, int n4, hipStream_t stream, int dry_run) 
 
 }  // namespace qs
 
-#ifdef QS_S4_TRACE
-extern "C" int qs_s4b_trace_reset(void) {
-    unsigned zero = 0;
-    return (int)hipMemcpyToSymbol(HIP_SYMBOL(qs::qs_s4b_trace_n), &zero, sizeof(zero));
-}
-extern "C" int qs_s4b_trace_read(void* dst) {      // dst: device buffer of 4097 x 8 bytes: count, stamps
-    unsigned n = 0;
-    (void)hipMemcpyFromSymbol(&n, HIP_SYMBOL(qs::qs_s4b_trace_n), sizeof(n));
-    unsigned long long nn = n;
-    (void)hipMemcpy(dst, &nn, 8, hipMemcpyHostToDevice);
-    void* src = nullptr;
-    (void)hipGetSymbolAddress(&src, HIP_SYMBOL(qs::qs_s4b_trace));
-    return (int)hipMemcpy((char*)dst + 8, src, 4096 * 8, hipMemcpyDeviceToDevice);
-}
-#endif
+QS_TRACE_EXPORTS(qs_s4b_trace)

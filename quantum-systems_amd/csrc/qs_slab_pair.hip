@@ -31,12 +31,10 @@
 // Same k order as the tiled kernels (d ascending, then c ascending).
 // Algorithmic bytes per launch: 8 (L^2 + M^2) per slab; roofline = HBM below l ~ 64.
 
-#include "qs_common.h"
+#include "qs_mfma4.h"      // vector typedefs, uniform_rsrc
 
 namespace qs {
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 struct SlabArgs {
     const double* X;
@@ -71,11 +69,7 @@ void slab_pair_kernel(const SlabArgs g) {
 
     const unsigned x_slab = (unsigned)(L * L * 8), z_slab = (unsigned)(M * M * 8);
     auto rsrc = [&](const double* base, unsigned slab, unsigned stride, unsigned room) __attribute__((always_inline)) {
-        const uint64_t p = reinterpret_cast<uint64_t>(base) + (uint64_t)slab * stride;
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)p);
-        const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(p >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)hi << 32) | lo), (short)0,
-                                                 (int)room, 0x00020000);
+        return uniform_rsrc(reinterpret_cast<uint64_t>(base) + (uint64_t)slab * stride, (int)room);
     };
     // lane offsets of the X fragments: row 16 i + c16, column 4 kk + g4; tails are zeroed after the load
     unsigned x_off[TL];
@@ -207,11 +201,7 @@ void slab_pair_split_kernel(const SlabArgs g) {
 
     const unsigned x_slab = (unsigned)(L * L * 8), z_slab = (unsigned)(M * M * 8);
     auto rsrc = [&](const double* base, unsigned slab, unsigned stride, unsigned room) __attribute__((always_inline)) {
-        const uint64_t p = reinterpret_cast<uint64_t>(base) + (uint64_t)slab * stride;
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)p);
-        const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(p >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)hi << 32) | lo), (short)0,
-                                                 (int)room, 0x00020000);
+        return uniform_rsrc(reinterpret_cast<uint64_t>(base) + (uint64_t)slab * stride, (int)room);
     };
     unsigned x_off[TL];
 #pragma unroll

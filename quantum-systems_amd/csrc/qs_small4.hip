@@ -10,9 +10,8 @@
 // 14.6 us, profiles/r02_small_basis_sweep.txt), and RandomBasisSet -- the reference's own test input,
 // random_basis.py:52-69 -- and every spin-doubled tensor are complex, which the fused kernels of round 2 do not take.
 // This kernel is the simple end of the same idea, written for latency instead of throughput:
-//   * v_mfma_f64_4x4x4_4b_f64, four ITEMS per instruction (lane = x + 4 y + 16 z: A row x / item y / k z, B k z / item y /
-//     column x, D row z / item y / column x): extents pad to 4, and Y = In . R leaves the accumulators in the B-operand
-//     layout of Lm . Y -- no LDS round trip between the two products;
+//   * v_mfma_f64_4x4x4_4b_f64, four ITEMS per instruction (its blocks; the lane layouts: qs_mfma4.h): extents pad to 4, and
+//     Y = In . R leaves the accumulators in the B-operand layout of Lm . Y -- no LDS round trip between the two products;
 //   * a workgroup takes an item quad: all four items (<= 64 KB) are staged into LDS with coalesced loads, zero-padded, and
 //     every wave reads its A fragments from there (conflict-free pitches); the fragments of R and Lm come from LDS tables
 //     built once per workgroup; a wave owns one or two column groups of four columns;
@@ -25,9 +24,7 @@
 // workgroups but 3.5 / 6.2 / 11 us for 64 / 128 / 256, and the cooperative-groups grid sync 24-33 us.
 // Algorithmic bytes per launch: e (L^2 + M^2) per item (e = 8 / 16); the tensor (<= 16.8 MB) lives in L2 / Infinity Cache.
 
-#include <type_traits>
-
-#include "qs_common.h"
+#include "qs_mfma4.h"
 
 // Development builds only (never defined in the shipped library): bit mask of parts to leave out, to find what bounds the
 // kernel.  1 loads of the item quad, 2 stores, 4 all MFMAs, 8 LDS reads of A fragments
@@ -39,24 +36,13 @@ namespace qs {
 
 namespace {
 
-template <int I, int N, class F>
-__device__ __forceinline__ void unroll(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        unroll<I + 1, N>(f);
-    }
-}
-
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-
 struct Small4Args : FusedPass {
     int tensor_is_b;      // complex only: in the 16-wide kernels' call for the FIRST product the tensor is the B operand
                           // (the b contraction, gemm(Ct, T2)): the two imaginary-part products then come in the other order
 };
 
-__device__ __forceinline__ double mfma4(double a, double b, double c) {
-    if constexpr (QS_SMALL4_ABLATE & 4) return a + b + c;
-    return __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, c, 0, 0, 0);
+__device__ __forceinline__ double mfma4_or_sum(double a, double b, double c) {
+    return (QS_SMALL4_ABLATE & 4) ? a + b + c : mfma4(a, b, c);
 }
 
 // LDS geometry for N4 = ceil(L / 4): row pitch Lp (doubles) with Lp % 8 == 4 and item pitch == 16 mod 32, so that the
@@ -107,8 +93,8 @@ __global__ __launch_bounds__(small4_threads(CX, N4)) void small4_kernel(const Sm
     const int L = g.L, M = g.M;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int x = lane & 3, y = (lane >> 2) & 3, z = lane >> 4;
-    const int e_lane = z * 4 + x;
+    const Lane4 l4 = lane4(lane);
+    const int x = l4.x, y = l4.y, z = l4.z, e_lane = l4.e;
     constexpr int es = CX ? 2 : 1;                          // doubles per element in memory
 
     const bool slab = g.in_col == 1;
@@ -157,10 +143,9 @@ __global__ __launch_bounds__(small4_threads(CX, N4)) void small4_kernel(const Sm
     // XCD they meet in its L2 (one fetch, one whole-line write-back); spread round-robin over the XCDs -- the first
     // version -- every line was fetched by four L2s and written back as four partial lines (at l = 32: 12 of 29 us in the
     // loads, 16 in the stores; profiles/r03_small4.txt).
-    const unsigned n_xcd = 8, xcd = blockIdx.x % n_xcd, slot = blockIdx.x / n_xcd, slots = gridDim.x / n_xcd;
-    const unsigned per = (g.ntuples + n_xcd - 1) / n_xcd;
-    const unsigned u_end = (xcd + 1) * per < g.ntuples ? (xcd + 1) * per : g.ntuples;
-    unsigned unit = xcd * per + slot;
+    const XcdRange units = xcd_range(g.ntuples);
+    const unsigned u_end = units.end, slots = units.stride;
+    unsigned unit = units.first;
     if (unit >= u_end) return;                              // (the whole workgroup, before any barrier)
     {   // ---- tables: every element of R and Lm once per workgroup (they sit in L2 after the first workgroup); the loads of
         // the tables and of the first item quad all go out before anything is written
@@ -233,39 +218,39 @@ __global__ __launch_bounds__(small4_threads(CX, N4)) void small4_kernel(const Sm
                     if constexpr (!CX) {
                         unroll<0, NJ>([&](auto J) __attribute__((always_inline)) {
                             constexpr int j = decltype(J)::value;
-                            yr[ka][j] = mfma4(ar, br[ks][j], yr[ka][j]);
+                            yr[ka][j] = mfma4_or_sum(ar, br[ks][j], yr[ka][j]);
                         });
                     } else {
                         const double ai = in_pl[G::plane + a_lane + 4 * ka * Lp + 4 * ks];
                         // re: ar.br then ai.(-bi) in both roles; im: (A = tensor) ar.bi then ai.br, (B = tensor) the other way
                         unroll<0, NJ>([&](auto J) __attribute__((always_inline)) {
                             constexpr int j = decltype(J)::value;
-                            yr[ka][j] = mfma4(ar, br[ks][j], yr[ka][j]);
+                            yr[ka][j] = mfma4_or_sum(ar, br[ks][j], yr[ka][j]);
                         });
                         if (!g.tensor_is_b) {
                             unroll<0, NJ>([&](auto J) __attribute__((always_inline)) {
                                 constexpr int j = decltype(J)::value;
-                                yi[ka][j] = mfma4(ar, bi[ks][j], yi[ka][j]);
+                                yi[ka][j] = mfma4_or_sum(ar, bi[ks][j], yi[ka][j]);
                             });
                         } else {
                             unroll<0, NJ>([&](auto J) __attribute__((always_inline)) {
                                 constexpr int j = decltype(J)::value;
-                                yi[ka][j] = mfma4(ai, br[ks][j], yi[ka][j]);
+                                yi[ka][j] = mfma4_or_sum(ai, br[ks][j], yi[ka][j]);
                             });
                         }
                         unroll<0, NJ>([&](auto J) __attribute__((always_inline)) {
                             constexpr int j = decltype(J)::value;
-                            yr[ka][j] = mfma4(ai, bn[ks][j], yr[ka][j]);
+                            yr[ka][j] = mfma4_or_sum(ai, bn[ks][j], yr[ka][j]);
                         });
                         if (!g.tensor_is_b) {
                             unroll<0, NJ>([&](auto J) __attribute__((always_inline)) {
                                 constexpr int j = decltype(J)::value;
-                                yi[ka][j] = mfma4(ai, br[ks][j], yi[ka][j]);
+                                yi[ka][j] = mfma4_or_sum(ai, br[ks][j], yi[ka][j]);
                             });
                         } else {
                             unroll<0, NJ>([&](auto J) __attribute__((always_inline)) {
                                 constexpr int j = decltype(J)::value;
-                                yi[ka][j] = mfma4(ar, bi[ks][j], yi[ka][j]);
+                                yi[ka][j] = mfma4_or_sum(ar, bi[ks][j], yi[ka][j]);
                             });
                         }
                     }
@@ -286,19 +271,19 @@ __global__ __launch_bounds__(small4_threads(CX, N4)) void small4_kernel(const Sm
                     if constexpr (!CX) {
                         unroll<0, NJ>([&](auto J) __attribute__((always_inline)) {
                             constexpr int j = decltype(J)::value;
-                            o_r[j] = mfma4(lr, yr[ka][j], o_r[j]);
+                            o_r[j] = mfma4_or_sum(lr, yr[ka][j], o_r[j]);
                         });
                     } else {
                         const double li = ltab[G::table + f], ln = ltab[2 * G::table + f];
                         unroll<0, NJ>([&](auto J) __attribute__((always_inline)) {
                             constexpr int j = decltype(J)::value;
-                            o_r[j] = mfma4(lr, yr[ka][j], o_r[j]);
-                            o_i[j] = mfma4(lr, yi[ka][j], o_i[j]);
+                            o_r[j] = mfma4_or_sum(lr, yr[ka][j], o_r[j]);
+                            o_i[j] = mfma4_or_sum(lr, yi[ka][j], o_i[j]);
                         });
                         unroll<0, NJ>([&](auto J) __attribute__((always_inline)) {
                             constexpr int j = decltype(J)::value;
-                            o_r[j] = mfma4(ln, yi[ka][j], o_r[j]);
-                            o_i[j] = mfma4(li, yr[ka][j], o_i[j]);
+                            o_r[j] = mfma4_or_sum(ln, yi[ka][j], o_r[j]);
+                            o_i[j] = mfma4_or_sum(li, yr[ka][j], o_i[j]);
                         });
                     }
                 });
