@@ -205,6 +205,19 @@ int qs_transform_two_body_inplace(int dtype, void* u, const void* C,
  *   qs_exchange_mirror: in place on t (n,n,m,m),
  *     t[a,b,r,s] = t[b,a,s,r] for every pair with a / block > b / block
  *     (block = 1: the lower triangle a > b); nothing else is written.
+ *   qs_transform_two_body_exchange_leading_pairs: 1 where the exchange entries
+ *     would contract the leading indices of (dtype, L, M) on pairs under the
+ *     calling thread's tuning keys ("exchange_order", "exchange_leading"),
+ *     else 0.  Launches nothing.
+ *   qs_exchange_pair_transpose / qs_exchange_pair_transpose_back: the two byte
+ *     movers of "exchange_leading" = 2 (below), exact copies of bits.  The
+ *     first, both tensors (L,L,L,L): dst[c,d,a,b] = src[a,b,c,d] for the pairs
+ *     d >= c; nothing is written at d < c.  The second, src (L,L,M,M) stored on
+ *     the pairs d >= c only (never read at d < c), dst (M,M,L,L):
+ *     dst[p,q,c,d] = src[c,d,p,q] where d >= c, src[d,c,q,p] where d < c, for
+ *     the pairs q >= p; nothing is written at q < p.  L, M <= 4096 and a grid
+ *     below 2^31 workgroups (else QS_ERR_BAD_EXTENT); src and dst must not
+ *     overlap (QS_ERR_ALIAS).
  */
 int qs_two_body_exchange_symmetric(int dtype, const void* u, int64_t L,
                                    void* scratch, void* stream);
@@ -219,6 +232,11 @@ int qs_transform_two_body_inplace_exchange(int dtype, void* u, const void* C,
 int qs_transform_two_body_exchange_wanted(int dtype, int64_t L, int64_t M);
 int qs_exchange_mirror(int dtype, void* t, int64_t n, int64_t m, int64_t block,
                        void* stream);
+int qs_transform_two_body_exchange_leading_pairs(int dtype, int64_t L, int64_t M);
+int qs_exchange_pair_transpose(int dtype, const void* src, void* dst, int64_t L,
+                               void* stream);
+int qs_exchange_pair_transpose_back(int dtype, const void* src, void* dst,
+                                    int64_t L, int64_t M, void* stream);
 
 /*
  * Same transform restricted to rows [a_lo, a_hi) of the leading index of `u`
@@ -582,7 +600,19 @@ const char* qs_last_dispatch(void);
  *     grid, one mirror; 1, the default = 2 where M >= L and L is at least the
  *     smallest size measured to gain, never below the route's own thresholds,
  *     else 0.  The two orders agree to rounding, not bit for bit; a value
- *     outside 0 ... 2 is refused with QS_ERR_BAD_EXTENT).
+ *     outside 0 ... 2 is refused with QS_ERR_BAD_EXTENT),
+ *     "exchange_leading" (how order 2 contracts the leading indices: 0 = a as
+ *     one product and the closing blocks; 2 = on pairs: u's trailing indices
+ *     have the symmetry too, u[:,:,c,d] == u[:,:,d,c]^T, so the pair matrix is
+ *     turned (qs_exchange_pair_transpose), b and a run as two products over
+ *     the pairs d >= c of u's grid, and qs_exchange_pair_transpose_back turns
+ *     the result and fills in the other half -- 1.0 instead of 1.625 products'
+ *     worth of matrix work, plus two passes over half a tensor.  Its
+ *     intermediates need M >= L: for M < L, and where a mover's grid would
+ *     not fit, 2 gives the very launches of 0.  1, the default = 2 from the
+ *     smallest size measured to gain, never below the route's own
+ *     thresholds, else 0.  b runs before a: 0 and 2 agree to rounding, not
+ *     bit for bit; outside 0 ... 2: QS_ERR_BAD_EXTENT).
  *   qs_probe_mfma_f64: register-resident fp64 MFMA loop, `blocks` workgroups
  *     of 4 waves, each wave issuing iters*8 v_mfma_f64_16x16x4_f64
  *     (flops = blocks*4*iters*8*2048); `sink` is a device scratch of

@@ -44,6 +44,9 @@ SIGNATURES = {
         c_int, [c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_ptr]),
     "qs_transform_two_body_exchange_wanted": (c_int, [c_int, c_i64, c_i64]),
     "qs_exchange_mirror": (c_int, [c_int, c_ptr, c_i64, c_i64, c_i64, c_ptr]),
+    "qs_transform_two_body_exchange_leading_pairs": (c_int, [c_int, c_i64, c_i64]),
+    "qs_exchange_pair_transpose": (c_int, [c_int, c_ptr, c_ptr, c_i64, c_ptr]),
+    "qs_exchange_pair_transpose_back": (c_int, [c_int, c_ptr, c_ptr, c_i64, c_i64, c_ptr]),
     "qs_transform_two_body_partial_workspace": (c_i64, [c_int, c_i64, c_i64, c_i64]),
     "qs_transform_two_body_partial": (
         c_int, [c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, c_ptr]),

@@ -270,6 +270,11 @@ int qs_tuning_set(const char* key, int64_t value) {
         g_tune.exchange_order = (int)value;
         return QS_OK;
     }
+    if (!strcmp(key, "exchange_leading")) {
+        if (value < 0 || value > 2) return QS_ERR_BAD_EXTENT;
+        g_tune.exchange_leading = (int)value;
+        return QS_OK;
+    }
     if (!strcmp(key, "mean_field_batch_g")) {
         if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8) return QS_ERR_BAD_EXTENT;
         g_tune.mean_field_batch_g = (int)value;
@@ -520,6 +525,26 @@ static bool exchange_leading_first(int dtype, int64_t L, int64_t M) {
     return M >= L && L >= (dtype == QS_C128 ? kExchangeOrderMinC128 : kExchangeOrderMin);
 }
 
+// g_tune.exchange_leading: how the second order contracts its leading indices.  Seen through its trailing indices u has the
+// same symmetry, u[:, :, c, d] == u[:, :, d, c]^T, so for a fixed (c, d) the a and b contractions are a two-sided product of
+// the L x L matrix over (a, b), needed on the pairs d >= c only -- the trailing pass itself, with Ct^T for C and Ct for CT, once
+// the pair matrix is turned (qs_permute.hip):
+//   in:    Xs[c, d][a, b]   = u[a, b, c, d]                         on the pairs d >= c
+//   b, a:  Xt[c, d][p, q]   = Ct[p, a] (Xs[c, d][a, b] Ct^T[b, q])  over those pairs: 0.502 + 0.502 of a product, not 1 + 0.625
+//   back:  X2[p, q][c, d]   = Xt[c, d][p, q] (d >= c), Xt[d, c][q, p] (d < c)     on the pairs q >= p
+// Xs (L, L, L, L) and Xt (L, L, M, M) go where X goes, the one between them (L, L, L, M) where T2 goes: that needs M >= L.
+// 2 = this wherever M >= L and the movers' grids fit (else the launches of 0), 0 = never, 1 = from the smallest size at which
+// it measured faster (profiles/exchange_leading_pairs_ab.txt section 2), never below the route's own thresholds.
+// (fp64: 192 level, 224 loses 0.7 ms of 62; 240, 256, 288 and 320 gain 5.6, 5.9, 10.6 and 8.9 ms = 3-6.5 %; complex128 gains 7.5-16 % from 160 to 256)
+static constexpr int64_t kExchangeLeadingMin = 240, kExchangeLeadingMinC128 = 160;
+
+static bool exchange_leading_pairs(int dtype, int64_t L, int64_t M) {
+    if (g_tune.exchange_leading == 0 || M < L || !exchange_pair_grids_fit(dtype, L, M)) return false;
+    if (g_tune.exchange_leading == 2) return true;
+    const bool c128 = dtype == QS_C128;
+    return L >= (c128 ? kExchangeMinC128 : kExchangeMin) && L >= (c128 ? kExchangeLeadingMinC128 : kExchangeLeadingMin);
+}
+
 // T1, T2, X: the three buffers of the comment above.  The a, b, d, c order keeps X1 where X goes, X2 where T2 goes and Y
 // where T1 goes; in either order every product reads one of the two storages and writes the other.
 static int transform_two_body_exchange_route(int dtype, const void* u, const void* C, const void* Ct, void* CT, void* T1,
@@ -532,10 +557,13 @@ static int transform_two_body_exchange_route(int dtype, const void* u, const voi
     const int64_t blk_d = g_tune.exchange_block_d > 0 ? g_tune.exchange_block_d : (blk < 16 ? blk : 16);
     auto cat = [&](const void* base, int64_t elems) { return (const double*)((const char*)base + (size_t)elems * es); };
     auto mat = [&](void* base, int64_t elems) { return (double*)at(base, elems, es); };
-    int rc = transpose_small(dtype, C, CT, L, M, s);
+    const bool leading_pairs = exchange_leading_first(dtype, L, M) && exchange_leading_pairs(dtype, L, M);
+    int rc = leading_pairs ? QS_OK : transpose_small(dtype, C, CT, L, M, s);      // (on pairs the slot holds Ct^T first)
     if (rc) return rc;
     // The trailing indices, on the pairs j >= i of a G x G grid of (L, L) matrices (G = L on u, G = M on X2):
     //   mid[i, j][c, s] = src[i, j][c, d] C[d, s],   dst[i, j][r, s] = CT[r, c] mid[i, j][c, s]
+    // with the two small matrices the caller names: (C, C^T) for the trailing indices, (Ct^T, Ct) for the leading ones of a
+    // turned tensor.
     // d and c are one product per pair on operands that are contiguous in the flat pair index i G + j: a
     // triangular batch (Product::pairs) runs each as ONE launch on exactly the G (G + 1) / 2 pairs.  For c that is the
     // per-row launches' tile list in one grid.  For d it pads the L rows of EVERY pair to whole tiles where the blocks'
@@ -550,7 +578,7 @@ static int transform_two_body_exchange_route(int dtype, const void* u, const voi
     // `mirrored` (null: not wanted): dst is the result and its other half is wanted too -- where the dispatch can, the c
     // launch stores it from its own registers (Product::mirror) and *mirrored says so; otherwise the caller launches the
     // mirror.
-    auto trailing = [&](const void* src, void* mid, void* dst, int64_t G, bool* mirrored) -> int {
+    auto trailing = [&](const void* src, void* mid, void* dst, int64_t G, const void* C, const void* CT, bool* mirrored) -> int {
         const int64_t npairs = G * (G + 1) / 2, LL = L * L, LM = L * M;
         auto d_block = [&](int64_t i0) {
             const int64_t rows = (i0 + blk_d < G ? i0 + blk_d : G) - i0;
@@ -592,14 +620,26 @@ static int transform_two_body_exchange_route(int dtype, const void* u, const voi
         return QS_OK;
     };
     if (exchange_leading_first(dtype, L, M)) {
-        rc = leading(u, /*X1*/ X, /*X2*/ T2, L * L);
+        if (leading_pairs) {
+            rc = exchange_pair_transpose(dtype, u, /*Xs*/ X, L, s);
+            if (rc) return rc;
+            rc = transpose_small(dtype, Ct, CT, M, L, s);
+            if (rc) return rc;
+            rc = trailing(/*Xs*/ X, T2, /*Xt*/ X, L, /*Ct^T*/ CT, Ct, nullptr);
+            if (rc) return rc;
+            rc = exchange_pair_transpose_back(dtype, /*Xt*/ X, /*X2*/ T2, L, M, s);
+            if (rc) return rc;
+            rc = transpose_small(dtype, C, CT, L, M, s);
+        } else {
+            rc = leading(u, /*X1*/ X, /*X2*/ T2, L * L);
+        }
         if (rc) return rc;
         bool mirrored = false;
-        rc = trailing(/*X2*/ T2, /*Y*/ T1, out, M, &mirrored);
+        rc = trailing(/*X2*/ T2, /*Y*/ T1, out, M, C, CT, &mirrored);
         if (rc || mirrored) return rc;
         return exchange_mirror(dtype, out, M, M, 1, s);
     }
-    rc = trailing(u, T1, T2, L, nullptr);
+    rc = trailing(u, T1, T2, L, C, CT, nullptr);
     if (rc) return rc;
     rc = exchange_mirror(dtype, T2, L, M, 1, s);
     if (rc) return rc;
@@ -741,6 +781,32 @@ int qs_exchange_mirror(int dtype, void* t, int64_t n, int64_t m, int64_t block, 
     if (!t) return QS_ERR_NULL_POINTER;
     if (!aligned(t, elem_size(dtype))) return QS_ERR_MISALIGNED;
     return exchange_mirror(dtype, t, n, m, block < n ? block : n, (hipStream_t)stream);
+}
+
+int qs_transform_two_body_exchange_leading_pairs(int dtype, int64_t L, int64_t M) {
+    return dtype_ok(dtype) && extents_ok(L, M) && exchange_leading_first(dtype, L, M) && exchange_leading_pairs(dtype, L, M) ? 1 : 0;
+}
+
+int qs_exchange_pair_transpose(int dtype, const void* src, void* dst, int64_t L, void* stream) {
+    dispatch_reset();
+    if (!dtype_ok(dtype)) return QS_ERR_BAD_DTYPE;
+    if (L <= 0 || L > 4096 || !exchange_pair_grids_fit(dtype, L, 1)) return QS_ERR_BAD_EXTENT;      // (a grid of 2^31 workgroups or more)
+    if (!src || !dst) return QS_ERR_NULL_POINTER;
+    const int64_t es = (int64_t)elem_size(dtype), bytes = L * L * L * L * es;
+    if (!aligned(src, es) || !aligned(dst, es)) return QS_ERR_MISALIGNED;
+    if (overlaps(src, bytes, dst, bytes)) return QS_ERR_ALIAS;
+    return exchange_pair_transpose(dtype, src, dst, L, (hipStream_t)stream);
+}
+
+int qs_exchange_pair_transpose_back(int dtype, const void* src, void* dst, int64_t L, int64_t M, void* stream) {
+    dispatch_reset();
+    if (!dtype_ok(dtype)) return QS_ERR_BAD_DTYPE;
+    if (L <= 0 || M <= 0 || L > 4096 || M > 4096 || !exchange_pair_grids_fit(dtype, L, M)) return QS_ERR_BAD_EXTENT;
+    if (!src || !dst) return QS_ERR_NULL_POINTER;
+    const int64_t es = (int64_t)elem_size(dtype), bytes = L * L * M * M * es;
+    if (!aligned(src, es) || !aligned(dst, es)) return QS_ERR_MISALIGNED;
+    if (overlaps(src, bytes, dst, bytes)) return QS_ERR_ALIAS;
+    return exchange_pair_transpose_back(dtype, src, dst, L, M, (hipStream_t)stream);
 }
 
 int64_t qs_transform_two_body_partial_workspace(int dtype, int64_t L, int64_t M, int64_t rows) {

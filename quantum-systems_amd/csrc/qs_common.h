@@ -215,6 +215,13 @@ int exchange_check(int dtype, const void* u, int64_t l, int* flag, hipStream_t s
 int exchange_mirror(int dtype, void* t, int64_t n, int64_t m, int64_t block, hipStream_t stream);
 // Do the grids of the check and of both mirrors of an (L -> M) transform fit their 31 bits?
 bool exchange_grids_fit(int64_t L, int64_t M);
+// The route's leading indices on pairs: dst[c,d][a,b] = src[a,b,c,d] on the pairs d >= c (both (l, l, l, l)), and the way back
+// with the other half filled in, src (l, l, m, m) stored on d >= c -> dst (m, m, l, l) on the pairs q >= p:
+// dst[p,q][c,d] = src[c,d][p,q] where d >= c, src[d,c][q,p] where d < c.  Nothing else is written; src and dst are distinct.
+int exchange_pair_transpose(int dtype, const void* src, void* dst, int64_t l, hipStream_t stream);
+int exchange_pair_transpose_back(int dtype, const void* src, void* dst, int64_t l, int64_t m, hipStream_t stream);
+// ... and whether their grids fit (fewer than 2^31 workgroups, at most 65535 along y and z)
+bool exchange_pair_grids_fit(int dtype, int64_t L, int64_t M);
 
 // Tuning knobs (qs_tuning_set / qs_tuning_reset): state of the CALLING THREAD only, so a tuning
 // run or a test cannot change the dispatch of another thread's calls; every thread starts from the
@@ -271,6 +278,10 @@ struct Tuning {
     int exchange_order = 1;      // that route's order of the contractions: 0 = the trailing indices first (d, c on the pairs of u, mirror, a, closing
                                  // blocks, mirror), 2 = the leading ones first (a, closing blocks, d, c on the pairs of the result's grid, ONE
                                  // mirror), 1 = the second where M >= L from the smallest size measured to gain, else the first
+    int exchange_leading = 1;    // the leading indices of that route's second order (exchange_order): 0 = one product and the closing blocks,
+                                 // 2 = on the pairs d >= c of u's trailing indices, between two transposes of the pair matrix (M >= L only:
+                                 // below that, and where a mover's grid does not fit, the launches of 0), 1 = the second from the smallest
+                                 // size measured to gain
     int sandwich = 1;            // 4-wide fused passes of a small-basis transform: 0 off, 1 both (d, c) and (b, a), 2 (d, c) only, 3 (b, a) only;
                                  // tuning runs, wherever the kernel exists (not only where it measured faster): 4 both, 5 (d, c) only, 6 (b, a) only
 };

@@ -322,6 +322,109 @@ __global__ __launch_bounds__(256) void exchange_transpose_kernel(T* t, int n, in
     }
 }
 
+// ----------------------------------------------------------------------------
+// The exchange route's leading indices on pairs (qs_api.hip): seen through its TRAILING indices a tensor with the symmetry
+// has u[:, :, c, d] == u[:, :, d, c]^T, so the two leading contractions are a two-sided product of the matrix over (a, b)
+// for the pairs d >= c alone -- once the pair matrix l^2 x l^2 is turned, and turned back afterwards.  Two byte movers do
+// that.  A tile fixes one index of each pair and turns the other two: on both sides it moves runs of 32 or 64 contiguous
+// elements, and the rows of a tile lie a whole matrix (l^2 elements) or more apart.
+// ----------------------------------------------------------------------------
+
+// Rows i < n of a triangle in tiles of ts elements: row i has the tiles that reach its side of the diagonal -- `up`: tiles
+// i / ts ... nt - 1 (columns j >= i), else tiles 0 ... i / ts (columns j <= i).  All of them, counted (a grid extent):
+__host__ __device__ inline int64_t triangle_tiles(int n, bool up, int ts) {
+    const int nt = (n + ts - 1) / ts;
+    int64_t sum = 0;
+    for (int B = 0; B < nt; ++B) sum += (int64_t)(n - B * ts < ts ? n - B * ts : ts) * (up ? nt - B : B + 1);
+    return sum;
+}
+
+// ... and the idx-th of them, row by row: returns the row, idx becomes the tile's place among the row's own.  (Rows of one
+// block of ts have the same count, so the loop runs over blocks; 32-bit arithmetic and one division -- with 64-bit
+// divisions in a flat index the way back took 10.8 ms where it now takes 7.5.)
+__device__ __forceinline__ int triangle_tiles_row(uint32_t& idx, int n, bool up, int ts) {
+    const int nt = (n + ts - 1) / ts;
+    int B = 0, cnt;
+    for (;; ++B) {
+        cnt = up ? nt - B : B + 1;
+        const uint32_t span = (uint32_t)(n - B * ts < ts ? n - B * ts : ts) * cnt;
+        if (idx < span || B >= nt - 1) break;
+        idx -= span;
+    }
+    const uint32_t r = idx / cnt;
+    idx -= r * cnt;
+    return B * ts + (int)r;
+}
+
+// dst[c,d][a,b] = src[a,b,c,d] for the pairs d >= c; nothing is written at d < c.  Both (l, l, l, l).  A workgroup fixes
+// (a, c) and turns one 32 x 32 tile of (b, d): it reads rows b (l^2 apart, d contiguous) and writes rows d (l^2 apart, b
+// contiguous).  The grid is three-dimensional: x = the tiles along b; a and the pair (c, tile along d) are y and z, or z
+// and y with A_SLOWEST (fp64 is faster with c slowest, 6.6 against 7.1 ms at l = 256, complex128 with a slowest, 12.1
+// against 13.4: profiles/exchange_leading_pairs_ab.txt section 1, with the other tiles and walks tried).
+template <typename T, bool A_SLOWEST>
+__global__ __launch_bounds__(256) void exchange_pair_transpose_kernel(const T* __restrict__ src, T* __restrict__ dst, int l) {
+    __shared__ T t[PT][PS];
+    const int tb = blockIdx.x, a = A_SLOWEST ? blockIdx.z : blockIdx.y;
+    uint32_t idx = A_SLOWEST ? blockIdx.y : blockIdx.z;
+    const int c = triangle_tiles_row(idx, l, true, PT), td = c / PT + (int)idx;
+    if (a >= l || c >= l) return;
+    const int64_t ll = (int64_t)l * l;
+    const int tx = threadIdx.x & (PT - 1), ty = threadIdx.x / PT;
+    const T* s = src + (a * ll + c) * l;                       // + b l^2 + d
+#pragma unroll
+    for (int rr = ty; rr < PT; rr += 8) {
+        const int b = tb * PT + rr, d = td * PT + tx;
+        if (b < l && d < l && d >= c) t[rr][tx] = stream_load(&s[b * ll + d]);
+    }
+    __syncthreads();
+    T* o = dst + (c * ll + a) * l;                             // + d l^2 + b
+#pragma unroll
+    for (int rr = ty; rr < PT; rr += 8) {
+        const int d = td * PT + rr, b = tb * PT + tx;
+        if (b < l && d < l && d >= c) stream_store(&o[d * ll + b], t[tx][rr]);
+    }
+}
+
+// The way back, with the other half filled in: src (l, l, m, m) is stored on the pairs d >= c only; on the pairs q >= p
+//   dst[p,q][c,d] = src[c,d][p,q]  where d >= c  (`upper` tiles: fix (p, c), turn (q, d)),
+//                 = src[d,c][q,p]  where d <  c  (the others:    fix (q, c), turn (p, d));
+// dst (m, m, l, l), nothing is written at q < p and src is never read at d < c.  Either kind reads rows d with the other
+// turned index y contiguous (a TD x 32 tile) and writes rows y with d contiguous.  The grid: z = the kind, x = the pair (fixed
+// index of the result's pair, tile along y), y = the pair (c, tile along d); either kind has its own triangles, the grid
+// takes the larger and the few surplus workgroups leave at once.  TD = 64 for fp64 (512-byte runs of the stores, half the
+// workgroups: 8.8 -> 7.5 ms at l = 256), 32 for complex128 (12.1 ms; 64 there: 13.8).
+template <typename T, int TD>
+__global__ __launch_bounds__(256) void exchange_pair_transpose_back_kernel(const T* __restrict__ src, T* __restrict__ dst, int l,
+                                                                           int m) {
+    __shared__ T t[TD][PS];
+    const bool upper = blockIdx.z == 0;
+    // upper: x = p with the tiles of q >= p, c with the tiles of d >= c; else x = q with the tiles of p <= q, and c >= 1 with
+    // the tiles of d <= c - 1
+    const int lc = upper ? l : l - 1;
+    uint32_t ix = blockIdx.x, ic = blockIdx.y;
+    if (ix >= (uint32_t)triangle_tiles(m, upper, PT) || ic >= (uint32_t)triangle_tiles(lc, upper, TD)) return;
+    const int x = triangle_tiles_row(ix, m, upper, PT);
+    int c = triangle_tiles_row(ic, lc, upper, TD);
+    if (x >= m || c >= lc) return;
+    int tyy = (int)ix, td = (int)ic;            // tiles along y and along d
+    if (upper) { tyy += x / PT; td += c / TD; } else { c += 1; }
+    const int64_t ll = (int64_t)l * l, mm = (int64_t)m * m;
+    const T* s = src + (upper ? ((int64_t)c * l * m + x) * m : ((int64_t)c * m + x) * m);      // + d * srs + y
+    T* o = dst + (upper ? ((int64_t)x * m * l + c) * l : ((int64_t)x * l + c) * l);            // + y * drs + d
+    const int64_t srs = upper ? mm : l * mm, drs = upper ? ll : m * ll;
+#pragma unroll
+    for (int rr = threadIdx.x / PT; rr < TD; rr += 256 / PT) {
+        const int d = td * TD + rr, tx = threadIdx.x & (PT - 1), y = tyy * PT + tx;
+        if (upper ? (y >= x && y < m && d >= c && d < l) : (y <= x && d < c)) t[rr][tx] = stream_load(&s[d * srs + y]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int rr = threadIdx.x / TD; rr < PT; rr += 256 / TD) {
+        const int y = tyy * PT + rr, tx = threadIdx.x & (TD - 1), d = td * TD + tx;
+        if (upper ? (y >= x && y < m && d >= c && d < l) : (y <= x && d < c)) stream_store(&o[y * drs + d], t[tx][rr]);
+    }
+}
+
 // ------------------------------------------------------------------ launchers
 
 static inline unsigned stream_grid(int64_t total, int block) {
@@ -394,6 +497,56 @@ int exchange_mirror(int dtype, void* t, int64_t n, int64_t m, int64_t block, hip
                            (f64x2*)t, (int)n, (int)m, nt, (int)block);
     note_dispatch("qs::exchange_transpose_kernel<%s>", dtype == QS_F64 ? "double" : "f64x2");
     return launch_status("exchange_mirror launch");
+}
+
+// The pair movers' grids: x, y, z extents (y and z hold at most 65535 workgroups each, a whole grid fewer than 2^31).
+static inline int pair_back_td(int dtype) { return dtype == QS_F64 ? 64 : PT; }
+
+struct PairGrid { int64_t x, y, z; bool fits() const { return y <= 65535 && z <= 65535 && x * y * z < (int64_t(1) << 31); } };
+
+static inline PairGrid pair_transpose_grid(int dtype, int64_t l) {
+    const int64_t pairs = triangle_tiles((int)l, true, PT);
+    return dtype == QS_F64 ? PairGrid{cdiv(l, PT), l, pairs} : PairGrid{cdiv(l, PT), pairs, l};
+}
+
+static inline PairGrid pair_transpose_back_grid(int dtype, int64_t l, int64_t m) {
+    const int td = pair_back_td(dtype);
+    const int64_t xu = triangle_tiles((int)m, true, PT), xl = triangle_tiles((int)m, false, PT);
+    const int64_t cu = triangle_tiles((int)l, true, td), cl = triangle_tiles((int)l - 1, false, td);
+    return PairGrid{xu > xl ? xu : xl, cu > cl ? cu : cl, 2};
+}
+
+bool exchange_pair_grids_fit(int dtype, int64_t L, int64_t M) {
+    return L > 0 && M > 0 && L <= 4096 && M <= 4096 && pair_transpose_grid(dtype, L).fits() && pair_transpose_back_grid(dtype, L, M).fits();
+}
+
+int exchange_pair_transpose(int dtype, const void* src, void* dst, int64_t l, hipStream_t stream) {
+    const PairGrid g = pair_transpose_grid(dtype, l);
+    if (l <= 0 || l > 4096 || !g.fits()) return QS_ERR_BAD_EXTENT;
+    const dim3 grid((unsigned)g.x, (unsigned)g.y, (unsigned)g.z);
+    if (dtype == QS_F64)
+        hipLaunchKernelGGL((exchange_pair_transpose_kernel<double, false>), grid, dim3(256), 0, stream,
+                           (const double*)src, (double*)dst, (int)l);
+    else
+        hipLaunchKernelGGL((exchange_pair_transpose_kernel<f64x2, true>), grid, dim3(256), 0, stream,
+                           (const f64x2*)src, (f64x2*)dst, (int)l);
+    note_dispatch("qs::exchange_pair_transpose_kernel<%s>", dtype == QS_F64 ? "double, false" : "f64x2, true");
+    return launch_status("exchange_pair_transpose launch");
+}
+
+int exchange_pair_transpose_back(int dtype, const void* src, void* dst, int64_t l, int64_t m, hipStream_t stream) {
+    if (l <= 0 || m <= 0 || l > 4096 || m > 4096) return QS_ERR_BAD_EXTENT;
+    const PairGrid g = pair_transpose_back_grid(dtype, l, m);
+    if (!g.fits()) return QS_ERR_BAD_EXTENT;
+    const dim3 grid((unsigned)g.x, (unsigned)g.y, (unsigned)g.z);
+    if (dtype == QS_F64)
+        hipLaunchKernelGGL((exchange_pair_transpose_back_kernel<double, 64>), grid, dim3(256), 0, stream,
+                           (const double*)src, (double*)dst, (int)l, (int)m);
+    else
+        hipLaunchKernelGGL((exchange_pair_transpose_back_kernel<f64x2, PT>), grid, dim3(256), 0, stream,
+                           (const f64x2*)src, (f64x2*)dst, (int)l, (int)m);
+    note_dispatch("qs::exchange_pair_transpose_back_kernel<%s>", dtype == QS_F64 ? "double, 64" : "f64x2, 32");
+    return launch_status("exchange_pair_transpose_back launch");
 }
 
 int spin_expand(int in_dtype, int out_dtype, const void* u, void* out, int64_t l, int64_t nq, int64_t p_lo,

@@ -432,6 +432,40 @@ def exchange_mirror_(t, block=1):
     return t
 
 
+def _pair_operands(name, src, dst, src_shape, dst_shape):
+    for t, shape in ((src, src_shape), (dst, dst_shape)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shape \
+                or t.dtype != src.dtype:
+            raise ValueError(f"{name} needs contiguous device tensors of one dtype, shapes {src_shape} and {dst_shape}")
+
+
+@_plain
+def exchange_pair_transpose(src, dst):
+    """``dst[c,d,a,b] = src[a,b,c,d]`` for the pairs ``d >= c``, both (l,l,l,l); the rest of ``dst`` is left as it is
+    (``qs_exchange_pair_transpose``: the way in of ``exchange_leading=2``); returns ``dst``."""
+    lib = _lib.load()
+    l = src.shape[0] if isinstance(src, torch.Tensor) and src.dim() == 4 else 0
+    _pair_operands("exchange_pair_transpose", src, dst, (l, l, l, l), (l, l, l, l))
+    with _on_device_of(src, dst):
+        _ran(lib.qs_exchange_pair_transpose(dtype_code(src.dtype), src.data_ptr(), dst.data_ptr(), l, _stream()),
+             "qs_exchange_pair_transpose")
+    return dst
+
+
+@_plain
+def exchange_pair_transpose_back(src, dst):
+    """The way back: ``src`` (l,l,m,m), read on the pairs ``d >= c`` only, to ``dst`` (m,m,l,l) on the pairs ``q >= p``:
+    ``dst[p,q,c,d] = src[c,d,p,q]`` where ``d >= c``, ``src[d,c,q,p]`` where ``d < c``; the rest of ``dst`` is left as it
+    is (``qs_exchange_pair_transpose_back``); returns ``dst``."""
+    lib = _lib.load()
+    l, m = (src.shape[0], src.shape[2]) if isinstance(src, torch.Tensor) and src.dim() == 4 else (0, 0)
+    _pair_operands("exchange_pair_transpose_back", src, dst, (l, l, m, m), (m, m, l, l))
+    with _on_device_of(src, dst):
+        _ran(lib.qs_exchange_pair_transpose_back(dtype_code(src.dtype), src.data_ptr(), dst.data_ptr(), l, m, _stream()),
+             "qs_exchange_pair_transpose_back")
+    return dst
+
+
 @_plain
 def transform_two_body_partial(u_slab, C, C_tilde=None, out=None):
     """Contractions over d, c, b of a leading-index slab:

@@ -1,7 +1,7 @@
 """Same-process A/B of the transform's exchange-symmetry route against the plain route, and the route's phases.
 
     python tools/exchange_route_ab.py --sizes 160,192,224,256 --dtype f64 [--blocks 32,64,128] [--blocks-d 8,16,64]
-                                      [--pairs 0,1] [--orders 0,2] [--reps 5] [--phases [--c-blocks 16,64]]
+                                      [--pairs 0,1] [--orders 0,2] [--leading 0,2] [--reps 5] [--phases [--c-blocks 16,64]]
 
 Per size: one symmetric tensor (bench.make_inputs), then the plain route (`exchange=0`) and every (block, block_d)
 of the forced route (`exchange=2`) in ALTERNATING repetitions (NOTES.md "How to measure here"), HIP-event time per
@@ -10,7 +10,9 @@ call; the route's time includes the check kernel and its read-back, as `kernels.
 pair around each (the phases of qs_api.hip's transform_two_body_exchange_route, same shapes and strides): d and c both as
 the launches per block / per row of `exchange_pairs=0` and as the one triangular-batch launch (`qs_matmul_pairs`) of
 `exchange_pairs=1`.  `--pairs 0,1` times the whole route at both settings of that key, `--orders 0,2` at both orders of the contractions
-(`exchange_order`); `--phases` then replays each of those orders' launches."""
+(`exchange_order`); `--phases` then replays each of those orders' launches.  `--leading 0,2` times order 2 with its leading
+indices as one product and the closing blocks, and on pairs between the two transposes (`exchange_leading`); with 2 in
+the list `--phases` also replays the pair movers and the two products between them, and prints the total of either form."""
 
 import argparse
 import os
@@ -34,7 +36,7 @@ def med(xs):
     return s[len(s) // 2] if len(s) % 2 else 0.5 * (s[len(s) // 2 - 1] + s[len(s) // 2])
 
 
-def phases(torch, K, u, C, Ct, out, blk, blk_d, reps, c_blocks=(), other_order=False, order=0):
+def phases(torch, K, u, C, Ct, out, blk, blk_d, reps, c_blocks=(), other_order=False, order=0, leading_pairs=False):
     """The route's launches, phase by phase (T1 and X in one spare buffer, T2 in `out`), in the order `order` takes (0: d, c,
     mirror, a, closing, mirror; 2: a, closing, d, c, mirror -- X1 and Y in the spare buffer, X2 in `out`).  `c_blocks`: also time the c phase
     with every row a of a block [a0, a1) batched over b >= a0 instead of b >= a (needs blk_d to divide those blocks)."""
@@ -62,11 +64,11 @@ def phases(torch, K, u, C, Ct, out, blk, blk_d, reps, c_blocks=(), other_order=F
             b0 = a // cb * cb
             K.gemm_raw(dt, CT, W, out, L, L, L, L, L, L, L - b0, 0, L2, L2, b_off=(a * L + b0) * L2, c_off=(a * L + b0) * L2)
 
-    def d_pairs(src=u):
-        K.gemm_raw(dt, src, C, W, L, L, L, L, L, L, 0, L2, 0, L2, pairs=L)
+    def d_pairs(src=u, dst=W, small=C):
+        K.gemm_raw(dt, src, small, dst, L, L, L, L, L, L, 0, L2, 0, L2, pairs=L)
 
-    def c_pairs(mirror=False):
-        K.gemm_raw(dt, CT, W, out, L, L, L, L, L, L, 0, 0, L2, L2, pairs=L, mirror=mirror)
+    def c_pairs(mirror=False, src=W, dst=out, small=CT):
+        K.gemm_raw(dt, small, src, dst, L, L, L, L, L, L, 0, 0, L2, L2, pairs=L, mirror=mirror)
 
     def a_(src=out):
         K.gemm_raw(dt, Ct, src, W, L, L3, L, L, L3, L3)
@@ -93,6 +95,13 @@ def phases(torch, K, u, C, Ct, out, blk, blk_d, reps, c_blocks=(), other_order=F
                  ("d", lambda: d_pairs(out)), ("c, per row", c), ("c", c_pairs), ("mirror out", lambda: mirror(1))]
         if not dt.is_complex and L % 128 == 0:      # where the c launch can store the mirror itself: against "c" + "mirror out"
             steps.append(("c, storing the mirror", lambda: c_pairs(True)))
+        if leading_pairs:
+            # exchange_leading=2: u turned into W on the pairs d >= c, b (W -> out) and a (out -> W) as the trailing pass with
+            # (Ct^T, Ct), and the way back W -> out (X2 on q >= p); in the place of "a" and "closing product"
+            CtT, W4 = Ct.t().contiguous(), W.view(L, L, L, L)
+            steps += [("pairs: way in", lambda: K.exchange_pair_transpose(u, W4)),
+                      ("pairs: b", lambda: d_pairs(W, out, CtT)), ("pairs: a", lambda: c_pairs(False, out, W, Ct)),
+                      ("pairs: way back", lambda: K.exchange_pair_transpose_back(W4, out.view(L, L, L, L)))]
     else:
         other = [("other order: b full", b_full), ("other order: a blocks", a_blocks)] if other_order else []
         steps = [("check", check), ("d, per block", d), ("d", d_pairs)] + [(f"c, b >= block {cb}", lambda cb=cb: c(cb)) for cb in c_blocks] + [
@@ -106,9 +115,13 @@ def phases(torch, K, u, C, Ct, out, blk, blk_d, reps, c_blocks=(), other_order=F
     total = 0.0
     for name, _ in steps:
         t = med(times[name][1:])
-        total += 0.0 if name.startswith(("c, ", "d, ", "other order")) else t
+        total += 0.0 if name.startswith(("c, ", "d, ", "other order", "pairs: ")) else t
         print(f"    phase {name:20s} {t:8.3f} ms   (runs: {' '.join('%.3f' % x for x in times[name][1:])})")
     print(f"    phases total     {total:8.3f} ms")
+    if order == 2 and leading_pairs:
+        blocks = med(times["a"][1:]) + med(times["closing product"][1:])
+        pairs = sum(med(times[name][1:]) for name, _ in steps if name.startswith("pairs: "))
+        print(f"    leading indices: a + closing product {blocks:8.3f} ms, on pairs {pairs:8.3f} ms; phases total on pairs {total - blocks + pairs:8.3f} ms")
     del W
 
 
@@ -120,6 +133,7 @@ def main():
     ap.add_argument("--blocks-d", default="16")
     ap.add_argument("--pairs", default="1", help="exchange_pairs settings of the route to time, e.g. 0,1")
     ap.add_argument("--orders", default="1", help="exchange_order settings of the route to time, e.g. 0,2 (1: the automatic rule)")
+    ap.add_argument("--leading", default="1", help="exchange_leading settings of the route to time, e.g. 0,2 (1: the automatic rule)")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--phases", action="store_true")
     ap.add_argument("--other-order", action="store_true", help="with --phases: also time b full, then a per block of rows")
@@ -132,7 +146,8 @@ def main():
 
     dev = torch.device("cuda:0")
     dtype = torch.float64 if args.dtype == "f64" else torch.complex128
-    configs = [(int(b), int(bd), int(pr), int(od)) for b in args.blocks.split(",") for bd in args.blocks_d.split(",") for pr in args.pairs.split(",") for od in args.orders.split(",")]
+    configs = [(int(b), int(bd), int(pr), int(od), int(ld)) for b in args.blocks.split(",") for bd in args.blocks_d.split(",") for pr in args.pairs.split(",")
+               for od in args.orders.split(",") for ld in args.leading.split(",")]
     for l in [int(x) for x in args.sizes.split(",")]:
         u, C, Ct = bench.make_inputs(torch, l, dtype, dev)
         out = torch.empty_like(u)
@@ -142,8 +157,8 @@ def main():
             with K.tuning(exchange=0):
                 K.transform_two_body(u, C, Ct, out=out)
 
-        def route(b, bd, pr, od):
-            with K.tuning(exchange=2, exchange_block=b, exchange_block_d=bd, exchange_pairs=pr, exchange_order=od):
+        def route(b, bd, pr, od, ld):
+            with K.tuning(exchange=2, exchange_block=b, exchange_block_d=bd, exchange_pairs=pr, exchange_order=od, exchange_leading=ld):
                 K.transform_two_body(u, C, Ct, out=out)
 
         plain()
@@ -164,16 +179,17 @@ def main():
         print(f"  plain                       median {base:8.3f} ms   runs {' '.join('%.3f' % x for x in runs['plain'])}")
         for cfg in configs:
             m = med(runs[cfg])
-            print(f"  route block={cfg[0]:3d} block_d={cfg[1]:3d} pairs={cfg[2]} order={cfg[3]} median {m:8.3f} ms   runs {' '.join('%.3f' % x for x in runs[cfg])}"
+            print(f"  route block={cfg[0]:3d} block_d={cfg[1]:3d} pairs={cfg[2]} order={cfg[3]} leading={cfg[4]} median {m:8.3f} ms   runs {' '.join('%.3f' % x for x in runs[cfg])}"
                   f"   plain/route {base / m:.3f}")
         sys.stdout.flush()
         if args.phases:
             for od in sorted({cfg[3] for cfg in configs}):       # (1, the automatic rule, reads as the order it takes here)
                 if od == 1:
-                    route(configs[0][0], configs[0][1], 1, 1)
+                    route(configs[0][0], configs[0][1], 1, 1, 0)
                     od = 2 if K.last_dispatch().count("exchange_transpose_kernel") == 1 else 0
                 phases(torch, K, u, C, Ct, out, configs[0][0], configs[0][1], args.reps,
-                       [int(x) for x in args.c_blocks.split(",") if x], args.other_order, od)
+                       [int(x) for x in args.c_blocks.split(",") if x], args.other_order, od,
+                       leading_pairs=od == 2 and any(cfg[4] == 2 for cfg in configs))
         del u, out
         K.workspace.release()
         torch.cuda.empty_cache()
