@@ -11,12 +11,13 @@ The directory is named ``quantum-systems_amd`` after the upstream project;
 import it as ``quantum_systems_amd`` (the sibling shim package aliases it).
 """
 
-from . import _lib, cholesky, configuration_interaction, determinant_ci, kernels, moller_plesset, response, sharded, string_ci, two_particle  # noqa: F401
+from . import _lib, cholesky, configuration_interaction, coupled_cluster, determinant_ci, kernels, moller_plesset, response, sharded, string_ci, two_particle  # noqa: F401
 from .array_module import DeviceArray, DeviceModule, hip
 from .sharded_module import ShardedDeviceModule, ShardedTensor4
 from .basis_set import BasisSet, ChangeBasisPlan
 from .cholesky import CholeskyTwoBody
 from .configuration_interaction import CIS
+from .coupled_cluster import CCD
 from .custom_system import construct_custom_system, setup_basis_set
 from .general_orbital_system import GeneralOrbitalSystem
 from .hartree_fock import HartreeFock
@@ -33,7 +34,7 @@ from .two_dim_ho import TwoDimensionalDoubleWell, TwoDimensionalHarmonicOscillat
 
 __all__ = [
     "BasisSet", "RandomBasisSet", "QuantumSystem", "SpatialOrbitalSystem",
-    "GeneralOrbitalSystem", "HartreeFock", "mp2_energy", "CIS", "configuration_interaction", "TwoParticleCI", "two_particle", "DeterminantCI", "determinant_ci", "full_space", "sz_sector", "truncated_space", "StringCI", "string_ci", "full_strings", "response", "setup_basis_set", "construct_custom_system",
+    "GeneralOrbitalSystem", "HartreeFock", "mp2_energy", "CIS", "configuration_interaction", "TwoParticleCI", "two_particle", "CCD", "coupled_cluster", "DeterminantCI", "determinant_ci", "full_space", "sz_sector", "truncated_space", "StringCI", "string_ci", "full_strings", "response", "setup_basis_set", "construct_custom_system",
     "TwoDimensionalHarmonicOscillator", "TwoDimensionalDoubleWell", "TwoDimHarmonicOscB", "ODQD", "ODSincDVR",
     "ChangeBasisPlan", "cholesky", "CholeskyTwoBody", "hip", "DeviceModule", "DeviceArray", "ShardedDeviceModule", "ShardedTensor4", "kernels", "sharded",
 ]

@@ -1,0 +1,220 @@
+"""Coupled-cluster doubles (CCD) for a ``GeneralOrbitalSystem`` with an anti-symmetrised ``u``, the particle-particle
+ladder on the UNTRANSFORMED tensor through ``kernels.pair_contract_antisym``.
+
+The ``n = system.n`` lowest orbitals of ``C`` are occupied (i, j, k, l), the rest virtual (a, b, c, d).  Amplitudes
+``t[a,b,i,j]`` are anti-symmetric in both pairs; with ``f`` the Fock matrix of the reference determinant in the orbitals
+
+    R^{ab}_{ij} = u^{ab}_{ij} + P(ab) f^b_c t^{ac}_{ij} - P(ij) f^k_j t^{ab}_{ik}
+                + 1/2 u^{ab}_{cd} t^{cd}_{ij} + 1/2 u^{kl}_{ij} t^{ab}_{kl} + P(ab) P(ij) u^{kb}_{cj} t^{ac}_{ik}
+                + 1/4 u^{kl}_{cd} t^{cd}_{ij} t^{ab}_{kl} + P(ij) u^{kl}_{cd} t^{ac}_{ik} t^{bd}_{jl}
+                - 1/2 P(ij) u^{kl}_{cd} t^{dc}_{ik} t^{ab}_{lj} - 1/2 P(ab) u^{kl}_{cd} t^{ac}_{lk} t^{db}_{ij}
+    t <- t + R / D,   D = f_ii + f_jj - f_aa - f_bb,      E_corr = 1/4 sum u^{ij}_{ab} t^{ab}_{ij}
+
+One iteration is ONE pass over the quarter of ``u`` that its symmetries do not repeat, plus O(o^3 v^3) of small products:
+
+    tau[k = (i < j)] = C_v t[:, :, i, j] C_v^T                  (l x l each, anti-symmetric; K = o (o - 1) / 2 of them)
+    S = pair_contract_antisym(u, tau)                           (the pass; u is never transformed)
+    C_v^H S[k] C_v^*  =  u^{ab}_{cd} t^{cd}_{ij},       C_o^H S[k] C_o^*  =  u^{kl}_{cd} t^{cd}_{ij}   (the 1/4 term)
+
+The blocks ``u^{ab}_{ij}``, ``u^{ij}_{ab}``, ``u^{kl}_{ij}`` and ``u^{kb}_{cj}`` are formed once, at construction
+(``transform_two_body_blocks``, or slices of ``u`` when the system is in the orbital basis already); every other term is a
+product on them and ``t``, in torch.
+
+    ccd = CCD(system, C, epsilon)            # or CCD(system) after change_basis(C); or HartreeFock.ccd()
+    e_corr = ccd.solve(tol=1e-8)             # ccd.t, ccd.residuals, ccd.converged, ccd.iterations
+"""
+
+import torch
+
+from . import kernels
+from .basis_set import _deliver, _stage
+from .general_orbital_system import GeneralOrbitalSystem
+from .sharded_module import is_sharded
+
+
+def _plain(arr):
+    return _stage(arr).as_subclass(torch.Tensor)
+
+
+def _dagger(A):
+    return A.conj().transpose(0, 1)
+
+
+def _sandwich(Ch, S):
+    """``Ch S[k] Ch^T`` for every k: ``Ch`` (m, l), ``S`` (K, l, l) -> (K, m, m), two batched products."""
+    X = kernels.matmul(Ch, S)                                          # (K, m, l): Ch S
+    Y = kernels.matmul(Ch, X.transpose(1, 2).contiguous())             # (K, m, m): Ch (Ch S)^T = (Ch S Ch^T)^T
+    return Y.transpose(1, 2)
+
+
+class CCD:
+    """Coupled-cluster doubles on the reference determinant of the ``system.n`` lowest orbitals.
+
+    ``C`` (l, l; columns = orthonormal orbitals, ``C^H s C = 1``, canonical or not) with ``epsilon`` (the diagonal of
+    the Fock matrix in them: the orbital energies ``HartreeFock.scf()`` returns) leaves the system in its basis; with
+    ``C=None`` the system is taken to be in the orbital basis already.  ``ladder="antisym"`` sends the ladder through
+    ``kernels.pair_contract_antisym`` (a quarter of ``u`` per pass), ``ladder="full"`` through ``kernels.pair_contract``
+    (all of it): the same numbers by another kernel, kept for comparison."""
+
+    def __init__(self, system, C=None, epsilon=None, ladder="antisym"):
+        if not isinstance(system, GeneralOrbitalSystem):
+            raise TypeError("CCD needs a GeneralOrbitalSystem with an anti-symmetrised u: "
+                            "pass spatial_system.construct_general_orbital_system(anti_symmetrize=True)")
+        if not system._basis_set._anti_symmetrized_u:
+            raise ValueError("CCD needs an anti-symmetrised u: build the GeneralOrbitalSystem with anti_symmetrize=True")
+        if is_sharded(system.u):
+            raise NotImplementedError("CCD does not take a sharded u: the pair contraction is not sharded -- "
+                                      "pass a system whose u lives on one device")
+        if ladder not in ("antisym", "full"):
+            raise ValueError(f"ladder must be 'antisym' or 'full', got {ladder!r}")
+        n, l = system.n, system.l
+        if not 0 < n < l:
+            raise ValueError(f"{n} occupied of {l} orbitals leave no occupied-virtual block")
+        if (C is None) != (epsilon is None):
+            raise ValueError("give both C and epsilon, or neither (system already in the orbital basis)")
+        self.system, self.ladder = system, ladder
+        self.n, self.l = n, l
+        with torch._C.DisableTorchFunctionSubclass():
+            u, h = _plain(system.u), _plain(system.h)
+            self._u = u
+            o, v = slice(0, n), slice(n, l)
+            if C is None:
+                self._dt = torch.complex128 if (u.is_complex() or h.is_complex()) else torch.float64
+                self._Co = self._Cv = None
+                f = _plain(system.construct_fock_matrix(system.h, system.u)).to(self._dt)
+                self._vvoo = u[v, v, o, o].to(self._dt).contiguous()
+                self._oovv = u[o, o, v, v].to(self._dt).contiguous()
+                self._oooo = u[o, o, o, o].to(self._dt).contiguous()
+                self._ovvo = u[o, v, v, o].to(self._dt).contiguous()
+                eps = f.diagonal()
+            else:
+                C = _plain(C)
+                if C.dim() != 2 or tuple(C.shape) != (l, l):
+                    raise ValueError(f"C must be (l, l) with l = {l}, got {tuple(C.shape)}")
+                self._dt = torch.complex128 if (C.is_complex() or u.is_complex() or h.is_complex()) else torch.float64
+                C = C.to(self._dt)
+                self._Co, self._Cv = C[:, o].contiguous(), C[:, v].contiguous()
+                self._Coh, self._Cvh = _dagger(self._Co).contiguous(), _dagger(self._Cv).contiguous()
+                cj, ck = system._mean_field_weights()
+                rho = (self._Co @ self._Coh).contiguous()
+                F = h.to(self._dt) + kernels.mean_field(u, rho, cj=cj, ck=ck).to(self._dt)
+                f = _dagger(C) @ F @ C
+                Co, Cv, Coh, Cvh = self._Co, self._Cv, self._Coh, self._Cvh
+
+                def block(b0, b1, k0, k1):
+                    return kernels.transform_two_body_blocks(u, b0, b1, k0, k1).to(self._dt)
+
+                self._vvoo = block(Cvh, Cvh, Co, Co)
+                self._oovv = block(Coh, Coh, Cv, Cv)
+                self._oooo = block(Coh, Coh, Co, Co)
+                self._ovvo = block(Coh, Cvh, Cv, Co)
+                eps = _plain(epsilon)
+                if eps.dim() != 1 or eps.shape[0] != l:
+                    raise ValueError(f"epsilon must hold the {l} diagonal Fock elements, got {tuple(eps.shape)}")
+            self._foo, self._fvv = f[o, o].contiguous(), f[v, v].contiguous()
+            eps = (eps.real if eps.is_complex() else eps).to(torch.float64)
+            eo, ev = eps[:n], eps[n:]
+            self._D = ev.neg()[:, None, None, None] - ev[None, :, None, None] + eo[None, None, :, None] + eo[None, None, None, :]
+            # the occupied pairs i < j: one amplitude matrix of the pass each
+            self._pi, self._pj = torch.triu_indices(n, n, offset=1, device=u.device)
+            self._t = self._vvoo / self._D
+        self.t = _deliver(self._t, system.np)
+        self.residuals, self.converged, self.iterations = [], False, 0
+
+    # -- the pass over u: u^{ab}_{cd} t^{cd}_{ij} and u^{kl}_{cd} t^{cd}_{ij} from one contraction
+    def _ladder(self, t):
+        n, l, nv = self.n, self.l, self.l - self.n
+        K = self._pi.numel()
+        vvoo = torch.zeros((nv, nv, n, n), dtype=self._dt, device=t.device)
+        oooo = torch.zeros((n, n, n, n), dtype=self._dt, device=t.device)
+        if K == 0:                                    # one occupied orbital: t has no anti-symmetric pair
+            return vvoo, oooo
+        tk = t[:, :, self._pi, self._pj].permute(2, 0, 1).contiguous()              # (K, v, v)
+        if self._Cv is None:
+            tau = torch.zeros((K, l, l), dtype=self._dt, device=t.device)
+            tau[:, n:, n:] = tk
+        else:
+            tau = _sandwich(self._Cv, tk).contiguous()
+        u = self._u
+        if self.ladder == "antisym":
+            S = kernels.pair_contract_antisym(u, tau)
+        else:
+            S = kernels.pair_contract(u, tau)
+        S = S.to(self._dt)
+        if self._Cv is None:
+            pp, hh = S[:, n:, n:], S[:, :n, :n]
+        else:
+            pp, hh = _sandwich(self._Cvh, S), _sandwich(self._Coh, S)
+        pp, hh = pp.permute(1, 2, 0), hh.permute(1, 2, 0)
+        vvoo[:, :, self._pi, self._pj] = pp
+        vvoo[:, :, self._pj, self._pi] = -pp
+        oooo[:, :, self._pi, self._pj] = hh
+        oooo[:, :, self._pj, self._pi] = -hh
+        return vvoo, oooo
+
+    def residual(self, t=None):
+        """``R^{ab}_{ij}`` of the amplitudes ``t`` (v, v, o, o), by default the current ones: a device tensor."""
+        with torch._C.DisableTorchFunctionSubclass():
+            t = self._t if t is None else _plain(t).to(self._dt)
+            return self._residual(t)
+
+    def _residual(self, t):
+        ein = torch.einsum
+        n, nv = self.n, self.l - self.n
+        pp, W = self._ladder(t)                                          # u^{ab}_{cd} t^{cd}_{ij},  u^{kl}_{cd} t^{cd}_{ij}
+        R = self._vvoo + 0.5 * pp
+        X = ein("bc,acij->abij", self._fvv, t)
+        R = R + X - X.transpose(0, 1)
+        Y = ein("kj,abik->abij", self._foo, t)
+        R = R - (Y - Y.transpose(2, 3))
+        R = R + 0.5 * ein("klij,abkl->abij", self._oooo, t)
+        Z = ein("kbcj,acik->abij", self._ovvo, t)
+        R = R + Z - Z.transpose(0, 1) - Z.transpose(2, 3) + Z.transpose(0, 1).transpose(2, 3)
+        R = R + 0.25 * ein("abkl,klij->abij", t, W)
+        I = ein("klcd,acik->ladi", self._oovv, t)                        # u^{kl}_{cd} t^{ac}_{ik}
+        Q = ein("ladi,bdjl->abij", I, t)
+        R = R + Q - Q.transpose(2, 3)
+        # the two one-index intermediates have a long sum and a small result: batched over the leading indices of the
+        # sum and added up afterwards, so that the device is filled (one product of that shape is one workgroup's work)
+        A = torch.bmm(self._oovv.permute(0, 2, 1, 3).reshape(n * nv, n, nv),
+                      t.permute(3, 1, 0, 2).reshape(n * nv, nv, n)).sum(0)             # u^{kl}_{cd} t^{dc}_{ik} -> [l, i]
+        B = ein("li,ablj->abij", A, t)
+        R = R - 0.5 * (B - B.transpose(2, 3))
+        A2 = torch.bmm(self._oovv.permute(0, 1, 3, 2).reshape(n * n, nv, nv),
+                       t.permute(3, 2, 1, 0).reshape(n * n, nv, nv)).sum(0)            # u^{kl}_{cd} t^{ac}_{lk} -> [d, a]
+        B2 = ein("da,dbij->abij", A2, t)
+        R = R - 0.5 * (B2 - B2.transpose(0, 1))
+        return R
+
+    def energy(self, t=None):
+        """``1/4 sum u^{ij}_{ab} t^{ab}_{ij}`` of the amplitudes (a float)."""
+        with torch._C.DisableTorchFunctionSubclass():
+            t = self._t if t is None else _plain(t).to(self._dt)
+            e = 0.25 * (self._oovv * t.permute(2, 3, 0, 1)).sum()
+            return float(e.real.item())
+
+    def solve(self, tol=1e-8, max_iter=100, mixing=0.0):
+        """Iterate ``t <- t + R / D`` (``mixing`` of the old amplitudes kept: ``t <- mixing t + (1 - mixing) (t + R / D)``)
+        until the 2-norm of ``R`` is below ``tol``.  Starts from ``t = u^{ab}_{ij} / D``, so ``max_iter=0`` returns the
+        MP2 energy.  A strongly correlated system (a shallow dot) may need ``mixing`` around 0.5 to converge.  Returns
+        the correlation energy; keeps ``t``, ``residuals`` (the norm per iteration), ``converged`` and ``iterations``."""
+        if not 0.0 <= mixing < 1.0:
+            raise ValueError(f"mixing must lie in [0, 1), got {mixing}")
+        with torch._C.DisableTorchFunctionSubclass():
+            t = self._vvoo / self._D
+            self.residuals, self.converged, self.iterations = [], False, 0
+            for it in range(1, max_iter + 1):
+                R = self._residual(t)
+                norm = float(torch.linalg.vector_norm(R).item())
+                self.residuals.append(norm)
+                if norm < tol:
+                    self.converged = True
+                    break
+                self.iterations = it
+                t = t + (1.0 - mixing) * (R / self._D)
+                # rounding leaves the anti-symmetric amplitudes, and the equations do not damp what it adds outside them
+                t = 0.5 * (t - t.transpose(0, 1))
+                t = 0.5 * (t - t.transpose(2, 3))
+            self._t = t
+            self.t = _deliver(t.contiguous(), self.system.np)
+        return self.energy()

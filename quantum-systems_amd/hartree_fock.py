@@ -187,3 +187,16 @@ class HartreeFock:
                 "the system is in its Hartree-Fock basis already (change_system_basis): C no longer refers to it -- "
                 "call string_ci.StringCI(system)")
         return StringCI(self.system, self.C, **kw)
+
+    def ccd(self, **kw):
+        """Coupled-cluster doubles on the converged orbitals of a general (``GeneralOrbitalSystem``) solution:
+        ``coupled_cluster.CCD(system, C, epsilon, **kw)``."""
+        from .coupled_cluster import CCD
+
+        if self.C is None:
+            raise RuntimeError("run scf() first")
+        if self._basis_changed:
+            raise RuntimeError(
+                "the system is in its Hartree-Fock basis already (change_system_basis): C no longer refers to it -- "
+                "call coupled_cluster.CCD(system)")
+        return CCD(self.system, self.C, self.epsilon, **kw)
