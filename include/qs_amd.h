@@ -580,8 +580,8 @@ const char* qs_last_dispatch(void);
  *     "lead_rows_max" (qs_transform_two_body_blocks: the most leading rows M0
  *     whose step a takes the streaming kernel of qs_lead_contract, 0 ... 32;
  *     a value outside that range is refused with QS_ERR_BAD_EXTENT),
- *     "pair_contract_g" (qs_pair_contract and qs_pair_contract_antisym: vectors
- *     per load of U, 0 = the shipped group size of the dtype pair, 1, 2, 4 or 8
+ *     "pair_contract_g" (qs_pair_contract, qs_pair_contract_antisym and
+ *     qs_pair_contract_exchange: vectors per load of U, 0 = the shipped group size of the dtype pair, 1, 2, 4 or 8
  *     for tuning runs),
  *     "det_ci_g" (qs_det_ci_sigma: vectors per walk of a determinant's
  *     excitations, 0 = shipped, 1, 2, 4 or 8 for tuning runs),
@@ -837,6 +837,43 @@ int64_t qs_pair_contract_antisym_workspace(int u_dtype, int t_dtype, int64_t l, 
 int qs_pair_contract_antisym(int u_dtype, int t_dtype, const void* U, const void* T, void* S,
                              int64_t l, int64_t K, int64_t ldu,
                              void* work, int64_t work_elems, void* stream);
+/*
+ * Pair contraction of a tensor with particle-exchange symmetry with ANY amplitudes,
+ * from the half of the tensor the symmetry does not repeat
+ * (csrc/qs_pair_contract_exchange.hip):
+ *   S[k,p,q] = sum_rs U[p,q,r,s] * T[k,r,s]   for all p, q      (no conjugation)
+ *   U : (l, l, l, l), consecutive (p, q) rows ldu >= l^2 elements apart;
+ *   T : (K, l, l);  S : (K, l, l), written in full.
+ * For U[p,q,r,s] = U[q,p,s,r] (the two-body integrals of spatial orbitals: what
+ * qs_two_body_exchange_symmetric checks) this is np.einsum("pqrs,krs->kpq", U, T)
+ * from half of the bytes and half of the products: with a = U[p,q,r,s],
+ * b = U[q,p,r,s] for p <= q, r <= s,
+ *   S+-[p,q] = sum_{r<=s} w_rs (a +- b) (T[k,r,s] +- T[k,s,r]),  w_rs = 1/2 if r = s else 1
+ *   S[k,p,q] = (S+ + S-) / 2,   S[k,q,p] = (S+ - S-) / 2.
+ * The particle-particle ladder of closed-shell coupled-cluster doubles on the
+ * untransformed tensor.  The symmetry is taken on trust, not checked.
+ * dtype pairs (U, T): (F64, F64) -> S fp64; (C128, C128) -> S complex128; every other
+ * pair is QS_ERR_BAD_DTYPE (a real U against complex T is the fp64 form on the real
+ * and the imaginary parts as 2 K amplitudes, which is exact).
+ * 1 <= l <= 4096, l^2 <= ldu <= 2^24, 1 <= K <= 65536.  ceil(K / G) launches and nothing
+ * else, workspace 0 bytes (`work` may be NULL); G = 8 in both forms, the tuning key
+ * "pair_contract_g" overrides it as it does for qs_pair_contract.
+ * Promises (tests/test_gpu_pair_contract_exchange.py):
+ *   1. only U[p,q,r,s] with r <= s is read; all of T[k] is read;
+ *   2. S[k] has the same bits alone, at any position in a batch of any K, under any
+ *      "pair_contract_g" and on repetition: the order of every sum depends on l only;
+ *   3. if T[k] equals its transpose bit for bit, S[k,q,p] and S[k,p,q] have the same
+ *      bits; if T[k] = -T[k]^T, they differ in the sign bit only;
+ *   4. a non-finite value in a read element of row (p, q) of U reaches S[:, p, q] and
+ *      S[:, q, p] only, one in T[k] reaches S[k] only.
+ * Errors, checked in this order before any HIP call: dtype pair, extents (l < 1,
+ * K < 1, ldu < l^2 included), null U / T / S, misaligned pointer (element size), S
+ * overlapping U or T (QS_ERR_ALIAS), work_elems below the query (negative).
+ */
+int64_t qs_pair_contract_exchange_workspace(int u_dtype, int t_dtype, int64_t l, int64_t K);
+int qs_pair_contract_exchange(int u_dtype, int t_dtype, const void* U, const void* T, void* S,
+                              int64_t l, int64_t K, int64_t ldu,
+                              void* work, int64_t work_elems, void* stream);
 /*
  * Direct configuration interaction on Slater determinants (csrc/qs_det_ci.hip):
  *   H = sum_pq ht[p,q] a+_p a_q + 1/4 sum_pqrs ut[p,q,r,s] a+_p a+_q a_s a_r

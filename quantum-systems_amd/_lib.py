@@ -103,6 +103,8 @@ SIGNATURES = {
     "qs_pair_contract": (c_int, [c_int, c_int, c_ptr, c_ptr, c_ptr] + [c_i64] * 4 + [c_ptr, c_i64, c_ptr]),
     "qs_pair_contract_antisym_workspace": (c_i64, [c_int, c_int, c_i64, c_i64]),
     "qs_pair_contract_antisym": (c_int, [c_int, c_int, c_ptr, c_ptr, c_ptr] + [c_i64] * 3 + [c_ptr, c_i64, c_ptr]),
+    "qs_pair_contract_exchange_workspace": (c_i64, [c_int, c_int, c_i64, c_i64]),
+    "qs_pair_contract_exchange": (c_int, [c_int, c_int, c_ptr, c_ptr, c_ptr] + [c_i64] * 3 + [c_ptr, c_i64, c_ptr]),
     "qs_det_ci_workspace": (c_i64, [c_int, c_int] + [c_i64] * 4),
     "qs_det_ci_diagonal": (c_int, [c_int, c_ptr, c_ptr, c_ptr, c_ptr] + [c_i64] * 3 + [c_ptr]),
     "qs_det_ci_sigma": (c_int, [c_int, c_int] + [c_ptr] * 6 + [c_i64] * 5 + [c_ptr, c_i64, c_ptr]),

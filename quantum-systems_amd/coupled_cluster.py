@@ -1,5 +1,6 @@
-"""Coupled-cluster doubles (CCD) for a ``GeneralOrbitalSystem`` with an anti-symmetrised ``u``, the particle-particle
-ladder on the UNTRANSFORMED tensor through ``kernels.pair_contract_antisym``.
+"""Coupled-cluster doubles: ``CCD`` for a ``GeneralOrbitalSystem`` with an anti-symmetrised ``u``, the particle-particle
+ladder on the UNTRANSFORMED tensor through ``kernels.pair_contract_antisym``; ``RCCD`` (below) for a closed shell on a
+``SpatialOrbitalSystem``, spin-summed, its ladder through ``kernels.pair_contract_exchange``.
 
 The ``n = system.n`` lowest orbitals of ``C`` are occupied (i, j, k, l), the rest virtual (a, b, c, d).  Amplitudes
 ``t[a,b,i,j]`` are anti-symmetric in both pairs; with ``f`` the Fock matrix of the reference determinant in the orbitals
@@ -30,6 +31,7 @@ from . import kernels
 from .basis_set import _deliver, _stage
 from .general_orbital_system import GeneralOrbitalSystem
 from .sharded_module import is_sharded
+from .spatial_orbital_system import SpatialOrbitalSystem
 
 
 def _plain(arr):
@@ -215,6 +217,211 @@ class CCD:
                 # rounding leaves the anti-symmetric amplitudes, and the equations do not damp what it adds outside them
                 t = 0.5 * (t - t.transpose(0, 1))
                 t = 0.5 * (t - t.transpose(2, 3))
+            self._t = t
+            self.t = _deliver(t.contiguous(), self.system.np)
+        return self.energy()
+
+
+_EXCHANGE_ROUNDING = 1e-10
+
+
+def _exchange_symmetric_to_rounding(u):
+    """Is ``u[p,q,r,s] - u[q,p,s,r]`` at most ``_EXCHANGE_ROUNDING * max|u|`` everywhere?  What a four-index transform
+    leaves of the symmetry where it did not take the mirrored route (``change_basis``): the fp64 rounding of sums of
+    4 l terms, about 1e-13 at l = 256, times the growth under a non-unitary ``C`` -- far below any tolerance ``solve``
+    is used with, and far above it a tensor simply does not have the symmetry.  Looked at only after the bit-for-bit
+    check of ``kernels.two_body_exchange_symmetric`` has failed; one (l, l, l) slab at a time, no copy of ``u``."""
+    worst = torch.zeros((), dtype=torch.float64, device=u.device)
+    top = torch.zeros((), dtype=torch.float64, device=u.device)
+    for p in range(u.shape[0]):
+        worst = torch.maximum(worst, (u[p] - u[:, p].transpose(1, 2)).abs().max())
+        top = torch.maximum(top, u[p].abs().max())
+    return bool(worst <= _EXCHANGE_ROUNDING * top)
+
+
+class RCCD:
+    """Spin-adapted closed-shell coupled-cluster doubles on a ``SpatialOrbitalSystem``: the ``system.n`` lowest orbitals
+    of ``C`` doubly occupied (i, j, k, l), the rest virtual (a, b, c, d), ``u`` as it is (``<pq|rs>``, not
+    anti-symmetrised, never spin-doubled).  Amplitudes ``t[a,b,i,j] = t[b,a,j,i]``; with ``P X = X^{ab}_{ij} + X^{ba}_{ji}``
+
+        L_klcd = 2<kl|cd> - <kl|dc>
+        W_klij = <kl|ij> + sum_cd <kl|cd> t^{cd}_{ij}
+        F_bc = f_bc - sum_kld L_klcd t^{bd}_{kl}                 F_kj = f_kj + sum_lcd L_klcd t^{cd}_{jl}
+        Wd_kbcj =  <kb|cj> - 1/2 sum_ld <kl|cd> t^{db}_{jl} + 1/2 sum_ld L_klcd t^{db}_{lj}
+        Wx_kbjc = -<kb|jc> + 1/2 sum_ld <kl|dc> t^{db}_{jl}
+        R^{ab}_{ij} = <ab|ij> + sum_cd <ab|cd> t^{cd}_{ij} + sum_kl W_klij t^{ab}_{kl}
+                    + P{ F_bc t^{ac}_{ij} - F_kj t^{ab}_{ik}
+                         + sum_kc [(t^{ac}_{ik} - t^{ca}_{ik}) Wd_kbcj + t^{ac}_{ik} (Wd_kbcj + Wx_kbjc) + t^{ac}_{kj} Wx_kbic] }
+        t <- t + R / D,   D = f_ii + f_jj - f_aa - f_bb,      E_corr = sum (2<ij|ab> - <ij|ba>) t^{ab}_{ij}
+
+    One iteration is ONE pass over the half of ``u`` that its particle-exchange symmetry does not repeat:
+
+        tau[k = (i <= j)] = C_v t[:, :, i, j] C_v^T                 (l x l each, generic; K = o (o + 1) / 2 of them)
+        S = pair_contract_exchange(u, tau)                          (the pass; u is never transformed)
+        C_v^H S[k] C_v^*  =  sum_cd <ab|cd> t^{cd}_{ij},     C_o^H S[k] C_o^*  =  sum_cd <kl|cd> t^{cd}_{ij}
+
+    and the (j, i) results are their transposes.  The blocks vvoo, oovv, oooo, ovvo and ovov are formed once, at
+    construction.  ``ladder="exchange"`` sends the ladder through ``kernels.pair_contract_exchange`` (half of ``u`` per
+    pass), ``ladder="full"`` through ``kernels.pair_contract`` (all of it): the same numbers by another kernel.
+    ``C``, ``epsilon``, ``solve``, ``residual``, ``energy``, ``t``, ``residuals``, ``converged`` and ``iterations`` are
+    those of ``CCD``; ``max_iter=0`` gives the closed-shell MP2 energy.  ``u`` is checked for the symmetry once, at
+    construction, for either ladder: bit for bit, and where that fails (a ``u`` that went through ``change_basis``) to
+    rounding (``_exchange_symmetric_to_rounding``); anything else is refused."""
+
+    def __init__(self, system, C=None, epsilon=None, ladder="exchange"):
+        if isinstance(system, GeneralOrbitalSystem):
+            raise TypeError("RCCD needs a SpatialOrbitalSystem: for a GeneralOrbitalSystem call coupled_cluster.CCD")
+        if not isinstance(system, SpatialOrbitalSystem):
+            raise TypeError("RCCD needs a SpatialOrbitalSystem")
+        if is_sharded(system.u):
+            raise NotImplementedError("RCCD does not take a sharded u: the pair contraction is not sharded -- "
+                                      "pass a system whose u lives on one device")
+        if ladder not in ("exchange", "full"):
+            raise ValueError(f"ladder must be 'exchange' or 'full', got {ladder!r}")
+        n, l = system.n, system.l                     # a SpatialOrbitalSystem keeps the doubly occupied orbitals as its n
+        if not 0 < n < l:
+            raise ValueError(f"{n} doubly occupied of {l} orbitals leave no occupied-virtual block")
+        if (C is None) != (epsilon is None):
+            raise ValueError("give both C and epsilon, or neither (system already in the orbital basis)")
+        self.system, self.ladder = system, ladder
+        self.n, self.l = n, l
+        with torch._C.DisableTorchFunctionSubclass():
+            u, h = _plain(system.u), _plain(system.h)
+            if not kernels.two_body_exchange_symmetric(u) and not _exchange_symmetric_to_rounding(u):
+                raise ValueError("RCCD needs a u with particle-exchange symmetry, u[p,q,r,s] = u[q,p,s,r]: "
+                                 "both ladders and the equations rest on it")
+            self._u = u
+            o, v = slice(0, n), slice(n, l)
+            if C is None:
+                self._dt = torch.complex128 if (u.is_complex() or h.is_complex()) else torch.float64
+                self._Co = self._Cv = None
+                f = _plain(system.construct_fock_matrix(system.h, system.u)).to(self._dt)
+                self._vvoo = u[v, v, o, o].to(self._dt).contiguous()
+                self._oovv = u[o, o, v, v].to(self._dt).contiguous()
+                self._oooo = u[o, o, o, o].to(self._dt).contiguous()
+                self._ovvo = u[o, v, v, o].to(self._dt).contiguous()
+                self._ovov = u[o, v, o, v].to(self._dt).contiguous()
+                eps = f.diagonal()
+            else:
+                C = _plain(C)
+                if C.dim() != 2 or tuple(C.shape) != (l, l):
+                    raise ValueError(f"C must be (l, l) with l = {l}, got {tuple(C.shape)}")
+                self._dt = torch.complex128 if (C.is_complex() or u.is_complex() or h.is_complex()) else torch.float64
+                C = C.to(self._dt)
+                self._Co, self._Cv = C[:, o].contiguous(), C[:, v].contiguous()
+                self._Coh, self._Cvh = _dagger(self._Co).contiguous(), _dagger(self._Cv).contiguous()
+                cj, ck = system._mean_field_weights()
+                rho = (2.0 * (self._Co @ self._Coh)).contiguous()                  # the spin-summed density
+                F = h.to(self._dt) + kernels.mean_field(u, rho, cj=cj, ck=ck).to(self._dt)
+                f = _dagger(C) @ F @ C
+                Co, Cv, Coh, Cvh = self._Co, self._Cv, self._Coh, self._Cvh
+
+                def block(b0, b1, k0, k1):
+                    return kernels.transform_two_body_blocks(u, b0, b1, k0, k1).to(self._dt)
+
+                self._vvoo = block(Cvh, Cvh, Co, Co)
+                self._oovv = block(Coh, Coh, Cv, Cv)
+                self._oooo = block(Coh, Coh, Co, Co)
+                self._ovvo = block(Coh, Cvh, Cv, Co)
+                self._ovov = block(Coh, Cvh, Co, Cv)
+                eps = _plain(epsilon)
+                if eps.dim() != 1 or eps.shape[0] != l:
+                    raise ValueError(f"epsilon must hold the {l} diagonal Fock elements, got {tuple(eps.shape)}")
+            self._foo, self._fvv = f[o, o].contiguous(), f[v, v].contiguous()
+            self._L = 2.0 * self._oovv - self._oovv.transpose(2, 3)
+            eps = (eps.real if eps.is_complex() else eps).to(torch.float64)
+            eo, ev = eps[:n], eps[n:]
+            self._D = ev.neg()[:, None, None, None] - ev[None, :, None, None] + eo[None, None, :, None] + eo[None, None, None, :]
+            # the occupied pairs i <= j: one amplitude matrix of the pass each
+            self._pi, self._pj = torch.triu_indices(n, n, device=u.device)
+            self._t = self._vvoo / self._D
+        self.t = _deliver(self._t, system.np)
+        self.residuals, self.converged, self.iterations = [], False, 0
+
+    # -- the pass over u: sum_cd <ab|cd> t^{cd}_{ij} and sum_cd <kl|cd> t^{cd}_{ij} from one contraction
+    def _ladder(self, t):
+        n, l, nv = self.n, self.l, self.l - self.n
+        K = self._pi.numel()
+        tk = t[:, :, self._pi, self._pj].permute(2, 0, 1).contiguous()              # (K, v, v)
+        if self._Cv is None:
+            tau = torch.zeros((K, l, l), dtype=self._dt, device=t.device)
+            tau[:, n:, n:] = tk
+        else:
+            tau = _sandwich(self._Cv, tk).contiguous()
+        u = self._u
+        if self.ladder == "exchange":
+            S = kernels.pair_contract_exchange(u, tau)
+        else:
+            S = kernels.pair_contract(u, tau)
+        S = S.to(self._dt)
+        if self._Cv is None:
+            pp, hh = S[:, n:, n:], S[:, :n, :n]
+        else:
+            pp, hh = _sandwich(self._Cvh, S), _sandwich(self._Coh, S)
+        vvoo = torch.empty((nv, nv, n, n), dtype=self._dt, device=t.device)
+        oooo = torch.empty((n, n, n, n), dtype=self._dt, device=t.device)
+        # the (j, i) results are the transposes: sum_cd <ab|cd> t^{cd}_{ji} = sum_cd <ba|dc> t^{dc}_{ij}
+        vvoo[:, :, self._pj, self._pi] = pp.permute(2, 1, 0)
+        vvoo[:, :, self._pi, self._pj] = pp.permute(1, 2, 0)
+        oooo[:, :, self._pj, self._pi] = hh.permute(2, 1, 0)
+        oooo[:, :, self._pi, self._pj] = hh.permute(1, 2, 0)
+        return vvoo, oooo
+
+    def residual(self, t=None):
+        """``R^{ab}_{ij}`` of the amplitudes ``t`` (v, v, o, o) with ``t[a,b,i,j] = t[b,a,j,i]``, by default the
+        current ones: a device tensor."""
+        with torch._C.DisableTorchFunctionSubclass():
+            t = self._t if t is None else _plain(t).to(self._dt)
+            return self._residual(t)
+
+    def _residual(self, t):
+        ein = torch.einsum
+        n, nv = self.n, self.l - self.n
+        oovv, L = self._oovv, self._L
+        pp, hh = self._ladder(t)                                         # sum_cd <ab|cd> t^{cd}_{ij},  sum_cd <kl|cd> t^{cd}_{ij}
+        W = self._oooo + hh
+        R = self._vvoo + pp + ein("klij,abkl->abij", W, t)
+        # the two one-index intermediates have a long sum and a small result: batched over the leading indices of the
+        # sum and added up afterwards, so that the device is filled (one product of that shape is one workgroup's work)
+        Fvv = self._fvv - torch.bmm(t.permute(2, 3, 0, 1).reshape(n * n, nv, nv),
+                                    L.permute(0, 1, 3, 2).reshape(n * n, nv, nv)).sum(0)       # L_klcd t^{bd}_{kl} -> [b, c]
+        Foo = self._foo + torch.bmm(L.permute(1, 2, 0, 3).reshape(n * nv, n, nv),
+                                    t.permute(3, 0, 1, 2).reshape(n * nv, nv, n)).sum(0)       # L_klcd t^{cd}_{jl} -> [k, j]
+        Wd = self._ovvo - 0.5 * ein("klcd,dbjl->kbcj", oovv, t) + 0.5 * ein("klcd,dblj->kbcj", L, t)
+        Wx = -self._ovov + 0.5 * ein("kldc,dbjl->kbjc", oovv, t)
+        X = ein("bc,acij->abij", Fvv, t) - ein("kj,abik->abij", Foo, t)
+        X = X + ein("acik,kbcj->abij", t - t.transpose(0, 1), Wd)
+        X = X + ein("acik,kbcj->abij", t, Wd + Wx.transpose(2, 3))
+        X = X + ein("ackj,kbic->abij", t, Wx)
+        return R + X + X.transpose(0, 1).transpose(2, 3)
+
+    def energy(self, t=None):
+        """``sum (2<ij|ab> - <ij|ba>) t^{ab}_{ij}`` of the amplitudes (a float)."""
+        with torch._C.DisableTorchFunctionSubclass():
+            t = self._t if t is None else _plain(t).to(self._dt)
+            e = (self._L * t.permute(2, 3, 0, 1)).sum()
+            return float(e.real.item())
+
+    def solve(self, tol=1e-8, max_iter=100, mixing=0.0):
+        """Iterate ``t <- t + R / D`` (``mixing`` of the old amplitudes kept) until the 2-norm of ``R`` is below ``tol``,
+        as ``CCD.solve``.  Starts from ``t = <ab|ij> / D``, so ``max_iter=0`` returns the closed-shell MP2 energy.
+        Returns the correlation energy; keeps ``t``, ``residuals``, ``converged`` and ``iterations``."""
+        if not 0.0 <= mixing < 1.0:
+            raise ValueError(f"mixing must lie in [0, 1), got {mixing}")
+        with torch._C.DisableTorchFunctionSubclass():
+            t = self._vvoo / self._D
+            self.residuals, self.converged, self.iterations = [], False, 0
+            for it in range(1, max_iter + 1):
+                R = self._residual(t)
+                norm = float(torch.linalg.vector_norm(R).item())
+                self.residuals.append(norm)
+                if norm < tol:
+                    self.converged = True
+                    break
+                self.iterations = it
+                t = t + (1.0 - mixing) * (R / self._D)
+                # back onto t^{ab}_{ij} = t^{ba}_{ji}: the (j, i) halves of the ladder are taken from it
+                t = 0.5 * (t + t.transpose(0, 1).transpose(2, 3))
             self._t = t
             self.t = _deliver(t.contiguous(), self.system.np)
         return self.energy()

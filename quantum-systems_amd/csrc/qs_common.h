@@ -263,7 +263,7 @@ struct Tuning {
                                  // 8 = the 8-row instantiation, the largest measured one that beats the product (profiles/r08_blocks.txt)
     int mean_field_batch_g = 0;  // qs_mean_field_batch: densities per load of u, 0 = the shipped group size of the form; 1, 2, 4, 8 = tuning runs
                                  // (the chunk length follows the group size: results of different settings agree to rounding, not bit for bit)
-    int pair_contract_g = 0;     // qs_pair_contract, qs_pair_contract_antisym: vectors per load of U, 0 = the shipped group size of the form; 1, 2, 4, 8 = tuning runs
+    int pair_contract_g = 0;     // qs_pair_contract, qs_pair_contract_antisym, qs_pair_contract_exchange: vectors per load of U, 0 = the shipped group size of the form; 1, 2, 4, 8 = tuning runs
                                  // (every setting gives the same bits: the fma chains and the closing butterfly do not know G)
     int det_ci_g = 0;            // qs_det_ci_sigma: vectors per walk of a determinant's excitations, 0 = the shipped group size of the form;
                                  // 1, 2, 4, 8 = tuning runs (every setting gives the same bits: a vector's fma chain does not know G)

@@ -189,14 +189,17 @@ class HartreeFock:
         return StringCI(self.system, self.C, **kw)
 
     def ccd(self, **kw):
-        """Coupled-cluster doubles on the converged orbitals of a general (``GeneralOrbitalSystem``) solution:
-        ``coupled_cluster.CCD(system, C, epsilon, **kw)``."""
-        from .coupled_cluster import CCD
+        """Coupled-cluster doubles on the converged orbitals: ``coupled_cluster.RCCD(system, C, epsilon, **kw)`` for a
+        closed shell (``SpatialOrbitalSystem``), ``coupled_cluster.CCD(system, C, epsilon, **kw)`` for a general
+        (``GeneralOrbitalSystem``) solution."""
+        from .coupled_cluster import CCD, RCCD
+        from .spatial_orbital_system import SpatialOrbitalSystem
 
+        cls = RCCD if isinstance(self.system, SpatialOrbitalSystem) else CCD
         if self.C is None:
             raise RuntimeError("run scf() first")
         if self._basis_changed:
             raise RuntimeError(
                 "the system is in its Hartree-Fock basis already (change_system_basis): C no longer refers to it -- "
-                "call coupled_cluster.CCD(system)")
-        return CCD(self.system, self.C, self.epsilon, **kw)
+                f"call coupled_cluster.{cls.__name__}(system)")
+        return cls(self.system, self.C, self.epsilon, **kw)

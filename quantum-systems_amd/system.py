@@ -77,16 +77,20 @@ class QuantumSystem(metaclass=abc.ABCMeta):
         cj, ck = self._mean_field_weights()
         return _deliver(kernels.mean_field_batch(_stage(u), _stage(rhos), cj=cj, ck=ck), self.np)
 
-    def contract_two_body_pairs(self, T, u=None, antisymmetric=False):
+    def contract_two_body_pairs(self, T, u=None, antisymmetric=False, exchange=False):
         """``S[k,p,q] = sum_rs u[p,q,r,s] T[k,r,s]`` for a stack of two-index amplitudes ``T`` (K, l, l), or one (l, l),
         from ONE read of ``u`` per group of them (``kernels.pair_contract``): the two-body part of the sigma vector of
         a two-particle state, the particle-particle ladder of coupled-cluster doubles.  No conjugation; a real ``u``
         with complex amplitudes stays real.  ``antisymmetric=True`` states that ``T[k] = -T[k]^T`` and needs the basis
-        set's anti-symmetrised ``u``: ``kernels.pair_contract_antisym`` then reads a quarter of ``u``."""
+        set's anti-symmetrised ``u``: ``kernels.pair_contract_antisym`` then reads a quarter of ``u``.
+        ``exchange=True`` is the caller's word that ``u[p,q,r,s] = u[q,p,s,r]`` (the ``u`` of a spatial basis set; any
+        amplitudes): ``kernels.pair_contract_exchange`` then reads half of ``u``."""
         from . import kernels
         from .basis_set import _deliver, _stage
         from .sharded_module import is_sharded
 
+        if antisymmetric and exchange:
+            raise ValueError("antisymmetric=True and exchange=True name two different kernels: set one of them")
         if antisymmetric and not (u is None and getattr(self._basis_set, "_anti_symmetrized_u", False)):
             raise ValueError("antisymmetric=True needs the basis set's own anti-symmetrised u "
                              "(a GeneralOrbitalSystem built with anti_symmetrize=True)")
@@ -94,7 +98,8 @@ class QuantumSystem(metaclass=abc.ABCMeta):
         if is_sharded(u):
             raise NotImplementedError("contract_two_body_pairs does not take a sharded u: "
                                       "the pair contraction is not sharded")
-        contract = kernels.pair_contract_antisym if antisymmetric else kernels.pair_contract
+        contract = (kernels.pair_contract_antisym if antisymmetric else
+                    kernels.pair_contract_exchange if exchange else kernels.pair_contract)
         return _deliver(contract(_stage(u), _stage(T)), self.np)
 
     def construct_fock_matrix_from_density(self, rho_qp, h=None, u=None, f=None):
