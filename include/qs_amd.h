@@ -1231,6 +1231,50 @@ int64_t qs_cholesky_two_body_block(void);
 int qs_cholesky_two_body(int dtype, const void* u, int64_t m, double tau, void* vectors, int64_t capacity,
                          int64_t* rank, double* diag, int64_t* pivots, double* extremes, void* work,
                          int64_t work_bytes, void* stream);
+/*
+ * Coulomb elements of the two-dimensional harmonic oscillator by exact quadrature
+ * (csrc/qs_tdho_quadrature.hip): the tensor of
+ * qs_tdho_coulomb_elements / _nm, omega = 1, from a form with no cancellation,
+ *   out[p - p_lo, q, r, s] = sum_{g < R} (F_pr[g] * F_qs[g]) * wt_g   where m_p + m_q == m_r + m_s,
+ *                            +0.0                                      elsewhere,
+ * one fma chain over ascending g.  F_pr[g] is the form factor of the orbital pair
+ * at node k_g: a signed product of two orthonormal Laguerre functions of k_g^2 / 4.
+ * R = max_shell nodes (the positive half of the 2R-point Gauss-Hermite rule) make
+ * the sum exact: the integrand is exp(-k^2 / 2) times an even polynomial of degree
+ * <= 4 (R - 1).  Measured against 80-digit values up to 22 shells: DESIGN 3.19.
+ *   out       : (p_hi - p_lo, l, l, l) fp64, device, 8-byte aligned
+ *   nm_table  : device array of 2 l int32 (n of every orbital, then m of every
+ *               orbital) with max_shell = max(2 n + |m| + 1) over it, or NULL:
+ *               the shell order of qs_tdho_coulomb_elements, and max_shell is
+ *               ignored and derived from l
+ *   workspace : qs_tdho_coulomb_quadrature_workspace bytes, device, 16-byte
+ *               aligned: F (l, l, max_shell) and the orbitals grouped by m.  The
+ *               query takes max_shell <= 0 for the shell order.
+ * Limits: 1 <= l <= 2048, 1 <= max_shell <= 32 (shell order: l <= 528), else
+ * QS_ERR_BAD_EXTENT.  A table that exceeds its max_shell gives wrong numbers for
+ * the orbitals that do, and is never read or written out of bounds.
+ * Promises:
+ *   - the bits of an element depend on neither p_lo / p_hi nor repetition;
+ *   - u[p,q,r,s], u[q,p,s,r] and u[r,s,p,q] have identical bits (F[p][r] and
+ *     F[r][p] are one number, and the product above commutes), so
+ *     qs_two_body_exchange_symmetric says yes;
+ *   - an element that does not conserve m is +0.0, sign bit included.
+ * Three launches in stream order (the index of m groups, F, the assembly: one store
+ * per element, no atomics); asynchronous.  Errors, in this order, before any HIP
+ * call: null out / workspace (and bytes of the query); extents (l, the slab,
+ * max_shell); misaligned pointer (8 out, 4 nm_table, 16 workspace);
+ * workspace_bytes below the query (QS_ERR_WORKSPACE).
+ *
+ * qs_tdho_quadrature_nodes: HOST arrays k_out, w_out of max_shell doubles receive
+ * the nodes k_g = sqrt(2) t_g, ascending, and the weights wt_g = sqrt(2) w_g
+ * exp(t_g^2) of that rule (t_g, w_g: the positive half of Gauss-Hermite with
+ * 2 max_shell points).  Plain host code, no HIP call.  (Additions: the ABI version
+ * stays 4.)
+ */
+int qs_tdho_quadrature_nodes(int64_t max_shell, double* k_out, double* w_out);
+int qs_tdho_coulomb_quadrature_workspace(int64_t l, int64_t max_shell, int64_t* bytes);
+int qs_tdho_coulomb_quadrature(void* out, const void* nm_table, int64_t l, int64_t max_shell, int64_t p_lo,
+                               int64_t p_hi, void* workspace, int64_t workspace_bytes, void* stream);
 int qs_probe_mfma_f64(void* sink, int64_t blocks, int64_t iters, void* stream);
 int qs_probe_stream_copy(const void* src, void* dst, int64_t bytes, void* stream);
 

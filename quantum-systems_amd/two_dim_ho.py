@@ -22,6 +22,7 @@ setting it and raises upstream, two_dim_ho.py:190-210; the element generator is
 here as a function).
 """
 
+import ctypes
 import math
 
 import numpy
@@ -68,17 +69,64 @@ def get_one_body_elements(num_orbitals):
     return h
 
 
-def get_coulomb_elements(num_orbitals, p_lo=0, p_hi=None, device=None, nm=None):
+QUADRATURE_MAX_SHELLS = 32     # nodes of qs_tdho_coulomb_quadrature
+COULOMB_METHODS = ("closed_form", "quadrature")
+
+
+def _quadrature_shells(num_orbitals, nm):
+    """Shells (= nodes) of an orbital table, or of the shell order; refuses more than the kernel takes."""
+    if nm is None:
+        shells = get_shell_energy(*get_indices_nm(num_orbitals - 1))
+    else:
+        shells = int((2 * nm[:, 0] + abs(nm[:, 1]) + 1).max())
+    if shells > QUADRATURE_MAX_SHELLS:
+        raise ValueError(f"the quadrature generator takes at most {QUADRATURE_MAX_SHELLS} shells, not {shells}")
+    return shells
+
+
+def _coulomb_quadrature(out, num_orbitals, p_lo, p_hi, nm, device, stream):
+    """``method="quadrature"`` of ``get_coulomb_elements``: the exact Gauss-Hermite
+    form (``qs_tdho_coulomb_quadrature``), which has no cancellation."""
+    lib = _lib.load()
+    shells = _quadrature_shells(num_orbitals, nm)
+    table = None if nm is None else torch.from_numpy(numpy.ascontiguousarray(nm.T)).to(device)   # n of all, then m of all
+    table_ptr = None if table is None else table.data_ptr()
+    need = ctypes.c_int64(0)
+    _lib.check(lib.qs_tdho_coulomb_quadrature_workspace(num_orbitals, shells, ctypes.byref(need)),
+               "qs_tdho_coulomb_quadrature_workspace")
+    work = torch.empty(need.value, dtype=torch.uint8, device=device)
+    _lib.check(
+        lib.qs_tdho_coulomb_quadrature(out.data_ptr(), table_ptr, num_orbitals, shells, p_lo, p_hi, work.data_ptr(),
+                                       need.value, stream),
+        "qs_tdho_coulomb_quadrature",
+    )
+    return out
+
+
+def get_coulomb_elements(num_orbitals, p_lo=0, p_hi=None, device=None, nm=None, method="closed_form"):
     """Coulomb elements ``u[p, q, r, s]`` (omega = 1) as a device tensor,
     rows ``p_lo:p_hi`` (two_dim_helper.py:185-268; generated on the GPU).
     ``nm``: optional list of (n, m) per orbital replacing the shell order
-    (``get_coulomb_elements_B``, two_dim_helper.py:284-301)."""
+    (``get_coulomb_elements_B``, two_dim_helper.py:284-301).
+    ``method``: ``"closed_form"``, the alternating sums of the reference, which
+    lose digits from about 9 shells on, or ``"quadrature"``, exact up to 32
+    shells."""
+    if method not in COULOMB_METHODS:
+        raise ValueError(f"method must be one of {COULOMB_METHODS}, not {method!r}")
+    if method == "quadrature":
+        if nm is not None:
+            nm = numpy.asarray(nm, dtype=numpy.int32)
+            if nm.shape != (num_orbitals, 2):
+                raise ValueError("nm must list (n, m) for every orbital")
+        _quadrature_shells(num_orbitals, nm)        # the limit is a ValueError with or without a GPU
     if not torch.cuda.is_available():
         raise RuntimeError("the Coulomb-element generator runs on the GPU only")
     p_hi = num_orbitals if p_hi is None else p_hi
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
     out = torch.empty((p_hi - p_lo,) + (num_orbitals,) * 3, dtype=torch.float64, device=device)
     stream = torch.cuda.current_stream().cuda_stream
+    if method == "quadrature":
+        return _coulomb_quadrature(out, num_orbitals, p_lo, p_hi, nm, device, stream)
     if nm is None:
         _lib.check(_lib.load().qs_tdho_coulomb_elements(out.data_ptr(), num_orbitals, p_lo, p_hi, stream),
                    "qs_tdho_coulomb_elements")
@@ -232,10 +280,16 @@ class TwoDimensionalHarmonicOscillator(BasisSet):
     ``h = omega * diag(shell energies)``, ``s = 1``,
     ``u = sqrt(omega) * Coulomb elements``, the orbitals on the polar grid
     ``radius x theta`` and the dipole elements (two_dim_ho.py:60-139).  Same
-    constructor as the reference."""
+    constructor as the reference, and ``coulomb``: the generator of ``u``,
+    ``"closed_form"`` (the reference's sums) or ``"quadrature"`` (exact up to 32
+    shells: ``get_coulomb_elements``)."""
 
-    def __init__(self, l, radius_length, num_grid_points, omega=1, mass=1, verbose=False, **kwargs):
+    def __init__(self, l, radius_length, num_grid_points, omega=1, mass=1, verbose=False, coulomb="closed_form",
+                 **kwargs):
         super().__init__(l, dim=2, **kwargs)
+        if coulomb not in COULOMB_METHODS:
+            raise ValueError(f"coulomb must be one of {COULOMB_METHODS}, not {coulomb!r}")
+        self.coulomb = coulomb
         self.omega, self.mass, self.verbose = omega, mass, verbose
         self.radius_length, self.num_grid_points = radius_length, num_grid_points
         self.radius = numpy.linspace(0, radius_length, num_grid_points)
@@ -249,7 +303,7 @@ class TwoDimensionalHarmonicOscillator(BasisSet):
         np = self.np
         self._h = convert(self.omega * get_one_body_elements(self.l), np)
         self._s = convert(numpy.eye(self.l), np)
-        self._u = convert(numpy.sqrt(self.omega) * get_coulomb_elements(self.l), np)
+        self._u = convert(numpy.sqrt(self.omega) * get_coulomb_elements(self.l, method=self.coulomb), np)
         self.setup_spf()
         self.construct_position_integrals()
 
@@ -316,7 +370,7 @@ class TwoDimHarmonicOscB(TwoDimensionalHarmonicOscillator):
             numpy.arange(l), numpy.arange(-l - 5, l + 6), omega_c=self.omega_c, omega=self.omega)
         self._h = convert(numpy.diag(self.level_energy[:l]), np)
         self._s = convert(numpy.eye(l), np)
-        self._u = convert(numpy.sqrt(self.omega) * get_coulomb_elements(l, nm=self.level_nm[:l]), np)
+        self._u = convert(numpy.sqrt(self.omega) * get_coulomb_elements(l, nm=self.level_nm[:l], method=self.coulomb), np)
         self.setup_spf()
         self.construct_position_integrals()
         self.cast_to_complex()
