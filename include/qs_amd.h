@@ -1211,7 +1211,10 @@ int qs_string_ci_ladder(int h_dtype, int c_dtype, const void* phi, int64_t d, in
  *   pivots   : capacity int64, device: the flat index (q*, s*) of every step
  *   extremes : HOST pointer, 2 doubles out: the largest and the smallest residual
  *              diagonal at exit (largest <= tau: converged; smallest < 0 beyond
- *              rounding: G is not positive semidefinite)
+ *              rounding: G is not positive semidefinite).  A NaN anywhere on
+ *              the residual diagonal ends the run at the next pivot: *rank is
+ *              the number of steps completed and extremes[0] is NaN -- a
+ *              caller must not read "not > tau" as converged
  *   work     : qs_cholesky_two_body_workspace bytes, device, 16-byte aligned
  * Two plain launches per step, in stream order (no grid-wide barrier, no spin
  * wait): the pivot, the rank and a stop flag stay in device memory and every

@@ -22,6 +22,8 @@ Hermiticity of ``G`` -- ``u[p,q,r,s] == conj(u[r,s,p,q])`` -- is the caller's co
 decomposition reads one triangle's worth of columns and would silently decompose the Hermitian matrix they imply.
 """
 
+import math
+
 import torch
 
 from . import kernels
@@ -53,7 +55,9 @@ def decompose(u_or_system, tol, max_rank=None):
 
     Raises ``ValueError`` for a system whose ``u`` is anti-symmetrised, and where the smallest residual diagonal is
     below ``-tol``: the matrix is not positive semidefinite (an anti-symmetrised tensor, the negative of an
-    interaction, or an otherwise indefinite one).  Hermiticity of ``G[(r,p),(q,s)] = u[p,q,r,s]`` is the caller's
+    interaction, or an otherwise indefinite one), and where a residual extreme is not finite: a NaN on the residual
+    diagonal ends the kernel's run with a NaN as its largest element, which is an error here, never "converged".
+    Hermiticity of ``G[(r,p),(q,s)] = u[p,q,r,s]`` is the caller's
     contract and is not checked."""
     u = u_or_system
     if hasattr(u_or_system, "_basis_set"):
@@ -77,6 +81,10 @@ def decompose(u_or_system, tol, max_rank=None):
         while True:
             L, _, (dmax, dmin), state = kernels.cholesky_two_body(u, tol, max_rank=cap, state=state)
             converged = dmax <= tol
+            if not (math.isfinite(dmax) and math.isfinite(dmin)):
+                raise ValueError(
+                    f"non-finite residual diagonal after {state.rank} vectors (largest {dmax}, smallest {dmin}): u holds a "
+                    "NaN or an infinity, or the run produced one")
             if converged or state.rank < cap or cap >= limit:
                 break
             cap = min(2 * cap, limit)

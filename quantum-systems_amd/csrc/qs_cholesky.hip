@@ -4,7 +4,7 @@
 // positive interaction, G = V V^H and the stored vectors L_x = conj(V_x) (m x m, row x of a (capacity, n) buffer) give
 //   u[p,q,r,s] = sum_x conj(L_x[r,p]) L_x[q,s].
 // Left-looking: step j takes the pivot piv = (q*, s*) = argmax of the residual diagonal d (lowest flat index on ties),
-// stops when d[piv] <= tau, and otherwise forms, for every i = (r, p),
+// stops when d[piv] <= tau or when any d[i] is a NaN (dmax is then that NaN), and otherwise forms, for every i = (r, p),
 //   L_j[i] = (u[s*, r, q*, p] - sum_{x<j} L_x[i] conj(L_x[piv])) / sqrt(d[piv]),    d[i] -= |L_j[i]|^2,   d[piv] = 0.
 // u[s*, r, q*, p] is the conjugated pivot column (G is Hermitian): contiguous in p, no stride-m^3 gather.
 //
@@ -58,9 +58,10 @@ struct CholArgs {
     double tau;
 };
 
-// larger value wins, the lower index on equal values; a NaN never wins
+// larger value wins, the lower index on equal values; a NaN beats every number, offered (v2 != v2) or held (no
+// comparison with a held NaN is true), so one NaN among the candidates is the maximum of every reduction it enters
 __device__ inline void take_max(double& v, int64_t& i, double v2, int64_t i2) {
-    if (v2 > v || (v2 == v && i2 < i)) { v = v2; i = i2; }
+    if (v2 != v2 || v2 > v || (v2 == v && i2 < i)) { v = v2; i = i2; }
 }
 
 // (max, argmax, min) of the workgroup's 256 candidates, valid in thread 0
@@ -119,7 +120,7 @@ __global__ __launch_bounds__(256) void cholesky_pivot_kernel(const CholArgs g, c
     CholState* s = g.state;
     s->dmax = v;
     s->dmin = lo;
-    if (j >= g.capacity || !(v > g.tau)) {      // (a NaN diagonal stops too)
+    if (j >= g.capacity || !(v > g.tau)) {      // a NaN anywhere on the diagonal arrives here as v (take_max): it stops too
         s->stop = 1;
         s->rank = j;
         return;

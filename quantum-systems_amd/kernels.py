@@ -1666,7 +1666,8 @@ def cholesky_two_body(u, tol, max_rank=None, state=None):
     the vectors to a larger buffer first.  The bits do not depend on where a run was interrupted.
 
     Returns ``(L, pivots, (dmax, dmin), state)``: views ``(rank, m, m)`` and ``(rank,)`` of the state's buffers, the
-    largest and the smallest residual diagonal at exit, and the state.  The call blocks (one read-back of the device's
+    largest and the smallest residual diagonal at exit, and the state.  A NaN on the residual diagonal ends the run at
+    the next pivot with ``dmax`` NaN (``cholesky.decompose`` raises on it).  The call blocks (one read-back of the device's
     stop flag per ``qs_cholesky_two_body_block()`` steps)."""
     lib = _lib.load()
     if not isinstance(u, torch.Tensor):

@@ -89,3 +89,53 @@ def test_truncated_run_is_bounded_by_its_largest_residual_diagonal():
     assert d.max() <= tau
     assert np.abs(R).max() <= d.max() + 64 * EPS * scale
     assert np.abs(np.real(np.diagonal(ref.gram(R))) - d).max() <= 64 * EPS * scale
+
+
+@pytest.mark.parametrize("m, r, cplx", [(6, 9, False), (5, 7, True), (9, 78, False)])
+def test_replay_on_the_pivots_of_the_reference_is_the_reference(m, r, cplx):
+    u = ref.seeded_low_rank(m, r, cplx, seed=100 * m + r)
+    L, piv, d = ref.pivoted_cholesky(u, 1e-10 * np.abs(u).max())
+    assert L.shape[0] == r
+    Lr, D, gap = ref.replay(u, piv, u.dtype)
+    assert Lr.dtype == L.dtype and np.array_equal(Lr, L)
+    assert D.shape == (r + 1, m * m) and np.array_equal(D[r], d) and np.array_equal(D[0], np.real(np.diagonal(ref.gram(u))))
+    assert gap.shape == (r,) and not gap.any()
+    # a pivot that is NOT the maximum shows in the gap: the first two pivots swapped
+    swapped = piv.copy()
+    swapped[[0, 1]] = swapped[[1, 0]]
+    assert ref.replay(u, swapped, u.dtype)[2][0] > 0
+    # extended precision: 64 bits of significand, and the same decomposition to the rounding of the fp64 run
+    ref.require_extended_precision()
+    Lq, Dq, gapq = ref.replay(u, piv, np.clongdouble if cplx else np.longdouble)
+    assert Lq.dtype == (np.clongdouble if cplx else np.longdouble) and Dq.dtype == np.longdouble
+    assert 0 < np.abs(Lq - L).max() <= 1e-9 * np.abs(L).max()
+
+
+@pytest.mark.parametrize("cplx", [False, True])
+def test_exact_blocks_decompose_to_the_derived_integers(cplx):
+    m = 33
+    n = m * m
+    u, piv, L = ref.exact_blocks(m, cplx, seed=7)
+    assert u.dtype == (np.complex128 if cplx else np.float64) and L.dtype == u.dtype
+    assert sorted(piv.tolist()) == list(range(n))
+    G = ref.gram(u)
+    assert np.array_equal(G, G.conj().T) and np.array_equal(G, np.rint(G.real) + 1j * np.rint(G.imag) if cplx else np.rint(G))
+    V = np.conj(L).reshape(n, n)
+    assert np.array_equal(V.T @ np.conj(V), G)                  # integers: the product is exact
+    Lr, pr, d = ref.pivoted_cholesky(u, 0.5)
+    assert Lr.shape[0] == n and np.array_equal(pr, piv) and np.array_equal(Lr, L) and not d.any()
+    if cplx:
+        assert np.abs(L.imag).max() == 2                        # z = +-i is drawn
+    # the tie rule is asked across the order of a pair: pairs with i2 < i1 exist, and so do pairs with i1 < i2
+    half = n // 2
+    below = np.argmax(np.abs(V[:half]) == 2, axis=1) < piv[:half]
+    assert below.any() and not below.all()
+    # the second coefficient chunk of the kernel (512 coefficients at a time): a step j >= 513 whose ONLY non-zero
+    # coefficient conj(L_x[piv_j]) sits at an x >= 512, in each of the four summation chains x & 3
+    chains = set()
+    for j in range(513, n):
+        (x,) = np.nonzero(V[:j, piv[j]])
+        if len(x) == 1 and x[0] >= 512:
+            chains.add(int(x[0]) & 3)
+    print(f"exact_blocks(33, {cplx}): chains {sorted(chains)}")
+    assert chains == {0, 1, 2, 3}

@@ -9,6 +9,8 @@ summation order and its fused multiply-adds, it does not come from the code unde
 
 Pivots and vectors are NOT compared with the CPU: the diagonal has exact ties, ``d[(r,p)] = d[(p,r)]``, which rounding
 may break differently there.  Invariants only: rank, reconstruction, residual extremes, bits between runs.
+(tests/test_gpu_cholesky_scale.py compares them: with a replay of the GPU's own pivots in extended precision, and
+exactly on integer input; it also holds the ranks past 512 and the non-finite input.)
 
 Every test prints its measured figures (``pytest -s``)."""
 
