@@ -1,7 +1,8 @@
 // What the streamed contractions share (qs_mean_field.hip, qs_mean_field_batch.hip, qs_pair_contract.hip,
 // qs_pair_contract_antisym.hip, qs_pair_contract_exchange.hip, qs_lead_contract.hip, qs_det_ci.hip): the dtype pair -> form rule and the widths a form implies, the group size and
 // the dispatch of a run-time form / group size to a kernel instantiation, the loop over the groups of a batch, and the
-// tile arithmetic and the closing launch of the two mean-field kernels.
+// tile arithmetic and the closing launch of the two mean-field kernels.  What only the three pair contractions share
+// (the closing butterfly, the chunk loop, the launch, the packed-triangle walk and its C entry) is in qs_pair_walk.h.
 #pragma once
 
 #include <type_traits>

@@ -15,7 +15,8 @@
 // one product needs are adjacent (records padded to an odd number of 16-byte units, so that a wave's 128-bit reads
 // spread over the banks); two buffers, chunk c + 1 is staged while chunk c is consumed.
 // After the last step a wave closes its kPcRows * G row sums once with ONE xor butterfly over masks 32, 16, ... 1 in
-// which every stage also halves the number of values a lane carries (the lane pair splits them), so that each lane ends
+// which every stage also halves the number of values a lane carries (the lane pair splits them: pair_close of
+// qs_pair_walk.h, shared with the two triangle kernels like the launch), so that each lane ends
 // with one finished sum and stores it: plain vector stores, no floating-point atomics, no workspace, no closing launch.
 //
 // Reproducible: every product is an explicit fma in a fixed order, a row's items are dealt to the lanes by Y alone, and
@@ -23,7 +24,7 @@
 // nothing at all -- so row x has the same bits whatever X, ldu, K, the position of k in the batch or the instantiation
 // its group runs on (a partial last group takes the smallest instantiation that holds it).
 
-#include "qs_contract_common.h"
+#include "qs_pair_walk.h"
 
 namespace qs {
 
@@ -58,34 +59,6 @@ static constexpr int pc_steps(int form, int G) {
 
 static constexpr size_t pc_lds_bytes(int form, int G) {
     return (size_t)2 * pc_steps(form, G) * 64 * pc_record_units(form, G) * 16;
-}
-
-// Sum of v[j] over the 64 lanes for every j, N a power of two <= 64: butterfly stages 32 ... 1; while a lane carries
-// more than one value a stage hands half of them to the partner lane.  Returns the index j of the finished sum left in
-// v[0] (lanes that agree in the bits of the halving stages hold the same one).
-template <int CNT, int M, int N>
-__device__ __forceinline__ int pc_close_stage(double (&v)[N], int lane) {
-    if constexpr (M == 0) {
-        return 0;
-    } else if constexpr (CNT > 1) {
-        constexpr int half = CNT / 2;
-        const bool up = (lane & M) != 0;
-#pragma unroll
-        for (int j = 0; j < half; ++j) {
-            const double keep = up ? v[j + half] : v[j];
-            const double send = up ? v[j] : v[j + half];
-            v[j] = keep + __shfl_xor(send, M);
-        }
-        return (up ? half : 0) + pc_close_stage<half, M / 2, N>(v, lane);
-    } else {
-        v[0] += __shfl_xor(v[0], M);
-        return pc_close_stage<1, M / 2, N>(v, lane);
-    }
-}
-
-template <int N>
-__device__ __forceinline__ int pc_close(double (&v)[N], int lane) {
-    return pc_close_stage<N, 32, N>(v, lane);
 }
 
 // FORM 0: U, T, S real; 1: all complex128; 2: real U, complex T and S.  G: vectors per load of U.
@@ -153,6 +126,8 @@ __global__ __launch_bounds__(256) void pair_contract_kernel(const PcArgs g) {
     stage(0);
     __syncthreads();
 
+    // the chunk loop of pair_chunk_walk (qs_pair_walk.h), kept in place: through the template this kernel's shipped
+    // instantiations ran 1-5 % slower on the same registers (profiles/pair_walk_ab.txt)
     for (int c = 0; c < nchunks; ++c) {
         if (c + 1 < nchunks) stage(c + 1);
         const double* buf = pc_lds + (c & 1) * CW;
@@ -195,18 +170,20 @@ __global__ __launch_bounds__(256) void pair_contract_kernel(const PcArgs g) {
     }
 
     // close the wave's row sums; the lane that holds value (i, q, w) stores it
-    const int idx = pc_close<NV>(acc, lane);
+    const int idx = pair_close<NV>(acc, lane);
     const int w = idx % AW, q = (idx / AW) % G, i = idx / (AW * G);
     const bool first = NV >= 64 || (lane & (64 / NV - 1)) == 0;       // the lanes below a halving-stage bit hold copies
     if (first && q < g.ng && row0 + i < X) g.S[((int64_t)q * X + row0 + i) * AW + w] = acc[0];
 }
 
 // One group of g.ng vectors on the smallest instantiation that holds it.
-static void pc_launch(int form, const PcArgs& g, unsigned grid, hipStream_t s) {
-    with_form(form, [&](auto F) {
-        with_group(g.ng, [&](auto G) {
-            hipLaunchKernelGGL((pair_contract_kernel<F, G>), dim3(grid), dim3(256), pc_lds_bytes(F, G), s, g);
-            note_dispatch("qs::pair_contract_kernel<%d, %d>", (int)F, (int)G);
+static int pc_launch(int form, const PcArgs& g, unsigned grid, hipStream_t s) {
+    return with_form(form, [&](auto F) {
+        return with_group(g.ng, [&](auto G) {
+            static PerDeviceLds once;
+            return pair_launch(pair_contract_kernel<F, G>, g, pc_lds_bytes(F, G), once, grid, s,
+                               "hipFuncSetAttribute(pair_contract)", "pair contract launch",
+                               "qs::pair_contract_kernel<%d, %d>", (int)F, (int)G);
         });
     });
 }
@@ -256,8 +233,7 @@ int qs_pair_contract(int u_dtype, int t_dtype, const void* U, const void* T, voi
         g.ng = ng;
         g.T = (const double*)T + k0 * Y * aw;
         g.S = (double*)S + k0 * X * aw;
-        pc_launch(form, g, grid, s);
-        return launch_status("pair contract launch");
+        return pc_launch(form, g, grid, s);
     });
 }
 

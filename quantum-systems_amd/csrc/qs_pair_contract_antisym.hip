@@ -11,14 +11,15 @@
 // carries a term of the sum.  A workgroup of 256 threads takes 16 consecutive pair rows (p < q, row-major), wave w the
 // kPaRows rows from row 4 w of them; the 64 lanes of a wave cover 64 consecutive packed positions of ONE row per load and
 // walk along t in steps of 64, the next step's elements issued before the current step's fmas.  A lane carries its
-// (r, s) along: a step adds 64 to s and wraps into the following runs, so only the first position of a lane needs the
-// inverse of the triangle map (a square root and a correction).  The T values of a chunk of kPaSteps steps are staged in LDS
-// already packed in the order of the walk, as [position][g] (records padded to an odd number of 16-byte units), two
-// buffers, chunk c + 1 staged while chunk c is consumed: the staging threads are the only other users of the map.
+// (r, s) along (PairCursor<false> of qs_pair_walk.h), so only the first position of a lane needs the inverse of the
+// triangle map (pair_unpack<false>: qs_triangle.h's map of l - 1).  The T values of a chunk of kPaSteps steps are staged
+// in LDS already packed in the order of the walk, as [position][g] (records padded to an odd number of 16-byte units), two
+// buffers, chunk c + 1 staged while chunk c is consumed (pair_chunk_walk): the staging threads and the wave's (p, q) are
+// the only other users of the map.
 // A lane past the end of the triangle, and a wave row past the last pair, re-reads an element of the quarter (position
 // 0 / the last pair row) and drops it by a select.
 // After the last step a wave closes its kPaRows * G row sums with one xor butterfly over masks 32 ... 1 in which every
-// stage also halves the values a lane carries (the reduce-scatter of qs_pair_contract.hip); the lane left with the sum
+// stage also halves the values a lane carries (pair_close); the lane left with the sum
 // of (row, g) doubles it -- exact -- and stores it at (p, q), its negation at (q, p) and the zeros of the diagonal that
 // its row owns: plain vector stores, no atomics, no workspace, no closing launch.
 //
@@ -26,38 +27,14 @@
 // and every sum goes through the same butterfly stages whatever G.  So S[k] has the same bits alone, anywhere in a batch
 // and under any group size; a non-finite value stays in its row of U or its T[k].
 
-#include "qs_contract_common.h"
+#include "qs_pair_walk.h"
 
 namespace qs {
 
 constexpr int kPaRows = 4;             // pair rows per wave; a workgroup takes 4 * kPaRows of them
 constexpr int kPaSteps = 3;            // steps of 64 positions per staged chunk of T
-constexpr int64_t kPaMaxL = 4096;      // l^2 <= 2^24 elements: every byte offset inside a row stays below 2^32
 // Shipped group size per form {fp64, complex128}: the largest that keeps two workgroups per CU in VGPRs and in LDS
 constexpr int kPaGroup[2] = {8, 8};
-
-struct PaArgs {
-    const double* U;
-    const double* T;          // first amplitude of the group, [ng][l][l]
-    double* S;                // first result of the group, [ng][l][l]
-    int64_t ldu;
-    int l, ng;                // ng: amplitudes of this launch, 1 ... G of the instantiation
-};
-
-// First packed position of run r: the elements (r, r + 1 ... l - 1) follow those of the runs before it
-__host__ __device__ inline int pa_run_start(int r, int l) { return (int)(((int64_t)r * (2 * l - r - 1)) / 2); }
-
-// (r, s) of packed position t < l (l - 1) / 2: the root of the quadratic, then a correction of its rounding
-__host__ __device__ inline void pa_unpack(int t, int l, int& r, int& s) {
-    const double b = 2.0 * l - 1.0;
-    int rr = (int)((b - sqrt(b * b - 8.0 * t)) * 0.5);
-    if (rr < 0) rr = 0;
-    if (rr > l - 2) rr = l - 2;
-    while (rr > 0 && pa_run_start(rr, l) > t) --rr;
-    while (rr < l - 2 && pa_run_start(rr + 1, l) <= t) ++rr;
-    r = rr;
-    s = rr + 1 + (t - pa_run_start(rr, l));
-}
 
 // doubles of one position's record in LDS: G * AW, padded to an odd number of 16-byte units
 static constexpr int pa_record_words(int form, int G) { return (((G * form_widths(form).aw) / 2) | 1) * 2; }
@@ -66,32 +43,9 @@ static constexpr size_t pa_lds_bytes(int form, int G) {
     return (size_t)2 * kPaSteps * 64 * pa_record_words(form, G) * 8;
 }
 
-// Sum of v[j] over the 64 lanes for every j, N a power of two <= 64 (as pc_close of qs_pair_contract.hip): butterfly
-// stages 32 ... 1; while a lane carries more than one value a stage hands half of them to the partner lane.  Returns the
-// index j of the finished sum left in v[0].
-template <int CNT, int M, int N>
-__device__ __forceinline__ int pa_close_stage(double (&v)[N], int lane) {
-    if constexpr (M == 0) {
-        return 0;
-    } else if constexpr (CNT > 1) {
-        constexpr int half = CNT / 2;
-        const bool up = (lane & M) != 0;
-#pragma unroll
-        for (int j = 0; j < half; ++j) {
-            const double keep = up ? v[j + half] : v[j];
-            const double send = up ? v[j] : v[j + half];
-            v[j] = keep + __shfl_xor(send, M);
-        }
-        return (up ? half : 0) + pa_close_stage<half, M / 2, N>(v, lane);
-    } else {
-        v[0] += __shfl_xor(v[0], M);
-        return pa_close_stage<1, M / 2, N>(v, lane);
-    }
-}
-
 // FORM 0: U, T, S real; 1: all complex128.  G: amplitudes per load of U.
 template <int FORM, int G>
-__global__ __launch_bounds__(256) void pair_contract_antisym_kernel(const PaArgs g) {
+__global__ __launch_bounds__(256) void pair_contract_antisym_kernel(const PairTriArgs g) {
     constexpr int W = FORM == 1 ? 2 : 1;                   // doubles per element of U, T and S
     constexpr int TA = kPaRows;
     constexpr int RW = pa_record_words(FORM, G);
@@ -99,12 +53,12 @@ __global__ __launch_bounds__(256) void pair_contract_antisym_kernel(const PaArgs
     constexpr int CW = NS * 64 * RW;                       // doubles of one buffer
     constexpr int NV = TA * G * W;
     typedef typename std::conditional<FORM == 1, f64x2, double>::type elem_t;
+    typedef PairCursor<false> Cursor;
     extern __shared__ __attribute__((aligned(16))) double pa_lds[];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l = g.l;
-    const int n = l * (l - 1) / 2;                          // packed positions of a row = pair rows of U
-    const int nsteps = (n + 63) >> 6, nchunks = (nsteps + NS - 1) / NS;
+    const int n = pair_count<false>(l);                     // packed positions of a row = pair rows of U
     const int row0 = __builtin_amdgcn_readfirstlane((blockIdx.x * 4 + wave) * TA);
 
     // the wave's rows: (p, q) of pair row0 + i, or the last pair for a row past the end (loaded, never stored)
@@ -114,7 +68,7 @@ __global__ __launch_bounds__(256) void pair_contract_antisym_kernel(const PaArgs
     for (int i = 0; i < TA; ++i) {
         const int row = row0 + i < n ? row0 + i : n - 1;
         int p, q;
-        pa_unpack(row, l, p, q);
+        pair_unpack<false>(row, l, p, q);
         rp[i] = __builtin_amdgcn_readfirstlane(p);
         rq[i] = __builtin_amdgcn_readfirstlane(q);
         urow[i] = reinterpret_cast<const elem_t*>(g.U) + ((int64_t)rp[i] * l + rq[i]) * g.ldu;
@@ -124,11 +78,9 @@ __global__ __launch_bounds__(256) void pair_contract_antisym_kernel(const PaArgs
     auto stage = [&](int c) {
         double* buf = pa_lds + (c & 1) * CW;
         for (int idx = tid; idx < NS * 64; idx += 256) {
-            const int t = c * (NS * 64) + idx;
-            const bool ok = t < n;
-            int r, s;
-            pa_unpack(ok ? t : 0, l, r, s);
-            const double* src = g.T + (int64_t)(r * l + s) * W;
+            const Cursor at(c * (NS * 64) + idx, l);
+            const bool ok = at.term();
+            const double* src = g.T + (int64_t)at.offset() * W;
             double* dst = buf + idx * RW;
 #pragma unroll
             for (int gg = 0; gg < G; ++gg) {
@@ -147,22 +99,10 @@ __global__ __launch_bounds__(256) void pair_contract_antisym_kernel(const PaArgs
 #pragma unroll
     for (int j = 0; j < NV; ++j) acc[j] = 0.0;
 
-    // the lane's position: t = 64 st + lane <-> (r, s); off = r l + s, position 0 (element (0, 1)) once t is past n
-    int t = lane, r = 0, s = 1;
-    if (t < n) pa_unpack(t, l, r, s);
-    auto offset = [&]() { return t < n ? (unsigned)(r * l + s) : 1u; };
-    auto advance = [&]() {
-        t += 64;
-        if (t < n) {
-            s += 64;
-            while (s >= l) {
-                s += r + 2 - l;
-                ++r;
-            }
-        }
-    };
+    // the lane's position t = 64 st + lane of the step that is fetched next
+    Cursor pos(lane, l);
     auto fetch = [&](elem_t (&dst)[TA]) {
-        const unsigned off = offset();
+        const unsigned off = pos.offset();
 #pragma unroll
         for (int i = 0; i < TA; ++i) dst[i] = urow[i][off];
     };
@@ -171,19 +111,13 @@ __global__ __launch_bounds__(256) void pair_contract_antisym_kernel(const PaArgs
     fetch(cur);
 #pragma unroll
     for (int i = 0; i < TA; ++i) nxt[i] = cur[i];
-    stage(0);
-    __syncthreads();
+    bool mine = pos.term();                                 // the position in `cur` is a term of the sum
+    pos.advance();
 
-    for (int c = 0; c < nchunks; ++c) {
-        if (c + 1 < nchunks) stage(c + 1);
-        const double* buf = pa_lds + (c & 1) * CW;
-        const int s_hi = nsteps - c * NS < NS ? nsteps - c * NS : NS;
-        for (int ss = 0; ss < s_hi; ++ss) {
-            const int st = c * NS + ss;
-            const bool mine = t < n;                        // this step's position is a term of the sum
-            advance();
-            if (st + 1 < nsteps) fetch(nxt);
-            const double* rec = buf + (ss * 64 + lane) * RW;
+    pair_chunk_walk<NS>(
+        (n + 63) >> 6, stage, [&](int) { fetch(nxt); },
+        [&](int b, int ss, int) {
+            const double* rec = pa_lds + b * CW + (ss * 64 + lane) * RW;
             double tv[G * W];
 #pragma unroll
             for (int j = 0; j < G * W; ++j) tv[j] = rec[j];
@@ -206,12 +140,12 @@ __global__ __launch_bounds__(256) void pair_contract_antisym_kernel(const PaArgs
             }
 #pragma unroll
             for (int i = 0; i < TA; ++i) cur[i] = nxt[i];
-        }
-        __syncthreads();
-    }
+            mine = pos.term();
+            pos.advance();
+        });
 
     // close the wave's sums; the lane that holds value (i, q, w) doubles it and stores it, its mirror and its zeros
-    const int idx = pa_close_stage<NV, 32, NV>(acc, lane);
+    const int idx = pair_close<NV>(acc, lane);
     const int w = idx % W, q = (idx / W) % G, i = idx / (W * G);
     const bool first = NV >= 64 || (lane & (64 / NV - 1)) == 0;       // the lanes below a halving-stage bit hold copies
     if (first && q < g.ng && row0 + i < n) {
@@ -229,23 +163,17 @@ __global__ __launch_bounds__(256) void pair_contract_antisym_kernel(const PaArgs
 }
 
 // One group of g.ng amplitudes on the smallest instantiation that holds it.
-static void pa_launch(int form, const PaArgs& g, unsigned grid, hipStream_t s) {
-    with_width(form + 1, [&](auto WW) {
+static int pa_launch(int form, const PairTriArgs& g, unsigned grid, hipStream_t s) {
+    return with_width(form + 1, [&](auto WW) {
         constexpr int F = decltype(WW)::value - 1;
-        with_group(g.ng, [&](auto G) {
-            hipLaunchKernelGGL((pair_contract_antisym_kernel<F, G>), dim3(grid), dim3(256), pa_lds_bytes(F, G), s, g);
-            note_dispatch("qs::pair_contract_antisym_kernel<%d, %d>", F, (int)G);
+        return with_group(g.ng, [&](auto G) {
+            static PerDeviceLds once;
+            return pair_launch(pair_contract_antisym_kernel<F, G>, g, pa_lds_bytes(F, G), once, grid, s,
+                               "hipFuncSetAttribute(pair_contract_antisym)", "pair contract antisym launch",
+                               "qs::pair_contract_antisym_kernel<%d, %d>", F, (int)G);
         });
     });
 }
-
-// The two forms: both operands fp64, or both complex128 (a real U against complex T is two fp64 columns per amplitude)
-static inline int pa_form(int u_dtype, int t_dtype) {
-    if (!dtype_ok(u_dtype) || !dtype_ok(t_dtype) || u_dtype != t_dtype) return QS_ERR_BAD_DTYPE;
-    return u_dtype == QS_C128 ? 1 : 0;
-}
-
-static inline bool pa_extents_ok(int64_t l, int64_t K) { return l >= 2 && l <= kPaMaxL && K >= 1 && K <= 65536; }
 
 }  // namespace qs
 
@@ -254,40 +182,13 @@ using namespace qs;
 extern "C" {
 
 int64_t qs_pair_contract_antisym_workspace(int u_dtype, int t_dtype, int64_t l, int64_t K) {
-    const int form = pa_form(u_dtype, t_dtype);
-    if (form < 0) return form;
-    if (!pa_extents_ok(l, K)) return QS_ERR_BAD_EXTENT;
-    return 0;          // the triangle of a row is never split: every sum is closed inside its wave
+    return pair_tri_workspace<false>(u_dtype, t_dtype, l, K);
 }
 
 int qs_pair_contract_antisym(int u_dtype, int t_dtype, const void* U, const void* T, void* S, int64_t l, int64_t K,
                              int64_t ldu, void* work, int64_t work_elems, void* stream) {
-    dispatch_reset();
     (void)work;
-    const int form = pa_form(u_dtype, t_dtype);
-    if (form < 0) return form;
-    if (!pa_extents_ok(l, K) || ldu < l * l || ldu > (int64_t(1) << 24)) return QS_ERR_BAD_EXTENT;
-    if (!U || !T || !S) return QS_ERR_NULL_POINTER;
-    const int64_t es = (int64_t)elem_size(t_dtype);
-    if (!aligned(U, (size_t)es) || !aligned(T, (size_t)es) || !aligned(S, (size_t)es)) return QS_ERR_MISALIGNED;
-    const int64_t s_bytes = K * l * l * es;
-    if (overlaps(S, s_bytes, U, ((l * l - 1) * ldu + l * l) * es) || overlaps(S, s_bytes, T, s_bytes)) return QS_ERR_ALIAS;
-    if (work_elems < qs_pair_contract_antisym_workspace(u_dtype, t_dtype, l, K)) return QS_ERR_WORKSPACE;
-
-    const int w = form + 1;
-    PaArgs g{};
-    g.U = (const double*)U;
-    g.l = (int)l;
-    g.ldu = ldu;
-    const unsigned grid = (unsigned)cdiv(l * (l - 1) / 2, 4 * kPaRows);
-    hipStream_t s = (hipStream_t)stream;
-    return for_each_group(K, group_size(g_tune.pair_contract_g, kPaGroup[form]), [&](int64_t k0, int ng) {
-        g.ng = ng;
-        g.T = (const double*)T + k0 * l * l * w;
-        g.S = (double*)S + k0 * l * l * w;
-        pa_launch(form, g, grid, s);
-        return launch_status("pair contract antisym launch");
-    });
+    return pair_tri_entry<false>(4 * kPaRows, kPaGroup, pa_launch, u_dtype, t_dtype, U, T, S, l, K, ldu, work_elems, stream);
 }
 
 }  // extern "C"

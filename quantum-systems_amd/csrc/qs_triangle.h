@@ -1,6 +1,8 @@
 // The upper triangle of an n x n grid as one flat list: pair t is the t-th (i, j >= i) in row-major order.  ONE remap for
 // host and device: the check kernel's pair decode (qs_permute.hip), the triangular batch of the products (qs_gemm.hip,
-// qs_gemm_fast.hip) and qs_triangle_pair (qs_api.hip) all go through triangle_row.
+// qs_gemm_fast.hip), the packed walks of the two triangle pair contractions (pair_unpack of qs_pair_walk.h: the strict
+// triangle r < s of l is this one of n = l - 1 with its second index shifted by one) and qs_triangle_pair (qs_api.hip)
+// all go through triangle_row.
 //
 // Everything is 32-bit: a grid of at most kTriangleMax rows has fewer than 2^31 pairs, and every product below stays under
 // 2^32.  Inside a product kernel the remap runs once per tile on a wave-uniform index, so it has to be light on

@@ -883,79 +883,17 @@ def pair_contract(u, T, out=None):
     return out
 
 
-@_plain
-def pair_contract_antisym(u, T, out=None):
-    """``S[k,p,q] = sum_rs u[p,q,r,s] T[k,r,s]`` (no conjugation) for an anti-symmetrised ``u`` (minus itself under
-    ``p <-> q`` and under ``r <-> s``) and amplitudes ``T[k] = -T[k]^T``, on the kernel of ``qs_pair_contract_antisym``:
-    only ``p < q``, ``r < s`` of ``u`` and ``r < s`` of ``T`` are read, a quarter of the bytes of ``pair_contract``;
-    ``S[k,p,q] = 2 sum_{r<s}``, ``S[k,q,p]`` its negation, a zero diagonal.  The symmetries are the caller's word and
-    are not checked.  ``u`` is (l, l, l, l), contiguous or rows (p, q) at one uniform
-    distance, read in place; ``T`` is (K, l, l) or (l, l).  A real ``u`` with a complex ``T`` runs the fp64
-    kernel on the real and the imaginary parts as 2 K amplitudes: exact, and one read of ``u`` per group as well.
-    Returns (K, l, l), or (l, l) for a 2-D ``T``."""
+def _pair_contract_triangle(name, min_l, u, T, out):
+    """The two pair contractions on a packed triangle of ``u`` (``name``: the C entry, ``min_l``: its smallest l): ``u``
+    (l, l, l, l) read in place where its rows (p, q) lie at one uniform distance, ``T`` (K, l, l) or (l, l); a real
+    ``u`` with a complex ``T`` as 2 K fp64 columns."""
     lib = _lib.load()
     dt = result_dtype(u, T)
     udt = _F64 if isinstance(u, torch.Tensor) and u.dtype == _F64 else dt
     if not isinstance(u, torch.Tensor):
         raise TypeError("expected a torch.Tensor")
-    if u.dim() != 4 or len(set(u.shape)) != 1 or u.shape[0] < 2 or not isinstance(T, torch.Tensor) or T.dim() not in (2, 3):
-        raise ValueError("u must be (l, l, l, l) with l >= 2 and T (K, l, l) or (l, l)")
-    l = u.shape[0]
-    ldu = u.stride(1)
-    if not (u.is_cuda and u.dtype == udt and not u.is_conj() and u.stride(3) == 1 and u.stride(2) == l and
-            ldu >= l * l and u.stride(0) == l * ldu):
-        u = _dev(u, udt)
-        ldu = l * l
-    T = _dev(T, dt)
-    single = T.dim() == 2
-    if single:
-        T = T[None]
-    K = T.shape[0]
-    if tuple(T.shape[1:]) != (l, l) or K < 1:
-        raise ValueError(f"u has shape {tuple(u.shape)}, T {tuple(T.shape)}: need u (l, l, l, l) and T (K, l, l), K >= 1")
-    shape = (l, l) if single else (K, l, l)
-    if out is not None:
-        _check_out(out, shape, dt, "pair_contract_antisym")
-    split = udt != dt                      # real u, complex T: (re, im) of every amplitude as two fp64 columns
-    if split:
-        cols = torch.view_as_real(T).permute(0, 3, 1, 2).reshape(2 * K, l, l).contiguous()
-        res = torch.empty((2 * K, l, l), dtype=_F64, device=u.device)
-    else:
-        cols = T
-        res = out if out is not None else torch.empty(shape, dtype=dt, device=u.device)
-    code, ncols = dtype_code(udt), cols.shape[0]
-    nbytes = check(lib.qs_pair_contract_antisym_workspace(code, code, l, ncols), "workspace query")
-    with _on_device_of(u, cols, res):
-        _ran(
-            lib.qs_pair_contract_antisym(code, code, u.data_ptr(), cols.data_ptr(), res.data_ptr(), l, ncols, ldu,
-                                         *_work(nbytes, u.device), _stream()),
-            "qs_pair_contract_antisym",
-        )
-    if split:
-        S = torch.view_as_complex(res.view(K, 2, l, l).permute(0, 2, 3, 1).contiguous())
-        S = S[0] if single else S
-        if out is None:
-            return S
-        out.copy_(S)
-    return out if out is not None else res
-
-
-@_plain
-def pair_contract_exchange(u, T, out=None):
-    """``S[k,p,q] = sum_rs u[p,q,r,s] T[k,r,s]`` (no conjugation) for ALL p, q and ANY amplitudes, for a ``u`` with
-    particle-exchange symmetry ``u[p,q,r,s] = u[q,p,s,r]`` (spatial orbitals; ``two_body_exchange_symmetric``), on the
-    kernel of ``qs_pair_contract_exchange``: only ``r <= s`` of ``u`` is read, half of the bytes and of the products
-    of ``pair_contract``.  The symmetry is the caller's word and is not checked.  ``u`` is (l, l, l, l), contiguous or
-    rows (p, q) at one uniform distance, read in place (a permuted ``u`` is made contiguous); ``T`` is (K, l, l) or
-    (l, l).  A real ``u`` with a complex ``T`` runs the fp64 kernel on the real and the imaginary parts as 2 K
-    amplitudes: exact, and one read of ``u`` per group as well.  Returns (K, l, l), or (l, l) for a 2-D ``T``."""
-    lib = _lib.load()
-    dt = result_dtype(u, T)
-    udt = _F64 if isinstance(u, torch.Tensor) and u.dtype == _F64 else dt
-    if not isinstance(u, torch.Tensor):
-        raise TypeError("expected a torch.Tensor")
-    if u.dim() != 4 or len(set(u.shape)) != 1 or u.shape[0] < 1 or not isinstance(T, torch.Tensor) or T.dim() not in (2, 3):
-        raise ValueError("u must be (l, l, l, l) with l >= 1 and T (K, l, l) or (l, l)")
+    if u.dim() != 4 or len(set(u.shape)) != 1 or u.shape[0] < min_l or not isinstance(T, torch.Tensor) or T.dim() not in (2, 3):
+        raise ValueError(f"u must be (l, l, l, l) with l >= {min_l} and T (K, l, l) or (l, l)")
     l = u.shape[0]
     ldu = u.stride(1) if l > 1 else 1
     if not (u.is_cuda and u.dtype == udt and not u.is_conj() and (l == 1 or (
@@ -971,7 +909,7 @@ def pair_contract_exchange(u, T, out=None):
         raise ValueError(f"u has shape {tuple(u.shape)}, T {tuple(T.shape)}: need u (l, l, l, l) and T (K, l, l), K >= 1")
     shape = (l, l) if single else (K, l, l)
     if out is not None:
-        _check_out(out, shape, dt, "pair_contract_exchange")
+        _check_out(out, shape, dt, name[3:])
     split = udt != dt                      # real u, complex T: (re, im) of every amplitude as two fp64 columns
     if split:
         cols = torch.view_as_real(T).permute(0, 3, 1, 2).reshape(2 * K, l, l).contiguous()
@@ -980,13 +918,10 @@ def pair_contract_exchange(u, T, out=None):
         cols = T
         res = out if out is not None else torch.empty(shape, dtype=dt, device=u.device)
     code, ncols = dtype_code(udt), cols.shape[0]
-    nbytes = check(lib.qs_pair_contract_exchange_workspace(code, code, l, ncols), "workspace query")
+    nbytes = check(getattr(lib, name + "_workspace")(code, code, l, ncols), "workspace query")
     with _on_device_of(u, cols, res):
-        _ran(
-            lib.qs_pair_contract_exchange(code, code, u.data_ptr(), cols.data_ptr(), res.data_ptr(), l, ncols, ldu,
-                                          *_work(nbytes, u.device), _stream()),
-            "qs_pair_contract_exchange",
-        )
+        _ran(getattr(lib, name)(code, code, u.data_ptr(), cols.data_ptr(), res.data_ptr(), l, ncols, ldu,
+                                *_work(nbytes, u.device), _stream()), name)
     if split:
         parts = res.view(K, 2, l, l)
         S = torch.complex(parts[:, 0], parts[:, 1])
@@ -995,6 +930,31 @@ def pair_contract_exchange(u, T, out=None):
             return S
         out.copy_(S)
     return out if out is not None else res
+
+
+@_plain
+def pair_contract_antisym(u, T, out=None):
+    """``S[k,p,q] = sum_rs u[p,q,r,s] T[k,r,s]`` (no conjugation) for an anti-symmetrised ``u`` (minus itself under
+    ``p <-> q`` and under ``r <-> s``) and amplitudes ``T[k] = -T[k]^T``, on the kernel of ``qs_pair_contract_antisym``:
+    only ``p < q``, ``r < s`` of ``u`` and ``r < s`` of ``T`` are read, a quarter of the bytes of ``pair_contract``;
+    ``S[k,p,q] = 2 sum_{r<s}``, ``S[k,q,p]`` its negation, a zero diagonal.  The symmetries are the caller's word and
+    are not checked.  ``u`` is (l, l, l, l), contiguous or rows (p, q) at one uniform
+    distance, read in place; ``T`` is (K, l, l) or (l, l).  A real ``u`` with a complex ``T`` runs the fp64
+    kernel on the real and the imaginary parts as 2 K amplitudes: exact, and one read of ``u`` per group as well.
+    Returns (K, l, l), or (l, l) for a 2-D ``T``."""
+    return _pair_contract_triangle("qs_pair_contract_antisym", 2, u, T, out)
+
+
+@_plain
+def pair_contract_exchange(u, T, out=None):
+    """``S[k,p,q] = sum_rs u[p,q,r,s] T[k,r,s]`` (no conjugation) for ALL p, q and ANY amplitudes, for a ``u`` with
+    particle-exchange symmetry ``u[p,q,r,s] = u[q,p,s,r]`` (spatial orbitals; ``two_body_exchange_symmetric``), on the
+    kernel of ``qs_pair_contract_exchange``: only ``r <= s`` of ``u`` is read, half of the bytes and of the products
+    of ``pair_contract``.  The symmetry is the caller's word and is not checked.  ``u`` is (l, l, l, l), contiguous or
+    rows (p, q) at one uniform distance, read in place (a permuted ``u`` is made contiguous); ``T`` is (K, l, l) or
+    (l, l).  A real ``u`` with a complex ``T`` runs the fp64 kernel on the real and the imaginary parts as 2 K
+    amplitudes: exact, and one read of ``u`` per group as well.  Returns (K, l, l), or (l, l) for a 2-D ``T``."""
+    return _pair_contract_triangle("qs_pair_contract_exchange", 1, u, T, out)
 
 
 def _dets_checked(dets):

@@ -107,28 +107,45 @@ def triangle(l):
     return np.triu_indices(l, 1)
 
 
+def packed_rows(Urows, T, extended=False):
+    """``2 sum_{r<s} Urows[x,r,s] T[k,r,s]`` as (K, x): the sum of the pair rows ``Urows[x] = U[p_x, q_x]``, from their
+    elements r < s and those of ``T`` alone."""
+    r, s = triangle(T.shape[-1])
+    A, B = Urows[:, r, s], T[:, r, s]
+    if extended:
+        A, B = _wide(A), _wide(B)
+    return 2 * np.einsum("xt,kt->kx", A, B)
+
+
 def pair_contract_antisym(U, T, extended=False):
     """``S[k,p,q] = 2 sum_{r<s} U[p,q,r,s] T[k,r,s]`` for p < q, ``S[k,q,p] = -S[k,p,q]``, a zero diagonal -- from the
     elements p < q, r < s of ``U`` and r < s of ``T`` alone."""
-    if extended:
-        U, T = _wide(U), _wide(T)
-    l = U.shape[0]
-    r, s = triangle(l)
-    packed = 2 * np.einsum("xt,kt->kx", U[r, s][:, r, s], T[:, r, s])            # (K, pairs): rows (p < q), columns (r < s)
+    r, s = triangle(U.shape[0])
+    packed = packed_rows(U[r, s], T, extended)                                   # (K, pairs): rows (p < q), columns (r < s)
     S = np.zeros(T.shape, dtype=packed.dtype)
     S[:, r, s] = packed
     S[:, s, r] = -packed
     return S
 
 
-def pair_bound(U, T):
-    """Any-order bound on the device sum of n = l (l - 1) / 2 products and the (exact) doubling:
-    ``gamma_(n+2) * 2 sum_{r<s} |U||T|``, a further ``2 sqrt 2`` for complex products (as ``_two_particle_ref``)."""
-    l = U.shape[0]
+def rows_bound(Urows, T):
+    """Any-order bound on the device sum of n = l (l - 1) / 2 products and the (exact) doubling, for the pair rows of
+    ``packed_rows``: ``gamma_(n+2) * 2 sum_{r<s} |U||T|``, a further ``2 sqrt 2`` for complex products (as
+    ``_two_particle_ref``)."""
+    l = T.shape[-1]
     n = l * (l - 1) // 2
-    A = pair_contract_antisym(np.abs(U), np.abs(T))
-    A = np.abs(A)
-    return gamma(n + 2) * A * (2.0 * np.sqrt(2.0) if (np.iscomplexobj(U) or np.iscomplexobj(T)) else 1.0)
+    A = np.abs(packed_rows(np.abs(Urows), np.abs(T)))
+    return gamma(n + 2) * A * (2.0 * np.sqrt(2.0) if (np.iscomplexobj(Urows) or np.iscomplexobj(T)) else 1.0)
+
+
+def pair_bound(U, T):
+    """``rows_bound`` of every pair row p < q, at (p, q) and at (q, p); zero on the diagonal."""
+    r, s = triangle(U.shape[0])
+    b = rows_bound(U[r, s], T)
+    B = np.zeros(T.shape, dtype=b.dtype)
+    B[:, r, s] = b
+    B[:, s, r] = b
+    return B
 
 
 # -- seeded inputs

@@ -135,40 +135,51 @@ def triangle(l):
     return np.triu_indices(l)
 
 
-def _halves(U, T):
-    l = U.shape[0]
-    r, s = triangle(l)
-    a, b = U[r, s][:, r, s], U[s, r][:, r, s]                                # rows (p <= q) and their mirrors, columns (r <= s)
-    w = np.where(r == s, 0.5, 1.0)
-    return r, s, a, b, w
+def packed_rows(Arows, Brows, T, extended=False):
+    """``(S[k, p_x, q_x], S[k, q_x, p_x])`` as two (K, x), for the row pairs ``Arows[x] = U[p_x, q_x]`` and
+    ``Brows[x] = U[q_x, p_x]``, p <= q, from their elements r <= s alone:
+    ``S+- = sum_{r<=s} w (U[p,q,r,s] +- U[q,p,r,s]) (T[r,s] +- T[s,r])``."""
+    r, s = triangle(T.shape[-1])
+    a, b, t, tt = Arows[:, r, s], Brows[:, r, s], T[:, r, s], T[:, s, r]     # columns (r <= s)
+    if extended:
+        a, b, t, tt = _wide(a), _wide(b), _wide(t), _wide(tt)
+    Sp = np.einsum("xt,kt->kx", a + b, (t + tt) * np.where(r == s, 0.5, 1.0))
+    Sm = np.einsum("xt,kt->kx", a - b, t - tt)
+    return (Sp + Sm) / 2, (Sp - Sm) / 2
 
 
 def pair_contract_exchange(U, T, extended=False):
     """``S[k,p,q] = sum_rs U[p,q,r,s] T[k,r,s]`` for a ``U`` with ``U[p,q,r,s] = U[q,p,s,r]``, from the elements
-    r <= s of ``U`` alone: ``S+- = sum_{r<=s} w (U[p,q,r,s] +- U[q,p,r,s]) (T[r,s] +- T[s,r])``."""
-    if extended:
-        U, T = _wide(U), _wide(T)
-    r, s, a, b, w = _halves(U, T)
-    Sp = np.einsum("xt,kt->kx", a + b, (T[:, r, s] + T[:, s, r]) * w)
-    Sm = np.einsum("xt,kt->kx", a - b, T[:, r, s] - T[:, s, r])
-    S = np.zeros(T.shape, dtype=Sp.dtype)
-    S[:, s, r] = (Sp - Sm) / 2
-    S[:, r, s] = (Sp + Sm) / 2
+    r <= s of ``U`` alone (``packed_rows`` of every row pair p <= q)."""
+    r, s = triangle(U.shape[0])
+    upper, lower = packed_rows(U[r, s], U[s, r], T, extended)
+    S = np.zeros(T.shape, dtype=upper.dtype)
+    S[:, s, r] = lower
+    S[:, r, s] = upper
     return S
 
 
-def pair_bound(U, T):
+def rows_bound(Arows, Brows, T):
     """Any-order bound on the device sums of n = l (l + 1) / 2 products each, the two combinations before them, the one
-    after and the (exact) halving: ``gamma_(n+4) sum_{r<=s} w (|U[p,q,r,s]| + |U[q,p,r,s]|) (|T[r,s]| + |T[s,r]|)``, a
-    further ``2 sqrt 2`` for complex products."""
-    l = U.shape[0]
+    after and the (exact) halving, for the row pairs of ``packed_rows`` (the same at (p, q) and (q, p)):
+    ``gamma_(n+4) sum_{r<=s} w (|U[p,q,r,s]| + |U[q,p,r,s]|) (|T[r,s]| + |T[s,r]|)``, a further ``2 sqrt 2`` for complex
+    products."""
+    l = T.shape[-1]
     n = l * (l + 1) // 2
-    r, s, a, b, w = _halves(np.abs(U), np.abs(T))
-    A = np.einsum("xt,kt->kx", a + b, (np.abs(T)[:, r, s] + np.abs(T)[:, s, r]) * w)
+    r, s = triangle(l)
+    a, b, t = np.abs(Arows)[:, r, s], np.abs(Brows)[:, r, s], np.abs(T)
+    A = np.einsum("xt,kt->kx", a + b, (t[:, r, s] + t[:, s, r]) * np.where(r == s, 0.5, 1.0))
+    return gamma(n + 4) * A * (2.0 * np.sqrt(2.0) if (np.iscomplexobj(Arows) or np.iscomplexobj(T)) else 1.0)
+
+
+def pair_bound(U, T):
+    """``rows_bound`` of every row pair p <= q, at (p, q) and at (q, p)."""
+    r, s = triangle(U.shape[0])
+    b = rows_bound(U[r, s], U[s, r], T)
     B = np.zeros(T.shape, dtype=np.float64)
-    B[:, r, s] = A
-    B[:, s, r] = A
-    return gamma(n + 4) * B * (2.0 * np.sqrt(2.0) if (np.iscomplexobj(U) or np.iscomplexobj(T)) else 1.0)
+    B[:, r, s] = b
+    B[:, s, r] = b
+    return B
 
 
 # -- seeded inputs

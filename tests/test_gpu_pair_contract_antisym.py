@@ -138,6 +138,42 @@ def test_parity_quarter_read_mirror_and_batches(form, l):
         assert torch.equal(bits(kernels.pair_contract_antisym(padded(ud, ldu), Td[:G + 1])), b[:G + 1]), ldu
 
 
+@pytest.mark.parametrize("l", [66, 130])
+def test_parity_where_a_step_stays_inside_its_run(l):
+    """Up to l = 65 every step of 64 positions leaves its run, so the lane cursor always wraps.  l = 66: the first run is
+    65 long, its lane 0 steps from (0, 1) to (0, 65) without a wrap; l = 130: runs past 128, two such steps in a row.
+    fp64, K = 3, a contiguous u (152 MB | 2.3 GB, drawn on the device).  The parity assertion of
+    ``test_parity_quarter_read_mirror_and_batches`` on EVERY pair row p < q (only those rows come back to the host: the
+    long-double sums of all 8385 rows at l = 130 take a few seconds); the mirror and the diagonal are checked bit for bit
+    on every element."""
+    from quantum_systems_amd import kernels
+
+    K, n = 3, l * (l - 1) // 2
+    gen = torch.Generator(device="cuda").manual_seed(l)
+    w = torch.randn((l,) * 4, dtype=torch.float64, device="cuda", generator=gen)
+    w = w - w.transpose(0, 1)
+    ud = w - w.transpose(2, 3)
+    del w
+    T = antisym_T(np.random.default_rng(l), K, l, False)
+    S = kernels.pair_contract_antisym(ud, dev(T))
+    mine, other = launches(kernels.last_dispatch())
+    assert not other and mine == [(0, 4, 1)]
+
+    p, q = (torch.from_numpy(x).cuda() for x in cc.triangle(l))
+    urows = ud[p, q].cpu().numpy()
+    err = np.abs(S[:, p, q].cpu().numpy() - cc.packed_rows(urows, T, extended=True)).astype(np.float64)
+    bound = cc.rows_bound(urows, T)
+    print(f"fp64 l={l}: largest error / bound = {float((err[bound > 0] / bound[bound > 0]).max()):.3f} on {n} rows")
+    assert (err <= bound).all()
+
+    b = bits(S)
+    sign = torch.tensor(-2 ** 63, dtype=torch.int64, device="cuda")
+    r, s = torch.triu_indices(l, l, offset=1, device="cuda")
+    assert torch.equal(b[:, s, r], b[:, r, s] ^ sign)
+    d = torch.arange(l, device="cuda")
+    assert (b[:, d, d] == 0).all()
+
+
 @pytest.mark.parametrize("form", list(FORMS))
 def test_a_result_knows_neither_its_batch_nor_the_group_size(form):
     from quantum_systems_amd import kernels

@@ -123,6 +123,38 @@ def test_parity_half_read_and_batches(form, l):
         assert torch.equal(bits(kernels.pair_contract_exchange(padded(ud, ldu), Td[:G + 1])), b[:G + 1]), ldu
 
 
+@pytest.mark.parametrize("l", [66, 130])
+def test_parity_where_a_step_stays_inside_its_run(l):
+    """Up to l = 64 every step of 64 positions leaves its run, so the lane cursor always wraps.  l = 66: the first run is
+    66 long, its lanes 0 and 1 step without a wrap; l = 130: runs past 128, two such steps in a row.  fp64, K = 3, a
+    contiguous u (152 MB | 2.3 GB, drawn on the device).  The parity assertion of ``test_parity_half_read_and_batches``
+    on (p, q) and (q, p) of EVERY row pair p <= q, which is every element (the long-double sums of all 8515 row pairs
+    at l = 130 take a few seconds)."""
+    from quantum_systems_amd import kernels
+
+    K, n = 3, l * (l + 1) // 2
+    gen = torch.Generator(device="cuda").manual_seed(l)
+    w = torch.randn((l,) * 4, dtype=torch.float64, device="cuda", generator=gen)
+    ud = w + w.permute(1, 0, 3, 2)
+    del w
+    assert torch.equal(ud, ud.permute(1, 0, 3, 2))
+    T = rand(np.random.default_rng(l), (K, l, l), False)
+    S = kernels.pair_contract_exchange(ud, dev(T))
+    mine, other = launches(kernels.last_dispatch())
+    assert not other and mine == [(0, 4, 1)]
+
+    p, q = (torch.from_numpy(x).cuda() for x in rc.triangle(l))
+    arows, brows = ud[p, q].cpu().numpy(), ud[q, p].cpu().numpy()
+    upper, lower = rc.packed_rows(arows, brows, T, extended=True)
+    bound = rc.rows_bound(arows, brows, T)
+    worst = 0.0
+    for got, want in ((S[:, p, q], upper), (S[:, q, p], lower)):
+        err = np.abs(got.cpu().numpy() - want).astype(np.float64)
+        worst = max(worst, float((err[bound > 0] / bound[bound > 0]).max()))
+        assert (err <= bound).all()
+    print(f"fp64 l={l}: largest error / bound = {worst:.3f} on {n} row pairs")
+
+
 @pytest.mark.parametrize("form", list(FORMS))
 def test_a_result_knows_neither_its_batch_nor_the_group_size(form):
     from quantum_systems_amd import kernels

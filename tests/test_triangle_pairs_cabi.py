@@ -43,6 +43,28 @@ def test_first_and_last_pair_of_every_row_of_a_large_grid(lib, n):
     assert start == n * (n + 1) // 2
 
 
+def _strict_pair(lib, l, t):
+    """(r, s), r < s, of packed position t by the identity that csrc/qs_pair_walk.h's pair_unpack<false> rests on: the
+    triangle WITH its diagonal of n = l - 1, its second index shifted by one.  The shift is redone HERE, on top of
+    ``qs_triangle_pair``: this pins the identity and ``triangle_row`` at n = l - 1, not the C++ line itself (that one
+    runs under the GPU parity tests only)."""
+    r, j = _pair(lib, l - 1, t)
+    return r, j + 1
+
+
+def test_the_strict_triangle_is_the_triangle_of_l_minus_1_shifted(lib):
+    for l in range(2, 41):
+        want = [(r, s) for r in range(l) for s in range(r + 1, l)]
+        got = [_strict_pair(lib, l, t) for t in range(len(want))]
+        assert got == want, l
+    l, start = 4096, 0
+    for r in range(l - 1):                                   # run r: (r, r + 1) ... (r, l - 1)
+        assert _strict_pair(lib, l, start) == (r, r + 1), r
+        assert _strict_pair(lib, l, start + l - r - 2) == (r, l - 1), r
+        start += l - r - 1
+    assert start == l * (l - 1) // 2
+
+
 def test_pair_refuses_bad_arguments(lib):
     i, j = ctypes.c_int64(7), ctypes.c_int64(7)
     ri, rj = ctypes.byref(i), ctypes.byref(j)
