@@ -588,6 +588,9 @@ const char* qs_last_dispatch(void);
  *     "string_ci_bytes" (qs_string_ci_group: the byte budget of the D and G
  *     panels of one qs_string_ci_sigma call, 0 = the caller's shipped value;
  *     a negative value is refused with QS_ERR_BAD_EXTENT),
+ *     "triples_bytes" (qs_triples_energy_budget: the byte budget of the blocks
+ *     of one pass of the triples correction, 0 = the caller's shipped value;
+ *     a negative value is refused with QS_ERR_BAD_EXTENT),
  *     "exchange" (qs_transform_two_body_exchange_wanted: 0 = never, 1 = where
  *     the exchange route measured faster, 2 = wherever it exists, any size),
  *     "exchange_block" / "exchange_block_d" (rows per block of that route's
@@ -1278,6 +1281,47 @@ int qs_tdho_quadrature_nodes(int64_t max_shell, double* k_out, double* w_out);
 int qs_tdho_coulomb_quadrature_workspace(int64_t l, int64_t max_shell, int64_t* bytes);
 int qs_tdho_coulomb_quadrature(void* out, const void* nm_table, int64_t l, int64_t max_shell, int64_t p_lo,
                                int64_t p_hi, void* workspace, int64_t workspace_bytes, void* stream);
+/*
+ * Closed-shell perturbative triples: the energy of occupied triples from their
+ * blocks (csrc/qs_triples.hip).  Triple x owns six blocks of X, each
+ * (v, v, v) row-major of dtype: X_0 ... X_5 = X_ijk, X_ikj, X_jik, X_jki, X_kij,
+ * X_kji at the block indices slots[x][0 ... 5] (equal occupied indices share
+ * blocks: equal entries are allowed and read once).  With
+ *   W[a,b,c] = X_0[a,b,c] + X_1[a,c,b] + X_2[b,a,c] + X_3[b,c,a] + X_4[c,a,b] + X_5[c,b,a]
+ *   Z[a,b,c] = (4 W[abc] + W[bca] + W[cab] - 2 W[acb] - 2 W[cba] - 2 W[bac]) / 3
+ *   e[x]     = sum_abc Re(conj(W[abc]) Z[abc]) / (eo3[x] - ev[a] - ev[b] - ev[c])
+ * without the weight of the triple.  W and Z are never stored; every element of
+ * the six blocks is read once.
+ *   X      : (nblocks, v, v, v) of dtype, device
+ *   slots  : (n, 6) int32, device, every entry in 0 ... nblocks - 1; a triple
+ *            with an entry outside that range reads nothing and gets e = NaN
+ *   eo3    : n doubles, device: e_i + e_j + e_k of the triple
+ *   ev     : v doubles, device: the virtual orbital energies
+ *   e      : n doubles, device, out
+ *   work   : qs_triples_energy_workspace bytes, device, 8-byte aligned: one
+ *            partial per (triple, set of three tiles)
+ * Two launches in stream order, no atomics, asynchronous: a workgroup per triple
+ * and unordered set of three tiles of edge qs_triples_energy_tile(dtype) along
+ * a, b, c adds its elements in a fixed order; a closing launch adds the partials
+ * of a triple in an order fixed by v alone.  e[x] has the same bits on every
+ * run, and the same alone as anywhere in a batch.
+ * Limits: 1 <= v <= 4096, n >= 1, n times the tile sets of one triple below 2^31,
+ * 1 <= nblocks < 2^31 with the bytes of X inside int64, else QS_ERR_BAD_EXTENT.
+ * Errors, in this order, before any HIP call: dtype; extents; null pointer;
+ * misaligned pointer (element size X, 4 slots, 8 the others); work_bytes below
+ * the query (QS_ERR_WORKSPACE); e sharing a byte with an input or the workspace,
+ * or the workspace with X (QS_ERR_ALIAS).
+ *
+ * qs_triples_energy_budget: the byte budget in force on the calling thread --
+ * the tuning key "triples_bytes" where it is positive, else budget_bytes
+ * (negative: QS_ERR_BAD_EXTENT).  Plain host code.  (Additions: the ABI version
+ * stays 4.)
+ */
+int64_t qs_triples_energy_tile(int dtype);
+int64_t qs_triples_energy_budget(int64_t budget_bytes);
+int64_t qs_triples_energy_workspace(int dtype, int64_t v, int64_t n);
+int qs_triples_energy(int dtype, const void* X, int64_t nblocks, const int32_t* slots, const double* eo3, const double* ev,
+                      int64_t v, int64_t n, double* e, void* work, int64_t work_bytes, void* stream);
 int qs_probe_mfma_f64(void* sink, int64_t blocks, int64_t iters, void* stream);
 int qs_probe_stream_copy(const void* src, void* dst, int64_t bytes, void* stream);
 

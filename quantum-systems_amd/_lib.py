@@ -136,6 +136,10 @@ SIGNATURES = {
     "qs_cholesky_two_body": (
         c_int, [c_int, c_ptr, c_i64, ctypes.c_double, c_ptr, c_i64, ctypes.POINTER(c_i64), c_ptr, c_ptr,
                 ctypes.POINTER(ctypes.c_double), c_ptr, c_i64, c_ptr]),
+    "qs_triples_energy_tile": (c_i64, [c_int]),
+    "qs_triples_energy_budget": (c_i64, [c_i64]),
+    "qs_triples_energy_workspace": (c_i64, [c_int, c_i64, c_i64]),
+    "qs_triples_energy": (c_int, [c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_i64, c_ptr]),
     "qs_tdho_quadrature_nodes": (c_int, [c_i64, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "qs_tdho_coulomb_quadrature_workspace": (c_int, [c_i64, c_i64, ctypes.POINTER(c_i64)]),
     "qs_tdho_coulomb_quadrature": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, c_ptr, c_i64, c_ptr]),

@@ -23,6 +23,9 @@ product on them and ``t``, in torch.
 
     ccd = CCD(system, C, epsilon)            # or CCD(system) after change_basis(C); or HartreeFock.ccd()
     e_corr = ccd.solve(tol=1e-8)             # ccd.t, ccd.residuals, ccd.converged, ccd.iterations
+
+``RCCD.triples()`` adds the perturbative triples correction on the closed-shell amplitudes (``kernels.triples_energy``);
+the spin-orbital ``CCD`` has none.
 """
 
 import torch
@@ -266,7 +269,8 @@ class RCCD:
     ``C``, ``epsilon``, ``solve``, ``residual``, ``energy``, ``t``, ``residuals``, ``converged`` and ``iterations`` are
     those of ``CCD``; ``max_iter=0`` gives the closed-shell MP2 energy.  ``u`` is checked for the symmetry once, at
     construction, for either ladder: bit for bit, and where that fails (a ``u`` that went through ``change_basis``) to
-    rounding (``_exchange_symmetric_to_rounding``); anything else is refused."""
+    rounding (``_exchange_symmetric_to_rounding``); anything else is refused.  ``triples()`` adds the perturbative
+    triples correction on the amplitudes (canonical orbitals only)."""
 
     def __init__(self, system, C=None, epsilon=None, ladder="exchange"):
         if isinstance(system, GeneralOrbitalSystem):
@@ -328,8 +332,10 @@ class RCCD:
                 if eps.dim() != 1 or eps.shape[0] != l:
                     raise ValueError(f"epsilon must hold the {l} diagonal Fock elements, got {tuple(eps.shape)}")
             self._foo, self._fvv = f[o, o].contiguous(), f[v, v].contiguous()
+            self._fov, self._fvo = f[o, v].contiguous(), f[v, o].contiguous()       # (triples: are the orbitals canonical?)
             self._L = 2.0 * self._oovv - self._oovv.transpose(2, 3)
             eps = (eps.real if eps.is_complex() else eps).to(torch.float64)
+            self._eps = eps
             eo, ev = eps[:n], eps[n:]
             self._D = ev.neg()[:, None, None, None] - ev[None, :, None, None] + eo[None, None, :, None] + eo[None, None, None, :]
             # the occupied pairs i <= j: one amplitude matrix of the pass each
@@ -337,6 +343,7 @@ class RCCD:
             self._t = self._vvoo / self._D
         self.t = _deliver(self._t, system.np)
         self.residuals, self.converged, self.iterations = [], False, 0
+        self._triples_blocks, self.triples_passes = None, []
 
     # -- the pass over u: sum_cd <ab|cd> t^{cd}_{ij} and sum_cd <kl|cd> t^{cd}_{ij} from one contraction
     def _ladder(self, t):
@@ -425,3 +432,125 @@ class RCCD:
             self._t = t
             self.t = _deliver(t.contiguous(), self.system.np)
         return self.energy()
+
+    # -- the perturbative triples on the doubles
+    def _require_canonical(self, canonical_tol):
+        foo, fvv = self._foo, self._fvv
+        worst = max(float((foo - torch.diag(foo.diagonal())).abs().max().item()),
+                    float((fvv - torch.diag(fvv.diagonal())).abs().max().item()),
+                    float(self._fov.abs().max().item()), float(self._fvo.abs().max().item()))
+        top = float(self._eps.abs().max().item())
+        if worst > canonical_tol * top:
+            raise ValueError(f"RCCD.triples needs canonical orbitals (a diagonal Fock matrix): the largest off-diagonal "
+                             f"element is {worst:.3e}, above canonical_tol * max|epsilon| = {canonical_tol * top:.3e} -- "
+                             "pass the C and epsilon of HartreeFock.scf()")
+
+    def _triples_integrals(self):
+        """``Vp[k,d,b,c] = <bc|dk>`` (o, v, v, v) and ``Hh[j,k,l,c] = -<lc|jk>`` (o, o, o, v), formed once."""
+        if self._triples_blocks is None:
+            n, l = self.n, self.l
+            o, v = slice(0, n), slice(n, l)
+            u = self._u
+            if self._Cv is None:
+                vvvo, ovoo = u[v, v, v, o], u[o, v, o, o]
+            else:
+                Co, Cv, Coh, Cvh = self._Co, self._Cv, self._Coh, self._Cvh
+                vvvo = kernels.transform_two_body_blocks(u, Cvh, Cvh, Cv, Co)
+                ovoo = kernels.transform_two_body_blocks(u, Coh, Cvh, Co, Co)
+            self._triples_blocks = (vvvo.to(self._dt).permute(3, 2, 0, 1).contiguous(),
+                                    ovoo.to(self._dt).permute(2, 3, 0, 1).neg().contiguous())
+        return self._triples_blocks
+
+    def triples(self, t=None, canonical_tol=1e-8):
+        """The perturbative triples correction ``E_T`` (a float) on the doubles amplitudes ``t`` (v, v, o, o), by default
+        the current ones: "+T(CCD)" on converged amplitudes, the fourth-order triples energy on first-order ones
+        (``solve(max_iter=0)``).  With ``T2`` the doubles operator of ``t``,
+
+            E_T = sum_mu |<mu| H T2 |0>|^2 / D_mu,      D_mu = sum eps(holes of mu) - sum eps(particles of mu)
+
+        over the triply excited determinants; in the closed-shell working form
+
+            X_ijk[a,b,c] = sum_d t[a,d,i,j] <bc|dk>  -  sum_l t[a,b,i,l] <lc|jk>
+            W_ijk[a,b,c] = X_ijk[a,b,c] + X_ikj[a,c,b] + X_jik[b,a,c] + X_jki[b,c,a] + X_kij[c,a,b] + X_kji[c,b,a]
+            Z[a,b,c]     = (4 W_abc + W_bca + W_cab - 2 W_acb - 2 W_cba - 2 W_bac) / 3
+            e_ijk        = sum_abc Re(conj(W_abc) Z_abc) / (eps_i + eps_j + eps_k - eps_a - eps_b - eps_c)
+            E_T          = sum_{i<=j<=k} m_ijk e_ijk,     m = 6 (all different), 3 (two equal), 0 (i = j = k)
+
+        The blocks ``X`` are products on the GEMM dispatcher (with the blocks laid out (k, j, i), the particle term of every
+        (i, j) at a fixed k is ONE product and the hole term of every i at a fixed (j, k) one accumulating product);
+        ``kernels.triples_energy`` turns them into ``e_ijk`` in one read.  Where all o^3 blocks fit
+        ``kernels.TRIPLES_BYTES`` (tuning key ``triples_bytes``) there is one launch of it over all triples; otherwise
+        passes over as many triples as their own blocks (six, or three where two indices are equal) fit, at least one,
+        each block one particle and one hole product.  ``triples_passes`` keeps (triples, blocks, kernels) of every pass.
+
+        The formula holds in canonical orbitals only: ``ValueError`` where an off-diagonal element of the Fock matrix
+        exceeds ``canonical_tol * max|epsilon|`` (the orbitals of ``HartreeFock.scf`` at its default tolerance pass)."""
+        if is_sharded(self.system.u):
+            raise NotImplementedError("RCCD.triples does not take a sharded u: pass a system whose u lives on one device")
+        with torch._C.DisableTorchFunctionSubclass():
+            n, nv = self.n, self.l - self.n
+            if t is None:
+                t = self._t
+            else:
+                t = _plain(t)
+                if tuple(t.shape) != (nv, nv, n, n):
+                    raise ValueError(f"t must be (v, v, o, o) = {(nv, nv, n, n)}, got {tuple(t.shape)}")
+                t = t.to(self._dt)
+            self._require_canonical(canonical_tol)
+            self.triples_passes = []
+            todo = [(i, j, k) for i in range(n) for j in range(i, n) for k in range(j, n) if not i == j == k]
+            if not todo:                    # one occupied orbital: three like spins cannot share it
+                return 0.0
+            Vp, Hh = self._triples_integrals()
+            dt, dev = self._dt, t.device
+            tp = t.permute(3, 2, 0, 1).contiguous()                  # tp[j,i,a,d] = t[a,d,i,j]
+            th = t.permute(2, 0, 1, 3).contiguous()                  # th[i,a,b,l] = t[a,b,i,l]
+            eo, ev = self._eps[:n].tolist(), self._eps[n:].contiguous()
+            v2, v3 = nv * nv, nv * nv * nv
+
+            def orders(i, j, k):
+                return ((i, j, k), (i, k, j), (j, i, k), (j, k, i), (k, i, j), (k, j, i))
+
+            def energies(X, group, where):
+                slots = torch.tensor([[where[pqr] for pqr in orders(*ijk)] for ijk in group], dtype=torch.int32, device=dev)
+                eo3 = torch.tensor([eo[i] + eo[j] + eo[k] for i, j, k in group], dtype=torch.float64, device=dev)
+                e = kernels.triples_energy(X, slots, eo3, ev)
+                self.triples_passes.append((len(group), X.shape[0], kernels.last_dispatch()))
+                return e
+
+            fit = kernels.triples_budget() // (v3 * t.element_size())
+            if fit >= n ** 3:
+                # every block, X_pqr at (r, q, p): o particle products and o^2 hole products
+                X = torch.empty((n ** 3, nv, nv, nv), dtype=dt, device=dev)
+                for k in range(n):
+                    kernels.gemm_raw(dt, tp, Vp, X, n * n * nv, v2, nv, nv, v2, v2, b_off=k * v3, c_off=k * n * n * v3)
+                    for j in range(n):
+                        kernels.gemm_raw(dt, th, Hh, X, n * v2, nv, n, n, nv, nv, accumulate=True,
+                                         b_off=(j * n + k) * n * nv, c_off=(k * n + j) * n * v3)
+                e = energies(X, todo, {(p, q, r): (r * n + q) * n + p for p in range(n) for q in range(n) for r in range(n)})
+            else:
+                # passes: triples share no block, so a group's blocks are the sum of its triples' own
+                groups, count = [[]], 0
+                for ijk in todo:
+                    own = len(set(orders(*ijk)))
+                    if groups[-1] and count + own > fit:
+                        groups.append([])
+                        count = 0
+                    groups[-1].append(ijk)
+                    count += own
+                parts = []
+                for group in groups:
+                    where = {}
+                    for ijk in group:
+                        for pqr in orders(*ijk):
+                            where.setdefault(pqr, len(where))
+                    X = torch.empty((len(where), nv, nv, nv), dtype=dt, device=dev)
+                    for (p, q, r), x in where.items():
+                        kernels.gemm_raw(dt, tp, Vp, X, nv, v2, nv, nv, v2, v2, a_off=(q * n + p) * v2, b_off=r * v3, c_off=x * v3)
+                        kernels.gemm_raw(dt, th, Hh, X, v2, nv, n, n, nv, nv, accumulate=True,
+                                         a_off=p * v2 * n, b_off=(q * n + r) * n * nv, c_off=x * v3)
+                    parts.append(energies(X, group, where))
+                    del X
+                e = torch.cat(parts)
+            m = torch.tensor([3.0 if (i == j or j == k) else 6.0 for i, j, k in todo], dtype=torch.float64, device=dev)
+            return float((m * e).sum().item())

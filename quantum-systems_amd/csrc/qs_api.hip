@@ -295,6 +295,11 @@ int qs_tuning_set(const char* key, int64_t value) {
         g_tune.string_ci_bytes = value;
         return QS_OK;
     }
+    if (!strcmp(key, "triples_bytes")) {
+        if (value < 0) return QS_ERR_BAD_EXTENT;
+        g_tune.triples_bytes = value;
+        return QS_OK;
+    }
     if (!strcmp(key, "lead_rows_max")) {
         if (value < 0 || value > 32) return QS_ERR_BAD_EXTENT;
         g_tune.lead_rows_max = (int)value;

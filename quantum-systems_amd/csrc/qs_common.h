@@ -268,6 +268,7 @@ struct Tuning {
     int det_ci_g = 0;            // qs_det_ci_sigma: vectors per walk of a determinant's excitations, 0 = the shipped group size of the form;
                                  // 1, 2, 4, 8 = tuning runs (every setting gives the same bits: a vector's fma chain does not know G)
     int64_t string_ci_bytes = 0; // qs_string_ci_group: byte budget of the D and G panels of one qs_string_ci_sigma call, 0 = the caller's shipped value
+    int64_t triples_bytes = 0;   // qs_triples_energy_budget: byte budget of the blocks of one pass of RCCD.triples, 0 = the caller's shipped value
     int exchange = 1;            // the transform's route for a tensor with particle-exchange symmetry (qs_transform_two_body_exchange_wanted):
                                  // 0 never, 1 where it measured faster, 2 wherever it exists (any size, ahead of the fused small-basis routes)
     int exchange_block = 0;      // rows per block of that route's closing product (and of its mirror), 0 = automatic

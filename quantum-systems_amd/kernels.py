@@ -1673,6 +1673,67 @@ def cholesky_two_body(u, tol, max_rank=None, state=None):
     return state.vectors[:r], state.pivots[:r], (float(extremes[0]), float(extremes[1])), state
 
 
+# Byte budget of the blocks X of ONE pass of ``coupled_cluster.RCCD.triples``: all o^3 blocks where they fit it (one
+# ``triples_energy`` launch over every triple), else passes over as many triples as their own blocks fit (at least one).
+# The tuning key ``triples_bytes`` overrides it for the calling thread.
+TRIPLES_BYTES = 8 << 30
+
+
+def triples_budget():
+    """The byte budget in force on the calling thread: the tuning key ``triples_bytes`` where it is set, else
+    ``TRIPLES_BYTES``."""
+    return check(_lib.load().qs_triples_energy_budget(TRIPLES_BYTES), "budget query")
+
+
+def triples_tile(dtype):
+    """Tile edge of ``triples_energy`` along each virtual index for ``dtype``: 8 for float64, 6 for complex128."""
+    return check(_lib.load().qs_triples_energy_tile(dtype_code(dtype)), "tile query")
+
+
+@_plain
+def triples_energy(X, slots, eo3, ev, out=None):
+    """``e[x] = sum_abc Re(conj(W) Z) / (eo3[x] - ev[a] - ev[b] - ev[c])`` of n occupied triples (``qs_triples_energy``),
+    without the triple's weight:
+
+        W[a,b,c] = X0[a,b,c] + X1[a,c,b] + X2[b,a,c] + X3[b,c,a] + X4[c,a,b] + X5[c,b,a]
+        Z[a,b,c] = (4 W[abc] + W[bca] + W[cab] - 2 W[acb] - 2 W[cba] - 2 W[bac]) / 3
+
+    with ``X0 ... X5`` the blocks ``X[slots[x]]`` of ``X`` (nblocks, v, v, v), float64 or complex128; ``slots`` (n, 6)
+    int32 with every entry in ``0 ... nblocks - 1`` (equal entries allowed), ``eo3`` (n,) and ``ev`` (v,) float64.  One
+    read of the blocks, neither W nor Z stored, no atomics: the same bits on every run and for a triple alone or in a
+    batch.  Returns ``e`` (n,) float64."""
+    lib = _lib.load()
+    if not isinstance(X, torch.Tensor) or X.dtype not in (_F64, _C128):
+        raise TypeError("X must be a float64 or complex128 tensor")
+    if X.dim() != 4 or X.shape[0] < 1 or X.shape[1] < 1 or not X.shape[1] == X.shape[2] == X.shape[3]:
+        raise ValueError(f"X must be (nblocks, v, v, v), got {tuple(X.shape)}")
+    dt, (nblocks, v) = X.dtype, X.shape[:2]
+    if not isinstance(slots, torch.Tensor) or slots.dtype != torch.int32 or slots.dim() != 2 or slots.shape[1] != 6 or slots.shape[0] < 1:
+        raise ValueError("slots must be an (n, 6) int32 tensor of block indices")
+    n = slots.shape[0]
+    for name, arr, length in (("eo3", eo3, n), ("ev", ev, v)):
+        if not isinstance(arr, torch.Tensor) or arr.dtype != _F64 or tuple(arr.shape) != (length,):
+            raise ValueError(f"{name} must be a float64 tensor of shape ({length},)")
+    X, slots, eo3, ev = _dev(X), _dev(slots), _dev(eo3), _dev(ev)
+    lo, hi = slots.aminmax()
+    if int(lo) < 0 or int(hi) >= nblocks:
+        raise ValueError(f"slots must lie in 0 ... {nblocks - 1}, got {int(lo)} ... {int(hi)}")
+    code = dtype_code(dt)
+    nbytes = check(lib.qs_triples_energy_workspace(code, v, n), "workspace query")
+    if out is None:
+        out = torch.empty(n, dtype=_F64, device=X.device)
+    else:
+        _check_out(out, (n,), _F64, "triples_energy")
+    with _on_device_of(X, slots, eo3, ev, out):
+        work = workspace.get(nbytes, X.device)
+        _ran(
+            lib.qs_triples_energy(code, X.data_ptr(), nblocks, slots.data_ptr(), eo3.data_ptr(), ev.data_ptr(), v, n,
+                                  out.data_ptr(), work.data_ptr(), work.numel(), _stream()),
+            "qs_triples_energy",
+        )
+    return out
+
+
 class RcclComm:
     """The C ABI's communicator (``qs_comm_init``: RCCL over xGMI, one process per GPU) for hosts that drive the
     library from Python without ``torch.distributed``.  ``unique_id()`` on one rank, the 128 bytes to the others by
