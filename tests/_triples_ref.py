@@ -216,6 +216,73 @@ def kernel_bound(X, slots, eo3, ev):
     return np.array([kernel_bound_terms(X, row, eo3[x], ev, v ** 3).sum() for x, row in enumerate(np.asarray(slots))])
 
 
+# -- the kernel's work units: what one (triple, tile set) adds, every coincidence of six slots
+
+
+def tile_set_sums(terms, T):
+    """What every unordered set of three tiles of edge ``T`` adds to the sum of ``terms`` (v, v, v), in the kernel's order
+    of sets (tc slowest, then tb, then ta <= tb <= tc): an element belongs to the set of its sorted tile indices, so a set
+    holds whole orbits of (a, b, c).  Length nt (nt + 1) (nt + 2) / 6."""
+    v = terms.shape[0]
+    nt = -(-v // T)
+    tile = np.arange(v) // T
+    ta, tb, tc = np.sort(np.stack(np.meshgrid(tile, tile, tile, indexing="ij")), axis=0)
+    index = tc * (tc + 1) * (tc + 2) // 6 + tb * (tb + 1) // 2 + ta
+    sums = np.zeros(nt * (nt + 1) * (nt + 2) // 6, dtype=terms.dtype)
+    np.add.at(sums, index.ravel(), terms.ravel())
+    return sums
+
+
+def tile_set_sensitivity(X, slots, eo3, ev, T):
+    """The least ``|contribution of a tile set| / kernel_bound`` over the triples of the table and their tile sets, from
+    the long-double reference alone: a workgroup left out or corrupted moves ``e`` by that many bounds at least.  What is
+    0 by identity is left out, and nothing else:
+      * a set that holds a = b = c alone -- the diagonal set of a ragged tile of one element: the six W are equal, Z = 0;
+      * every set of a triple with ONE block in all six slots: W is totally symmetric, Z = 0, e = 0 (``e_iii``);
+      * where the even orders (slots 0, 3, 4) hold one block and the odd ones (1, 2, 5) one block, W is the same at the
+        three cyclic orders of (a, b, c), so it is totally symmetric wherever two of the indices are equal: the diagonal
+        set of a ragged tile of TWO elements holds such orbits alone."""
+    v = len(ev)
+    ragged = v % T
+    bound = kernel_bound(X, slots, eo3, ev)
+    least = np.inf
+    for x, row in enumerate(np.asarray(slots)):
+        if len(set(row.tolist())) == 1:
+            continue
+        cyclic = row[0] == row[3] == row[4] and row[1] == row[2] == row[5]
+        sums = np.abs(tile_set_sums(kernel_terms(X, row, eo3[x], ev, extended=True), T)).astype(np.float64)
+        if ragged == 1 or (ragged == 2 and cyclic):
+            sums = sums[:-1]                # (nt - 1, nt - 1, nt - 1), the last set
+        if sums.size:
+            least = min(least, sums.min() / bound[x])
+    return least
+
+
+def _set_partitions(m):
+    """The partitions of m things as restricted growth strings: thing x in class s[x], classes numbered as they appear."""
+    if m == 0:
+        return [[]]
+    return [s + [c] for s in _set_partitions(m - 1) for c in range(max(s, default=-1) + 2)]
+
+
+def coincidence(row):
+    """Which slots of a row hold the same block: the row with its blocks renumbered as they appear."""
+    seen = {}
+    return tuple(seen.setdefault(int(b), len(seen)) for b in row)
+
+
+def slot_partitions(nblocks, seed=0):
+    """(203, 6) int32: one slot row for every way in which the six slots of a triple can coincide (the set partitions of
+    six things).  The classes of a row go to distinct blocks of ``nblocks >= 6`` drawn by ``seed``, so which class has the
+    lowest block, and which appears first, varies from row to row."""
+    rng = np.random.default_rng(seed)
+    rows = []
+    for s in _set_partitions(6):
+        blocks = rng.choice(nblocks, max(s) + 1, replace=False)
+        rows.append(blocks[s])
+    return np.array(rows, dtype=np.int32)
+
+
 def block_index(ns, p, q, r):
     """Where ``X_pqr`` sits among the o^3 blocks: the last occupied index slowest."""
     return (r * ns + q) * ns + p

@@ -52,6 +52,8 @@ def tile_sizes(name):
     T = kernels.triples_tile(DTYPES[name])
     assert T == {"f64": 8, "c128": 6}[name]
     # a lone (ragged) diagonal tile; a full one; two tiles (sets with two and three equal indices); three (all different)
+    # (a ragged tile of ONE element, T + 1 and 2 T + 1: its diagonal set holds a = b = c alone and adds 0 by identity --
+    # tests/test_gpu_triples_scale.py has the ragged tiles of two and more, and more than three tiles)
     return [1, 2, 3, T - 1, T, T + 1, 2 * T + 1]
 
 
