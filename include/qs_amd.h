@@ -1322,6 +1322,32 @@ int64_t qs_triples_energy_budget(int64_t budget_bytes);
 int64_t qs_triples_energy_workspace(int dtype, int64_t v, int64_t n);
 int qs_triples_energy(int dtype, const void* X, int64_t nblocks, const int32_t* slots, const double* eo3, const double* ev,
                       int64_t v, int64_t n, double* e, void* work, int64_t work_bytes, void* stream);
+/*
+ * The same with the singles term of (T) beside it.  Block beta of
+ * triple x has a partner Y_beta[p,q,r] = A[sa][p] G[sg][q,r], an outer product
+ * that is never stored, with (sa, sg) = sslots[x][beta]; V' is made from the
+ * Y_beta as W from the X_beta, and
+ *   e[x]  = as qs_triples_energy (the connected part)
+ *   es[x] = sum_abc Re(conj(V'[abc]) Z[abc]) / (eo3[x] - ev[a] - ev[b] - ev[c])
+ *   A      : (na, v) of dtype, device
+ *   G      : (ng, v, v) of dtype, device
+ *   sslots : (n, 6, 2) int32, device: (sa, sg) per slot, in 0 ... na - 1 and
+ *            0 ... ng - 1; a triple with an entry of slots or sslots out of
+ *            range reads nothing and gets e = es = NaN
+ *   e, es  : n doubles each, device, out
+ *   work   : qs_triples_energy_singles_workspace bytes (two partials per triple
+ *            and set of tiles), device, 8-byte aligned
+ * Three launches in stream order (the work units, one close per output), no
+ * atomics, asynchronous; the bits of e[x] and es[x] depend on the triple's own
+ * inputs alone.  Limits and errors as qs_triples_energy, with 1 <= na, ng < 2^31,
+ * A and G aligned to the element size, sslots to 4; QS_ERR_ALIAS where e, es or
+ * the workspace share a byte with an input or with one another.  (Additions:
+ * the ABI version stays 4.)
+ */
+int64_t qs_triples_energy_singles_workspace(int dtype, int64_t v, int64_t n);
+int qs_triples_energy_singles(int dtype, const void* X, int64_t nblocks, const int32_t* slots, const double* eo3,
+                              const double* ev, const void* A, int64_t na, const void* G, int64_t ng, const int32_t* sslots,
+                              int64_t v, int64_t n, double* e, double* es, void* work, int64_t work_bytes, void* stream);
 int qs_probe_mfma_f64(void* sink, int64_t blocks, int64_t iters, void* stream);
 int qs_probe_stream_copy(const void* src, void* dst, int64_t bytes, void* stream);
 

@@ -17,7 +17,7 @@ from .sharded_module import ShardedDeviceModule, ShardedTensor4
 from .basis_set import BasisSet, ChangeBasisPlan
 from .cholesky import CholeskyTwoBody
 from .configuration_interaction import CIS
-from .coupled_cluster import CCD, RCCD
+from .coupled_cluster import CCD, RCCD, RCCSD
 from .custom_system import construct_custom_system, setup_basis_set
 from .general_orbital_system import GeneralOrbitalSystem
 from .hartree_fock import HartreeFock
@@ -34,7 +34,7 @@ from .two_dim_ho import TwoDimensionalDoubleWell, TwoDimensionalHarmonicOscillat
 
 __all__ = [
     "BasisSet", "RandomBasisSet", "QuantumSystem", "SpatialOrbitalSystem",
-    "GeneralOrbitalSystem", "HartreeFock", "mp2_energy", "CIS", "configuration_interaction", "TwoParticleCI", "two_particle", "CCD", "RCCD", "coupled_cluster", "DeterminantCI", "determinant_ci", "full_space", "sz_sector", "truncated_space", "StringCI", "string_ci", "full_strings", "response", "setup_basis_set", "construct_custom_system",
+    "GeneralOrbitalSystem", "HartreeFock", "mp2_energy", "CIS", "configuration_interaction", "TwoParticleCI", "two_particle", "CCD", "RCCD", "RCCSD", "coupled_cluster", "DeterminantCI", "determinant_ci", "full_space", "sz_sector", "truncated_space", "StringCI", "string_ci", "full_strings", "response", "setup_basis_set", "construct_custom_system",
     "TwoDimensionalHarmonicOscillator", "TwoDimensionalDoubleWell", "TwoDimHarmonicOscB", "ODQD", "ODSincDVR",
     "ChangeBasisPlan", "cholesky", "CholeskyTwoBody", "hip", "DeviceModule", "DeviceArray", "ShardedDeviceModule", "ShardedTensor4", "kernels", "sharded",
 ]

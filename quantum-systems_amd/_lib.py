@@ -140,6 +140,10 @@ SIGNATURES = {
     "qs_triples_energy_budget": (c_i64, [c_i64]),
     "qs_triples_energy_workspace": (c_i64, [c_int, c_i64, c_i64]),
     "qs_triples_energy": (c_int, [c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_i64, c_ptr]),
+    "qs_triples_energy_singles_workspace": (c_i64, [c_int, c_i64, c_i64]),
+    "qs_triples_energy_singles": (
+        c_int, [c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_ptr,
+                c_ptr, c_i64, c_ptr]),
     "qs_tdho_quadrature_nodes": (c_int, [c_i64, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "qs_tdho_coulomb_quadrature_workspace": (c_int, [c_i64, c_i64, ctypes.POINTER(c_i64)]),
     "qs_tdho_coulomb_quadrature": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, c_ptr, c_i64, c_ptr]),

@@ -25,7 +25,8 @@ product on them and ``t``, in torch.
     e_corr = ccd.solve(tol=1e-8)             # ccd.t, ccd.residuals, ccd.converged, ccd.iterations
 
 ``RCCD.triples()`` adds the perturbative triples correction on the closed-shell amplitudes (``kernels.triples_energy``);
-the spin-orbital ``CCD`` has none.
+the spin-orbital ``CCD`` has none.  ``RCCSD`` (last) adds single excitations by T1-dressing the Hamiltonian that ``RCCD``
+works on, and (T): the triples with their singles term (``kernels.triples_energy_singles``).
 """
 
 import torch
@@ -242,6 +243,28 @@ def _exchange_symmetric_to_rounding(u):
     return bool(worst <= _EXCHANGE_ROUNDING * top)
 
 
+def _closed_shell_doubles(t, driver, W, fvv, foo, oovv, L, ovvo, ovov):
+    """The closed-shell doubles residual (the formula of ``RCCD``) from ``driver = <ab|ij> + sum_cd <ab|cd> t^{cd}_{ij}``,
+    ``W = <kl|ij> + sum_cd <kl|cd> t^{cd}_{ij}``, the Fock blocks and the small integral blocks.  Nothing in it uses
+    hermiticity, so the blocks may be T1-dressed ones (``RCCSD``)."""
+    ein = torch.einsum
+    nv, n = t.shape[0], t.shape[2]
+    R = driver + ein("klij,abkl->abij", W, t)
+    # the two one-index intermediates have a long sum and a small result: batched over the leading indices of the
+    # sum and added up afterwards, so that the device is filled (one product of that shape is one workgroup's work)
+    Fvv = fvv - torch.bmm(t.permute(2, 3, 0, 1).reshape(n * n, nv, nv),
+                          L.permute(0, 1, 3, 2).reshape(n * n, nv, nv)).sum(0)                 # L_klcd t^{bd}_{kl} -> [b, c]
+    Foo = foo + torch.bmm(L.permute(1, 2, 0, 3).reshape(n * nv, n, nv),
+                          t.permute(3, 0, 1, 2).reshape(n * nv, nv, n)).sum(0)                 # L_klcd t^{cd}_{jl} -> [k, j]
+    Wd = ovvo - 0.5 * ein("klcd,dbjl->kbcj", oovv, t) + 0.5 * ein("klcd,dblj->kbcj", L, t)
+    Wx = -ovov + 0.5 * ein("kldc,dbjl->kbjc", oovv, t)
+    X = ein("bc,acij->abij", Fvv, t) - ein("kj,abik->abij", Foo, t)
+    X = X + ein("acik,kbcj->abij", t - t.transpose(0, 1), Wd)
+    X = X + ein("acik,kbcj->abij", t, Wd + Wx.transpose(2, 3))
+    X = X + ein("ackj,kbic->abij", t, Wx)
+    return R + X + X.transpose(0, 1).transpose(2, 3)
+
+
 class RCCD:
     """Spin-adapted closed-shell coupled-cluster doubles on a ``SpatialOrbitalSystem``: the ``system.n`` lowest orbitals
     of ``C`` doubly occupied (i, j, k, l), the rest virtual (a, b, c, d), ``u`` as it is (``<pq|rs>``, not
@@ -294,7 +317,7 @@ class RCCD:
             if not kernels.two_body_exchange_symmetric(u) and not _exchange_symmetric_to_rounding(u):
                 raise ValueError("RCCD needs a u with particle-exchange symmetry, u[p,q,r,s] = u[q,p,s,r]: "
                                  "both ladders and the equations rest on it")
-            self._u = u
+            self._u, self._h = u, h
             o, v = slice(0, n), slice(n, l)
             if C is None:
                 self._dt = torch.complex128 if (u.is_complex() or h.is_complex()) else torch.float64
@@ -382,25 +405,9 @@ class RCCD:
             return self._residual(t)
 
     def _residual(self, t):
-        ein = torch.einsum
-        n, nv = self.n, self.l - self.n
-        oovv, L = self._oovv, self._L
         pp, hh = self._ladder(t)                                         # sum_cd <ab|cd> t^{cd}_{ij},  sum_cd <kl|cd> t^{cd}_{ij}
-        W = self._oooo + hh
-        R = self._vvoo + pp + ein("klij,abkl->abij", W, t)
-        # the two one-index intermediates have a long sum and a small result: batched over the leading indices of the
-        # sum and added up afterwards, so that the device is filled (one product of that shape is one workgroup's work)
-        Fvv = self._fvv - torch.bmm(t.permute(2, 3, 0, 1).reshape(n * n, nv, nv),
-                                    L.permute(0, 1, 3, 2).reshape(n * n, nv, nv)).sum(0)       # L_klcd t^{bd}_{kl} -> [b, c]
-        Foo = self._foo + torch.bmm(L.permute(1, 2, 0, 3).reshape(n * nv, n, nv),
-                                    t.permute(3, 0, 1, 2).reshape(n * nv, nv, n)).sum(0)       # L_klcd t^{cd}_{jl} -> [k, j]
-        Wd = self._ovvo - 0.5 * ein("klcd,dbjl->kbcj", oovv, t) + 0.5 * ein("klcd,dblj->kbcj", L, t)
-        Wx = -self._ovov + 0.5 * ein("kldc,dbjl->kbjc", oovv, t)
-        X = ein("bc,acij->abij", Fvv, t) - ein("kj,abik->abij", Foo, t)
-        X = X + ein("acik,kbcj->abij", t - t.transpose(0, 1), Wd)
-        X = X + ein("acik,kbcj->abij", t, Wd + Wx.transpose(2, 3))
-        X = X + ein("ackj,kbic->abij", t, Wx)
-        return R + X + X.transpose(0, 1).transpose(2, 3)
+        return _closed_shell_doubles(t, self._vvoo + pp, self._oooo + hh, self._fvv, self._foo, self._oovv, self._L,
+                                     self._ovvo, self._ovov)
 
     def energy(self, t=None):
         """``sum (2<ij|ab> - <ij|ba>) t^{ab}_{ij}`` of the amplitudes (a float)."""
@@ -441,8 +448,8 @@ class RCCD:
                     float(self._fov.abs().max().item()), float(self._fvo.abs().max().item()))
         top = float(self._eps.abs().max().item())
         if worst > canonical_tol * top:
-            raise ValueError(f"RCCD.triples needs canonical orbitals (a diagonal Fock matrix): the largest off-diagonal "
-                             f"element is {worst:.3e}, above canonical_tol * max|epsilon| = {canonical_tol * top:.3e} -- "
+            raise ValueError(f"{type(self).__name__}.triples needs canonical orbitals (a diagonal Fock matrix): the largest "
+                             f"off-diagonal element is {worst:.3e}, above canonical_tol * max|epsilon| = {canonical_tol * top:.3e} -- "
                              "pass the C and epsilon of HartreeFock.scf()")
 
     def _triples_integrals(self):
@@ -497,60 +504,247 @@ class RCCD:
                     raise ValueError(f"t must be (v, v, o, o) = {(nv, nv, n, n)}, got {tuple(t.shape)}")
                 t = t.to(self._dt)
             self._require_canonical(canonical_tol)
-            self.triples_passes = []
-            todo = [(i, j, k) for i in range(n) for j in range(i, n) for k in range(j, n) if not i == j == k]
+            todo, e, _ = self._triples_energies(t)
             if not todo:                    # one occupied orbital: three like spins cannot share it
                 return 0.0
-            Vp, Hh = self._triples_integrals()
-            dt, dev = self._dt, t.device
-            tp = t.permute(3, 2, 0, 1).contiguous()                  # tp[j,i,a,d] = t[a,d,i,j]
-            th = t.permute(2, 0, 1, 3).contiguous()                  # th[i,a,b,l] = t[a,b,i,l]
-            eo, ev = self._eps[:n].tolist(), self._eps[n:].contiguous()
-            v2, v3 = nv * nv, nv * nv * nv
+            return float((self._triples_weights(todo, t.device) * e).sum().item())
 
-            def orders(i, j, k):
-                return ((i, j, k), (i, k, j), (j, i, k), (j, k, i), (k, i, j), (k, j, i))
+    @staticmethod
+    def _triples_weights(todo, dev):
+        return torch.tensor([3.0 if (i == j or j == k) else 6.0 for i, j, k in todo], dtype=torch.float64, device=dev)
 
-            def energies(X, group, where):
-                slots = torch.tensor([[where[pqr] for pqr in orders(*ijk)] for ijk in group], dtype=torch.int32, device=dev)
-                eo3 = torch.tensor([eo[i] + eo[j] + eo[k] for i, j, k in group], dtype=torch.float64, device=dev)
-                e = kernels.triples_energy(X, slots, eo3, ev)
-                self.triples_passes.append((len(group), X.shape[0], kernels.last_dispatch()))
-                return e
+    def _triples_energies(self, t, t1=None):
+        """The blocks and the pass loop of ``triples``: ``(todo, e, es)`` with ``todo`` the triples i <= j <= k (without
+        i = j = k) and ``e`` their energies.  With ``t1`` (v, o) the passes go through ``kernels.triples_energy_singles``
+        on ``A = 1/2 t1^T`` (o, v) and ``G[q o + r] = <bc|qr>`` (o^2, v, v), block ``X_pqr`` with the slot ``(p, q o + r)``,
+        and ``es`` is the singles part of every triple; without it ``es`` is None."""
+        n, nv = self.n, self.l - self.n
+        self.triples_passes = []
+        todo = [(i, j, k) for i in range(n) for j in range(i, n) for k in range(j, n) if not i == j == k]
+        if not todo:
+            return todo, None, None
+        Vp, Hh = self._triples_integrals()
+        dt, dev = self._dt, t.device
+        tp = t.permute(3, 2, 0, 1).contiguous()                  # tp[j,i,a,d] = t[a,d,i,j]
+        th = t.permute(2, 0, 1, 3).contiguous()                  # th[i,a,b,l] = t[a,b,i,l]
+        eo, ev = self._eps[:n].tolist(), self._eps[n:].contiguous()
+        v2, v3 = nv * nv, nv * nv * nv
+        if t1 is not None:
+            A = (0.5 * t1.transpose(0, 1)).contiguous()
+            G = self._vvoo.permute(2, 3, 0, 1).contiguous().reshape(n * n, nv, nv)
 
-            fit = kernels.triples_budget() // (v3 * t.element_size())
-            if fit >= n ** 3:
-                # every block, X_pqr at (r, q, p): o particle products and o^2 hole products
-                X = torch.empty((n ** 3, nv, nv, nv), dtype=dt, device=dev)
-                for k in range(n):
-                    kernels.gemm_raw(dt, tp, Vp, X, n * n * nv, v2, nv, nv, v2, v2, b_off=k * v3, c_off=k * n * n * v3)
-                    for j in range(n):
-                        kernels.gemm_raw(dt, th, Hh, X, n * v2, nv, n, n, nv, nv, accumulate=True,
-                                         b_off=(j * n + k) * n * nv, c_off=(k * n + j) * n * v3)
-                e = energies(X, todo, {(p, q, r): (r * n + q) * n + p for p in range(n) for q in range(n) for r in range(n)})
+        def orders(i, j, k):
+            return ((i, j, k), (i, k, j), (j, i, k), (j, k, i), (k, i, j), (k, j, i))
+
+        def energies(X, group, where):
+            slots = torch.tensor([[where[pqr] for pqr in orders(*ijk)] for ijk in group], dtype=torch.int32, device=dev)
+            eo3 = torch.tensor([eo[i] + eo[j] + eo[k] for i, j, k in group], dtype=torch.float64, device=dev)
+            if t1 is None:
+                e = kernels.triples_energy(X, slots, eo3, ev), None
             else:
-                # passes: triples share no block, so a group's blocks are the sum of its triples' own
-                groups, count = [[]], 0
-                for ijk in todo:
-                    own = len(set(orders(*ijk)))
-                    if groups[-1] and count + own > fit:
-                        groups.append([])
-                        count = 0
-                    groups[-1].append(ijk)
-                    count += own
-                parts = []
-                for group in groups:
-                    where = {}
-                    for ijk in group:
-                        for pqr in orders(*ijk):
-                            where.setdefault(pqr, len(where))
-                    X = torch.empty((len(where), nv, nv, nv), dtype=dt, device=dev)
-                    for (p, q, r), x in where.items():
-                        kernels.gemm_raw(dt, tp, Vp, X, nv, v2, nv, nv, v2, v2, a_off=(q * n + p) * v2, b_off=r * v3, c_off=x * v3)
-                        kernels.gemm_raw(dt, th, Hh, X, v2, nv, n, n, nv, nv, accumulate=True,
-                                         a_off=p * v2 * n, b_off=(q * n + r) * n * nv, c_off=x * v3)
-                    parts.append(energies(X, group, where))
-                    del X
-                e = torch.cat(parts)
-            m = torch.tensor([3.0 if (i == j or j == k) else 6.0 for i, j, k in todo], dtype=torch.float64, device=dev)
-            return float((m * e).sum().item())
+                sslots = torch.tensor([[(p, q * n + r) for p, q, r in orders(*ijk)] for ijk in group], dtype=torch.int32,
+                                      device=dev)
+                e = kernels.triples_energy_singles(X, slots, eo3, ev, A, G, sslots)
+            self.triples_passes.append((len(group), X.shape[0], kernels.last_dispatch()))
+            return e
+
+        fit = kernels.triples_budget() // (v3 * t.element_size())
+        if fit >= n ** 3:
+            # every block, X_pqr at (r, q, p): o particle products and o^2 hole products
+            X = torch.empty((n ** 3, nv, nv, nv), dtype=dt, device=dev)
+            for k in range(n):
+                kernels.gemm_raw(dt, tp, Vp, X, n * n * nv, v2, nv, nv, v2, v2, b_off=k * v3, c_off=k * n * n * v3)
+                for j in range(n):
+                    kernels.gemm_raw(dt, th, Hh, X, n * v2, nv, n, n, nv, nv, accumulate=True,
+                                     b_off=(j * n + k) * n * nv, c_off=(k * n + j) * n * v3)
+            e, es = energies(X, todo, {(p, q, r): (r * n + q) * n + p for p in range(n) for q in range(n) for r in range(n)})
+        else:
+            # passes: triples share no block, so a group's blocks are the sum of its triples' own
+            groups, count = [[]], 0
+            for ijk in todo:
+                own = len(set(orders(*ijk)))
+                if groups[-1] and count + own > fit:
+                    groups.append([])
+                    count = 0
+                groups[-1].append(ijk)
+                count += own
+            parts = []
+            for group in groups:
+                where = {}
+                for ijk in group:
+                    for pqr in orders(*ijk):
+                        where.setdefault(pqr, len(where))
+                X = torch.empty((len(where), nv, nv, nv), dtype=dt, device=dev)
+                for (p, q, r), x in where.items():
+                    kernels.gemm_raw(dt, tp, Vp, X, nv, v2, nv, nv, v2, v2, a_off=(q * n + p) * v2, b_off=r * v3, c_off=x * v3)
+                    kernels.gemm_raw(dt, th, Hh, X, v2, nv, n, n, nv, nv, accumulate=True,
+                                     a_off=p * v2 * n, b_off=(q * n + r) * n * nv, c_off=x * v3)
+                parts.append(energies(X, group, where))
+                del X
+            e = torch.cat([part[0] for part in parts])
+            es = None if t1 is None else torch.cat([part[1] for part in parts])
+        return todo, e, es
+
+
+class RCCSD(RCCD):
+    """Closed-shell coupled-cluster singles and doubles on a ``SpatialOrbitalSystem``, with the perturbative triples
+    (T): ``RCCD`` on the T1-dressed Hamiltonian.  Constructor, checks and conventions are those of
+    ``RCCD``; amplitudes ``t1`` (v, o) and ``t`` (v, v, o, o).  With ``tau`` (l, l) zero except ``tau[virt, occ] = t1``,
+
+        h~ = (1 - tau) h (1 + tau),      <pq|rs>~ = (1 - tau) (1 - tau) <..|..> (1 + tau) (1 + tau)
+
+    (bras ``1 - tau``, kets ``1 + tau``; ``t1`` is never conjugated), ``f~ = h~ + 2 J~ - K~`` of the occupied orbitals and
+    ``tt = 2 t - t.transpose(0, 1)``:
+
+        R2       = the residual of RCCD on f~ and <..|..>~
+        R1[a,i]  = f~[a,i] + sum_kc f~[k,c] tt[a,c,i,k] + sum_kcd <ak|cd>~ tt[c,d,i,k] - sum_klc <kl|ic>~ tt[a,c,k,l]
+        E_corr   = 2 sum f[i,a] t1[a,i] + sum (2<ij|ab> - <ij|ba>) (t[a,b,i,j] + t1[a,i] t1[b,j])
+
+    The dressing keeps the particle-exchange symmetry of ``u`` and gives up hermiticity, which the equations of RCCD
+    never use.  Only two coefficient blocks change: the bra-virtual rows ``Xvh = Cv^H - t1 Co^H`` and the ket-occupied
+    columns ``Yo = Co + Cv t1``.  One iteration is still ONE pass over half of ``u``:
+
+        tau[k = (i <= j)] = Cv t[:, :, i, j] Cv^T + Yo[:, i] Yo[:, j]^T       (the driver <ab|ij>~ rides in the ladder)
+        S = pair_contract_exchange(u, tau)
+        B S[k] B^T,  B = [Co^H; Xvh]:   vv = <ab|ij>~ + sum_cd <ab|cd>~ t,   oo = <kl|ij>~ + sum_cd <kl|cd> t,
+                                        vo and ov = <ak|ij>~ + sum_cd <ak|cd>~ t  at (i, j) and (j, i)
+
+    and ``sum_k (2 vo_ik - vo_ki)[a,k]`` is the ``<ak|cd>~ tt`` term of ``R1`` TOGETHER WITH the mean-field part of
+    ``f~[a,i]``, so ``R1`` starts from ``h~[a,i]``.  The small dressed blocks ovvo~, ovov~ and ooov~ come every iteration
+    from ``transform_two_body_blocks`` with the dressed matrices (three more block passes over ``u`` per iteration);
+    oovv is undressed and static; ``f~`` is ``kernels.mean_field(u, 2 Yo Co^H)`` between ``B`` and ``[Yo, Cv]``.  With
+    ``C=None`` the same code runs on the unit matrix.
+
+    ``solve`` iterates ``t1 += R1 / (e_i - e_a)``, ``t += R2 / D`` from ``f_ai / (e_i - e_a)`` and the first-order
+    doubles until the norm of ``(R1, R2)`` together is below ``tol``.  ``triples()`` is E_(T): the connected part
+    ``E_[T]`` of ``RCCD.triples`` and the singles part ``E_ST`` from one launch of ``kernels.triples_energy_singles``
+    (``triples_parts``); canonical orbitals only."""
+
+    def __init__(self, system, C=None, epsilon=None, ladder="exchange"):
+        # RCCD's checks, Fock blocks, denominators and static blocks: vvoo (the start, and G of the triples), oovv and L are
+        # used as they are; oooo, ovvo and ovov are dressed anew in every iteration and RCCD's copies stay unused
+        super().__init__(system, C, epsilon, ladder)
+        with torch._C.DisableTorchFunctionSubclass():
+            n, l = self.n, self.l
+            if self._Co is None:                       # the system is in the orbital basis: the unit matrix
+                one = torch.eye(l, dtype=self._dt, device=self._u.device)
+                self._Co, self._Cv = one[:, :n].contiguous(), one[:, n:].contiguous()
+                self._Coh, self._Cvh = _dagger(self._Co).contiguous(), _dagger(self._Cv).contiguous()
+            self._cj, self._ck = system._mean_field_weights()
+            eo, ev = self._eps[:n], self._eps[n:]
+            self._D1 = eo[None, :] - ev[:, None]
+            self._t1 = self._fvo / self._D1
+        self.t1 = _deliver(self._t1, system.np)
+        self.triples_parts = None
+
+    def _residuals(self, t1, t):
+        ein = torch.einsum
+        n, l = self.n, self.l
+        u, dt = self._u, self._dt
+        Co, Cv, Coh = self._Co, self._Cv, self._Coh
+        Xvh = self._Cvh - t1 @ Coh                                        # bra-virtual rows
+        Yo = Co + Cv @ t1                                                 # ket-occupied columns
+        B = torch.cat([Coh, Xvh]).contiguous()                            # the bras (l, l): occupied undressed
+        Kt = torch.cat([Yo, Cv], dim=1).contiguous()                      # the kets (l, l): virtual undressed
+        # -- the pass over half of u
+        tk = t[:, :, self._pi, self._pj].permute(2, 0, 1).contiguous()                # (K, v, v)
+        tau = _sandwich(Cv, tk) + ein("pk,qk->kpq", Yo[:, self._pi], Yo[:, self._pj])
+        tau = tau.contiguous()
+        S = (kernels.pair_contract_exchange(u, tau) if self.ladder == "exchange" else kernels.pair_contract(u, tau)).to(dt)
+        Q = _sandwich(B, S)                                               # (K, l, l): B S B^T
+        nv = l - n
+        driver = torch.empty((nv, nv, n, n), dtype=dt, device=t.device)
+        W = torch.empty((n, n, n, n), dtype=dt, device=t.device)
+        M = torch.empty((n, n, nv, n), dtype=dt, device=t.device)        # M[i,j,a,k] = <ak|ij>~ + sum_cd <ak|cd>~ t^{cd}_{ij}
+        # the (j, i) results are the transposes
+        driver[:, :, self._pj, self._pi] = Q[:, n:, n:].permute(2, 1, 0)
+        driver[:, :, self._pi, self._pj] = Q[:, n:, n:].permute(1, 2, 0)
+        W[:, :, self._pj, self._pi] = Q[:, :n, :n].permute(2, 1, 0)
+        W[:, :, self._pi, self._pj] = Q[:, :n, :n].permute(1, 2, 0)
+        M[self._pj, self._pi] = Q[:, :n, n:].transpose(1, 2)
+        M[self._pi, self._pj] = Q[:, n:, :n]
+        # -- the dressed one-body matrices and small blocks
+        rho = (2.0 * (Yo @ Coh)).contiguous()
+        hd = B @ self._h.to(dt) @ Kt
+        fd = hd + B @ kernels.mean_field(u, rho, cj=self._cj, ck=self._ck).to(dt) @ Kt
+        o, v = slice(0, n), slice(n, l)
+
+        def block(b0, b1, k0, k1):
+            return kernels.transform_two_body_blocks(u, b0.contiguous(), b1.contiguous(), k0.contiguous(), k1.contiguous()).to(dt)
+
+        ovvo, ovov, ooov = block(Coh, Xvh, Cv, Yo), block(Coh, Xvh, Yo, Cv), block(Coh, Coh, Yo, Cv)
+        R2 = _closed_shell_doubles(t, driver, W, fd[v, v], fd[o, o], self._oovv, self._L, ovvo, ovov)
+        tt = 2.0 * t - t.transpose(0, 1)
+        R1 = hd[v, o] + 2.0 * ein("ikak->ai", M) - ein("kiak->ai", M)    # f~[a,i] and the <ak|cd>~ tt term
+        R1 = R1 + ein("kc,acik->ai", fd[o, v], tt) - ein("klic,ackl->ai", ooov, tt)
+        return R1, R2
+
+    def _amplitudes(self, t1, t):
+        n, nv = self.n, self.l - self.n
+        t1 = self._t1 if t1 is None else _plain(t1)
+        t = self._t if t is None else _plain(t)
+        if tuple(t1.shape) != (nv, n) or tuple(t.shape) != (nv, nv, n, n):
+            raise ValueError(f"t1 must be (v, o) = {(nv, n)} and t (v, v, o, o) = {(nv, nv, n, n)}, "
+                             f"got {tuple(t1.shape)} and {tuple(t.shape)}")
+        return t1.to(self._dt), t.to(self._dt)
+
+    def residual(self, t1=None, t=None):
+        """``(R1, R2)`` of the amplitudes ``t1`` (v, o) and ``t`` (v, v, o, o) with ``t[a,b,i,j] = t[b,a,j,i]``, by
+        default the current ones: device tensors."""
+        with torch._C.DisableTorchFunctionSubclass():
+            return self._residuals(*self._amplitudes(t1, t))
+
+    def energy(self, t1=None, t=None):
+        """``2 sum f_ia t1 + sum (2<ij|ab> - <ij|ba>) (t + t1 t1)`` of the amplitudes (a float)."""
+        with torch._C.DisableTorchFunctionSubclass():
+            t1, t = self._amplitudes(t1, t)
+            pairs = t.permute(2, 3, 0, 1) + torch.einsum("ai,bj->ijab", t1, t1)
+            e = 2.0 * (self._fov * t1.transpose(0, 1)).sum() + (self._L * pairs).sum()
+            return float(e.real.item())
+
+    def solve(self, tol=1e-8, max_iter=100, mixing=0.0):
+        """Iterate ``t1 <- t1 + R1 / (e_i - e_a)``, ``t <- t + R2 / D`` (``mixing`` of the old amplitudes kept) until the
+        2-norm of ``(R1, R2)`` together is below ``tol``.  Starts from ``f_ai / (e_i - e_a)`` and ``<ab|ij> / D``.
+        Returns the correlation energy; keeps ``t1``, ``t``, ``residuals``, ``converged`` and ``iterations``."""
+        if not 0.0 <= mixing < 1.0:
+            raise ValueError(f"mixing must lie in [0, 1), got {mixing}")
+        with torch._C.DisableTorchFunctionSubclass():
+            t1, t = self._fvo / self._D1, self._vvoo / self._D
+            self.residuals, self.converged, self.iterations = [], False, 0
+            for it in range(1, max_iter + 1):
+                R1, R2 = self._residuals(t1, t)
+                norm = float(torch.hypot(torch.linalg.vector_norm(R1), torch.linalg.vector_norm(R2)).item())
+                self.residuals.append(norm)
+                if norm < tol:
+                    self.converged = True
+                    break
+                self.iterations = it
+                t1 = t1 + (1.0 - mixing) * (R1 / self._D1)
+                t = t + (1.0 - mixing) * (R2 / self._D)
+                t = 0.5 * (t + t.transpose(0, 1).transpose(2, 3))
+            self._t1, self._t = t1, t
+            self.t1 = _deliver(t1.contiguous(), self.system.np)
+            self.t = _deliver(t.contiguous(), self.system.np)
+        return self.energy()
+
+    def triples(self, canonical_tol=1e-8):
+        """E_(T) (a float) on the current amplitudes: ``E_[T] + E_ST``, kept as ``triples_parts``.  ``E_[T]`` is the
+        correction of ``RCCD.triples`` on ``t``; with ``Y_ijk[a,b,c] = 1/2 t1[a,i] <bc|jk>`` and ``V'`` the six-fold
+        permuted sum of ``Y`` that makes ``W`` from ``X``,
+
+            E_ST = sum_{i<=j<=k} m_ijk sum_abc Re(conj(V'_abc) Z_abc) / D
+
+        The blocks ``X`` come from ``t`` and the undressed integrals exactly as in ``RCCD.triples`` (the same budget and
+        passes, ``triples_passes``); ``Y`` is never formed: ``kernels.triples_energy_singles`` reads ``A = 1/2 t1^T`` and
+        ``G[q o + r] = <bc|qr>``.  Canonical orbitals only (``ValueError`` otherwise)."""
+        if is_sharded(self.system.u):
+            raise NotImplementedError("RCCSD.triples does not take a sharded u: pass a system whose u lives on one device")
+        with torch._C.DisableTorchFunctionSubclass():
+            self._require_canonical(canonical_tol)
+            todo, e, es = self._triples_energies(self._t, self._t1)
+            if not todo:
+                self.triples_parts = (0.0, 0.0)
+                return 0.0
+            m = self._triples_weights(todo, self._t.device)
+            self.triples_parts = (float((m * e).sum().item()), float((m * es).sum().item()))
+            return self.triples_parts[0] + self.triples_parts[1]

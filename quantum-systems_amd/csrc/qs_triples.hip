@@ -25,6 +25,13 @@
 // partial per (triple, tile set); triples_close_kernel adds the partials of a triple in a fixed order that depends on the
 // number of tile sets alone.  The bits of e[x] depend on the triple's own blocks, eo3[x], ev and v, on nothing else: not on
 // the batch, not on the run.
+//
+// The singles term of (T) (triples_energy_singles_kernel): a second permuted family V' built like W from blocks that are
+// outer products, Y_beta[p,q,r] = A[sa][p] G[sg][q,r], and never stored: the thread of an orbit reads its 18 elements of A
+// and 36 of G from memory (small, L2-resident; LDS is full), forms the six V' beside the six W and adds
+//   sum_orbit Re(conj(V') Z) = sum_orbit Re(conj(V') W) + Re(conj(S'_e) (S_e - 2 S_o) + conj(S'_o) (S_o - 2 S_e)) / 3
+// into a second partial of the work unit.  Everything else -- work units, load, LDS image, reduction, close -- is shared,
+// and the connected part e[x] is the one of triples_energy_kernel, operation for operation.
 
 #include <cmath>
 
@@ -72,6 +79,14 @@ struct TriplesArgs {
     unsigned nsets;         // nt (nt + 1) (nt + 2) / 6
 };
 
+struct TriplesSingles {
+    const double* A;        // (na, v)
+    const double* G;        // (ng, v, v)
+    const int32_t* sslots;  // (n, 6, 2): (sa, sg) of the six blocks
+    double* part;           // (n, nsets): the singles partials
+    int64_t na, ng;
+};
+
 // first entry of key[0 ... 5] equal to key[s]
 __device__ inline int first_equal(const int64_t (&key)[6], int s) {
     int f = s;
@@ -81,12 +96,13 @@ __device__ inline int first_equal(const int64_t (&key)[6], int s) {
     return f;
 }
 
-template <int W>
-__global__ __launch_bounds__(TriplesGeo<W>::threads) void triples_energy_kernel(const TriplesArgs g) {
+// one work unit; SINGLES adds the singles partial (q is not looked at without it)
+template <int W, bool SINGLES>
+__device__ __forceinline__ void triples_unit(const TriplesArgs& g, const TriplesSingles& q) {
     using G = TriplesGeo<W>;
     constexpr int T = G::T;
     extern __shared__ __align__(16) double tiles[];
-    __shared__ double s_wave[G::threads / 64];
+    __shared__ double s_wave[SINGLES ? 2 : 1][G::threads / 64];
     const int tid = threadIdx.x;
     const unsigned triple = blockIdx.x / g.nsets;
     unsigned rest = blockIdx.x - triple * g.nsets;
@@ -105,8 +121,20 @@ __global__ __launch_bounds__(TriplesGeo<W>::threads) void triples_energy_kernel(
         bkey[s] = g.slots[(int64_t)triple * 6 + s];
         bad = bad || bkey[s] < 0 || bkey[s] >= g.nblocks;
     }
-    if (bad) {          // a block index outside X: nothing is read, the triple's energy is a NaN
-        if (tid == 0) g.part[blockIdx.x] = NAN;
+    int64_t akey[6], gkey[6];
+    if constexpr (SINGLES) {
+#pragma unroll
+        for (int s = 0; s < 6; ++s) {
+            akey[s] = q.sslots[((int64_t)triple * 6 + s) * 2];
+            gkey[s] = q.sslots[((int64_t)triple * 6 + s) * 2 + 1];
+            bad = bad || akey[s] < 0 || akey[s] >= q.na || gkey[s] < 0 || gkey[s] >= q.ng;
+        }
+    }
+    if (bad) {          // a block index outside X (A, G): nothing is read, the triple's energy is a NaN
+        if (tid == 0) {
+            g.part[blockIdx.x] = NAN;
+            if constexpr (SINGLES) q.part[blockIdx.x] = NAN;
+        }
         return;
     }
     int omap[6], bmap[6];
@@ -152,7 +180,7 @@ __global__ __launch_bounds__(TriplesGeo<W>::threads) void triples_energy_kernel(
     // -- the orbit of (a, b, c) = tile set + (lp, lq, lr), a <= b <= c < v
     const int l[3] = {lp, lq, lr};
     const int64_t a = (int64_t)t[0] * T + lp, b = (int64_t)t[1] * T + lq, c = (int64_t)t[2] * T + lr;
-    double mine = 0.0;
+    double mine = 0.0, mine_s = 0.0;
     if (in_cube && a <= b && b <= c && c < v) {
         int off[6];         // where (a, b, c) at order s sits in a tile of order s
 #pragma unroll
@@ -184,19 +212,84 @@ __global__ __launch_bounds__(TriplesGeo<W>::threads) void triples_energy_kernel(
         const double D = ((g.eo3[triple] - g.ev[a]) - g.ev[b]) - g.ev[c];
         const double weight = (a == b && b == c) ? 1.0 / 6.0 : (a == b || b == c) ? 0.5 : 1.0;
         mine = weight * (sq + cross / 3.0) / D;
+        if constexpr (SINGLES) {
+            // V'[pi] = sum_beta Y_beta at order s of (a, b, c): A at the first index of the order, G at the other two
+            const int64_t abc[3] = {a, b, c};
+            double Vv[6][W];
+#pragma unroll
+            for (int pi = 0; pi < 6; ++pi) {
+#pragma unroll
+                for (int w = 0; w < W; ++w) Vv[pi][w] = 0.0;
+            }
+#pragma unroll
+            for (int beta = 0; beta < 6; ++beta) {
+                const double* Ab = q.A + akey[beta] * v * W;
+                const double* Gb = q.G + gkey[beta] * v * v * W;
+                double Av[3][W];
+#pragma unroll
+                for (int x = 0; x < 3; ++x) {
+#pragma unroll
+                    for (int w = 0; w < W; ++w) Av[x][w] = Ab[abc[x] * W + w];
+                }
+#pragma unroll
+                for (int pi = 0; pi < 6; ++pi) {
+                    const int s = order_of_orders(pi, beta);
+                    const double* gs = Gb + (abc[order_at(s, 1)] * v + abc[order_at(s, 2)]) * W;
+                    const double* as = Av[order_at(s, 0)];
+                    if constexpr (W == 1) {
+                        Vv[pi][0] += as[0] * gs[0];
+                    } else {
+                        Vv[pi][0] += as[0] * gs[0] - as[1] * gs[1];
+                        Vv[pi][1] += as[0] * gs[1] + as[1] * gs[0];
+                    }
+                }
+            }
+            double dot = 0.0, mixed = 0.0;
+#pragma unroll
+            for (int w = 0; w < W; ++w) {
+                const double Te = (Vv[0][w] + Vv[3][w]) + Vv[4][w], To = (Vv[1][w] + Vv[2][w]) + Vv[5][w];
+#pragma unroll
+                for (int pi = 0; pi < 6; ++pi) dot = __builtin_fma(Vv[pi][w], Wv[pi][w], dot);
+                mixed += Te * (Se[w] - 2.0 * So[w]) + To * (So[w] - 2.0 * Se[w]);
+            }
+            mine_s = weight * (dot + mixed / 3.0) / D;
+        }
     }
 
     // -- the workgroup's partial: lanes by shuffles, waves in order
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) mine += __shfl_down(mine, d, 64);
-    if ((tid & 63) == 0) s_wave[tid >> 6] = mine;
+    if constexpr (SINGLES) {
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) mine_s += __shfl_down(mine_s, d, 64);
+    }
+    if ((tid & 63) == 0) {
+        s_wave[0][tid >> 6] = mine;
+        if constexpr (SINGLES) s_wave[1][tid >> 6] = mine_s;
+    }
     __syncthreads();
     if (tid == 0) {
-        double sum = s_wave[0];
+        double sum = s_wave[0][0];
 #pragma unroll
-        for (int x = 1; x < G::threads / 64; ++x) sum += s_wave[x];
+        for (int x = 1; x < G::threads / 64; ++x) sum += s_wave[0][x];
         g.part[blockIdx.x] = sum;
+        if constexpr (SINGLES) {
+            double sum_s = s_wave[1][0];
+#pragma unroll
+            for (int x = 1; x < G::threads / 64; ++x) sum_s += s_wave[1][x];
+            q.part[blockIdx.x] = sum_s;
+        }
     }
+}
+
+template <int W>
+__global__ __launch_bounds__(TriplesGeo<W>::threads) void triples_energy_kernel(const TriplesArgs g) {
+    triples_unit<W, false>(g, TriplesSingles{});
+}
+
+template <int W>
+__global__ __launch_bounds__(TriplesGeo<W>::threads) void triples_energy_singles_kernel(const TriplesArgs g, const TriplesSingles q) {
+    triples_unit<W, true>(g, q);
 }
 
 // e[x] = the partials of triple x: thread-strided sums, then a tree, both in a fixed order
@@ -233,6 +326,17 @@ static int launch_triples(const TriplesArgs& g, int64_t n, hipStream_t stream) {
     hipLaunchKernelGGL(kern, dim3((unsigned)(n * g.nsets)), dim3(G::threads), G::lds_bytes, stream, g);
     note_dispatch("qs::triples_energy_kernel<%d>", W);
     return launch_status("triples_energy launch");
+}
+
+template <int W>
+static int launch_triples_singles(const TriplesArgs& g, const TriplesSingles& q, int64_t n, hipStream_t stream) {
+    using G = TriplesGeo<W>;
+    auto kern = triples_energy_singles_kernel<W>;
+    static PerDeviceLds lds_opt_in;
+    if (int rc = opt_in_dynamic_lds((const void*)kern, G::lds_bytes, lds_opt_in, "hipFuncSetAttribute(triples_energy_singles)")) return rc;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(n * g.nsets)), dim3(G::threads), G::lds_bytes, stream, g, q);
+    note_dispatch("qs::triples_energy_singles_kernel<%d>", W);
+    return launch_status("triples_energy_singles launch");
 }
 
 }  // namespace qs
@@ -279,6 +383,52 @@ int qs_triples_energy(int dtype, const void* X, int64_t nblocks, const int32_t* 
     const TriplesArgs g{(const double*)X, slots, eo3, ev, (double*)work, e, v, nblocks, (int)cdiv(v, triples_tile(dtype)),
                         (unsigned)nsets};
     if (int rc = dtype == QS_C128 ? launch_triples<2>(g, n, s) : launch_triples<1>(g, n, s)) return rc;
+    hipLaunchKernelGGL(triples_close_kernel, dim3((unsigned)n), dim3(256), 0, s, g);
+    note_dispatch("qs::triples_close_kernel");
+    return launch_status("triples_close launch");
+}
+
+int64_t qs_triples_energy_singles_workspace(int dtype, int64_t v, int64_t n) {
+    if (!dtype_ok(dtype)) return QS_ERR_BAD_DTYPE;
+    const int64_t nsets = triples_sets(dtype, v, n);
+    if (!nsets) return QS_ERR_BAD_EXTENT;
+    return 2 * n * nsets * (int64_t)sizeof(double);     // the connected and the singles partial of every (triple, tile set)
+}
+
+int qs_triples_energy_singles(int dtype, const void* X, int64_t nblocks, const int32_t* slots, const double* eo3,
+                              const double* ev, const void* A, int64_t na, const void* G, int64_t ng, const int32_t* sslots,
+                              int64_t v, int64_t n, double* e, double* es_out, void* work, int64_t work_bytes, void* stream) {
+    dispatch_reset();
+    if (!dtype_ok(dtype)) return QS_ERR_BAD_DTYPE;
+    const int64_t nsets = triples_sets(dtype, v, n);
+    const int64_t es = (int64_t)elem_size(dtype);
+    if (!nsets || nblocks < 1 || nblocks > INT32_MAX || nblocks > INT64_MAX / (v * v * v * es)) return QS_ERR_BAD_EXTENT;
+    if (na < 1 || na > INT32_MAX || ng < 1 || ng > INT32_MAX) return QS_ERR_BAD_EXTENT;     // (v <= 4096: no product overflows)
+    if (!X || !slots || !eo3 || !ev || !A || !G || !sslots || !e || !es_out || !work) return QS_ERR_NULL_POINTER;
+    if (!aligned(X, (size_t)es) || !aligned(slots, 4) || !aligned(eo3, 8) || !aligned(ev, 8) || !aligned(A, (size_t)es) ||
+        !aligned(G, (size_t)es) || !aligned(sslots, 4) || !aligned(e, 8) || !aligned(es_out, 8) || !aligned(work, 8))
+        return QS_ERR_MISALIGNED;
+    const int64_t half = n * nsets * (int64_t)sizeof(double), need = 2 * half;
+    if (work_bytes < need) return QS_ERR_WORKSPACE;
+    const int64_t xbytes = nblocks * v * v * v * es, abytes = na * v * es, gbytes = ng * v * v * es;
+    const struct { const void* p; int64_t bytes; } inputs[] = {{X, xbytes},   {slots, n * 24}, {eo3, n * 8},     {ev, v * 8},
+                                                               {A, abytes}, {G, gbytes},     {sslots, n * 48}};
+    for (const auto& in : inputs)
+        if (overlaps(e, n * 8, in.p, in.bytes) || overlaps(es_out, n * 8, in.p, in.bytes) || overlaps(work, need, in.p, in.bytes))
+            return QS_ERR_ALIAS;
+    if (overlaps(e, n * 8, work, need) || overlaps(es_out, n * 8, work, need) || overlaps(e, n * 8, es_out, n * 8)) return QS_ERR_ALIAS;
+
+    hipStream_t s = (hipStream_t)stream;
+    TriplesArgs g{(const double*)X, slots, eo3, ev, (double*)work, e, v, nblocks, (int)cdiv(v, triples_tile(dtype)),
+                  (unsigned)nsets};
+    const TriplesSingles q{(const double*)A, (const double*)G, sslots, (double*)work + n * nsets, na, ng};
+    if (int rc = dtype == QS_C128 ? launch_triples_singles<2>(g, q, n, s) : launch_triples_singles<1>(g, q, n, s)) return rc;
+    // the close, once per output: the connected partials into e, the singles partials into es
+    hipLaunchKernelGGL(triples_close_kernel, dim3((unsigned)n), dim3(256), 0, s, g);
+    note_dispatch("qs::triples_close_kernel");
+    if (int rc = launch_status("triples_close launch")) return rc;
+    g.part = q.part;
+    g.e = es_out;
     hipLaunchKernelGGL(triples_close_kernel, dim3((unsigned)n), dim3(256), 0, s, g);
     note_dispatch("qs::triples_close_kernel");
     return launch_status("triples_close launch");

@@ -203,3 +203,19 @@ class HartreeFock:
                 "the system is in its Hartree-Fock basis already (change_system_basis): C no longer refers to it -- "
                 f"call coupled_cluster.{cls.__name__}(system)")
         return cls(self.system, self.C, self.epsilon, **kw)
+
+    def ccsd(self, **kw):
+        """Closed-shell coupled-cluster singles and doubles on the converged orbitals:
+        ``coupled_cluster.RCCSD(system, C, epsilon, **kw)``, whose ``triples()`` is (T).  Spatial systems only."""
+        from .coupled_cluster import RCCSD
+        from .spatial_orbital_system import SpatialOrbitalSystem
+
+        if not isinstance(self.system, SpatialOrbitalSystem):
+            raise TypeError("ccsd() needs a SpatialOrbitalSystem: coupled_cluster.RCCSD is the closed-shell method")
+        if self.C is None:
+            raise RuntimeError("run scf() first")
+        if self._basis_changed:
+            raise RuntimeError(
+                "the system is in its Hartree-Fock basis already (change_system_basis): C no longer refers to it -- "
+                "call coupled_cluster.RCCSD(system)")
+        return RCCSD(self.system, self.C, self.epsilon, **kw)

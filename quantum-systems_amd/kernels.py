@@ -1734,6 +1734,64 @@ def triples_energy(X, slots, eo3, ev, out=None):
     return out
 
 
+@_plain
+def triples_energy_singles(X, slots, eo3, ev, A, G, sslots, out=None):
+    """``(e, es)``: ``e`` as ``triples_energy`` and, beside it in the same read of the blocks, the singles part of (T)
+    (``qs_triples_energy_singles``)
+
+        es[x] = sum_abc Re(conj(V'[abc]) Z[abc]) / (eo3[x] - ev[a] - ev[b] - ev[c])
+
+    with ``V'`` made like ``W`` from the outer products ``Y_beta[p,q,r] = A[sa][p] G[sg][q,r]``, ``(sa, sg) =
+    sslots[x, beta]``, which are never stored.  ``A`` (na, v) and ``G`` (ng, v, v) in the dtype of ``X``; ``sslots``
+    (n, 6, 2) int32 with ``sa`` in ``0 ... na - 1`` and ``sg`` in ``0 ... ng - 1``.  ``out``: a pair of (n,) float64
+    tensors.  The same bits on every run and for a triple alone or in a batch."""
+    lib = _lib.load()
+    if not isinstance(X, torch.Tensor) or X.dtype not in (_F64, _C128):
+        raise TypeError("X must be a float64 or complex128 tensor")
+    if X.dim() != 4 or X.shape[0] < 1 or X.shape[1] < 1 or not X.shape[1] == X.shape[2] == X.shape[3]:
+        raise ValueError(f"X must be (nblocks, v, v, v), got {tuple(X.shape)}")
+    dt, (nblocks, v) = X.dtype, X.shape[:2]
+    if not isinstance(slots, torch.Tensor) or slots.dtype != torch.int32 or slots.dim() != 2 or slots.shape[1] != 6 or slots.shape[0] < 1:
+        raise ValueError("slots must be an (n, 6) int32 tensor of block indices")
+    n = slots.shape[0]
+    for name, arr, length in (("eo3", eo3, n), ("ev", ev, v)):
+        if not isinstance(arr, torch.Tensor) or arr.dtype != _F64 or tuple(arr.shape) != (length,):
+            raise ValueError(f"{name} must be a float64 tensor of shape ({length},)")
+    if not isinstance(A, torch.Tensor) or A.dtype != dt or A.dim() != 2 or A.shape[0] < 1 or A.shape[1] != v:
+        raise ValueError(f"A must be an (na, {v}) tensor of the dtype of X")
+    if not isinstance(G, torch.Tensor) or G.dtype != dt or G.dim() != 3 or G.shape[0] < 1 or tuple(G.shape[1:]) != (v, v):
+        raise ValueError(f"G must be an (ng, {v}, {v}) tensor of the dtype of X")
+    if not isinstance(sslots, torch.Tensor) or sslots.dtype != torch.int32 or tuple(sslots.shape) != (n, 6, 2):
+        raise ValueError(f"sslots must be an ({n}, 6, 2) int32 tensor of (A row, G block) indices")
+    na, ng = A.shape[0], G.shape[0]
+    X, slots, eo3, ev, A, G, sslots = _dev(X), _dev(slots), _dev(eo3), _dev(ev), _dev(A), _dev(G), _dev(sslots)
+    # the three ranges in one trip to the host
+    tables = (("slots", slots, nblocks), ("sslots[..., 0]", sslots[..., 0], na), ("sslots[..., 1]", sslots[..., 1], ng))
+    ends = torch.stack([torch.stack(table.aminmax()) for _, table, _ in tables]).tolist()
+    for (name, _, top), (lo, hi) in zip(tables, ends):
+        if lo < 0 or hi >= top:
+            raise ValueError(f"{name} must lie in 0 ... {top - 1}, got {lo} ... {hi}")
+    code = dtype_code(dt)
+    nbytes = check(lib.qs_triples_energy_singles_workspace(code, v, n), "workspace query")
+    if out is None:
+        e, es = torch.empty(n, dtype=_F64, device=X.device), torch.empty(n, dtype=_F64, device=X.device)
+    else:
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise ValueError("out must be a pair (e, es) of tensors")
+        e, es = out
+        _check_out(e, (n,), _F64, "triples_energy_singles")
+        _check_out(es, (n,), _F64, "triples_energy_singles")
+    with _on_device_of(X, slots, eo3, ev, A, G, sslots, e, es):
+        work = workspace.get(nbytes, X.device)
+        _ran(
+            lib.qs_triples_energy_singles(code, X.data_ptr(), nblocks, slots.data_ptr(), eo3.data_ptr(), ev.data_ptr(),
+                                          A.data_ptr(), na, G.data_ptr(), ng, sslots.data_ptr(), v, n, e.data_ptr(),
+                                          es.data_ptr(), work.data_ptr(), work.numel(), _stream()),
+            "qs_triples_energy_singles",
+        )
+    return e, es
+
+
 class RcclComm:
     """The C ABI's communicator (``qs_comm_init``: RCCL over xGMI, one process per GPU) for hosts that drive the
     library from Python without ``torch.distributed``.  ``unique_id()`` on one rank, the 128 bytes to the others by

@@ -2,12 +2,17 @@
 them, a torch restatement of the same reduction on the same blocks, and a whole ``RCCD.triples`` call.
 
     python tools/triples_bench.py [--out FILE] [--reps N] [--v 64,128,250] [--whole 64:3,128:3,250:3] [--dtype fp64]
+    python tools/triples_bench.py --singles [--v 250] [--dtype fp64]      (and --v 120 --dtype complex128)
 
   products  the six particle and six hole products of ONE triple (``kernels.gemm_raw``, as a pass of ``RCCD.triples``)
   kernel    ONE call of ``kernels.triples_energy`` over n triples of six distinct blocks each, n so that the blocks
             exceed the last-level cache (about 1.5 GB); per triple = the call's time / n
   torch     the same reduction in torch ops on the same blocks: six permuted adds for W, the combination Z, the
             product, the division and the sum, triple by triple
+  singles   (``--singles``, instead of the parts above) ``kernels.triples_energy_singles`` against ``kernels.triples_energy``
+            on the SAME blocks and slots, alternating in one process; ``A`` (o, v), ``G`` (o^2, v, v) and the ``sslots`` of
+            random occupied triples.  The yardstick: the baseline plus the time of one more read of the blocks at the
+            rate the baseline reads them
 "of copy" is the ``6 v^3`` elements the kernel has to read per triple over its time, against the rate of
 ``qs_probe_stream_copy`` (read + write counted) measured in the same run.  The whole call builds ``coupled_cluster.RCCD``
 on a random closed-shell system of v + o canonical orbitals and times ``triples()`` on its first-order amplitudes; the
@@ -82,6 +87,45 @@ def run_parts(v, o, dt, reps, roof, emit):
     return m_k
 
 
+def run_singles(v, o, dt, reps, roof, emit):
+    """The singles kernel against the plain one on the same blocks: alternating calls, so that both see the same machine."""
+    es = 16 if dt == torch.complex128 else 8
+    block = v ** 3 * es
+    n = max(1, -(-1500000000 // (6 * block)))
+    X = fill((6 * n, v, v, v), dt, 1)
+    slots = torch.arange(6 * n, dtype=torch.int32, device="cuda").reshape(n, 6)
+    ev = torch.arange(v, dtype=torch.float64, device="cuda") * 0.5 + 1.0
+    eo3 = -3.0 - torch.rand(n, dtype=torch.float64, device="cuda")
+    A, G = fill((o, v), dt, 7), fill((o * o, v, v), dt, 8)
+    gen = torch.Generator(device="cpu").manual_seed(9)
+    ijk = torch.randint(0, o, (n, 3), generator=gen)
+    orders = ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0))
+    sslots = torch.stack([torch.stack([ijk[:, p], ijk[:, q] * o + ijk[:, r]], dim=1) for p, q, r in orders], dim=1)
+    sslots = sslots.to(torch.int32).cuda().contiguous()
+    plain = lambda: kernels.triples_energy(X, slots, eo3, ev)                              # noqa: E731
+    singles = lambda: kernels.triples_energy_singles(X, slots, eo3, ev, A, G, sslots)      # noqa: E731
+    for _ in range(2):
+        e0, (e1, es1) = plain(), singles()
+    names = kernels.last_dispatch()
+    torch.cuda.synchronize()
+    t_p, t_s = [], []
+    for _ in range(reps):
+        t_p.append(timed(plain)[0])
+        t_s.append(timed(singles)[0])
+    same = bool((e0 == e1).all())
+    m_p, m_s = statistics.median(t_p) / n, statistics.median(t_s) / n
+    rate_p, rate_s = 6 * block / (m_p * 1e-3) / 1e9, 6 * block / (m_s * 1e-3) / 1e9
+    emit(f"v={v} o={o} {str(dt).split('.')[-1]}: {n} triples of 6 blocks ({6 * block / 1e6:.1f} MB per triple), A {tuple(A.shape)}, "
+         f"G {tuple(G.shape)} ({G.numel() * es / 1e6:.2f} MB)  [{names}]")
+    emit(f"  baseline {stats(t_p)} per call, {m_p:9.4f} ms per triple: {rate_p:7.1f} GB/s read ({rate_p / roof:.2f} of copy)")
+    emit(f"  singles  {stats(t_s)} per call, {m_s:9.4f} ms per triple: {rate_s:7.1f} GB/s read ({rate_s / roof:.2f} of copy)")
+    emit(f"  singles / baseline = {m_s / m_p:.3f} (baseline + one more read of X at the baseline's rate = 2.000); "
+         f"e equal bit for bit: {same}; sum es = {float(es1.sum()):.6e}")
+    del X, A, G
+    torch.cuda.empty_cache()
+    return m_s / m_p
+
+
 def run_whole(v, o, reps, per_triple, emit):
     import numpy as np
 
@@ -117,6 +161,7 @@ def main():
     ap.add_argument("--o", type=int, default=3)
     ap.add_argument("--whole", default="64:3,128:3,250:3")
     ap.add_argument("--dtype", default="fp64", choices=["fp64", "complex128"])
+    ap.add_argument("--singles", action="store_true", help="time kernels.triples_energy_singles against kernels.triples_energy")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("triples_bench needs a GPU: timings are not taken on a CPU")
@@ -132,6 +177,10 @@ def main():
     emit(f"# triples_bench: {torch.cuda.get_device_name(0)}, reps {args.reps}, HIP events, median [min, max]")
     roof = copy_rate(args.reps)
     emit(f"# qs_probe_stream_copy on 2 GiB: {roof:.1f} GB/s read + write")
+    if args.singles:
+        for v in (int(x) for x in filter(None, args.v.split(","))):
+            run_singles(v, args.o, dt, args.reps, roof, emit)
+        return
     per_triple = {}
     for v in (int(x) for x in filter(None, args.v.split(","))):
         per_triple[v] = run_parts(v, args.o, dt, args.reps, roof, emit)
