@@ -115,6 +115,31 @@ int qs_matmul_pairs_mirrored(int dtype, const void* A, const void* B, void* out,
                              int64_t stride_c, int accumulate, void* stream);
 
 /*
+ * The product on a COLUMN TRIANGLE: the n = stack * side * side columns of B
+ * and out are a stack of row-major side x side matrices (c, d), and only the
+ * column blocks that meet d >= c are computed.  A tile's 128 columns are R
+ * rows c of S contiguous columns d (S = 16 and R = 8; the tuning key
+ * "gemm_upper_s" = 32 gives S = 32 and R = 4), and a tile exists iff its last
+ * column >= its first row: 272 of the 512 tiles of a 256 x 256 matrix.
+ * Elements with d < c inside such a block are computed and stored (correct
+ * values); nothing else of B is read and nothing else of out is written.
+ *   out[t] (m x n) = A[t] (m x k) . B[t] (k x n)   on those blocks, t < batch
+ * float64 only, on the exact forms of the tiled kernel: k a multiple of 16, m
+ * of 64, side of S, accumulate == 0 (the argument is there for the shape of
+ * qs_matmul's list; a nonzero value is refused); anything else is refused with
+ * QS_ERR_BAD_EXTENT (complex128 included) before a launch -- no fallback.  The
+ * dispatch record names the launch
+ * "qs::gemm_fast_kernel<false, 4, 4, true, false>(qs::FastUpperArgs)" (m a
+ * multiple of 128) or "<false, 2, 4, true, false>".  Every computed element
+ * has the bits qs_matmul gives it.  (An addition: the ABI version stays 4.)
+ */
+int qs_matmul_upper(int dtype, const void* A, const void* B, void* out,
+                    int64_t m, int64_t side, int64_t stack, int64_t k,
+                    int64_t lda, int64_t ldb, int64_t ldc,
+                    int64_t batch, int64_t stride_a, int64_t stride_b,
+                    int64_t stride_c, int accumulate, void* stream);
+
+/*
  * Host only: pair number t (0 <= t < n (n + 1) / 2) of that order -> (*i, *j),
  * by the same remap the kernels use.  QS_ERR_BAD_EXTENT for n <= 0 or t out
  * of range.
@@ -218,6 +243,16 @@ int qs_transform_two_body_inplace(int dtype, void* u, const void* C,
  *     the pairs q >= p; nothing is written at q < p.  L, M <= 4096 and a grid
  *     below 2^31 workgroups (else QS_ERR_BAD_EXTENT); src and dst must not
  *     overlap (QS_ERR_ALIAS).
+ *   qs_transform_two_body_exchange_leading_upper: 1 where the exchange entries
+ *     would contract the leading indices of (dtype, L, M) as two
+ *     qs_matmul_upper products and one qs_exchange_mirror_lower under the
+ *     calling thread's tuning keys ("exchange_order", "exchange_upper",
+ *     "exchange_leading"), else 0; qs_transform_two_body_exchange_leading_pairs
+ *     answers 0 wherever this answers 1.  Launches nothing.
+ *   qs_exchange_mirror_lower: in place on t (n,n,m,m), float64,
+ *     t[i,j][r,s] = t[j,i][s,r] for every pair i <= j (the diagonal pairs
+ *     included) and every s < r; nothing else is written.  The fill after the
+ *     two products of "exchange_upper".
  */
 int qs_two_body_exchange_symmetric(int dtype, const void* u, int64_t L,
                                    void* scratch, void* stream);
@@ -233,6 +268,9 @@ int qs_transform_two_body_exchange_wanted(int dtype, int64_t L, int64_t M);
 int qs_exchange_mirror(int dtype, void* t, int64_t n, int64_t m, int64_t block,
                        void* stream);
 int qs_transform_two_body_exchange_leading_pairs(int dtype, int64_t L, int64_t M);
+int qs_transform_two_body_exchange_leading_upper(int dtype, int64_t L, int64_t M);
+int qs_exchange_mirror_lower(int dtype, void* t, int64_t n, int64_t m,
+                             void* stream);
 int qs_exchange_pair_transpose(int dtype, const void* src, void* dst, int64_t L,
                                void* stream);
 int qs_exchange_pair_transpose_back(int dtype, const void* src, void* dst,
@@ -616,7 +654,22 @@ const char* qs_last_dispatch(void);
  *     not fit, 2 gives the very launches of 0.  1, the default = 2 from the
  *     smallest size measured to gain, never below the route's own
  *     thresholds, else 0.  b runs before a: 0 and 2 agree to rounding, not
- *     bit for bit; outside 0 ... 2: QS_ERR_BAD_EXTENT).
+ *     bit for bit; outside 0 ... 2: QS_ERR_BAD_EXTENT),
+ *     "exchange_upper" (order 2's leading indices with the triangle on the
+ *     COLUMNS of the products instead of on their batch: b and a as two
+ *     qs_matmul_upper products on the column blocks d >= c of u's trailing
+ *     indices, for all leading indices, then qs_exchange_mirror_lower fills
+ *     the triangles d < c of the pairs q >= p -- 1.06 products' worth of
+ *     matrix work and one pass over a quarter of a tensor, no pair movers;
+ *     also for M < L and in place.  float64 only.  0 = never; 2 = wherever
+ *     qs_matmul_upper takes both products (L a multiple of 16, M of 64);
+ *     1, the default = 2 where M >= L from the smallest size measured to gain
+ *     (192 orbitals, the route's own threshold), and only while
+ *     "exchange_leading" is at its own default: an explicit 0 or 2 there keeps
+ *     exactly those launches.  Agrees with the other forms to rounding;
+ *     outside 0 ... 2: QS_ERR_BAD_EXTENT),
+ *     "gemm_upper_s" (the segment length S of qs_matmul_upper's tiles: 16 or
+ *     32, 0 = the shipped choice, 16; anything else: QS_ERR_BAD_EXTENT).
  *   qs_probe_mfma_f64: register-resident fp64 MFMA loop, `blocks` workgroups
  *     of 4 waves, each wave issuing iters*8 v_mfma_f64_16x16x4_f64
  *     (flops = blocks*4*iters*8*2048); `sink` is a device scratch of

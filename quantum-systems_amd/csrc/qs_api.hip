@@ -275,6 +275,16 @@ int qs_tuning_set(const char* key, int64_t value) {
         g_tune.exchange_leading = (int)value;
         return QS_OK;
     }
+    if (!strcmp(key, "exchange_upper")) {
+        if (value < 0 || value > 2) return QS_ERR_BAD_EXTENT;
+        g_tune.exchange_upper = (int)value;
+        return QS_OK;
+    }
+    if (!strcmp(key, "gemm_upper_s")) {
+        if (value != 0 && value != 16 && value != 32) return QS_ERR_BAD_EXTENT;
+        g_tune.gemm_upper_s = (int)value;
+        return QS_OK;
+    }
     if (!strcmp(key, "mean_field_batch_g")) {
         if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8) return QS_ERR_BAD_EXTENT;
         g_tune.mean_field_batch_g = (int)value;
@@ -347,6 +357,22 @@ int qs_matmul_pairs_mirrored(int dtype, const void* A, const void* B, void* out,
                              int64_t lda, int64_t ldb, int64_t ldc, int64_t grid_n, int64_t stride_a,
                              int64_t stride_b, int64_t stride_c, int accumulate, void* stream) {
     return matmul_pairs(dtype, A, B, out, m, n, k, lda, ldb, ldc, grid_n, stride_a, stride_b, stride_c, accumulate, stream, true);
+}
+
+int qs_matmul_upper(int dtype, const void* A, const void* B, void* out, int64_t m, int64_t side, int64_t stack, int64_t k,
+                    int64_t lda, int64_t ldb, int64_t ldc, int64_t batch, int64_t stride_a, int64_t stride_b,
+                    int64_t stride_c, int accumulate, void* stream) {
+    dispatch_reset();
+    if (!dtype_ok(dtype)) return QS_ERR_BAD_DTYPE;
+    if (!A || !B || !out) return QS_ERR_NULL_POINTER;
+    const size_t es = elem_size(dtype);
+    if (!aligned(A, es) || !aligned(B, es) || !aligned(out, es)) return QS_ERR_MISALIGNED;
+    if (stride_a < 0 || stride_b < 0 || stride_c < 0) return QS_ERR_BAD_EXTENT;
+    if (side <= 0 || side > 65535 || stack <= 0 || stack > INT32_MAX / (side * side)) return QS_ERR_BAD_EXTENT;
+    Product p{dtype, (const double*)A, (const double*)B, (double*)out, m, stack * side * side, k, lda, ldb, ldc, batch,
+              stride_a, stride_b, stride_c, accumulate};
+    p.upper = side;
+    return gemm(p, (hipStream_t)stream);
 }
 
 int qs_triangle_pair(int64_t n, int64_t t, int64_t* i, int64_t* j) {
@@ -543,11 +569,52 @@ static bool exchange_leading_first(int dtype, int64_t L, int64_t M) {
 // (fp64: 192 level, 224 loses 0.7 ms of 62; 240, 256, 288 and 320 gain 5.6, 5.9, 10.6 and 8.9 ms = 3-6.5 %; complex128 gains 7.5-16 % from 160 to 256)
 static constexpr int64_t kExchangeLeadingMin = 240, kExchangeLeadingMinC128 = 160;
 
+static bool exchange_leading_upper(int dtype, int64_t L, int64_t M);
+
 static bool exchange_leading_pairs(int dtype, int64_t L, int64_t M) {
+    if (exchange_leading_upper(dtype, L, M)) return false;
     if (g_tune.exchange_leading == 0 || M < L || !exchange_pair_grids_fit(dtype, L, M)) return false;
     if (g_tune.exchange_leading == 2) return true;
     const bool c128 = dtype == QS_C128;
     return L >= (c128 ? kExchangeMinC128 : kExchangeMin) && L >= (c128 ? kExchangeLeadingMinC128 : kExchangeLeadingMin);
+}
+
+// g_tune.exchange_upper: the leading indices with the triangle on the COLUMNS of the products' tile lists instead of on their
+// batch index (Product::upper): every operand stays in its natural layout, so there is no way in and no way back --
+//   b':   Z[a][q][c,d]  = Ct[q,b] u[a][b][c,d]     m = M (q), k = L (b, ldb = L^2), columns (c, d), batch a
+//   a':   X2[p][q][c,d] = Ct[p,a] Z[a][q][c,d]     m = M (p), k = L (a, ldb = M L^2), columns (q, c, d)
+//         ... both on the column blocks that meet d >= c only, for ALL (a | q) and ALL (p, q)
+//   fill: X2[p,q][c,d]  = X2[q,p][d,c]             p <= q, d < c (the lower triangles of the pairs d and c read)
+// Z (L, M, L, L) goes where X1 goes, X2 where it goes now; also for M < L and in place.
+// 2 = wherever gemm_upper() takes both products and the fill's grid fits, 0 = never, 1 = where it measured faster, and only
+// while exchange_leading is at its own automatic value (an explicit 0 or 2 there keeps exactly those launches).
+// (fp64, L == M, profiles/exchange_upper_ab.txt: 192 gains 3.3 ms of 26.7 against the closing blocks, 256 8.0 ms of 89.0 and
+// 320 33.2 ms of 296.4 against the pairs between two transposes: every eligible size measured, from the route's own threshold)
+static constexpr int64_t kExchangeUpperMin = 192;
+
+// the two products of a (L -> M) transform as gemm() would get them
+static Product exchange_upper_b(const void* Ct, const void* src, void* mid, int64_t L, int64_t M) {
+    Product p{QS_F64, (const double*)Ct, (const double*)src, (double*)mid, M, L * L, L, L, L * L, L * L, L, 0, L * L * L, M * L * L, 0};
+    p.upper = L;
+    return p;
+}
+
+static Product exchange_upper_a(const void* Ct, const void* mid, void* dst, int64_t L, int64_t M) {
+    Product p{QS_F64, (const double*)Ct, (const double*)mid, (double*)dst, M, M * L * L, L, L, M * L * L, M * L * L, 1, 0, 0, 0, 0};
+    p.upper = L;
+    return p;
+}
+
+static bool exchange_leading_upper(int dtype, int64_t L, int64_t M) {
+    if (g_tune.exchange_upper == 0 || dtype != QS_F64 || !exchange_mirror_lower_fits(M, L)) return false;
+    // (16-byte aligned stand-ins for the buffers: the conditions on the extents are what is asked here)
+    const double* al = reinterpret_cast<const double*>(uintptr_t(256));
+    if (!gemm_upper(exchange_upper_b(al, al, const_cast<double*>(al), L, M)) ||
+        !gemm_upper(exchange_upper_a(al, al, const_cast<double*>(al), L, M)))
+        return false;
+    if (g_tune.exchange_upper == 2) return true;
+    // (M < L, reached under a forced order only, was not measured)
+    return g_tune.exchange_leading == 1 && M >= L && L >= kExchangeMin && L >= kExchangeUpperMin;
 }
 
 // T1, T2, X: the three buffers of the comment above.  The a, b, d, c order keeps X1 where X goes, X2 where T2 goes and Y
@@ -562,6 +629,9 @@ static int transform_two_body_exchange_route(int dtype, const void* u, const voi
     const int64_t blk_d = g_tune.exchange_block_d > 0 ? g_tune.exchange_block_d : (blk < 16 ? blk : 16);
     auto cat = [&](const void* base, int64_t elems) { return (const double*)((const char*)base + (size_t)elems * es); };
     auto mat = [&](void* base, int64_t elems) { return (double*)at(base, elems, es); };
+    // (asked again with the buffers themselves: their alignment is one of the product's conditions)
+    const bool leading_upper = exchange_leading_first(dtype, L, M) && exchange_leading_upper(dtype, L, M) &&
+                               gemm_upper(exchange_upper_b(Ct, u, X, L, M)) && gemm_upper(exchange_upper_a(Ct, X, T2, L, M));
     const bool leading_pairs = exchange_leading_first(dtype, L, M) && exchange_leading_pairs(dtype, L, M);
     int rc = leading_pairs ? QS_OK : transpose_small(dtype, C, CT, L, M, s);      // (on pairs the slot holds Ct^T first)
     if (rc) return rc;
@@ -624,8 +694,17 @@ static int transform_two_body_exchange_route(int dtype, const void* u, const voi
         }
         return QS_OK;
     };
+    // ... on the column blocks d >= c of W = L L (g_tune.exchange_upper, above): mid (L, M, L, L), dst (M, M, L, L) complete on
+    // the pairs q >= p after the fill
+    auto leading_upper_pass = [&](const void* src, void* mid, void* dst) -> int {
+        if (int rc = gemm(exchange_upper_b(Ct, src, mid, L, M), s)) return rc;
+        if (int rc = gemm(exchange_upper_a(Ct, mid, dst, L, M), s)) return rc;
+        return exchange_mirror_lower(dtype, dst, M, L, s);
+    };
     if (exchange_leading_first(dtype, L, M)) {
-        if (leading_pairs) {
+        if (leading_upper) {
+            rc = leading_upper_pass(u, /*Z*/ X, /*X2*/ T2);
+        } else if (leading_pairs) {
             rc = exchange_pair_transpose(dtype, u, /*Xs*/ X, L, s);
             if (rc) return rc;
             rc = transpose_small(dtype, Ct, CT, M, L, s);
@@ -790,6 +869,19 @@ int qs_exchange_mirror(int dtype, void* t, int64_t n, int64_t m, int64_t block, 
 
 int qs_transform_two_body_exchange_leading_pairs(int dtype, int64_t L, int64_t M) {
     return dtype_ok(dtype) && extents_ok(L, M) && exchange_leading_first(dtype, L, M) && exchange_leading_pairs(dtype, L, M) ? 1 : 0;
+}
+
+int qs_transform_two_body_exchange_leading_upper(int dtype, int64_t L, int64_t M) {
+    return dtype_ok(dtype) && extents_ok(L, M) && exchange_leading_first(dtype, L, M) && exchange_leading_upper(dtype, L, M) ? 1 : 0;
+}
+
+int qs_exchange_mirror_lower(int dtype, void* t, int64_t n, int64_t m, void* stream) {
+    dispatch_reset();
+    if (dtype != QS_F64) return QS_ERR_BAD_DTYPE;                             // (complex128: not built)
+    if (!exchange_mirror_lower_fits(n, m)) return QS_ERR_BAD_EXTENT;          // (n, m in 1 ... 4096 and fewer than 2^31 workgroups)
+    if (!t) return QS_ERR_NULL_POINTER;
+    if (!aligned(t, elem_size(dtype))) return QS_ERR_MISALIGNED;
+    return exchange_mirror_lower(dtype, t, n, m, (hipStream_t)stream);
 }
 
 int qs_exchange_pair_transpose(int dtype, const void* src, void* dst, int64_t L, void* stream) {

@@ -98,6 +98,12 @@ struct Product {
     // ... whose entry (i, j > i) is ALSO stored transposed at entry (j, i): element (r, c) at C + (j n + i) sc + c ldc + r.  Needs
     // pairs, m == n and no accumulate; entries (i, i) are stored once.  Only where gemm_mirrors() says yes.
     bool mirror = false;
+    // Column triangle: upper = s > 0 makes the n columns a stack of n / s^2 row-major s x s matrices (c, d), of which only the
+    // column blocks that meet d >= c are computed: a tile's 128 columns are R rows c of S contiguous columns d (R S = 128),
+    // and a tile exists iff its last column >= its first row.  Elements with d < c inside such a block are computed and
+    // stored; nothing else of B is read and nothing else of C is written.  A plain batch only (no pairs, mirror or
+    // accumulate), s a multiple of S, and only where gemm_upper() says yes.
+    int64_t upper = 0;
     // which operand is the stream that neighbouring tiles should share in L2: a shared (stride-0) A, or a short-and-wide
     // product, streams B (the tiled kernels walk the tiles of one B panel first)
     int group_along_m() const { return ((sa == 0 && batch > 1) || m < n) ? 1 : 0; }
@@ -115,6 +121,14 @@ int gemm(const Product& p, hipStream_t stream);
 // keys?  Only the exact fp64 128 x 128 form of qs_gemm_fast.hip has the mirrored epilogue; gemm() refuses a mirrored product
 // that fails this with QS_ERR_BAD_EXTENT and launches nothing.
 bool gemm_mirrors(const Product& p);
+
+// Does gemm() take this product with its Product::upper under the calling thread's tuning keys?  Only the exact fp64 DMA
+// forms of qs_gemm_fast.hip walk the column triangle (fp64, 16-byte items, k % 16 == 0, m % 64 == 0, s a multiple of the
+// segment length, 32-bit lane offsets); gemm() refuses one that fails this with QS_ERR_BAD_EXTENT and launches nothing.
+bool gemm_upper(const Product& p);
+// Columns d of one segment of such a tile (16 or 32: g_tune.gemm_upper_s, 0 = the shipped choice) and the tiles of one s x s matrix
+int64_t gemm_upper_segment();
+int64_t gemm_upper_tiles(int64_t s);
 
 // The dispatch's own estimate of a product's time on its tiled kernels (the smaller of the general kernel's best shape
 // and qs_gemm_fast.hip's best form, in the latter's units: rounds of the tile list x tile area / relative rate).  For a
@@ -138,6 +152,9 @@ int gemm_d(int in_dtype, int dtype, const void* u, const void* C, void* T1, int6
 int gemm_fast_try(const Product& p, double general_cost, hipStream_t stream);
 // ... and whether that would be the form with the mirrored epilogue (Product::mirror)
 bool gemm_fast_mirrors(const Product& p);
+// ... the column-triangle form (Product::upper): whether the exact DMA forms take it, and its launch
+bool gemm_fast_upper(const Product& p);
+int gemm_fast_upper_launch(const Product& p, hipStream_t stream);
 
 // Small-coefficient streaming product, m, k <= 64 (qs_gemm_stream.hip).
 int gemm_stream_try(const Product& p, hipStream_t stream);
@@ -222,6 +239,10 @@ int exchange_pair_transpose(int dtype, const void* src, void* dst, int64_t l, hi
 int exchange_pair_transpose_back(int dtype, const void* src, void* dst, int64_t l, int64_t m, hipStream_t stream);
 // ... and whether their grids fit (fewer than 2^31 workgroups, at most 65535 along y and z)
 bool exchange_pair_grids_fit(int dtype, int64_t L, int64_t M);
+// In place on t (n, n, m, m): t[i,j][r,s] = t[j,i][s,r] for every pair i <= j and every s < r; nothing else is written
+// (fp64 only).  The fill after the route's column-triangle products.
+int exchange_mirror_lower(int dtype, void* t, int64_t n, int64_t m, hipStream_t stream);
+bool exchange_mirror_lower_fits(int64_t n, int64_t m);
 
 // Tuning knobs (qs_tuning_set / qs_tuning_reset): state of the CALLING THREAD only, so a tuning
 // run or a test cannot change the dispatch of another thread's calls; every thread starts from the
@@ -279,6 +300,10 @@ struct Tuning {
     int exchange_order = 1;      // that route's order of the contractions: 0 = the trailing indices first (d, c on the pairs of u, mirror, a, closing
                                  // blocks, mirror), 2 = the leading ones first (a, closing blocks, d, c on the pairs of the result's grid, ONE
                                  // mirror), 1 = the second where M >= L from the smallest size measured to gain, else the first
+    int gemm_upper_s = 0;        // segment length S of a column-triangle tile (Product::upper): 16 or 32, 0 = the shipped choice
+    int exchange_upper = 1;      // the leading indices of that route's second order as two products on the column blocks d >= c of u's
+                                 // trailing indices and one fill of the other triangles (no pair movers): 0 = never, 2 = wherever
+                                 // gemm_upper() takes both products, 1 = where it measured faster (and only while exchange_leading is 1)
     int exchange_leading = 1;    // the leading indices of that route's second order (exchange_order): 0 = one product and the closing blocks,
                                  // 2 = on the pairs d >= c of u's trailing indices, between two transposes of the pair matrix (M >= L only:
                                  // below that, and where a mover's grid does not fit, the launches of 0), 1 = the second from the smallest

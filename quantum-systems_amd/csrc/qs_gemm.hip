@@ -507,6 +507,7 @@ static double in_fast_units(const Product& p, double cost) { return p.dtype == Q
 // (the strip kernels keep their estimate to themselves: a launch that they would take is costed as the better of the
 // other two here)
 double gemm_cost(const Product& p) {
+    if (p.upper) return gemm_fast_estimate(p, true);      // (only that kernel walks a column triangle)
     const bool vec = f64_vec(p);
     int cfg = 0, fit_cfg = 0;
     const double cost = general_estimate(p, vec, &cfg, &fit_cfg);
@@ -519,6 +520,7 @@ static bool product_ok(const Product& p) {
     if (p.m > INT32_MAX || p.n > INT32_MAX || p.k > INT32_MAX) return false;
     if (p.lda < p.k || p.ldb < p.n || p.ldc < p.n) return false;
     // a triangular batch names every pair of its grid exactly once
+    if (p.upper < 0) return false;
     return p.pairs >= 0 && p.pairs <= kTriangleMax && (!p.pairs || p.batch == p.pairs * (p.pairs + 1) / 2);
 }
 
@@ -528,10 +530,16 @@ bool gemm_mirrors(const Product& p) {
     return dtype_ok(p.dtype) && product_ok(p) && g_tune.gemm_f64_cfg == 0 && gemm_fast_mirrors(p);
 }
 
+// (a forced shape of the general kernel skips the fast kernel, as above)
+bool gemm_upper(const Product& p) {
+    return dtype_ok(p.dtype) && product_ok(p) && p.upper > 0 && g_tune.gemm_f64_cfg == 0 && gemm_fast_upper(p);
+}
+
 int gemm(const Product& p, hipStream_t stream) {
     if (!dtype_ok(p.dtype)) return QS_ERR_BAD_DTYPE;
     if (!product_ok(p)) return QS_ERR_BAD_EXTENT;
     if (p.mirror && !gemm_mirrors(p)) return QS_ERR_BAD_EXTENT;
+    if (p.upper) return gemm_upper(p) ? gemm_fast_upper_launch(p, stream) : QS_ERR_BAD_EXTENT;
     const bool cx = p.dtype == QS_C128;
     const int64_t m = p.m, n = p.n, batch = p.batch;
     GemmArgs g;

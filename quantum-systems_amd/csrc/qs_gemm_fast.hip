@@ -99,6 +99,13 @@ struct FastPairsArgs : FastArgs {
 // for the same reason.  Only what fast_mirror_form() names is ever instantiated.
 struct FastPairsMirrorArgs : FastPairsArgs {};
 
+// ... of a product on the column triangle (Product::upper): the n columns are a stack of side x side matrices, tiles_n counts
+// the tiles that exist (per_matrix of each), and a tile's 128 columns are 128 >> sshift rows of 1 << sshift columns.  A
+// fourth overload, for the same reason; only the exact fp64 DMA forms are instantiated.
+struct FastUpperArgs : FastArgs {
+    unsigned side, per_matrix, sshift;
+};
+
 template <bool CX, int TM, int TN, bool VEC, bool EDGE>
 __global__ __launch_bounds__(256, 2)
 void gemm_fast_kernel(const FastArgs g) {
@@ -124,6 +131,14 @@ void gemm_fast_kernel(const FastPairsMirrorArgs g) {
 }
 
 template <bool CX, int TM, int TN, bool VEC, bool EDGE>
+__global__ __launch_bounds__(256, 2)
+void gemm_fast_kernel(const FastUpperArgs g) {
+#define QS_FAST_PAIRS 3
+#include "qs_gemm_fast_body.h"
+#undef QS_FAST_PAIRS
+}
+
+template <bool CX, int TM, int TN, bool VEC, bool EDGE>
 static int launch_fast(const Product& p, hipStream_t stream) {
     constexpr int KT = CX ? 8 : 16;
     constexpr int NP = CX ? 2 : 1;
@@ -143,7 +158,7 @@ static int launch_fast(const Product& p, hipStream_t stream) {
     g.m = p.m; g.n = (int)p.n; g.k = (int)p.k;
     g.nk = (int)cdiv(p.k, KT);
     g.tiles_m = (int)cdiv(p.m, BM);
-    g.tiles_n = (int)cdiv(p.n, BN);
+    g.tiles_n = p.upper ? (int)((p.n / (p.upper * p.upper)) * gemm_upper_tiles(p.upper)) : (int)cdiv(p.n, BN);
     g.group_along_m = p.group_along_m();
     g.accumulate = p.accumulate ? 1 : 0;
     const int64_t total = (int64_t)g.tiles_m * g.tiles_n * p.batch;
@@ -177,8 +192,25 @@ static int launch_fast(const Product& p, hipStream_t stream) {
     constexpr bool DMA = QS_FAST_DMA && !CX && VEC && !EDGE;     // unpadded A rows (the kernel's kDma)
     const size_t lds = sizeof(double) * 2 * NP * (BM * (CX || DMA ? KT : KT + 2) + KT * (CX ? BN + 16 : BN));
 #endif
-    static PerDeviceLds lds_opt_in[3];   // per instantiation, batch kind and device
+    static PerDeviceLds lds_opt_in[4];   // per instantiation, batch kind and device
     constexpr bool kMirrors = !CX && TM == 4 && TN == 4 && VEC && !EDGE;      // (fast_mirror_form)
+    constexpr bool kUpper = QS_FAST_DMA && !CX && VEC && !EDGE && (TM == 4 || TM == 2) && TN == 4;      // (gemm_fast_upper)
+    if (p.upper) {
+        if constexpr (kUpper) {
+            FastUpperArgs gu;
+            static_cast<FastArgs&>(gu) = g;
+            gu.side = (unsigned)p.upper;
+            gu.per_matrix = (unsigned)gemm_upper_tiles(p.upper);
+            gu.sshift = gemm_upper_segment() == 32 ? 5u : 4u;
+            void (*kern)(const FastUpperArgs) = gemm_fast_kernel<CX, TM, TN, VEC, EDGE>;
+            if (int rc = opt_in_dynamic_lds((const void*)kern, lds, lds_opt_in[3], "hipFuncSetAttribute(gemm_fast)")) return rc;
+            hipLaunchKernelGGL(kern, dim3((unsigned)P), dim3(256), lds, stream, gu);
+            note_dispatch("qs::gemm_fast_kernel<false, %d, 4, true, false>(qs::FastUpperArgs)", TM);
+            return launch_status("gemm_fast launch");
+        } else {
+            return QS_ERR_BAD_EXTENT;      // not reached: gemm() asks gemm_upper() first
+        }
+    }
     if (p.mirror) {
         if constexpr (kMirrors) {
             FastPairsMirrorArgs gm;
@@ -248,12 +280,15 @@ double gemm_fast_estimate(const Product& p, bool even) {
     const int64_t m = p.m, n = p.n, k = p.k, batch = p.batch;
     const double slots = 2.0 * device_cu_count();
     auto whole = [&](int bm, int bn, double w) {
-        const double tiles = (double)(m / bm) * (double)(n / bn) * (double)batch;
+        // (a column triangle: its real tile list)
+        const double tiles_n = p.upper ? (double)((n / (p.upper * p.upper)) * gemm_upper_tiles(p.upper)) : (double)(n / bn);
+        const double tiles = (double)(m / bm) * tiles_n * (double)batch;
         const double rounds = tiles > 8 * slots ? tiles / slots : ceil(tiles / slots);
         return rounds * bm * bn / w;
     };
     // (the exact form against the edge form of the same shape: no guards, no range arithmetic: l = 128 58.4 TFLOP/s against the
     // ~51 the edge form's l = 120 scales to)
+    if (p.upper) return gemm_fast_upper(p) ? (m % 128 == 0 ? whole(128, 128, 1.12) : whole(64, 128, 1.04)) : 1e300;
     if (!cx && even && k % 16 == 0) {
         if (m % 128 == 0 && n % 128 == 0) return whole(128, 128, 1.12);
         if (m % 64 == 0 && n % 128 == 0) return whole(64, 128, 1.04);
@@ -295,6 +330,35 @@ bool gemm_fast_mirrors(const Product& p) {
     const bool even = aligned(p.A, 16) && aligned(p.B, 16) && aligned(p.C, 16) && !(p.lda & 1) && !(p.ldb & 1) &&
                       !(p.ldc & 1) && !(p.sa & 1) && !(p.sb & 1) && !(p.sc & 1) && !(p.n & 1);
     return (even || g_tune.gemm_fast_unaligned != 0) && p.k % 16 == 0 && p.m % 128 == 0;
+}
+
+// Segment length of a column-triangle tile and the tiles of one s x s matrix (s a multiple of it): S x S super-blocks on
+// and above the diagonal, S^2 / 128 tiles each.
+// (shipped: S = 16, 272 of 512 tiles at s = 256 where S = 32 keeps 288)
+int64_t gemm_upper_segment() { return g_tune.gemm_upper_s == 32 ? 32 : 16; }
+
+int64_t gemm_upper_tiles(int64_t s) {
+    const int64_t S = gemm_upper_segment(), ns = s / S;
+    return ns * (ns + 1) / 2 * (S * S / 128);
+}
+
+// Does a product with Product::upper go on the exact fp64 DMA forms (the only ones that walk the column triangle)?  The
+// conditions are those of gemm_fast_try and launch_fast up to those forms, and the form's own.
+bool gemm_fast_upper(const Product& p) {
+    const int64_t s = p.upper, S = gemm_upper_segment();
+    if (!g_tune.gemm_fast || !QS_FAST_DMA || p.dtype != QS_F64 || s <= 0 || p.pairs || p.mirror || p.accumulate) return false;
+    if (s % S || s > 65535 || p.n % (s * s)) return false;
+    if (32 * p.lda * 8 + 256 >= (int64_t(1) << 32)) return false;
+    if ((128 / S) * s * 8 + 256 >= (int64_t(1) << 32)) return false;      // the B lane offset spans the tile's R rows of (c, d)
+    if (p.m >= (int64_t(1) << 31) - 256 || p.n >= (int64_t(1) << 31) - 256 || p.k >= (int64_t(1) << 31) - 256) return false;
+    const bool even = aligned(p.A, 16) && aligned(p.B, 16) && aligned(p.C, 16) && !(p.lda & 1) && !(p.ldb & 1) &&
+                      !(p.ldc & 1) && !(p.sa & 1) && !(p.sb & 1) && !(p.sc & 1);
+    return (even || g_tune.gemm_fast_unaligned != 0) && p.k % 16 == 0 && p.m % 64 == 0;
+}
+
+int gemm_fast_upper_launch(const Product& p, hipStream_t stream) {
+    if (!gemm_fast_upper(p)) return QS_ERR_BAD_EXTENT;
+    return p.m % 128 == 0 ? launch_fast<false, 4, 4, true, false>(p, stream) : launch_fast<false, 2, 4, true, false>(p, stream);
 }
 
 // Returns QS_OK after launching, or 1 when the product does not qualify

@@ -1,6 +1,8 @@
 // Body of gemm_fast_kernel (qs_gemm_fast.hip), included once per overload inside the kernel's braces: `g` is the kernel's
 // argument, QS_FAST_PAIRS says whether it is a FastPairsArgs (triangular batch: the remap in `decode`, nothing else) or, 2, a
-// FastPairsMirrorArgs (the same, and the epilogue of pair (i, j > i) also stores the tile transposed at pair (j, i)).  Text
+// FastPairsMirrorArgs (the same, and the epilogue of pair (i, j > i) also stores the tile transposed at pair (j, i)) or, 3, a
+// FastUpperArgs (the column triangle of Product::upper: the n-tile's decode, the B stage's lane offset and the epilogue's
+// column offsets; exact fp64 DMA forms only).  Text
 // inclusion, not a shared device function: the plain batch's kernels then compile exactly as they did before the
 // triangular batch existed (through a forced-inline function eight of them spilled other scalar registers).
 // No include guard on purpose.
@@ -94,7 +96,19 @@
         }
 #endif
         m0 = __builtin_amdgcn_readfirstlane(mt) * BM;
+#if QS_FAST_PAIRS == 3
+        {
+            // n-tile -> (stack entry e, tile t of its side x side matrix).  S x S super-blocks hold S^2 / 128 tiles of R rows each
+            // and form an upper triangle themselves: super-block sb is the pair (I, J >= I), the tile's first element (I S + sub R, J S).
+            const uint32_t e = (uint32_t)nt / g.per_matrix, t = (uint32_t)nt - e * g.per_matrix;
+            const uint32_t tshift = 2u * g.sshift - 7u, sb = t >> tshift, sub = t & ((1u << tshift) - 1u);
+            const uint32_t ns = g.side >> g.sshift;
+            const uint32_t I = triangle_row(sb, ns), J = I + (sb - triangle_row_start(I, ns));
+            n0 = __builtin_amdgcn_readfirstlane((int)((e * g.side + (I << g.sshift) + sub * (128u >> g.sshift)) * g.side + (J << g.sshift)));
+        }
+#else
         n0 = __builtin_amdgcn_readfirstlane(nt) * BN;
+#endif
     };
 
     // ---- fetch cursor: scalar bases of the tile being loaded + loop-invariant lane offsets
@@ -125,8 +139,15 @@
     // (tid / IPR_A) + i RA agree in bits 1-3, so the permutation is loop-invariant)
     const unsigned voff_a = (unsigned)(tid / IPR_A) * (unsigned)g.lda * (unsigned)ESZ +
                             (unsigned)(kDma ? (tid % IPR_A) ^ (((tid / IPR_A) >> 1) & 7) : tid % IPR_A) * IB;
+#if QS_FAST_PAIRS == 3
+    // column triangle: the tile's column 2 lane is column (2 lane) % S of segment (2 lane) / S, a row of the (c, d) matrix
+    // apart -- one wave-instruction reads R pieces of 8 S bytes; its lane-linear destination is the B row as ever
+    static_assert(kDma && TN == 4, "the column-triangle form exists for the exact fp64 DMA forms, 128 columns");
+    const unsigned voff_b = (((2u * lane) >> g.sshift) * g.side + ((2u * lane) & ((1u << g.sshift) - 1u))) * (unsigned)ESZ;
+#else
     const unsigned voff_b = (IPR_B < 64 ? (unsigned)(lane / IPR_B) * (unsigned)g.ldb * (unsigned)ESZ : 0u) +
                             (unsigned)(tid % IPR_B) * IB;
+#endif
     const size_t a_step = KT * ESZ;
     const size_t b_step = (size_t)KT * g.ldb * ESZ;
 
@@ -312,7 +333,16 @@
         int m0, n0; int64_t b;
         decode(v, m0, n0, b);
         const int64_t row_l = (int64_t)m0 + wm * 16 * TM + (lane >> 4);
+#if QS_FAST_PAIRS == 3
+        // column triangle: tile column wn 64 + jp 32 + 2 (lane & 15) in segments of S -- the lane's own part, and jp steps
+        // 32 / S rows of the (c, d) matrix (16 bytes per lane still; eight lanes complete a 128-byte line)
+        const unsigned tcl = (unsigned)(wn * 16 * TN + 2 * (lane & 15));
+        const int col_l = n0 + (int)((tcl >> g.sshift) * g.side + (tcl & ((1u << g.sshift) - 1u)));
+        const int64_t jp_step = (int64_t)((32u >> g.sshift) * g.side);
+#else
         const int col_l = n0 + wn * 16 * TN + (CX ? 1 : 2) * (lane & 15);
+        constexpr int jp_step = 32;
+#endif
         double* __restrict__ C = g.C + (b * g.sc + row_l * g.ldc + col_l) * ES;
         auto store_all = [&](auto add_c, auto guard_c) __attribute__((always_inline)) {
             constexpr bool add = decltype(add_c)::value;
@@ -337,7 +367,7 @@
 #pragma unroll
                         for (int jp = 0; jp < TN / 2; ++jp) {
                             if (row_ok && (!guard || col_l + jp * 32 + 1 < g.n)) {
-                                f64x2* dst = reinterpret_cast<f64x2*>(crow + jp * 32);
+                                f64x2* dst = reinterpret_cast<f64x2*>(crow + jp * jp_step);
                                 f64x2 v2 = f64x2{acc[0][i][2 * jp][r], acc[0][i][2 * jp + 1][r]};
                                 if constexpr (add) v2 += *dst;
                                 QS_FAST_STORE(dst, v2);

@@ -322,6 +322,31 @@ __global__ __launch_bounds__(256) void exchange_transpose_kernel(T* t, int n, in
     }
 }
 
+// In place on t (n, n, m, m):  t[i,j][r,s] = t[j,i][s,r]  for every pair i <= j and every s < r; nothing else is written (the
+// fill after the route's column-triangle products, which store the blocks that meet s >= r of EVERY pair).  A workgroup
+// takes one pair i <= j and one 32 x 32 tile (ti, tj <= ti) of t[i,j]: it reads tile (tj, ti) of t[j,i] by rows, turns it
+// in LDS and writes rows.  A diagonal tile -- and with it the diagonal pair i == j -- stores s < r only: the elements
+// s >= r were computed directly and differ from their mirror images in rounding.  Sources (strictly upper) and
+// destinations (strictly lower) never overlap; a diagonal tile is read whole before its barrier and written after it.
+template <typename T>
+__global__ __launch_bounds__(256) void exchange_transpose_lower_kernel(T* t, int n, int m, int nt) {
+    __shared__ T t1[PT][PS];
+    const uint32_t ntl = (uint32_t)nt * (uint32_t)(nt + 1) / 2u;
+    const uint32_t pair = blockIdx.x / ntl, tile = blockIdx.x - pair * ntl;
+    const uint32_t i = triangle_row(pair, (uint32_t)n), j = i + (pair - triangle_row_start(i, (uint32_t)n));
+    const uint32_t tj = triangle_row(tile, (uint32_t)nt), ti = tj + (tile - triangle_row_start(tj, (uint32_t)nt));      // tj <= ti
+    const int64_t mm = (int64_t)m * m;
+    load_tile<T, true>(t1, (const T*)t + ((int64_t)j * n + i) * mm, m, (int)tj * PT, (int)ti * PT);
+    __syncthreads();
+    T* o = t + ((int64_t)i * n + j) * mm;
+    const int tx = threadIdx.x & (PT - 1), ty = threadIdx.x / PT;
+#pragma unroll
+    for (int rr = ty; rr < PT; rr += 8) {
+        const int r = (int)ti * PT + rr, c = (int)tj * PT + tx;
+        if (r < m && c < r) stream_store(&o[(int64_t)r * m + c], t1[tx][rr]);
+    }
+}
+
 // ----------------------------------------------------------------------------
 // The exchange route's leading indices on pairs (qs_api.hip): seen through its TRAILING indices a tensor with the symmetry
 // has u[:, :, c, d] == u[:, :, d, c]^T, so the two leading contractions are a two-sided product of the matrix over (a, b)
@@ -497,6 +522,22 @@ int exchange_mirror(int dtype, void* t, int64_t n, int64_t m, int64_t block, hip
                            (f64x2*)t, (int)n, (int)m, nt, (int)block);
     note_dispatch("qs::exchange_transpose_kernel<%s>", dtype == QS_F64 ? "double" : "f64x2");
     return launch_status("exchange_mirror launch");
+}
+
+bool exchange_mirror_lower_fits(int64_t n, int64_t m) {
+    const int64_t nt = cdiv(m, PT);
+    return n > 0 && m > 0 && n <= 4096 && m <= 4096 && n * (n + 1) / 2 * (nt * (nt + 1) / 2) < (int64_t(1) << 31);
+}
+
+int exchange_mirror_lower(int dtype, void* t, int64_t n, int64_t m, hipStream_t stream) {
+    if (dtype != QS_F64) return QS_ERR_BAD_DTYPE;
+    if (!exchange_mirror_lower_fits(n, m)) return QS_ERR_BAD_EXTENT;
+    const int nt = (int)cdiv(m, PT);
+    const int64_t nwg = n * (n + 1) / 2 * ((int64_t)nt * (nt + 1) / 2);
+    hipLaunchKernelGGL(exchange_transpose_lower_kernel<double>, dim3((unsigned)nwg), dim3(256), 0, stream, (double*)t, (int)n,
+                       (int)m, nt);
+    note_dispatch("qs::exchange_transpose_lower_kernel<double>");
+    return launch_status("exchange_mirror_lower launch");
 }
 
 // The pair movers' grids: x, y, z extents (y and z hold at most 65535 workgroups each, a whole grid fewer than 2^31).

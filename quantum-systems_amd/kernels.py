@@ -217,6 +217,26 @@ def gemm_raw(dt, A, B, out, m, n, k, lda, ldb, ldc, batch=1, sa=0, sb=0, sc=0,
 
 
 @_plain
+def matmul_upper(dt, A, B, out, m, side, stack, k, lda, ldb, ldc, batch=1, sa=0, sb=0, sc=0, accumulate=False,
+                 a_off=0, b_off=0, c_off=0):
+    """Thin call of ``qs_matmul_upper`` on tensors already prepared by the caller, offsets and strides in elements: the
+    product on the column blocks that meet ``d >= c`` of a stack of row-major ``side x side`` matrices ``(c, d)``
+    (``n = stack * side * side`` columns).  float64 on the exact tiled forms only; raises ``ValueError`` where no kernel
+    can.  Returns ``out``."""
+    lib = _lib.load()
+    es = 16 if dt == _C128 else 8
+    with _on_device_of(A, B, out):
+        _ran(
+            lib.qs_matmul_upper(
+                dtype_code(dt), A.data_ptr() + a_off * es, B.data_ptr() + b_off * es, out.data_ptr() + c_off * es,
+                m, side, stack, k, lda, ldb, ldc, batch, sa, sb, sc, 1 if accumulate else 0, _stream(),
+            ),
+            "qs_matmul_upper",
+        )
+    return out
+
+
+@_plain
 def matmul(A, B, out=None, accumulate=False):
     """Row-major ``A @ B`` for 2-D operands (or a shared 2-D ``A`` against a
     batch ``B`` of shape (batch, k, n)); ``accumulate`` adds into ``out``."""
@@ -429,6 +449,20 @@ def exchange_mirror_(t, block=1):
     with _on_device_of(t):
         _ran(lib.qs_exchange_mirror(dtype_code(t.dtype), t.data_ptr(), t.shape[0], t.shape[2], int(block), _stream()),
              "qs_exchange_mirror")
+    return t
+
+
+@_plain
+def exchange_mirror_lower_(t):
+    """In place on ``t`` (n,n,m,m), contiguous float64: ``t[i,j,r,s] = t[j,i,s,r]`` for every pair ``i <= j`` and every
+    ``s < r`` (``qs_exchange_mirror_lower``: the fill of ``exchange_upper``); returns ``t``."""
+    lib = _lib.load()
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or not t.is_contiguous() or t.dim() != 4 \
+            or t.shape[0] != t.shape[1] or t.shape[2] != t.shape[3]:
+        raise ValueError("exchange_mirror_lower_ needs a contiguous device tensor of shape (n, n, m, m)")
+    with _on_device_of(t):
+        _ran(lib.qs_exchange_mirror_lower(dtype_code(t.dtype), t.data_ptr(), t.shape[0], t.shape[2], _stream()),
+             "qs_exchange_mirror_lower")
     return t
 
 

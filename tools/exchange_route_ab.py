@@ -1,7 +1,8 @@
 """Same-process A/B of the transform's exchange-symmetry route against the plain route, and the route's phases.
 
     python tools/exchange_route_ab.py --sizes 160,192,224,256 --dtype f64 [--blocks 32,64,128] [--blocks-d 8,16,64]
-                                      [--pairs 0,1] [--orders 0,2] [--leading 0,2] [--reps 5] [--phases [--c-blocks 16,64]]
+                                      [--pairs 0,1] [--orders 0,2] [--leading 0,2] [--upper 0,2] [--reps 5]
+                                      [--phases [--c-blocks 16,64]]
 
 Per size: one symmetric tensor (bench.make_inputs), then the plain route (`exchange=0`) and every (block, block_d)
 of the forced route (`exchange=2`) in ALTERNATING repetitions (NOTES.md "How to measure here"), HIP-event time per
@@ -12,7 +13,9 @@ the launches per block / per row of `exchange_pairs=0` and as the one triangular
 `exchange_pairs=1`.  `--pairs 0,1` times the whole route at both settings of that key, `--orders 0,2` at both orders of the contractions
 (`exchange_order`); `--phases` then replays each of those orders' launches.  `--leading 0,2` times order 2 with its leading
 indices as one product and the closing blocks, and on pairs between the two transposes (`exchange_leading`); with 2 in
-the list `--phases` also replays the pair movers and the two products between them, and prints the total of either form."""
+the list `--phases` also replays the pair movers and the two products between them, and prints the total of either form.
+`--upper 0,2` times order 2 with its leading indices on the column triangle (`exchange_upper`: two `qs_matmul_upper`
+products and the fill); with 2 in the list `--phases` replays those three launches too."""
 
 import argparse
 import os
@@ -36,7 +39,8 @@ def med(xs):
     return s[len(s) // 2] if len(s) % 2 else 0.5 * (s[len(s) // 2 - 1] + s[len(s) // 2])
 
 
-def phases(torch, K, u, C, Ct, out, blk, blk_d, reps, c_blocks=(), other_order=False, order=0, leading_pairs=False):
+def phases(torch, K, u, C, Ct, out, blk, blk_d, reps, c_blocks=(), other_order=False, order=0, leading_pairs=False,
+           leading_upper=False):
     """The route's launches, phase by phase (T1 and X in one spare buffer, T2 in `out`), in the order `order` takes (0: d, c,
     mirror, a, closing, mirror; 2: a, closing, d, c, mirror -- X1 and Y in the spare buffer, X2 in `out`).  `c_blocks`: also time the c phase
     with every row a of a block [a0, a1) batched over b >= a0 instead of b >= a (needs blk_d to divide those blocks)."""
@@ -102,6 +106,11 @@ def phases(torch, K, u, C, Ct, out, blk, blk_d, reps, c_blocks=(), other_order=F
             steps += [("pairs: way in", lambda: K.exchange_pair_transpose(u, W4)),
                       ("pairs: b", lambda: d_pairs(W, out, CtT)), ("pairs: a", lambda: c_pairs(False, out, W, Ct)),
                       ("pairs: way back", lambda: K.exchange_pair_transpose_back(W4, out.view(L, L, L, L)))]
+        if leading_upper:
+            # exchange_upper=2: b' (u -> W) and a' (W -> out) on the column blocks d >= c, then the fill of out's lower triangles
+            steps += [("upper: b", lambda: K.matmul_upper(dt, Ct, u, W, L, L, 1, L, L, L2, L2, L, 0, L3, L3)),
+                      ("upper: a", lambda: K.matmul_upper(dt, Ct, W, out, L, L, L, L, L, L3, L3, 1)),
+                      ("upper: fill", lambda: K.exchange_mirror_lower_(out.view(L, L, L, L)))]
     else:
         other = [("other order: b full", b_full), ("other order: a blocks", a_blocks)] if other_order else []
         steps = [("check", check), ("d, per block", d), ("d", d_pairs)] + [(f"c, b >= block {cb}", lambda cb=cb: c(cb)) for cb in c_blocks] + [
@@ -115,13 +124,17 @@ def phases(torch, K, u, C, Ct, out, blk, blk_d, reps, c_blocks=(), other_order=F
     total = 0.0
     for name, _ in steps:
         t = med(times[name][1:])
-        total += 0.0 if name.startswith(("c, ", "d, ", "other order", "pairs: ")) else t
+        total += 0.0 if name.startswith(("c, ", "d, ", "other order", "pairs: ", "upper: ")) else t
         print(f"    phase {name:20s} {t:8.3f} ms   (runs: {' '.join('%.3f' % x for x in times[name][1:])})")
     print(f"    phases total     {total:8.3f} ms")
     if order == 2 and leading_pairs:
         blocks = med(times["a"][1:]) + med(times["closing product"][1:])
         pairs = sum(med(times[name][1:]) for name, _ in steps if name.startswith("pairs: "))
         print(f"    leading indices: a + closing product {blocks:8.3f} ms, on pairs {pairs:8.3f} ms; phases total on pairs {total - blocks + pairs:8.3f} ms")
+    if order == 2 and leading_upper:
+        blocks = med(times["a"][1:]) + med(times["closing product"][1:])
+        upper = sum(med(times[name][1:]) for name, _ in steps if name.startswith("upper: "))
+        print(f"    leading indices: a + closing product {blocks:8.3f} ms, on the column triangle {upper:8.3f} ms; phases total on it {total - blocks + upper:8.3f} ms")
     del W
 
 
@@ -134,6 +147,7 @@ def main():
     ap.add_argument("--pairs", default="1", help="exchange_pairs settings of the route to time, e.g. 0,1")
     ap.add_argument("--orders", default="1", help="exchange_order settings of the route to time, e.g. 0,2 (1: the automatic rule)")
     ap.add_argument("--leading", default="1", help="exchange_leading settings of the route to time, e.g. 0,2 (1: the automatic rule)")
+    ap.add_argument("--upper", default="1", help="exchange_upper settings of the route to time, e.g. 0,2 (1: the automatic rule)")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--phases", action="store_true")
     ap.add_argument("--other-order", action="store_true", help="with --phases: also time b full, then a per block of rows")
@@ -146,8 +160,8 @@ def main():
 
     dev = torch.device("cuda:0")
     dtype = torch.float64 if args.dtype == "f64" else torch.complex128
-    configs = [(int(b), int(bd), int(pr), int(od), int(ld)) for b in args.blocks.split(",") for bd in args.blocks_d.split(",") for pr in args.pairs.split(",")
-               for od in args.orders.split(",") for ld in args.leading.split(",")]
+    configs = [(int(b), int(bd), int(pr), int(od), int(ld), int(up)) for b in args.blocks.split(",") for bd in args.blocks_d.split(",") for pr in args.pairs.split(",")
+               for od in args.orders.split(",") for ld in args.leading.split(",") for up in args.upper.split(",")]
     for l in [int(x) for x in args.sizes.split(",")]:
         u, C, Ct = bench.make_inputs(torch, l, dtype, dev)
         out = torch.empty_like(u)
@@ -157,8 +171,9 @@ def main():
             with K.tuning(exchange=0):
                 K.transform_two_body(u, C, Ct, out=out)
 
-        def route(b, bd, pr, od, ld):
-            with K.tuning(exchange=2, exchange_block=b, exchange_block_d=bd, exchange_pairs=pr, exchange_order=od, exchange_leading=ld):
+        def route(b, bd, pr, od, ld, up=1):
+            with K.tuning(exchange=2, exchange_block=b, exchange_block_d=bd, exchange_pairs=pr, exchange_order=od, exchange_leading=ld,
+                          exchange_upper=up):
                 K.transform_two_body(u, C, Ct, out=out)
 
         plain()
@@ -179,17 +194,18 @@ def main():
         print(f"  plain                       median {base:8.3f} ms   runs {' '.join('%.3f' % x for x in runs['plain'])}")
         for cfg in configs:
             m = med(runs[cfg])
-            print(f"  route block={cfg[0]:3d} block_d={cfg[1]:3d} pairs={cfg[2]} order={cfg[3]} leading={cfg[4]} median {m:8.3f} ms   runs {' '.join('%.3f' % x for x in runs[cfg])}"
+            print(f"  route block={cfg[0]:3d} block_d={cfg[1]:3d} pairs={cfg[2]} order={cfg[3]} leading={cfg[4]} upper={cfg[5]} median {m:8.3f} ms   runs {' '.join('%.3f' % x for x in runs[cfg])}"
                   f"   plain/route {base / m:.3f}")
         sys.stdout.flush()
         if args.phases:
             for od in sorted({cfg[3] for cfg in configs}):       # (1, the automatic rule, reads as the order it takes here)
                 if od == 1:
-                    route(configs[0][0], configs[0][1], 1, 1, 0)
+                    route(configs[0][0], configs[0][1], 1, 1, 0, 0)
                     od = 2 if K.last_dispatch().count("exchange_transpose_kernel") == 1 else 0
                 phases(torch, K, u, C, Ct, out, configs[0][0], configs[0][1], args.reps,
                        [int(x) for x in args.c_blocks.split(",") if x], args.other_order, od,
-                       leading_pairs=od == 2 and any(cfg[4] == 2 for cfg in configs))
+                       leading_pairs=od == 2 and any(cfg[4] == 2 for cfg in configs),
+                       leading_upper=od == 2 and not dtype.is_complex and any(cfg[5] == 2 for cfg in configs))
         del u, out
         K.workspace.release()
         torch.cuda.empty_cache()
