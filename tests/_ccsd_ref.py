@@ -360,6 +360,45 @@ def singles_bound(X, slots, A, G, sslots, eo3, ev):
                      for x, row in enumerate(np.asarray(slots))])
 
 
+def _cyclic(entries):
+    """The even orders (0, 3, 4) hold one thing and the odd ones (1, 2, 5) one thing."""
+    return entries[0] == entries[3] == entries[4] and entries[1] == entries[2] == entries[5]
+
+
+def singles_tile_set_sensitivity(X, slots, A, G, sslots, eo3, ev, T):
+    """The least ``|singles contribution of a tile set| / singles_bound`` over the triples of the tables and their tile
+    sets, from the long-double reference alone (the analogue of ``_triples_ref.tile_set_sensitivity``): a workgroup whose
+    singles partial is left out, doubled or put elsewhere moves ``es`` by that many bounds at least.  A tile set holds
+    whole orbits of (a, b, c), D is the same on an orbit, and the sum of Z over an orbit is 0 (its coefficients add up
+    to 0), so an orbit adds nothing where Z = 0 on it or where V' is the same at its six orders.  What is 0 by such an
+    identity is left out, and nothing else:
+      * a set that holds a = b = c alone -- the diagonal set of a ragged tile of one element: Z = 0;
+      * every set of a triple with ONE block in all six ``slots``: W is totally symmetric, Z = 0;
+      * ``slots`` cyclic (orders 0, 3, 4 one block, orders 1, 2, 5 one block): W is totally symmetric wherever two
+        indices are equal, Z = 0 there: the diagonal set of a ragged tile of TWO elements holds such orbits alone;
+      * every set of a triple whose six ``(sa, sg)`` are all equal: V' is totally symmetric;
+      * ``sslots`` cyclic in the same sense (the pairs ``(sa, sg)`` compared): V' is totally symmetric wherever two
+        indices are equal, again the diagonal set of a ragged tile of two.
+    (Not left out, because no table of the tests has it and the condition then fails on the safe side: a cyclic ``sslots``
+    row beside a ``slots`` row under which W is the same at two orders a transposition apart, as the table of i = j is;
+    the even and the odd sums of W are then equal and every orbit adds 0.)"""
+    v = len(ev)
+    ragged = v % T
+    bound = singles_bound(X, slots, A, G, sslots, eo3, ev)
+    least = np.inf
+    for x, row in enumerate(np.asarray(slots)):
+        pairs = [tuple(int(y) for y in entry) for entry in np.asarray(sslots[x])]
+        if len(set(row.tolist())) == 1 or len(set(pairs)) == 1:
+            continue
+        terms = singles_terms(X, row, A, G, sslots[x], eo3[x], ev, extended=True)
+        sums = np.abs(tr.tile_set_sums(terms, T)).astype(np.float64)
+        if ragged == 1 or (ragged == 2 and (_cyclic(row.tolist()) or _cyclic(pairs))):
+            sums = sums[:-1]                # (nt - 1, nt - 1, nt - 1), the last set
+        if sums.size:
+            least = min(least, sums.min() / bound[x])
+    return least
+
+
 def singles_problem(v, n, na, ng, seed, complex_=False, share="none"):
     """Seeded ``A`` (na, v), ``G`` (ng, v, v) and ``sslots`` (n, 6, 2).  ``share``: "none" = six distinct (sa, sg)
     entries per triple, both columns distinct; "repeat" = entries that repeat inside a triple."""

@@ -3,7 +3,11 @@ part ``e``) and tests/_ccsd_ref.py (the singles part ``es``; tests/test_ccsd_ref
 determinant definition of (T)).
 
 Tolerances (derived, not tuned): ``kernel_bound`` and ``singles_bound``, the any-order rounding bounds of the kernel's
-two sums, against the ``numpy.longdouble`` evaluation of the same inputs."""
+two sums, against the ``numpy.longdouble`` evaluation of the same inputs.
+
+The sizes here never make a last diagonal tile set count (where there is more than one tile, the last is a ragged tile of
+one element, whose diagonal set adds 0 to both sums by identity): tests/test_gpu_triples_singles_scale.py has the ragged
+tiles of two and more, more than three tiles, every slot pattern and the far offsets."""
 
 import numpy as np
 import pytest
