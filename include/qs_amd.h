@@ -115,6 +115,29 @@ int qs_matmul_pairs_mirrored(int dtype, const void* A, const void* B, void* out,
                              int64_t stride_c, int accumulate, void* stream);
 
 /*
+ * qs_matmul_pairs whose A entries are square (m == k == lda, at least m * m
+ * elements apart) and stored, at ALL grid_n * grid_n flat indices, on their
+ * 16 x 16 blocks (G, J >= G) only, with A(i, j) == A(j, i)^T.  For every pair
+ * (i, j >= i) the launch reads these blocks and nothing else of A:
+ *   of entry (i, j): the blocks (G, J >= G);
+ *   of entry (j, i): the blocks (J, G) with J < G, each standing for block
+ *                    (G, J) of entry (i, j) transposed.
+ * The k order is that of qs_matmul_pairs, so on a complete A whose diagonal
+ * blocks are symmetric between (i, j) and (j, i) the result has its bits.
+ * float64 on the exact tiled forms only: m a multiple of 64, n of 128,
+ * 16-byte aligned operands with even strides, accumulate == 0, under the
+ * calling thread's tuning keys; anything else is refused with
+ * QS_ERR_BAD_EXTENT before a launch (no fallback).  The dispatch record names
+ * the launch "qs::gemm_fast_kernel<false, 4|2, 4, true, false>(qs::FastPairsLowerArgs)".
+ * (An addition: the ABI version stays 4.)
+ */
+int qs_matmul_pairs_lower(int dtype, const void* A, const void* B, void* out,
+                          int64_t m, int64_t n, int64_t k,
+                          int64_t lda, int64_t ldb, int64_t ldc,
+                          int64_t grid_n, int64_t stride_a, int64_t stride_b,
+                          int64_t stride_c, int accumulate, void* stream);
+
+/*
  * The product on a COLUMN TRIANGLE: the n = stack * side * side columns of B
  * and out are a stack of row-major side x side matrices (c, d), and only the
  * column blocks that meet d >= c are computed.  A tile's 128 columns are R
@@ -249,6 +272,10 @@ int qs_transform_two_body_inplace(int dtype, void* u, const void* C,
  *     calling thread's tuning keys ("exchange_order", "exchange_upper",
  *     "exchange_leading"), else 0; qs_transform_two_body_exchange_leading_pairs
  *     answers 0 wherever this answers 1.  Launches nothing.
+ *   qs_transform_two_body_exchange_lower_d: 1 where that form would drop its
+ *     qs_exchange_mirror_lower and run the d contraction as one
+ *     qs_matmul_pairs_lower instead ("exchange_lower", and the keys above),
+ *     else 0.  Launches nothing.
  *   qs_exchange_mirror_lower: in place on t (n,n,m,m), float64,
  *     t[i,j][r,s] = t[j,i][s,r] for every pair i <= j (the diagonal pairs
  *     included) and every s < r; nothing else is written.  The fill after the
@@ -269,6 +296,7 @@ int qs_exchange_mirror(int dtype, void* t, int64_t n, int64_t m, int64_t block,
                        void* stream);
 int qs_transform_two_body_exchange_leading_pairs(int dtype, int64_t L, int64_t M);
 int qs_transform_two_body_exchange_leading_upper(int dtype, int64_t L, int64_t M);
+int qs_transform_two_body_exchange_lower_d(int dtype, int64_t L, int64_t M);
 int qs_exchange_mirror_lower(int dtype, void* t, int64_t n, int64_t m,
                              void* stream);
 int qs_exchange_pair_transpose(int dtype, const void* src, void* dst, int64_t L,
@@ -668,6 +696,20 @@ const char* qs_last_dispatch(void);
  *     "exchange_leading" is at its own default: an explicit 0 or 2 there keeps
  *     exactly those launches.  Agrees with the other forms to rounding;
  *     outside 0 ... 2: QS_ERR_BAD_EXTENT),
+ *     "exchange_lower" (that column-triangle form WITHOUT its fill: the d
+ *     launch over the pairs q >= p, the fill's one reader, runs as
+ *     qs_matmul_pairs_lower and takes each 16 x 16 block below the block
+ *     diagonal from the mirror pair, where the second product stored it; the
+ *     blocks below the diagonal of the intermediate are then never written,
+ *     and in place they hold stale input that nothing reads.  float64 only.
+ *     0 = never; 2 = wherever "exchange_upper" runs and qs_matmul_pairs_lower
+ *     takes that launch (L a multiple of 64, M of 128), elsewhere the launches
+ *     with the fill; 1, the default = 2 from the smallest size measured to
+ *     gain (256 orbitals), and only while "exchange_upper" is at its own
+ *     default: an explicit 2 there keeps exactly its launches, the fill
+ *     included.  Agrees with the filled form to rounding (its bits except on
+ *     the diagonal blocks, whose lower elements no longer come from their
+ *     mirror images); outside 0 ... 2: QS_ERR_BAD_EXTENT),
  *     "gemm_upper_s" (the segment length S of qs_matmul_upper's tiles: 16 or
  *     32, 0 = the shipped choice, 16; anything else: QS_ERR_BAD_EXTENT).
  *   qs_probe_mfma_f64: register-resident fp64 MFMA loop, `blocks` workgroups

@@ -28,6 +28,7 @@ SIGNATURES = {
     "qs_matmul": (c_int, [c_int, c_ptr, c_ptr, c_ptr] + [c_i64] * 10 + [c_int, c_ptr]),
     "qs_matmul_pairs": (c_int, [c_int, c_ptr, c_ptr, c_ptr] + [c_i64] * 10 + [c_int, c_ptr]),
     "qs_matmul_pairs_mirrored": (c_int, [c_int, c_ptr, c_ptr, c_ptr] + [c_i64] * 10 + [c_int, c_ptr]),
+    "qs_matmul_pairs_lower": (c_int, [c_int, c_ptr, c_ptr, c_ptr] + [c_i64] * 10 + [c_int, c_ptr]),
     "qs_matmul_upper": (c_int, [c_int, c_ptr, c_ptr, c_ptr] + [c_i64] * 11 + [c_int, c_ptr]),
     "qs_triangle_pair": (c_int, [c_i64, c_i64, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
     "qs_transform_two_body_workspace": (c_i64, [c_int, c_i64, c_i64]),
@@ -47,6 +48,7 @@ SIGNATURES = {
     "qs_exchange_mirror": (c_int, [c_int, c_ptr, c_i64, c_i64, c_i64, c_ptr]),
     "qs_transform_two_body_exchange_leading_pairs": (c_int, [c_int, c_i64, c_i64]),
     "qs_transform_two_body_exchange_leading_upper": (c_int, [c_int, c_i64, c_i64]),
+    "qs_transform_two_body_exchange_lower_d": (c_int, [c_int, c_i64, c_i64]),
     "qs_exchange_mirror_lower": (c_int, [c_int, c_ptr, c_i64, c_i64, c_ptr]),
     "qs_exchange_pair_transpose": (c_int, [c_int, c_ptr, c_ptr, c_i64, c_ptr]),
     "qs_exchange_pair_transpose_back": (c_int, [c_int, c_ptr, c_ptr, c_i64, c_i64, c_ptr]),

@@ -280,6 +280,11 @@ int qs_tuning_set(const char* key, int64_t value) {
         g_tune.exchange_upper = (int)value;
         return QS_OK;
     }
+    if (!strcmp(key, "exchange_lower")) {
+        if (value < 0 || value > 2) return QS_ERR_BAD_EXTENT;
+        g_tune.exchange_lower = (int)value;
+        return QS_OK;
+    }
     if (!strcmp(key, "gemm_upper_s")) {
         if (value != 0 && value != 16 && value != 32) return QS_ERR_BAD_EXTENT;
         g_tune.gemm_upper_s = (int)value;
@@ -334,7 +339,7 @@ int qs_matmul(int dtype, const void* A, const void* B, void* out, int64_t m, int
 
 static int matmul_pairs(int dtype, const void* A, const void* B, void* out, int64_t m, int64_t n, int64_t k,
                         int64_t lda, int64_t ldb, int64_t ldc, int64_t grid_n, int64_t stride_a,
-                        int64_t stride_b, int64_t stride_c, int accumulate, void* stream, bool mirror) {
+                        int64_t stride_b, int64_t stride_c, int accumulate, void* stream, bool mirror, bool lower = false) {
     dispatch_reset();
     if (!dtype_ok(dtype)) return QS_ERR_BAD_DTYPE;
     if (!A || !B || !out) return QS_ERR_NULL_POINTER;
@@ -342,9 +347,10 @@ static int matmul_pairs(int dtype, const void* A, const void* B, void* out, int6
     if (!aligned(A, es) || !aligned(B, es) || !aligned(out, es)) return QS_ERR_MISALIGNED;
     if (stride_a < 0 || stride_b < 0 || stride_c < 0) return QS_ERR_BAD_EXTENT;
     if (grid_n <= 0 || grid_n > kTriangleMax) return QS_ERR_BAD_EXTENT;
-    return gemm(Product{dtype, (const double*)A, (const double*)B, (double*)out, m, n, k, lda, ldb, ldc,
-                        grid_n * (grid_n + 1) / 2, stride_a, stride_b, stride_c, accumulate, grid_n, mirror},
-                (hipStream_t)stream);
+    Product p{dtype, (const double*)A, (const double*)B, (double*)out, m, n, k, lda, ldb, ldc,
+              grid_n * (grid_n + 1) / 2, stride_a, stride_b, stride_c, accumulate, grid_n, mirror};
+    p.lower_from_mirror = lower;
+    return gemm(p, (hipStream_t)stream);
 }
 
 int qs_matmul_pairs(int dtype, const void* A, const void* B, void* out, int64_t m, int64_t n, int64_t k,
@@ -357,6 +363,12 @@ int qs_matmul_pairs_mirrored(int dtype, const void* A, const void* B, void* out,
                              int64_t lda, int64_t ldb, int64_t ldc, int64_t grid_n, int64_t stride_a,
                              int64_t stride_b, int64_t stride_c, int accumulate, void* stream) {
     return matmul_pairs(dtype, A, B, out, m, n, k, lda, ldb, ldc, grid_n, stride_a, stride_b, stride_c, accumulate, stream, true);
+}
+
+int qs_matmul_pairs_lower(int dtype, const void* A, const void* B, void* out, int64_t m, int64_t n, int64_t k,
+                          int64_t lda, int64_t ldb, int64_t ldc, int64_t grid_n, int64_t stride_a,
+                          int64_t stride_b, int64_t stride_c, int accumulate, void* stream) {
+    return matmul_pairs(dtype, A, B, out, m, n, k, lda, ldb, ldc, grid_n, stride_a, stride_b, stride_c, accumulate, stream, false, true);
 }
 
 int qs_matmul_upper(int dtype, const void* A, const void* B, void* out, int64_t m, int64_t side, int64_t stack, int64_t k,
@@ -617,6 +629,28 @@ static bool exchange_leading_upper(int dtype, int64_t L, int64_t M) {
     return g_tune.exchange_leading == 1 && M >= L && L >= kExchangeMin && L >= kExchangeUpperMin;
 }
 
+// g_tune.exchange_lower: the column-triangle pass WITHOUT its fill.  The fill's one consumer is the d launch over the pairs
+// q >= p, which for row block G = block(c) walks the k-stages J = block(d): the block X2[p,q](G, J >= G) is there after a', and
+// for J < G the wanted block is X2[q,p](J, G)^T, and X2[q,p](J, G) is there.  The d launch then carries
+// Product::lower_from_mirror (qs_gemm_fast.hip: the mirror pair's block lands in LDS as it is and is read the other way
+// round).  The lower blocks of X2 are never written -- in place they hold stale u -- and nothing reads them.
+// 2 = wherever the pass runs, d is one launch over the pairs and gemm_lower() takes it (L a multiple of 64, M of 128; else the
+// launches with the fill), 0 = never, 1 = where it measured faster, and only while exchange_upper is at its own automatic
+// value (an explicit 2 there keeps exactly its launches, the fill included).
+// (fp64, profiles/exchange_lower_ab.txt: L == M == 256, the one eligible size that fits one device with L == M)
+static constexpr int64_t kExchangeLowerMin = 256;
+
+static bool exchange_lower_wanted(int64_t L) {
+    if (g_tune.exchange_lower == 0) return false;
+    if (g_tune.exchange_lower == 2) return true;
+    return g_tune.exchange_upper == 1 && L >= kExchangeLowerMin;
+}
+
+// the d launch over the pairs j >= i of a G x G grid of (L, L) matrices, as gemm() would get it
+static Product exchange_d_pairs(int dtype, const void* src, const void* C, void* mid, int64_t G, int64_t L, int64_t M) {
+    return Product{dtype, (const double*)src, (const double*)C, (double*)mid, L, M, L, L, M, M, G * (G + 1) / 2, L * L, 0, L * M, 0, G};
+}
+
 // T1, T2, X: the three buffers of the comment above.  The a, b, d, c order keeps X1 where X goes, X2 where T2 goes and Y
 // where T1 goes; in either order every product reads one of the two storages and writes the other.
 static int transform_two_body_exchange_route(int dtype, const void* u, const void* C, const void* Ct, void* CT, void* T1,
@@ -653,25 +687,29 @@ static int transform_two_body_exchange_route(int dtype, const void* u, const voi
     // `mirrored` (null: not wanted): dst is the result and its other half is wanted too -- where the dispatch can, the c
     // launch stores it from its own registers (Product::mirror) and *mirrored says so; otherwise the caller launches the
     // mirror.
-    auto trailing = [&](const void* src, void* mid, void* dst, int64_t G, const void* C, const void* CT, bool* mirrored) -> int {
-        const int64_t npairs = G * (G + 1) / 2, LL = L * L, LM = L * M;
-        auto d_block = [&](int64_t i0) {
-            const int64_t rows = (i0 + blk_d < G ? i0 + blk_d : G) - i0;
-            return Product{dtype, cat(src, (i0 * G + i0) * LL), (const double*)C, mat(mid, (i0 * G + i0) * LM),
-                           (G - i0) * L, M, L, L, M, M, rows, G * LL, 0, G * LM, 0};
-        };
-        const Product d_pairs{dtype, (const double*)src, (const double*)C, (double*)mid, L, M, L, L, M, M, npairs, LL, 0, LM, 0, G};
-        bool d_single = g_tune.exchange_pairs != 0;
-        if (d_single) {
-            double blocks_cost = 0.0;
-            for (int64_t i0 = 0; i0 < G; i0 += blk_d) blocks_cost += gemm_cost(d_block(i0));
-            d_single = gemm_cost(d_pairs) <= blocks_cost;
-        }
-        if (d_single) {
+    // `lower`: src holds the blocks (G, J >= G) of every entry only (g_tune.exchange_lower, above); the caller has asked
+    // d_is_single() and gemm_lower() for this very launch.
+    auto d_block = [&](const void* src, void* mid, int64_t G, const void* C, int64_t i0) {
+        const int64_t rows = (i0 + blk_d < G ? i0 + blk_d : G) - i0, LL = L * L, LM = L * M;
+        return Product{dtype, cat(src, (i0 * G + i0) * LL), (const double*)C, mat(mid, (i0 * G + i0) * LM),
+                       (G - i0) * L, M, L, L, M, M, rows, G * LL, 0, G * LM, 0};
+    };
+    auto d_is_single = [&](const void* src, void* mid, int64_t G, const void* C) {
+        if (g_tune.exchange_pairs == 0) return false;
+        double blocks_cost = 0.0;
+        for (int64_t i0 = 0; i0 < G; i0 += blk_d) blocks_cost += gemm_cost(d_block(src, mid, G, C, i0));
+        return gemm_cost(exchange_d_pairs(dtype, src, C, mid, G, L, M)) <= blocks_cost;
+    };
+    auto trailing = [&](const void* src, void* mid, void* dst, int64_t G, const void* C, const void* CT, bool* mirrored,
+                        bool lower = false) -> int {
+        const int64_t npairs = G * (G + 1) / 2, LM = L * M;
+        Product d_pairs =exchange_d_pairs(dtype, src, C, mid, G, L, M);
+        d_pairs.lower_from_mirror = lower;
+        if (lower || d_is_single(src, mid, G, C)) {
             if (int rc = gemm(d_pairs, s)) return rc;
         } else {
             for (int64_t i0 = 0; i0 < G; i0 += blk_d)
-                if (int rc = gemm(d_block(i0), s)) return rc;
+                if (int rc = gemm(d_block(src, mid, G, C, i0), s)) return rc;
         }
         if (g_tune.exchange_pairs) {
             Product c{dtype, (const double*)CT, (const double*)mid, (double*)dst, M, M, L, L, M, M, npairs, 0, LM, MM, 0, G};
@@ -695,15 +733,18 @@ static int transform_two_body_exchange_route(int dtype, const void* u, const voi
         return QS_OK;
     };
     // ... on the column blocks d >= c of W = L L (g_tune.exchange_upper, above): mid (L, M, L, L), dst (M, M, L, L) complete on
-    // the pairs q >= p after the fill
-    auto leading_upper_pass = [&](const void* src, void* mid, void* dst) -> int {
+    // the pairs q >= p after the fill (`fill`; without it, on the blocks (G, J >= G) of every pair)
+    auto leading_upper_pass = [&](const void* src, void* mid, void* dst, bool fill) -> int {
         if (int rc = gemm(exchange_upper_b(Ct, src, mid, L, M), s)) return rc;
         if (int rc = gemm(exchange_upper_a(Ct, mid, dst, L, M), s)) return rc;
-        return exchange_mirror_lower(dtype, dst, M, L, s);
+        return fill ? exchange_mirror_lower(dtype, dst, M, L, s) : QS_OK;
     };
     if (exchange_leading_first(dtype, L, M)) {
+        // (the d launch that follows, asked with the buffers themselves)
+        const bool lower_d = leading_upper && exchange_lower_wanted(L) && d_is_single(T2, T1, M, C) &&
+                             gemm_lower(exchange_d_pairs(dtype, T2, C, T1, M, L, M));
         if (leading_upper) {
-            rc = leading_upper_pass(u, /*Z*/ X, /*X2*/ T2);
+            rc = leading_upper_pass(u, /*Z*/ X, /*X2*/ T2, !lower_d);
         } else if (leading_pairs) {
             rc = exchange_pair_transpose(dtype, u, /*Xs*/ X, L, s);
             if (rc) return rc;
@@ -719,7 +760,7 @@ static int transform_two_body_exchange_route(int dtype, const void* u, const voi
         }
         if (rc) return rc;
         bool mirrored = false;
-        rc = trailing(/*X2*/ T2, /*Y*/ T1, out, M, C, CT, &mirrored);
+        rc = trailing(/*X2*/ T2, /*Y*/ T1, out, M, C, CT, &mirrored, lower_d);
         if (rc || mirrored) return rc;
         return exchange_mirror(dtype, out, M, M, 1, s);
     }
@@ -873,6 +914,14 @@ int qs_transform_two_body_exchange_leading_pairs(int dtype, int64_t L, int64_t M
 
 int qs_transform_two_body_exchange_leading_upper(int dtype, int64_t L, int64_t M) {
     return dtype_ok(dtype) && extents_ok(L, M) && exchange_leading_first(dtype, L, M) && exchange_leading_upper(dtype, L, M) ? 1 : 0;
+}
+
+int qs_transform_two_body_exchange_lower_d(int dtype, int64_t L, int64_t M) {
+    if (!qs_transform_two_body_exchange_leading_upper(dtype, L, M) || !exchange_lower_wanted(L) || !g_tune.exchange_pairs) return 0;
+    // (16-byte aligned stand-ins for the buffers: the conditions on the extents are what is asked here; the route itself
+    // also asks the dispatch's estimates whether d is one launch, which it is wherever L is a whole number of row tiles)
+    const double* al = reinterpret_cast<const double*>(uintptr_t(256));
+    return gemm_lower(exchange_d_pairs(dtype, al, al, const_cast<double*>(al), M, L, M)) ? 1 : 0;
 }
 
 int qs_exchange_mirror_lower(int dtype, void* t, int64_t n, int64_t m, void* stream) {

@@ -104,6 +104,11 @@ struct Product {
     // stored; nothing else of B is read and nothing else of C is written.  A plain batch only (no pairs, mirror or
     // accumulate), s a multiple of S, and only where gemm_upper() says yes.
     int64_t upper = 0;
+    // Lower blocks from the mirror pair: the A entries of a triangular batch are square (m == k == lda) and hold their
+    // 16 x 16 blocks (G, J >= G) only, at ALL flat indices of the grid, with A(i, j) == A(j, i)^T.  The kernel takes block
+    // (G, J < G) of entry (i, j) from block (J, G) of entry (j, i) and reads nothing else below the block diagonal.  Needs pairs,
+    // fp64, no mirror, upper or accumulate, and only where gemm_lower() says yes.
+    bool lower_from_mirror = false;
     // which operand is the stream that neighbouring tiles should share in L2: a shared (stride-0) A, or a short-and-wide
     // product, streams B (the tiled kernels walk the tiles of one B panel first)
     int group_along_m() const { return ((sa == 0 && batch > 1) || m < n) ? 1 : 0; }
@@ -126,6 +131,12 @@ bool gemm_mirrors(const Product& p);
 // forms of qs_gemm_fast.hip walk the column triangle (fp64, 16-byte items, k % 16 == 0, m % 64 == 0, s a multiple of the
 // segment length, 32-bit lane offsets); gemm() refuses one that fails this with QS_ERR_BAD_EXTENT and launches nothing.
 bool gemm_upper(const Product& p);
+
+// Does gemm() take this product with Product::lower_from_mirror (read with the flag set or not) under the calling thread's
+// tuning keys?  Only the exact fp64 DMA forms of qs_gemm_fast.hip fetch the mirror pair's blocks (a triangular fp64 batch,
+// m == k == lda a multiple of 64, n of 128, entries at least m^2 apart, 16-byte items, no accumulate); gemm() refuses one that
+// fails this with QS_ERR_BAD_EXTENT and launches nothing.
+bool gemm_lower(const Product& p);
 // Columns d of one segment of such a tile (16 or 32: g_tune.gemm_upper_s, 0 = the shipped choice) and the tiles of one s x s matrix
 int64_t gemm_upper_segment();
 int64_t gemm_upper_tiles(int64_t s);
@@ -155,6 +166,9 @@ bool gemm_fast_mirrors(const Product& p);
 // ... the column-triangle form (Product::upper): whether the exact DMA forms take it, and its launch
 bool gemm_fast_upper(const Product& p);
 int gemm_fast_upper_launch(const Product& p, hipStream_t stream);
+// ... the lower-from-mirror form (Product::lower_from_mirror): the same two
+bool gemm_fast_lower(const Product& p);
+int gemm_fast_lower_launch(const Product& p, hipStream_t stream);
 
 // Small-coefficient streaming product, m, k <= 64 (qs_gemm_stream.hip).
 int gemm_stream_try(const Product& p, hipStream_t stream);
@@ -304,6 +318,9 @@ struct Tuning {
     int exchange_upper = 1;      // the leading indices of that route's second order as two products on the column blocks d >= c of u's
                                  // trailing indices and one fill of the other triangles (no pair movers): 0 = never, 2 = wherever
                                  // gemm_upper() takes both products, 1 = where it measured faster (and only while exchange_leading is 1)
+    int exchange_lower = 1;      // that column-triangle pass without its fill: the d launch takes the blocks below the block diagonal from
+                                 // the mirror pair (Product::lower_from_mirror): 0 = never, 2 = wherever gemm_lower() takes that launch,
+                                 // 1 = where it measured faster (and only while exchange_upper is 1)
     int exchange_leading = 1;    // the leading indices of that route's second order (exchange_order): 0 = one product and the closing blocks,
                                  // 2 = on the pairs d >= c of u's trailing indices, between two transposes of the pair matrix (M >= L only:
                                  // below that, and where a mover's grid does not fit, the launches of 0), 1 = the second from the smallest

@@ -535,10 +535,16 @@ bool gemm_upper(const Product& p) {
     return dtype_ok(p.dtype) && product_ok(p) && p.upper > 0 && g_tune.gemm_f64_cfg == 0 && gemm_fast_upper(p);
 }
 
+// (a forced shape of the general kernel skips the fast kernel, as above)
+bool gemm_lower(const Product& p) {
+    return dtype_ok(p.dtype) && product_ok(p) && p.pairs > 0 && g_tune.gemm_f64_cfg == 0 && gemm_fast_lower(p);
+}
+
 int gemm(const Product& p, hipStream_t stream) {
     if (!dtype_ok(p.dtype)) return QS_ERR_BAD_DTYPE;
     if (!product_ok(p)) return QS_ERR_BAD_EXTENT;
     if (p.mirror && !gemm_mirrors(p)) return QS_ERR_BAD_EXTENT;
+    if (p.lower_from_mirror) return gemm_lower(p) ? gemm_fast_lower_launch(p, stream) : QS_ERR_BAD_EXTENT;
     if (p.upper) return gemm_upper(p) ? gemm_fast_upper_launch(p, stream) : QS_ERR_BAD_EXTENT;
     const bool cx = p.dtype == QS_C128;
     const int64_t m = p.m, n = p.n, batch = p.batch;

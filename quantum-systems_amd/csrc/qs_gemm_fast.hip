@@ -138,6 +138,22 @@ void gemm_fast_kernel(const FastUpperArgs g) {
 #undef QS_FAST_PAIRS
 }
 
+// ... of a triangular batch whose A entries are square (m == k == lda) and stored on their 16 x 16 blocks (G, J >= G) only, for
+// ALL entries of the grid (Product::lower_from_mirror).  For every entry (i, j >= i) the kernel reads these blocks and
+// nothing else of A:
+//   of entry (i, j): the blocks (G, J >= G);
+//   of entry (j, i): the blocks (J, G) with J < G, each taken for block (G, J) of entry (i, j) transposed.
+// A fifth overload, for the same reason; only the exact fp64 DMA forms are instantiated.
+struct FastPairsLowerArgs : FastPairsArgs {};
+
+template <bool CX, int TM, int TN, bool VEC, bool EDGE>
+__global__ __launch_bounds__(256, 2)
+void gemm_fast_kernel(const FastPairsLowerArgs g) {
+#define QS_FAST_PAIRS 4
+#include "qs_gemm_fast_body.h"
+#undef QS_FAST_PAIRS
+}
+
 template <bool CX, int TM, int TN, bool VEC, bool EDGE>
 static int launch_fast(const Product& p, hipStream_t stream) {
     constexpr int KT = CX ? 8 : 16;
@@ -192,9 +208,23 @@ static int launch_fast(const Product& p, hipStream_t stream) {
     constexpr bool DMA = QS_FAST_DMA && !CX && VEC && !EDGE;     // unpadded A rows (the kernel's kDma)
     const size_t lds = sizeof(double) * 2 * NP * (BM * (CX || DMA ? KT : KT + 2) + KT * (CX ? BN + 16 : BN));
 #endif
-    static PerDeviceLds lds_opt_in[4];   // per instantiation, batch kind and device
+    static PerDeviceLds lds_opt_in[5];   // per instantiation, batch kind and device
     constexpr bool kMirrors = !CX && TM == 4 && TN == 4 && VEC && !EDGE;      // (fast_mirror_form)
-    constexpr bool kUpper = QS_FAST_DMA && !CX && VEC && !EDGE && (TM == 4 || TM == 2) && TN == 4;      // (gemm_fast_upper)
+    constexpr bool kUpper = QS_FAST_DMA && !CX && VEC && !EDGE && (TM == 4 || TM == 2) && TN == 4;      // (gemm_fast_upper, gemm_fast_lower)
+    if (p.lower_from_mirror) {
+        if constexpr (kUpper) {
+            FastPairsLowerArgs gl;
+            static_cast<FastArgs&>(gl) = g;
+            gl.pairs = (unsigned)p.pairs;
+            void (*kern)(const FastPairsLowerArgs) = gemm_fast_kernel<CX, TM, TN, VEC, EDGE>;
+            if (int rc = opt_in_dynamic_lds((const void*)kern, lds, lds_opt_in[4], "hipFuncSetAttribute(gemm_fast)")) return rc;
+            hipLaunchKernelGGL(kern, dim3((unsigned)P), dim3(256), lds, stream, gl);
+            note_dispatch("qs::gemm_fast_kernel<false, %d, 4, true, false>(qs::FastPairsLowerArgs)", TM);
+            return launch_status("gemm_fast launch");
+        } else {
+            return QS_ERR_BAD_EXTENT;      // not reached: gemm() asks gemm_lower() first
+        }
+    }
     if (p.upper) {
         if constexpr (kUpper) {
             FastUpperArgs gu;
@@ -358,6 +388,26 @@ bool gemm_fast_upper(const Product& p) {
 
 int gemm_fast_upper_launch(const Product& p, hipStream_t stream) {
     if (!gemm_fast_upper(p)) return QS_ERR_BAD_EXTENT;
+    return p.m % 128 == 0 ? launch_fast<false, 4, 4, true, false>(p, stream) : launch_fast<false, 2, 4, true, false>(p, stream);
+}
+
+// Does a product go on the lower-from-mirror forms (Product::lower_from_mirror, read with the flag set or not)?  A triangular
+// fp64 batch of square A entries, side x side with lda == side and the entries at least side^2 apart, side a multiple of the
+// 16-column block and of the row tile (128 rows, or 64 where side is no multiple of 128), no accumulate; and the conditions
+// of gemm_fast_try and launch_fast up to the exact DMA forms.
+bool gemm_fast_lower(const Product& p) {
+    if (!g_tune.gemm_fast || !QS_FAST_DMA || p.dtype != QS_F64 || p.pairs <= 0 || p.mirror || p.upper || p.accumulate) return false;
+    if (p.m != p.k || p.lda != p.k || p.sa < p.k * p.k) return false;
+    if (32 * p.lda * 8 + 256 >= (int64_t(1) << 32)) return false;
+    if (p.m >= (int64_t(1) << 31) - 256 || p.n >= (int64_t(1) << 31) - 256) return false;
+    const bool even = aligned(p.A, 16) && aligned(p.B, 16) && aligned(p.C, 16) && !(p.lda & 1) && !(p.ldb & 1) &&
+                      !(p.ldc & 1) && !(p.sa & 1) && !(p.sb & 1) && !(p.sc & 1);
+    // (16-byte items at 16-byte addresses only: the turned blocks were not probed at odd strides)
+    return even && p.k % 16 == 0 && p.m % 64 == 0 && p.n % 128 == 0;
+}
+
+int gemm_fast_lower_launch(const Product& p, hipStream_t stream) {
+    if (!p.lower_from_mirror || !gemm_fast_lower(p)) return QS_ERR_BAD_EXTENT;
     return p.m % 128 == 0 ? launch_fast<false, 4, 4, true, false>(p, stream) : launch_fast<false, 2, 4, true, false>(p, stream);
 }
 

@@ -2,7 +2,9 @@
 // argument, QS_FAST_PAIRS says whether it is a FastPairsArgs (triangular batch: the remap in `decode`, nothing else) or, 2, a
 // FastPairsMirrorArgs (the same, and the epilogue of pair (i, j > i) also stores the tile transposed at pair (j, i)) or, 3, a
 // FastUpperArgs (the column triangle of Product::upper: the n-tile's decode, the B stage's lane offset and the epilogue's
-// column offsets; exact fp64 DMA forms only).  Text
+// column offsets; exact fp64 DMA forms only) or, 4, a FastPairsLowerArgs (the triangular batch whose A entries are square and
+// stored on their 16 x 16 blocks (G, J >= G) only: a block (G, J < G) of pair (i, j) is fetched as block (J, G) of pair (j, i) and
+// read from LDS the other way round; exact fp64 DMA forms only).  Text
 // inclusion, not a shared device function: the plain batch's kernels then compile exactly as they did before the
 // triangular batch existed (through a forced-inline function eight of them spilled other scalar registers).
 // No include guard on purpose.
@@ -70,6 +72,9 @@
 #if QS_FAST_PAIRS == 2
     static_assert(!CX && VEC && !EDGE, "the mirrored epilogue exists for the exact fp64 forms");
     int64_t b_mirror = 0;        // flat index j n + i of the pair that the last decode()'s pair (i, j) mirrors to
+#elif QS_FAST_PAIRS == 4
+    static_assert(QS_FAST_DMA && !CX && VEC && !EDGE && TN == 4, "the lower-from-mirror form exists for the exact fp64 DMA forms");
+    int64_t b_mirror = 0;        // flat index j n + i of the pair whose blocks (J, G) are the last decode()'s pair's blocks (G, J < G)
 #endif
     // tile coordinates of virtual block v
     auto decode = [&](unsigned v, int& m0, int& n0, int64_t& b) {
@@ -88,7 +93,7 @@
         // triangular batch: entry b is a pair (i, j >= i), its operands sit at the flat index i n + j
 #if QS_FAST_PAIRS == 1
         b = (uint32_t)__builtin_amdgcn_readfirstlane((int)triangle_flat((uint32_t)b, g.pairs));
-#elif QS_FAST_PAIRS == 2
+#elif QS_FAST_PAIRS == 2 || QS_FAST_PAIRS == 4
         {
             const uint32_t pi = triangle_row((uint32_t)b, g.pairs), pj = pi + ((uint32_t)b - triangle_row_start(pi, g.pairs));
             b = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pi * g.pairs + pj));
@@ -120,13 +125,33 @@
     unsigned f_v = blockIdx.x;   // virtual block the cursor is in
     int f_k = 0;                 // next k-stage to load in that tile
     bool f_valid = true;
+#if QS_FAST_PAIRS == 4
+    // A wave-instruction i of this wave is one half (rows 8 (wave & 1) ...) of the 16-row group f_g + 2 i of the entry.  At the
+    // k-stages f_k >= that group the block (group, f_k) is there and is fetched as ever (base a_nat + i RA rows, a_step per
+    // stage); before, the mirror entry's block (f_k, group) lands as it is: its rows 16 f_k + 8 (wave & 1) ..., columns
+    // 16 group ..., t_step = 16 rows per stage.  voff_a serves both (8 rows x 8 slots, row stride lda, and the wave's 8 wave rows,
+    // which the turned base takes off again).
+    uint64_t a_nat = 0;
+    int f_g = 0;
+    const size_t t_step = (size_t)16 * g.lda * 8;
+#endif
     auto aim = [&](unsigned v) {
         int m0, n0; int64_t b;
         decode(v, m0, n0, b);
         const char* Ab = reinterpret_cast<const char*>(g.A + (b * g.sa + (int64_t)m0 * g.lda) * ES);
         const char* Bb = reinterpret_cast<const char*>(g.B + (b * g.sb + n0) * ES);
+#if QS_FAST_PAIRS == 4
+        a_nat = uniform64(reinterpret_cast<uint64_t>(Ab));
+        f_g = (m0 >> 4) + (wave >> 1);
+        const uint64_t a_turned = uniform64(reinterpret_cast<uint64_t>(g.A + b_mirror * g.sa) +
+                                            (uint64_t)((int64_t)(8 * (wave & 1) - 8 * wave) * g.lda * 8));
+#pragma unroll
+        for (int i = 0; i < NA; ++i)
+            a_ptr[i] = f_g + 2 * i > 0 ? a_turned + (uint64_t)(f_g + 2 * i) * 128u : a_nat + (uint64_t)i * RA * g.lda * ESZ;
+#else
 #pragma unroll
         for (int i = 0; i < NA; ++i) a_ptr[i] = uniform64(reinterpret_cast<uint64_t>(Ab + (size_t)i * RA * g.lda * ESZ));
+#endif
         // B rows: the wave's first row of an item step is part of the scalar base (no limit on
         // ldb); only when a wave-instruction spans several rows (IPR_B < 64) does the lane
         // offset carry a row term
@@ -180,6 +205,30 @@
             }
         }
     }
+#if QS_FAST_PAIRS == 4
+    // A turned block sits in LDS as [dd = d - 16 j][cc = c - 16 G]: lane (r = lane & 15, kq = lane >> 4) reads at k-step kk row
+    // dd = 4 kk + kq, slot (r >> 1) ^ ((dd >> 1) & 7), double r & 1 -- the slot is the natural read's, so the two offsets differ
+    // by 16 (4 kk + kq - r) + (r & 1) - (kq & 1), one lane value and 64 kk.  A half wave then reads two whole adjacent 128-byte
+    // rows.  Row group i of the wave's rows (group c_g + i of the entry) is read turned at the k-stages c_k < c_g + i: the
+    // offsets are rewritten at the tile's first stage and at the group's own, ahead of the first fragments of that stage.
+    const unsigned rd_a_turn = (unsigned)(16 * ((lane >> 4) - (lane & 15)) + (lane & 1) - ((lane >> 4) & 1));
+    auto turn = [&](int i, bool to_turned) __attribute__((always_inline)) {
+#pragma unroll
+        for (int kk = 0; kk < KS; ++kk) {
+            if (to_turned) rd_a_dma[kk][i] += rd_a_turn + 64u * kk; else rd_a_dma[kk][i] -= rd_a_turn + 64u * kk;
+            asm volatile("" : "+v"(rd_a_dma[kk][i]));
+        }
+    };
+    int c_g = 0;                 // first 16-row group of this wave's rows in the tile being computed
+    auto open_tile = [&](unsigned v) {
+        int m0, n0; int64_t b;
+        decode(v, m0, n0, b);
+        c_g = (m0 >> 4) + wm * TM;
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+            if (c_g + i > 0) turn(i, true);
+    };
+#endif
     // DMA destinations: the wave's first 16-byte item of each item step (lane-linear after it)
     double* dst_a = As + wave * 64 * DPI;
     double* dst_b = Bs + wave * SB;
@@ -219,9 +268,17 @@
         typedef __attribute__((address_space(3))) void* lds_ptr;
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
+#if QS_FAST_PAIRS == 4
+            // (the group's own stage: from here on its blocks are the entry's own)
+            if (f_k == f_g + 2 * i) a_ptr[i] = a_nat + (uint64_t)i * RA * g.lda * ESZ + (uint64_t)f_k * a_step;
+#endif
             const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(a_ptr[i]), (short)0, -1, 0x00020000);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr)(dst_a + buf * A_STAGE + i * RA * SA), 16, (int)voff_a, 0, 0, 0);
+#if QS_FAST_PAIRS == 4
+            a_ptr[i] += f_k < f_g + 2 * i ? t_step : a_step;
+#else
             a_ptr[i] += a_step;
+#endif
         }
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
@@ -457,6 +514,9 @@
         if (f_valid) fetch(B1{});      // stage 1
         if (f_valid) fetch(B0{});      // stage 2
     }
+#if QS_FAST_PAIRS == 4
+    open_tile(blockIdx.x);
+#endif
     read_frags(B0{}, 0, a0, b0);
 
     unsigned c_v = blockIdx.x;   // virtual block being computed
@@ -513,6 +573,18 @@
             __syncthreads();
             if (f_valid) fetch(NXT{});         // stage gs+3 into the set just written out
         }
+#if QS_FAST_PAIRS == 4
+        // (every fragment read of this stage has been issued: the offsets may go over to the next stage's)
+        if (has_next) {
+            if (c_k + 1 == nk) {
+                open_tile(c_v + P);
+            } else {
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+                    if (c_k + 1 == c_g + i) turn(i, false);
+            }
+        }
+#endif
         if (has_next) read_frags(NXT{}, 0, a0, b0);
         __builtin_amdgcn_sched_barrier(0);
         if (!EDGE || KS - 1 < ks_live) mfma_step(a1, b1, F_{});

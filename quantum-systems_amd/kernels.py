@@ -190,19 +190,24 @@ mixed_real_u = True
 
 @_plain
 def gemm_raw(dt, A, B, out, m, n, k, lda, ldb, ldc, batch=1, sa=0, sb=0, sc=0,
-             accumulate=False, a_off=0, b_off=0, c_off=0, pairs=None, mirror=False):
+             accumulate=False, a_off=0, b_off=0, c_off=0, pairs=None, mirror=False, lower=False):
     """Thin call of ``qs_matmul`` on tensors already prepared by the caller
     (contiguous storage, matching dtype); offsets and strides in elements.
 
     ``pairs=n``: ``qs_matmul_pairs`` -- the batch is the upper triangle of an n x n grid (``batch`` is not used), the
     operands of pair (i, j >= i) at ``(i * n + j)`` strides; with ``mirror=True`` ``qs_matmul_pairs_mirrored``, which also
-    stores pair (i, j > i) transposed at (j, i) and raises ``ValueError`` where no kernel can."""
+    stores pair (i, j > i) transposed at (j, i) and raises ``ValueError`` where no kernel can; with ``lower=True``
+    ``qs_matmul_pairs_lower``, which takes the 16 x 16 blocks below the block diagonal of the square ``A`` entry of pair
+    (i, j) from the mirror entry (j, i) and raises ``ValueError`` where no kernel can."""
     lib = _lib.load()
     es = 16 if dt == _C128 else 8
-    if mirror and pairs is None:
-        raise ValueError("mirror=True needs pairs=n")
+    if (mirror or lower) and pairs is None:
+        raise ValueError("mirror=True and lower=True need pairs=n")
+    if mirror and lower:
+        raise ValueError("mirror=True and lower=True are two different launches")
     fn, name, count = ((lib.qs_matmul, "qs_matmul", batch) if pairs is None else
                        (lib.qs_matmul_pairs_mirrored, "qs_matmul_pairs_mirrored", pairs) if mirror else
+                       (lib.qs_matmul_pairs_lower, "qs_matmul_pairs_lower", pairs) if lower else
                        (lib.qs_matmul_pairs, "qs_matmul_pairs", pairs))
     with _on_device_of(A, B, out):
         _ran(

@@ -1,7 +1,7 @@
 """Same-process A/B of the transform's exchange-symmetry route against the plain route, and the route's phases.
 
     python tools/exchange_route_ab.py --sizes 160,192,224,256 --dtype f64 [--blocks 32,64,128] [--blocks-d 8,16,64]
-                                      [--pairs 0,1] [--orders 0,2] [--leading 0,2] [--upper 0,2] [--reps 5]
+                                      [--pairs 0,1] [--orders 0,2] [--leading 0,2] [--upper 0,2,3] [--reps 5]
                                       [--phases [--c-blocks 16,64]]
 
 Per size: one symmetric tensor (bench.make_inputs), then the plain route (`exchange=0`) and every (block, block_d)
@@ -15,7 +15,9 @@ the launches per block / per row of `exchange_pairs=0` and as the one triangular
 indices as one product and the closing blocks, and on pairs between the two transposes (`exchange_leading`); with 2 in
 the list `--phases` also replays the pair movers and the two products between them, and prints the total of either form.
 `--upper 0,2` times order 2 with its leading indices on the column triangle (`exchange_upper`: two `qs_matmul_upper`
-products and the fill); with 2 in the list `--phases` replays those three launches too."""
+products and the fill); with 2 in the list `--phases` replays those three launches too.  `--upper 3` is that form without
+the fill (`exchange_upper=2` and `exchange_lower=2`: the d launch takes the blocks below the block diagonal from the mirror
+pair, `qs_matmul_pairs_lower`; 2 alone keeps the fill); with 3 in the list `--phases` adds that d launch where it exists."""
 
 import argparse
 import os
@@ -40,7 +42,7 @@ def med(xs):
 
 
 def phases(torch, K, u, C, Ct, out, blk, blk_d, reps, c_blocks=(), other_order=False, order=0, leading_pairs=False,
-           leading_upper=False):
+           leading_upper=False, lower_d=False):
     """The route's launches, phase by phase (T1 and X in one spare buffer, T2 in `out`), in the order `order` takes (0: d, c,
     mirror, a, closing, mirror; 2: a, closing, d, c, mirror -- X1 and Y in the spare buffer, X2 in `out`).  `c_blocks`: also time the c phase
     with every row a of a block [a0, a1) batched over b >= a0 instead of b >= a (needs blk_d to divide those blocks)."""
@@ -68,8 +70,8 @@ def phases(torch, K, u, C, Ct, out, blk, blk_d, reps, c_blocks=(), other_order=F
             b0 = a // cb * cb
             K.gemm_raw(dt, CT, W, out, L, L, L, L, L, L, L - b0, 0, L2, L2, b_off=(a * L + b0) * L2, c_off=(a * L + b0) * L2)
 
-    def d_pairs(src=u, dst=W, small=C):
-        K.gemm_raw(dt, src, small, dst, L, L, L, L, L, L, 0, L2, 0, L2, pairs=L)
+    def d_pairs(src=u, dst=W, small=C, lower=False):
+        K.gemm_raw(dt, src, small, dst, L, L, L, L, L, L, 0, L2, 0, L2, pairs=L, lower=lower)
 
     def c_pairs(mirror=False, src=W, dst=out, small=CT):
         K.gemm_raw(dt, small, src, dst, L, L, L, L, L, L, 0, 0, L2, L2, pairs=L, mirror=mirror)
@@ -111,6 +113,9 @@ def phases(torch, K, u, C, Ct, out, blk, blk_d, reps, c_blocks=(), other_order=F
             steps += [("upper: b", lambda: K.matmul_upper(dt, Ct, u, W, L, L, 1, L, L, L2, L2, L, 0, L3, L3)),
                       ("upper: a", lambda: K.matmul_upper(dt, Ct, W, out, L, L, L, L, L, L3, L3, 1)),
                       ("upper: fill", lambda: K.exchange_mirror_lower_(out.view(L, L, L, L)))]
+            if lower_d:
+                # exchange_lower=2: d on the blocks (G, J >= G) of every pair, in the place of "upper: fill" and "d"
+                steps.append(("upper: d, no fill", lambda: d_pairs(out, lower=True)))
     else:
         other = [("other order: b full", b_full), ("other order: a blocks", a_blocks)] if other_order else []
         steps = [("check", check), ("d, per block", d), ("d", d_pairs)] + [(f"c, b >= block {cb}", lambda cb=cb: c(cb)) for cb in c_blocks] + [
@@ -134,7 +139,12 @@ def phases(torch, K, u, C, Ct, out, blk, blk_d, reps, c_blocks=(), other_order=F
     if order == 2 and leading_upper:
         blocks = med(times["a"][1:]) + med(times["closing product"][1:])
         upper = sum(med(times[name][1:]) for name, _ in steps if name.startswith("upper: "))
+        if lower_d:
+            upper -= med(times["upper: d, no fill"][1:])
         print(f"    leading indices: a + closing product {blocks:8.3f} ms, on the column triangle {upper:8.3f} ms; phases total on it {total - blocks + upper:8.3f} ms")
+        if lower_d:
+            fill, d_old, d_new = (med(times[n][1:]) for n in ("upper: fill", "d", "upper: d, no fill"))
+            print(f"    fill + d {fill + d_old:8.3f} ms, d without the fill {d_new:8.3f} ms; phases total on it {total - blocks + upper - fill - d_old + d_new:8.3f} ms")
     del W
 
 
@@ -147,7 +157,7 @@ def main():
     ap.add_argument("--pairs", default="1", help="exchange_pairs settings of the route to time, e.g. 0,1")
     ap.add_argument("--orders", default="1", help="exchange_order settings of the route to time, e.g. 0,2 (1: the automatic rule)")
     ap.add_argument("--leading", default="1", help="exchange_leading settings of the route to time, e.g. 0,2 (1: the automatic rule)")
-    ap.add_argument("--upper", default="1", help="exchange_upper settings of the route to time, e.g. 0,2 (1: the automatic rule)")
+    ap.add_argument("--upper", default="1", help="exchange_upper settings of the route to time, e.g. 0,2 (1: the automatic rule; 3: 2 without the fill, exchange_lower=2)")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--phases", action="store_true")
     ap.add_argument("--other-order", action="store_true", help="with --phases: also time b full, then a per block of rows")
@@ -172,8 +182,9 @@ def main():
                 K.transform_two_body(u, C, Ct, out=out)
 
         def route(b, bd, pr, od, ld, up=1):
+            lower = {"exchange_lower": 2} if up == 3 else {}
             with K.tuning(exchange=2, exchange_block=b, exchange_block_d=bd, exchange_pairs=pr, exchange_order=od, exchange_leading=ld,
-                          exchange_upper=up):
+                          exchange_upper=min(up, 2), **lower):
                 K.transform_two_body(u, C, Ct, out=out)
 
         plain()
@@ -205,7 +216,8 @@ def main():
                 phases(torch, K, u, C, Ct, out, configs[0][0], configs[0][1], args.reps,
                        [int(x) for x in args.c_blocks.split(",") if x], args.other_order, od,
                        leading_pairs=od == 2 and any(cfg[4] == 2 for cfg in configs),
-                       leading_upper=od == 2 and not dtype.is_complex and any(cfg[5] == 2 for cfg in configs))
+                       leading_upper=od == 2 and not dtype.is_complex and any(cfg[5] >= 2 for cfg in configs),
+                       lower_d=od == 2 and not dtype.is_complex and l % 128 == 0 and any(cfg[5] == 3 for cfg in configs))
         del u, out
         K.workspace.release()
         torch.cuda.empty_cache()
