@@ -637,6 +637,11 @@ const char* qs_last_dispatch(void);
  *     a strip launch: 0 = one per CU, 1 ... 4096 = at most that many, each
  *     walking more tiles; any other value is refused with QS_ERR_BAD_EXTENT;
  *     the result does not depend on either key),
+ *     "gemm_stream_wgs" (the most workgroups of a launch of the
+ *     small-coefficient streaming product: 0 = as many as stay resident,
+ *     1 ... 4096 = at most that many, each wave walking more column blocks;
+ *     any other value is refused with QS_ERR_BAD_EXTENT; the result does not
+ *     depend on it),
  *     "gemm_fast_unaligned" (0 = 8-byte global items at
  *     odd strides as in rounds 1-3, 1 = 16-byte items at any 8-byte-aligned
  *     address), "comm_drop_wait" (TEST HOOK of the sharded entry points: a bit

@@ -245,6 +245,11 @@ int qs_tuning_set(const char* key, int64_t value) {
         g_tune.gemm_strip_wgs = (int)value;
         return QS_OK;
     }
+    if (!strcmp(key, "gemm_stream_wgs")) {
+        if (value < 0 || value > 4096) return QS_ERR_BAD_EXTENT;
+        g_tune.gemm_stream_wgs = (int)value;
+        return QS_OK;
+    }
     if (!strcmp(key, "gemm_fast_unaligned")) { g_tune.gemm_fast_unaligned = (int)value; return QS_OK; }
     if (!strcmp(key, "comm_drop_wait")) { g_tune.comm_drop_wait = (int)value; return QS_OK; }
     if (!strcmp(key, "sandwich_mode")) { g_tune.sandwich_mode = (int)value; return QS_OK; }

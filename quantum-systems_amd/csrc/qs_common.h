@@ -274,6 +274,8 @@ struct Tuning {
                                  // 16): 1 by estimated time, 2 wherever they exist, 0 off
     int gemm_skinny = 1;         // 0 disables the short-and-wide streaming product
     int gemm_stream = 1;         // 0 disables the small-coefficient streaming product, 2 = never split rows over two waves
+    int gemm_stream_wgs = 0;     // most workgroups of a stream launch, 1 ... 4096 (0 = as many as stay resident): a short block list walks on few
+                                 // waves, across batch slices -- tests reach the walk at the smallest eligible shape (tests/test_gpu_stream_forms.py)
     int slab_pair = 1;           // 0 disables the fused (d, c) pass, 2 = one wave per slab always
     int sandwich_t2 = -1;        // the intermediate of the two fused passes stored transposed, (r, s, a, b): -1 automatic, 0 never, 1 always
     int sandwich_v2 = -1;        // the balanced small-basis kernel with a cooperative fetch (qs_sandwich4b.hip): -1 automatic, 0 never, 1 wherever it exists,

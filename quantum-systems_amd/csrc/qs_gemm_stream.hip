@@ -334,6 +334,7 @@ static int launch_stream(const StreamArgs& g0, int64_t batch, hipStream_t stream
                                               (TMW * KQ > 8) ? 1 : 2);
     int64_t wgs = cdiv(total * SPLIT, 4);
     if (wgs > (int64_t)wg_per_cu * n_cu) wgs = (int64_t)wg_per_cu * n_cu;
+    if (g_tune.gemm_stream_wgs > 0 && wgs > g_tune.gemm_stream_wgs) wgs = g_tune.gemm_stream_wgs;   // (fewer waves, each walking more blocks)
     hipLaunchKernelGGL((gemm_stream_left_kernel<TMW, SPLIT, KQ, NT, VEC>), dim3((unsigned)wgs), dim3(256), 0, stream, g);
     note_dispatch("qs::gemm_stream_left_kernel<%d, %d, %d, %d, %s>", TMW, SPLIT, KQ, NT, VEC ? "true" : "false");
     return launch_status("gemm_stream launch");
@@ -353,6 +354,7 @@ static int launch_stream_cx(const StreamArgs& g0, int64_t batch, hipStream_t str
                                               (TMW * KQ > 3) ? 1 : 2);
     int64_t wgs = cdiv(total * SPLIT, 4);
     if (wgs > (int64_t)wg_per_cu * n_cu) wgs = (int64_t)wg_per_cu * n_cu;
+    if (g_tune.gemm_stream_wgs > 0 && wgs > g_tune.gemm_stream_wgs) wgs = g_tune.gemm_stream_wgs;   // (fewer waves, each walking more blocks)
     hipLaunchKernelGGL((gemm_stream_left_cx_kernel<TMW, SPLIT, KQ>), dim3((unsigned)wgs), dim3(256), 0, stream, g);
     note_dispatch("qs::gemm_stream_left_cx_kernel<%d, %d, %d>", TMW, SPLIT, KQ);
     return launch_status("gemm_stream_cx launch");
@@ -368,8 +370,11 @@ int gemm_stream_try(const Product& p, hipStream_t stream) {
     if (m > 64 || k > 64) return 1;
     if (batch > 1 && p.sa != 0) return 1;                // A is the shared coefficient matrix
     // 32-bit offsets inside a batch slice, with the "column >= n" marker bit free (the range checks also rely on
-    // ldb, ldc >= n: rows do not overlap)
-    if (((k + 3) * ldb + n) * esz >= (int64_t(1) << 31) || ((m + 63) * ldc + n) * esz >= (int64_t(1) << 31)) return 1;
+    // ldb, ldc >= n: rows do not overlap).  The ring addresses ALL 16 KQ rows of B, the ones past k included (they must
+    // land past the records, not wrap below 2^32 back into them: with k <= 4 a bound on k + 3 rows let row 15 wrap into
+    // the padding of row 0, and 0.0 times a NaN there reached every column -- tests/test_gpu_stream_forms.py)
+    const int64_t ring_rows = 16 * cdiv(k, 16);
+    if ((ring_rows * ldb + n) * esz >= (int64_t(1) << 31) || ((m + 63) * ldc + n) * esz >= (int64_t(1) << 31)) return 1;
     if (batch >= (int64_t(1) << 30)) return 1;
     // a stream long enough to keep every wave busy for a few blocks.  Measured against the tiled kernels
     // (profiles/r01_gemm_notes.txt): fp64 wins from l = 32 up (+5...10 %), complex128 only around l = 48

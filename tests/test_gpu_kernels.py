@@ -930,10 +930,15 @@ def test_skinny_product_vs_oracle(K, m, k, cplx):
 # ------------------------------------------- small-coefficient streaming product (qs_gemm_stream.hip)
 
 
+# (m, k, n, batch): (a stream kernel runs for fp64, for complex128).  complex128 k > 48 is refused, and the whole-tile fp64
+# product (64, 64, 4096) goes to the exact tiled form -- at n = 4100 it streams
+_STREAM_SHAPES = {(55, 55, 55 * 55, 55): (True, False), (55, 55, 55, 3025): (True, False), (64, 64, 4096, 16): (False, False),
+                  (64, 64, 4100, 16): (True, False), (1, 1, 70000, 1): (True, True), (17, 3, 1000, 70): (True, True),
+                  (40, 61, 33, 2100): (True, False), (64, 5, 100001, 1): (True, True), (33, 64, 130, 600): (True, False)}
+
+
 @pytest.mark.parametrize("cplx", [False, True])
-@pytest.mark.parametrize("m,k,n,batch", [(55, 55, 55 * 55, 55), (55, 55, 55, 3025), (64, 64, 4096, 16),
-                                          (1, 1, 70000, 1), (17, 3, 1000, 70), (40, 61, 33, 2100),
-                                          (64, 5, 100001, 1), (33, 64, 130, 600)])
+@pytest.mark.parametrize("m,k,n,batch", list(_STREAM_SHAPES))
 def test_stream_product_vs_oracle(K, m, k, n, batch, cplx):
     # the c, b, a contractions of a small-l transform: A (m x k) is Ct or C^T, shared by the batch
     rng = np.random.default_rng(m * 1000 + k * 10 + batch)
@@ -943,12 +948,15 @@ def test_stream_product_vs_oracle(K, m, k, n, batch, cplx):
         A = A + 1j * rng.standard_normal((m, k))
         B = B + 1j * rng.standard_normal((batch, k, n))
     ref = np.matmul(A, B)
+    streams = _STREAM_SHAPES[(m, k, n, batch)][cplx]
     try:
         K.tuning_set("gemm_stream", 0)
         general = host(K.matmul(dev(A), dev(B)))
+        assert "gemm_stream_left" not in K.last_dispatch(), K.last_dispatch()
         for knob in (1, 2):       # 2 = never split the rows of A over two waves
             K.tuning_set("gemm_stream", knob)
             got = host(K.matmul(dev(A), dev(B)))
+            assert ("gemm_stream_left" in K.last_dispatch()) == streams, f"gemm_stream={knob}: {K.last_dispatch()}"
             assert relerr(got, ref) <= 1e-13, f"gemm_stream={knob}"
             assert np.array_equal(got, general), f"gemm_stream={knob}: same k order as the tiled kernels"
     finally:
