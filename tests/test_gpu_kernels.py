@@ -93,8 +93,9 @@ def test_mixed_real_u_complex_C_runs_without_a_complex_copy_of_u(K, golden):
     assert (got - cast).abs().max().item() <= 1e-13 * cast.abs().max().item()
     # oracle sweep through the new route: odd sizes, rectangular both ways, explicit C~, whole tiles, the fused sizes
     rng = np.random.default_rng(33)
+    # ((11, 9) ... (51, 52): pair4s_kernel<N, true> for N = 3, 6, 7, 9, 11, 13, which the other shapes do not reach)
     for (L, M) in ((5, 5), (9, 14), (21, 13), (13, 15), (20, 20), (31, 29), (40, 40), (47, 45), (64, 64), (55, 55), (56, 53), (70, 66),
-                   (128, 128)):
+                   (128, 128), (11, 9), (23, 21), (27, 28), (35, 36), (43, 41), (51, 52)):
         un = rng.standard_normal((L,) * 4)
         Cn = (rng.standard_normal((L, M)) + 1j * rng.standard_normal((L, M))) / np.sqrt(L)
         Ctn = (rng.standard_normal((M, L)) + 1j * rng.standard_normal((M, L))) / np.sqrt(L)
@@ -191,6 +192,7 @@ def test_streamed_fp64_kernel_is_bit_identical_to_the_16_wide_path(K):
                                55, 56, 57, 60, 63, 64)]
     shapes += [(7, 5), (10, 12), (18, 20), (20, 17), (30, 32), (32, 29), (55, 53), (62, 64)]     # rectangular within one quad count
     shapes += [(65, 65), (66, 68), (71, 69), (77, 78), (84, 81), (91, 91), (96, 93)]             # two workgroups per item quad
+    shapes += [(75, 73), (86, 88)]                                # quad4s_kernel<19, 2> and <22, 2>: with them every instantiation
     for (L, M) in shapes:
         u = dev(rng.standard_normal((L,) * 4))
         C = dev(rng.standard_normal((L, M)) / np.sqrt(L))
@@ -1003,6 +1005,23 @@ def test_fused_dc_pass_equals_two_products(K, L, M):
     assert relerr(fused, ref) <= 1e-13
     assert np.array_equal(fused, plain) and np.array_equal(fused1, plain)
     np.testing.assert_allclose(part, orc.transform_two_body_dcb(u[3:9], C, Ct), rtol=1e-12, atol=1e-13)
+    # the same three settings with nothing ahead of the kernel (at equal quad counts quad4s or the sandwich kernels take the
+    # whole transform above): it runs for 1 and 2, and a slab of ceil(256 / L) + 1 rows (at most L) is past its 256-slab gate
+    rows = min(-(-256 // L) + 1, L)
+    a0 = min(2, L - rows)
+    runs = {}
+    for knob in (0, 2, 1):
+        with K.tuning(slab_pair=knob, sandwich=0, quad4s=0, small4=0):
+            whole = host(K.transform_two_body(dev(u), dev(C), dev(Ct)))
+            ran_whole = K.last_dispatch()
+            some = host(K.transform_two_body_partial(dev(u[a0:a0 + rows]), dev(C), dev(Ct)))
+            ran_some = K.last_dispatch()
+        assert ("qs::slab_pair" in ran_whole) == (knob != 0) and ("qs::slab_pair" in ran_some) == (knob != 0), (knob, ran_whole, ran_some)
+        runs[knob] = (whole, some)
+    assert np.array_equal(runs[0][0], plain)
+    for knob in (1, 2):
+        assert np.array_equal(runs[knob][0], plain) and np.array_equal(runs[knob][1], runs[0][1]), knob
+    np.testing.assert_allclose(runs[1][1], orc.transform_two_body_dcb(u[a0:a0 + rows], C, Ct), rtol=1e-12, atol=1e-13)
 
 
 def test_fused_dc_pass_keeps_non_finite_values_in_their_slabs(K):
