@@ -68,6 +68,21 @@
 #define QS_FAST_DMA 1
 #endif
 
+// Measurement only (wrong results): -DQS_FAST_ABLATE_EPI_COPIES=1 stores each accumulator block's own register quads as the
+// 16-byte items of the DMA forms' epilogue (same stores, bytes and addresses, none of the 124 vector moves that put an item
+// together from two accumulator blocks).  It bounds what any cheaper epilogue can gain: 0.03 ms of the exchange route's 74 ms
+// in this kernel at l = 256 (profiles/gemm_fast_epilogue_ab.txt), so the epilogue stays as it is.
+#ifndef QS_FAST_ABLATE_EPI_COPIES
+#define QS_FAST_ABLATE_EPI_COPIES 0
+#endif
+// The overloads (triangular batch, mirror, column triangle, lower from mirror) form the LDS destinations of a stage's DMA from
+// one opaque base per stage, so that none of them is a spilled scalar reloaded in every stage (qs_gemm_fast_body.h,
+// fetch_dma).  Results are unchanged, so this is also the ablation that bounds its own gain; -DQS_FAST_STAGE_M0=0 builds the
+// hoisted form for A/B.
+#ifndef QS_FAST_STAGE_M0
+#define QS_FAST_STAGE_M0 1
+#endif
+
 namespace qs {
 
 struct FastArgs {
@@ -130,6 +145,10 @@ void gemm_fast_kernel(const FastPairsMirrorArgs g) {
 #undef QS_FAST_PAIRS
 }
 
+// (`g` must stay this kernel's FIRST parameter: the body reads the fields that only a tile change needs from offset 0 of the
+// kernarg segment as a FastUpperArgs -- tile_args() in qs_gemm_fast_body.h.)
+static_assert(std::is_trivially_copyable<FastUpperArgs>::value && std::is_base_of<FastArgs, FastUpperArgs>::value,
+              "the kernarg segment begins with the argument's own bytes");
 template <bool CX, int TM, int TN, bool VEC, bool EDGE>
 __global__ __launch_bounds__(256, 2)
 void gemm_fast_kernel(const FastUpperArgs g) {

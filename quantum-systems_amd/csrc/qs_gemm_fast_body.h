@@ -57,8 +57,11 @@
     using item_t = typename Item::type;
 
     extern __shared__ __attribute__((aligned(16))) double smem[];
+    // (in doubles: where the B stages begin, and how far apart the waves' first DMA items of an item step lie -- 64 items of
+    // A, one row of B; fetch_dma forms the same addresses in bytes from these)
+    constexpr int B_BASE = 2 * A_STAGE, DST_A_WAVE = 64 * DPI, DST_B_WAVE = SB;
     double* As = smem;
-    double* Bs = smem + 2 * A_STAGE;
+    double* Bs = smem + B_BASE;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -76,28 +79,41 @@
     static_assert(QS_FAST_DMA && !CX && VEC && !EDGE && TN == 4, "the lower-from-mirror form exists for the exact fp64 DMA forms");
     int64_t b_mirror = 0;        // flat index j n + i of the pair whose blocks (J, G) are the last decode()'s pair's blocks (G, J < G)
 #endif
+    // The arguments as decode() reads them.  Column triangle: the fields that only a tile change needs (the tile grid, the
+    // triangle's three) are read from the kernarg segment there, through a pointer the compiler cannot see through, and so
+    // hold no scalar registers across the k-stages -- with them live the stage loop reloaded a spilled scalar in every stage.
+#if QS_FAST_PAIRS == 3 && QS_FAST_STAGE_M0
+    auto tile_args = [&]() {
+        auto ka = (const __attribute__((address_space(4))) FastUpperArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(ka));
+        return ka;
+    };
+#else
+    auto tile_args = [&]() { return &g; };
+#endif
     // tile coordinates of virtual block v
     auto decode = [&](unsigned v, int& m0, int& n0, int64_t& b) {
-        unsigned w = xcd_chunked_index_fast(v, g.total);
+        const auto* gd = tile_args();
+        unsigned w = xcd_chunked_index_fast(v, gd->total);
         int mt, nt;
-        if (g.group_along_m) {
-            mt = w % g.tiles_m; w /= g.tiles_m;
-            nt = w % g.tiles_n; w /= g.tiles_n;
+        if (gd->group_along_m) {
+            mt = w % gd->tiles_m; w /= gd->tiles_m;
+            nt = w % gd->tiles_n; w /= gd->tiles_n;
         } else {
-            nt = w % g.tiles_n; w /= g.tiles_n;
-            mt = w % g.tiles_m; w /= g.tiles_m;
+            nt = w % gd->tiles_n; w /= gd->tiles_n;
+            mt = w % gd->tiles_m; w /= gd->tiles_m;
         }
         // integer division runs on the vector ALU; bring the (wave-uniform) results back to
         // scalar registers so that every pointer derived from them stays an SGPR base
         b = __builtin_amdgcn_readfirstlane((int)w);
         // triangular batch: entry b is a pair (i, j >= i), its operands sit at the flat index i n + j
 #if QS_FAST_PAIRS == 1
-        b = (uint32_t)__builtin_amdgcn_readfirstlane((int)triangle_flat((uint32_t)b, g.pairs));
+        b = (uint32_t)__builtin_amdgcn_readfirstlane((int)triangle_flat((uint32_t)b, gd->pairs));
 #elif QS_FAST_PAIRS == 2 || QS_FAST_PAIRS == 4
         {
-            const uint32_t pi = triangle_row((uint32_t)b, g.pairs), pj = pi + ((uint32_t)b - triangle_row_start(pi, g.pairs));
-            b = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pi * g.pairs + pj));
-            b_mirror = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pj * g.pairs + pi));
+            const uint32_t pi = triangle_row((uint32_t)b, gd->pairs), pj = pi + ((uint32_t)b - triangle_row_start(pi, gd->pairs));
+            b = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pi * gd->pairs + pj));
+            b_mirror = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pj * gd->pairs + pi));
         }
 #endif
         m0 = __builtin_amdgcn_readfirstlane(mt) * BM;
@@ -105,11 +121,11 @@
         {
             // n-tile -> (stack entry e, tile t of its side x side matrix).  S x S super-blocks hold S^2 / 128 tiles of R rows each
             // and form an upper triangle themselves: super-block sb is the pair (I, J >= I), the tile's first element (I S + sub R, J S).
-            const uint32_t e = (uint32_t)nt / g.per_matrix, t = (uint32_t)nt - e * g.per_matrix;
-            const uint32_t tshift = 2u * g.sshift - 7u, sb = t >> tshift, sub = t & ((1u << tshift) - 1u);
-            const uint32_t ns = g.side >> g.sshift;
+            const uint32_t e = (uint32_t)nt / gd->per_matrix, t = (uint32_t)nt - e * gd->per_matrix;
+            const uint32_t tshift = 2u * gd->sshift - 7u, sb = t >> tshift, sub = t & ((1u << tshift) - 1u);
+            const uint32_t ns = gd->side >> gd->sshift;
             const uint32_t I = triangle_row(sb, ns), J = I + (sb - triangle_row_start(I, ns));
-            n0 = __builtin_amdgcn_readfirstlane((int)((e * g.side + (I << g.sshift) + sub * (128u >> g.sshift)) * g.side + (J << g.sshift)));
+            n0 = __builtin_amdgcn_readfirstlane((int)((e * gd->side + (I << gd->sshift) + sub * (128u >> gd->sshift)) * gd->side + (J << gd->sshift)));
         }
 #else
         n0 = __builtin_amdgcn_readfirstlane(nt) * BN;
@@ -186,13 +202,19 @@
     const double* rd_a_cx[2] = {As + (wm * 16 * TM + (lane & 15)) * SA + ((lane >> 4) ^ swz_r),
                                 As + (wm * 16 * TM + (lane & 15)) * SA + ((4 + (lane >> 4)) ^ swz_r)};
     // fp64: lane c of n-tile pair (2jp, 2jp+1) owns the ADJACENT columns 32jp + 2c, 32jp + 2c + 1,
-    // so one 16-byte LDS read feeds two MFMA tiles and the epilogue stores 16 bytes per lane
+    // so one 16-byte LDS read feeds two MFMA tiles and the epilogue stores 16 bytes per lane.  (Every such item is put
+    // together from two accumulator blocks, four vector moves and a wait state per store, 124 + 31 per tile and wave: with two
+    // waves per SIMD they cost nothing measurable, and a layout without them was slower -- profiles/gemm_fast_epilogue_ab.txt.)
     const double* rd_b = Bs + (lane >> 4) * SB + wn * 16 * TN + (CX ? 1 : 2) * (lane & 15);
     // DMA form: k = 4 kk + (lane >> 4) sits in slot (2 kk + (lane >> 5)) ^ ((row >> 1) & 7) of its row, an XOR with kk --
     // one offset per k-step of a stage (KS = 4) and, on top, per 16-row block i: the blocks are 2048 bytes apart, and
     // reads of one base at those distances are fused into ds_read2st64_b64, which banks over 32 banks instead of 64
     // (the even and odd rows of a half wave then collide: SQ_LDS_BANK_CONFLICT 1.1e9 per launch at l = 256).  An empty
     // asm makes each offset opaque, so no two fragment reads share a base (16 VGPRs, set once).
+    // (lower-from-mirror form: its offsets change inside a tile, so the shift to bytes and the base could not be hoisted and
+    // were a vector instruction per read: that form keeps whole LDS byte addresses)
+    typedef const __attribute__((address_space(3))) double* lds_cdouble;
+    constexpr unsigned RD_SC = (QS_FAST_PAIRS == 4 && QS_FAST_STAGE_M0) ? (unsigned)sizeof(double) : 1u;
     unsigned rd_a_dma[KS][TM];
     if constexpr (kDma) {
 #pragma unroll
@@ -200,7 +222,8 @@
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
                 rd_a_dma[kk][i] = (unsigned)((wm * 16 * TM + i * 16 + (lane & 15)) * SA +
-                                             2 * ((2 * kk + (lane >> 5)) ^ ((lane >> 1) & 7)) + ((lane >> 4) & 1));
+                                             2 * ((2 * kk + (lane >> 5)) ^ ((lane >> 1) & 7)) + ((lane >> 4) & 1)) * RD_SC;
+                if constexpr (RD_SC != 1u) rd_a_dma[kk][i] += (unsigned)(uintptr_t)(lds_cdouble)As;
                 asm volatile("" : "+v"(rd_a_dma[kk][i]));
             }
         }
@@ -211,11 +234,11 @@
     // by 16 (4 kk + kq - r) + (r & 1) - (kq & 1), one lane value and 64 kk.  A half wave then reads two whole adjacent 128-byte
     // rows.  Row group i of the wave's rows (group c_g + i of the entry) is read turned at the k-stages c_k < c_g + i: the
     // offsets are rewritten at the tile's first stage and at the group's own, ahead of the first fragments of that stage.
-    const unsigned rd_a_turn = (unsigned)(16 * ((lane >> 4) - (lane & 15)) + (lane & 1) - ((lane >> 4) & 1));
+    const unsigned rd_a_turn = (unsigned)(16 * ((lane >> 4) - (lane & 15)) + (lane & 1) - ((lane >> 4) & 1)) * RD_SC;
     auto turn = [&](int i, bool to_turned) __attribute__((always_inline)) {
 #pragma unroll
         for (int kk = 0; kk < KS; ++kk) {
-            if (to_turned) rd_a_dma[kk][i] += rd_a_turn + 64u * kk; else rd_a_dma[kk][i] -= rd_a_turn + 64u * kk;
+            if (to_turned) rd_a_dma[kk][i] += rd_a_turn + 64u * RD_SC * kk; else rd_a_dma[kk][i] -= rd_a_turn + 64u * RD_SC * kk;
             asm volatile("" : "+v"(rd_a_dma[kk][i]));
         }
     };
@@ -230,8 +253,8 @@
     };
 #endif
     // DMA destinations: the wave's first 16-byte item of each item step (lane-linear after it)
-    double* dst_a = As + wave * 64 * DPI;
-    double* dst_b = Bs + wave * SB;
+    double* dst_a = As + wave * DST_A_WAVE;
+    double* dst_b = Bs + wave * DST_B_WAVE;
 
     // two staging register sets: the data of global stage s waits in set s & 1, so a load has
     // two stages (not one) to arrive from HBM before it is written to LDS
@@ -266,6 +289,22 @@
     auto fetch_dma = [&](auto buf_c) {
         constexpr int buf = decltype(buf_c)::value;
         typedef __attribute__((address_space(3))) void* lds_ptr;
+#if QS_FAST_PAIRS != 0 && QS_FAST_STAGE_M0
+        // The sixteen destinations (two buffers x NDMA) are loop-invariant sums: hoisted, they are sixteen scalars that the
+        // overloads have no room for, and each came back through a v_readlane in every stage.  One opaque base per call
+        // keeps them one scalar add each, and both bases come from the wave's number: dst_a and dst_b above, in bytes, from
+        // the same constants.  (The plain batch has the room: its kernels stay as they were.)
+        unsigned wave_o = (unsigned)wave;
+        asm volatile("" : "+s"(wave_o));
+        const unsigned lds_0 = (unsigned)(uintptr_t)(lds_ptr)smem;
+        const unsigned lds_a = lds_0 + wave_o * (unsigned)(DST_A_WAVE * sizeof(double));
+        const unsigned lds_b = lds_0 + (unsigned)(B_BASE * sizeof(double)) + wave_o * (unsigned)(DST_B_WAVE * sizeof(double));
+#define QS_FAST_DST_A(off) ((lds_ptr)(uintptr_t)(lds_a + (unsigned)((off) * sizeof(double))))
+#define QS_FAST_DST_B(off) ((lds_ptr)(uintptr_t)(lds_b + (unsigned)((off) * sizeof(double))))
+#else
+#define QS_FAST_DST_A(off) ((lds_ptr)(dst_a + (off)))
+#define QS_FAST_DST_B(off) ((lds_ptr)(dst_b + (off)))
+#endif
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
 #if QS_FAST_PAIRS == 4
@@ -273,7 +312,7 @@
             if (f_k == f_g + 2 * i) a_ptr[i] = a_nat + (uint64_t)i * RA * g.lda * ESZ + (uint64_t)f_k * a_step;
 #endif
             const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(a_ptr[i]), (short)0, -1, 0x00020000);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr)(dst_a + buf * A_STAGE + i * RA * SA), 16, (int)voff_a, 0, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, QS_FAST_DST_A(buf * A_STAGE + i * RA * SA), 16, (int)voff_a, 0, 0, 0);
 #if QS_FAST_PAIRS == 4
             a_ptr[i] += f_k < f_g + 2 * i ? t_step : a_step;
 #else
@@ -283,9 +322,11 @@
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
             const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(b_ptr[i]), (short)0, -1, 0x00020000);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr)(dst_b + buf * B_STAGE + i * RPS * SB), 16, (int)voff_b, 0, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, QS_FAST_DST_B(buf * B_STAGE + i * RPS * SB), 16, (int)voff_b, 0, 0, 0);
             b_ptr[i] += b_step;
         }
+#undef QS_FAST_DST_A
+#undef QS_FAST_DST_B
         if (++f_k == nk) {
             f_k = 0;
             f_v += P;
@@ -344,7 +385,9 @@
         for (int p = 0; p < NP; ++p) {
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
-                if constexpr (kDma) af[p][i] = As[rd_a_dma[kk][i] + buf * A_STAGE];
+                if constexpr (kDma && RD_SC != 1u)
+                    af[p][i] = *(lds_cdouble)(uintptr_t)(rd_a_dma[kk][i] + (unsigned)(buf * A_STAGE * sizeof(double)));
+                else if constexpr (kDma) af[p][i] = As[rd_a_dma[kk][i] + buf * A_STAGE];
                 else af[p][i] = as[p * BM * SA + i * 16 * SA + kk * 4];
             }
             if constexpr (CX) {
@@ -425,7 +468,13 @@
                         for (int jp = 0; jp < TN / 2; ++jp) {
                             if (row_ok && (!guard || col_l + jp * 32 + 1 < g.n)) {
                                 f64x2* dst = reinterpret_cast<f64x2*>(crow + jp * jp_step);
+#if QS_FAST_ABLATE_EPI_COPIES
+                                // (measurement only: the item is half of ONE accumulator block, registers as they lie)
+                                f64x2 v2 = kDma ? f64x2{acc[0][i][2 * jp + (r >> 1)][2 * (r & 1)], acc[0][i][2 * jp + (r >> 1)][2 * (r & 1) + 1]}
+                                                : f64x2{acc[0][i][2 * jp][r], acc[0][i][2 * jp + 1][r]};
+#else
                                 f64x2 v2 = f64x2{acc[0][i][2 * jp][r], acc[0][i][2 * jp + 1][r]};
+#endif
                                 if constexpr (add) v2 += *dst;
                                 QS_FAST_STORE(dst, v2);
                             } else if (guard && row_ok && col_l + jp * 32 < g.n) {   // odd n: the last column alone
