@@ -1382,6 +1382,41 @@ int qs_tdho_coulomb_quadrature_workspace(int64_t l, int64_t max_shell, int64_t* 
 int qs_tdho_coulomb_quadrature(void* out, const void* nm_table, int64_t l, int64_t max_shell, int64_t p_lo,
                                int64_t p_hi, void* workspace, int64_t workspace_bytes, void* stream);
 /*
+ * The same tensor as vectors, without building it (csrc/qs_tdho_quadrature.hip,
+ * DESIGN 3.22): the m-conservation delta splits by the transfer mu = m_s - m_q, so
+ *   u[p,q,r,s] = sum_x L_x[r,p] L_x[q,s],     x = j R + g,  mu_j = j - (m_max - m_min),
+ *   out[x - x_lo][q][s] = fl(sqrt(wt_g)) * F_qs[g]   where m_s - m_q == mu_j,
+ *                         +0.0                        elsewhere,
+ * with R = max_shell, g ascending as in qs_tdho_quadrature_nodes and j = 0 ...
+ * 2 (m_max - m_min): rank = R (2 (m_max - m_min) + 1) vectors, R (4 R - 3) for
+ * full shells.  L_x is real, so M_x = L_x^T = L_x^H in u = sum_x M_x (x) L_x.
+ *   out       : (x_hi - x_lo, l, l) fp64, device, 8-byte aligned
+ *   nm_table, max_shell, workspace: as for qs_tdho_coulomb_quadrature;
+ *               qs_tdho_coulomb_vectors_workspace is the same number of bytes
+ *   x_lo, x_hi: the vectors to write, 0 <= x_lo < x_hi <= rank.  Under a table,
+ *               which lives on the device, x_hi is checked against the most its
+ *               max_shell allows, max_shell (4 max_shell - 3); vectors past the
+ *               table's own rank are all +0.0.
+ * qs_tdho_coulomb_vectors_rank: the rank of a table given as a HOST array of
+ * 2 l int32 (same layout), or of the shell order (NULL); plain host code.  A table
+ * whose m spread exceeds 2 (max_shell - 1) is QS_ERR_BAD_EXTENT.
+ * Limits and the order of the argument errors are those of
+ * qs_tdho_coulomb_quadrature, the slab x_lo:x_hi among the extents.
+ * Promises:
+ *   - the bits of an element depend on neither x_lo / x_hi nor repetition;
+ *   - out[(j, g)][q][s] and out[(N - 1 - j, g)][s][q], N = 2 (m_max - m_min) + 1,
+ *     have identical bits (F[q][s] and F[s][q] are one number);
+ *   - an element outside its band is +0.0, sign bit included;
+ *   - every element of out is stored exactly once (16-byte stores, one 8-byte
+ *     store where a vector starts or ends on an odd double), nothing else is.
+ * Three launches in stream order (index, F, the store kernel; no atomics, 64-bit
+ * offsets); asynchronous.  (Additions: the ABI version stays 4.)
+ */
+int qs_tdho_coulomb_vectors_workspace(int64_t l, int64_t max_shell, int64_t* bytes);
+int qs_tdho_coulomb_vectors_rank(const void* nm_table_host, int64_t l, int64_t max_shell, int64_t* rank);
+int qs_tdho_coulomb_vectors(void* out, const void* nm_table, int64_t l, int64_t max_shell, int64_t x_lo,
+                            int64_t x_hi, void* workspace, int64_t workspace_bytes, void* stream);
+/*
  * Closed-shell perturbative triples: the energy of occupied triples from their
  * blocks (csrc/qs_triples.hip).  Triple x owns six blocks of X, each
  * (v, v, v) row-major of dtype: X_0 ... X_5 = X_ijk, X_ikj, X_jik, X_jki, X_kij,

@@ -152,6 +152,9 @@ SIGNATURES = {
     "qs_tdho_quadrature_nodes": (c_int, [c_i64, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "qs_tdho_coulomb_quadrature_workspace": (c_int, [c_i64, c_i64, ctypes.POINTER(c_i64)]),
     "qs_tdho_coulomb_quadrature": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, c_ptr, c_i64, c_ptr]),
+    "qs_tdho_coulomb_vectors_workspace": (c_int, [c_i64, c_i64, ctypes.POINTER(c_i64)]),
+    "qs_tdho_coulomb_vectors_rank": (c_int, [c_ptr, c_i64, c_i64, ctypes.POINTER(c_i64)]),
+    "qs_tdho_coulomb_vectors": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, c_ptr, c_i64, c_ptr]),
 }
 
 ABI_VERSION = 4

@@ -117,6 +117,21 @@ def _module_of(np):
     return numpy if np is None else np
 
 
+def vectors_only(obj):
+    """True for a basis set (or the system on top of one) that carries its two-body operator as vectors alone:
+    ``u is None`` and ``two_body`` set, as the quantum dots built with ``two_body="vectors"`` do."""
+    bs = getattr(obj, "_basis_set", obj)
+    return getattr(bs, "_u", None) is None and getattr(bs, "two_body", None) is not None
+
+
+def refuse_vectors_only(obj, what):
+    """The one refusal of everything that reads the tensor ``u`` itself."""
+    if vectors_only(obj):
+        raise NotImplementedError(
+            f'{what} reads the two-body tensor u, and this basis set was built with two_body="vectors": it holds the '
+            "Coulomb vectors (basis_set.two_body) and no u")
+
+
 class _Checked:
     """Attribute whose every axis must equal ``owner.l`` (:87-115, :780-782)."""
 
@@ -184,6 +199,9 @@ class BasisSet:
         self.particle_charge = -1  # electrons
         self._includes_spin = includes_spin
         self._anti_symmetrized_u = anti_symmetrized_u
+        # the two-body operator as vectors (a cholesky.CholeskyTwoBody, always on the device): with u = None it stands in
+        # for u in change_basis, transform_two_body_blocks and the systems' mean fields
+        self.two_body = None
 
     # ------------------------------------------------------------ plain props
     @property
@@ -378,6 +396,8 @@ class BasisSet:
                 "transform_two_body_blocks does not take a sharded u: the block transform is not sharded (gather u, "
                 "or run the sharded transform_two_body_elements and slice)")
         (Ct0, Ct1), (C2, C3) = bras, kets
+        if vectors_only(self):
+            return _deliver(self.two_body.transform_blocks((_stage(Ct0), _stage(Ct1)), (_stage(C2), _stage(C3))), self.np)
         return _deliver(
             kernels.transform_two_body_blocks(_stage(self.u), _stage(Ct0), _stage(Ct1), _stage(C2), _stage(C3)), self.np)
 
@@ -392,6 +412,7 @@ class BasisSet:
         and bra coefficients ``C_tilde`` (l_new, l_old), default ``C^dagger``
         (:413-464).  Rectangular ``C`` changes ``l``."""
         if is_sharded_module(self.np):
+            refuse_vectors_only(self, "the sharded change_basis")
             return sharded_basis.change_basis(self, C, C_tilde)
         # (the host side of a small basis costs more than its kernels: inside, device arrays are handled as plain
         # tensors -- no __torch_function__ round trip per tensor method -- and re-wrapped when they are stored)
@@ -455,6 +476,11 @@ class BasisSet:
         # reference, no view) its storage is reused: the transform runs in place with one spare buffer
         # instead of workspace + result -- 69 GB instead of 103 GB at l = 256.
         for slot in ("_u", "_spin_2_tb"):
+            if slot == "_u" and vectors_only(self):
+                # no u: its vectors take the same C and C~ (rank one-body transforms, O(rank l^3)); real vectors stay
+                # real under real coefficients whatever the dtype of h
+                self.two_body = self.two_body.transform(d_C, None if C_tilde is None else d_Ct)
+                continue
             if slot == "_spin_2_tb" and self._spin_2_tb_recipe_valid():
                 # :379-382 transforms the (2l)^4 tensor; it is sum_i S_i (x) S_i (minus the r <-> s term), so its
                 # transform is the same expression in S'_i = C~ S_i C: three one-body transforms, and the tensor is
@@ -550,6 +576,7 @@ class BasisSet:
         """Anti-symmetrise ``u`` and ``spin_2_tb`` once (:511-528)."""
         if self._anti_symmetrized_u:
             return
+        refuse_vectors_only(self, "anti_symmetrize_two_body_elements")
         if is_sharded(self._u):
             return sharded_basis.anti_symmetrize_two_body_elements(self)
         if self._statics_overridden() or len(self.u.shape) != 4:
@@ -641,6 +668,7 @@ class BasisSet:
         operators are set up in the spinor basis {a, b} and all arrays end up
         complex128.  Returns ``self``; warns and returns ``None`` when the basis
         already carries spin."""
+        refuse_vectors_only(self, "change_to_general_orbital_basis (a GeneralOrbitalSystem)")
         if is_sharded_module(self.np):
             return sharded_basis.change_to_general_orbital_basis(self, a=a, b=b, anti_symmetrize=anti_symmetrize)
         if self._includes_spin:
@@ -749,6 +777,7 @@ class ChangeBasisPlan:
     def __init__(self, basis, C_tilde_given=False):
         from . import _lib
 
+        refuse_vectors_only(basis, "change_basis_plan")
         if not is_device_module(basis.np) or is_sharded_module(basis.np):
             raise NotImplementedError("ChangeBasisPlan: device array module only")
         if basis.spf is not None:

@@ -27,7 +27,7 @@ import math
 import torch
 
 from . import kernels
-from .basis_set import _stage
+from .basis_set import _stage, refuse_vectors_only
 from .sharded_module import is_sharded
 
 
@@ -61,6 +61,7 @@ def decompose(u_or_system, tol, max_rank=None):
     contract and is not checked."""
     u = u_or_system
     if hasattr(u_or_system, "_basis_set"):
+        refuse_vectors_only(u_or_system, "cholesky.decompose")
         if u_or_system._basis_set._anti_symmetrized_u:
             raise ValueError(
                 "the system's u is anti-symmetrised: its matrix G[(r,p),(q,s)] is indefinite and has no Cholesky "
@@ -175,6 +176,30 @@ class CholeskyTwoBody:
                 return torch.zeros(shape, dtype=self.L.dtype, device=self.L.device).permute(0, 2, 1, 3).contiguous()
             A = self._bra()[:, p0:p1, r0:r1].permute(1, 2, 0).reshape(shape[0] * shape[1], self.rank)
             B = self.L[:, q0:q1, s0:s1].reshape(self.rank, shape[2] * shape[3])
+            return kernels.matmul(A, B).reshape(shape).permute(0, 2, 1, 3).contiguous()
+
+    def transform_blocks(self, bras, kets):
+        """``out[pqrs] = Ct0[pa] Ct1[qb] u[abcd] C2[cr] C3[ds]`` with ``bras = (Ct0, Ct1)`` (rows, (M, m)) and ``kets =
+        (C2, C3)`` (columns, (m, M)) -- ``BasisSet.transform_two_body_blocks`` on the vectors: the two stacks of
+        rectangular one-body transforms ``Ct0 M_x C2`` and ``Ct1 L_x C3`` (bra first: the small side of ``<ij|ab>``
+        shrinks the stack), then one product over ``x``, put in the project's index order."""
+        with torch._C.DisableTorchFunctionSubclass():
+            (Ct0, Ct1), (C2, C3) = ((_plain(c) for c in bras), (_plain(c) for c in kets))
+            m, r = self.m, self.rank
+            if not (Ct0.dim() == Ct1.dim() == C2.dim() == C3.dim() == 2
+                    and Ct0.shape[1] == Ct1.shape[1] == C2.shape[0] == C3.shape[0] == m):
+                raise ValueError(f"bras must be (M, {m}) and kets ({m}, M)")
+            dt = kernels.result_dtype(self.L, Ct0, Ct1, C2, C3)
+            shape = (Ct0.shape[0], C2.shape[1], Ct1.shape[0], C3.shape[1])
+            if r == 0:
+                return torch.zeros(shape, dtype=dt, device=self.L.device).permute(0, 2, 1, 3).contiguous()
+
+            def stack(V, Ct, C):
+                half = kernels.matmul(Ct.to(dt), V.to(dt))                                  # (rank, M, m)
+                return kernels.matmul(half.reshape(r * Ct.shape[0], m), C.to(dt))          # (rank M, M')
+
+            A = stack(self._bra(), Ct0, C2).reshape(r, shape[0] * shape[1]).transpose(0, 1).contiguous()
+            B = stack(self.L, Ct1, C3).reshape(r, shape[2] * shape[3])
             return kernels.matmul(A, B).reshape(shape).permute(0, 2, 1, 3).contiguous()
 
     def mean_field(self, D, cj=1.0, ck=0.0):

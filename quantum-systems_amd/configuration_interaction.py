@@ -29,7 +29,7 @@ import math
 import torch
 
 from . import kernels
-from .basis_set import _deliver, _stage
+from .basis_set import _deliver, _stage, refuse_vectors_only
 from .general_orbital_system import GeneralOrbitalSystem
 from .sharded_module import is_sharded
 from .spatial_orbital_system import SpatialOrbitalSystem
@@ -52,6 +52,7 @@ class CIS:
     bit, one read of ``u`` per vector): the baseline of the timing in ``examples/cis_quantum_dot.py``."""
 
     def __init__(self, system, C=None, epsilon=None, batched=True):
+        refuse_vectors_only(system, "CIS")
         if not isinstance(system, (SpatialOrbitalSystem, GeneralOrbitalSystem)):
             raise TypeError("CIS needs a SpatialOrbitalSystem or a GeneralOrbitalSystem")
         n_occ = system.n

@@ -32,7 +32,7 @@ works on, and (T): the triples with their singles term (``kernels.triples_energy
 import torch
 
 from . import kernels
-from .basis_set import _deliver, _stage
+from .basis_set import _deliver, _stage, refuse_vectors_only
 from .general_orbital_system import GeneralOrbitalSystem
 from .sharded_module import is_sharded
 from .spatial_orbital_system import SpatialOrbitalSystem
@@ -63,6 +63,7 @@ class CCD:
     (all of it): the same numbers by another kernel, kept for comparison."""
 
     def __init__(self, system, C=None, epsilon=None, ladder="antisym"):
+        refuse_vectors_only(system, "CCD")
         if not isinstance(system, GeneralOrbitalSystem):
             raise TypeError("CCD needs a GeneralOrbitalSystem with an anti-symmetrised u: "
                             "pass spatial_system.construct_general_orbital_system(anti_symmetrize=True)")
@@ -296,6 +297,7 @@ class RCCD:
     triples correction on the amplitudes (canonical orbitals only)."""
 
     def __init__(self, system, C=None, epsilon=None, ladder="exchange"):
+        refuse_vectors_only(system, type(self).__name__)
         if isinstance(system, GeneralOrbitalSystem):
             raise TypeError("RCCD needs a SpatialOrbitalSystem: for a GeneralOrbitalSystem call coupled_cluster.CCD")
         if not isinstance(system, SpatialOrbitalSystem):

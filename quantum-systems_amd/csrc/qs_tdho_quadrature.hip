@@ -19,6 +19,9 @@
 //             panel F[q][.][.] are gathered through the caches: staged in LDS (46 KB at l = 253) the panel left two
 //             workgroups to a CU and the kernel at 0.65 of this one's rate.
 // The tensor is store-bound: l^4 doubles, of which at most R per row of l are not zero.
+//
+// qs_tdho_coulomb_vectors stops before the l^4: the same index and form launches, then one store kernel
+// writes the factors themselves, u = sum_x L_x^T (x) L_x with R (2 (m_max - m_min) + 1) vectors of l^2 doubles.
 
 #include <math.h>
 
@@ -239,6 +242,53 @@ __global__ __launch_bounds__(TQ_THREADS) void tdho_quad_assemble_kernel(double* 
     }
 }
 
+// Coulomb vectors: u[p,q,r,s] = sum_x M_x[p,r] L_x[q,s] with x = j R + g, mu_j = j - (m_max - m_min),
+//   L_x[q][s] = sqrt(wt_g) F_qs[g]  where m_s - m_q == mu_j,  +0.0 elsewhere;  M_x = L_x^T.
+// Workgroup (chunk, x - x_lo): TV_PAIRS * TQ_THREADS 16-byte stores of the vector's run of l^2 doubles, which starts on
+// an odd double for every other vector of an odd l: one 8-byte store ahead of the pairs there, one behind them where an
+// odd count is left.  Every element is stored exactly once, no atomics; mu and g are uniform over the workgroup.  The
+// span m_max - m_min is read off the group starts of the index (a ballot over the 2R - 1 keys, per wave); F is gathered
+// through the caches: each of its l^2 R numbers is read once over the whole rank.
+static constexpr int TV_PAIRS = 4;
+
+__device__ inline double quad_vector_element(const double* __restrict__ F, const int* __restrict__ m, int l, int R, int g,
+                                             int mu, double sw, int q, int s) {
+    return m[s] - m[q] == mu ? sw * F[((int64_t)q * l + s) * R + g] : 0.0;
+}
+
+__global__ __launch_bounds__(TQ_THREADS) void tdho_quad_vectors_kernel(double* __restrict__ out, const double* __restrict__ F,
+                                                                      const int* __restrict__ index, QuadNodes sw, int l, int R,
+                                                                      int x_lo) {
+    const int tid = threadIdx.x, key = tid & 63;
+    const int* __restrict__ start = index + 2 * l;
+    const unsigned long long filled = __ballot(key <= 2 * R - 2 && start[key + 1] > start[key]);
+    const int span = (63 - __clzll(filled)) - (__ffsll(filled) - 1);          // l >= 1: some key is filled
+    const int x = x_lo + (int)blockIdx.y, j = x / R, g = x - j * R, mu = j - span;
+    const double w = sw.v[g];
+
+    double* __restrict__ dst = out + (int64_t)blockIdx.y * l * l;
+    const int n = l * l;
+    const int head = (int)(((uintptr_t)dst >> 3) & 1);
+    const int pairs = (n - head) >> 1;
+#pragma unroll
+    for (int t = 0; t < TV_PAIRS; ++t) {
+        const int i = ((int)blockIdx.x * TV_PAIRS + t) * TQ_THREADS + tid;
+        if (i >= pairs) break;
+        const int e = head + 2 * i;
+        const int q0 = e / l, s0 = e - q0 * l;
+        const int wrap = s0 + 1 == l ? 1 : 0;
+        const int q1 = q0 + wrap, s1 = wrap ? 0 : s0 + 1;
+        double2 v;
+        v.x = quad_vector_element(F, index, l, R, g, mu, w, q0, s0);
+        v.y = quad_vector_element(F, index, l, R, g, mu, w, q1, s1);
+        *(double2*)(dst + e) = v;
+    }
+    if (blockIdx.x == 0) {
+        if (tid == 0 && head) dst[0] = quad_vector_element(F, index, l, R, g, mu, w, 0, 0);
+        if (tid == 32 && ((n - head) & 1)) dst[n - 1] = quad_vector_element(F, index, l, R, g, mu, w, l - 1, l - 1);
+    }
+}
+
 // shells of the table-less form: the shell of the last orbital
 static int shells_of(int64_t l) {
     int n, m;
@@ -254,6 +304,32 @@ static int64_t quad_workspace_bytes(int64_t l, int64_t R) {
 static int rows_per_chunk(int64_t l) {
     const int64_t rc = TQ_BUF_DOUBLES / l;
     return (int)(rc < 1 ? 1 : (rc > l ? l : rc));
+}
+
+// m_max - m_min of a HOST table (n of every orbital, then m of every orbital), or of the shell order
+static int64_t m_span_of(const int* table, int64_t l) {
+    int lo = 0, hi = 0;
+    for (int64_t p = 0; p < l; ++p) {
+        int n, m;
+        if (table) m = table[l + p]; else quad_shell_nm((int)p, n, m);
+        if (p == 0 || m < lo) lo = m;
+        if (p == 0 || m > hi) hi = m;
+    }
+    return (int64_t)hi - lo;
+}
+
+// the index and the form factors of a table in the workspace: F (l, l, R), then the index
+static int launch_form_factors(void* workspace, const int* table, int L, int R, const QuadNodes& k, hipStream_t s) {
+    double* F = (double*)workspace;
+    int* index = (int*)(F + (int64_t)L * L * R);
+    hipLaunchKernelGGL(tdho_quad_index_kernel, dim3(1), dim3(TQ_THREADS), 0, s, index, table, L, R);
+    if (int rc = launch_status("tdho_quad_index launch")) return rc;
+    note_dispatch("tdho_quad_index_kernel");
+    hipLaunchKernelGGL(tdho_quad_form_kernel, dim3((unsigned)cdiv((int64_t)L * L * R, TQ_THREADS)), dim3(TQ_THREADS), 0, s, F,
+                       table, k, L, R);
+    if (int rc = launch_status("tdho_quad_form launch")) return rc;
+    note_dispatch("tdho_quad_form_kernel");
+    return QS_OK;
 }
 
 }  // namespace qs
@@ -304,13 +380,7 @@ int qs_tdho_coulomb_quadrature(void* out, const void* nm_table, int64_t l, int64
     const int* table = (const int*)nm_table;
     hipStream_t s = (hipStream_t)stream;
 
-    hipLaunchKernelGGL(tdho_quad_index_kernel, dim3(1), dim3(TQ_THREADS), 0, s, index, table, L, R);
-    if (int rc = launch_status("tdho_quad_index launch")) return rc;
-    note_dispatch("tdho_quad_index_kernel");
-    hipLaunchKernelGGL(tdho_quad_form_kernel, dim3((unsigned)cdiv(l * l * R, TQ_THREADS)), dim3(TQ_THREADS), 0, s, F, table, k,
-                       L, R);
-    if (int rc = launch_status("tdho_quad_form launch")) return rc;
-    note_dispatch("tdho_quad_form_kernel");
+    if (int rc = launch_form_factors(workspace, table, L, R, k, s)) return rc;
 
     const int rc_rows = rows_per_chunk(l);
     // at most 16 KB of chunk, 12 KB of F[p] rows and 17 KB of tables: under 64 KB at every extent
@@ -320,6 +390,59 @@ int qs_tdho_coulomb_quadrature(void* out, const void* nm_table, int64_t l, int64
                        (int)p_lo, rc_rows);
     note_dispatch("tdho_quad_assemble_kernel");
     return launch_status("tdho_quad_assemble launch");
+}
+
+int qs_tdho_coulomb_vectors_workspace(int64_t l, int64_t max_shell, int64_t* bytes) {
+    return qs_tdho_coulomb_quadrature_workspace(l, max_shell, bytes);
+}
+
+int qs_tdho_coulomb_vectors_rank(const void* nm_table_host, int64_t l, int64_t max_shell, int64_t* rank) {
+    if (!rank) return QS_ERR_NULL_POINTER;
+    if (l < 1 || l > TQ_MAXL) return QS_ERR_BAD_EXTENT;
+    if (!nm_table_host) {
+        if (l > TQ_MAXR * (TQ_MAXR + 1) / 2) return QS_ERR_BAD_EXTENT;
+        max_shell = shells_of(l);
+    }
+    if (max_shell < 1 || max_shell > TQ_MAXR) return QS_ERR_BAD_EXTENT;
+    if (!aligned(nm_table_host, 4)) return QS_ERR_MISALIGNED;
+    const int64_t span = m_span_of((const int*)nm_table_host, l);
+    if (span > 2 * (max_shell - 1)) return QS_ERR_BAD_EXTENT;                // a table that breaks its max_shell
+    *rank = max_shell * (2 * span + 1);
+    return QS_OK;
+}
+
+int qs_tdho_coulomb_vectors(void* out, const void* nm_table, int64_t l, int64_t max_shell, int64_t x_lo, int64_t x_hi,
+                            void* workspace, int64_t workspace_bytes, void* stream) {
+    dispatch_reset();
+    if (!out || !workspace) return QS_ERR_NULL_POINTER;
+    if (l < 1 || l > TQ_MAXL || x_lo < 0 || x_lo >= x_hi) return QS_ERR_BAD_EXTENT;
+    if (!nm_table) {
+        if (l > TQ_MAXR * (TQ_MAXR + 1) / 2) return QS_ERR_BAD_EXTENT;       // more than 32 shells
+        max_shell = shells_of(l);
+    }
+    if (max_shell < 1 || max_shell > TQ_MAXR) return QS_ERR_BAD_EXTENT;
+    // the rank of the shell order; under a table, which lives on the device, the most its max_shell allows: vectors
+    // past the table's own rank (qs_tdho_coulomb_vectors_rank) are all +0.0
+    const int64_t span = nm_table ? 2 * (max_shell - 1) : m_span_of(nullptr, l);
+    if (x_hi > max_shell * (2 * span + 1)) return QS_ERR_BAD_EXTENT;
+    if (!aligned(out, 8) || !aligned(nm_table, 4) || !aligned(workspace, 16)) return QS_ERR_MISALIGNED;
+    if (workspace_bytes < quad_workspace_bytes(l, max_shell)) return QS_ERR_WORKSPACE;
+
+    const int R = (int)max_shell, L = (int)l;
+    QuadNodes k, sw;
+    quadrature_nodes(R, k.v, sw.v);
+    for (int g = 0; g < R; ++g) sw.v[g] = sqrt(sw.v[g]);
+    for (int g = R; g < TQ_MAXR; ++g) k.v[g] = sw.v[g] = 0.0;
+    const double* F = (const double*)workspace;
+    const int* index = (const int*)(F + l * l * R);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = launch_form_factors(workspace, (const int*)nm_table, L, R, k, s)) return rc;
+
+    const int64_t chunks = cdiv(l * l / 2, (int64_t)TV_PAIRS * TQ_THREADS);
+    hipLaunchKernelGGL(tdho_quad_vectors_kernel, dim3((unsigned)(chunks < 1 ? 1 : chunks), (unsigned)(x_hi - x_lo)),
+                       dim3(TQ_THREADS), 0, s, (double*)out, F, index, sw, L, R, (int)x_lo);
+    note_dispatch("tdho_quad_vectors_kernel");
+    return launch_status("tdho_quad_vectors launch");
 }
 
 }  // extern "C"

@@ -29,7 +29,7 @@ import numpy
 import torch
 
 from . import kernels
-from .basis_set import _deliver, _stage
+from .basis_set import _deliver, _stage, refuse_vectors_only
 from .general_orbital_system import GeneralOrbitalSystem
 from .sharded_module import is_sharded
 from .spatial_orbital_system import SpatialOrbitalSystem
@@ -152,6 +152,7 @@ class DeterminantCI:
     own basis, which must then be orthonormal."""
 
     def __init__(self, system, C=None, dets=None):
+        refuse_vectors_only(system, "DeterminantCI")
         if isinstance(system, SpatialOrbitalSystem):
             raise TypeError("DeterminantCI works on spin orbitals: build the system with "
                             "construct_general_orbital_system() first")

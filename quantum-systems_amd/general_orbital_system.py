@@ -2,6 +2,7 @@
 (reference: quantum_systems/general_orbital_system.py)."""
 
 from . import sharded_basis
+from .basis_set import refuse_vectors_only
 from .sharded_module import is_sharded
 from .system import QuantumSystem
 
@@ -13,6 +14,7 @@ class GeneralOrbitalSystem(QuantumSystem):
     ``anti_symmetrize=False`` (general_orbital_system.py:39-53)."""
 
     def __init__(self, n, basis_set, a=[1, 0], b=[0, 1], anti_symmetrize=True, **kwargs):
+        refuse_vectors_only(basis_set, "GeneralOrbitalSystem")
         if not basis_set.includes_spin:
             basis_set = basis_set.change_to_general_orbital_basis(
                 a=a, b=b, anti_symmetrize=anti_symmetrize

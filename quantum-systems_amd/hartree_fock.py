@@ -15,6 +15,9 @@ one ``qs_mean_field`` launch, one read of ``u`` -- and everything else is O(l^3)
     chol = system.cholesky_two_body(tol)            # RHF on Cholesky vectors of u (cholesky.py): the mean field is a
     hf = HartreeFock(system, two_body=chol)         # few products on about 4 l matrices, u is not read again
 
+A system whose basis set carries vectors and no ``u`` (the quantum dots' ``two_body="vectors"``) needs no
+keyword: ``HartreeFock(system)`` picks ``system._basis_set.two_body`` up and ``scf()`` never touches ``system.u``.
+
 ``system.change_to_hf_basis()`` keeps raising ``NotImplementedError`` as in the reference.
 """
 
@@ -44,6 +47,9 @@ class HartreeFock:
             self.occupation = 1.0
         else:
             raise TypeError("HartreeFock needs a SpatialOrbitalSystem (RHF) or a GeneralOrbitalSystem (GHF)")
+        if two_body is None and isinstance(system, SpatialOrbitalSystem):
+            # a basis set that carries vectors (two_dim_ho's two_body="vectors": no u at all) brings its own
+            two_body = getattr(system._basis_set, "two_body", None)
         if two_body is not None:
             # Cholesky vectors (cholesky.CholeskyTwoBody) of the system's plain u: the mean field is a few products on
             # them and u is never read.  RHF only: the vectors of a spin-expanded, anti-symmetrised tensor do not exist.
@@ -81,10 +87,14 @@ class HartreeFock:
         core-guess determinant's)."""
         system = self.system
         with torch._C.DisableTorchFunctionSubclass():
-            u = system.u if is_sharded(system.u) else _stage(system.u).as_subclass(torch.Tensor)
+            if self.two_body is not None:
+                u = None                                                   # the vectors stand in: u is never touched
+            else:
+                u = system.u if is_sharded(system.u) else _stage(system.u).as_subclass(torch.Tensor)
             h = _stage(system.h).as_subclass(torch.Tensor)
             s = _stage(system.s).as_subclass(torch.Tensor)
-            dt = torch.complex128 if torch.complex128 in (h.dtype, s.dtype, u.dtype) else torch.float64
+            two_body_dtype = self.two_body.L.dtype if u is None else u.dtype
+            dt = torch.complex128 if torch.complex128 in (h.dtype, s.dtype, two_body_dtype) else torch.float64
             h, s = h.to(dt), s.to(dt)
             e_nuc = system.nuclear_repulsion_energy
 

@@ -14,7 +14,7 @@ numerator.  The reduction over the o^2 v^2 block is plain torch: under a thousan
 
 import torch
 
-from .basis_set import _stage
+from .basis_set import _stage, vectors_only
 from .general_orbital_system import GeneralOrbitalSystem
 from .sharded_module import is_sharded
 from .spatial_orbital_system import SpatialOrbitalSystem
@@ -47,7 +47,10 @@ def mp2_energy(system, C=None, epsilon=None):
     with torch._C.DisableTorchFunctionSubclass():
         if C is None:
             o, v = slice(0, n_occ), slice(n_occ, system.l)
-            g = _plain(system.u)[o, o, v, v]
+            if vectors_only(system):
+                g = system._basis_set.two_body.block(o, o, v, v)
+            else:
+                g = _plain(system.u)[o, o, v, v]
             f = _plain(system.construct_fock_matrix(system.h, system.u))
             eps = f.diagonal().real.to(torch.float64) if f.is_complex() else f.diagonal().to(torch.float64)
         else:

@@ -3,7 +3,10 @@
 
 import copy
 
+import torch
+
 from . import sharded_basis
+from .basis_set import refuse_vectors_only, vectors_only
 from .general_orbital_system import GeneralOrbitalSystem
 from .sharded_module import is_sharded
 from .system import QuantumSystem
@@ -37,6 +40,7 @@ class SpatialOrbitalSystem(QuantumSystem):
         # spatial ``u`` -- it reads it and writes the 16x larger spin tensor -- so the copy of ``u`` (34 GB at
         # l = 256, and the one thing that does not fit when ``u`` is sharded over the node) is elided: the
         # copy shares the tensor, everything O(l^2) is copied as upstream.
+        refuse_vectors_only(self, "construct_general_orbital_system")
         bs = self._basis_set
         u = bs._u
         bs._u = None
@@ -56,6 +60,10 @@ class SpatialOrbitalSystem(QuantumSystem):
         o = self.o
         np = self.np
         h = self.h if h is None else h
+        if u is None and vectors_only(self):
+            # no u: E0 = tr((h + W / 2) rho) with the mean field W of the reference determinant's density
+            W = self._reference_mean_field()
+            return 2 * np.trace(h[o, o]) + np.trace(W[o, o]) + self.nuclear_repulsion_energy
         u = self.u if u is None else u
         if is_sharded(u):       # slab-local sums + one all-reduce of a single number
             return sharded_basis.compute_reference_energy(h, u, self.n, False, self.nuclear_repulsion_energy)
@@ -66,11 +74,32 @@ class SpatialOrbitalSystem(QuantumSystem):
             + self.nuclear_repulsion_energy
         )
 
-    def construct_fock_matrix(self, h, u, f=None):
+    def _reference_mean_field(self):
+        """``2 u_piqi - u_piiq`` from the basis set's vectors: their mean field of the reference determinant's density,
+        2 on the occupied diagonal."""
+        from .basis_set import _deliver
+
+        L = self._basis_set.two_body.L
+        rho = torch.zeros((self.l, self.l), dtype=L.dtype, device=L.device)
+        rho.diagonal()[: self.n] = 2.0
+        cj, ck = self._mean_field_weights()
+        return _deliver(self._basis_set.two_body.mean_field(rho, cj=cj, ck=ck), self.np)
+
+    def construct_fock_matrix(self, h, u=None, f=None):
         """Restricted closed-shell Fock matrix
-        f_pq = h_pq + 2 u_piqi - u_piiq (spatial_orbital_system.py:152-190)."""
+        f_pq = h_pq + 2 u_piqi - u_piiq (spatial_orbital_system.py:152-190).  ``u=None``: the basis set's ``u``, or its
+        vectors where it holds no ``u``."""
         np = self.np
         o = self.o
+        if u is None and vectors_only(self):
+            W = self._reference_mean_field()
+            if f is None:
+                return h + W
+            f.fill(0)
+            f += h
+            f += W
+            return f
+        u = self.u if u is None else u
         if is_sharded(u):       # slab-local rows / partial sums + l*l numbers over the node
             return sharded_basis.construct_fock_matrix(h, u, self.n, False, f=f)
         if f is None:

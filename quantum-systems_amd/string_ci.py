@@ -68,7 +68,7 @@ import numpy
 import torch
 
 from . import kernels, response
-from .basis_set import _deliver
+from .basis_set import _deliver, refuse_vectors_only
 from .determinant_ci import M_MAX, _dagger, _plain, block_davidson, full_space, popcounts
 from .general_orbital_system import GeneralOrbitalSystem
 from .sharded_module import is_sharded
@@ -144,6 +144,7 @@ class StringCI:
     vectors with ``c = spin_parity * c^T``: the states of even or of odd spin ``S``."""
 
     def __init__(self, system, C=None, n_up=None, n_down=None, strings_up=None, strings_down=None, spin_parity=None):
+        refuse_vectors_only(system, "StringCI")
         if isinstance(system, GeneralOrbitalSystem):
             raise TypeError("StringCI works on spatial orbitals: a GeneralOrbitalSystem goes to DeterminantCI")
         if not isinstance(system, SpatialOrbitalSystem):

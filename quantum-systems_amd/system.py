@@ -10,6 +10,8 @@ import abc
 import copy
 from collections.abc import Iterable
 
+from .basis_set import refuse_vectors_only, vectors_only
+
 
 class QuantumSystem(metaclass=abc.ABCMeta):
     """``n`` occupied basis functions on top of ``basis_set`` (system.py:20-30)."""
@@ -56,8 +58,10 @@ class QuantumSystem(metaclass=abc.ABCMeta):
         from .basis_set import _deliver, _stage
         from .sharded_module import is_sharded
 
-        u = self.u if u is None else u
         cj, ck = self._mean_field_weights()
+        if u is None and vectors_only(self):
+            return _deliver(self._basis_set.two_body.mean_field(_stage(rho_qp), cj=cj, ck=ck), self.np)
+        u = self.u if u is None else u
         if is_sharded(u):
             return sharded_basis.mean_field(u, rho_qp, cj, ck, self.np)
         return _deliver(kernels.mean_field(_stage(u), _stage(rho_qp), cj=cj, ck=ck), self.np)
@@ -70,6 +74,8 @@ class QuantumSystem(metaclass=abc.ABCMeta):
         from .basis_set import _deliver, _stage
         from .sharded_module import is_sharded
 
+        if u is None:
+            refuse_vectors_only(self, "construct_mean_fields_from_densities")
         u = self.u if u is None else u
         if is_sharded(u):
             raise NotImplementedError("construct_mean_fields_from_densities does not take a sharded u: "
@@ -94,6 +100,8 @@ class QuantumSystem(metaclass=abc.ABCMeta):
         if antisymmetric and not (u is None and getattr(self._basis_set, "_anti_symmetrized_u", False)):
             raise ValueError("antisymmetric=True needs the basis set's own anti-symmetrised u "
                              "(a GeneralOrbitalSystem built with anti_symmetrize=True)")
+        if u is None:
+            refuse_vectors_only(self, "contract_two_body_pairs")
         u = self.u if u is None else u
         if is_sharded(u):
             raise NotImplementedError("contract_two_body_pairs does not take a sharded u: "
@@ -187,6 +195,7 @@ class QuantumSystem(metaclass=abc.ABCMeta):
         return h_0 + sum(op.h_t(current_time) for op in self._time_evolution_operator)
 
     def u_t(self, current_time):
+        refuse_vectors_only(self, "u_t")
         u_0 = self._basis_set.u if self._add_u_0 else self.np.zeros_like(self._basis_set.u)
         if not self.has_two_body_time_evolution_operator:
             return u_0

@@ -144,6 +144,72 @@ def get_coulomb_elements(num_orbitals, p_lo=0, p_hi=None, device=None, nm=None, 
     return out
 
 
+TWO_BODY_FORMS = ("tensor", "vectors")
+
+
+def _orbital_table(num_orbitals, nm):
+    nm = numpy.asarray(nm, dtype=numpy.int32)
+    if nm.shape != (num_orbitals, 2):
+        raise ValueError("nm must list (n, m) for every orbital")
+    return nm
+
+
+def coulomb_vectors_rank(num_orbitals, nm=None):
+    """Number of Coulomb vectors of ``get_coulomb_vectors``: ``shells * (2 (m_max - m_min) + 1)``, which is
+    ``R (4 R - 3)`` for ``R`` full shells (``qs_tdho_coulomb_vectors_rank``; host code, no GPU)."""
+    nm = None if nm is None else _orbital_table(num_orbitals, nm)
+    shells = _quadrature_shells(num_orbitals, nm)
+    table = None if nm is None else numpy.ascontiguousarray(nm.T)
+    rank = ctypes.c_int64(0)
+    _lib.check(_lib.load().qs_tdho_coulomb_vectors_rank(None if table is None else table.ctypes.data, num_orbitals, shells,
+                                                        ctypes.byref(rank)), "qs_tdho_coulomb_vectors_rank")
+    return rank.value
+
+
+def get_coulomb_vectors(num_orbitals, nm=None, device=None, x_lo=0, x_hi=None):
+    """The Coulomb elements of ``get_coulomb_elements(method="quadrature")`` (omega = 1) as vectors, without the
+    tensor: a (x_hi - x_lo, l, l) device tensor ``L`` with
+
+        u[p, q, r, s] = sum_x L[x, r, p] L[x, q, s]
+
+    Vector ``x = j R + g`` is ``sqrt(wt_g) F_qs(k_g)`` on the band ``m_s - m_q = j - (m_max - m_min)`` and +0.0
+    elsewhere; ``R`` shells, ``coulomb_vectors_rank`` vectors in all, rows ``x_lo:x_hi`` of them here."""
+    nm = None if nm is None else _orbital_table(num_orbitals, nm)
+    shells = _quadrature_shells(num_orbitals, nm)       # the limit is a ValueError with or without a GPU
+    rank = coulomb_vectors_rank(num_orbitals, nm)
+    x_hi = rank if x_hi is None else x_hi
+    if not 0 <= x_lo < x_hi <= rank:
+        raise ValueError(f"x_lo:x_hi must be a non-empty range inside 0 ... {rank}, got {x_lo}:{x_hi}")
+    if not torch.cuda.is_available():
+        raise RuntimeError("the Coulomb-vector generator runs on the GPU only")
+    lib = _lib.load()
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    out = torch.empty((x_hi - x_lo, num_orbitals, num_orbitals), dtype=torch.float64, device=device)
+    table = None if nm is None else torch.from_numpy(numpy.ascontiguousarray(nm.T)).to(device)   # n of all, then m of all
+    need = ctypes.c_int64(0)
+    _lib.check(lib.qs_tdho_coulomb_vectors_workspace(num_orbitals, shells, ctypes.byref(need)),
+               "qs_tdho_coulomb_vectors_workspace")
+    work = torch.empty(need.value, dtype=torch.uint8, device=device)
+    _lib.check(
+        lib.qs_tdho_coulomb_vectors(out.data_ptr(), None if table is None else table.data_ptr(), num_orbitals, shells,
+                                    x_lo, x_hi, work.data_ptr(), need.value, torch.cuda.current_stream().cuda_stream),
+        "qs_tdho_coulomb_vectors",
+    )
+    return out
+
+
+def coulomb_vectors(num_orbitals, nm=None, omega=1.0):
+    """The two-body tensor ``sqrt(omega) * get_coulomb_elements(..., method="quadrature")`` as a
+    ``cholesky.CholeskyTwoBody``: ``L = omega**0.25 * get_coulomb_vectors(...)``, ``M = L^H`` implicit, exact
+    (``tol = 0``, ``residual = (0, 0)``, ``converged``)."""
+    from .cholesky import CholeskyTwoBody
+
+    L = get_coulomb_vectors(num_orbitals, nm=nm)
+    if omega != 1:
+        L *= float(omega) ** 0.25
+    return CholeskyTwoBody(L, None, tol=0.0, residual=(0.0, 0.0), converged=True)
+
+
 def get_shell_energy_B(n, m, omega_c=0, omega=1):
     """Fock-Darwin level in a perpendicular field (two_dim_helper.py:271-272)."""
     return omega * (2 * n + abs(m) + 1) - (omega_c * m) / 2
@@ -282,14 +348,22 @@ class TwoDimensionalHarmonicOscillator(BasisSet):
     ``radius x theta`` and the dipole elements (two_dim_ho.py:60-139).  Same
     constructor as the reference, and ``coulomb``: the generator of ``u``,
     ``"closed_form"`` (the reference's sums) or ``"quadrature"`` (exact up to 32
-    shells: ``get_coulomb_elements``)."""
+    shells: ``get_coulomb_elements``), and ``two_body``: ``"tensor"`` builds ``u``;
+    ``"vectors"`` (with ``coulomb="quadrature"``) builds no ``u`` (``u is None``) and
+    sets ``two_body`` to its exact Coulomb vectors (``coulomb_vectors``),
+    on which the mean field, RHF, ``change_basis`` and MP2 run."""
 
     def __init__(self, l, radius_length, num_grid_points, omega=1, mass=1, verbose=False, coulomb="closed_form",
-                 **kwargs):
+                 two_body="tensor", **kwargs):
         super().__init__(l, dim=2, **kwargs)
         if coulomb not in COULOMB_METHODS:
             raise ValueError(f"coulomb must be one of {COULOMB_METHODS}, not {coulomb!r}")
-        self.coulomb = coulomb
+        if two_body not in TWO_BODY_FORMS:
+            raise ValueError(f"two_body must be one of {TWO_BODY_FORMS}, not {two_body!r}")
+        if two_body == "vectors" and coulomb != "quadrature":
+            raise ValueError('two_body="vectors" needs coulomb="quadrature": the vectors are the factors of the quadrature '
+                             f"form, and coulomb={coulomb!r} has none")
+        self.coulomb, self.two_body_form = coulomb, two_body
         self.omega, self.mass, self.verbose = omega, mass, verbose
         self.radius_length, self.num_grid_points = radius_length, num_grid_points
         self.radius = numpy.linspace(0, radius_length, num_grid_points)
@@ -303,9 +377,18 @@ class TwoDimensionalHarmonicOscillator(BasisSet):
         np = self.np
         self._h = convert(self.omega * get_one_body_elements(self.l), np)
         self._s = convert(numpy.eye(self.l), np)
-        self._u = convert(numpy.sqrt(self.omega) * get_coulomb_elements(self.l, method=self.coulomb), np)
+        self._setup_two_body(None)
         self.setup_spf()
         self.construct_position_integrals()
+
+    def _setup_two_body(self, nm):
+        """``u`` from the generator ``coulomb``, or -- ``two_body="vectors"`` -- no ``u`` at all and its Coulomb vectors
+        as ``self.two_body`` (a ``cholesky.CholeskyTwoBody`` on the device, whatever the array module)."""
+        if self.two_body_form == "vectors":
+            self._u = None
+            self.two_body = coulomb_vectors(self.l, nm=nm, omega=self.omega)
+            return
+        self._u = convert(numpy.sqrt(self.omega) * get_coulomb_elements(self.l, nm=nm, method=self.coulomb), self.np)
 
     def setup_spf(self):
         """Orbitals on ``meshgrid(radius, theta)`` (two_dim_ho.py:96-108)."""
@@ -370,7 +453,7 @@ class TwoDimHarmonicOscB(TwoDimensionalHarmonicOscillator):
             numpy.arange(l), numpy.arange(-l - 5, l + 6), omega_c=self.omega_c, omega=self.omega)
         self._h = convert(numpy.diag(self.level_energy[:l]), np)
         self._s = convert(numpy.eye(l), np)
-        self._u = convert(numpy.sqrt(self.omega) * get_coulomb_elements(l, nm=self.level_nm[:l], method=self.coulomb), np)
+        self._setup_two_body(self.level_nm[:l])
         self.setup_spf()
         self.construct_position_integrals()
         self.cast_to_complex()

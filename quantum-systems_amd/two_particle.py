@@ -22,7 +22,7 @@ so a Davidson step reads ``u`` once per group of trial vectors and ``u`` is neve
 import torch
 
 from . import kernels
-from .basis_set import _deliver, _stage
+from .basis_set import _deliver, _stage, refuse_vectors_only
 from .general_orbital_system import GeneralOrbitalSystem
 from .sharded_module import is_sharded
 from .spatial_orbital_system import SpatialOrbitalSystem
@@ -42,6 +42,7 @@ class TwoParticleCI:
     the system's own basis, which must then be orthonormal (``s = 1``)."""
 
     def __init__(self, system, C=None):
+        refuse_vectors_only(system, "TwoParticleCI")
         if not isinstance(system, (SpatialOrbitalSystem, GeneralOrbitalSystem)):
             raise TypeError("TwoParticleCI needs a SpatialOrbitalSystem or a GeneralOrbitalSystem")
         # a SpatialOrbitalSystem counts doubly occupied orbitals (its n is half the particle number)
